@@ -155,6 +155,40 @@ def cpu_baseline(args, scene=None):
     return out
 
 
+DUMP_PARTICLES = 1 << 20      # --dump-outputs: particles kept in all (13 float32 each: 52 MB, under the 64 MB cap)
+DUMP_SEED = 20240607
+
+
+def canonical_sample(states, keep, seed):
+    """One rank's particle state [(xyz, state9, logjp) per model], as mpm_retrieve_state returns it, reduced to a fixed sample.
+    The library returns particles in an order set by atomics (it changes from run to run), so each model's particles are first put
+    in a canonical order - lexicographic by position, ties broken by the remaining fields - and `keep[m]` of them are then taken at
+    indices drawn from a seeded generator.  Runs whose positions agree pick the same particles; where rounding swaps two nearly equal
+    positions, the two files pair different particles and are best compared by matching positions."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for (xyz, st, lj), k in zip(states, keep):
+        o = np.lexsort((xyz[:, 2], xyz[:, 1], xyz[:, 0]))
+        xs = xyz[o]
+        if len(o) > 1 and np.all(xs[1:] == xs[:-1], axis=1).any():       # coincident positions: order those by all fields
+            cols = np.concatenate([xyz, st, lj[:, None]], axis=1)
+            o = np.lexsort(cols.T[::-1])
+        idx = o[np.sort(rng.choice(len(o), size=k, replace=False))] if k < len(o) else o
+        out.append((xyz[idx], st[idx], lj[idx]))
+    return out
+
+
+def write_outputs(path, samples, grid_totals=None):
+    """--dump-outputs: one .npy per array (float32 particle fields per model, float64 grid totals)."""
+    os.makedirs(path, exist_ok=True)
+    for m, (xyz, st, lj) in enumerate(samples):
+        np.save(os.path.join(path, f"model{m}_xyz.npy"), np.ascontiguousarray(xyz, dtype=np.float32))
+        np.save(os.path.join(path, f"model{m}_state9.npy"), np.ascontiguousarray(st, dtype=np.float32))
+        np.save(os.path.join(path, f"model{m}_logjp.npy"), np.ascontiguousarray(lj, dtype=np.float32))
+    if grid_totals is not None:
+        np.save(os.path.join(path, "grid_totals.npy"), np.asarray(grid_totals, dtype=np.float64))
+
+
 def loaded_library_sha16():
     """First 16 hex digits of the sha256 of the engine library this process loads (what tools/stamp.sh writes into every profile)."""
     import hashlib
@@ -240,7 +274,13 @@ def main():
     ap.add_argument("--baseline-timeout", type=float, default=420.0,
                     help="seconds the CPU baseline may take after the GPU measurement is complete; beyond it the record is emitted with "
                          "cpu_baseline.error instead of a value (the finished GPU numbers are never lost to a slow host)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed substeps, write what they computed to DIR/<name>.npy: per model the particles' positions, state "
+                         "and log Jp (a fixed, seeded sample of %d particles in all, in a canonical order) and, on one GPU, the grid's mass and "
+                         "momentum totals" % DUMP_PARTICLES)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # stdout carries exactly one line, the JSON record: libraries that print banners there (gloo's "connected to N peer ranks",
     # RCCL's version block) are sent to stderr for the duration of the run
@@ -362,6 +402,11 @@ def main():
         assert bucketed == n_total, check
         assert diag.lost_particles == 0 and diag.discarded_p2g == 0, check
         assert check["grid_mass_rel_err"] < 1e-4 and np.isfinite(totals).all(), check
+        if args.dump_outputs:
+            stage["at"] = "dump outputs"
+            st = [eng.retrieve_state(m) for m in range(len(sc["models"]))]
+            keep = [min(len(x), DUMP_PARTICLES * len(x) // n_total) for x, _, _ in st]
+            write_outputs(args.dump_outputs, canonical_sample(st, keep, DUMP_SEED), totals)
         flow = None
         done = args.start_step + args.warmup + args.steps
         if args.scene == "sand40m" and args.fraction >= 1.0 and not args.start_step and args.flow_start > done:
@@ -437,6 +482,17 @@ def main():
         dist.all_reduce(tot, op=dist.ReduceOp.SUM)
         check = {"particles_bucketed": int(tot[0].item()), "lost_particles": int(tot[1].item()), "discarded_p2g": int(tot[2].item())}
         assert check["particles_bucketed"] == n_total and check["lost_particles"] == 0 and check["discarded_p2g"] == 0, check
+        if args.dump_outputs:
+            # each rank owns a fixed set of particles for the whole run: rank 0 writes the ranks' samples one after the other
+            stage["at"] = "dump outputs"
+            st = sim.local_state()
+            keep = [min(len(x), DUMP_PARTICLES * len(x) // n_total) for x, _, _ in st]
+            parts = [None] * world if rank == 0 else None
+            dist.gather_object(canonical_sample(st, keep, DUMP_SEED + rank), parts, dst=0)
+            if rank == 0:
+                nm = max(len(p) for p in parts)
+                write_outputs(args.dump_outputs, [tuple(np.concatenate([p[m][f] for p in parts if m < len(p)]) for f in range(3))
+                                                  for m in range(nm)])
         flow = None
         sim.close()
 

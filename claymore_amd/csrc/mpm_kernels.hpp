@@ -972,10 +972,16 @@ __global__ __launch_bounds__(256) void fill_bins_kernel(GridCfg cfg, int nch, fl
 	}
 }
 // rasterize, mgmpm_kernels.cuh:153-219, block by block (round 6): one workgroup per particle block - the particles are bucketed by block when this
-// runs (ids[block][slot], size[block]) - sums the B-spline masses of the block's particles in an LDS image of the 8^3 node cube its stencils reach
-// (nodes 1..6 per axis, like G2P2G's arenas) and writes every touched node back with ONE global atomic per channel; the initial velocity is uniform
-// per model, so the three momentum channels are the mass times v0.  The per-particle version below (27 x 4 global atomics per particle) took 98.6 ms
-// at 40 M particles and 253.7 ms at 100 M - 40 % of a 110-substep profile run; it stays as the fall-back for a particle outside every block.
+// runs (ids[block][slot], size[block]) - sums the B-spline masses of the block's particles in an LDS image of the 8^3 node cube that starts at node
+// 4 * key of the block, and writes every touched node back with ONE global atomic per channel; the initial velocity is uniform per model, so the three
+// momentum channels are the mass times v0.  (A per-particle form with 27 x 4 global atomics per particle took 98.6 ms at 40 M particles and 253.7 ms at
+// 100 M - 40 % of a 110-substep profile run; it is gone: every particle reaches this kernel through a block, mpm_initial_setup rejects the others.)
+// Where a particle's stencil lands in the cube: node N = lround(x / dx), stencil base = N - 1, block key = (N - 2) / 4 (truncating, particle_block_key).
+//  - inside the domain (N >= 2) the block owns the cells N - 2 with (N - 2) / 4 == key, so the base is 1..4 in the cube and the stencil 1..6;
+//  - at the lower face, cells -2 and -1 (N = 0, 1) truncate into block 0 too: their base is -1 and 0.  Node -1 lies outside the domain, and outside
+//    the cube; the oracle's rasterize drops it (its block key -1 >> 2 is out of range, oracle/mpm_oracle.c) and so does the range check below;
+//  - at the upper face the stencil reaches block G (base <= 4, stencil <= 6: inside the cube); table_query finds no block there and the write-back
+//    drops those nodes, as the oracle does.
 __global__ __launch_bounds__(256) void rasterize_blocks_kernel(GridCfg cfg, const float* __restrict__ xyz, const int* __restrict__ ids, const int* __restrict__ size, const int* __restrict__ keys, const int* __restrict__ table, float* grid, float mass, float v0x, float v0y, float v0z) {
 	__shared__ float s_m[512];
 	const int b = blockIdx.x;
@@ -994,13 +1000,16 @@ __global__ __launch_bounds__(256) void rasterize_blocks_kernel(GridCfg cfg, cons
 			base[d]		  = lround_pos(p) - 1;
 			bspline_weight_cells(p - (float) base[d], w[d]);
 		}
-		const int lx = base[0] - 4 * kx, ly = base[1] - 4 * ky, lz = base[2] - 4 * kz;// 1..4: the block owns the cells base - 1
+		const int lx = base[0] - 4 * kx, ly = base[1] - 4 * ky, lz = base[2] - 4 * kz;// 1..4 inside the domain, -1 / 0 for cells -2 / -1 (above)
+		// (node -1 of the lower face: dropped, never written below s_m.  Three compares per node of a kernel that runs once at set-up; a body that
+		//  keeps off the lower faces, like C3's column 12 cells above the floor, never takes the branch - its set-up time is not expected to move)
 #pragma unroll
 		for(int i = 0; i < 3; ++i)
 #pragma unroll
 			for(int j = 0; j < 3; ++j)
 #pragma unroll
-				for(int k = 0; k < 3; ++k) atomicAdd(&s_m[((lx + i) << 6) | ((ly + j) << 3) | (lz + k)], mass * (w[0][i] * w[1][j] * w[2][k]));
+				for(int k = 0; k < 3; ++k)
+					if((unsigned) (lx + i) < 8u && (unsigned) (ly + j) < 8u && (unsigned) (lz + k) < 8u) atomicAdd(&s_m[((lx + i) << 6) | ((ly + j) << 3) | (lz + k)], mass * (w[0][i] * w[1][j] * w[2][k]));
 	}
 	__syncthreads();
 	for(int i = threadIdx.x; i < 512; i += 256) {
@@ -1015,31 +1024,6 @@ __global__ __launch_bounds__(256) void rasterize_blocks_kernel(GridCfg cfg, cons
 		if(v0y != 0.f) unsafeAtomicAdd(g + 128, m * v0y);
 		if(v0z != 0.f) unsafeAtomicAdd(g + 192, m * v0z);
 	}
-}
-// (per particle, global atomics: the reference's form)
-__global__ void rasterize_kernel(GridCfg cfg, size_t n, const float* __restrict__ xyz, const int* __restrict__ table, float* grid, float mass, float v0x, float v0y, float v0z) {
-	const size_t pi = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
-	if(pi >= n) return;
-	int base[3];
-	float w[3][3];
-	for(int d = 0; d < 3; ++d) {
-		const float p = xyz[3 * pi + d] * cfg.dx_inv;
-		base[d]		  = lround_pos(p) - 1;
-		bspline_weight_cells(p - (float) base[d], w[d]);
-	}
-	for(int i = 0; i < 3; ++i)
-		for(int j = 0; j < 3; ++j)
-			for(int k = 0; k < 3; ++k) {
-				const int gx = base[0] + i, gy = base[1] + j, gz = base[2] + k;
-				const int bno = table_query(cfg, table, gx >> 2, gy >> 2, gz >> 2);
-				if(bno < 0) continue;
-				const float wm = mass * (w[0][i] * w[1][j] * w[2][k]);
-				float* g	   = grid + (size_t) bno * 256 + (gx & 3) * 16 + (gy & 3) * 4 + (gz & 3);
-				unsafeAtomicAdd(g, wm);
-				unsafeAtomicAdd(g + 64, wm * v0x);
-				unsafeAtomicAdd(g + 128, wm * v0y);
-				unsafeAtomicAdd(g + 192, wm * v0z);
-			}
 }
 
 // ------------------------------------------------------------------------------------------------------

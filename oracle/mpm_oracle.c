@@ -890,16 +890,19 @@ static void g2p2g_model(mpmo_ctx* c, orc_model* m, float dt, float new_dt, const
 		if(size == 0) continue;
 		int nb[8];
 		for(int lb = 0; lb < 8; ++lb) {
+			/* The +1 neighbours of a block with key G - 1 lie beyond the upper faces: no table entry (part_query -1; the reference indexes its
+			 * grid with -1 there, undefined).  Rule of both engines (mpm_g2p2g.hpp / mpm_g2p2g_pair.hpp): such a block gathers
+			 * zero velocity and receives nothing. */
 			nb[lb]			= part_query(c, cur, blockid[0] + ((lb & 4) ? 1 : 0), blockid[1] + ((lb & 2) ? 1 : 0), blockid[2] + ((lb & 1) ? 1 : 0));
-			const float* gb = grid_block(c->grid[0], nb[lb]);
+			const float* gb = nb[lb] >= 0 ? grid_block(c->grid[0], nb[lb]) : NULL;
 			for(int cx = 0; cx < 4; ++cx)
 				for(int cy = 0; cy < 4; ++cy)
 					for(int cz = 0; cz < 4; ++cz) {
 						const int cell = cx * 16 + cy * 4 + cz;
 						const int ax = cx + ((lb & 4) ? 4 : 0), ay = cy + ((lb & 2) ? 4 : 0), az = cz + ((lb & 1) ? 4 : 0);
-						g2p[0][ax][ay][az] = gb[64 + cell];
-						g2p[1][ax][ay][az] = gb[128 + cell];
-						g2p[2][ax][ay][az] = gb[192 + cell];
+						g2p[0][ax][ay][az] = gb ? gb[64 + cell] : 0.f;
+						g2p[1][ax][ay][az] = gb ? gb[128 + cell] : 0.f;
+						g2p[2][ax][ay][az] = gb ? gb[192 + cell] : 0.f;
 					}
 		}
 		memset(p2g, 0, sizeof(p2g));
@@ -940,6 +943,7 @@ static void g2p2g_model(mpmo_ctx* c, orc_model* m, float dt, float new_dt, const
 		}
 		/* arena -> next grid (:907-936) */
 		for(int lb = 0; lb < 8; ++lb) {
+			if(nb[lb] < 0) continue; /* (beyond an upper face: dropped, above) */
 			float* gb = grid_block(c->grid[1], nb[lb]);
 			for(int ch = 0; ch < 4; ++ch)
 				for(int cx = 0; cx < 4; ++cx)

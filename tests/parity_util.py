@@ -29,6 +29,8 @@ def run_engine(scene, nsteps, dt=None, api=None, adaptive=False, dt_default=None
     out["counts"] = eng.counts()
     out["totals"] = eng.grid_totals()
     out["state"] = [eng.retrieve_state(m) for m in range(len(scene["models"]))]
+    if api is None:             # (the HIP engine's lost / dropped particle counters; the oracle has none - it keeps fewer particles)
+        out["diag"] = eng.diagnostics()
     if collect_grid:
         out["grid"] = eng.dump_grid()
     eng.close()

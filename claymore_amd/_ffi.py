@@ -103,6 +103,7 @@ HIP_ONLY = {
     "sync": (_i, [_vp]),
     "get_capacity": (_i, [_vp, _P(C.c_int64), _P(C.c_int64), _ip]),
     "get_diagnostics": (_i, [_vp, _P(Diagnostics)]),
+    "retrieve_velocity": (_i, [_vp, _i, _vp, _vp, _vp, _P(_sz)]),
     "checkpoint_size": (_i, [_vp, _P(_sz)]),
     "checkpoint_save": (_i, [_vp, _vp, _sz, _P(_sz)]),
     "checkpoint_load": (_i, [_vp, _vp, _sz]),

@@ -15,6 +15,7 @@
 
 #include "../../include/claymore_amd.h"
 #include "mpm_kernels.hpp"
+#include "mpm_readout.hpp"
 
 using namespace mpm;
 #define MPM_STR_(x) #x
@@ -77,6 +78,9 @@ struct mpm_ctx {
 	// grid[0] already holds the velocities of the coming substep (the rebuild's carry-over applied the grid update for this dt):
 	// only inside mpm_run_fixed, never when a call returns
 	bool grid_preupdated = false;
+	// grid[0] holds the mass and momentum of the last P2G (set-up, an unfused carry-over, a checkpoint that says so) - what mpm_retrieve_velocity
+	// reads; a grid update turns the momenta into velocities in place, and a fused carry-over leaves velocities too: false until the next plain rebuild
+	bool grid_momentum = false;
 	float preupdate_dt	 = 0.f;
 	float fuse_dt_once	 = 0.f;// set by a driver that knows the next substep's dt (mpm_group_run_fixed): consumed by the next rebuild
 	// Between two host synchronisations of mpm_run_fixed the block counts below are ESTIMATES (the values of the last
@@ -114,6 +118,7 @@ struct mpm_ctx {
 	int mgsp_world	   = 0;
 	int mgsp_rank	   = -1;// this rank's number in the last fused tagging (-1: none yet)
 	bool halo_tagged   = false;
+	int group_refs	   = 0;// mpm_group handles on this context (grp_common_init / mpm_group_destroy): its grid holds only its own share of the halo nodes
 	int* d_send_ids[32] = {nullptr};
 	int n_halo = 0, n_inner = 0;
 	int send_count[32] = {0};
@@ -580,13 +585,15 @@ int mpm_initial_setup(mpm_ctx* ctx) {
 	if(rc) return rc;
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipStreamSynchronize(s));
-	ctx->ready = true;
+	ctx->ready		   = true;
+	ctx->grid_momentum = true;
 	return MPM_OK;
 }
 
 // grid-update phase, gmpm_simulator.cuh:326-347
 static int launch_grid_update(mpm_ctx* ctx, float dt) {
 	hipStream_t s = ctx->s_compute;
+	ctx->grid_momentum = false;// (from here on grid[0] holds velocities, until a rebuild carries the next P2G over)
 	if(ctx->grid_preupdated) {
 		ctx->grid_preupdated = false;
 		if(dt != ctx->preupdate_dt) return fail(ctx, MPM_ERR_INVALID, "grid was updated for another dt");
@@ -794,6 +801,7 @@ static int launch_rebuild(mpm_ctx* ctx, float fuse_dt = 0.f, bool without_prepar
 	Partition& Pn = ctx->part[n];
 	Partition& Pr = ctx->part[r];
 	const bool fused = fuse_dt > 0.f && !ctx->has_collision;
+	ctx->grid_momentum = !fused;// the carry-over below writes grid[0]: the P2G's mass and momentum, or (fused) the updated velocities
 	int rc			 = launch_clear(ctx, kClearRebuild | (fused ? kClearMaxVel : 0));// un-insert the old keys of Pn (reset_table, hash_table.cuh:110-112), counters, totals
 	if(rc) return rc;
 	RebuildModels rm {};
@@ -1228,6 +1236,40 @@ int mpm_retrieve_state(mpm_ctx* ctx, int model, float* xyz, float* state9, float
 	HIP_TRY(hipMemcpy(xyz, m.d_xyz, sizeof(float) * 3 * got, hipMemcpyDeviceToHost));
 	if(state9) HIP_TRY(hipMemcpy(state9, d_state, sizeof(float) * 9 * got, hipMemcpyDeviceToHost));
 	if(logjp) HIP_TRY(hipMemcpy(logjp, d_lj, sizeof(float) * got, hipMemcpyDeviceToHost));
+	*n = got;
+	if(count > cap) return fail(ctx, MPM_ERR_CAPACITY, "output array too small");
+	return MPM_OK;
+}
+
+// Per-particle velocity and affine matrix gathered from grid[0] (mpm_readout.hpp; an extension, the reference has no velocity output)
+int mpm_retrieve_velocity(mpm_ctx* ctx, int model, float* xyz, float* vel, float* affine9, size_t* n) {
+	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
+	if(model < 0 || model >= (int) ctx->models.size() || !n || !xyz || !vel) return fail(ctx, MPM_ERR_INVALID, "mpm_retrieve_velocity: bad model or NULL output array");
+	if(ctx->group_refs > 0 || ctx->mgsp_rank >= 0 || ctx->halo_tagged)
+		return fail(ctx, MPM_ERR_INVALID, "mpm_retrieve_velocity: the context belongs (or belonged) to a multi-GPU group, whose halo nodes hold only this rank's share of the momentum between two substeps");
+	if(!ctx->grid_momentum)
+		return fail(ctx, MPM_ERR_INVALID, "mpm_retrieve_velocity: the grid holds velocities (mpm_grid_update ran after the last rebuild): call mpm_rebuild_partition (or finish the substep) first");
+	HIP_TRY(hipSetDevice(ctx->device));
+	hipStream_t s = ctx->s_compute;
+	Model& m	  = ctx->models[model];
+	const int r = ctx->rollid, nn = r ^ 1;
+	const size_t cap = std::min(*n, m.n);
+	// (an output call: its staging arrays are allocated here and released on every exit path; positions are staged in m.d_xyz as retrieve does)
+	DevScratch<float> b_vel, b_aff;
+	HIP_TRY(b_vel.alloc(3 * cap));
+	if(affine9) HIP_TRY(b_aff.alloc(9 * cap));
+	HIP_TRY(hipMemsetAsync(ctx->d_counter, 0, sizeof(unsigned long long), s));
+	if(ctx->pbc)
+		retrieve_velocity_kernel<<<ctx->pbc, kReadoutThreads, 0, s>>>(ctx->g, m.nch, ctx->part[r].keys, ctx->part[r].table, ctx->part[nn].table, m.size, m.row_of, m.list[m.list_in], m.binoff[r], m.bins[r], ctx->grid[0], m.d_xyz, b_vel.p,
+																	  b_aff.p, (unsigned long long) cap, ctx->d_counter, m.pair ? 1 : 0);
+	HIP_TRY(hipGetLastError());
+	unsigned long long count = 0;
+	HIP_TRY(hipMemcpyAsync(&count, ctx->d_counter, sizeof(count), hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	const size_t got = std::min<size_t>(count, cap);
+	HIP_TRY(hipMemcpy(xyz, m.d_xyz, sizeof(float) * 3 * got, hipMemcpyDeviceToHost));
+	HIP_TRY(hipMemcpy(vel, b_vel.p, sizeof(float) * 3 * got, hipMemcpyDeviceToHost));
+	if(affine9) HIP_TRY(hipMemcpy(affine9, b_aff.p, sizeof(float) * 9 * got, hipMemcpyDeviceToHost));
 	*n = got;
 	if(count > cap) return fail(ctx, MPM_ERR_CAPACITY, "output array too small");
 	return MPM_OK;

@@ -19,7 +19,8 @@ struct CkptHeader {
 	int32_t pbc, nbc, ebc, prev_count;
 	uint64_t total_bytes;
 	uint64_t param_hash;// FNV-1a over the physical parameters (ckpt_param_hash): a checkpoint only loads into the same physics
-	int32_t prev_pbc, pad0;// particle blocks of the previous numbering: the source-bin offsets that are in use
+	int32_t prev_pbc;// particle blocks of the previous numbering: the source-bin offsets that are in use
+	int32_t grid_velocity;// 1: the grid was saved after a grid update (it holds velocities, not momenta: mpm_retrieve_velocity refuses it); 0 otherwise (formerly padding, always 0)
 	CkptModel models[8];
 };
 constexpr uint64_t kCkptMagic = 0x3754504b434d504dull;
@@ -102,6 +103,7 @@ static int ckpt_header(mpm_ctx* ctx, CkptHeader& h) {
 	h.nbc		  = ctx->nbc;
 	h.ebc		  = ctx->ebc;
 	h.prev_pbc	  = ctx->pbc_prev;
+	h.grid_velocity = ctx->grid_momentum ? 0 : 1;
 	HIP_TRY(hipMemcpy(&h.prev_count, ctx->part[ctx->rollid ^ 1].count, sizeof(int), hipMemcpyDeviceToHost));
 	for(int m = 0; m < h.nmodels; ++m) {
 		const Model& M = ctx->models[m];
@@ -187,7 +189,7 @@ int mpm_checkpoint_load(mpm_ctx* ctx, const void* buf, size_t bytes) {
 			return fail(ctx, MPM_ERR_INVALID, "checkpoint: model " + std::to_string(m) + " differs from the context (material, particle count or list layout)");
 	if(h.param_hash != ckpt_param_hash(ctx)) return fail(ctx, MPM_ERR_INVALID, "checkpoint: configuration or material parameters differ from the context");
 	const long long table_blocks = 1ll << (3 * (ctx->cfg.domain_bits - 2));
-	if(h.pbc < 0 || h.pbc > h.nbc || h.nbc > h.ebc || h.ebc > table_blocks || h.prev_count < 0 || h.prev_count > table_blocks || (h.rollid != 0 && h.rollid != 1) || h.prev_pbc < 0 || h.prev_pbc > h.prev_count)
+	if(h.pbc < 0 || h.pbc > h.nbc || h.nbc > h.ebc || h.ebc > table_blocks || h.prev_count < 0 || h.prev_count > table_blocks || (h.rollid != 0 && h.rollid != 1) || (h.grid_velocity != 0 && h.grid_velocity != 1) || h.prev_pbc < 0 || h.prev_pbc > h.prev_count)
 		return fail(ctx, MPM_ERR_INVALID, "checkpoint: inconsistent block counts");
 	for(int m = 0; m < h.nmodels; ++m) {
 		const CkptModel& cm = h.models[m];
@@ -311,6 +313,7 @@ int mpm_checkpoint_load(mpm_ctx* ctx, const void* buf, size_t bytes) {
 	ctx->grid_preupdated = false;
 	ctx->fuse_dt_once	 = 0.f;
 	ctx->rebuild_cleared = false;
+	ctx->grid_momentum	 = h.grid_velocity == 0;
 	ctx->rollid	   = h.rollid;
 	ctx->pbc	   = h.pbc;
 	ctx->nbc	   = h.nbc;

@@ -526,6 +526,7 @@ int grp_halo_comm_half(mpm_group* g, int gid, bool collect_again = false) {
 }
 
 int grp_common_init(mpm_group* g) {
+	g->ctx->group_refs++;// (undone by mpm_group_destroy, which every failure below leads to)
 	if(const char* e = getenv("MPM_GROUP_DEFER")) g->no_defer = e[0] == '0';
 	if(const char* e = getenv("MPM_GROUP_PAD_TIGHT")) g->tight_pad = e[0] == '1';
 	if(const char* e = getenv("MPM_GROUP_OVERLAP_TAG")) g->overlap_tag = e[0] != '0';
@@ -649,6 +650,7 @@ int mpm_group_create_local(mpm_ctx* const* ctxs, int world, mpm_group** out) {
 void mpm_group_destroy(mpm_group* g) {
 	if(!g) return;
 	if(g->ctx) hipSetDevice(g->ctx->device);
+	if(g->ctx && g->ctx->group_refs > 0) g->ctx->group_refs--;
 	hipDeviceSynchronize();
 	if(getenv("MPM_GROUP_VERBOSE")) fprintf(stderr, "claymore_hip: rank %d of %d: %ld substeps in the group loop, %d key-list re-tags (a list outgrew its padding)\n", g->rank, g->world, (long) g->steps, g->retags);
 	if(g->comm && rccl() && !g->aborted) rccl()->CommDestroy(g->comm);

@@ -138,6 +138,31 @@ class Engine:
         k = n.value
         return xyz[:k], st[:k], lj[:k]
 
+    def retrieve_velocity(self, model=0, affine=False):
+        """Per-particle velocity read out from the grid of the last P2G (mpm_retrieve_velocity, HIP library only): (xyz, v) or, with
+        affine=True, (xyz, v, C) in one particle order.  v_p = sum_i w_ip p_i / m_i over G2P's stencil, before the next grid update
+        (no gravity, walls or collision object); C: (n, 3, 3) with C[p, r, c] = C_rc = D^-1 sum_i w_ip v_ir (x_i - x_p)_c."""
+        n = C.c_size_t(self.models[model]["n"])
+        xyz = np.empty((n.value, 3), dtype=np.float32)
+        vel = np.empty((n.value, 3), dtype=np.float32)
+        aff = np.empty((n.value, 9), dtype=np.float32) if affine else None
+        self._check(self.api.retrieve_velocity(self.ctx, model, xyz.ctypes.data_as(C.c_void_p), vel.ctypes.data_as(C.c_void_p),
+                                               aff.ctypes.data_as(C.c_void_p) if affine else None, C.byref(n)))
+        k = n.value
+        if not affine:
+            return xyz[:k], vel[:k]
+        # the library's column-major 9 floats (index 3 c + r) -> C[p, r, c]
+        return xyz[:k], vel[:k], aff[:k].reshape(k, 3, 3).transpose(0, 2, 1)
+
+    def kinetic_energy(self, model=None):
+        """1/2 sum_p m_p |v_p|^2 in float64 from retrieve_velocity (m_p as model_mass); all models when model is None."""
+        ids = range(len(self.models)) if model is None else [model]
+        e = 0.0
+        for mi in ids:
+            _, v = self.retrieve_velocity(mi)
+            e += 0.5 * self.model_mass(mi) * float(np.sum(v.astype(np.float64) ** 2))
+        return e
+
     def counts(self):
         c = _ffi.Counts()
         self._check(self.api.get_counts(self.ctx, C.byref(c)))

@@ -8,7 +8,9 @@
 // (default 8), simulation.max_ppc, simulation.gravity, simulation.output_dir; model.file may be "sphere" or "box"
 // (analytic shapes on the reference's 8-per-node lattice, offset = min corner, span = extent) besides "*.sdf"
 // (text level set; sampled on the same lattice where phi < 0 - deterministic, unlike the reference's rand()-based
-// Poisson sampling, Library/MnSystem/IO/PoissonDisk/SampleGenerator.h:112-176).
+// Poisson sampling, Library/MnSystem/IO/PoissonDisk/SampleGenerator.h:112-176).  simulation.output_velocity (default false):
+// every frame also carries a 3-float point attribute "v" (mpm_retrieve_velocity; frame 0: the model's initial velocity);
+// without it the frames are byte for byte the position-only ones.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -133,6 +135,7 @@ int main(int argc, char** argv) {
 	const float dt_def	 = num(sim, "default_dt", 1e-4f);// DEFAULT_DT :26
 	const int bits		 = (int) num(sim, "domain_bits", 8);
 	const std::string out_dir = sim.has("output_dir") ? sim["output_dir"].string() : ".";
+	const bool out_vel		  = sim.has("output_velocity") && sim["output_velocity"].type == mj::Value::Bool && sim["output_velocity"].b;
 	std::printf("simulation: gpuid[%d], defaultDt[%g], fps[%d], frames[%d]\n", gpuid, dt_def, fps, frames);
 
 	mpm_config cfg;
@@ -183,7 +186,14 @@ int main(int argc, char** argv) {
 		rc	   = mpm_add_model(ctx, mat, &p, pts.empty() ? nullptr : pts[0].data(), pts.size(), v0, &id);
 		if(rc) die(ctx, rc);
 		std::printf("init %d-th model with %zu particles\n", id, pts.size());
-		pio::write_bgeo(out_dir + "/model_id[" + std::to_string(id) + "]_frame[0].bgeo", pts.empty() ? nullptr : pts[0].data(), pts.size());
+		const std::string frame0 = out_dir + "/model_id[" + std::to_string(id) + "]_frame[0].bgeo";
+		if(out_vel) {
+			std::vector<float> v(3 * pts.size());
+			for(size_t i = 0; i < pts.size(); ++i)
+				for(int d = 0; d < 3; ++d) v[3 * i + d] = v0[d];
+			pio::write_bgeo(frame0, pts.empty() ? nullptr : pts[0].data(), pts.size(), v.data());
+		} else
+			pio::write_bgeo(frame0, pts.empty() ? nullptr : pts[0].data(), pts.size());
 		counts.push_back(pts.size());
 	}
 
@@ -197,7 +207,7 @@ int main(int argc, char** argv) {
 	std::printf("block count on device %d: %d, %d, %d\n", gpuid, c.particle_blocks, c.neighbor_blocks, c.exterior_blocks);
 	float cur_time = 0.f;
 	long steps	   = 0;
-	std::vector<float> buf;
+	std::vector<float> buf, vbuf;
 	pio::AsyncWriter io;
 	const auto wall0 = std::chrono::steady_clock::now();
 	for(int frame = 1; frame <= frames; ++frame) {
@@ -223,11 +233,19 @@ int main(int argc, char** argv) {
 		for(size_t mi = 0; mi < counts.size(); ++mi) {// output_model, :594-634
 			buf.resize(3 * counts[mi]);
 			size_t n = counts[mi];
-			rc		 = mpm_retrieve_positions(ctx, (int) mi, buf.data(), &n);
+			if(out_vel) {
+				vbuf.resize(3 * counts[mi]);
+				rc = mpm_retrieve_velocity(ctx, (int) mi, buf.data(), vbuf.data(), nullptr, &n);
+			} else
+				rc = mpm_retrieve_positions(ctx, (int) mi, buf.data(), &n);
 			if(rc) die(ctx, rc);
 			std::printf("total number of particles %zu\n", n);
 			// IO::insert_job (gmpm_simulator.cuh:626-632): the frame is written by the IO thread while the next frame is computed
-			io.write_bgeo_async(out_dir + "/model_id[" + std::to_string(mi) + "]_frame[" + std::to_string(frame) + "].bgeo", buf, n);
+			const std::string fn = out_dir + "/model_id[" + std::to_string(mi) + "]_frame[" + std::to_string(frame) + "].bgeo";
+			if(out_vel)
+				io.write_bgeo_async(fn, buf, vbuf, n);
+			else
+				io.write_bgeo_async(fn, buf, n);
 		}
 	}
 	io.flush();// IO::flush() at the end of main_loop (gmpm_simulator.cuh:591)

@@ -4,6 +4,9 @@
 // Externals/partio/io/BGEO.cpp:311-407): Houdini classic BGEO, big-endian: magic 'Bgeo', 'V', version 5, nPoints,
 // nPrims 0, nPointGroups 0, nPrimGroups 0, nPointAttrib 0, nVertexAttrib 0, nPrimAttrib 0, nAttrib 0, then per point
 // x y z w(=1) as float32, then the two trailing bytes 0x00 0xff.
+// With a velocity array (gmpm's opt-in simulation.output_velocity) the frame is what partio writes for a second, VECTOR point attribute
+// "v" of 3 floats (BGEO.cpp:345-378): nPointAttrib 1, the attribute's definition behind the header - name as a big-endian 16-bit length and
+// its bytes, 16-bit size 3, 32-bit Houdini type 5 (vector), 3 zero defaults - and per point x y z w vx vy vz.
 #pragma once
 #include <condition_variable>
 #include <deque>
@@ -34,19 +37,32 @@ inline void put_bef(std::vector<unsigned char>& o, float f) {
 	std::memcpy(&u, &f, 4);
 	put_be32(o, u);
 }
-inline bool write_bgeo(const std::string& filename, const float* xyz, size_t n) {
+inline bool write_bgeo(const std::string& filename, const float* xyz, size_t n, const float* vel = nullptr) {
 	std::vector<unsigned char> o;
-	o.reserve(64 + n * 16);
+	o.reserve(64 + n * (vel ? 28 : 16));
 	put_be32(o, ((((('B' << 8) | 'g') << 8) | 'e') << 8) | 'o');
 	o.push_back('V');
 	put_be32(o, 5);
 	put_be32(o, (uint32_t) n);// nPoints
-	for(int k = 0; k < 7; ++k) put_be32(o, 0);// nPrims, nPointGroups, nPrimGroups, nPointAttrib, nVertexAttrib, nPrimAttrib, nAttrib
+	for(int k = 0; k < 3; ++k) put_be32(o, 0);// nPrims, nPointGroups, nPrimGroups
+	put_be32(o, vel ? 1 : 0);				  // nPointAttrib
+	for(int k = 0; k < 3; ++k) put_be32(o, 0);// nVertexAttrib, nPrimAttrib, nAttrib
+	if(vel) {
+		o.push_back(0);// name length 1 (16 bit), "v"
+		o.push_back(1);
+		o.push_back('v');
+		o.push_back(0);// size 3 (16 bit)
+		o.push_back(3);
+		put_be32(o, 5);// vector
+		for(int k = 0; k < 3; ++k) put_be32(o, 0);
+	}
 	for(size_t i = 0; i < n; ++i) {
 		put_bef(o, xyz[3 * i]);
 		put_bef(o, xyz[3 * i + 1]);
 		put_bef(o, xyz[3 * i + 2]);
 		put_bef(o, 1.0f);
+		if(vel)
+			for(int d = 0; d < 3; ++d) put_bef(o, vel[3 * i + d]);
 	}
 	o.push_back(0x00);// "beginExtra" / "endExtra" markers partio appends (BGEO.cpp:424-427)
 	o.push_back(0xff);
@@ -155,6 +171,9 @@ public:
 	}
 	void write_bgeo_async(std::string fn, std::vector<float> xyz, size_t n) {
 		insert_job([fn = std::move(fn), xyz = std::move(xyz), n] { write_bgeo(fn, xyz.data(), n); });
+	}
+	void write_bgeo_async(std::string fn, std::vector<float> xyz, std::vector<float> vel, size_t n) {// with the "v" point attribute
+		insert_job([fn = std::move(fn), xyz = std::move(xyz), vel = std::move(vel), n] { write_bgeo(fn, xyz.data(), n, vel.data()); });
 	}
 	void flush() {// IO::flush: wait until every queued job has been written
 		std::unique_lock<std::mutex> lk(mut_);

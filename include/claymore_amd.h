@@ -166,6 +166,24 @@ int mpm_retrieve_state(mpm_ctx* ctx, int model, float* xyz, float* state9, float
  * mpm_build_info() carries the same fact as "state=b" and the ABI number. */
 enum { MPM_STATE_F = 0, MPM_STATE_B = 1 };
 int mpm_state_kind(void);
+/* Extension (the reference has no velocity output): per-particle velocity of a model, read out from the grid the last call left
+ * behind - the mass m_i and momentum p_i of each node after the last P2G - with the APIC gather of G2P at the particle's position:
+ *   v_i = p_i / m_i for m_i > 0, else 0.  This is the state BEFORE the next grid update: gravity, walls and the collision object
+ *         are not applied;
+ *   vel[3*i..]     v_p = sum_i w_ip v_i over the 27-node quadratic B-spline stencil (base node, weights and tie rule of G2P);
+ *   affine9[9*i..] C_p = D^-1 sum_i w_ip v_i (x_i - x_p)^T, D^-1 = 4 / dx^2, column-major like G2P2G's (affine9[9*i + 3*c + r] = C_rc);
+ *                  may be NULL.
+ * A node outside [0, 4G)^3 or in a block that is not registered holds nothing (v_i = 0); particles of cells -2 / -1 use the wrapped
+ * stencil key of G2P.  xyz, vel and affine9 share one order (unspecified, as for mpm_retrieve_positions);
+ * *n: in = capacity in particles, out = particles written.
+ * Precondition: the grid holds momenta, which is the case after mpm_initial_setup, mpm_rebuild_partition, mpm_substep and mpm_run_fixed and
+ * after loading a checkpoint saved in that state.  mpm_grid_update turns the momenta into velocities in place; between it and the next
+ * mpm_rebuild_partition (mpm_g2p2g included) the readout is refused with MPM_ERR_INVALID.
+ * Errors: MPM_ERR_NOT_READY before mpm_initial_setup; MPM_ERR_INVALID for a bad model, a NULL xyz / vel / n, a grid that holds velocities
+ * (above), or a context that has ever joined an mpm_group or been through the halo tagging - its halo nodes hold only its own share of the
+ * momentum between two substeps, and the refusal is permanent for that context (a group-level readout is not built); MPM_ERR_CAPACITY when
+ * *n is too small (the first *n particles are written).  mpm_last_error says which.  HIP library only. */
+int mpm_retrieve_velocity(mpm_ctx* ctx, int model, float* xyz, float* vel, float* affine9, size_t* n);
 
 int mpm_get_counts(mpm_ctx* ctx, mpm_counts* counts);
 

@@ -104,6 +104,7 @@ HIP_ONLY = {
     "get_capacity": (_i, [_vp, _P(C.c_int64), _P(C.c_int64), _ip]),
     "get_diagnostics": (_i, [_vp, _P(Diagnostics)]),
     "retrieve_velocity": (_i, [_vp, _i, _vp, _vp, _vp, _P(_sz)]),
+    "particle_momentum": (_i, [_vp, _i, _P(C.c_double)]),
     "checkpoint_size": (_i, [_vp, _P(_sz)]),
     "checkpoint_save": (_i, [_vp, _vp, _sz, _P(_sz)]),
     "checkpoint_load": (_i, [_vp, _vp, _sz]),
@@ -120,6 +121,8 @@ HIP_ONLY = {
     "group_compute_dt": (_f, [_vp, _f, _f, _f, _f]),
     "group_main_loop": (_i, [_vp, _i, _i, _f, _vp, _vp, _ip]),
     "group_stats": (_i, [_vp, _ip, _ip, _fp]),
+    "group_retrieve_velocity": (_i, [_vp, _i, _vp, _vp, _vp, _P(_sz)]),
+    "group_particle_momentum": (_i, [_vp, _i, _P(C.c_double)]),
 }
 
 

@@ -118,7 +118,10 @@ struct mpm_ctx {
 	int mgsp_world	   = 0;
 	int mgsp_rank	   = -1;// this rank's number in the last fused tagging (-1: none yet)
 	bool halo_tagged   = false;
-	int group_refs	   = 0;// mpm_group handles on this context (grp_common_init / mpm_group_destroy): its grid holds only its own share of the halo nodes
+	// grid[0] holds the mass and momentum summed over the group's ranks on every node this rank's particles reach: set by a group call
+	// that completed (mpm_group.inc), cleared at the start of every group call and by every phase-level call (phase_call)
+	bool group_summed  = false;
+	int group_refs	   = 0;// mpm_group handles on this context (grp_common_init / mpm_group_destroy): the single-context readouts refuse it
 	int* d_send_ids[32] = {nullptr};
 	int n_halo = 0, n_inner = 0;
 	int send_count[32] = {0};
@@ -177,6 +180,13 @@ static int launch_prepare(mpm_ctx* ctx, int cur, int prev, bool list_is_out, int
 static int fail(mpm_ctx* ctx, int code, const std::string& msg) {
 	ctx->err = msg;
 	return code;
+}
+
+// Every public phase-level entry (a grid update, a G2P2G pass, a rebuild, the halo / MGSP phases, a checkpoint load, the single-context
+// substep drivers) calls this first: from then on a grouped context's grid[0] is no longer known to hold the group's summed momentum,
+// until the next group call that completes (mpm_group_retrieve_velocity).
+static inline void phase_call(mpm_ctx* ctx) {
+	if(ctx) ctx->group_summed = false;
 }
 
 template<typename T>
@@ -442,6 +452,7 @@ static int check_status(mpm_ctx* ctx) {
 
 // initial_setup, gmpm_simulator.cuh:637-781
 int mpm_initial_setup(mpm_ctx* ctx) {
+	phase_call(ctx);
 	if(!ctx || ctx->ready || ctx->models.empty()) return MPM_ERR_INVALID;
 	HIP_TRY(hipSetDevice(ctx->device));
 	GridCfg& g		   = ctx->g;
@@ -611,6 +622,7 @@ static int launch_grid_update(mpm_ctx* ctx, float dt) {
 }
 
 int mpm_grid_update(mpm_ctx* ctx, float dt, float* max_vel_sqr) {
+	phase_call(ctx);
 	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
 	HIP_TRY(hipSetDevice(ctx->device));
 	hipStream_t s = ctx->s_compute;
@@ -741,6 +753,7 @@ static int launch_g2p2g(mpm_ctx* ctx, float dt, float next_dt, hipEvent_t e0, hi
 }
 
 int mpm_g2p2g(mpm_ctx* ctx, float dt, float next_dt) {
+	phase_call(ctx);
 	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
 	HIP_TRY(hipSetDevice(ctx->device));
 	int rc = launch_g2p2g(ctx, dt, next_dt, ctx->ev_g0, ctx->ev_g1);
@@ -955,6 +968,7 @@ static int finish_rebuild(mpm_ctx* ctx, mpm_counts* counts) {
 }
 
 int mpm_rebuild_partition(mpm_ctx* ctx, mpm_counts* counts) {
+	phase_call(ctx);
 	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
 	HIP_TRY(hipSetDevice(ctx->device));
 	hipStream_t s = ctx->s_compute;
@@ -970,6 +984,7 @@ int mpm_rebuild_partition(mpm_ctx* ctx, mpm_counts* counts) {
 }
 
 int mpm_substep(mpm_ctx* ctx, float dt, float step_time, float frame_time, float dt_default, float* next_dt, float* max_vel) {
+	phase_call(ctx);
 	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
 	FlagGuard guard {ctx};
 	ctx->fuse_dt_once = 0.f;// (this path keeps the grid update a kernel of its own: the rebuild below must not apply one)
@@ -1004,6 +1019,7 @@ int mpm_substep(mpm_ctx* ctx, float dt, float step_time, float frame_time, float
 // synchronisation plus a margin (a kernel walks over what is beyond its launch), errors raised in between are sticky flags.
 // The reference synchronises the host six times per substep (gmpm_simulator.cuh:398,:470,:503,:518,:541,:564).
 int mpm_run_fixed(mpm_ctx* ctx, int nsteps, float dt) {
+	phase_call(ctx);
 	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
 	HIP_TRY(hipSetDevice(ctx->device));
 	hipStream_t s = ctx->s_compute;
@@ -1241,14 +1257,9 @@ int mpm_retrieve_state(mpm_ctx* ctx, int model, float* xyz, float* state9, float
 	return MPM_OK;
 }
 
-// Per-particle velocity and affine matrix gathered from grid[0] (mpm_readout.hpp; an extension, the reference has no velocity output)
-int mpm_retrieve_velocity(mpm_ctx* ctx, int model, float* xyz, float* vel, float* affine9, size_t* n) {
-	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
-	if(model < 0 || model >= (int) ctx->models.size() || !n || !xyz || !vel) return fail(ctx, MPM_ERR_INVALID, "mpm_retrieve_velocity: bad model or NULL output array");
-	if(ctx->group_refs > 0 || ctx->mgsp_rank >= 0 || ctx->halo_tagged)
-		return fail(ctx, MPM_ERR_INVALID, "mpm_retrieve_velocity: the context belongs (or belonged) to a multi-GPU group, whose halo nodes hold only this rank's share of the momentum between two substeps");
-	if(!ctx->grid_momentum)
-		return fail(ctx, MPM_ERR_INVALID, "mpm_retrieve_velocity: the grid holds velocities (mpm_grid_update ran after the last rebuild): call mpm_rebuild_partition (or finish the substep) first");
+// Per-particle velocity and affine matrix gathered from grid[0] (mpm_readout.hpp; an extension, the reference has no velocity output).
+// The readout of this context's own grid, without the state checks of its callers (mpm_retrieve_velocity, mpm_group_retrieve_velocity).
+static int readout_velocity(mpm_ctx* ctx, int model, float* xyz, float* vel, float* affine9, size_t* n) {
 	HIP_TRY(hipSetDevice(ctx->device));
 	hipStream_t s = ctx->s_compute;
 	Model& m	  = ctx->models[model];
@@ -1273,6 +1284,50 @@ int mpm_retrieve_velocity(mpm_ctx* ctx, int model, float* xyz, float* vel, float
 	*n = got;
 	if(count > cap) return fail(ctx, MPM_ERR_CAPACITY, "output array too small");
 	return MPM_OK;
+}
+
+// {count, sum m v_p (3), sum 1/2 m |v_p|^2} of one model (model >= 0) or of all models (-1), from this context's own grid[0]:
+// particle_momentum_kernel, one launch per model into one float64 accumulator.
+static int readout_momentum(mpm_ctx* ctx, int model, double out[5]) {
+	HIP_TRY(hipSetDevice(ctx->device));
+	hipStream_t s = ctx->s_compute;
+	const int r = ctx->rollid, nn = r ^ 1;
+	DevScratch<double> d_out;
+	HIP_TRY(d_out.alloc(kMomentumSums));
+	HIP_TRY(hipMemsetAsync(d_out.p, 0, sizeof(double) * kMomentumSums, s));
+	for(int mi = model < 0 ? 0 : model; mi < (model < 0 ? (int) ctx->models.size() : model + 1); ++mi) {
+		Model& m = ctx->models[mi];
+		if(ctx->pbc && m.n)
+			particle_momentum_kernel<<<ctx->pbc, kReadoutThreads, 0, s>>>(ctx->g, m.nch, ctx->part[r].keys, ctx->part[r].table, ctx->part[nn].table, m.size, m.row_of, m.list[m.list_in], m.binoff[r], m.bins[r], ctx->grid[0],
+																		  (double) m.mc.mass, d_out.p, m.pair ? 1 : 0);
+		HIP_TRY(hipGetLastError());
+	}
+	HIP_TRY(hipMemcpyAsync(out, d_out.p, sizeof(double) * kMomentumSums, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	return MPM_OK;
+}
+
+// The state checks of the single-context readouts: NOT_READY, then INVALID for a context of a group and for a grid that holds velocities.
+static int readout_state(mpm_ctx* ctx, const char* who) {
+	if(ctx->group_refs > 0 || ctx->mgsp_rank >= 0 || ctx->halo_tagged)
+		return fail(ctx, MPM_ERR_INVALID, std::string(who) + ": the context belongs (or belonged) to a multi-GPU group; read it out through the group (mpm_group_retrieve_velocity, mpm_group_particle_momentum), which knows whether its grid holds the summed momentum");
+	if(!ctx->grid_momentum)
+		return fail(ctx, MPM_ERR_INVALID, std::string(who) + ": the grid holds velocities (mpm_grid_update ran after the last rebuild): call mpm_rebuild_partition (or finish the substep) first");
+	return MPM_OK;
+}
+
+int mpm_retrieve_velocity(mpm_ctx* ctx, int model, float* xyz, float* vel, float* affine9, size_t* n) {
+	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
+	if(model < 0 || model >= (int) ctx->models.size() || !n || !xyz || !vel) return fail(ctx, MPM_ERR_INVALID, "mpm_retrieve_velocity: bad model or NULL output array");
+	if(int rc = readout_state(ctx, "mpm_retrieve_velocity")) return rc;
+	return readout_velocity(ctx, model, xyz, vel, affine9, n);
+}
+
+int mpm_particle_momentum(mpm_ctx* ctx, int model, double out[5]) {
+	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
+	if(model < -1 || model >= (int) ctx->models.size() || !out) return fail(ctx, MPM_ERR_INVALID, "mpm_particle_momentum: bad model or NULL output array");
+	if(int rc = readout_state(ctx, "mpm_particle_momentum")) return rc;
+	return readout_momentum(ctx, model, out);
 }
 
 int mpm_retrieve_positions(mpm_ctx* ctx, int model, float* xyz, size_t* n) {

@@ -178,6 +178,7 @@ int mpm_checkpoint_save(mpm_ctx* ctx, void* buf, size_t capacity, size_t* writte
 }
 
 int mpm_checkpoint_load(mpm_ctx* ctx, const void* buf, size_t bytes) {
+	phase_call(ctx);
 	if(!ctx || !ctx->ready || !buf) return MPM_ERR_NOT_READY;
 	if(bytes < sizeof(CkptHeader)) return fail(ctx, MPM_ERR_INVALID, "checkpoint: truncated header");
 	CkptHeader h;

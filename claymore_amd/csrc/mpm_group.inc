@@ -686,12 +686,14 @@ const char* mpm_group_last_error(const mpm_group* g) {
 // MgspBenchmark::initial_setup (mgsp_benchmark.cuh:561-659): per-rank setup, first tagging, initial rasterised grids summed once
 int mpm_group_initial_setup(mpm_group* g) {
 	if(!g || !g->ctx) return MPM_ERR_INVALID;
+	g->ctx->group_summed = false;
 	GRP_TRY(mpm_initial_setup(g->ctx));
 	int rc = grp_tag(g);
 	if(rc) return rc;
 	rc = grp_exchange_halo(g, 0, false, 0.f, 0.f);
 	if(rc) return rc;
 	GRP_TRY(mpm_sync(g->ctx));
+	g->ctx->group_summed = true;
 	return MPM_OK;
 }
 
@@ -701,15 +703,18 @@ int mpm_group_initial_setup(mpm_group* g) {
 // the halo / interior lists and the per-peer send lists (grp_tag: all-gather of the block keys + tagging).
 int mpm_group_resume(mpm_group* g) {
 	if(!g || !g->ctx) return MPM_ERR_INVALID;
+	g->ctx->group_summed = false;
 	if(g->aborted) return gfail(g, MPM_ERR_DEVICE, "the RCCL communicator was aborted after an error");
 	mpm_ctx* ctx = g->ctx;
 	if(!ctx->ready) return gfail(g, MPM_ERR_NOT_READY, "mpm_group_resume: the context holds no state (initial set-up or mpm_checkpoint_load first)");
+	ctx->group_summed = false;
 	GRP_TRY(mpm_sync(ctx));
 	ctx->halo_tagged = false;
 	g->pad			 = 0;// (agreed on again from the ranks' block counts)
 	int rc			 = grp_tag(g);
 	if(rc) return rc;
 	GRP_TRY(mpm_sync(ctx));
+	ctx->group_summed = true;// (the checkpoint's grid is the sum: see above)
 	return MPM_OK;
 }
 
@@ -799,6 +804,7 @@ int grp_substep_wait(mpm_group* g, int par, float* max_vel_sqr, bool* truncated)
 
 int mpm_group_substep(mpm_group* g, float dt, float next_dt, float* max_vel_sqr) {
 	if(!g || !g->ctx) return MPM_ERR_INVALID;
+	g->ctx->group_summed = false;
 	int rc = grp_substep_begin(g, dt, next_dt, false, -1);
 	if(rc) return rc;
 	rc = grp_substep_enqueue(g, dt, next_dt, -1);
@@ -808,8 +814,9 @@ int mpm_group_substep(mpm_group* g, float dt, float next_dt, float* max_vel_sqr)
 	if(rc) return rc;
 	if(truncated) {// a key list was truncated (same verdict on every rank): tag again with the larger padding
 		g->retags++;
-		return grp_tag(g);
+		if((rc = grp_tag(g))) return rc;
 	}
+	g->ctx->group_summed = true;
 	return MPM_OK;
 }
 
@@ -820,7 +827,8 @@ int mpm_group_substep(mpm_group* g, float dt, float next_dt, float* max_vel_sqr)
 // the key all-gather carries its status word): all return the error, nobody is left waiting in a collective.
 int mpm_group_run_fixed(mpm_group* g, int nsteps, float dt) {
 	if(!g || !g->ctx) return MPM_ERR_INVALID;
-	mpm_ctx* ctx = g->ctx;
+	mpm_ctx* ctx	  = g->ctx;
+	ctx->group_summed = false;
 	bool pending = false;// the read-back of the previous substep is outstanding
 	bool retagged = false;// the wait half had to repeat the last tagging (a key list outgrew its padding)
 	auto bail = [&](int rc) {// an interrupted run leaves no promise about the grid behind
@@ -875,7 +883,8 @@ int mpm_group_run_fixed(mpm_group* g, int nsteps, float dt) {
 		pending = true;
 		if((!defer || i + 1 == nsteps) && (rc = finish(par, true))) return bail(rc);
 	}
-	ctx->lean_events = false;
+	ctx->lean_events  = false;
+	ctx->group_summed = true;// (the last carry-over is not fused: grid[0] holds the summed momentum)
 	return MPM_OK;
 }
 
@@ -903,6 +912,7 @@ float mpm_group_compute_dt(const mpm_group* g, float max_vel, float cur, float n
 int mpm_group_main_loop(mpm_group* g, int frames, int fps, float dt_default, void (*on_frame)(int frame, void* user), void* user, int* steps_out) {
 	if(!g || !g->ctx || frames < 0 || fps < 1) return MPM_ERR_INVALID;
 	mpm_ctx* ctx			= g->ctx;
+	ctx->group_summed		= false;
 	const float seconds_pf	= 1.f / (float) fps;
 	float next_dt			= mpm_group_compute_dt(g, 0.f, 0.f, seconds_pf, dt_default);
 	int steps				= 0;
@@ -931,9 +941,81 @@ int mpm_group_main_loop(mpm_group* g, int frames, int fps, float dt_default, voi
 			steps++;
 			cur_time += dt;
 		}
+		ctx->group_summed = true;// (an unfused rebuild behind the summing exchange: the group readout may run inside on_frame)
 		if(on_frame) on_frame(frame, user);
 	}
 	if(steps_out) *steps_out = steps;
+	return MPM_OK;
+}
+
+// ---- readout of a group (an extension: mpm_readout.hpp) ----------------------------------------------------------------
+// At the return of a group call that completed, and inside mpm_group_main_loop's on_frame, every rank's grid[0] holds the mass and
+// momentum summed over the ranks on every node its own particles reach: the halo exchange reduces the peers' shares of each shared block
+// into grid[1] before the rebuild's carry-over copies it into grid[0] (and the set-up exchange sums the rasterised grids in grid[0]).
+// So the single-context readout, run on each rank's own grid, reads the group's velocity field; tests/test_group_velocity_gpu.py
+// checks the premise node by node against a single context.
+// A readout error leaves the group as it is (gfail would break an in-process group's rendez-vous for good): it is only reported.
+static int grp_readout_fail(mpm_group* g, int code, const std::string& msg) {
+	g->err = g->ctx->err = msg;
+	return code;
+}
+static int grp_readout_state(mpm_group* g, const char* who) {
+	mpm_ctx* ctx = g->ctx;
+	if(!ctx->ready) return grp_readout_fail(g, MPM_ERR_NOT_READY, std::string(who) + ": the context holds no state (mpm_group_initial_setup first)");
+	if(!ctx->group_summed)
+		return grp_readout_fail(g, MPM_ERR_INVALID, std::string(who) + ": the grid does not hold the group's summed momentum - a group call failed, or a phase-level call ran on the context since the last group call completed");
+	if(!ctx->grid_momentum) return grp_readout_fail(g, MPM_ERR_INVALID, std::string(who) + ": the grid holds velocities");
+	return MPM_OK;
+}
+
+int mpm_group_retrieve_velocity(mpm_group* g, int model, float* xyz, float* vel, float* affine9, size_t* n) {
+	if(!g || !g->ctx) return MPM_ERR_INVALID;
+	mpm_ctx* ctx = g->ctx;
+	if(int rc = grp_readout_state(g, "mpm_group_retrieve_velocity")) return rc;
+	if(model < 0 || model >= (int) ctx->models.size() || !n || !xyz || !vel) return grp_readout_fail(g, MPM_ERR_INVALID, "mpm_group_retrieve_velocity: bad model or NULL output array");
+	if(int rc = readout_velocity(ctx, model, xyz, vel, affine9, n)) return grp_readout_fail(g, rc, ctx->err);
+	return MPM_OK;
+}
+
+// Collective: every rank contributes its status and its five float64 sums to one all-gather (12 ints per rank: status, 0, the sums as
+// 10 ints) - grp_all_gather, the one collective every transport has - and each rank adds the sums on the host in rank order, so all
+// ranks return the same bits.  A rank that cannot read out still takes part: its status fails the call on every rank.
+int mpm_group_particle_momentum(mpm_group* g, int model, double out[5]) {
+	if(!g || !g->ctx) return MPM_ERR_INVALID;
+	mpm_ctx* ctx = g->ctx;
+	constexpr int kRow = 2 + 2 * kMomentumSums;
+	int row[kRow] = {};
+	double mine[kMomentumSums] = {};
+	int rc = grp_readout_state(g, "mpm_group_particle_momentum");
+	if(!rc && (model < -1 || model >= (int) ctx->models.size() || !out)) rc = grp_readout_fail(g, MPM_ERR_INVALID, "mpm_group_particle_momentum: bad model or NULL output array");
+	if(!rc && (rc = readout_momentum(ctx, model, mine))) grp_readout_fail(g, rc, ctx->err);
+	const std::string mine_err = g->err;
+	row[0] = rc;
+	memcpy(row + 2, mine, sizeof(mine));
+	GRP_HIP(hipSetDevice(ctx->device));
+	hipStream_t s = ctx->s_compute;
+	DevScratch<int> d_row, d_all;
+	GRP_HIP(d_row.alloc(kRow));
+	GRP_HIP(d_all.alloc((size_t) kRow * g->world));
+	GRP_HIP(hipMemcpyAsync(d_row.p, row, sizeof(row), hipMemcpyHostToDevice, s));
+	const int grc = grp_all_gather(g, d_row.p, d_all.p, kRow, s);
+	if(grc) return rc ? grp_readout_fail(g, rc, mine_err) : grc;// (a group that a failed call left broken: this rank's own reason first)
+	std::vector<int> all((size_t) kRow * g->world);
+	GRP_HIP(hipMemcpyAsync(all.data(), d_all.p, sizeof(int) * all.size(), hipMemcpyDeviceToHost, s));
+	GRP_HIP(hipStreamSynchronize(s));
+	if(g->hub && g->hub->have_kdone)// (asynchronous in-process gather: a peer may still be copying d_row, which goes out of scope here)
+		for(int p = 0; p < g->world; ++p)
+			if(p != g->rank && g->hub->ev_kdone[p]) GRP_HIP(hipEventSynchronize(g->hub->ev_kdone[p]));
+	if(rc) return grp_readout_fail(g, rc, mine_err);
+	double sum[kMomentumSums] = {};
+	for(int p = 0; p < g->world; ++p) {
+		const int* r = all.data() + (size_t) kRow * p;
+		if(r[0]) return grp_readout_fail(g, r[0], "mpm_group_particle_momentum: rank " + std::to_string(p) + " could not read out its particles");
+		double d[kMomentumSums];
+		memcpy(d, r + 2, sizeof(d));
+		for(int k = 0; k < kMomentumSums; ++k) sum[k] += d[k];
+	}
+	for(int k = 0; k < kMomentumSums; ++k) out[k] = sum[k];
 	return MPM_OK;
 }
 

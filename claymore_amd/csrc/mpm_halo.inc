@@ -209,6 +209,7 @@ static int halo_alloc(mpm_ctx* ctx) {
 extern "C" {
 
 int mpm_halo_keys(mpm_ctx* ctx, int* dev_keys, int capacity_blocks, int* count) {
+	phase_call(ctx);
 	if(!ctx || !ctx->ready || !dev_keys) return MPM_ERR_NOT_READY;
 	HIP_TRY(hipSetDevice(ctx->device));
 	const int ncopy = std::min(ctx->nbc, capacity_blocks);// *count reports the true number; the caller retries if truncated
@@ -218,6 +219,7 @@ int mpm_halo_keys(mpm_ctx* ctx, int* dev_keys, int capacity_blocks, int* count) 
 }
 
 int mpm_halo_tag_begin(mpm_ctx* ctx) {
+	phase_call(ctx);
 	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
 	HIP_TRY(hipSetDevice(ctx->device));
 	int rc = halo_alloc(ctx);
@@ -229,6 +231,7 @@ int mpm_halo_tag_begin(mpm_ctx* ctx) {
 }
 
 int mpm_halo_tag_peer(mpm_ctx* ctx, int peer, const int* dev_peer_keys, int npeer_keys) {
+	phase_call(ctx);
 	if(!ctx || !ctx->ready || !ctx->d_overlap || peer < 0 || peer >= 32) return MPM_ERR_INVALID;
 	HIP_TRY(hipSetDevice(ctx->device));
 	if(!ctx->d_send_ids[peer]) HIP_TRY(dalloc(&ctx->d_send_ids[peer], (size_t) ctx->g.cap + 1));
@@ -238,6 +241,7 @@ int mpm_halo_tag_peer(mpm_ctx* ctx, int peer, const int* dev_peer_keys, int npee
 }
 
 int mpm_halo_tag_end(mpm_ctx* ctx, int* halo_particle_blocks, int* send_counts) {
+	phase_call(ctx);
 	if(!ctx || !ctx->ready || !ctx->d_overlap) return MPM_ERR_INVALID;
 	HIP_TRY(hipSetDevice(ctx->device));
 	hipStream_t s = ctx->s_compute;
@@ -280,6 +284,7 @@ static int g2p2g_halo(mpm_ctx* ctx, float dt, float next_dt, bool fused_clear, b
 	return MPM_OK;
 }
 int mpm_g2p2g_halo(mpm_ctx* ctx, float dt, float next_dt) {
+	phase_call(ctx);
 	return g2p2g_halo(ctx, dt, next_dt, false);
 }
 
@@ -301,6 +306,7 @@ static int g2p2g_interior(mpm_ctx* ctx, float dt, float next_dt, hipEvent_t ev_g
 	return MPM_OK;
 }
 int mpm_g2p2g_interior(mpm_ctx* ctx, float dt, float next_dt) {
+	phase_call(ctx);
 	return g2p2g_interior(ctx, dt, next_dt, nullptr);
 }
 
@@ -327,10 +333,12 @@ static int halo_collect_all_on(mpm_ctx* ctx, hipStream_t s, int gid, float* dev_
 	return MPM_OK;
 }
 int mpm_halo_collect(mpm_ctx* ctx, int peer, int gid, int* dev_keys, float* dev_blocks, int capacity_blocks, int* nsend) {
+	phase_call(ctx);
 	return halo_collect_on(ctx, ctx ? ctx->s_comm : nullptr, peer, gid, dev_keys, dev_blocks, capacity_blocks, nsend);
 }
 
 int mpm_halo_reduce(mpm_ctx* ctx, int gid, const int* dev_keys, const float* dev_blocks, int nrecv) {
+	phase_call(ctx);
 	if(!ctx || !ctx->ready || gid < 0 || gid > 1) return MPM_ERR_INVALID;
 	HIP_TRY(hipSetDevice(ctx->device));
 	if(nrecv > 0) halo_reduce_kernel<<<cdiv(nrecv, 4), 256, 0, ctx->s_comm>>>(ctx->g, nrecv, dev_keys, dev_blocks, ctx->part[ctx->rollid].table, ctx->nbc, ctx->grid[gid]);
@@ -352,6 +360,7 @@ static int mgsp_begin(mpm_ctx* ctx, float dt, float next_dt, bool device_sized, 
 	return g2p2g_halo(ctx, dt, next_dt, true, device_sized, ev_g0);
 }
 int mpm_mgsp_begin(mpm_ctx* ctx, float dt, float next_dt) {
+	phase_call(ctx);
 	return mgsp_begin(ctx, dt, next_dt, false, nullptr, nullptr);
 }
 
@@ -374,6 +383,7 @@ static int mgsp_rebuild_export(mpm_ctx* ctx, int* dev_keys, int pad_rows, bool w
 }
 
 int mpm_mgsp_rebuild_export(mpm_ctx* ctx, int* dev_keys, int pad_rows) {
+	phase_call(ctx);
 	return mgsp_rebuild_export(ctx, dev_keys, pad_rows, false);
 }
 
@@ -404,6 +414,7 @@ static int mgsp_tag(mpm_ctx* ctx, const int* dev_all_keys, int pad_rows, int wor
 	return MPM_OK;
 }
 int mpm_mgsp_tag(mpm_ctx* ctx, const int* dev_all_keys, int pad_rows, int world, int rank) {
+	phase_call(ctx);
 	return mgsp_tag(ctx, dev_all_keys, pad_rows, world, rank, nullptr);
 }
 
@@ -466,6 +477,7 @@ static int mgsp_end_wait(mpm_ctx* ctx, int rank, int* send_counts, int* halo_par
 	return MPM_OK;
 }
 int mpm_mgsp_end(mpm_ctx* ctx, int* send_counts, int* halo_particle_blocks, int* max_peer_rows, float* max_vel_sqr) {
+	phase_call(ctx);
 	int rc = mgsp_end_enqueue(ctx);
 	if(rc) return rc;
 	return mgsp_end_wait(ctx, ctx->mgsp_rank, send_counts, halo_particle_blocks, max_peer_rows, max_vel_sqr, nullptr, nullptr, nullptr, nullptr);

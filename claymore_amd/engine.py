@@ -15,6 +15,11 @@ class EngineError(RuntimeError):
         self.code = code
 
 
+def momentum_dict(out):
+    """The five doubles of mpm_particle_momentum / mpm_group_particle_momentum as a dict."""
+    return {"count": int(out[0]), "momentum": np.array(out[1:4], dtype=np.float64), "kinetic": float(out[4])}
+
+
 class Engine:
     """One simulation context on one device.
 
@@ -162,6 +167,13 @@ class Engine:
             _, v = self.retrieve_velocity(mi)
             e += 0.5 * self.model_mass(mi) * float(np.sum(v.astype(np.float64) ** 2))
         return e
+
+    def particle_momentum(self, model=None):
+        """Totals of the velocity readout, summed on the device in float64 (mpm_particle_momentum, HIP library only): {"count", "momentum":
+        sum_p m_p v_p (3,), "kinetic": sum_p 1/2 m_p |v_p|^2}; all models when model is None."""
+        out = (C.c_double * 5)()
+        self._check(self.api.particle_momentum(self.ctx, -1 if model is None else int(model), out))
+        return momentum_dict(out)
 
     def counts(self):
         c = _ffi.Counts()

@@ -11,10 +11,12 @@
 // --transport peer|rccl or MPM_GROUP_TRANSPORT selects.
 //
 //   mgsp [--devices N] [--scenario 2|3] [--bits B] [--frames F] [--fps R] [--same-device] [--transport peer|rccl] [--out DIR]
-//        [--boundary PREFIX [--boundary-type sticky|slip|separate] [--friction MU]]
+//        [--boundary PREFIX [--boundary-type sticky|slip|separate] [--friction MU]] [--output-velocity]
 // --boundary reads PREFIX_sdf.bin, PREFIX_grad_{0,1,2}.bin (N^3 floats each) like MgspBenchmark::init_boundary
 // (mgsp_benchmark.cuh:257-266, boundary_condition.cuh:292-321) and installs the collision object on every device.
 // --same-device puts every context on GPU 0 (functional testing on a single GPU).
+// --output-velocity: every frame also carries the 3-float point attribute "v" (an extension, as gmpm's simulation.output_velocity):
+// frame 0 the model's initial velocity, later frames the group readout of each rank's particles (mpm_group_retrieve_velocity).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -55,7 +57,7 @@ static void check(Dev& d, int rc) {
 
 int main(int argc, char** argv) {
 	int ndev = 2, scenario = 2, bits = 8, frames = 2, fps = 48;
-	bool same = false;
+	bool same = false, out_vel = false;
 	std::string out = ".", boundary, boundary_type = "sticky";
 	std::string transport = std::getenv("MPM_GROUP_TRANSPORT") ? std::getenv("MPM_GROUP_TRANSPORT") : "peer";
 	float friction = 0.3f;
@@ -72,6 +74,7 @@ int main(int argc, char** argv) {
 		else if(is("--boundary-type")) boundary_type = argv[++i];
 		else if(is("--friction")) friction = (float) std::atof(argv[++i]);
 		else if(!std::strcmp(argv[i], "--same-device")) same = true;
+		else if(!std::strcmp(argv[i], "--output-velocity")) out_vel = true;
 	}
 	if(transport != "peer" && transport != "rccl") {
 		std::fprintf(stderr, "--transport must be peer or rccl\n");
@@ -121,7 +124,14 @@ int main(int argc, char** argv) {
 		check(D, mpm_add_model(D.ctx, MPM_FIXED_COROTATED, &p, pts[0].data(), pts.size(), v0, &id));
 		D.n = pts.size();
 		std::printf("init model on device %d (gpu %d) with %zu particles\n", d, D.gpu, D.n);
-		pio::write_bgeo(out + "/model_dev[" + std::to_string(d) + "]_frame[0].bgeo", pts[0].data(), pts.size());
+		const std::string frame0 = out + "/model_dev[" + std::to_string(d) + "]_frame[0].bgeo";
+		if(out_vel) {
+			std::vector<float> v(3 * pts.size());
+			for(size_t i = 0; i < pts.size(); ++i) std::copy(v0, v0 + 3, v.begin() + 3 * i);
+			pio::write_bgeo(frame0, pts[0].data(), pts.size(), v.data());
+		} else {
+			pio::write_bgeo(frame0, pts[0].data(), pts.size());
+		}
 	}
 	if(!boundary.empty()) {// init_boundary (mgsp_benchmark.cuh:257-266)
 		const size_t n = (size_t) N * N * N;
@@ -170,18 +180,31 @@ int main(int argc, char** argv) {
 	struct FrameCtx {
 		Dev* D;
 		int d;
+		mpm_group* g;// non-null: write "v" (mpm_group_retrieve_velocity)
 		const std::string* out;
 		pio::AsyncWriter* io;
 		std::mutex* m;
 	};
 	auto on_frame = [](int frame, void* user) {// output_model, mgsp_benchmark.cuh:565-591
 		FrameCtx* F = static_cast<FrameCtx*>(user);
-		std::vector<float> buf(3 * F->D->n);
+		std::vector<float> buf(3 * F->D->n), vbuf;
 		size_t n = F->D->n;
-		if(mpm_retrieve_positions(F->D->ctx, 0, buf.data(), &n) != MPM_OK) return;
+		if(F->g) {
+			vbuf.resize(3 * F->D->n);
+			if(mpm_group_retrieve_velocity(F->g, 0, buf.data(), vbuf.data(), nullptr, &n) != MPM_OK) {
+				std::fprintf(stderr, "device %d: %s\n", F->d, mpm_group_last_error(F->g));
+				return;
+			}
+		} else if(mpm_retrieve_positions(F->D->ctx, 0, buf.data(), &n) != MPM_OK) {
+			return;
+		}
 		std::lock_guard<std::mutex> lk(*F->m);
 		std::printf("total number of particles %zu\n", n);
-		F->io->write_bgeo_async(*F->out + "/model_dev[" + std::to_string(F->d) + "]_frame[" + std::to_string(frame) + "].bgeo", buf, n);// IO::insert_job, :586-590
+		const std::string fn = *F->out + "/model_dev[" + std::to_string(F->d) + "]_frame[" + std::to_string(frame) + "].bgeo";
+		if(F->g)
+			F->io->write_bgeo_async(fn, buf, vbuf, n);
+		else
+			F->io->write_bgeo_async(fn, buf, n);// IO::insert_job, :586-590
 	};
 	std::vector<std::thread> workers;
 	std::vector<int> steps(ndev, 0);
@@ -193,7 +216,7 @@ int main(int argc, char** argv) {
 				failed = 1;
 				return;
 			}
-			FrameCtx F {&D, d, &out, &io, &io_mutex};
+			FrameCtx F {&D, d, out_vel ? groups[d] : nullptr, &out, &io, &io_mutex};
 			int rc = mpm_group_initial_setup(groups[d]);
 			if(rc == MPM_OK) rc = mpm_group_main_loop(groups[d], frames, fps, 1e-4f, on_frame, &F, &steps[d]);
 			if(rc != MPM_OK) {

@@ -27,7 +27,7 @@ import torch
 import torch.distributed as dist
 
 from . import _ffi, scenes
-from .engine import EngineError, build_engine
+from .engine import EngineError, build_engine, momentum_dict
 
 ROW = 3 + 256  # one halo record: key (3 x int32) + grid block (4 x 64 x f32)
 
@@ -328,6 +328,9 @@ class MgspRank:
         return out
 
 
+_ON_FRAME = C.CFUNCTYPE(None, C.c_int, C.c_void_p)   # void (*on_frame)(int frame, void* user) of mpm_group_main_loop
+
+
 class MgspGroupRank:
     """One rank of the C++ MGSP driver (claymore_amd/csrc/mpm_group.inc): the whole substep loop - grid update, halo-first
     G2P2G, collect / ncclSend+ncclRecv / reduce on the comm stream beside the interior G2P2G, rebuild, ncclAllGather of
@@ -380,9 +383,12 @@ class MgspGroupRank:
     def run_fixed(self, nsteps, dt):
         self._check(self.api.group_run_fixed(self.grp, int(nsteps), dt))
 
-    def main_loop(self, frames, fps, dt_default):
+    def main_loop(self, frames, fps, dt_default, on_frame=None):
+        """mpm_group_main_loop; on_frame(frame) (optional) is called on this rank's thread after every frame - the group readout
+        (retrieve_velocity) may run there."""
         n = C.c_int(0)
-        self._check(self.api.group_main_loop(self.grp, int(frames), int(fps), dt_default, None, None, C.byref(n)))
+        cb = _ON_FRAME(lambda frame, user: on_frame(frame)) if on_frame is not None else None
+        self._check(self.api.group_main_loop(self.grp, int(frames), int(fps), dt_default, C.cast(cb, C.c_void_p) if cb else None, None, C.byref(n)))
         return n.value
 
     def stats(self):
@@ -412,6 +418,27 @@ class MgspGroupRank:
 
     def local_state(self):
         return [self.eng.retrieve_state(m) for m in range(len(self.eng.models))]
+
+    def retrieve_velocity(self, model=0, affine=False):
+        """This rank's particles of `model` read out from the group's summed grid (mpm_group_retrieve_velocity; not collective):
+        (xyz, v) or (xyz, v, C) as Engine.retrieve_velocity."""
+        n = C.c_size_t(self.eng.models[model]["n"])
+        xyz = np.empty((n.value, 3), dtype=np.float32)
+        vel = np.empty((n.value, 3), dtype=np.float32)
+        aff = np.empty((n.value, 9), dtype=np.float32) if affine else None
+        self._check(self.api.group_retrieve_velocity(self.grp, model, xyz.ctypes.data_as(C.c_void_p), vel.ctypes.data_as(C.c_void_p),
+                                                     aff.ctypes.data_as(C.c_void_p) if affine else None, C.byref(n)))
+        k = n.value
+        if not affine:
+            return xyz[:k], vel[:k]
+        return xyz[:k], vel[:k], aff[:k].reshape(k, 3, 3).transpose(0, 2, 1)
+
+    def particle_momentum(self, model=None):
+        """{"count", "momentum" (3,), "kinetic"} over the particles of ALL ranks (mpm_group_particle_momentum).  Collective: every rank
+        calls it (a LocalGroup's ranks each from their own thread) and gets the same values."""
+        out = (C.c_double * 5)()
+        self._check(self.api.group_particle_momentum(self.grp, -1 if model is None else int(model), out))
+        return momentum_dict(out)
 
     def close(self):
         if self.grp:

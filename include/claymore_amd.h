@@ -180,10 +180,16 @@ int mpm_state_kind(void);
  * after loading a checkpoint saved in that state.  mpm_grid_update turns the momenta into velocities in place; between it and the next
  * mpm_rebuild_partition (mpm_g2p2g included) the readout is refused with MPM_ERR_INVALID.
  * Errors: MPM_ERR_NOT_READY before mpm_initial_setup; MPM_ERR_INVALID for a bad model, a NULL xyz / vel / n, a grid that holds velocities
- * (above), or a context that has ever joined an mpm_group or been through the halo tagging - its halo nodes hold only its own share of the
- * momentum between two substeps, and the refusal is permanent for that context (a group-level readout is not built); MPM_ERR_CAPACITY when
+ * (above), or a context that has ever joined an mpm_group or been through the halo tagging - the refusal is permanent for that context: its
+ * grid holds the group's summed momentum only at the return of a group call, which the group readout tracks (mpm_group_retrieve_velocity
+ * below; after a phase-level call it may hold only this rank's share of the halo nodes); MPM_ERR_CAPACITY when
  * *n is too small (the first *n particles are written).  mpm_last_error says which.  HIP library only. */
 int mpm_retrieve_velocity(mpm_ctx* ctx, int model, float* xyz, float* vel, float* affine9, size_t* n);
+/* Extension: the totals of the same readout without per-particle output, summed on the device in float64:
+ *   out[0] = particle count, out[1..3] = sum_p m_p v_p, out[4] = sum_p 1/2 m_p |v_p|^2, m_p = volume * rho of the particle's model
+ *   (the mass the set-up P2G uses).  model = -1: all models.  Preconditions and errors those of mpm_retrieve_velocity (a NULL out is
+ *   MPM_ERR_INVALID).  The order of the device's float64 additions is unspecified: the last bits may differ between calls. */
+int mpm_particle_momentum(mpm_ctx* ctx, int model, double out[5]);
 
 int mpm_get_counts(mpm_ctx* ctx, mpm_counts* counts);
 
@@ -341,6 +347,19 @@ float mpm_group_compute_dt(const mpm_group* g, float max_vel, float cur_time, fl
 /* main_loop with adaptive dt from the maximum grid velocity over all ranks (:410-418); on_frame may be NULL. */
 int mpm_group_main_loop(mpm_group* g, int frames, int fps, float dt_default, void (*on_frame)(int frame, void* user), void* user, int* steps_out);
 int mpm_group_stats(const mpm_group* g, int* send_counts32, int* halo_particle_blocks, float* g2p2g_ms_avg);
+/* Readout of a group (extension).  At the return of a group call that completed (mpm_group_initial_setup,
+ * _resume, _substep, _run_fixed) and inside mpm_group_main_loop's on_frame, every rank's grid holds the mass and momentum summed over the
+ * ranks on every node its particles reach, and the readout of mpm_retrieve_velocity is evaluated on it.
+ * mpm_group_retrieve_velocity: this rank's particles of `model` (positions, v_p, C_p as mpm_retrieve_velocity; affine9 may be NULL).
+ *   Per rank, NOT collective: it may be called from on_frame.
+ * mpm_group_particle_momentum: the five totals of mpm_particle_momentum over the particles of ALL ranks (model = -1: all models).
+ *   Collective: every rank calls it; every rank gets the same bits (the ranks' float64 sums gathered and added in rank order).  A rank
+ *   that cannot read out makes the call fail on every rank.
+ * Errors: MPM_ERR_NOT_READY before set-up; MPM_ERR_INVALID for a bad model or NULL array, after a group call that failed, and after a
+ * phase-level call on the context (mpm_grid_update, mpm_g2p2g*, mpm_rebuild_partition, mpm_mgsp_*, mpm_halo_*, mpm_checkpoint_load ...)
+ * until the next group call completes; MPM_ERR_CAPACITY when *n is too small.  A readout error does not break the group. */
+int mpm_group_retrieve_velocity(mpm_group* g, int model, float* xyz, float* vel, float* affine9, size_t* n);
+int mpm_group_particle_momentum(mpm_group* g, int model, double out[5]);
 
 #ifdef __cplusplus
 }

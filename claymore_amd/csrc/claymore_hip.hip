@@ -664,6 +664,12 @@ static ModelView make_view(mpm_ctx* ctx, Model& m) {
 	return v;
 }
 
+// Model m as every readout reads it (mpm_readout.hpp): its list and bins, in the numberings of the last rebuild.
+static ReadoutArgs make_readout_args(mpm_ctx* ctx, const Model& m) {
+	const int r = ctx->rollid;
+	return ReadoutArgs {ctx->g, m.nch, m.pair ? 1 : 0, ctx->part[r].keys, ctx->part[r].table, ctx->part[r ^ 1].table, m.size, m.row_of, m.list[m.list_in], m.binoff[r], m.bins[r]};
+}
+
 // a launch size for `n` (an estimate that may be a few substeps old) particle blocks: margin for growth, a multiple of 8 (XCDs)
 static inline int hint_blocks(const mpm_ctx* ctx, int n) {
 	const long long h = (long long) n + n / 16 + 64;
@@ -1230,76 +1236,62 @@ int mpm_get_timers(mpm_ctx* ctx, mpm_timers* t) {
 	return MPM_OK;
 }
 
-// output_model, gmpm_simulator.cuh:594-634
-int mpm_retrieve_state(mpm_ctx* ctx, int model, float* xyz, float* state9, float* logjp, size_t* n) {
-	if(!ctx || !ctx->ready || model < 0 || model >= (int) ctx->models.size() || !n || !xyz) return MPM_ERR_INVALID;
+// One per-particle readout of a model (readout_kernel<kind>, kReadState or kReadVelocity) into the caller's arrays: host[0] the positions,
+// host[1] and host[2] (null: not asked for) kReadoutWidth[kind][c] floats a particle.  Positions are staged in m.d_xyz, the other columns
+// in scratch released on every exit path (an output call, once per frame at most).  *n: the capacity of the arrays in, the particles
+// written out - MPM_ERR_CAPACITY if that is not all of them.
+static int readout_particles(mpm_ctx* ctx, int model, ReadoutKind kind, float* const host[3], size_t* n) {
 	HIP_TRY(hipSetDevice(ctx->device));
-	hipStream_t s = ctx->s_compute;
-	Model& m	  = ctx->models[model];
-	const int r = ctx->rollid, nn = r ^ 1;
+	hipStream_t s	 = ctx->s_compute;
+	Model& m		 = ctx->models[model];
 	const size_t cap = std::min(*n, m.n);
-	// (an output call, once per frame at most: its two staging arrays are allocated here and released on every exit path)
-	DevScratch<float> b_state, b_lj;
-	if(state9) HIP_TRY(b_state.alloc(9 * cap));
-	if(logjp) HIP_TRY(b_lj.alloc(cap));
-	float *d_state = b_state.p, *d_lj = b_lj.p;
+	DevScratch<float> scratch[3];
+	ReadoutOut out {{m.d_xyz, nullptr, nullptr}, cap, ctx->d_counter, 0.0, nullptr};
+	for(int c = 1; c < 3; ++c)
+		if(host[c]) {
+			HIP_TRY(scratch[c].alloc(kReadoutWidth[kind][c] * cap));
+			out.col[c] = scratch[c].p;
+		}
 	HIP_TRY(hipMemsetAsync(ctx->d_counter, 0, sizeof(unsigned long long), s));
-	if(ctx->pbc) retrieve_kernel<<<ctx->pbc, 256, 0, s>>>(ctx->g, m.nch, ctx->part[r].keys, ctx->part[nn].table, m.size, m.row_of, m.list[m.list_in], m.binoff[r], m.bins[r], m.d_xyz, d_state, d_lj, (unsigned long long) cap, ctx->d_counter, m.pair ? 1 : 0);
-	unsigned long long count = 0;
-	HIP_TRY(hipMemcpyAsync(&count, ctx->d_counter, sizeof(count), hipMemcpyDeviceToHost, s));
-	HIP_TRY(hipStreamSynchronize(s));
-	const size_t got = std::min<size_t>(count, cap);
-	HIP_TRY(hipMemcpy(xyz, m.d_xyz, sizeof(float) * 3 * got, hipMemcpyDeviceToHost));
-	if(state9) HIP_TRY(hipMemcpy(state9, d_state, sizeof(float) * 9 * got, hipMemcpyDeviceToHost));
-	if(logjp) HIP_TRY(hipMemcpy(logjp, d_lj, sizeof(float) * got, hipMemcpyDeviceToHost));
-	*n = got;
-	if(count > cap) return fail(ctx, MPM_ERR_CAPACITY, "output array too small");
-	return MPM_OK;
-}
-
-// Per-particle velocity and affine matrix gathered from grid[0] (mpm_readout.hpp; an extension, the reference has no velocity output).
-// The readout of this context's own grid, without the state checks of its callers (mpm_retrieve_velocity, mpm_group_retrieve_velocity).
-static int readout_velocity(mpm_ctx* ctx, int model, float* xyz, float* vel, float* affine9, size_t* n) {
-	HIP_TRY(hipSetDevice(ctx->device));
-	hipStream_t s = ctx->s_compute;
-	Model& m	  = ctx->models[model];
-	const int r = ctx->rollid, nn = r ^ 1;
-	const size_t cap = std::min(*n, m.n);
-	// (an output call: its staging arrays are allocated here and released on every exit path; positions are staged in m.d_xyz as retrieve does)
-	DevScratch<float> b_vel, b_aff;
-	HIP_TRY(b_vel.alloc(3 * cap));
-	if(affine9) HIP_TRY(b_aff.alloc(9 * cap));
-	HIP_TRY(hipMemsetAsync(ctx->d_counter, 0, sizeof(unsigned long long), s));
-	if(ctx->pbc)
-		retrieve_velocity_kernel<<<ctx->pbc, kReadoutThreads, 0, s>>>(ctx->g, m.nch, ctx->part[r].keys, ctx->part[r].table, ctx->part[nn].table, m.size, m.row_of, m.list[m.list_in], m.binoff[r], m.bins[r], ctx->grid[0], m.d_xyz, b_vel.p,
-																	  b_aff.p, (unsigned long long) cap, ctx->d_counter, m.pair ? 1 : 0);
+	if(ctx->pbc && kind == kReadState) readout_kernel<kReadState><<<ctx->pbc, kReadoutThreads, 0, s>>>(make_readout_args(ctx, m), nullptr, out);
+	if(ctx->pbc && kind == kReadVelocity) readout_kernel<kReadVelocity><<<ctx->pbc, kReadoutThreads, 0, s>>>(make_readout_args(ctx, m), ctx->grid[0], out);
 	HIP_TRY(hipGetLastError());
 	unsigned long long count = 0;
 	HIP_TRY(hipMemcpyAsync(&count, ctx->d_counter, sizeof(count), hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
 	const size_t got = std::min<size_t>(count, cap);
-	HIP_TRY(hipMemcpy(xyz, m.d_xyz, sizeof(float) * 3 * got, hipMemcpyDeviceToHost));
-	HIP_TRY(hipMemcpy(vel, b_vel.p, sizeof(float) * 3 * got, hipMemcpyDeviceToHost));
-	if(affine9) HIP_TRY(hipMemcpy(affine9, b_aff.p, sizeof(float) * 9 * got, hipMemcpyDeviceToHost));
+	for(int c = 0; c < 3; ++c)
+		if(host[c]) HIP_TRY(hipMemcpy(host[c], out.col[c], sizeof(float) * kReadoutWidth[kind][c] * got, hipMemcpyDeviceToHost));
 	*n = got;
 	if(count > cap) return fail(ctx, MPM_ERR_CAPACITY, "output array too small");
 	return MPM_OK;
 }
 
+// output_model, gmpm_simulator.cuh:594-634 (+ state for the parity tests): whatever grid[0] holds
+int mpm_retrieve_state(mpm_ctx* ctx, int model, float* xyz, float* state9, float* logjp, size_t* n) {
+	if(!ctx || !ctx->ready || model < 0 || model >= (int) ctx->models.size() || !n || !xyz) return MPM_ERR_INVALID;
+	float* const host[3] = {xyz, state9, logjp};
+	return readout_particles(ctx, model, kReadState, host, n);
+}
+
+// Per-particle velocity and affine matrix gathered from grid[0] (mpm_readout.hpp; an extension, the reference has no velocity output).
+// The readout of this context's own grid, without the state checks of its callers (mpm_retrieve_velocity, mpm_group_retrieve_velocity).
+static int readout_velocity(mpm_ctx* ctx, int model, float* xyz, float* vel, float* affine9, size_t* n) {
+	float* const host[3] = {xyz, vel, affine9};
+	return readout_particles(ctx, model, kReadVelocity, host, n);
+}
+
 // {count, sum m v_p (3), sum 1/2 m |v_p|^2} of one model (model >= 0) or of all models (-1), from this context's own grid[0]:
-// particle_momentum_kernel, one launch per model into one float64 accumulator.
+// readout_kernel<kReadMomentum>, one launch per model into one float64 accumulator.
 static int readout_momentum(mpm_ctx* ctx, int model, double out[5]) {
 	HIP_TRY(hipSetDevice(ctx->device));
 	hipStream_t s = ctx->s_compute;
-	const int r = ctx->rollid, nn = r ^ 1;
 	DevScratch<double> d_out;
 	HIP_TRY(d_out.alloc(kMomentumSums));
 	HIP_TRY(hipMemsetAsync(d_out.p, 0, sizeof(double) * kMomentumSums, s));
 	for(int mi = model < 0 ? 0 : model; mi < (model < 0 ? (int) ctx->models.size() : model + 1); ++mi) {
 		Model& m = ctx->models[mi];
-		if(ctx->pbc && m.n)
-			particle_momentum_kernel<<<ctx->pbc, kReadoutThreads, 0, s>>>(ctx->g, m.nch, ctx->part[r].keys, ctx->part[r].table, ctx->part[nn].table, m.size, m.row_of, m.list[m.list_in], m.binoff[r], m.bins[r], ctx->grid[0],
-																		  (double) m.mc.mass, d_out.p, m.pair ? 1 : 0);
+		if(ctx->pbc && m.n) readout_kernel<kReadMomentum><<<ctx->pbc, kReadoutThreads, 0, s>>>(make_readout_args(ctx, m), ctx->grid[0], ReadoutOut {{}, 0, nullptr, (double) m.mc.mass, d_out.p});
 		HIP_TRY(hipGetLastError());
 	}
 	HIP_TRY(hipMemcpyAsync(out, d_out.p, sizeof(double) * kMomentumSums, hipMemcpyDeviceToHost, s));

@@ -1026,46 +1026,6 @@ __global__ __launch_bounds__(256) void rasterize_blocks_kernel(GridCfg cfg, cons
 	}
 }
 
-// ------------------------------------------------------------------------------------------------------
-// Output: retrieve_particle_buffer, mgmpm_kernels.cuh:1087-1122 (+ state for the parity tests)
-// ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void retrieve_kernel(GridCfg cfg, int nch, const int* __restrict__ cur_keys, const int* __restrict__ prev_table, const int* __restrict__ size, const int* __restrict__ row_of, const int* __restrict__ list_in, const int* __restrict__ binoff_src, const float* __restrict__ bins_src, float* xyz, float* state9, float* logjp, unsigned long long capacity, unsigned long long* counter, int dense) {
-	const int b = blockIdx.x;
-	const int n = size[b];
-	if(n == 0) return;
-	const int kx = cur_keys[3 * b], ky = cur_keys[3 * b + 1], kz = cur_keys[3 * b + 2];
-	const int* list = list_in + (size_t) row_of[b] * cfg.ppb;
-	for(int pidib = threadIdx.x; pidib < ((n + 63) & ~63); pidib += blockDim.x) {
-		if(dense ? pidib >= n : (pidib & 63) >= slice_records_at(n, pidib & ~63)) continue;// a hole of the sliced list layout (the pair layout has none)
-		const int rec = list[pidib];
-		int ox, oy, oz;
-		dir_components((rec >> (cfg.pid_bits + kKeyBits)) & 31, ox, oy, oz);
-		const int sp	 = rec & (cfg.ppb - 1);
-		const int srcno	 = table_query(cfg, prev_table, kx + ox, ky + oy, kz + oz);
-		const int recf = rec_floats(nch), rowf = nch - recf;
-		const float* bin = bins_src + (size_t) (binoff_src[srcno] + (sp >> 6)) * (kBin * nch);
-		const float* src = bin + (sp & 63) * recf;
-		const float* row = bin + kBin * recf + (sp & 63) * rowf;
-		const unsigned long long o = atomicAdd(counter, 1ull);
-		if(o >= capacity) continue;
-		xyz[3 * o]	   = src[0] * cfg.dx;// (stored in cell units)
-		xyz[3 * o + 1] = src[1] * cfg.dx;
-		xyz[3 * o + 2] = src[2] * cfg.dx;
-		if(state9) {
-			if(nch == 4) {
-				state9[9 * o] = src[3];
-				for(int d = 1; d < 9; ++d) state9[9 * o + d] = 0.f;
-			} else {// b = F F^T as a full symmetric matrix (the sign of b00 marks a reflected F: reported as it is stored)
-				const float s6[6] = {src[3], src[4], src[5], src[6], src[7], row[0]};
-				float m[9];
-				sym_expand(s6, m);
-				for(int d = 0; d < 9; ++d) state9[9 * o + d] = m[d];
-			}
-		}
-		if(logjp) logjp[o] = rowf == 2 ? row[1] : 0.f;
-	}
-}
-
 __global__ void grid_totals_kernel(int nblocks, const float* __restrict__ grid, double* out) {
 	const int lane = threadIdx.x & 63;
 	double acc[4]  = {0, 0, 0, 0};

@@ -1,28 +1,74 @@
-// mpm_readout.hpp — per-particle velocity output (an extension: the reference's output_model, mgmpm_kernels.cuh:1087-1122, copies
-// positions only).  G2P2G is fused, so a particle's velocity v_p and affine matrix C_p exist only in registers of the substep kernels;
-// this kernel gathers them again, the way G2P does, from the grid a public call leaves behind: grid[0] holds each node's mass m_i and
-// momentum p_i of the last P2G.
+// mpm_readout.hpp - every readout of a model's particles, one walk of each particle block's list (readout_kernel<K>):
+//   kReadState     x, the 9-float state and log Jp (output_model, gmpm_simulator.cuh:594-634; the reference's retrieve_particle_buffer,
+//                  mgmpm_kernels.cuh:1087-1122, copies x only) - from the record and row alone, whatever the grid holds
+//   kReadVelocity  x, v_p and C_p (an extension: G2P2G is fused, so they exist only in registers of the substep kernels), gathered again the
+//                  way G2P does from grid[0], the mass m_i and momentum p_i of the last P2G
+//   kReadMomentum  {count, sum m v_p, sum 1/2 m |v_p|^2} of the same gather, summed instead of written
 //   v_i = p_i / m_i (m_i > 0, else 0)   - the state BEFORE the next grid update: no gravity, walls or collision object
 //   v_p = sum_i w_ip v_i                - 27-node quadratic B-spline stencil, base node and weights those of G2P (lround_pos, bspline_weight_cells)
 //   C_p = D^-1 sum_i w_ip v_i (x_i - x_p)^T, D^-1 = 4 / dx^2, column-major: C[3 * c + r] = C_rc (G2P2G's A, mpm_g2p2g.hpp)
-// Layout: one workgroup (256 lanes) per particle block, walking the block's list as retrieve_kernel does (sliced holes, pair layout,
-// row_of, binoff, the neighbour direction in the record).  The 2x2x2 grid blocks the block's stencils reach are staged once in LDS as
-// velocities: 8^3 nodes x 16 B = 8 KiB; a block that is not registered (or beyond an upper face) stages zero.  Each particle then reads
-// its 27 nodes from LDS at the cube-local stencil base ((base - 1) & 3) + 1 - G2P's, which also gives particles of cells -2 / -1 the
-// reference's wrapped key.  Output slots: ONE global atomic per workgroup reserves the block's n slots, its waves take theirs from an LDS
-// counter (the block's list holds exactly n records).  Per-wave global atomics on the one counter - what retrieve_kernel amounts to after
-// the compiler's wave aggregation - serialise at ~12 ns each: 7.5 ms for C3's 626 k waves; this kernel takes 1.10 ms, and so does the
-// reduction below, which has no counter at all (profiles/c3_velocity_readout.txt, c3_particle_momentum.txt).  Position,
-// velocity and C of a particle go to the same slot.  particle_momentum_kernel sums the same readout instead of writing it.
+// One workgroup (256 lanes) per particle block.  The gathers stage the 2x2x2 grid blocks the block's stencils reach once in LDS as
+// velocities (8 KiB; a block that is not registered, or beyond an upper face, stages zero) and read each particle's 27 nodes from there at
+// G2P's cube-local stencil base ((base - 1) & 3) + 1, which also gives particles of cells -2 / -1 the reference's wrapped key.  Output
+// slots: ONE global atomic per workgroup reserves the block's n slots (its list holds exactly n records), its waves take theirs from an
+// LDS counter; all outputs of a particle share its slot, and the slot order is unspecified.
 #pragma once
 #include "mpm_kernels.hpp"
 
 namespace mpm {
 
 constexpr int kReadoutThreads = 256;
+constexpr int kMomentumSums	  = 5;
 
-// The pieces both readout kernels share - the cube staging, the record fetch and the 27-node gather - so that the stencil, tie and
-// face rules live in one place.
+enum ReadoutKind { kReadState, kReadVelocity, kReadMomentum };
+
+// What every readout reads of a model: the block numberings, the list and the bins (make_readout_args, claymore_hip.hip).
+struct ReadoutArgs {
+	GridCfg cfg;
+	int nch;			  // floats per particle in a bin
+	int dense;			  // the pair list layout (no holes), else the sliced one
+	const int* cur_keys;  // [block][3], current numbering
+	const int* cur_table; // current numbering (the staged grid blocks)
+	const int* prev_table;// the numbering the bins are laid out in
+	const int* size;	  // particles per current block
+	const int* row_of;	  // row of `list` that belongs to current block b
+	const int* list;	  // advection records, cfg.ppb per row
+	const int* binoff;	  // first bin of a block, previous numbering
+	const float* bins;
+};
+
+// Where a readout puts its result.  kReadState / kReadVelocity: slot o of col[c] holds kReadoutWidth[K][c] floats of one particle - col[0] x
+// (never null), then state9 and log Jp, or v and C; a null column is not written -, slots at or beyond `capacity` are dropped, and *counter
+// (zeroed by the caller) ends at the number of particles.  kReadMomentum: sums[0..4] (zeroed by the caller) += the totals, m = mass.
+struct ReadoutOut {
+	float* col[3];
+	unsigned long long capacity;
+	unsigned long long* counter;
+	double mass;
+	double* sums;
+};
+constexpr int kReadoutWidth[2][3] = {{3, 9, 1}, {3, 3, 9}};
+
+// The pieces the readouts share - the list walk's liveness test, the record fetch, the cube staging and the 27-node gather - so that the
+// list layouts, the record format and the stencil, tie and face rules live in one place.
+// Whether slot pidib of a list of n records holds a particle (a hole of the sliced list layout does not; the pair layout has none).
+__device__ __forceinline__ bool readout_live(int n, int pidib, int dense) {
+	return dense ? pidib < n : (pidib & 63) < slice_records_at(n, pidib & ~63);
+}
+// Position (cell units) of the particle in record `rec` of block (kx, ky, kz), from the source bin the record's neighbour direction names.
+// Returns the particle's record (x, y, z, then J or five entries of b) and sets *row to its row (b21, log Jp; mpm_g2p2g.hpp).
+__device__ __forceinline__ const float* readout_position(const ReadoutArgs& a, int rec, int kx, int ky, int kz, float p[3], const float** row) {
+	int ox, oy, oz;
+	dir_components((rec >> (a.cfg.pid_bits + kKeyBits)) & 31, ox, oy, oz);
+	const int sp	 = rec & (a.cfg.ppb - 1);
+	const int srcno	 = table_query(a.cfg, a.prev_table, kx + ox, ky + oy, kz + oz);
+	const int recf	 = rec_floats(a.nch);
+	const float* bin = a.bins + (size_t) (a.binoff[srcno] + (sp >> 6)) * (kBin * a.nch);
+	const float* src = bin + (sp & 63) * recf;
+	*row			 = bin + kBin * recf + (sp & 63) * (a.nch - recf);
+	p[0] = src[0], p[1] = src[1], p[2] = src[2];
+	return src;
+}
 // Stage the 2x2x2 grid blocks at (kx, ky, kz) + {0, 1}^3 as velocities: node (x, y, z) of the 8^3 cube at (x << 6) | (y << 3) | z.
 // The eight table look-ups are done once, by eight lanes, into s_nb (not once per node: 64 hash probes per block).
 __device__ __forceinline__ void readout_stage_cube(const GridCfg& cfg, const int* __restrict__ cur_table, const float* __restrict__ grid, int kx, int ky, int kz, float4* s_v) {
@@ -41,19 +87,6 @@ __device__ __forceinline__ void readout_stage_cube(const GridCfg& cfg, const int
 		const int x = ((lb >> 2) & 1) * 4 + (c >> 4), y = ((lb >> 1) & 1) * 4 + ((c >> 2) & 3), z = (lb & 1) * 4 + (c & 3);
 		s_v[(x << 6) | (y << 3) | z] = v;
 	}
-}
-// Whether slot pidib of a list of n records holds a particle (a hole of the sliced list layout does not; the pair layout has none).
-__device__ __forceinline__ bool readout_live(int n, int pidib, int dense) {
-	return dense ? pidib < n : (pidib & 63) < slice_records_at(n, pidib & ~63);
-}
-// Position (cell units) of the particle in record `rec` of block (kx, ky, kz): the source bin the record's neighbour direction names.
-__device__ __forceinline__ void readout_position(const GridCfg& cfg, int nch, int rec, int kx, int ky, int kz, const int* __restrict__ prev_table, const int* __restrict__ binoff_src, const float* __restrict__ bins_src, float p[3]) {
-	int ox, oy, oz;
-	dir_components((rec >> (cfg.pid_bits + kKeyBits)) & 31, ox, oy, oz);
-	const int sp	 = rec & (cfg.ppb - 1);
-	const int srcno	 = table_query(cfg, prev_table, kx + ox, ky + oy, kz + oz);
-	const float* src = bins_src + (size_t) (binoff_src[srcno] + (sp >> 6)) * (kBin * nch) + (sp & 63) * rec_floats(nch);
-	p[0] = src[0], p[1] = src[1], p[2] = src[2];
 }
 // G2P's gather at p (cell units) from the staged cube: v_p, and with kAffine A = sum_i w_ip v_i (x_i - x_p)^T in cell units (column-major).
 template<bool kAffine>
@@ -90,92 +123,101 @@ __device__ __forceinline__ void readout_gather(const float4* s_v, const float p[
 			}
 }
 
-__global__ __launch_bounds__(kReadoutThreads) void retrieve_velocity_kernel(GridCfg cfg, int nch, const int* __restrict__ cur_keys, const int* __restrict__ cur_table, const int* __restrict__ prev_table, const int* __restrict__ size, const int* __restrict__ row_of, const int* __restrict__ list_in, const int* __restrict__ binoff_src, const float* __restrict__ bins_src, const float* __restrict__ grid, float* xyz, float* vel, float* affine9, unsigned long long capacity, unsigned long long* counter, int dense) {
-	__shared__ float4 s_v[512];// node (x, y, z) of the 8^3 cube at (x << 6) | (y << 3) | z, {vx, vy, vz, 0}
+// One workgroup per particle block; the walk's bound is a multiple of 64 and its stride 256, so every lane of a wave takes the same trips
+// (the slot counter is taken per wave).  kReadMomentum: each lane sums in float64, a wave folds its 64 lanes with __shfl_xor (DPP /
+// ds_swizzle), the 4 waves meet in LDS, and ONE set of five float64 atomics per workgroup goes to global memory (global_atomic_add_f64);
+// the order of the workgroups' atomics is unspecified, so the last bits of the sums may differ from run to run.
+template<ReadoutKind K>
+__global__ __launch_bounds__(kReadoutThreads) void readout_kernel(ReadoutArgs a, const float* __restrict__ grid, ReadoutOut out) {
+	constexpr bool kGrid = K != kReadState;// (the state readout neither stages nor reads the grid)
+	__shared__ float4 s_v[kGrid ? 512 : 1];// node (x, y, z) of the 8^3 cube at (x << 6) | (y << 3) | z, {vx, vy, vz, 0}
 	__shared__ unsigned long long s_first;// the block's output range [s_first, s_first + n)
 	__shared__ unsigned s_next;			  // slots of that range handed out so far
-	const int b = blockIdx.x;
-	const int n = size[b];
-	if(n == 0) return;
-	if(threadIdx.x == 0) {
-		s_first = atomicAdd(counter, (unsigned long long) n);
-		s_next	= 0u;
-	}
-	const int kx = cur_keys[3 * b], ky = cur_keys[3 * b + 1], kz = cur_keys[3 * b + 2];
-	readout_stage_cube(cfg, cur_table, grid, kx, ky, kz, s_v);
-	__syncthreads();
-	const int* list	 = list_in + (size_t) row_of[b] * cfg.ppb;
-	const float cdinv = cfg.d_inv * cfg.dx;// A is gathered in cell units: C = D^-1 A dx
-	const int lane	 = threadIdx.x & 63;
-	for(int pidib = threadIdx.x; pidib < ((n + 63) & ~63); pidib += kReadoutThreads) {
-		// (the loop bound is a multiple of 64 and the stride of 256: every lane of a wave takes the same trips - the slot atomic below is per wave)
-		const bool live = readout_live(n, pidib, dense);
-		float p[3] = {0.f, 0.f, 0.f};
-		if(live) readout_position(cfg, nch, list[pidib], kx, ky, kz, prev_table, binoff_src, bins_src, p);
-		const unsigned long long live_mask = __ballot(live);
-		if(live_mask == 0ull) continue;
-		const int leader = __ffsll((long long) live_mask) - 1;
-		unsigned first	 = 0;
-		if(lane == leader) first = atomicAdd(&s_next, (unsigned) __popcll(live_mask));
-		first = __shfl(first, leader);
-		if(!live) continue;
-		const unsigned rank = first + (unsigned) __popcll(live_mask & ((1ull << lane) - 1ull));
-		const unsigned long long o = s_first + rank;
-		if(rank >= (unsigned) n || o >= capacity) continue;// (the first never happens: the list holds n records)
-		float v[3], A[9];
-		readout_gather<true>(s_v, p, v, A);
-		xyz[3 * o]	   = p[0] * cfg.dx;
-		xyz[3 * o + 1] = p[1] * cfg.dx;
-		xyz[3 * o + 2] = p[2] * cfg.dx;
-		vel[3 * o]	   = v[0];
-		vel[3 * o + 1] = v[1];
-		vel[3 * o + 2] = v[2];
-		if(affine9)
-			for(int d = 0; d < 9; ++d) affine9[9 * o + d] = A[d] * cdinv;
-	}
-}
-
-// Totals of the readout without per-particle output (mpm_particle_momentum): out[0..4] += {count, sum m v_p (3), sum 1/2 m |v_p|^2}
-// over the model's particles, m = the model's particle mass.  Same walk, cube and gather as retrieve_velocity_kernel; each lane sums in
-// float64, a wave folds its 64 lanes with __shfl_xor (DPP / ds_swizzle), the 4 waves meet in LDS, and ONE set of five float64 atomics
-// per workgroup goes to global memory (global_atomic_add_f64; per-wave global atomics serialise, see above).  out must be zeroed by the
-// caller; the order of the workgroups' atomics is unspecified, so the last bits of the sums may differ from run to run.
-constexpr int kMomentumSums = 5;
-__global__ __launch_bounds__(kReadoutThreads) void particle_momentum_kernel(GridCfg cfg, int nch, const int* __restrict__ cur_keys, const int* __restrict__ cur_table, const int* __restrict__ prev_table, const int* __restrict__ size, const int* __restrict__ row_of, const int* __restrict__ list_in, const int* __restrict__ binoff_src, const float* __restrict__ bins_src, const float* __restrict__ grid, double mass, double* out, int dense) {
-	__shared__ float4 s_v[512];
 	__shared__ double s_red[kReadoutThreads / 64][kMomentumSums];
 	const int b = blockIdx.x;
-	const int n = size[b];
+	const int n = a.size[b];
 	if(n == 0) return;
-	const int kx = cur_keys[3 * b], ky = cur_keys[3 * b + 1], kz = cur_keys[3 * b + 2];
-	readout_stage_cube(cfg, cur_table, grid, kx, ky, kz, s_v);
+	// (the block's scalars are loaded before the first global store, the slot atomic: so the compiler knows them uniform and unclobbered)
+	const int kx = a.cur_keys[3 * b], ky = a.cur_keys[3 * b + 1], kz = a.cur_keys[3 * b + 2];
+	const int* list = a.list + (size_t) a.row_of[b] * a.cfg.ppb;
+	if(K != kReadMomentum && threadIdx.x == 0) {
+		s_first = atomicAdd(out.counter, (unsigned long long) n);
+		s_next	= 0u;
+	}
+	if constexpr(kGrid) readout_stage_cube(a.cfg, a.cur_table, grid, kx, ky, kz, s_v);
 	__syncthreads();
-	const int* list = list_in + (size_t) row_of[b] * cfg.ppb;
 	double acc[kMomentumSums] = {0.0, 0.0, 0.0, 0.0, 0.0};
 	for(int pidib = threadIdx.x; pidib < ((n + 63) & ~63); pidib += kReadoutThreads) {
-		if(!readout_live(n, pidib, dense)) continue;
-		float p[3], v[3];
-		readout_position(cfg, nch, list[pidib], kx, ky, kz, prev_table, binoff_src, bins_src, p);
-		readout_gather<false>(s_v, p, v, nullptr);
-		acc[0] += 1.0;
-		acc[1] += (double) v[0];
-		acc[2] += (double) v[1];
-		acc[3] += (double) v[2];
-		acc[4] += (double) v[0] * v[0] + (double) v[1] * v[1] + (double) v[2] * v[2];
+		const bool live = readout_live(n, pidib, a.dense);
+		if(K == kReadMomentum && !live) continue;// (no slots: the lanes of a wave need not agree)
+		float p[3]		 = {0.f, 0.f, 0.f};
+		const float *src = nullptr, *row = nullptr;
+		if(live) src = readout_position(a, list[pidib], kx, ky, kz, p, &row);
+		if constexpr(K == kReadMomentum) {
+			float v[3];
+			readout_gather<false>(s_v, p, v, nullptr);
+			acc[0] += 1.0;
+			acc[1] += (double) v[0];
+			acc[2] += (double) v[1];
+			acc[3] += (double) v[2];
+			acc[4] += (double) v[0] * v[0] + (double) v[1] * v[1] + (double) v[2] * v[2];
+		} else {
+			const unsigned long long live_mask = __ballot(live);
+			if(live_mask == 0ull) continue;
+			const int lane	 = threadIdx.x & 63;
+			const int leader = __ffsll((long long) live_mask) - 1;
+			unsigned first	 = 0;
+			if(lane == leader) first = atomicAdd(&s_next, (unsigned) __popcll(live_mask));
+			first = __shfl(first, leader);
+			if(!live) continue;
+			const unsigned rank		   = first + (unsigned) __popcll(live_mask & ((1ull << lane) - 1ull));
+			const unsigned long long o = s_first + rank;
+			if(rank >= (unsigned) n || o >= out.capacity) continue;// (the first never happens: the list holds n records)
+			float* xyz	   = out.col[0];
+			xyz[3 * o]	   = p[0] * a.cfg.dx;// (stored in cell units)
+			xyz[3 * o + 1] = p[1] * a.cfg.dx;
+			xyz[3 * o + 2] = p[2] * a.cfg.dx;
+			if constexpr(K == kReadState) {
+				float *state9 = out.col[1], *logjp = out.col[2];
+				if(state9) {
+					if(a.nch == 4) {
+						state9[9 * o] = src[3];
+						for(int d = 1; d < 9; ++d) state9[9 * o + d] = 0.f;
+					} else {// b = F F^T as a full symmetric matrix (the sign of b00 marks a reflected F: reported as it is stored)
+						const float s6[6] = {src[3], src[4], src[5], src[6], src[7], row[0]};
+						float m[9];
+						sym_expand(s6, m);
+						for(int d = 0; d < 9; ++d) state9[9 * o + d] = m[d];
+					}
+				}
+				if(logjp) logjp[o] = a.nch - rec_floats(a.nch) == 2 ? row[1] : 0.f;
+			} else {
+				float *vel = out.col[1], *affine9 = out.col[2];
+				const float cdinv = a.cfg.d_inv * a.cfg.dx;// A is gathered in cell units: C = D^-1 A dx
+				float v[3], A[9];
+				readout_gather<true>(s_v, p, v, A);
+				vel[3 * o]	   = v[0];
+				vel[3 * o + 1] = v[1];
+				vel[3 * o + 2] = v[2];
+				if(affine9)
+					for(int d = 0; d < 9; ++d) affine9[9 * o + d] = A[d] * cdinv;
+			}
+		}
 	}
+	if constexpr(K == kReadMomentum) {
 #pragma unroll
-	for(int d = 0; d < kMomentumSums; ++d)
+		for(int d = 0; d < kMomentumSums; ++d)
 #pragma unroll
-		for(int off = 32; off > 0; off >>= 1) acc[d] += __shfl_xor(acc[d], off);
-	const int wave = threadIdx.x >> 6;
-	if((threadIdx.x & 63) == 0)
-		for(int d = 0; d < kMomentumSums; ++d) s_red[wave][d] = acc[d];
-	__syncthreads();
-	if(threadIdx.x < kMomentumSums) {
-		double t = 0.0;
-		for(int w = 0; w < kReadoutThreads / 64; ++w) t += s_red[w][threadIdx.x];
-		const double scale = threadIdx.x == 0 ? 1.0 : threadIdx.x < 4 ? mass : 0.5 * mass;
-		atomicAdd(out + threadIdx.x, t * scale);
+			for(int off = 32; off > 0; off >>= 1) acc[d] += __shfl_xor(acc[d], off);
+		if((threadIdx.x & 63) == 0)
+			for(int d = 0; d < kMomentumSums; ++d) s_red[threadIdx.x >> 6][d] = acc[d];
+		__syncthreads();
+		if(threadIdx.x < kMomentumSums) {
+			double t = 0.0;
+			for(int w = 0; w < kReadoutThreads / 64; ++w) t += s_red[w][threadIdx.x];
+			const double scale = threadIdx.x == 0 ? 1.0 : threadIdx.x < 4 ? out.mass : 0.5 * out.mass;
+			atomicAdd(out.sums + threadIdx.x, t * scale);
+		}
 	}
 }
 

@@ -89,3 +89,21 @@ def test_no_scratch_access_inside_the_particle_loop_of_the_pair_kernels(device_a
     assert b > a + 500, (a, b)  # (the loop is some thousand instructions long)
     inside = [instr(l) for l in body[a:b + 1] if instr(l).startswith("scratch_")]
     assert len(inside) <= allowed, f"{sym}: scratch accesses inside the particle loop: {inside[:6]}"
+
+
+READOUTS = {kind: f"_ZN3mpm14readout_kernelILNS_11ReadoutKindE{kind}E" for kind in range(3)}  # kReadState, kReadVelocity, kReadMomentum
+
+
+def directive(body, name):
+    return int(next(l.split()[-1] for l in body if l.strip().startswith(name + " ")))
+
+
+@pytest.mark.parametrize("kind", sorted(READOUTS))
+def test_readout_budgets(device_asm, kind):
+    """The readouts (claymore_amd/csrc/mpm_readout.hpp) use no scratch, and the state readout stages no grid cube: it declares
+    under 1 KiB of LDS (the velocity readouts' cube alone is 8 KiB)."""
+    body = kernel_body(device_asm, READOUTS[kind])
+    assert directive(body, ".amdhsa_private_segment_fixed_size") == 0, kind
+    assert not any(instr(l).startswith("scratch_") for l in body), kind
+    lds = directive(body, ".amdhsa_group_segment_fixed_size")
+    assert lds < 1024 if kind == 0 else lds >= 8192, (kind, lds)

@@ -349,6 +349,55 @@ def test_refused_while_the_grid_holds_velocities():
     eng.close()
 
 
+# ---- the state readout (readout_kernel<kReadState>: the same list walk and slot rule, no grid) ----------------------------------------------------
+STATE_SCENES = {"sand": _ffi.SAND, "fluid": _ffi.J_FLUID}
+
+
+@pytest.mark.parametrize("material", sorted(STATE_SCENES))
+def test_retrieve_state_whatever_the_grid_holds_and_with_short_arrays(material):
+    """mpm_retrieve_state reads records and rows only.  Taken right after mpm_grid_update (grid[0] holds velocities) it equals, as a matched set,
+    the readout after the rebuild of a substep of dt = 0 (x += v * 0: no particle moves; the rebuild re-sorts the lists).  With an output array
+    of n // 3 it returns MPM_ERR_CAPACITY and n // 3 distinct particles of the full readout.  Runs with whichever G2P2G layout the process uses
+    (test_retrieve_state_in_both_list_layouts forces each)."""
+    sc = F.wall_zone_scene(5, "out", material=STATE_SCENES[material])
+    nm = len(sc["models"])
+    eng = build_engine(sc)
+    eng.initial_setup()
+    eng.run_fixed(20, sc["dt"])
+    eng.grid_update(sc["dt"])
+    before = [eng.retrieve_state(m) for m in range(nm)]
+    eng.g2p2g(0.0, sc["dt"])
+    eng.rebuild_partition()
+    after = [eng.retrieve_state(m) for m in range(nm)]
+    for (xa, sa, la), (xb, sb, lb) in zip(before, after):
+        assert xa.shape == xb.shape and xa.shape[0] > 100
+        idx, d = match(xa.astype(np.float64), xb.astype(np.float64))
+        assert d.max() <= 1e-6, d.max()
+        assert np.abs(sb[idx].astype(np.float64) - sa).max() <= 1e-5 * max(1.0, float(np.abs(sa).max()))
+        assert np.abs(lb[idx].astype(np.float64) - la).max() <= 1e-5
+    api, ctx = eng.api, eng.ctx
+    for m, (x, st, lj) in enumerate(after):
+        k = x.shape[0] // 3
+        xs, ss, ls = np.full((k, 3), np.nan, np.float32), np.full((k, 9), np.nan, np.float32), np.full(k, np.nan, np.float32)
+        n = C.c_size_t(k)
+        assert api.retrieve_state(ctx, m, *(a.ctypes.data_as(C.c_void_p) for a in (xs, ss, ls)), C.byref(n)) == _ffi.MPM_ERR_CAPACITY
+        assert n.value == k
+        idx, d = match(xs.astype(np.float64), x.astype(np.float64))     # (asserts k distinct particles)
+        assert d.max() == 0.0
+        assert np.array_equal(ss, st[idx]) and np.array_equal(ls, lj[idx])
+    eng.close()
+
+
+@pytest.mark.parametrize("mask", ["0", "0xF"])
+def test_retrieve_state_in_both_list_layouts(mask):
+    """test_retrieve_state_whatever_the_grid_holds_and_with_short_arrays with the G2P2G kernel forced per process, as test_both_list_layouts."""
+    env = dict(os.environ, MPM_G2P2G_PAIRS=mask)
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider",
+                        "-k", "test_retrieve_state_whatever_the_grid_holds"], env=env, capture_output=True, text=True, timeout=600)
+    tail = r.stdout[-1500:]
+    assert r.returncode == 0 and "2 passed" in tail and "failed" not in tail, (mask, tail, r.stderr[-1500:])
+
+
 # ---- the gmpm driver's frames -------------------------------------------------------------------------------------------------------------------------
 def _read_bgeo_any(path):
     raw = open(path, "rb").read()

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """C3 (40.1 M sand particles) after bench.py's default warm-up (10 substeps of 1e-4): twice a velocity readout and the device-side totals of
-the same readout (mpm_particle_momentum) - the driver behind profiles/c3_particle_momentum.txt (retrieve_velocity_kernel against
-particle_momentum_kernel), with the totals checked against a float64 sum over the readout.
+the same readout (mpm_particle_momentum) - the driver behind profiles/c3_particle_momentum.txt (readout_kernel<kReadVelocity> against
+readout_kernel<kReadMomentum>, then kernels of their own), with the totals checked against a float64 sum over the readout.
 Usage (one MI355X): rocprofv3 --kernel-trace --stats -f csv -d OUT -o c3 -- python tools/c3_particle_momentum.py"""
 import os
 import sys

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """C3 (40.1 M sand particles) after bench.py's default warm-up (10 substeps of 1e-4): twice a position readout, a velocity readout and a
-velocity + C readout - the driver behind profiles/c3_velocity_readout.txt (retrieve_kernel against retrieve_velocity_kernel).
+velocity + C readout - the driver behind profiles/c3_velocity_readout.txt (readout_kernel<kReadState> against readout_kernel<kReadVelocity>;
+that profile predates both, when the position readout was a kernel of its own with one slot atomic per particle).
 Usage (one MI355X): rocprofv3 --kernel-trace --stats -f csv -d OUT -o c3 -- python tools/c3_velocity_readout.py"""
 import os
 import sys

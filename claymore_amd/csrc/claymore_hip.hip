@@ -60,21 +60,25 @@ struct Model {
 
 }// namespace
 
+// the timing events of one substep: start, G2P2G start, G2P2G end, end
+struct SubstepEvents {
+	hipEvent_t start = nullptr, g2p2g_start = nullptr, g2p2g_end = nullptr, end = nullptr;
+};
+
 struct mpm_ctx {
 	mpm_config cfg {};
 	GridCfg g {};
 	int device = 0;
 	hipStream_t s_compute = nullptr, s_comm = nullptr;
-	hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_g0 = nullptr, ev_g1 = nullptr, ev_comm = nullptr, ev_halo = nullptr;
+	SubstepEvents ev;// (a group's windowed loop times its substeps with two sets of its own: mpm_group.inc)
+	hipEvent_t ev_comm = nullptr, ev_halo = nullptr;
 	hipEvent_t ev_tag0 = nullptr, ev_tag1 = nullptr;// group loop: key list exported (compute -> comm) / tagging complete (comm -> compute); created on first use
-	// MGSP windowed loop: the status read-back of substep t is waited for AFTER the halo-first G2P2G of substep t + 1 has been enqueued,
-	// so the timing events exist twice (index = parity of the substep)
 	// lean_events (the windowed group loop in its deferred order): a substep records three events on the compute stream instead of seven - an event between two
 	// kernels is a barrier packet of its own, 5-6 us each (profiles/r06_rank_alone_seq.txt) -: no start event (a substep's time is end-to-end of the previous one's),
 	// the end event doubles as the read-back's, the halo event is recorded once.  ev_pending: the event the outstanding read-back completes with.
 	bool lean_events = false;
 	hipEvent_t ev_pending = nullptr;
-	hipEvent_t ev_status = nullptr, ev2_a[2] = {nullptr, nullptr}, ev2_b[2] = {nullptr, nullptr}, ev2_g0[2] = {nullptr, nullptr}, ev2_g1[2] = {nullptr, nullptr};
+	hipEvent_t ev_status = nullptr;
 	// grid[0] already holds the velocities of the coming substep (the rebuild's carry-over applied the grid update for this dt):
 	// only inside mpm_run_fixed, never when a call returns
 	bool grid_preupdated = false;
@@ -334,7 +338,7 @@ int mpm_create(const mpm_config* cfg, int device, mpm_ctx** out) {
 		delete ctx;
 		return MPM_ERR_DEVICE;
 	}
-	if(hipEventCreate(&ctx->ev_a) != hipSuccess || hipEventCreate(&ctx->ev_b) != hipSuccess || hipEventCreate(&ctx->ev_g0) != hipSuccess || hipEventCreate(&ctx->ev_g1) != hipSuccess
+	if(hipEventCreate(&ctx->ev.start) != hipSuccess || hipEventCreate(&ctx->ev.end) != hipSuccess || hipEventCreate(&ctx->ev.g2p2g_start) != hipSuccess || hipEventCreate(&ctx->ev.g2p2g_end) != hipSuccess
 	   || hipEventCreateWithFlags(&ctx->ev_comm, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_halo, hipEventDisableTiming) != hipSuccess
 	   || hipEventCreateWithFlags(&ctx->ev_status, hipEventDisableTiming) != hipSuccess) {
 		mpm_destroy(ctx);// frees whatever was created (null handles are skipped)
@@ -378,18 +382,13 @@ void mpm_destroy(mpm_ctx* ctx) {
 	hipFree(ctx->d_inner_list);
 	for(auto& p: ctx->d_send_ids) hipFree(p);
 	if(ctx->h_status) hipHostFree(ctx->h_status);
-	if(ctx->ev_a) hipEventDestroy(ctx->ev_a);
-	if(ctx->ev_b) hipEventDestroy(ctx->ev_b);
-	if(ctx->ev_g0) hipEventDestroy(ctx->ev_g0);
-	if(ctx->ev_g1) hipEventDestroy(ctx->ev_g1);
+	for(hipEvent_t e: {ctx->ev.start, ctx->ev.g2p2g_start, ctx->ev.g2p2g_end, ctx->ev.end})
+		if(e) hipEventDestroy(e);
 	if(ctx->ev_comm) hipEventDestroy(ctx->ev_comm);
 	if(ctx->ev_halo) hipEventDestroy(ctx->ev_halo);
 	if(ctx->ev_tag0) hipEventDestroy(ctx->ev_tag0);
 	if(ctx->ev_tag1) hipEventDestroy(ctx->ev_tag1);
 	if(ctx->ev_status) hipEventDestroy(ctx->ev_status);
-	for(int i = 0; i < 2; ++i)
-		for(hipEvent_t e: {ctx->ev2_a[i], ctx->ev2_b[i], ctx->ev2_g0[i], ctx->ev2_g1[i]})
-			if(e) hipEventDestroy(e);
 	for(hipEvent_t e: ctx->ev_ring) hipEventDestroy(e);
 	if(ctx->s_compute) hipStreamDestroy(ctx->s_compute);
 	if(ctx->s_comm) hipStreamDestroy(ctx->s_comm);
@@ -626,13 +625,13 @@ int mpm_grid_update(mpm_ctx* ctx, float dt, float* max_vel_sqr) {
 	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
 	HIP_TRY(hipSetDevice(ctx->device));
 	hipStream_t s = ctx->s_compute;
-	HIP_TRY(hipEventRecord(ctx->ev_a, s));
+	HIP_TRY(hipEventRecord(ctx->ev.start, s));
 	int rc = launch_grid_update(ctx, dt);
 	if(rc) return rc;
-	HIP_TRY(hipEventRecord(ctx->ev_b, s));
+	HIP_TRY(hipEventRecord(ctx->ev.end, s));
 	HIP_TRY(hipMemcpyAsync(ctx->h_maxvel, ctx->d_maxvel, sizeof(float) * kMaxVelSlots * kMaxVelStride, hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
-	HIP_TRY(hipEventElapsedTime(&ctx->timers.grid_update_ms, ctx->ev_a, ctx->ev_b));
+	HIP_TRY(hipEventElapsedTime(&ctx->timers.grid_update_ms, ctx->ev.start, ctx->ev.end));
 	if(max_vel_sqr) *max_vel_sqr = host_maxvel(ctx);
 	return MPM_OK;
 }
@@ -762,11 +761,11 @@ int mpm_g2p2g(mpm_ctx* ctx, float dt, float next_dt) {
 	phase_call(ctx);
 	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
 	HIP_TRY(hipSetDevice(ctx->device));
-	int rc = launch_g2p2g(ctx, dt, next_dt, ctx->ev_g0, ctx->ev_g1);
+	int rc = launch_g2p2g(ctx, dt, next_dt, ctx->ev.g2p2g_start, ctx->ev.g2p2g_end);
 	if(rc) return rc;
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipStreamSynchronize(ctx->s_compute));
-	HIP_TRY(hipEventElapsedTime(&ctx->last_g2p2g_ms, ctx->ev_g0, ctx->ev_g1));
+	HIP_TRY(hipEventElapsedTime(&ctx->last_g2p2g_ms, ctx->ev.g2p2g_start, ctx->ev.g2p2g_end));
 	ctx->timers.g2p2g_ms = ctx->last_g2p2g_ms;
 	return MPM_OK;
 }
@@ -978,14 +977,14 @@ int mpm_rebuild_partition(mpm_ctx* ctx, mpm_counts* counts) {
 	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
 	HIP_TRY(hipSetDevice(ctx->device));
 	hipStream_t s = ctx->s_compute;
-	HIP_TRY(hipEventRecord(ctx->ev_a, s));
+	HIP_TRY(hipEventRecord(ctx->ev.start, s));
 	int rc = launch_rebuild(ctx);
 	if(rc) return rc;
-	HIP_TRY(hipEventRecord(ctx->ev_b, s));
+	HIP_TRY(hipEventRecord(ctx->ev.end, s));
 	HIP_TRY(hipGetLastError());
 	rc = finish_rebuild(ctx, counts);
 	if(rc) return rc;
-	HIP_TRY(hipEventElapsedTime(&ctx->timers.partition_ms, ctx->ev_a, ctx->ev_b));
+	HIP_TRY(hipEventElapsedTime(&ctx->timers.partition_ms, ctx->ev.start, ctx->ev.end));
 	return MPM_OK;
 }
 
@@ -1002,18 +1001,18 @@ int mpm_substep(mpm_ctx* ctx, float dt, float step_time, float frame_time, float
 	const float nd = mpm_compute_dt(ctx, mv, step_time, frame_time, dt_default);
 	if(max_vel) *max_vel = mv;
 	if(next_dt) *next_dt = nd;
-	rc = launch_g2p2g(ctx, dt, nd, ctx->ev_g0, ctx->ev_g1, true);
+	rc = launch_g2p2g(ctx, dt, nd, ctx->ev.g2p2g_start, ctx->ev.g2p2g_end, true);
 	if(rc) return rc;
 	hipStream_t s = ctx->s_compute;
-	HIP_TRY(hipEventRecord(ctx->ev_a, s));
+	HIP_TRY(hipEventRecord(ctx->ev.start, s));
 	rc = launch_rebuild(ctx);
 	if(rc) return rc;
-	HIP_TRY(hipEventRecord(ctx->ev_b, s));
+	HIP_TRY(hipEventRecord(ctx->ev.end, s));
 	HIP_TRY(hipGetLastError());
 	rc = finish_rebuild(ctx, nullptr);
 	if(rc) return rc;
-	HIP_TRY(hipEventElapsedTime(&ctx->last_g2p2g_ms, ctx->ev_g0, ctx->ev_g1));
-	HIP_TRY(hipEventElapsedTime(&ctx->timers.partition_ms, ctx->ev_a, ctx->ev_b));
+	HIP_TRY(hipEventElapsedTime(&ctx->last_g2p2g_ms, ctx->ev.g2p2g_start, ctx->ev.g2p2g_end));
+	HIP_TRY(hipEventElapsedTime(&ctx->timers.partition_ms, ctx->ev.start, ctx->ev.end));
 	ctx->timers.g2p2g_ms = ctx->last_g2p2g_ms;
 	ctx->timers.total_ms = ctx->timers.grid_update_ms + ctx->timers.g2p2g_ms + ctx->timers.partition_ms;
 	guard.armed = false;

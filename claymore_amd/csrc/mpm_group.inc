@@ -3,7 +3,7 @@
 // Included at the end of claymore_hip.hip.
 //
 // Per substep and rank (everything enqueued, ONE host synchronisation at the end):
-//   compute stream: grid update -> G2P2G on the halo particle blocks -> collect the blocks shared with each peer -> [event] ->
+//   compute stream: grid update -> G2P2G on the halo particle blocks -> collect the blocks shared with the peers -> [event] ->
 //                   G2P2G on the interior blocks -> [wait] -> partition rebuild -> padded key export -> ncclAllGather(keys) ->
 //                   overlap marks / send lists / halo split
 //   comm stream:    [event] -> ncclGroup{ncclSend, ncclRecv per peer} -> reduce -> [event back]
@@ -151,16 +151,15 @@ struct mpm_group {
 	int retags			= 0;// key lists that outgrew their padding inside mpm_group_run_fixed / mpm_group_substep and were tagged again
 	bool aborted		= false;// the communicator was aborted after an RCCL error
 	int pad_enqueued	= 0;	// the padding the outstanding substep's key lists were exported with
-	bool lean_prev_end		  = false;// (lean events) the previous substep of this run recorded its end event: the next one is timed from it
-	hipEvent_t ev_g1_override = nullptr;// the event the interior G2P2G of the substep being enqueued records (windowed loop)
+	// the windowed loop waits for the status read-back of substep t AFTER the halo-first G2P2G of substep t + 1 has been enqueued, so its
+	// timing events exist twice (index = parity of the substep); a call of one substep times it with the context's own set
+	SubstepEvents ev2[2];
 	hipEvent_t ev_sent = nullptr, ev_done = nullptr;// in-process transport, asynchronous exchange
 	hipEvent_t ev_keys = nullptr, ev_kdone = nullptr;// ... and asynchronous key all-gather
 	std::string err;
 };
 
 namespace {
-constexpr size_t kHaloRow = 3 + 256;// one halo record: key (3 x int32) + grid block (4 x 64 x f32)
-
 int gfail(mpm_group* g, int code, const std::string& msg) {
 	g->err = msg;
 	if(g->ctx && !msg.empty()) g->ctx->err = msg;
@@ -332,7 +331,6 @@ int grp_key_buffers(mpm_group* g) {
 	return MPM_OK;
 }
 
-// Phase-by-phase tagging (mgsp_benchmark.cuh:661-720): used at setup and when a key list outgrew the padding.
 // Padding of the key lists that travel in the tagging all-gather (row 0 = true count).  A list that outgrows its padding is truncated for
 // that one tagging and every rank sees it (same row 0s): the tagging is repeated with the larger length - at once where the host waits at
 // the end of the substep, after the substep's two G2P2G passes in the windowed loop (mpm_group_run_fixed).  Both cost a host round trip, so
@@ -347,6 +345,9 @@ bool grp_pad_close(const mpm_group* g, int rows, int pad) {
 	return g->tight_pad ? rows > pad : rows > 0.75 * pad;
 }
 
+// Tagging at set-up, on resume and after a truncation (mgsp_benchmark.cuh:661-720): the substep's chain - key export -> all-gather ->
+// marks / send lists / halo split - on the current partition, then one read-back of the halo counts and the row-0 heads.  A list that
+// was truncated (some head + 1 > pad) is tagged again with the larger padding.
 int grp_tag(mpm_group* g) {
 	mpm_ctx* ctx = g->ctx;
 	if(g->pad == 0) {// first call: agree on a padded length (every later length is derived from gathered counts)
@@ -355,104 +356,47 @@ int grp_tag(mpm_group* g) {
 		if(rc) return rc;
 		g->pad = std::max(2, grp_pad_for(g, (int) n + 1));
 	}
+	GRP_HIP(hipSetDevice(ctx->device));
+	GRP_TRY(halo_alloc(ctx));
 	for(;;) {
 		const int pad = g->pad;// identical on all ranks by construction
 		int rc		  = grp_key_buffers(g);
 		if(rc) return rc;
-		int cnt = 0;
-		GRP_TRY(mpm_halo_keys(ctx, g->d_keys_mine + 3, pad - 1, &cnt));
-		const int row0[3] = {cnt, 0, 0};// row 0 carries the true count (keys are truncated if it exceeds pad - 1)
-		GRP_HIP(hipMemcpyAsync(g->d_keys_mine, row0, sizeof(row0), hipMemcpyHostToDevice, ctx->s_compute));
+		ctx->halo_tagged = false;
+		GRP_TRY(halo_export(ctx, ctx->rollid, g->d_keys_mine, pad));
 		rc = grp_all_gather(g, g->d_keys_mine, g->d_keys_all, 3 * (size_t) pad, ctx->s_compute);
 		if(rc) return rc;
-		std::vector<int> heads(g->world);
-		for(int p = 0; p < g->world; ++p) GRP_HIP(hipMemcpyAsync(&heads[p], g->d_keys_all + 3 * (size_t) pad * p, sizeof(int), hipMemcpyDeviceToHost, ctx->s_compute));
-		GRP_HIP(hipStreamSynchronize(ctx->s_compute));
+		GRP_TRY(halo_tag(ctx, ctx->rollid, g->d_keys_all, pad, g->world, g->rank, ctx->s_compute));
+		GRP_TRY(halo_read_counts(ctx, g->world));
 		int need = 0;
-		for(int p = 0; p < g->world; ++p) need = std::max(need, heads[p] + 1);
+		for(int p = 0; p < g->world; ++p) need = std::max(need, ctx->h_peer_rows[p] + 1);
 		if(need > pad) {// some rank outgrew the padding: every rank sees it and repeats with the same larger length
 			g->pad = grp_pad_for(g, need);
 			continue;
 		}
 		if(grp_pad_close(g, need, pad)) g->pad = grp_pad_for(g, need);// grow ahead of time (takes effect at the next tagging)
-		GRP_TRY(mpm_halo_tag_begin(ctx));
-		for(int p = 0; p < g->world; ++p)
-			if(p != g->rank) GRP_TRY(mpm_halo_tag_peer(ctx, p, g->d_keys_all + 3 * ((size_t) pad * p + 1), heads[p]));
-		GRP_TRY(mpm_halo_tag_end(ctx, &g->n_halo_blocks, g->send_counts));
-		g->send_counts[g->rank] = 0;
+		g->n_halo_blocks = ctx->n_halo;
+		for(int p = 0; p < 32; ++p) g->send_counts[p] = p == g->rank ? 0 : ctx->send_count[p];
 		return MPM_OK;
 	}
 }
 
-// collect -> all-to-all-v -> reduce on the comm stream; the interior G2P2G (if any) is enqueued on the compute stream first
-// so that host time spent in the collective does not delay its launch (mgsp_benchmark.cuh:449-466, :723-776)
-int grp_exchange_halo(mpm_group* g, int gid, bool interior, float dt, float next_dt) {
-	mpm_ctx* ctx = g->ctx;
-	g->offs[0]	 = 0;
+// The halo exchange: collect -> all-to-all-v -> reduce, built from the helpers below in two orders.
+// Order matters for overlap.  The interior G2P2G fills every SIMD's register file with single-wave workgroups and refills
+// each slot a retiring wave frees at once, so a kernel that becomes ready while it runs - a 256-thread collect, RCCL's
+// send / receive workgroups - finds no room until it drains, whatever its stream priority (profiles/r02_mgsp_timeline.txt).
+// With early_exchange (RCCL transport) the collect therefore runs on the compute stream right behind the halo-first
+// G2P2G, and the grouped send / receive is enqueued on the high-priority comm stream BEFORE the interior G2P2G: both
+// become ready at the same event, on an empty GPU, and the transfer runs beside the interior blocks.  (The in-process
+// transport synchronises the host inside the exchange, so there the interior launch goes first and the collect runs on the
+// comm stream, so that host time spent in the collective does not delay the interior launch: mgsp_benchmark.cuh:449-466, :723-776.)
+// The windowed loop (mpm_group_run_fixed) splits the early order in two halves: grp_halo_compute_half, sized from device memory,
+// and grp_halo_comm_half, which needs the counts on the host.
+size_t grp_halo_offsets(mpm_group* g) {
+	g->offs[0] = 0;
 	for(int p = 0; p < g->world; ++p) g->offs[p + 1] = g->offs[p] + kHaloRow * (size_t) (p == g->rank ? 0 : g->send_counts[p]);
-	const size_t total = g->offs[g->world];
-	if(total > g->xcap) {
-		if(g->hub && g->hub->have_done)// (asynchronous in-process exchange: no peer may still be reading the buffer that is about to go)
-			for(int p = 0; p < g->world; ++p)
-				if(p != g->rank && g->hub->ev_done[p]) GRP_HIP(hipEventSynchronize(g->hub->ev_done[p]));
-		GRP_HIP(hipDeviceSynchronize());
-		hipFree(g->d_send);
-		hipFree(g->d_recv);
-		g->d_send = g->d_recv = nullptr;
-		g->xcap				  = total + total / 2 + kHaloRow;
-		GRP_HIP(hipMalloc((void**) &g->d_send, sizeof(float) * g->xcap));
-		GRP_HIP(hipMalloc((void**) &g->d_recv, sizeof(float) * g->xcap));
-	}
-	// Order matters for overlap.  The interior G2P2G fills every SIMD's register file with single-wave workgroups and refills
-	// each slot a retiring wave frees at once, so a kernel that becomes ready while it runs - a 256-thread collect, RCCL's
-	// send / receive workgroups - finds no room until it drains, whatever its stream priority (profiles/r02_mgsp_timeline.txt).
-	// With early_exchange (RCCL transport) the collect kernels therefore run on the compute stream right behind the halo-first
-	// G2P2G, and the grouped send / receive is enqueued on the high-priority comm stream BEFORE the interior G2P2G: both
-	// become ready at the same event, on an empty GPU, and the transfer runs beside the interior blocks.  (The in-process
-	// transport synchronises the host inside the exchange, so there the interior launch goes first.)
-	const bool early = g->early_exchange && interior;
-	if(g->hub && g->early_exchange && g->ev_sent && g->hub->have_done) {// (asynchronous in-process exchange: the peers may still be reading d_send)
-		for(int p = 0; p < g->world; ++p)
-			if(p != g->rank && g->hub->ev_done[p]) {
-				GRP_HIP(hipStreamWaitEvent(ctx->s_compute, g->hub->ev_done[p], 0));
-				GRP_HIP(hipStreamWaitEvent(ctx->s_comm, g->hub->ev_done[p], 0));
-			}
-	}
-	if(interior && !early) GRP_TRY(g2p2g_interior(ctx, dt, next_dt, g->ev_g1_override));
-	for(int p = 0; p < g->world; ++p) {
-		const int c = p == g->rank ? 0 : g->send_counts[p];
-		if(!c) continue;
-		float* base = g->d_send + g->offs[p];
-		int ns		= 0;
-		GRP_TRY(halo_collect_on(ctx, early ? ctx->s_compute : ctx->s_comm, p, gid, reinterpret_cast<int*>(base), base + 3 * (size_t) c, c, &ns));
-		if(ns != c) return gfail(g, MPM_ERR_INVALID, "halo send count changed between tagging and collection");
-	}
-	if(early) {
-		GRP_HIP(hipEventRecord(ctx->ev_halo, ctx->s_compute));
-		GRP_HIP(hipStreamWaitEvent(ctx->s_comm, ctx->ev_halo, 0));
-	}
-	if(g->world > 1) {
-		int rc = grp_exchange(g, g->d_send, g->d_recv, g->offs, ctx->s_comm);
-		if(rc) return rc;
-	}
-	if(early) GRP_TRY(g2p2g_interior(ctx, dt, next_dt, g->ev_g1_override));
-	bool any = false;
-	for(int p = 0; p < g->world; ++p) {
-		const int c = p == g->rank ? 0 : g->send_counts[p];
-		if(!c) continue;
-		const float* base = g->d_recv + g->offs[p];
-		GRP_TRY(mpm_halo_reduce(ctx, gid, reinterpret_cast<const int*>(base), base + 3 * (size_t) c, c));
-		any = true;
-	}
-	if(!any) GRP_TRY(mpm_halo_reduce(ctx, gid, nullptr, nullptr, 0));// nothing shared: still order the compute stream behind the comm stream
-	return MPM_OK;
+	return g->offs[g->world];
 }
-
-// The halo exchange of the windowed loop (RCCL ordering: early_exchange) in two halves.  Compute half: the collect of every peer's
-// blocks right behind the halo-first G2P2G and the interior G2P2G, all on the compute stream and all sized from DEVICE memory - it
-// can be enqueued while the read-back of the previous substep's counts is still outstanding.  Comm half (needs those counts on the
-// host): the grouped ncclSend / ncclRecv and the reduce on the comm stream, which waits for the collect's event; by then the interior
-// launch is running, the transfer goes on beside it.
 int grp_halo_capacity(mpm_group* g, size_t total) {
 	if(total <= g->xcap) return MPM_OK;
 	if(g->hub && g->hub->have_done)// (asynchronous in-process exchange: no peer may still be reading the buffer that is about to go)
@@ -467,53 +411,28 @@ int grp_halo_capacity(mpm_group* g, size_t total) {
 	GRP_HIP(hipMalloc((void**) &g->d_recv, sizeof(float) * g->xcap));
 	return MPM_OK;
 }
-size_t grp_halo_offsets(mpm_group* g) {
-	g->offs[0] = 0;
-	for(int p = 0; p < g->world; ++p) g->offs[p + 1] = g->offs[p] + kHaloRow * (size_t) (p == g->rank ? 0 : g->send_counts[p]);
-	return g->offs[g->world];
-}
-int grp_halo_compute_half(mpm_group* g, int gid, float dt, float next_dt, bool counts_known) {
-	mpm_ctx* ctx = g->ctx;
-	if(counts_known) {// (otherwise the buffer of the last exchange is used: the comm half checks it against the counts)
-		int rc = grp_halo_capacity(g, grp_halo_offsets(g));
-		if(rc) return rc;
-	}
-	if(g->hub && g->ev_sent && g->hub->have_done) {// (asynchronous in-process exchange: the peers may still be reading d_send)
-		for(int p = 0; p < g->world; ++p)
-			if(p != g->rank && g->hub->ev_done[p]) {
-				GRP_HIP(hipStreamWaitEvent(ctx->s_compute, g->hub->ev_done[p], 0));
-				GRP_HIP(hipStreamWaitEvent(ctx->s_comm, g->hub->ev_done[p], 0));
-			}
-	}
-	int est = 0;
-	for(int p = 0; p < g->world; ++p) est = std::max(est, p == g->rank ? 0 : g->send_counts[p]);
-	if(g->world > 1 && g->d_send) GRP_TRY(halo_collect_all_on(ctx, ctx->s_compute, gid, g->d_send, g->xcap, g->world, g->rank, est));
-	GRP_HIP(hipEventRecord(ctx->ev_halo, ctx->s_compute));
-	GRP_TRY(g2p2g_interior(ctx, dt, next_dt, g->ev_g1_override, counts_known));
+// asynchronous in-process exchange: the peers may still be reading d_send
+int grp_wait_peers_done(mpm_group* g) {
+	if(!(g->hub && g->ev_sent && g->hub->have_done)) return MPM_OK;
+	for(int p = 0; p < g->world; ++p)
+		if(p != g->rank && g->hub->ev_done[p]) {
+			GRP_HIP(hipStreamWaitEvent(g->ctx->s_compute, g->hub->ev_done[p], 0));
+			GRP_HIP(hipStreamWaitEvent(g->ctx->s_comm, g->hub->ev_done[p], 0));
+		}
 	return MPM_OK;
 }
-int grp_halo_comm_half(mpm_group* g, int gid, bool collect_again = false) {
-	mpm_ctx* ctx	   = g->ctx;
-	const size_t total = grp_halo_offsets(g);
-	if(total > g->xcap || collect_again) {// the counts outgrew the buffer the collect ran into (grow it), or the send lists were rebuilt after it ran: collect again (behind the interior launch, this once)
-		int rc = grp_halo_capacity(g, total);
-		if(rc) return rc;
-		for(int p = 0; p < g->world; ++p) {
-			const int c = p == g->rank ? 0 : g->send_counts[p];
-			if(!c) continue;
-			float* base = g->d_send + g->offs[p];
-			int ns		= 0;
-			GRP_TRY(halo_collect_on(ctx, ctx->s_compute, p, gid, reinterpret_cast<int*>(base), base + 3 * (size_t) c, c, &ns));
-			if(ns != c) return gfail(g, MPM_ERR_INVALID, "halo send count changed between tagging and collection");
-		}
-		GRP_HIP(hipEventRecord(ctx->ev_halo, ctx->s_compute));
-	}
-	GRP_HIP(hipStreamWaitEvent(ctx->s_comm, ctx->ev_halo, 0));
-	if(g->world > 1) {
-		int rc = grp_exchange(g, g->d_send, g->d_recv, g->offs, ctx->s_comm);
-		if(rc) return rc;
-	}
-	bool any = false;
+// every peer's blocks into d_send, in one launch on stream s (sizes from device memory); counts_known: g->send_counts are those of the
+// last tagging (otherwise one tagging old: they only size the launch)
+int grp_collect(mpm_group* g, int gid, hipStream_t s, bool counts_known = true) {
+	int est = 0;
+	for(int p = 0; p < g->world; ++p) est = std::max(est, p == g->rank ? 0 : g->send_counts[p]);
+	if(g->world > 1 && g->d_send && (est > 0 || !counts_known)) GRP_TRY(halo_collect(g->ctx, s, gid, 0, g->world, g->rank, est, g->d_send, g->xcap));
+	return MPM_OK;
+}
+// the received blocks into grid gid (comm stream); the compute stream waits for them
+int grp_reduce(mpm_group* g, int gid) {
+	mpm_ctx* ctx = g->ctx;
+	bool any	 = false;
 	for(int p = 0; p < g->world; ++p) {
 		const int c = p == g->rank ? 0 : g->send_counts[p];
 		if(!c) continue;
@@ -524,6 +443,49 @@ int grp_halo_comm_half(mpm_group* g, int gid, bool collect_again = false) {
 	if(!any) GRP_TRY(mpm_halo_reduce(ctx, gid, nullptr, nullptr, 0));// nothing shared: still order the compute stream behind the comm stream
 	return MPM_OK;
 }
+int grp_send_recv(mpm_group* g) {
+	return g->world > 1 ? grp_exchange(g, g->d_send, g->d_recv, g->offs, g->ctx->s_comm) : MPM_OK;
+}
+// interior: the interior G2P2G of this substep is enqueued too (ev.g2p2g_end marks its end)
+int grp_exchange_halo(mpm_group* g, int gid, bool interior, float dt, float next_dt, const SubstepEvents& ev) {
+	mpm_ctx* ctx	 = g->ctx;
+	const bool early = g->early_exchange && interior;
+	int rc			 = grp_halo_capacity(g, grp_halo_offsets(g));
+	if(rc || (rc = grp_wait_peers_done(g))) return rc;
+	if(interior && !early) GRP_TRY(g2p2g_interior(ctx, dt, next_dt, ev));
+	if((rc = grp_collect(g, gid, early ? ctx->s_compute : ctx->s_comm))) return rc;
+	if(early) {
+		GRP_HIP(hipEventRecord(ctx->ev_halo, ctx->s_compute));
+		GRP_HIP(hipStreamWaitEvent(ctx->s_comm, ctx->ev_halo, 0));
+	}
+	if((rc = grp_send_recv(g))) return rc;
+	if(early) GRP_TRY(g2p2g_interior(ctx, dt, next_dt, ev));
+	return grp_reduce(g, gid);
+}
+// Compute half: the collect right behind the halo-first G2P2G, then the interior G2P2G, all on the compute stream - it can be enqueued
+// while the read-back of the previous substep's counts is still outstanding.
+int grp_halo_compute_half(mpm_group* g, int gid, float dt, float next_dt, bool counts_known, const SubstepEvents& ev) {
+	mpm_ctx* ctx = g->ctx;
+	int rc		 = counts_known ? grp_halo_capacity(g, grp_halo_offsets(g)) : MPM_OK;// (otherwise the buffer of the last exchange is used: the comm half checks it against the counts)
+	if(rc || (rc = grp_wait_peers_done(g)) || (rc = grp_collect(g, gid, ctx->s_compute, counts_known))) return rc;
+	GRP_HIP(hipEventRecord(ctx->ev_halo, ctx->s_compute));
+	GRP_TRY(g2p2g_interior(ctx, dt, next_dt, ev, counts_known));
+	return MPM_OK;
+}
+// Comm half (needs the counts on the host): the grouped send / receive and the reduce on the comm stream, which waits for the collect's
+// event; by then the interior launch is running, the transfer goes on beside it.
+int grp_halo_comm_half(mpm_group* g, int gid, bool collect_again = false) {
+	mpm_ctx* ctx	   = g->ctx;
+	const size_t total = grp_halo_offsets(g);
+	if(total > g->xcap || collect_again) {// the counts outgrew the buffer the collect ran into (grow it), or the send lists were rebuilt after it ran: collect again (behind the interior launch, this once)
+		int rc = grp_halo_capacity(g, total);
+		if(rc || (rc = grp_collect(g, gid, ctx->s_compute))) return rc;
+		GRP_HIP(hipEventRecord(ctx->ev_halo, ctx->s_compute));
+	}
+	GRP_HIP(hipStreamWaitEvent(ctx->s_comm, ctx->ev_halo, 0));
+	int rc = grp_send_recv(g);
+	return rc ? rc : grp_reduce(g, gid);
+}
 
 int grp_common_init(mpm_group* g) {
 	g->ctx->group_refs++;// (undone by mpm_group_destroy, which every failure below leads to)
@@ -532,6 +494,8 @@ int grp_common_init(mpm_group* g) {
 	if(const char* e = getenv("MPM_GROUP_OVERLAP_TAG")) g->overlap_tag = e[0] != '0';
 	GRP_HIP(hipSetDevice(g->ctx->device));
 	GRP_HIP(hipMalloc((void**) &g->d_scalar, sizeof(float)));
+	for(SubstepEvents& ev: g->ev2)
+		for(hipEvent_t* e: {&ev.start, &ev.g2p2g_start, &ev.g2p2g_end, &ev.end}) GRP_HIP(hipEventCreate(e));
 	if(g->hub && g->early_exchange) {
 		GRP_HIP(hipEventCreateWithFlags(&g->ev_sent, hipEventDisableTiming));
 		GRP_HIP(hipEventCreateWithFlags(&g->ev_done, hipEventDisableTiming));
@@ -671,6 +635,9 @@ void mpm_group_destroy(mpm_group* g) {
 	if(g->ev_done) hipEventDestroy(g->ev_done);
 	if(g->ev_keys) hipEventDestroy(g->ev_keys);
 	if(g->ev_kdone) hipEventDestroy(g->ev_kdone);
+	for(const SubstepEvents& ev: g->ev2)
+		for(hipEvent_t e: {ev.start, ev.g2p2g_start, ev.g2p2g_end, ev.end})
+			if(e) hipEventDestroy(e);
 	delete g;
 }
 
@@ -690,7 +657,7 @@ int mpm_group_initial_setup(mpm_group* g) {
 	GRP_TRY(mpm_initial_setup(g->ctx));
 	int rc = grp_tag(g);
 	if(rc) return rc;
-	rc = grp_exchange_halo(g, 0, false, 0.f, 0.f);
+	rc = grp_exchange_halo(g, 0, false, 0.f, 0.f, g->ctx->ev);
 	if(rc) return rc;
 	GRP_TRY(mpm_sync(g->ctx));
 	g->ctx->group_summed = true;
@@ -722,22 +689,15 @@ int mpm_group_resume(mpm_group* g) {
 // The enqueue half (everything up to the status read-back) and the wait half are separate: mpm_group_run_fixed puts the next
 // substep's grid update and halo-first G2P2G between them.
 namespace {
-// par: 0 / 1 = the set of timing events this substep uses (the windowed loop alternates: a substep's events are read after the next
-// substep's first half has been enqueued), -1 = the context's single set.  device_sized: a status read-back is still outstanding, the
-// halo-first launch takes its block count from device memory.
-hipEvent_t grp_ev(mpm_ctx* ctx, hipEvent_t (&two)[2], int par) {
-	return par < 0 ? nullptr : two[par];
-}
-int grp_substep_begin(mpm_group* g, float dt, float next_dt, bool device_sized, int par) {
-	mpm_ctx* ctx = g->ctx;
-	if(par >= 0)
-		for(hipEvent_t* e: {&ctx->ev2_a[par], &ctx->ev2_b[par], &ctx->ev2_g0[par], &ctx->ev2_g1[par]})
-			if(!*e) GRP_HIP(hipEventCreate(e));
-	GRP_TRY(mgsp_begin(ctx, dt, next_dt, device_sized, grp_ev(ctx, ctx->ev2_a, par), grp_ev(ctx, ctx->ev2_g0, par)));
+// ev: the timing events this substep records (the windowed loop alternates two sets: a substep's events are read after the next
+// substep's first half has been enqueued).  device_sized: a status read-back is still outstanding, the halo-first launch takes its
+// block count from device memory.
+int grp_substep_begin(mpm_group* g, float dt, float next_dt, bool device_sized, const SubstepEvents& ev) {
+	GRP_TRY(mgsp_begin(g->ctx, dt, next_dt, device_sized, ev));
 	return MPM_OK;
 }
 // everything of a substep behind the halo exchange: rebuild, key export, all-gather, tagging, the status read-back
-int grp_substep_tail(mpm_group* g, int par) {
+int grp_substep_tail(mpm_group* g, const SubstepEvents& ev) {
 	mpm_ctx* ctx  = g->ctx;
 	const int pad = g->pad;
 	int rc		  = grp_key_buffers(g);
@@ -759,38 +719,31 @@ int grp_substep_tail(mpm_group* g, int par) {
 		GRP_TRY(launch_rebuild_prepare(ctx));
 		rc = grp_all_gather(g, g->d_keys_mine, g->d_keys_all, 3 * (size_t) pad, ctx->s_comm);
 		if(rc) return rc;
-		GRP_TRY(mgsp_tag(ctx, g->d_keys_all, pad, g->world, g->rank, nullptr, ctx->s_comm));
+		GRP_TRY(mgsp_tag(ctx, g->d_keys_all, pad, g->world, g->rank, ev, ctx->s_comm));
 		GRP_HIP(hipEventRecord(ctx->ev_tag1, ctx->s_comm));
 		GRP_HIP(hipStreamWaitEvent(ctx->s_compute, ctx->ev_tag1, 0));
-		hipEvent_t evb = grp_ev(ctx, ctx->ev2_b, par);
-		GRP_HIP(hipEventRecord(evb ? evb : ctx->ev_b, ctx->s_compute));
+		GRP_HIP(hipEventRecord(ev.end, ctx->s_compute));
 	} else {
 		GRP_TRY(mpm_mgsp_rebuild_export(ctx, g->d_keys_mine, pad));
 		rc = grp_all_gather(g, g->d_keys_mine, g->d_keys_all, 3 * (size_t) pad, ctx->s_compute);
 		if(rc) return rc;
-		GRP_TRY(mgsp_tag(ctx, g->d_keys_all, pad, g->world, g->rank, grp_ev(ctx, ctx->ev2_b, par)));
+		GRP_TRY(mgsp_tag(ctx, g->d_keys_all, pad, g->world, g->rank, ev));
 	}
-	GRP_TRY(mgsp_end_enqueue(ctx, ctx->lean_events ? grp_ev(ctx, ctx->ev2_b, par) : nullptr));
+	GRP_TRY(mgsp_end_enqueue(ctx, ev));
 	g->pad_enqueued = pad;
 	return MPM_OK;
 }
-int grp_substep_enqueue(mpm_group* g, float dt, float next_dt, int par) {
-	mpm_ctx* ctx	  = g->ctx;
-	g->ev_g1_override = grp_ev(ctx, ctx->ev2_g1, par);
-	int rc			  = grp_exchange_halo(g, 1, true, dt, next_dt);
-	g->ev_g1_override = nullptr;
-	if(rc) return rc;
-	return grp_substep_tail(g, par);
+int grp_substep_enqueue(mpm_group* g, float dt, float next_dt, const SubstepEvents& ev) {
+	int rc = grp_exchange_halo(g, 1, true, dt, next_dt, ev);
+	return rc ? rc : grp_substep_tail(g, ev);
 }
-// takes over the counts of the substep whose read-back is outstanding; truncated: a key list outgrew the padding it was exported with
-int grp_substep_wait(mpm_group* g, int par, float* max_vel_sqr, bool* truncated) {
+// takes over the counts of the substep whose read-back is outstanding (timed from ev.start); truncated: a key list outgrew the padding it
+// was exported with
+int grp_substep_wait(mpm_group* g, const SubstepEvents& ev, float* max_vel_sqr, bool* truncated) {
 	mpm_ctx* ctx = g->ctx;
 	int mx		 = 0;
 	float mv	 = 0.f;
-	// (lean events: no start event - a substep is timed from the end of the one before it, the first of a run from its G2P2G start)
-	hipEvent_t ev_start = !ctx->lean_events ? grp_ev(ctx, ctx->ev2_a, par) : (g->lean_prev_end ? grp_ev(ctx, ctx->ev2_b, par ^ 1) : grp_ev(ctx, ctx->ev2_g0, par));
-	g->lean_prev_end	= ctx->lean_events;
-	GRP_TRY(mgsp_end_wait(ctx, g->rank, g->send_counts, &g->n_halo_blocks, &mx, &mv, ev_start, grp_ev(ctx, ctx->ev2_b, par), grp_ev(ctx, ctx->ev2_g0, par), grp_ev(ctx, ctx->ev2_g1, par)));
+	GRP_TRY(mgsp_end_wait(ctx, g->rank, g->send_counts, &g->n_halo_blocks, &mx, &mv, ev));
 	g->send_counts[g->rank] = 0;
 	if(max_vel_sqr) *max_vel_sqr = mv;
 	g->g2p2g_ms_sum += ctx->last_g2p2g_ms;
@@ -805,12 +758,13 @@ int grp_substep_wait(mpm_group* g, int par, float* max_vel_sqr, bool* truncated)
 int mpm_group_substep(mpm_group* g, float dt, float next_dt, float* max_vel_sqr) {
 	if(!g || !g->ctx) return MPM_ERR_INVALID;
 	g->ctx->group_summed = false;
-	int rc = grp_substep_begin(g, dt, next_dt, false, -1);
+	const SubstepEvents& ev = g->ctx->ev;
+	int rc					= grp_substep_begin(g, dt, next_dt, false, ev);
 	if(rc) return rc;
-	rc = grp_substep_enqueue(g, dt, next_dt, -1);
+	rc = grp_substep_enqueue(g, dt, next_dt, ev);
 	if(rc) return rc;
 	bool truncated = false;
-	rc			   = grp_substep_wait(g, -1, max_vel_sqr, &truncated);
+	rc			   = grp_substep_wait(g, ev, max_vel_sqr, &truncated);
 	if(rc) return rc;
 	if(truncated) {// a key list was truncated (same verdict on every rank): tag again with the larger padding
 		g->retags++;
@@ -831,6 +785,7 @@ int mpm_group_run_fixed(mpm_group* g, int nsteps, float dt) {
 	ctx->group_summed = false;
 	bool pending = false;// the read-back of the previous substep is outstanding
 	bool retagged = false;// the wait half had to repeat the last tagging (a key list outgrew its padding)
+	bool lean_prev_end = false;// (lean events) the previous substep of this run recorded its end event: the next one is timed from it
 	auto bail = [&](int rc) {// an interrupted run leaves no promise about the grid behind
 		ctx->fuse_dt_once = 0.f, ctx->grid_preupdated = false, ctx->rebuild_cleared = false;
 		if(pending) hipEventSynchronize(ctx->ev_pending ? ctx->ev_pending : ctx->ev_status);
@@ -838,9 +793,13 @@ int mpm_group_run_fixed(mpm_group* g, int nsteps, float dt) {
 		return rc;
 	};
 	auto finish = [&](int par, bool may_retag) {// the wait half of a substep
+		// (lean events: no start event - a substep is timed from the end of the one before it, the first of a run from its G2P2G start)
+		SubstepEvents ev = g->ev2[par];
+		if(ctx->lean_events) ev.start = lean_prev_end ? g->ev2[par ^ 1].end : ev.g2p2g_start;
+		lean_prev_end  = ctx->lean_events;
 		float mv	   = 0.f;
 		bool truncated = false;
-		int rc		   = grp_substep_wait(g, par, &mv, &truncated);
+		int rc		   = grp_substep_wait(g, ev, &mv, &truncated);
 		pending		   = false;
 		if(rc == MPM_OK && (std::isinf(mv) || std::isnan(mv))) rc = gfail(g, MPM_ERR_NONFINITE, "Maximum velocity is infinity");
 		if(rc == MPM_OK && truncated) {
@@ -861,24 +820,21 @@ int mpm_group_run_fixed(mpm_group* g, int nsteps, float dt) {
 	// in-process transport's default (interior first, host synchronisations inside the exchange) keeps one wait per substep.
 	const bool defer = !g->no_defer && g->early_exchange;
 	ctx->lean_events = defer && !g->overlap_tag;// (the deferred order records the halo event itself; the overlapped tagging keeps its own end event)
-	g->lean_prev_end = false;
 	for(int i = 0; i < nsteps; ++i) {
 		const int par = i & 1;
 		// the next substep's dt is known: its grid update rides on this substep's carry-over (carry_grid_kernel<true>, which writes the
 		// max |v|^2 slots: this substep's clear resets them); the last substep of the call leaves the canonical state behind
 		if(i + 1 < nsteps) ctx->fuse_dt_once = dt;
-		int rc = grp_substep_begin(g, dt, dt, pending, par);// (its own grid update rode on the previous substep's carry-over)
+		const SubstepEvents& ev = g->ev2[par];
+		int rc					= grp_substep_begin(g, dt, dt, pending, ev);// (its own grid update rode on the previous substep's carry-over)
 		if(rc) return bail(rc);
 		if(defer) {
-			g->ev_g1_override = grp_ev(ctx, ctx->ev2_g1, par);
-			rc				  = grp_halo_compute_half(g, 1, dt, dt, !pending);
-			g->ev_g1_override = nullptr;
-			if(rc) return bail(rc);
+			if((rc = grp_halo_compute_half(g, 1, dt, dt, !pending, ev))) return bail(rc);
 			retagged = false;
 			if(pending && (rc = finish(par ^ 1, false))) return bail(rc);// the GPU is busy with the interior launch while the host looks at the counts
-			if((rc = grp_halo_comm_half(g, 1, retagged)) || (rc = grp_substep_tail(g, par))) return bail(rc);
+			if((rc = grp_halo_comm_half(g, 1, retagged)) || (rc = grp_substep_tail(g, ev))) return bail(rc);
 		} else {
-			if((rc = grp_substep_enqueue(g, dt, dt, par))) return bail(rc);
+			if((rc = grp_substep_enqueue(g, dt, dt, ev))) return bail(rc);
 		}
 		pending = true;
 		if((!defer || i + 1 == nsteps) && (rc = finish(par, true))) return bail(rc);
@@ -931,7 +887,7 @@ int mpm_group_main_loop(mpm_group* g, int frames, int fps, float dt_default, voi
 			next_dt = mpm_group_compute_dt(g, std::sqrt(mv2), cur_time + dt, next_time, dt_default);
 			if(!(next_dt > 0.f)) next_dt = mpm_group_compute_dt(g, std::sqrt(mv2), 0.f, seconds_pf, dt_default);// first dt of the next frame
 			GRP_TRY(mpm_g2p2g_halo(ctx, dt, next_dt));
-			rc = grp_exchange_halo(g, 1, true, dt, next_dt);
+			rc = grp_exchange_halo(g, 1, true, dt, next_dt, ctx->ev);
 			if(rc) return rc;
 			GRP_TRY(mpm_rebuild_partition(ctx, nullptr));
 			rc = grp_tag(g);

@@ -417,7 +417,7 @@ __global__ __launch_bounds__(64) void prepare_blocks_kernel(GridCfg cfg, Prepare
 	__shared__ int s_cnt[256];// per key (216 used): count, then first position of the key in key-major order
 	__shared__ int s_cur[256];// (pair layout, merged last chunk: the running rank of a key's records in the second pass)
 	const int lane = threadIdx.x;
-	// (MPM_GROUP_OVERLAP_TAG=1 runs the tagging kernels - halo_mark_all / halo_split_dev - on the comm stream BESIDE this kernel: they read
+	// (MPM_GROUP_OVERLAP_TAG=1 runs the tagging kernels - halo_mark / halo_split - on the comm stream BESIDE this kernel: they read
 	//  ST_NBC / ST_PBC only and must never read what is published here, ST_EBC and *part_count)
 	if(publish && blockIdx.x == 0 && lane == 0) {
 		const int ebc	 = publish[ST_CNT_P] + publish[ST_CNT_N] + publish[ST_CNT_E];

@@ -35,13 +35,13 @@ defs, uses, succ = [set() for _ in range(n)], [set() for _ in range(n)], [[] for
 for i, (ln, t) in enumerate(ins):
     op, _, rest = t.partition(" ")
     ops = [o.strip() for o in rest.split(",")] if rest else []
-    is_store = op.startswith(("global_store", "scratch_store", "ds_write", "buffer_store", "global_atomic", "ds_add", "ds_max")) and "rtn" not in op and not (op.startswith("global_atomic") and "glc" in t or "sc0" in t and op.startswith("global_atomic"))
+    writes = op.startswith(("global_store", "scratch_store", "ds_write", "buffer_store", "global_atomic", "ds_add", "ds_max")) and "rtn" not in op and not (op.startswith("global_atomic") and "glc" in t or "sc0" in t and op.startswith("global_atomic"))
     nd = 0
-    if op.startswith("v_") or op.startswith(("global_load", "scratch_load", "ds_read", "buffer_load", "ds_bpermute", "ds_swizzle")) or (op.startswith("global_atomic") and not is_store) or op.startswith("ds_add_rtn") or op.startswith("ds_append") or op.startswith("ds_consume"):
+    if op.startswith("v_") or op.startswith(("global_load", "scratch_load", "ds_read", "buffer_load", "ds_bpermute", "ds_swizzle")) or (op.startswith("global_atomic") and not writes) or op.startswith("ds_add_rtn") or op.startswith("ds_append") or op.startswith("ds_consume"):
         nd = 1
         if op.startswith("v_cmp") or op.startswith("v_readlane") or op.startswith("v_readfirstlane"):
             nd = 0
-    if is_store:
+    if writes:
         nd = 0
     for k, o in enumerate(ops):
         r = regs(o)

@@ -12,9 +12,13 @@ the one C3 column cut into N equal-count slabs along its longest axis.  `--scali
 columns on the same grid, one per rank, N x 40.1 M particles).  Inputs are resident in HBM before the timed region;
 value = particles of all ranks * K / time.
 
+A plain run does only what the headline needs: it sets up, warms up, times the K substeps, checks them, writes --dump-outputs
+if asked and prints the JSON line.  `--full` also measures what takes runs of its own: the flow and deep windows of the default
+run (roofline below) and the CPU baseline.
+
 Extra objects on the JSON line:
   roofline     - G2P2G (the dominant kernel): algorithmic bytes per launch (144 B/particle
-                 for sand) / average kernel duration from HIP events on the engine's compute stream, vs 8 TB/s.  For the default
+                 for sand) / average kernel duration from HIP events on the engine's compute stream, vs 8 TB/s.  For a --full
                  run (N = 1, C3) the HEADLINE roofline.frac is that of a second window INSIDE THE FLOW (20 substeps after
                  --flow-start: the column is collapsing - block churn, plastic return mapping, three Jacobi sweeps); the timed K
                  substeps themselves (the column in free fall, the kernel's cheapest regime) are roofline.rest.  `traffic` and
@@ -24,7 +28,7 @@ Extra objects on the JSON line:
                  NOTE: `value` and `ms_per_step` are ALWAYS the timed K substeps; when `headline_window` is "flow", roofline.frac /
                  kernel_ms describe ANOTHER window of the same run - the pair that belongs to `value` is roofline.rest
                  (roofline.timed_frac repeats its fraction); roofline.deep is a third window after --deep-start substeps (default 9000: deep in the collapse)
-  cpu_baseline - the CPU oracle ("port" of the reference pipeline) timed on this host on the same input, outside the timed
+  cpu_baseline - --full only: the CPU oracle ("port" of the reference pipeline) timed on this host on the same input, outside the timed
                  region (rank 0, N = 1 only): OpenMP over G2P2G's particle blocks, the grid update and the rebuild's
                  order-independent loops; `cores` = the threads it ran on
 """
@@ -246,7 +250,10 @@ def main():
                     help="untimed substeps before the warm-up: moves the timed window into the flow (the default window of C3 "
                          "starts at rest; after ~3000 substeps the column is collapsing: block churn, mispredicted sort keys)")
     ap.add_argument("--fraction", type=float, default=1.0, help="debug: shrink the sand column")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the flow and deep windows of the default run (roofline) "
+                         "and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--mgsp", action="store_true", help="debug: drive the multi-GPU code path even with one rank")
     ap.add_argument("--max-ppc", type=int, default=0, help="debug: override the scene's particles-per-cell capacity (reference: 128)")
     ap.add_argument("--scaling", default="strong", choices=["weak", "strong"],
@@ -258,11 +265,12 @@ def main():
                     help="--gpus N > 1, strong scaling: cut the column into exactly equal particle counts instead of moving the cut planes to the nearest "
                          "particle-block faces (default: block-aligned pieces within 10 %% of the equal share - no block is shared by two ranks at the start: "
                          "C3 cut 8 ways along y is 10 890 instead of 11 979 particle blocks on the largest rank)")
-    ap.add_argument("--flow-start", type=int, default=3000,
-                    help="N = 1, default scene: after the timed window the run goes on to this substep and a second short window is timed "
-                         "inside the flow (reported as roofline.flow; 0 = skip)")
-    ap.add_argument("--deep-start", type=int, default=9000,
-                    help="default run (N = 1, C3): a third 20-substep window after this many substeps, deep in the collapse -> roofline.deep (0 = skip; adds ~15 s)")
+    ap.add_argument("--flow-start", type=int, default=None,
+                    help="--full, N = 1, default scene: after the timed window the run goes on to this substep (default 3000) and a second short "
+                         "window is timed inside the flow (reported as roofline.flow; 0 = skip)")
+    ap.add_argument("--deep-start", type=int, default=None,
+                    help="--full, default scene (N = 1, C3): a third 20-substep window after this many substeps (default 9000), deep in the collapse "
+                         "-> roofline.deep (0 = skip; adds ~15 s)")
     ap.add_argument("--sync-interval", type=int, default=0, help="debug: mpm_config.sync_interval (0 = library default)")
     ap.add_argument("--oversubscribe", action="store_true",
                     help="debug: rank r uses device r %% (devices present) instead of device LOCAL_RANK - several ranks per GPU.  RCCL refuses "
@@ -281,6 +289,10 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full and (args.flow_start or args.deep_start):
+        ap.error("--flow-start and --deep-start place windows that only a --full run times: add --full")
+    args.flow_start = 3000 if args.flow_start is None else args.flow_start
+    args.deep_start = 9000 if args.deep_start is None else args.deep_start
 
     # stdout carries exactly one line, the JSON record: libraries that print banners there (gloo's "connected to N peer ranks",
     # RCCL's version block) are sent to stderr for the duration of the run
@@ -409,7 +421,7 @@ def main():
             write_outputs(args.dump_outputs, canonical_sample(st, keep, DUMP_SEED), totals)
         flow = None
         done = args.start_step + args.warmup + args.steps
-        if args.scene == "sand40m" and args.fraction >= 1.0 and not args.start_step and args.flow_start > done:
+        if args.full and args.scene == "sand40m" and args.fraction >= 1.0 and not args.start_step and args.flow_start > done:
             # second window, inside the flow: the column is collapsing (block churn, mispredicted sort keys, plastic return mapping)
             eng.run_fixed(args.flow_start - done, dt)
             eng.run_fixed(5, dt)
@@ -573,7 +585,7 @@ def main():
             sys.stdout.flush()
             os.write(json_fd, (json.dumps(out) + "\n").encode())
 
-        if world == 1 and not args.no_cpu_baseline and not args.mgsp:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.mgsp:
             # The GPU measurement is complete: from here on nothing may lose it.  The baseline runs in a worker with its own time limit; the
             # watchdog is disarmed (it guards the GPU part: a rank stuck in a collective).
             stage["at"] = "cpu baseline (oracle on the host cores)"

@@ -1,6 +1,7 @@
 #!/usr/bin/env bash
 # round 6, LAST call: everything profiles/r06_* holds, re-taken on the shipped library in one go ("re-take the proxies last").
-# Outputs: gpurun_out/ (profile set, bench line: tools/gpu_final_r06.sh) and gpurun_out/retake/ (proxies, long runs, probes), each headed by build_stamp.txt
+# Outputs: the profile set and the bench line (tools/gpu_final_r06.sh; the bench line in place, profiles/r06_bench_default_line.json) and, under $O,
+# the proxies, long runs and probes, each headed by build_stamp.txt
 cd "$(dirname "$0")/.."
 R=$PWD
 O=$R/gpurun_out/retake

@@ -59,7 +59,7 @@ open(os.path.join(P, "r06_mgsp_partition.txt"), "w").write("\n".join(out).rstrip
 
 # ---- the deep window
 deep = json.loads(open(os.path.join(G, "prof_r06", "c3_deep_bench.json")).read().strip().split("\n")[-1])
-line = json.loads(open(os.path.join(G, "r06_bench_default_line.json")).read().strip().split("\n")[-1])
+line = json.loads(open(os.path.join(P, "r06_bench_default_line.json")).read().strip().split("\n")[-1])
 rd, rl = deep["roofline"], line["roofline"]["deep"]
 txt = [
     f"# {stamp}: the window deep in the collapse (VERDICT r5 #2: a third window at step 9000); also roofline.deep of the default bench line (profiles/r06_bench_default_line.json); written by tools/summarise_retake_r06.py",

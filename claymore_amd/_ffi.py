@@ -105,6 +105,8 @@ HIP_ONLY = {
     "get_diagnostics": (_i, [_vp, _P(Diagnostics)]),
     "retrieve_velocity": (_i, [_vp, _i, _vp, _vp, _vp, _P(_sz)]),
     "particle_momentum": (_i, [_vp, _i, _P(C.c_double)]),
+    "set_collision_clock": (_i, [_vp, _i, _f]),
+    "get_collision_time": (_i, [_vp, _fp, _ip]),
     "checkpoint_size": (_i, [_vp, _P(_sz)]),
     "checkpoint_save": (_i, [_vp, _vp, _sz, _P(_sz)]),
     "checkpoint_load": (_i, [_vp, _vp, _sz]),

@@ -107,7 +107,8 @@ struct mpm_ctx {
 	int capacity_events = 0;// number of capacity growths so far (check_capacity)
 	long long books_bias = 0;// check_books: particles a loaded checkpoint's state lacked beyond this context's own lost / dropped counters
 	bool has_collision = false;// level-set collision object of the MGSP grid update
-	CollisionObject collision {};
+	CollisionObject collision {};// (collision.time is the clock: the time of the next grid update)
+	bool collision_running = false;// the clock advances by dt with every grid update (mpm_set_collision_clock)
 	float4* d_sdf = nullptr;
 	mpm_timers timers {};
 	float last_g2p2g_ms = 0.f;
@@ -600,6 +601,15 @@ int mpm_initial_setup(mpm_ctx* ctx) {
 	return MPM_OK;
 }
 
+// The collision object as the grid update that is being enqueued sees it: the pose at the current time T (the start of the substep), by
+// value; a running clock then moves on, T = T + dt in one float32 addition (the drivers' own cur_time += dt).  Called once per
+// applied grid update - by the stand-alone kernel's launch or by the fused carry-over's, never by both.
+static CollisionArgs collision_tick(mpm_ctx* ctx, float dt) {
+	CollisionArgs a {ctx->collision, collision_pose(ctx->collision, ctx->collision.time)};
+	if(ctx->collision_running) ctx->collision.time = ctx->collision.time + dt;
+	return a;
+}
+
 // grid-update phase, gmpm_simulator.cuh:326-347
 static int launch_grid_update(mpm_ctx* ctx, float dt) {
 	hipStream_t s = ctx->s_compute;
@@ -607,13 +617,13 @@ static int launch_grid_update(mpm_ctx* ctx, float dt) {
 	if(ctx->grid_preupdated) {
 		ctx->grid_preupdated = false;
 		if(dt != ctx->preupdate_dt) return fail(ctx, MPM_ERR_INVALID, "grid was updated for another dt");
-		return MPM_OK;
+		return MPM_OK;// (the carry-over that applied this update has advanced the object's clock)
 	}
 	HIP_TRY(hipMemsetAsync(ctx->d_maxvel, 0, sizeof(unsigned) * kMaxVelSlots * kMaxVelStride, s));
 	if(ctx->nbc) {
 		const int est = std::min(ctx->g.cap, ctx->nbc + ctx->nbc / 16 + 64);// (an estimate between two synchronisations of mpm_run_fixed)
 		if(ctx->has_collision)
-			grid_update_collision_kernel<<<cdiv(est, 4), 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, ctx->collision, ctx->d_maxvel);
+			grid_update_collision_kernel<<<cdiv(est, 4), 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, collision_tick(ctx, dt), ctx->d_maxvel);
 		else
 			grid_update_kernel<<<cdiv(est, 16), 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, ctx->d_maxvel);
 	}
@@ -818,7 +828,7 @@ static int launch_rebuild(mpm_ctx* ctx, float fuse_dt = 0.f, bool without_prepar
 	const int r = ctx->rollid, n = r ^ 1;
 	Partition& Pn = ctx->part[n];
 	Partition& Pr = ctx->part[r];
-	const bool fused = fuse_dt > 0.f && !ctx->has_collision;
+	const bool fused = fuse_dt > 0.f;
 	ctx->grid_momentum = !fused;// the carry-over below writes grid[0]: the P2G's mass and momentum, or (fused) the updated velocities
 	int rc			 = launch_clear(ctx, kClearRebuild | (fused ? kClearMaxVel : 0));// un-insert the old keys of Pn (reset_table, hash_table.cuh:110-112), counters, totals
 	if(rc) return rc;
@@ -838,11 +848,14 @@ static int launch_rebuild(mpm_ctx* ctx, float fuse_dt = 0.f, bool without_prepar
 	const unsigned rg8 = std::max(1u, std::min(4096u, cdiv((size_t) ebc_est * 8, 256))), rg32 = std::max(1u, std::min(8192u, cdiv((size_t) ebc_est * 32, 256)));
 	register_blocks_kernel<0, 1><<<rg8, 256, 0, s>>>(g, &st[ST_CNT_P], nullptr, &st[ST_CNT_N], &st[ST_PBC], Pn.table, Pn.keys, st);
 	if(fused) {
-		carry_grid_kernel<true><<<2048, 256, 0, s>>>(g, st, Pn.keys, Pr.table, ctx->grid[1], ctx->grid[0], fuse_dt, ctx->d_maxvel);
+		if(ctx->has_collision)
+			carry_grid_kernel<true, true><<<2048, 256, 0, s>>>(g, st, Pn.keys, Pr.table, ctx->grid[1], ctx->grid[0], fuse_dt, ctx->d_maxvel, collision_tick(ctx, fuse_dt));
+		else
+			carry_grid_kernel<true><<<2048, 256, 0, s>>>(g, st, Pn.keys, Pr.table, ctx->grid[1], ctx->grid[0], fuse_dt, ctx->d_maxvel, NoCollision {});
 		ctx->grid_preupdated = true;
 		ctx->preupdate_dt	 = fuse_dt;
 	} else
-		carry_grid_kernel<false><<<2048, 256, 0, s>>>(g, st, Pn.keys, Pr.table, ctx->grid[1], ctx->grid[0], 0.f, nullptr);
+		carry_grid_kernel<false><<<2048, 256, 0, s>>>(g, st, Pn.keys, Pr.table, ctx->grid[1], ctx->grid[0], 0.f, nullptr, NoCollision {});
 	register_blocks_kernel<-1, 1><<<rg32, 256, 0, s>>>(g, &st[ST_CNT_P], &st[ST_CNT_N], &st[ST_CNT_E], &st[ST_NBC], Pn.table, Pn.keys, st);
 	// the next G2P2G runs in the new numbering n with the particle data laid out in r: sort its lists (the ones the last
 	// G2P2G appended to), look up its blocks' neighbours; this last kernel also publishes the exterior block count
@@ -1049,7 +1062,7 @@ int mpm_run_fixed(mpm_ctx* ctx, int nsteps, float dt) {
 		int rc = launch_grid_update(ctx, dt);
 		if(rc) return rc;
 		const bool fuse_next = it + 1 < nsteps;// the last substep leaves the canonical state behind
-		rc = launch_g2p2g(ctx, dt, dt, ev[1], ev[2], true, fuse_next && !ctx->has_collision);
+		rc = launch_g2p2g(ctx, dt, dt, ev[1], ev[2], true, fuse_next);
 		if(rc) return rc;
 		rc = launch_rebuild(ctx, fuse_next ? dt : 0.f);
 		if(rc) return rc;
@@ -1175,8 +1188,9 @@ int mpm_set_collision_object(mpm_ctx* ctx, const mpm_collision_object* obj, cons
 	HIP_TRY(hipSetDevice(ctx->device));
 	HIP_TRY(hipDeviceSynchronize());
 	if(ctx->d_sdf) HIP_TRY(hipFree(ctx->d_sdf));
-	ctx->d_sdf		   = nullptr;
-	ctx->has_collision = false;
+	ctx->d_sdf			   = nullptr;
+	ctx->has_collision	   = false;
+	ctx->collision_running = false;// installing or removing an object stops the clock
 	if(!obj) return MPM_OK;
 	if(!sdf || !gx || !gy || !gz) return fail(ctx, MPM_ERR_INVALID, "collision object without a signed distance field");
 	if(obj->type < MPM_BOUNDARY_STICKY || obj->type > MPM_BOUNDARY_SEPARATE) return fail(ctx, MPM_ERR_INVALID, "[ERROR] Wrong Boundary Type!");// boundary_condition.cuh:244
@@ -1204,6 +1218,21 @@ int mpm_set_collision_object(mpm_ctx* ctx, const mpm_collision_object* obj, cons
 	c.time			   = obj->time;
 	c.field			   = ctx->d_sdf;
 	ctx->has_collision = true;
+	return MPM_OK;
+}
+
+int mpm_set_collision_clock(mpm_ctx* ctx, int running, float time) {
+	if(!ctx) return MPM_ERR_INVALID;
+	if(!ctx->has_collision) return fail(ctx, MPM_ERR_INVALID, "no collision object installed");
+	ctx->collision.time	   = time;
+	ctx->collision_running = running != 0;
+	return MPM_OK;
+}
+int mpm_get_collision_time(mpm_ctx* ctx, float* time, int* running) {
+	if(!ctx) return MPM_ERR_INVALID;
+	if(!ctx->has_collision) return fail(ctx, MPM_ERR_INVALID, "no collision object installed");
+	if(time) *time = ctx->collision.time;
+	if(running) *running = ctx->collision_running ? 1 : 0;
 	return MPM_OK;
 }
 

@@ -6,7 +6,11 @@
 // four scalar loads from four SoA channels of a 4x4x4-blocked field.  The arithmetic keeps the reference's quirks
 // (the "cross product" with plus signs, MatrixUtils.h:53-58; the early return of SEPARATE with a zero normal).
 #pragma once
-#include "mpm_device_math.hpp"
+#include <hip/hip_runtime.h>
+#include <math.h>
+#ifndef MPM_DEV// (mpm_device_math.hpp's; this header needs nothing else of it, so that tools/hostcheck can build it alone on x86)
+#define MPM_DEV __device__ __forceinline__
+#endif
 
 namespace mpm {
 
@@ -15,60 +19,76 @@ struct CollisionObject {// mpm_collision_object + the field
 	float friction, scale, dsdt;
 	float trans[3], trans_vel[3], omega[3];
 	float rot[9];// element (i, j) at [3 i + j] (the reference's vec3x3), handed to the column-major helpers as raw arrays
-	float time;
+	float time;// the object's clock: the time of the next grid update (mpm_set_collision_clock)
 	const float4* field;
 };
 
-// rot_angle_to_matrix (:68-91)
-MPM_DEV void col_rot_angle_to_matrix(float omega, int dim, float (&res)[9]) {
-#pragma unroll
-	for(int i = 0; i < 9; ++i) res[i] = 0.f;
-	const float c = cosf(omega), s = sinf(omega);
-	if(dim == 0) {
-		res[0] = 1.f;
-		res[4] = res[8] = c;
-		res[7]			= s;
-		res[5]			= -s;
-	} else if(dim == 1) {
-		res[4] = 1.f;
-		res[0] = res[8] = c;
-		res[2]			= s;
-		res[6]			= -s;
-	} else {
-		res[8] = 1.f;
-		res[0] = res[4] = c;
-		res[3]			= s;
-		res[1]			= -s;
-	}
-}
+// No contraction in the per-node code (the pragma at the top of each function): left to the compiler, the stand-alone kernel and the fused
+// carry-over came out with different fused multiply-adds and differed in the last bit of a velocity (1.2e-7 relative in position after 60
+// substeps of a deterministic scene).  Plain IEEE operations are the same in every kernel that inlines this - and the oracle's arithmetic.
 MPM_DEV void col_cross(float (&out)[3], const float (&a)[3], const float (&b)[3]) {// (sic) plus signs
+#pragma clang fp contract(off)
 	out[0] = a[1] * b[2] + a[2] * b[1];
 	out[1] = a[2] * b[0] + a[0] * b[2];
 	out[2] = a[0] * b[1] + a[1] * b[0];
 }
 
-// detect_and_resolve_collision (:164-248); node = integer node coordinates; bc_lo / bc_hi = query_sdf's domain box (:141-146)
-MPM_DEV void collision_resolve(const CollisionObject& o, const int (&node)[3], float dx, int N, float bc_lo, float bc_hi, float (&vel)[3]) {
-	const float t = o.time;
-	float xmt[3], x0[3], x[3];
-#pragma unroll
-	for(int d = 0; d < 3; ++d) xmt[d] = (float) node[d] * dx - (o.trans[d] + o.trans_vel[d] * t);
-	float rot[9];
-#pragma unroll
-	for(int i = 0; i < 9; ++i) rot[i] = o.rot[i];
-	const float inv = 1.f / (1.f + o.dsdt * t);
-#pragma unroll
-	for(int d = 0; d < 3; ++d) x0[d] = xmt[d] * inv;
+// The object's pose at one time: everything detect_and_resolve_collision (:164-187) derives from `current_time` alone.  The same for
+// every node of a grid update, so the host computes it once per launch (collision_pose) and hands it to the kernel by value: no
+// sinf / cosf and no 3x3 products per node.  At t = 0 it is {rot = the start orientation, inv = 1, shift = trans} exactly.
+struct CollisionPose {
+	float rot[9];  // start orientation x the three axis rotations by omega t
+	float inv;	   // 1 / (1 + dsdt t)
+	float shift[3];// trans + trans_vel t
+	float growth;  // dsdt / scale (time-independent; one IEEE division here instead of one per node)
+};
+// Host side (plain C++: no contraction, libm's cosf / sinf), statement order of rot_angle_to_matrix (:68-91) and of
+// matrix_matrix_multiplication_3d (MatrixUtils.h:147-157) on the raw arrays, as col_rot_angle_to_matrix / matmul3 have it.
+inline CollisionPose collision_pose(const CollisionObject& o, float t) {
+#pragma clang fp contract(off)
+	CollisionPose p;
+	for(int d = 0; d < 3; ++d) p.shift[d] = o.trans[d] + o.trans_vel[d] * t;
+	for(int i = 0; i < 9; ++i) p.rot[i] = o.rot[i];
+	p.inv	 = 1.f / (1.f + o.dsdt * t);
+	p.growth = o.dsdt / o.scale;
 	if(t != 0.f) {// at t = 0 the three factors are identities (the only case the reference exercises)
-#pragma unroll
 		for(int dim = 0; dim < 3; ++dim) {
 			float tmp[9], prev[9];
-			col_rot_angle_to_matrix(o.omega[dim] * t, dim, tmp);
-#pragma unroll
-			for(int i = 0; i < 9; ++i) prev[i] = rot[i];
-			matmul3(prev, tmp, rot);
+			for(int i = 0; i < 9; ++i) tmp[i] = 0.f;
+			const float c = cosf(o.omega[dim] * t), s = sinf(o.omega[dim] * t);
+			if(dim == 0) {
+				tmp[0] = 1.f;
+				tmp[4] = tmp[8] = c;
+				tmp[7]			= s;
+				tmp[5]			= -s;
+			} else if(dim == 1) {
+				tmp[4] = 1.f;
+				tmp[0] = tmp[8] = c;
+				tmp[2]			= s;
+				tmp[6]			= -s;
+			} else {
+				tmp[8] = 1.f;
+				tmp[0] = tmp[4] = c;
+				tmp[3]			= s;
+				tmp[1]			= -s;
+			}
+			for(int i = 0; i < 9; ++i) prev[i] = p.rot[i];
+			for(int j = 0; j < 3; ++j)
+				for(int i = 0; i < 3; ++i) p.rot[3 * j + i] = prev[i] * tmp[3 * j] + prev[3 + i] * tmp[3 * j + 1] + prev[6 + i] * tmp[3 * j + 2];
 		}
 	}
+	return p;
+}
+
+// detect_and_resolve_collision (:164-248) behind the pose; node = integer node coordinates; bc_lo / bc_hi = query_sdf's domain box (:141-146)
+MPM_DEV void collision_resolve(const CollisionObject& o, const CollisionPose& p, const int (&node)[3], float dx, int N, float bc_lo, float bc_hi, float (&vel)[3]) {
+#pragma clang fp contract(off)
+	float xmt[3], x0[3], x[3];
+#pragma unroll
+	for(int d = 0; d < 3; ++d) xmt[d] = (float) node[d] * dx - p.shift[d];
+	const float (&rot)[9] = p.rot;
+#pragma unroll
+	for(int d = 0; d < 3; ++d) x0[d] = xmt[d] * p.inv;
 	x[0] = rot[0] * x0[0] + rot[1] * x0[1] + rot[2] * x0[2];// mat_t_mul_vec_3d
 	x[1] = rot[3] * x0[0] + rot[4] * x0[1] + rot[5] * x0[2];
 	x[2] = rot[6] * x0[0] + rot[7] * x0[1] + rot[8] * x0[2];
@@ -108,7 +128,7 @@ MPM_DEV void collision_resolve(const CollisionObject& o, const int (&node)[3], f
 	col_cross(v_obj, o.omega, xmt);
 #pragma unroll
 	for(int d = 0; d < 3; ++d) {
-		v_obj[d] += xmt[d] * (o.dsdt / o.scale);
+		v_obj[d] += xmt[d] * p.growth;
 		radius[d] = x[d] - o.trans[d];
 	}
 	col_cross(mat_vel, o.omega, radius);

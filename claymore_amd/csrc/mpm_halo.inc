@@ -278,7 +278,7 @@ static int g2p2g_halo(mpm_ctx* ctx, float dt, float next_dt, bool fused_clear, b
 	FlagGuard guard {ctx};
 	HIP_TRY(hipSetDevice(ctx->device));
 	hipStream_t s = ctx->s_compute;
-	int rc		  = launch_g2p2g_prologue(ctx, fused_clear, fused_clear && ctx->fuse_dt_once > 0.f && !ctx->has_collision);
+	int rc		  = launch_g2p2g_prologue(ctx, fused_clear, fused_clear && ctx->fuse_dt_once > 0.f);
 	if(rc) return rc;
 	HIP_TRY(hipEventRecord(ev.g2p2g_start, s));
 	if(device_sized) {

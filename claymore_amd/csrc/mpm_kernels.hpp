@@ -295,36 +295,55 @@ __global__ __launch_bounds__(256) void grid_update_kernel(GridCfg cfg, const int
 }
 
 // Grid update with a level-set collision object (second update_grid_velocity_query_max overload,
-// Projects/MGSP/mgmpm_kernels.cuh:323-399): one wave per grid block, lane = cell.  Reports the reference's doubled
-// |v|^2 (vel.dot(vel) followed by the three += of the plain overload, :365-373).
-__global__ __launch_bounds__(256) void grid_update_collision_kernel(GridCfg cfg, const int* __restrict__ nbc_ptr, float* __restrict__ grid, const int* __restrict__ keys, float dt, CollisionObject obj, unsigned* __restrict__ max_vel_bits) {
+// Projects/MGSP/mgmpm_kernels.cuh:323-399): lane = cell.  Reports the reference's doubled |v|^2 (vel.dot(vel) followed by the
+// three += of the plain overload, :365-373).  The object and its pose at the time of this update travel by value.
+struct CollisionArgs {
+	CollisionObject obj;
+	CollisionPose pose;
+};
+struct NoCollision {};
+// One cell with mass: v = {mass, momentum} in, {mass, velocity} out; returns the cell's (doubled) |v|^2.  Shared by the stand-alone
+// kernel and the fused carry-over, so that both are the same statements on the same data.
+MPM_DEV float grid_cell_collision(const GridCfg& cfg, const CollisionArgs& col, int kx, int ky, int kz, int cell, float dt, float4& v) {
+#pragma clang fp contract(off)
+	const bool wx = kx < cfg.boundary || kx >= cfg.G - cfg.boundary;
+	const bool wy = ky < cfg.boundary || ky >= cfg.G - cfg.boundary;
+	const bool wz = kz < cfg.boundary || kz >= cfg.G - cfg.boundary;
+	const float mass_inv = 1.f / v.x;
+	float vel[3];
+	vel[0] = wx ? 0.0f : v.y * mass_inv;
+	vel[1] = (wy ? 0.0f : v.z * mass_inv) + cfg.gravity * dt;
+	vel[2] = wz ? 0.0f : v.w * mass_inv;
+	const int node[3] = {kx * 4 + (cell >> 4), ky * 4 + ((cell >> 2) & 3), kz * 4 + (cell & 3)};
+	collision_resolve(col.obj, col.pose, node, cfg.dx, cfg.G * 4, (float) cfg.boundary * cfg.dx * 4.f, (float) (cfg.G - cfg.boundary) * 4.f * cfg.dx, vel);
+	v.y		= vel[0];
+	v.z		= vel[1];
+	v.w		= vel[2];
+	float q = vel[0] * vel[0] + vel[1] * vel[1] + vel[2] * vel[2];
+	q += vel[0] * vel[0];
+	q += vel[1] * vel[1];
+	q += vel[2] * vel[2];
+	if(q != q) q = __builtin_inff();
+	return q;
+}
+// One wave per grid block; the kernel of the phase-level callers (mpm_grid_update, mpm_substep, the first substep of a run): between
+// the substeps of a run the update rides on the carry-over (carry_grid_kernel<true, true>).
+__global__ __launch_bounds__(256) void grid_update_collision_kernel(GridCfg cfg, const int* __restrict__ nbc_ptr, float* __restrict__ grid, const int* __restrict__ keys, float dt, CollisionArgs col, unsigned* __restrict__ max_vel_bits) {
 	const int cell	  = threadIdx.x & 63;
 	const int nblocks = min(*nbc_ptr, cfg.cap);
 	float vel_sqr	  = 0.f;
 	for(int blockno = (blockIdx.x * 256 + threadIdx.x) >> 6; blockno < nblocks; blockno += gridDim.x * 4) {
 		const int kx = keys[3 * blockno], ky = keys[3 * blockno + 1], kz = keys[3 * blockno + 2];
-		const bool wx = kx < cfg.boundary || kx >= cfg.G - cfg.boundary;
-		const bool wy = ky < cfg.boundary || ky >= cfg.G - cfg.boundary;
-		const bool wz = kz < cfg.boundary || kz >= cfg.G - cfg.boundary;
-		float* g		 = grid + (size_t) blockno * 256 + cell;
-		const float mass = g[0];
-		if(mass > 0.0f) {
-			const float mass_inv = 1.f / mass;
-			float vel[3];
-			vel[0] = wx ? 0.0f : g[64] * mass_inv;
-			vel[1] = (wy ? 0.0f : g[128] * mass_inv) + cfg.gravity * dt;
-			vel[2] = wz ? 0.0f : g[192] * mass_inv;
-			const int node[3] = {kx * 4 + (cell >> 4), ky * 4 + ((cell >> 2) & 3), kz * 4 + (cell & 3)};
-			collision_resolve(obj, node, cfg.dx, cfg.G * 4, (float) cfg.boundary * cfg.dx * 4.f, (float) (cfg.G - cfg.boundary) * 4.f * cfg.dx, vel);
-			g[64]	= vel[0];
-			g[128]	= vel[1];
-			g[192]	= vel[2];
-			float q = vel[0] * vel[0] + vel[1] * vel[1] + vel[2] * vel[2];
-			q += vel[0] * vel[0];
-			q += vel[1] * vel[1];
-			q += vel[2] * vel[2];
-			if(q != q) q = __builtin_inff();
-			vel_sqr = fmaxf(vel_sqr, q);
+		float* g	 = grid + (size_t) blockno * 256 + cell;
+		float4 v	 = {g[0], 0.f, 0.f, 0.f};
+		if(v.x > 0.0f) {
+			v.y = g[64];
+			v.z = g[128];
+			v.w = g[192];
+			vel_sqr = fmaxf(vel_sqr, grid_cell_collision(cfg, col, kx, ky, kz, cell, dt, v));
+			g[64]	= v.y;
+			g[128]	= v.z;
+			g[192]	= v.w;
 		}
 	}
 #pragma unroll
@@ -844,8 +863,11 @@ __global__ __launch_bounds__(256) void register_blocks_kernel(GridCfg cfg, const
 // grid.  Used between the substeps of mpm_run_fixed, where the next dt is known and nobody looks at the grid in between.
 // Runs between the neighbour and the exterior registration: the new neighbour count is the sum of the first two phase counters, the
 // published status[ST_NBC] is still the OLD one (the exterior registration publishes the new one).
-template<bool UPDATE>
-__global__ __launch_bounds__(256) void carry_grid_kernel(GridCfg cfg, const int* __restrict__ status, const int* __restrict__ new_keys, const int* __restrict__ old_table, const float* __restrict__ p2g_grid, float* __restrict__ grid, float dt, unsigned* __restrict__ max_vel_bits) {
+// COLLIDE (with UPDATE): the update is the collision object's (grid_cell_collision, the statements of grid_update_collision_kernel) with
+// the object and its pose in `col`; without it `col` is an empty struct and the kernel is the plain one, instruction for instruction.
+template<bool UPDATE, bool COLLIDE = false>
+__global__ __launch_bounds__(256) void carry_grid_kernel(GridCfg cfg, const int* __restrict__ status, const int* __restrict__ new_keys, const int* __restrict__ old_table, const float* __restrict__ p2g_grid, float* __restrict__ grid, float dt, unsigned* __restrict__ max_vel_bits, std::conditional_t<COLLIDE, CollisionArgs, NoCollision> col) {
+	static_assert(UPDATE || !COLLIDE, "the collision object belongs to the grid update");
 	const int nbc	  = min(status[ST_CNT_P] + status[ST_CNT_N], cfg.cap);
 	const int old_nbc = min(status[ST_NBC], cfg.cap);
 	const int lane = threadIdx.x & 63;
@@ -858,7 +880,9 @@ __global__ __launch_bounds__(256) void carry_grid_kernel(GridCfg cfg, const int*
 			const float* s = p2g_grid + (size_t) old * 256;
 			v			   = {s[lane], s[64 + lane], s[128 + lane], s[192 + lane]};
 		}
-		if constexpr(UPDATE) {
+		if constexpr(COLLIDE) {
+			if(v.x > 0.0f) vel_sqr = fmaxf(vel_sqr, grid_cell_collision(cfg, col, kx, ky, kz, lane, dt, v));
+		} else if constexpr(UPDATE) {
 			if(v.x > 0.0f) {
 				const bool wx = kx < cfg.boundary || kx >= cfg.G - cfg.boundary;
 				const bool wy = ky < cfg.boundary || ky >= cfg.G - cfg.boundary;

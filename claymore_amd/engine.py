@@ -180,10 +180,11 @@ class Engine:
         self._check(self.api.get_counts(self.ctx, C.byref(c)))
         return c
 
-    def set_collision_object(self, sdf=None, grad=None, **fields):
+    def set_collision_object(self, sdf=None, grad=None, animate=False, **fields):
         """Install the level-set collision object of the MGSP grid update (MgspBenchmark::init_boundary,
         mgsp_benchmark.cuh:257-266).  sdf: (N, N, N) float32 node values, grad: (3, N, N, N); fields: type, friction, scale,
-        dsdt, trans, trans_vel, omega, rot_mat, time.  sdf=None removes the object."""
+        dsdt, trans, trans_vel, omega, rot_mat, time.  sdf=None removes the object.  The object's clock is left stopped at
+        `time`; animate=True starts it there (set_collision_clock): the object then moves with every grid update."""
         if sdf is None:
             self._check(self.api.set_collision_object(self.ctx, None, None, None, None, None))
             return
@@ -202,6 +203,24 @@ class Engine:
         assert sdf.shape == (n, n, n) and grad.shape == (3, n, n, n), (sdf.shape, grad.shape)
         self._check(self.api.set_collision_object(self.ctx, C.byref(obj), sdf.ctypes.data, grad[0].ctypes.data,
                                                   grad[1].ctypes.data, grad[2].ctypes.data))
+        if animate:
+            self.set_collision_clock(True, float(obj.time))
+
+    def set_collision_clock(self, running=True, time=0.0):
+        """Set the collision object's time and start (or stop) its clock: a running clock advances by dt with every grid update,
+        the update of a substep sees the object at the time the substep starts (HIP engine only)."""
+        self._check(self.api.set_collision_clock(self.ctx, 1 if running else 0, float(time)))
+
+    def collision_time(self):
+        """The collision object's current time: where the next grid update will see it (HIP engine only)."""
+        t = C.c_float(0)
+        self._check(self.api.get_collision_time(self.ctx, C.byref(t), None))
+        return t.value
+
+    def collision_clock_running(self):
+        running = C.c_int(0)
+        self._check(self.api.get_collision_time(self.ctx, None, C.byref(running)))
+        return bool(running.value)
 
     def save_checkpoint(self):
         """Full state at the current substep boundary as a numpy byte array (HIP engine only)."""

@@ -61,6 +61,8 @@ int main(int argc, char** argv) {
 	std::string out = ".", boundary, boundary_type = "sticky";
 	std::string transport = std::getenv("MPM_GROUP_TRANSPORT") ? std::getenv("MPM_GROUP_TRANSPORT") : "peer";
 	float friction = 0.3f;
+	float b_vel[3] = {0.f, 0.f, 0.f}, b_omega[3] = {0.f, 0.f, 0.f}, b_dsdt = 0.f;// motion of the collision object; any of them starts its clock
+	bool moving = false;
 	for(int i = 1; i < argc; ++i) {
 		auto is = [&](const char* s) { return !std::strcmp(argv[i], s) && i + 1 < argc; };
 		if(is("--devices")) ndev = std::atoi(argv[++i]);
@@ -73,6 +75,9 @@ int main(int argc, char** argv) {
 		else if(is("--boundary")) boundary = argv[++i];
 		else if(is("--boundary-type")) boundary_type = argv[++i];
 		else if(is("--friction")) friction = (float) std::atof(argv[++i]);
+		else if(is("--boundary-velocity")) moving |= std::sscanf(argv[++i], "%f,%f,%f", &b_vel[0], &b_vel[1], &b_vel[2]) == 3;
+		else if(is("--boundary-omega")) moving |= std::sscanf(argv[++i], "%f,%f,%f", &b_omega[0], &b_omega[1], &b_omega[2]) == 3;
+		else if(is("--boundary-dsdt")) b_dsdt = (float) std::atof(argv[++i]), moving = true;
 		else if(!std::strcmp(argv[i], "--same-device")) same = true;
 		else if(!std::strcmp(argv[i], "--output-velocity")) out_vel = true;
 	}
@@ -152,8 +157,13 @@ int main(int argc, char** argv) {
 		mpm_default_collision_object(&obj);
 		obj.type	 = boundary_type == "slip" ? MPM_BOUNDARY_SLIP : (boundary_type == "separate" ? MPM_BOUNDARY_SEPARATE : MPM_BOUNDARY_STICKY);
 		obj.friction = friction;
-		for(auto& D: devs) check(D, mpm_set_collision_object(D.ctx, &obj, field[0].data(), field[1].data(), field[2].data(), field[3].data()));
-		std::printf("[Collision Object] %s, %s\n", boundary.c_str(), boundary_type.c_str());
+		obj.dsdt	 = b_dsdt;
+		for(int k = 0; k < 3; ++k) obj.trans_vel[k] = b_vel[k], obj.omega[k] = b_omega[k];
+		for(auto& D: devs) {
+			check(D, mpm_set_collision_object(D.ctx, &obj, field[0].data(), field[1].data(), field[2].data(), field[3].data()));
+			if(moving) check(D, mpm_set_collision_clock(D.ctx, 1, 0.f));// every device's context: the same object, the same clock
+		}
+		std::printf("[Collision Object] %s, %s%s\n", boundary.c_str(), boundary_type.c_str(), moving ? ", moving" : "");
 	}
 	// One worker thread per device, as the reference (mgsp_benchmark.cuh:309-356), each driving the library's MGSP loop
 	// (mpm_group_main_loop: halo-first G2P2G, grouped RCCL send / recv beside the interior G2P2G, all-gather of block keys,

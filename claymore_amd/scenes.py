@@ -215,3 +215,24 @@ def sphere_on_obstacle(bits=6, radius_cells=5.0, obstacle_cells=6.0, boundary="s
             "models": [{"material": material, "xyz": lattice_sphere(bits, c_sph, radius_cells), "v0": (0.0, -speed, 0.0),
                         "params": {"volume": vol, "youngs_modulus": 5e3, "poisson_ratio": 0.4, "rho": 1e3}}],
             "collision": {"sdf": sdf, "grad": grad, "type": {"sticky": 0, "slip": 1, "separate": 2}[boundary], "friction": friction}}
+
+
+def sphere_through_block(bits=6, block_cells=(20, 10, 20), radius_cells=5.0, gap_cells=2.0, speed=1.0, boundary="sticky", friction=0.3,
+                         omega=(0.0, 0.0, 0.0), dsdt=0.0, rot_mat=None, animate=True, dt=1e-4, material=FIXED_COROTATED):
+    """A block of material at rest (no gravity) and a spherical level set that starts `gap_cells` clear of its -x face and translates
+    through it along +x (the moving collision object: the clock runs unless animate=False).  The level set is centred at `trans`, so
+    omega / dsdt / rot_mat turn and grow the sphere about its own moving centre."""
+    dx, n = 1.0 / (1 << bits), 1 << bits
+    lo = [n // 2 - int(block_cells[d]) // 2 for d in range(3)]
+    hi = [lo[d] + int(block_cells[d]) for d in range(3)]
+    # (the centre sits off the block's mid-planes by fractions of a cell, so that no node lies on a symmetry plane of the contact)
+    centre = ((lo[0] - gap_cells - radius_cells) * dx, (lo[1] + hi[1]) / 2 * dx + 0.75 * dx, (lo[2] + hi[2]) / 2 * dx - 0.5 * dx)
+    sdf, grad = sphere_level_set(bits, centre, radius_cells * dx)
+    col = {"sdf": sdf, "grad": grad, "type": {"sticky": 0, "slip": 1, "separate": 2}[boundary], "friction": friction,
+           "trans": centre, "trans_vel": (speed, 0.0, 0.0), "omega": omega, "dsdt": dsdt, "animate": animate}
+    if rot_mat is not None:
+        col["rot_mat"] = rot_mat
+    return {"name": "sphere_through_block", "bits": bits, "dt": dt, "config": {"gravity": 0.0},
+            "models": [{"material": material, "xyz": lattice_box(bits, lo, hi), "v0": (0.0, 0.0, 0.0),
+                        "params": {"volume": _vol(bits), "youngs_modulus": 5e3, "poisson_ratio": 0.4, "rho": 1e3}}],
+            "collision": col}

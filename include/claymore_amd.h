@@ -215,7 +215,8 @@ typedef struct mpm_collision_object {
 	float trans_vel[3]; /* 0 */
 	float omega[3];		/* 0 */
 	float rot_mat[9];	/* identity; stored as the reference stores vec3x3: element (i, j) at [3 i + j] */
-	float time;			/* `current_time` handed to detect_and_resolve_collision; the reference passes 0.f (:364) */
+	float time;			/* `current_time` handed to detect_and_resolve_collision; the reference passes 0.f (:364).  Installing the
+						 * object sets its clock to this value, stopped: see mpm_set_collision_clock */
 	int reserved[3];
 } mpm_collision_object;
 int mpm_default_collision_object(mpm_collision_object* obj);
@@ -225,6 +226,21 @@ int mpm_default_collision_object(mpm_collision_object* obj);
  * With an object installed, mpm_grid_update follows the reference's boundary overload, including its max-velocity
  * quirk (|v|^2 is accumulated twice, mgmpm_kernels.cuh:365-373). */
 int mpm_set_collision_object(mpm_ctx* ctx, const mpm_collision_object* obj, const float* sdf, const float* grad_x, const float* grad_y, const float* grad_z);
+/* The object's clock: a moving object (trans_vel, omega, dsdt, start orientation rot_mat).  The pose is evaluated at the current
+ * time T as the reference's detect_and_resolve_collision(..., current_time, ...) does: shape at trans + trans_vel T, turned by
+ * rot_mat x Rx(omega_x T) x Ry(omega_y T) x Rz(omega_z T), grown by 1 + dsdt T.  A stopped clock (what mpm_set_collision_object
+ * leaves behind) gives the surface its velocity while the shape stands still.
+ * running = 1: the time advances by dt with every grid update of this context; running = 0: it stays at `time`.  Sets the current
+ * time to `time` either way.  MPM_ERR_INVALID without an installed object; installing or removing an object stops the clock.
+ * Rule: the grid update of a substep of length dt evaluates the object at T, the start of the substep, then T = T + dt in one
+ * float32 addition (the drivers' own cur_time += dt).  It holds on every path that applies a grid update - mpm_grid_update,
+ * mpm_substep (the dt actually used), mpm_run_fixed and the group drivers (whose fused carry-over applies the NEXT substep's
+ * update and advances the clock then), mpm_mgsp_begin - exactly once per update.  The pose is computed on the host when the
+ * update is enqueued and travels to the kernel by value.  Every rank of a group gets the same object and clock from its caller.
+ * Neither the object nor its clock is part of a checkpoint: a restart installs the object again and calls
+ * mpm_set_collision_clock with what mpm_get_collision_time returned when the checkpoint was saved.  HIP library only. */
+int mpm_set_collision_clock(mpm_ctx* ctx, int running, float time);
+int mpm_get_collision_time(mpm_ctx* ctx, float* time, int* running); /* either pointer may be NULL */
 
 /* Current capacities and the number of times check_capacity() (gmpm_simulator.cuh:283-300) has grown them: blocks
  * (exterior count limit), bins per model (bin_capacity[8]).  HIP library only. */

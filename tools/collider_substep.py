@@ -1,0 +1,87 @@
+#!/usr/bin/env python
+"""Per-phase substep times of mpm_run_fixed with a collision object: none / static / moving, for one or several prebuilt engine
+libraries in ONE process, interleaved (lib A, lib B, lib A, ...), so that a parent build and a branch build are compared on the same
+box under the same conditions.
+
+    python tools/collider_substep.py [--scene c2|c3] [--steps 200] [--warmup 50] [--reps 3] [--objects none,static,moving] [--out FILE] [lib.so ...]
+
+Scene: C2 (one elastic sphere of ~5 M particles dropped at 256^3; the level-set field is 256^3 float4 = 256 MiB) or C3 (the sand column at
+512^3; the field is 2 GiB).  The object is a sphere below the material, far enough that nothing touches it during the measurement: the
+kernel evaluates it at every grid node with mass either way, which is the cost in question.  A library without the clock's entry points
+(a parent build) runs `none` and `static` only.  Prints one JSON line per (rep, library, object) with the library's per-substep averages
+(HIP events on the compute stream) and the wall-clock time per substep, then a summary of medians."""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from claymore_amd import _ffi, scenes  # noqa: E402
+from claymore_amd.engine import build_engine  # noqa: E402
+
+
+def load(path):
+    lib = C.CDLL(path, mode=os.RTLD_LOCAL | os.RTLD_NOW)
+    names = {n: sig for n, sig in {**_ffi.SIGNATURES, **_ffi.HIP_ONLY}.items() if hasattr(lib, "mpm_" + n)}
+    return _ffi.Api(lib, "mpm_", names)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("libs", nargs="*", default=[_ffi.HIP_LIB_PATH])
+    ap.add_argument("--scene", default="c2", choices=["c2", "c3"])
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--objects", default="none,static,moving")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    sc = scenes.sphere_drop() if a.scene == "c2" else scenes.sand_column()
+    bits = sc["bits"]
+    sdf, grad = scenes.sphere_level_set(bits, (0.5, 0.12, 0.5), 0.06)
+    col = {"sdf": sdf, "grad": grad, "type": 1, "friction": 0.3, "trans": (0.5, 0.12, 0.5)}
+    apis = [(os.path.basename(os.path.dirname(os.path.abspath(p))) + "/" + os.path.basename(p), load(p)) for p in a.libs]
+    rows, lines = [], []
+    for rep in range(a.reps):
+        for name, api in apis:
+            for obj in a.objects.split(","):
+                if obj == "moving" and not hasattr(api, "set_collision_clock"):
+                    continue
+                eng = build_engine(sc, api=api)
+                if obj != "none":
+                    eng.set_collision_object(**col, **({"trans_vel": (0.0, 0.05, 0.0), "omega": (1.0, 2.0, 3.0), "dsdt": 0.1} if obj == "moving" else {}))
+                if obj == "moving":
+                    eng.set_collision_clock(True, 0.0)
+                eng.initial_setup()
+                eng.run_fixed(a.warmup, sc["dt"])
+                t0 = time.perf_counter()
+                eng.run_fixed(a.steps, sc["dt"])
+                wall = (time.perf_counter() - t0) * 1e3 / a.steps
+                t = eng.timers()
+                row = {"rep": rep, "lib": name, "build": api.build_info().decode(), "scene": a.scene, "object": obj, "steps": a.steps, "wall_ms": round(wall, 5),
+                       "grid_ms": round(t.grid_update_ms, 5), "g2p2g_ms": round(t.g2p2g_ms, 5), "partition_ms": round(t.partition_ms, 5), "total_ms": round(t.total_ms, 5)}
+                eng.close()
+                rows.append(row)
+                lines.append(json.dumps(row))
+                print(lines[-1], flush=True)
+    for name, _ in apis:
+        for obj in a.objects.split(","):
+            sel = [r for r in rows if r["lib"] == name and r["object"] == obj]
+            if sel:
+                med = {k: round(statistics.median(r[k] for r in sel), 5) for k in ("wall_ms", "grid_ms", "g2p2g_ms", "partition_ms", "total_ms")}
+                med.update(lo=min(r["wall_ms"] for r in sel), hi=max(r["wall_ms"] for r in sel))
+                lines.append(json.dumps({"summary": name, "object": obj, "n": len(sel), **med}))
+                print(lines[-1], flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -18,8 +18,6 @@
 #include "mpm_readout.hpp"
 
 using namespace mpm;
-#define MPM_STR_(x) #x
-#define MPM_STR(x) MPM_STR_(x)
 
 namespace {
 // ONE device block (and its pinned mirror) holds everything the host reads back at a synchronisation: the status words, the MGSP halo
@@ -164,20 +162,23 @@ static float host_maxvel(const mpm_ctx* ctx) {
 	return m;
 }
 
-// Which materials' G2P2G runs two particles per lane (bit m = material m; mpm_g2p2g_pair.hpp).  MPM_PAIR_BUILD: the instantiations compiled in;
+// Which materials' G2P2G runs two particles per lane (bit m = material m; mpm_g2p2g_pair.hpp).
 // MPM_PAIR_DEFAULT: the ones used unless the environment says otherwise (MPM_G2P2G_PAIRS=<mask>, read once: same-library A/B and tests).
-#ifndef MPM_PAIR_BUILD
-#define MPM_PAIR_BUILD 0xF
-#endif
 #ifndef MPM_PAIR_DEFAULT
 #define MPM_PAIR_DEFAULT 0xF// all four materials (NACC with the late record fetch: 163 registers, no scratch; -6 % on a 5 M-particle NACC sphere)
 #endif
 static int pair_mask() {
 	static const int mask = [] {
 		const char* e = std::getenv("MPM_G2P2G_PAIRS");
-		return (e && *e ? (int) std::strtol(e, nullptr, 0) : MPM_PAIR_DEFAULT) & MPM_PAIR_BUILD;
+		return (e && *e ? (int) std::strtol(e, nullptr, 0) : MPM_PAIR_DEFAULT) & 0xF;
 	}();
 	return mask;
+}
+
+// two particles per lane (mpm_g2p2g_pair.hpp) for the materials of pair_mask(); the others one particle per lane (same signature)
+template<int M>
+static auto g2p2g_for(bool pair) {
+	return pair ? g2p2g_pair_kernel<M> : g2p2g_kernel<M>;
 }
 
 static int launch_prepare(mpm_ctx* ctx, int cur, int prev, bool list_is_out, int binoff_sel, const int* pbc_ptr, int nblocks_est, bool sort, bool publish);
@@ -703,27 +704,14 @@ static void launch_g2p2g_model(mpm_ctx* ctx, Model& m, const int* block_list, co
 	sk.jdiv		= g.dx * dt * g.d_inv;
 	sk.jvisc	= g.dx * g.d_inv * m.mc.viscosity;
 	const int nwg = nblocks_ptr ? hint_blocks(ctx, nblocks) : nblocks;
-	// two particles per lane (mpm_g2p2g_pair.hpp) for the materials of pair_mask(); the others one particle per lane
-#define MPM_LAUNCH_PAIR(M)                                                                                                                                                                      \
-	if constexpr((MPM_PAIR_BUILD >> M) & 1) {                                                                                                                                                   \
-		if(m.pair) {                                                                                                                                                                            \
-			g2p2g_pair_kernel<M><<<nwg, kG2P2GThreads, 0, s>>>(ctx->g, v, cur_keys, ctx->grid[0], ctx->grid[1], block_list, only_flag, nblocks_ptr, nblocks, dt, next_dt, sk, ctx->d_status); \
-			return;                                                                                                                                                                             \
-		}                                                                                                                                                                                       \
-	}
+	auto kernel = g2p2g_for<3>(m.pair);
 	switch(m.material) {
-		case MPM_J_FLUID: MPM_LAUNCH_PAIR(0) break;
-		case MPM_FIXED_COROTATED: MPM_LAUNCH_PAIR(1) break;
-		case MPM_SAND: MPM_LAUNCH_PAIR(2) break;
-		default: MPM_LAUNCH_PAIR(3) break;
+		case MPM_J_FLUID: kernel = g2p2g_for<0>(m.pair); break;
+		case MPM_FIXED_COROTATED: kernel = g2p2g_for<1>(m.pair); break;
+		case MPM_SAND: kernel = g2p2g_for<2>(m.pair); break;
+		default: break;
 	}
-#undef MPM_LAUNCH_PAIR
-	switch(m.material) {
-		case MPM_J_FLUID: g2p2g_kernel<0><<<nwg, kG2P2GThreads, 0, s>>>(ctx->g, v, cur_keys, ctx->grid[0], ctx->grid[1], block_list, only_flag, nblocks_ptr, nblocks, dt, next_dt, sk, ctx->d_status); break;
-		case MPM_FIXED_COROTATED: g2p2g_kernel<1><<<nwg, kG2P2GThreads, 0, s>>>(ctx->g, v, cur_keys, ctx->grid[0], ctx->grid[1], block_list, only_flag, nblocks_ptr, nblocks, dt, next_dt, sk, ctx->d_status); break;
-		case MPM_SAND: g2p2g_kernel<2><<<nwg, kG2P2GThreads, 0, s>>>(ctx->g, v, cur_keys, ctx->grid[0], ctx->grid[1], block_list, only_flag, nblocks_ptr, nblocks, dt, next_dt, sk, ctx->d_status); break;
-		default: g2p2g_kernel<3><<<nwg, kG2P2GThreads, 0, s>>>(ctx->g, v, cur_keys, ctx->grid[0], ctx->grid[1], block_list, only_flag, nblocks_ptr, nblocks, dt, next_dt, sk, ctx->d_status); break;
-	}
+	kernel<<<nwg, kG2P2GThreads, 0, s>>>(ctx->g, v, cur_keys, ctx->grid[0], ctx->grid[1], block_list, only_flag, nblocks_ptr, nblocks, dt, next_dt, sk, ctx->d_status);
 }
 
 // substep_clear_kernel: the P2G part precedes G2P2G (clear_grid + the bucket counters, gmpm_simulator.cuh:383,:389), the rebuild
@@ -1113,38 +1101,11 @@ const char* mpm_build_info(void) {
 	return "claymore_hip abi7 state=b"
 #ifdef MPM_EXPERIMENT
 		   " experiment=MPM_EXPERIMENT"
-#ifdef MPM_HACK_EDGEWIN
-		   ",MPM_HACK_EDGEWIN"
-#endif
-#ifdef MPM_HACK_NOSHELL
-		   ",MPM_HACK_NOSHELL"
-#endif
 #ifdef MPM_HACK_STALE_INTERIOR
 		   ",MPM_HACK_STALE_INTERIOR"
 #endif
-#ifdef MPM_HACK_NOSERIAL
-		   ",MPM_HACK_NOSERIAL"
-#endif
-#ifdef MPM_HACK_NOWB
-		   ",MPM_HACK_NOWB"
-#endif
-#ifdef MPM_HACK_UNDEF
-		   ",MPM_HACK_UNDEF"
-#endif
-#ifdef MPM_LDS_PAD
-		   ",MPM_LDS_PAD"
-#endif
 #ifdef MPM_G2P2G_STATS
 		   ",MPM_G2P2G_STATS"
-#endif
-#ifdef MPM_G2P2G_WAVES
-		   ",MPM_G2P2G_WAVES"
-#endif
-#ifdef MPM_G2P2G_WAVES_FLUID
-		   ",MPM_G2P2G_WAVES_FLUID"
-#endif
-#ifdef MPM_VARIANT
-		   ",MPM_VARIANT=" MPM_STR(MPM_VARIANT)
 #endif
 #else
 		   " experiment=none"

@@ -9,15 +9,21 @@
 #include <hip/hip_runtime.h>
 
 // ---- experiment switches ------------------------------------------------------------------------------------------
-// Every compile-time switch that changes what the kernels COMPUTE (timing hacks that leave a part of the physics out, A/B
-// variants of a formulation) is honoured only under -DMPM_EXPERIMENT, which no build of the product sets (__graft_entry__.build(),
-// tools/build_variant.sh without it); mpm_build_info() reports the switches a library was built with and tests/test_abi.py checks
-// that the shipped one has none.  A stray -DMPM_HACK_* without the guard does not compile.
+// The rule: a compile-time switch exists if and only if a committed test or tool builds with it.  The live ones:
+//   MPM_HACK_STALE_INTERIOR (mpm_halo.inc)  the mutant library of tests/test_mgsp_gpu.py: round 4's windowed-loop bug put back
+//   MPM_G2P2G_STATS (both G2P2G kernels)    tools/g2p2g_stats_run.py: iteration / serial-path counters in the status words
+// Both change what the kernels compute and are honoured only under -DMPM_EXPERIMENT, which no build of the product sets
+// (__graft_entry__.build(), tools/build_variant.sh without it); mpm_build_info() reports them and tests/test_abi.py checks that the
+// shipped library has none.  (MPM_ASM_MARKS below only puts comments into the assembly: tools/mark_regions.py.  MPM_PAIR_DEFAULT,
+// claymore_hip.hip, picks the default of a run-time choice.)
+// Every other name in the list is RETIRED: the A/B variants and timing hacks of rounds 1 to 6, whose results are in profiles/ and
+// DESIGN.md 5 / 7 and whose code is in the history.  They stay listed so that an old command line that still passes one
+// (-DMPM_PAIR_DUAL=1, -DMPM_HACK_NOSERIAL) fails loudly instead of building the product unchanged.
 #if !defined(MPM_EXPERIMENT)
 #if defined(MPM_NO_FASTSTAY) || defined(MPM_HACK_STALE_INTERIOR) || defined(MPM_HACK_EDGEWIN) || defined(MPM_HACK_NOSHELL) || defined(MPM_HACK_NOSERIAL) || defined(MPM_HACK_NOWB) || defined(MPM_HACK_UNDEF) || defined(MPM_SCALAR_GS) || defined(MPM_GATHER_B96) || \
 	defined(MPM_NT_LOADS) || defined(MPM_LDS_PAD) || defined(MPM_G2P2G_NOLOOP) || defined(MPM_G2P2G_STATS) || defined(MPM_PRE_SITES) || defined(MPM_SERIAL_QUEUE) ||        \
 	defined(MPM_G2P2G_WAVES) || defined(MPM_G2P2G_WAVES_FLUID) || defined(MPM_QUEUE_ENTRIES) || defined(MPM_HACK_NOSPLIT) || defined(MPM_PAIR_WAVES) || defined(MPM_PAIR_WAVES_FLUID) ||                   \
-	defined(MPM_PAIR_SHARED_GATHER) || defined(MPM_PAIR_LATE_FETCH) || defined(MPM_PAIR_LATE_FETCH_FLUID) || defined(MPM_PAIR_LATE_FETCH_NACC) || defined(MPM_PAIR_DUAL) || defined(MPM_GATHER_ASM) || defined(MPM_CHAIN_ASM)
+	defined(MPM_PAIR_SHARED_GATHER) || defined(MPM_PAIR_LATE_FETCH) || defined(MPM_PAIR_LATE_FETCH_FLUID) || defined(MPM_PAIR_LATE_FETCH_NACC) || defined(MPM_PAIR_DUAL) || defined(MPM_GATHER_ASM) || defined(MPM_CHAIN_ASM) || defined(MPM_PAIR_BUILD)
 #error "experiment switch without -DMPM_EXPERIMENT: a product library is built with none of them"
 #endif
 #endif
@@ -224,9 +230,6 @@ MPM_DEV void sym_eig3(const float (&b)[6], float (&lam)[3], float (&U)[9], Hook&
 	undeformed = false;
 	MPM_CONVERGED()
 	if(done) undeformed = __all((s11 == 1.f) & (s22 == 1.f) & (s33 == 1.f));
-#if defined(MPM_EXPERIMENT) && defined(MPM_HACK_UNDEF)// timing experiment only: every wave takes the undeformed exit (wrong physics)
-	done = conv = undeformed = true;
-#endif
 	MPM_SWEEP(0, false)
 	MPM_SWEEP(1, false)
 	MPM_SWEEP(2, false)
@@ -338,11 +341,7 @@ MPM_DEV void stress_sand(const MaterialConst& mc, const StressScale& ss, float (
 	sym_eig3<BASE>(b, lam, U, hk, undeformed);
 	// undeformed, no cohesion, log Jp >= 0: ln sigma = 0 sits at the cone tip with zero strain (:282-289): b and log Jp stay, P F^T = 0.
 	// (The three parts are skipped in place, around the hook sites, so that every site exists once in the code.)
-#if defined(MPM_EXPERIMENT) && defined(MPM_HACK_UNDEF)
-	const bool skip = undeformed;
-#else
 	const bool skip = undeformed && mc.cohesion == 0.f && __all((log_jp >= 0.f) & !refl);
-#endif
 	const float scaled_mu = 2.0f * mc.mu;
 	float lns[3], epsilon[3], epsilon_hat[3], lnS[3];
 	float sum_epsilon = 0.f, trace_epsilon = 0.f, epsilon_hat_norm = 0.f;

@@ -26,13 +26,9 @@
 
 namespace mpm {
 
-#if !(defined(MPM_EXPERIMENT) && defined(MPM_G2P2G_WAVES_FLUID))
-#define MPM_G2P2G_WAVES_FLUID 4// J-fluid instantiation: 128 VGPRs suffice, and with a material update of a handful of instructions the
-								// scatter chain has little to hide behind - occupancy does it (same-box: 0.36 ms against 0.40 at three waves)
-#endif
-#if !(defined(MPM_EXPERIMENT) && defined(MPM_G2P2G_WAVES))
-#define MPM_G2P2G_WAVES 3// waves per SIMD the register allocation is held to (168 VGPRs)
-#endif
+constexpr int kG2P2GWaves = 3;// waves per SIMD the register allocation is held to (168 VGPRs)
+constexpr int kG2P2GWavesFluid = 4;// J-fluid instantiation: 128 VGPRs suffice, and with a material update of a handful of instructions the
+								   // scatter chain has little to hide behind - occupancy does it (same-box: 0.36 ms against 0.40 at three waves)
 
 // LDS arenas: nodes 1..6 per axis of the 8^3 cube spanned by the block's 2x2x2 grid blocks.
 // Sort key of a particle = its stencil base in that cube, key = y * 36 + x * 6 + z (y slowest): with the usual population
@@ -112,9 +108,6 @@ struct P2GPayload {
 // x / y components and the (w, w (x_i - x_p)) weight pairs go through packed fp32.  A node is {vx, vy, vz, vz}: the
 // duplicate makes the load a full ds_read_b128 (4.0 cycles per wave against 7.1 for ds_read_b96) and gives the z
 // accumulators a natural register pair.
-#if !defined(MPM_EXPERIMENT) || !defined(MPM_GATHER_ASM)
-#define MPM_GATHER_ASM 1
-#endif
 typedef float v4f_ __attribute__((ext_vector_type(4)));
 // One z-pencil of the gather arena (three nodes, 16 B each) with all three reads IN FLIGHT and a wait in front of each use.  Written out because the
 // compiler, short of registers in this kernel, loads the three nodes into ONE register quad, one after the other, each behind s_waitcnt lgkmcnt(0): 54 exposed
@@ -141,7 +134,6 @@ MPM_DEV void gather_apic(const float4* __restrict__ gbase, const float (&w)[3][3
 	v2f_ vel_xy = {0.f, 0.f}, A0_xy = {0.f, 0.f}, A3_xy = {0.f, 0.f}, A6_xy = {0.f, 0.f};
 	v2f_ velz_A2 = {0.f, 0.f};
 	float A5 = 0.f, A8 = 0.f;
-#if MPM_GATHER_ASM
 	// (Also measured: a rolling window - node q + 3 requested into the registers node q leaves behind - needs two registers more, which the sand and J-fluid
 	//  instantiations pay with a reload inside the particle loop: +3 % / +1.5 %, profiles/r06_ab_pairs_phase2.txt.)
 	const unsigned lds0 = (unsigned) (size_t) gbase;// (the low half of a generic pointer into LDS is the LDS address)
@@ -194,38 +186,6 @@ MPM_DEV void gather_apic(const float4* __restrict__ gbase, const float (&w)[3][3
 	slab(std::integral_constant<int, 0> {});
 	slab(std::integral_constant<int, 1> {});
 	slab(std::integral_constant<int, 2> {});
-#else
-#pragma unroll
-	for(int i = 0; i < 3; ++i) {
-		v2f_ u0_xy = {0.f, 0.f}, uy_xy = {0.f, 0.f}, uz_xy = {0.f, 0.f}, u0z_uyz = {0.f, 0.f};
-		float uzz = 0.f;
-#pragma unroll
-		for(int j = 0; j < 3; ++j) {
-			v2f_ t0_xy = {0.f, 0.f}, t1_xy = {0.f, 0.f}, t0z_t1z = {0.f, 0.f};
-#pragma unroll
-			for(int k = 0; k < 3; ++k) {
-				const float4 v = gbase[i * kG2PStrideX + j * kG2PStrideY + k * kG2PStrideZ];
-				const v2f_ vxy = {v.x, v.y}, vzz = {v.z, v.w};
-				t0_xy		   = vxy * wz[k].x + t0_xy;
-				t1_xy		   = vxy * wz[k].y + t1_xy;
-				t0z_t1z		   = wz[k] * vzz + t0z_t1z;
-			}
-			__builtin_amdgcn_sched_barrier(0);// at most one z-pencil (3 nodes, 12 registers) of loads in flight: the other waves of the SIMD cover the LDS latency, registers are the scarce resource
-			u0_xy	= t0_xy * wy[j].x + u0_xy;
-			uy_xy	= t0_xy * wy[j].y + uy_xy;
-			uz_xy	= t1_xy * wy[j].x + uz_xy;
-			u0z_uyz = wy[j] * t0z_t1z.x + u0z_uyz;
-			uzz += wy[j].x * t0z_t1z.y;
-		}
-		vel_xy	= u0_xy * wx[i].x + vel_xy;
-		A0_xy	= u0_xy * wx[i].y + A0_xy;
-		A3_xy	= uy_xy * wx[i].x + A3_xy;
-		A6_xy	= uz_xy * wx[i].x + A6_xy;
-		velz_A2 = wx[i] * u0z_uyz.x + velz_A2;
-		A5 += wx[i].x * u0z_uyz.y;
-		A8 += wx[i].x * uzz;
-	}
-#endif
 	vel[0] = vel_xy.x;
 	vel[1] = vel_xy.y;
 	vel[2] = velz_A2.x;
@@ -320,11 +280,7 @@ MPM_DEV void p2g_serial(float4* __restrict__ arena, bool pending, int code, cons
 // ds_read_b128 (all lanes of a half read the same entry) instead of 17 ds_bpermute, and consecutive pairs are independent up to the
 // read-modify-write itself, so their loads and arithmetic overlap; issued inside the particle loop every pair was an exposed
 // bpermute -> arithmetic -> LDS round trip (0.28 of 2.15 ms in the flow window of C3 for 3.6 % of the particles).
-#if defined(MPM_EXPERIMENT) && defined(MPM_QUEUE_ENTRIES)
-constexpr int kSerialQueue = MPM_QUEUE_ENTRIES;// (0: no queue, the lanes that cannot take the chain scatter inside the particle loop)
-#else
 constexpr int kSerialQueue = 28;// entries of 64 B: 10.8 + 1.8 KB of LDS per wave, still 12 single-wave workgroups per CU
-#endif
 MPM_DEV void serial_flush(float4* __restrict__ arena, const float4* __restrict__ queue, int qn, float mass, int lane, int info, float* __restrict__ next_grid) {
 	__asm__ volatile("" : "+v"(lane));
 	const int l	   = lane & 31;
@@ -360,9 +316,6 @@ MPM_DEV void serial_flush(float4* __restrict__ arena, const float4* __restrict__
 				const float4 acc = *node;
 				*node			 = make_float4(acc.x + v0, acc.y + v1, acc.z + v2, acc.w + v3);
 			} else if(nb >= 0) {
-#if defined(MPM_EXPERIMENT) && defined(MPM_HACK_NOSHELL)// timing / traffic experiment only: the shell contributions of the serial path are dropped (wrong physics)
-				if(size_t(next_grid) != 1) continue;
-#endif
 				float* g = next_grid + (size_t) nb * 256 + (gx & 3) * 16 + (gy & 3) * 4 + (gz & 3);
 				unsafeAtomicAdd(g, v0);
 				unsafeAtomicAdd(g + 64, v1);
@@ -499,7 +452,7 @@ MPM_DEV int code_off(int c) {
 }
 
 template<int MAT>
-__global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? MPM_G2P2G_WAVES_FLUID : MPM_G2P2G_WAVES) void g2p2g_kernel(GridCfg cfg, ModelView mv, const int* __restrict__ cur_keys, const float* __restrict__ grid, float* __restrict__ next_grid, const int* __restrict__ block_list, const int* __restrict__ only_flag, const int* __restrict__ nblocks_ptr, int nblocks, float dt, float new_dt, StepConst sk, int* __restrict__ status) {
+__global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? kG2P2GWavesFluid : kG2P2GWaves) void g2p2g_kernel(GridCfg cfg, ModelView mv, const int* __restrict__ cur_keys, const float* __restrict__ grid, float* __restrict__ next_grid, const int* __restrict__ block_list, const int* __restrict__ only_flag, const int* __restrict__ nblocks_ptr, int nblocks, float dt, float new_dt, StepConst sk, int* __restrict__ status) {
 	constexpr int NCH = MatTraits<MAT>::nch;// floats per particle in a bin
 	constexpr int REC = MatTraits<MAT>::rec;// floats per record (the rest: one 64-float row per channel behind the records)
 	// 10.8 KB of LDS per wave: 15 single-wave workgroups per CU.
@@ -511,10 +464,6 @@ __global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? MPM_G2P2G_WAVES_FLUID : M
 	// (not for the J-fluid: its instantiation runs at four waves per SIMD and 14 workgroups per CU, which the queue's LDS would cost)
 	constexpr bool kQueue = MAT != 0 && kSerialQueue > 0;
 	__shared__ float4 s_queue[kQueue ? 4 * kSerialQueue : 1];// payloads of the lanes that could not take the scatter chain (serial_push / serial_flush)
-#if defined(MPM_EXPERIMENT) && defined(MPM_LDS_PAD)
-	__shared__ float s_pad[MPM_LDS_PAD / 4];// experiment: lower the occupancy without touching the code
-	if(size_t(grid) == 1) s_pad[threadIdx.x] = 0.f;
-#endif
 
 	const int lane0 = threadIdx.x;
 	// Workgroups are dealt round-robin to the 8 XCDs (each with its own L2).  Consecutive block numbers are spatial
@@ -672,7 +621,7 @@ __global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? MPM_G2P2G_WAVES_FLUID : M
 		//      chain threaded through this iteration's register-only arithmetic - re-bucketing (kPreSites call sites) and the
 		//      material update - the others (and the edge lanes) afterwards
 		MPM_MARK("L_claim");
-		constexpr int kPreSites	   = 3;// chain sites in the re-bucketing
+		constexpr int kPreSites	   = 3;// chain sites in the re-bucketing: at<0> .. at<2> below
 		constexpr int kStressSites = MAT == 0 ? 1 : (MAT == 1 ? kFcSites : (MAT == 2 ? kSandSites : kNaccSites));
 		constexpr int kSites	   = kPreSites + kStressSites + 2;
 		// (Round 5 tried a second claim round - a lane that loses in its own arena takes the other one if no first-round winner sits there: the losers
@@ -709,13 +658,14 @@ __global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? MPM_G2P2G_WAVES_FLUID : M
 			const int step = (int) __builtin_rintf(fmaf(vel[d], pred, nfd[d]));
 			pk[d]		   = min(max(((narena[d] - 1) & 3) + step, 0), 5);
 		}
-		if constexpr(kPreSites == 3) chain.template at<0>();
-#if !(defined(MPM_EXPERIMENT) && defined(MPM_NO_FASTSTAY))// round 5: a wave whose particles all stay in this block skips the look-up of the destination block and the ballot arithmetic (-1.1 % at rest, -1.9 % on C2: profiles/r04_ab_faststay.txt); MPM_NO_FASTSTAY: the general path only (A/B)
+		chain.template at<0>();
+		// round 5: a wave whose particles all stay in this block skips the look-up of the destination block and the ballot arithmetic (-1.1 % at rest, -1.9 % on C2: profiles/r04_ab_faststay.txt)
 		int ntag, dno, stay_leader, stay_rank;
 		bool stay;
 		int raw_stay = 0, raw_move = 0;
 		int b_opaque = b;
-		__asm__("" : "+v"(b_opaque));
+		__asm__("" : "+v"(b_opaque));// hide the uniform address: the compiler's atomic optimiser would broadcast the
+									 // result with v_readfirstlane right here, i.e. wait for the round trip
 		if(__all((dirv[0] | dirv[1] | dirv[2]) == 0)) {
 			ntag		= kStay;
 			dno			= active ? b : -1;
@@ -730,46 +680,22 @@ __global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? MPM_G2P2G_WAVES_FLUID : M
 			const int dno_raw = __shfl(info, 27 + ntag);
 			dno				  = (active && dir_ok) ? dno_raw : -1;
 			stay			  = dno >= 0 && ntag == kStay;
+			// particles that stay in this block share one wave-aggregated atomic
 			const unsigned long long stay_m = __ballot(stay);
 			stay_leader						= stay_m ? __ffsll((long long) stay_m) - 1 : 0;
-			stay_rank						= (int) __builtin_amdgcn_mbcnt_hi((unsigned) (stay_m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) stay_m, 0u));
+			stay_rank						= (int) __builtin_amdgcn_mbcnt_hi((unsigned) (stay_m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) stay_m, 0u));// set bits below this lane
 			if(stay_m != 0ull && lane == stay_leader) raw_stay = atomicAdd(&mv.out_count[b_opaque], __popcll(stay_m));
 			if(dno >= 0 && !stay) raw_move = atomicAdd(&mv.out_count[dno], 1);
 			if(active) {
-				if(dno < 0) atomicAdd(&status[ST_LOST], 1);
-				if(!in_arena) atomicAdd(&status[ST_ARENA], 1);
+				if(dno < 0) atomicAdd(&status[ST_LOST], 1);// reference: particle silently lost (particle_buffer.cuh:105-113)
+				if(!in_arena) atomicAdd(&status[ST_ARENA], 1);// (:877-885) contribution discarded
 			}
 		}
-		if constexpr(kPreSites == 3) chain.template at<1>();
+		chain.template at<1>();
 		const int pkey = pk[1] * 36 + pk[0] * 6 + pk[2];
 		const int rec  = (ntag << tag_shift) | (pkey << key_shift) | pidib;
 		settled		   = settled && __all(!active || (stay && pkey == okey));
-#else
-		const bool dir_ok = ((unsigned) (dirv[0] + 1) < 3u) & ((unsigned) (dirv[1] + 1) < 3u) & ((unsigned) (dirv[2] + 1) < 3u);
-		const int ntag	  = dir_ok ? (dirv[0] + 1) * 9 + (dirv[1] + 1) * 3 + dirv[2] + 1 : kStay;
-		const int dno_raw = __shfl(info, 27 + ntag);
-		const int dno	  = (active && dir_ok) ? dno_raw : -1;
-		if constexpr(kPreSites == 3) chain.template at<1>();
-		const int pkey	= pk[1] * 36 + pk[0] * 6 + pk[2];
-		const int rec	= (ntag << tag_shift) | (pkey << key_shift) | pidib;
-		const bool stay = dno >= 0 && ntag == kStay;
-		settled = settled && __all(!active || (stay && pkey == okey));
-		// particles that stay in this block share one wave-aggregated atomic
-		const unsigned long long stay_m = __ballot(stay);
-		const int stay_leader			= stay_m ? __ffsll((long long) stay_m) - 1 : 0;
-		const int stay_rank				= (int) __builtin_amdgcn_mbcnt_hi((unsigned) (stay_m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) stay_m, 0u));// set bits below this lane
-		int raw_stay = 0, raw_move = 0;
-		int b_opaque = b;
-		__asm__("" : "+v"(b_opaque));// hide the uniform address: the compiler's atomic optimiser would broadcast the
-									 // result with v_readfirstlane right here, i.e. wait for the round trip
-		if(stay_m != 0ull && lane == stay_leader) raw_stay = atomicAdd(&mv.out_count[b_opaque], __popcll(stay_m));
-		if(dno >= 0 && !stay) raw_move = atomicAdd(&mv.out_count[dno], 1);
-		if(active) {
-			if(dno < 0) atomicAdd(&status[ST_LOST], 1);// reference: particle silently lost (particle_buffer.cuh:105-113)
-			if(!in_arena) atomicAdd(&status[ST_ARENA], 1);// (:877-885) contribution discarded
-		}
-#endif
-		if constexpr(kPreSites == 3) chain.template at<2>();
+		chain.template at<2>();
 		MPM_MARK("L_material");
 		// ---- material update, store to the destination bin (slot == pidib: consecutive records) (:470-663)
 		float* dbin = mv.bins_dst + (size_t) (binoff_dst + (pidib >> 6)) * (kBin * NCH);
@@ -818,9 +744,6 @@ __global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? MPM_G2P2G_WAVES_FLUID : M
 		MPM_MARK("L_contrib");
 		chain.template at<kSites - 1>();
 		ncode = in_arena ? (narena[0] | (narena[1] << 4) | (narena[2] << 8)) : -1;
-#if defined(MPM_EXPERIMENT) && defined(MPM_HACK_EDGEWIN)// timing experiment only: stencil bases on the cube's edge are moved inside, so no lane takes the serial path for that reason (wrong physics)
-		if(in_arena) ncode = min(max(narena[0], 1), 4) | (min(max(narena[1], 1), 4) << 4) | (min(max(narena[2], 1), 4) << 8);
-#endif
 		MPM_MARK("L_append");
 		// ---- list append: the atomics' results are in by now (and with them the next iteration's particle data)
 		{
@@ -854,12 +777,7 @@ __global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? MPM_G2P2G_WAVES_FLUID : M
 				st_retry_iters += __any(left) ? 1 : 0;
 			}
 #endif
-#if defined(MPM_EXPERIMENT) && defined(MPM_HACK_NOSERIAL)// timing experiment only: claim losers and edge lanes are dropped (wrong physics)
-			if(false)
-#else
-			if(__any(left))
-#endif
-			{
+			if(__any(left)) {
 				if constexpr(kQueue)
 					serial_push(p2g, s_queue, qn, left, pv_code, pv, mass, lane, info, next_grid);
 				else
@@ -916,12 +834,7 @@ __global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? MPM_G2P2G_WAVES_FLUID : M
 		const int n	  = in ? ax * kP2GStrideX + ay * kP2GStrideY + az : 0;
 		const float4 va = p2g[n], vb = p2g[kP2GArena2 + n];
 		const float4 v	= make_float4(va.x + vb.x, va.y + vb.y, va.z + vb.z, va.w + vb.w);
-#if defined(MPM_EXPERIMENT) && defined(MPM_HACK_NOWB)// timing experiment only: no write-back of the arenas (wrong physics)
-		if(size_t(next_grid) == 1)
-#else
-		if(in && nb >= 0)
-#endif
-		{
+		if(in && nb >= 0) {
 			float* g = next_grid + (size_t) nb * 256 + lane_wb;
 			if(v.x != 0.f) unsafeAtomicAdd(g, v.x);
 			if(v.y != 0.f) unsafeAtomicAdd(g + 64, v.y);

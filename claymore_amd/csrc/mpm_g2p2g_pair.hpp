@@ -6,8 +6,7 @@
 // mpm_kernels.hpp: pair slices, then the odd records of the keys as single slices).  Then
 //   * the two P2G contributions are summed in registers and take ONE read-modify-write per node: 27 pairs of ds_read_b128 / ds_write_b128 per 128
 //     particles instead of 54;
-//   * the 27 gather nodes are read ONCE for both when the whole wave's pairs share their base (J-fluid; the solid models' second set of gather
-//     accumulators does not fit 168 registers);
+//   * each particle still gathers its own 27 nodes (one read for both was measured and lost: the second set of accumulators does not fit the registers);
 //   * claims, exec brackets, slice arithmetic, list prefetch: once per 128 particles.
 // A pair whose members END the step with different bases splits: A takes the chain, B the serial path (mispredictions only: < 1 %).
 // The pair scatters at the end of its OWN iteration, 27 steps back to back: no loop-carried payload, no chain state beside the gather, and so
@@ -18,114 +17,6 @@
 #include "mpm_g2p2g.hpp"
 
 namespace mpm {
-
-#if !(defined(MPM_EXPERIMENT) && defined(MPM_PAIR_WAVES))
-#define MPM_PAIR_WAVES 3
-#endif
-// bit m: material m reads the 27 gather nodes once for both particles when the wave's pairs share their bases (else: one gather per particle)
-#if !(defined(MPM_EXPERIMENT) && defined(MPM_PAIR_WAVES_FLUID))
-#define MPM_PAIR_WAVES_FLUID 4// (J-fluid: with the late record fetch below the instantiation needs 127 registers: four waves per SIMD, -2 % at rest, -3 % in the flow against three)
-#endif
-#if !(defined(MPM_EXPERIMENT) && defined(MPM_PAIR_DUAL))
-#define MPM_PAIR_DUAL 0// 1: a B that cannot ride with its A claims the other arena and scatters in the same chain (ScatterChainDual) instead of the serial path - measured +6 % in the C3 flow (every iteration with such a lane pays two read-modify-writes per step): off, profiles/r06_ab_pairs_phase2.txt
-#endif
-#if !(defined(MPM_EXPERIMENT) && defined(MPM_PAIR_LATE_FETCH_FLUID))
-#define MPM_PAIR_LATE_FETCH_FLUID 1// the same switch for the J-fluid instantiation (16-byte records: the shorter prefetch distance costs nothing, the registers buy the fourth wave)
-#endif
-#if !(defined(MPM_EXPERIMENT) && defined(MPM_PAIR_LATE_FETCH_NACC))
-#define MPM_PAIR_LATE_FETCH_NACC 1// NACC: with the early fetch the instantiation reloads a dozen spilled constants per iteration; with the late one it needs 165 registers and none
-#endif
-#if !(defined(MPM_EXPERIMENT) && defined(MPM_PAIR_LATE_FETCH))
-#define MPM_PAIR_LATE_FETCH 0// 0: the next slice's particle records are requested at the top of the iteration; 1: behind the material update; 2: A's at the top, B's behind the material update
-#endif
-#if !(defined(MPM_EXPERIMENT) && defined(MPM_PAIR_SHARED_GATHER))
-#define MPM_PAIR_SHARED_GATHER 0x0// (the second set of gather accumulators does not fit 168 registers beside the slice bookkeeping: scratch operations inside the loop - every one drains the record prefetch - cost more than 27 LDS reads)
-#endif
-
-// Tensor-product APIC gather (gather_apic, mpm_g2p2g.hpp) for two particles that share their stencil base: every node is loaded once.
-MPM_DEV void gather_apic_shared(const float4* __restrict__ gbase, const float (&w)[2][3][3], const float (&fd)[2][3], float (&vel)[2][3], float (&A)[2][9]) {
-	v2f_ wz[2][3], wy[2][3], wx[2][3];
-#pragma unroll
-	for(int h = 0; h < 2; ++h)
-#pragma unroll
-		for(int t = 0; t < 3; ++t) {
-			wx[h][t] = (v2f_) {w[h][0][t], w[h][0][t] * ((float) t - fd[h][0])};
-			wy[h][t] = (v2f_) {w[h][1][t], w[h][1][t] * ((float) t - fd[h][1])};
-			wz[h][t] = (v2f_) {w[h][2][t], w[h][2][t] * ((float) t - fd[h][2])};
-		}
-	v2f_ vel_xy[2], A0_xy[2], A3_xy[2], A6_xy[2], velz_A2[2];
-	float A5[2], A8[2];
-#pragma unroll
-	for(int h = 0; h < 2; ++h) {
-		vel_xy[h] = A0_xy[h] = A3_xy[h] = A6_xy[h] = velz_A2[h] = (v2f_) {0.f, 0.f};
-		A5[h] = A8[h] = 0.f;
-	}
-#pragma unroll
-	for(int i = 0; i < 3; ++i) {
-		v2f_ u0_xy[2], uy_xy[2], uz_xy[2], u0z_uyz[2];
-		float uzz[2];
-#pragma unroll
-		for(int h = 0; h < 2; ++h) {
-			u0_xy[h] = uy_xy[h] = uz_xy[h] = u0z_uyz[h] = (v2f_) {0.f, 0.f};
-			uzz[h]										= 0.f;
-		}
-#pragma unroll
-		for(int j = 0; j < 3; ++j) {
-			v2f_ t0_xy[2], t1_xy[2], t0z_t1z[2];
-#pragma unroll
-			for(int h = 0; h < 2; ++h) t0_xy[h] = t1_xy[h] = t0z_t1z[h] = (v2f_) {0.f, 0.f};
-#pragma unroll
-			for(int k = 0; k < 3; ++k) {
-				const float4 v = gbase[i * kG2PStrideX + j * kG2PStrideY + k * kG2PStrideZ];
-				const v2f_ vxy = {v.x, v.y}, vzz = {v.z, v.w};
-#pragma unroll
-				for(int h = 0; h < 2; ++h) {
-					t0_xy[h]   = vxy * wz[h][k].x + t0_xy[h];
-					t1_xy[h]   = vxy * wz[h][k].y + t1_xy[h];
-					t0z_t1z[h] = wz[h][k] * vzz + t0z_t1z[h];
-				}
-			}
-			__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-			for(int h = 0; h < 2; ++h) {
-				u0_xy[h]   = t0_xy[h] * wy[h][j].x + u0_xy[h];
-				uy_xy[h]   = t0_xy[h] * wy[h][j].y + uy_xy[h];
-				uz_xy[h]   = t1_xy[h] * wy[h][j].x + uz_xy[h];
-				u0z_uyz[h] = wy[h][j] * t0z_t1z[h].x + u0z_uyz[h];
-				uzz[h] += wy[h][j].x * t0z_t1z[h].y;
-			}
-		}
-#pragma unroll
-		for(int h = 0; h < 2; ++h) {
-			vel_xy[h]  = u0_xy[h] * wx[h][i].x + vel_xy[h];
-			A0_xy[h]   = u0_xy[h] * wx[h][i].y + A0_xy[h];
-			A3_xy[h]   = uy_xy[h] * wx[h][i].x + A3_xy[h];
-			A6_xy[h]   = uz_xy[h] * wx[h][i].x + A6_xy[h];
-			velz_A2[h] = wx[h][i] * u0z_uyz[h].x + velz_A2[h];
-			A5[h] += wx[h][i].x * u0z_uyz[h].y;
-			A8[h] += wx[h][i].x * uzz[h];
-		}
-	}
-#pragma unroll
-	for(int h = 0; h < 2; ++h) {
-		vel[h][0] = vel_xy[h].x;
-		vel[h][1] = vel_xy[h].y;
-		vel[h][2] = velz_A2[h].x;
-		A[h][0]	  = A0_xy[h].x;
-		A[h][1]	  = A0_xy[h].y;
-		A[h][2]	  = velz_A2[h].y;
-		A[h][3]	  = A3_xy[h].x;
-		A[h][4]	  = A3_xy[h].y;
-		A[h][5]	  = A5[h];
-		A[h][6]	  = A6_xy[h].x;
-		A[h][7]	  = A6_xy[h].y;
-		A[h][8]	  = A8[h];
-#pragma unroll
-		for(int d = 0; d < 9; ++d) __asm__ volatile("" : "+v"(A[h][d]));
-#pragma unroll
-		for(int d = 0; d < 3; ++d) __asm__ volatile("" : "+v"(vel[h][d]));
-	}
-}
 
 // One particle's share of a chain step: B-spline weights of the new position and the incremental walk of the affine momentum term
 // (ScatterChain, mpm_g2p2g.hpp).  `on` = false zeroes the x weights: the particle contributes nothing (its pair split).
@@ -166,76 +57,14 @@ struct ChainHalf {
 		m0	= (v2f_) {mass, k == 0 ? pen0 : (k == 1 ? pen0 + cz0 : fmaf(2.f, cz0, pen0))};
 		t12 = k == 0 ? pen12 : (k == 1 ? pen12 + cz12 : cz12 * 2.f + pen12);
 	}
-	MPM_DEV void add(int o, float mass, v2f_& a01, v2f_& a23) {
-		float W;
-		v2f_ m0, t12;
-		prep(o, mass, W, m0, t12);
-		a01 = m0 * W + a01;
-		a23 = t12 * W + a23;
-	}
-};
-
-// The chain for an iteration in which some lane's B could NOT ride with its A (another stencil base: the sort's mismatched slots, a misprediction, an A
-// on the cube's edge) but holds a claim of its own in the OTHER arena: such a lane does two read-modify-writes per step, A's node in its arena and B's
-// node in the other one (different arenas: the two may be in flight together), instead of sending B down the serial path - which costs five times a
-// chain particle (profiles/r06_ab_pairs_phase2.txt: 2 % of the particles of the C3 flow, 0.2 of 1.98 ms).  Lanes whose B rides with A (`merge`) add it
-// into A's accumulator as before.  Only instantiated behind a wave-uniform test: an iteration without such a lane runs ScatterChain2.
-struct ScatterChainDual {
-	float4 *node0, *node1;
-	float mass, merge_w, dual_w;// 1 / 0: B's contribution goes into A's node / into its own
-	int win, dual;
-	ChainHalf h[2];
-	float4 acc, acc2;
-	MPM_DEV ScatterChainDual(float4* n0, float4* n1, const P2GPayload& pa, const P2GPayload& pb, float m, bool w, bool merge, bool d)
-		: node0(n0)
-		, node1(n1)
-		, mass(m)
-		, merge_w(merge ? 1.f : 0.f)
-		, dual_w(d ? 1.f : 0.f)
-		, win(w)
-		, dual(d) {
-		h[0].init(pa, w);
-		h[1].init(pb, merge || d);
-		acc = acc2 = make_float4(0.f, 0.f, 0.f, 0.f);
-		if(win) acc = node0[0];
-		if(dual) acc2 = node1[0];
-	}
-	MPM_DEV void run() {
-#pragma unroll
-		for(int o = 0; o < 27; ++o) {
-			v2f_ a01 = {acc.x, acc.y}, a23 = {acc.z, acc.w};
-			v2f_ b01 = {0.f, 0.f}, b23 = {0.f, 0.f};
-			h[0].add(o, mass, a01, a23);
-			h[1].add(o, mass, b01, b23);
-			a01 = b01 * merge_w + a01;
-			a23 = b23 * merge_w + a23;
-			const v2f_ c01 = b01 * dual_w + (v2f_) {acc2.x, acc2.y}, c23 = b23 * dual_w + (v2f_) {acc2.z, acc2.w};
-			const int i = o / 9, j = (o / 3) % 3, k = o % 3;
-			const int off = i * kP2GStrideX + j * kP2GStrideY + k;
-			if(win) node0[off] = make_float4(a01.x, a01.y, a23.x, a23.y);
-			if(dual) node1[off] = make_float4(c01.x, c01.y, c23.x, c23.y);
-			__asm__ volatile("" ::: "memory");
-			if(o + 1 < 27) {
-				const int i1 = (o + 1) / 9, j1 = ((o + 1) / 3) % 3, k1 = (o + 1) % 3;
-				const int off1 = i1 * kP2GStrideX + j1 * kP2GStrideY + k1;
-				if(win) acc = node0[off1];
-				if(dual) acc2 = node1[off1];
-			}
-		}
-	}
 };
 
 // The scatter chain for a PAIR: per node the two contributions are summed in registers, one read-modify-write (cf. ScatterChain).
-#if !defined(MPM_EXPERIMENT) || !defined(MPM_CHAIN_ASM)
-#define MPM_CHAIN_ASM 1
-#endif
-template<int NSITES>
 struct ScatterChain2 {
 	float4* node0;
 	float mass;
 	int win;
 	ChainHalf h[2];
-#if MPM_CHAIN_ASM
 	// A step is an LDS round trip: the read of node o can only be issued behind the write of node o - 1 (another lane may have written that very node), and what
 	// the wave can do meanwhile is the part of step o that does not need the accumulator - both particles' weights and channel values (prep).  The compiler put only
 	// A's half in front of its wait (B's went behind A's multiply-adds); the read is issued and awaited by hand here (lds_issue_b128 / s_waitcnt with the prepared
@@ -272,58 +101,30 @@ struct ScatterChain2 {
 			acc = lds_issue_b128<(i1 * kP2GStrideX + j1 * kP2GStrideY + k1) * 16>(lds0);
 		}
 	}
-	template<int O, int END>
+	template<int O>
 	MPM_DEV void steps() {
-		if constexpr(O < END) {
+		if constexpr(O < 27) {
 			step<O>();
-			steps<O + 1, END>();
+			steps<O + 1>();
 		}
 	}
-	template<int SITE>
-	MPM_DEV void at() {
-		static_assert(SITE >= 0 && SITE < NSITES, "site out of range");
-		if(win) steps<SITE * 27 / NSITES, (SITE + 1) * 27 / NSITES>();
+	MPM_DEV void run() {// 27 steps back to back, under one exec bracket
+		if(win) steps<0>();
 	}
-#else
-	float4 acc;
-	MPM_DEV ScatterChain2(float4* n0, const P2GPayload& pa, const P2GPayload& pb, float m, bool w, bool with_b)
-		: node0(n0)
-		, mass(m)
-		, win(w) {
-		h[0].init(pa, true);
-		h[1].init(pb, with_b);
-		if(win) acc = node0[0];
-	}
-	MPM_DEV void step(int o) {
-		v2f_ a01 = {acc.x, acc.y};
-		v2f_ a23 = {acc.z, acc.w};
-		h[0].add(o, mass, a01, a23);
-		h[1].add(o, mass, a01, a23);
-		const int i = o / 9, j = (o / 3) % 3, k = o % 3;
-		node0[i * kP2GStrideX + j * kP2GStrideY + k] = make_float4(a01.x, a01.y, a23.x, a23.y);
-		__asm__ volatile("" ::: "memory");
-		if(o + 1 < 27) {
-			const int i1 = (o + 1) / 9, j1 = ((o + 1) / 3) % 3, k1 = (o + 1) % 3;
-			acc			 = node0[i1 * kP2GStrideX + j1 * kP2GStrideY + k1];
-		}
-	}
-	template<int SITE>
-	MPM_DEV void at() {
-		static_assert(SITE >= 0 && SITE < NSITES, "site out of range");
-		if(win) {
-#pragma unroll
-			for(int o = SITE * 27 / NSITES; o < (SITE + 1) * 27 / NSITES; ++o) step(o);
-		}
-	}
-#endif
 };
 
+// waves per SIMD the register allocation is held to: three (168 registers); the J-fluid instantiation needs 127 with the late record fetch below:
+// four waves, -2 % at rest, -3 % in the flow against three
+constexpr int kPairWaves = 3, kPairWavesFluid = 4;
+
 template<int MAT>
-__global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? MPM_PAIR_WAVES_FLUID : MPM_PAIR_WAVES) void g2p2g_pair_kernel(GridCfg cfg, ModelView mv, const int* __restrict__ cur_keys, const float* __restrict__ grid, float* __restrict__ next_grid, const int* __restrict__ block_list, const int* __restrict__ only_flag, const int* __restrict__ nblocks_ptr, int nblocks, float dt, float new_dt, StepConst sk, int* __restrict__ status) {
+__global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? kPairWavesFluid : kPairWaves) void g2p2g_pair_kernel(GridCfg cfg, ModelView mv, const int* __restrict__ cur_keys, const float* __restrict__ grid, float* __restrict__ next_grid, const int* __restrict__ block_list, const int* __restrict__ only_flag, const int* __restrict__ nblocks_ptr, int nblocks, float dt, float new_dt, StepConst sk, int* __restrict__ status) {
 	constexpr int NCH = MatTraits<MAT>::nch;
 	constexpr int REC = MatTraits<MAT>::rec;
-	constexpr bool kSharedGather = ((MPM_PAIR_SHARED_GATHER >> MAT) & 1) != 0;
-	constexpr int kLateFetch	 = MAT == 0 ? MPM_PAIR_LATE_FETCH_FLUID : (MAT == 3 ? MPM_PAIR_LATE_FETCH_NACC : MPM_PAIR_LATE_FETCH);
+	// Where the next slice's particle records are requested: at the top of the iteration (early: fixed-corotated, sand) or behind the material update (late).
+	// J-fluid: 16-byte records, the shorter prefetch distance costs nothing and the registers buy the fourth wave.  NACC: with the early fetch the instantiation
+	// reloads a dozen spilled constants per iteration; with the late one it needs 165 registers and none.
+	constexpr bool kLateFetch = MAT == 0 || MAT == 3;
 	__shared__ float4 g2p[kG2PNodes];
 	__shared__ float4 p2g[kP2GArena2 + kP2GNodes];
 	__shared__ unsigned char s_owner[2 * 216];
@@ -435,7 +236,6 @@ __global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? MPM_PAIR_WAVES_FLUID : MP
 			f.row[1]	   = t.y;
 		}
 	};
-	auto fetch = [&](int rec, Prefetch& f) { fetch_from(rec, source_bin(rec), f); };
 	// both members of a slot: the two look-ups are in flight together (issued one after the other they were two exposed round trips at the top of every iteration)
 	auto fetch2 = [&](const int (&rec)[2], Prefetch (&f)[2]) {
 		int sb[2] = {source_bin(rec[0]), source_bin(rec[1])};
@@ -445,10 +245,10 @@ __global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? MPM_PAIR_WAVES_FLUID : MP
 	};
 	Prefetch pf[2];
 	fetch2(rec_cur, pf);
-	// (kLateFetch == 0) the source bins of the NEXT slice's records are looked up one phase ahead - in front of the scatter chain, whose 27 round trips cover this one -
+	// (early fetch) the source bins of the NEXT slice's records are looked up one phase ahead - in front of the scatter chain, whose 27 round trips cover this one -
 	// and carried into the next iteration, whose record loads then start at once
 	int sb_next[2] = {0, 0};
-	if constexpr(kLateFetch == 0) sb_next[0] = source_bin(rec_next[0]), sb_next[1] = source_bin(rec_next[1]);
+	if constexpr(!kLateFetch) sb_next[0] = source_bin(rec_next[0]), sb_next[1] = source_bin(rec_next[1]);
 #pragma unroll
 	for(int lb = 0; lb < 8; ++lb) {
 		const int cx = lane >> 4, cy = (lane >> 2) & 3, cz = lane & 3;
@@ -459,7 +259,7 @@ __global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? MPM_PAIR_WAVES_FLUID : MP
 	int qn		 = 0;
 	bool settled = true;
 #ifdef MPM_G2P2G_STATS
-	int st_iter = 0, st_losers = 0, st_edge = 0, st_retry_iters = 0, st_partial = 0, st_split = 0;
+	int st_iter = 0, st_losers = 0, st_edge = 0, st_retry_iters = 0, st_partial = 0;
 #endif
 	for(int t_cur = 0;; ++t_cur) {
 		MPM_MARK("P_top");
@@ -494,18 +294,16 @@ __global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? MPM_PAIR_WAVES_FLUID : MP
 		if(((t_cur + 2) & 63) == 0) form_slices(t_cur + 2);// (a block with more than 64 slices: the next batch of descriptors)
 		read_slice(t_cur + 2, s_nn);
 		load_recs(s_nn, rec_nn);
-		if constexpr(kLateFetch == 0) {
+		if constexpr(!kLateFetch) {
 			fetch_from(rec_next[0], sb_next[0], pf[0]);
 			fetch_from(rec_next[1], sb_next[1], pf[1]);
 		}
-		if constexpr(kLateFetch == 2) fetch(rec_next[0], pf[0]);
 		MPM_MARK("P_gather");
 		// ---- stencil bases + weights (:774-797), gather (:801-835)
 		int base[2][3], arena[2][3];
 		float vel[2][3], A[2][9];
 		{
 			float fd[2][3], w[2][3][3];
-			bool same = true;
 #pragma unroll
 			for(int h = 0; h < 2; ++h)
 #pragma unroll
@@ -516,14 +314,10 @@ __global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? MPM_PAIR_WAVES_FLUID : MP
 					bspline_weight_cells(fd[h][d], w[h][d]);
 					arena[h][d] = ((base[h][d] - 1) & 3) + 1;
 				}
+			// (Also measured: ONE read of the 27 nodes for both particles when the whole wave's pairs share their bases - the second set of gather accumulators does not
+			//  fit 168 registers beside the slice bookkeeping, and scratch operations inside the loop, every one of which drains the record prefetch, cost more than 27 LDS reads.)
 #pragma unroll
-			for(int d = 0; d < 3; ++d) same &= arena[0][d] == arena[1][d];
-			if(kSharedGather && __all(same)) {
-				gather_apic_shared(g2p + (arena[0][0] - 1) * kG2PStrideX + (arena[0][1] - 1) * kG2PStrideY + (arena[0][2] - 1) * kG2PStrideZ, w, fd, vel, A);
-			} else {
-#pragma unroll
-				for(int h = 0; h < 2; ++h) gather_apic(g2p + (arena[h][0] - 1) * kG2PStrideX + (arena[h][1] - 1) * kG2PStrideY + (arena[h][2] - 1) * kG2PStrideZ, w[h], fd[h], vel[h], A[h]);
-			}
+			for(int h = 0; h < 2; ++h) gather_apic(g2p + (arena[h][0] - 1) * kG2PStrideX + (arena[h][1] - 1) * kG2PStrideY + (arena[h][2] - 1) * kG2PStrideZ, w[h], fd[h], vel[h], A[h]);
 		}
 		MPM_MARK("P_rebucket");
 		// ---- advect (:838), new base, re-bucket (:852-866, add_advection particle_buffer.cuh:100-135)
@@ -661,8 +455,7 @@ __global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? MPM_PAIR_WAVES_FLUID : MP
 		// 22 destination registers (sand) are live through the gather and the material update, the allocator runs out, parks the loads in registers it
 		// needs again and waits for them - s_waitcnt vmcnt(0) in the re-bucketing, i.e. the whole HBM latency exposed in every iteration.  From here the
 		// loads have the scatter chain (27 LDS round trips) and the other two waves of the SIMD to arrive in.
-		if constexpr(kLateFetch == 1) fetch2(rec_next, pf);
-		if constexpr(kLateFetch == 2) fetch(rec_next[1], pf[1]);
+		if constexpr(kLateFetch) fetch2(rec_next, pf);
 		MPM_MARK("P_scatter");
 		// ---- the pair scatters now (:887-905): payload ((:850) contrib = (A m - stress new_dt) D^-1, times dx: cell units), claim, 27 steps back to back
 		P2GPayload pv[2];
@@ -683,62 +476,37 @@ __global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? MPM_PAIR_WAVES_FLUID : MP
 				pv_in[h]   = pv_code[h] >= 0;
 			}
 		}
-		// ---- claims: A for the slot's arena; a B with another base than its A (or without a chain-able A) for the OTHER arena, on its own.
-		//      (Also measured: claims written and read back in FRONT of the material update, which would cover the round trip: +0.5-1 % for sand, +2.5 % for the J-fluid -
-		//       one more register across the update; profiles/r06_ab_pairs_phase2.txt.)
+		// ---- claim: A for the slot's arena; B rides with its A or goes down the serial path.
+		//      (Also measured: a B that cannot ride claims the OTHER arena and scatters in the same chain, two read-modify-writes per step in such a lane: +6 % in the
+		//       C3 flow - every iteration with such a lane pays for them.  Also measured: claims written and read back in FRONT of the material update, which would cover
+		//       the round trip: +0.5-1 % for sand, +2.5 % for the J-fluid - one more register across the update.  Both: profiles/r06_ab_pairs_phase2.txt.)
 		const bool a_ok	   = pv_in[0] && !code_edge(pv_code[0]);
 		const bool b_same  = pv_in[1] && pv_in[0] && pv_code[1] == pv_code[0];
-#if MPM_PAIR_DUAL
-		const bool b_own = pv_in[1] && !b_same && !code_edge(pv_code[1]);
-#else
-		const bool b_own = false;
-#endif
 		const int key_a = (a_ok ? code_key(pv_code[0]) : 0) + arena_sel * 216;// two arenas, two claim tables: the sort says which one a slot uses
-		const int key_b = (b_own ? code_key(pv_code[1]) : 0) + (arena_sel ^ 1) * 216;
-		// (B's claims are written FIRST: a single wave's LDS stores execute in program order, so an A that claims the same base in the same arena overwrites
-		//  them - a B never takes an arena away from a pair, it only uses one that would have stayed idle)
-		if(b_own) s_owner[key_b] = (unsigned char) (lane | 64);
-		__asm__ volatile("" ::: "memory");
 		if(a_ok) s_owner[key_a] = (unsigned char) lane;
 		__asm__ volatile("" ::: "memory");// another lane may have written the same byte: no store-to-load forwarding
 		const bool win	   = a_ok && (int) s_owner[key_a] == lane;
-		const bool dual	   = b_own && (int) s_owner[key_b] == (lane | 64);
 		const bool merge_b = win && b_same;
 		MPM_MARK("P_serial");
-		// ---- what the chain will not take - A without a claim or on the cube's edge, B neither riding with its A nor holding a claim of its own - goes first:
+		// ---- what the chain will not take - A without a claim or on the cube's edge, B not riding with its A - goes first:
 		//      the payloads are dead once the chain is set up (both add into the arenas with plain read-modify-writes; a single wave's LDS operations execute
 		//      in program order)
 		{
 			const bool left_a = pv_in[0] && !win;
-#if defined(MPM_EXPERIMENT) && defined(MPM_HACK_NOSPLIT)// timing experiment only: a B that does not ride with its A is dropped (wrong physics)
-			const bool left_b = false;
-#else
-			const bool left_b = pv_in[1] && !merge_b && !dual;
-#endif
+			const bool left_b = pv_in[1] && !merge_b;
 #ifdef MPM_G2P2G_STATS
 			st_iter += 1;
 			st_losers += __popcll(__ballot(left_a && !code_edge(pv_code[0]))) + __popcll(__ballot(left_b && !code_edge(pv_code[1])));
 			st_edge += __popcll(__ballot(pv_in[0] && code_edge(pv_code[0]))) + __popcll(__ballot(pv_in[1] && code_edge(pv_code[1])));
-			st_split += __popcll(__ballot(dual));
 			st_retry_iters += __any(left_a || left_b) ? 1 : 0;
 #endif
-#if defined(MPM_EXPERIMENT) && defined(MPM_HACK_NOSERIAL)// timing experiment only: what the chain does not take is dropped (wrong physics)
-			if(false)
-#else
-			if(__any(left_a))
-#endif
-			{
+			if(__any(left_a)) {
 				if constexpr(kQueue)
 					serial_push(p2g, s_queue, qn, left_a, pv_code[0], pv[0], mass, lane, info, next_grid);
 				else
 					p2g_serial(p2g, left_a, pv_code[0], pv[0], mass, lane, info, next_grid);
 			}
-#if defined(MPM_EXPERIMENT) && defined(MPM_HACK_NOSERIAL)
-			if(false)
-#else
-			if(__any(left_b))
-#endif
-			{
+			if(__any(left_b)) {
 				if constexpr(kQueue)
 					serial_push(p2g, s_queue, qn, left_b, pv_code[1], pv[1], mass, lane, info, next_grid);
 				else
@@ -746,16 +514,10 @@ __global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? MPM_PAIR_WAVES_FLUID : MP
 			}
 		}
 		MPM_MARK("P_chain");
-		if constexpr(kLateFetch == 0) sb_next[0] = source_bin(rec_nn[0]), sb_next[1] = source_bin(rec_nn[1]);// (rec_nn was requested at the top of this iteration)
+		if constexpr(!kLateFetch) sb_next[0] = source_bin(rec_nn[0]), sb_next[1] = source_bin(rec_nn[1]);// (rec_nn was requested at the top of this iteration)
 		float4* const node0 = p2g + (win ? code_off(pv_code[0]) + arena_sel * kP2GArena2 : 0);
-		if(__any(dual)) {
-			float4* const node1 = p2g + (dual ? code_off(pv_code[1]) + (arena_sel ^ 1) * kP2GArena2 : 0);
-			ScatterChainDual chain(node0, node1, pv[0], pv[1], mass, win, merge_b, dual);
-			chain.run();
-		} else {
-			ScatterChain2<1> chain(node0, pv[0], pv[1], mass, win, merge_b);
-			chain.template at<0>();
-		}
+		ScatterChain2 chain(node0, pv[0], pv[1], mass, win, merge_b);
+		chain.run();
 		if(s_next.cnt == 0) break;
 		s_cur  = s_next;
 		s_next = s_nn;
@@ -767,7 +529,7 @@ __global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? MPM_PAIR_WAVES_FLUID : MP
 		atomicAdd(&status[24], st_iter);
 		atomicAdd(&status[25], st_losers);
 		atomicAdd(&status[26], st_edge);
-		atomicAdd(&status[27], MPM_PAIR_DUAL ? st_split : st_retry_iters);// iterations with a serial entry, as the one-particle kernel reports them (with MPM_PAIR_DUAL: the lanes whose B scattered from the other arena)
+		atomicAdd(&status[27], st_retry_iters);// iterations with a serial entry, as the one-particle kernel reports them
 		atomicAdd(&status[28], st_partial);
 		atomicAdd(&status[41], st_retry_iters);
 	}

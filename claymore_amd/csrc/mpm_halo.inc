@@ -141,7 +141,10 @@ __global__ __launch_bounds__(256) void halo_collect_kernel(const int* __restrict
 	}
 }
 
-// reduce_grid_blocks, halo_kernels.cuh:82-97
+// reduce_grid_blocks, halo_kernels.cuh:82-97.  A zero addend (+0 or -0) is skipped, which saves the atomics of the empty half of a shared block.
+// That is the float32 sum bit for bit except for one combination: +0 added to a node that holds -0 leaves -0 where the IEEE sum is +0.  No entry
+// point puts a -0 into a grid (it is cleared to +0, and a sum of +0 and normal values in round-to-nearest is never -0; a -0 addend is skipped
+// here), and the two zeros compare equal everywhere the grid is read.
 __global__ __launch_bounds__(256) void halo_reduce_kernel(GridCfg cfg, int n, const int* __restrict__ in_keys, const float* __restrict__ in_blocks, const int* __restrict__ table, int nbc, float* grid) {
 	const int i	   = blockIdx.x * 4 + (threadIdx.x >> 6);
 	const int lane = threadIdx.x & 63;
@@ -351,6 +354,20 @@ int mpm_halo_reduce(mpm_ctx* ctx, int gid, const int* dev_keys, const float* dev
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipEventRecord(ctx->ev_comm, ctx->s_comm));
 	HIP_TRY(hipStreamWaitEvent(ctx->s_compute, ctx->ev_comm, 0));// rebuild / grid update must see the summed blocks
+	return MPM_OK;
+}
+
+// Debug read-out of the last tagging (tests/test_halo_kernels_gpu.py): the marks of the current partition's neighbour blocks, the halo
+// list and the interior flags of its particle blocks, as the kernels left them.  Read-only; waits for both streams.
+int mpm_halo_dump(mpm_ctx* ctx, int* overlap, int* halo_list, int* n_halo, int* inner_flags) {
+	if(!ctx || !ctx->ready || !ctx->halo_tagged || !ctx->d_overlap) return MPM_ERR_INVALID;
+	HIP_TRY(hipSetDevice(ctx->device));
+	HIP_TRY(hipStreamSynchronize(ctx->s_compute));
+	HIP_TRY(hipStreamSynchronize(ctx->s_comm));
+	if(overlap && ctx->nbc) HIP_TRY(hipMemcpy(overlap, ctx->d_overlap, sizeof(int) * (size_t) ctx->nbc, hipMemcpyDeviceToHost));
+	if(halo_list && ctx->n_halo) HIP_TRY(hipMemcpy(halo_list, ctx->d_halo_list, sizeof(int) * (size_t) ctx->n_halo, hipMemcpyDeviceToHost));
+	if(inner_flags && ctx->pbc) HIP_TRY(hipMemcpy(inner_flags, ctx->d_inner_list, sizeof(int) * (size_t) ctx->pbc, hipMemcpyDeviceToHost));
+	if(n_halo) *n_halo = ctx->n_halo;
 	return MPM_OK;
 }
 

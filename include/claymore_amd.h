@@ -308,6 +308,13 @@ int mpm_g2p2g_interior(mpm_ctx* ctx, float dt, float next_dt);
 int mpm_halo_collect(mpm_ctx* ctx, int peer, int gid, int* dev_keys, float* dev_blocks, int capacity_blocks, int* nsend);
 /* reduce_grid_blocks (halo_kernels.cuh:82-97): add nrecv received blocks into grid `gid` (hardware f32 atomics). */
 int mpm_halo_reduce(mpm_ctx* ctx, int gid, const int* dev_keys, const float* dev_blocks, int nrecv);
+/* Debug read-out of the last tagging (mpm_halo_tag_end or mpm_mgsp_end), in the style of mpm_check_table / mpm_dump_grid; host arrays,
+ * each may be NULL: overlap[neighbor_blocks] = the marks, bit p set iff the block is shared with peer p (bit 31 is the sign bit);
+ * halo_list[*n_halo] = the halo particle blocks in no particular order (capacity: particle_blocks); inner_flags[particle_blocks] = 1 for
+ * an interior block, 0 for a halo block.  Block numbers index mpm_halo_keys' list.  MPM_ERR_INVALID before the first tagging.  Read-only
+ * (it waits for the context's streams).  Not to be called inside an open fused substep: between mpm_mgsp_rebuild_export and mpm_mgsp_end
+ * the marks already belong to the new partition while the counts that size the copies are still the old one's.  HIP library only. */
+int mpm_halo_dump(mpm_ctx* ctx, int* overlap, int* halo_list, int* n_halo, int* inner_flags);
 /* ---- fused multi-GPU substep: the same phases with ONE host synchronisation per substep ----
  * (the phase-by-phase calls above synchronise once each, like the reference's issue()/sync() barriers,
  * mgsp_benchmark.cuh:336-356; at 5 M particles per GPU that costs more than the kernels.)

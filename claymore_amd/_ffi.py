@@ -105,6 +105,8 @@ HIP_ONLY = {
     "get_diagnostics": (_i, [_vp, _P(Diagnostics)]),
     "retrieve_velocity": (_i, [_vp, _i, _vp, _vp, _vp, _P(_sz)]),
     "particle_momentum": (_i, [_vp, _i, _P(C.c_double)]),
+    "retrieve_stress": (_i, [_vp, _i, _vp, _vp, _vp, _P(_sz)]),
+    "stress_totals": (_i, [_vp, _i, _P(C.c_double)]),
     "halo_dump": (_i, [_vp, _vp, _vp, _ip, _vp]),
     "set_collision_clock": (_i, [_vp, _i, _f]),
     "get_collision_time": (_i, [_vp, _fp, _ip]),

@@ -1225,7 +1225,20 @@ int mpm_get_timers(mpm_ctx* ctx, mpm_timers* t) {
 	return MPM_OK;
 }
 
-// One per-particle readout of a model (readout_kernel<kind>, kReadState or kReadVelocity) into the caller's arrays: host[0] the positions,
+// The launch of readout_kernel<kind> for model m: the one place that knows which kinds read the grid.
+static void launch_readout(mpm_ctx* ctx, const Model& m, ReadoutKind kind, const ReadoutOut& out, hipStream_t s) {
+	if(!ctx->pbc) return;
+	const ReadoutArgs a = make_readout_args(ctx, m);
+	switch(kind) {
+	case kReadState: readout_kernel<kReadState><<<ctx->pbc, kReadoutThreads, 0, s>>>(a, nullptr, out); break;
+	case kReadVelocity: readout_kernel<kReadVelocity><<<ctx->pbc, kReadoutThreads, 0, s>>>(a, ctx->grid[0], out); break;
+	case kReadMomentum: readout_kernel<kReadMomentum><<<ctx->pbc, kReadoutThreads, 0, s>>>(a, ctx->grid[0], out); break;
+	case kReadStress: readout_kernel<kReadStress><<<ctx->pbc, kReadoutThreads, 0, s>>>(a, nullptr, out); break;
+	case kReadStressTotals: readout_kernel<kReadStressTotals><<<ctx->pbc, kReadoutThreads, 0, s>>>(a, nullptr, out); break;
+	}
+}
+
+// One per-particle readout of a model (readout_kernel<kind>: kReadState, kReadVelocity or kReadStress) into the caller's arrays: host[0] the positions,
 // host[1] and host[2] (null: not asked for) kReadoutWidth[kind][c] floats a particle.  Positions are staged in m.d_xyz, the other columns
 // in scratch released on every exit path (an output call, once per frame at most).  *n: the capacity of the arrays in, the particles
 // written out - MPM_ERR_CAPACITY if that is not all of them.
@@ -1235,15 +1248,14 @@ static int readout_particles(mpm_ctx* ctx, int model, ReadoutKind kind, float* c
 	Model& m		 = ctx->models[model];
 	const size_t cap = std::min(*n, m.n);
 	DevScratch<float> scratch[3];
-	ReadoutOut out {{m.d_xyz, nullptr, nullptr}, cap, ctx->d_counter, 0.0, nullptr};
+	ReadoutOut out {{m.d_xyz, nullptr, nullptr}, cap, ctx->d_counter, 0.0, nullptr, m.material, m.mc};
 	for(int c = 1; c < 3; ++c)
 		if(host[c]) {
 			HIP_TRY(scratch[c].alloc(kReadoutWidth[kind][c] * cap));
 			out.col[c] = scratch[c].p;
 		}
 	HIP_TRY(hipMemsetAsync(ctx->d_counter, 0, sizeof(unsigned long long), s));
-	if(ctx->pbc && kind == kReadState) readout_kernel<kReadState><<<ctx->pbc, kReadoutThreads, 0, s>>>(make_readout_args(ctx, m), nullptr, out);
-	if(ctx->pbc && kind == kReadVelocity) readout_kernel<kReadVelocity><<<ctx->pbc, kReadoutThreads, 0, s>>>(make_readout_args(ctx, m), ctx->grid[0], out);
+	launch_readout(ctx, m, kind, out, s);
 	HIP_TRY(hipGetLastError());
 	unsigned long long count = 0;
 	HIP_TRY(hipMemcpyAsync(&count, ctx->d_counter, sizeof(count), hipMemcpyDeviceToHost, s));
@@ -1270,22 +1282,31 @@ static int readout_velocity(mpm_ctx* ctx, int model, float* xyz, float* vel, flo
 	return readout_particles(ctx, model, kReadVelocity, host, n);
 }
 
-// {count, sum m v_p (3), sum 1/2 m |v_p|^2} of one model (model >= 0) or of all models (-1), from this context's own grid[0]:
-// readout_kernel<kReadMomentum>, one launch per model into one float64 accumulator.
-static int readout_momentum(mpm_ctx* ctx, int model, double out[5]) {
+// The totals of one model (model >= 0) or of all models (-1), one launch per model into one accumulator of nwords 64-bit words:
+// kReadMomentum {count, sum m v_p (3), sum 1/2 m |v_p|^2} from this context's own grid[0]; kReadStressTotals {count, sum V0 tau (6)} and,
+// in the eighth word, the float32 bit pattern of the largest von Mises stress (mpm_readout.hpp), handed back as a double.
+static int readout_totals(mpm_ctx* ctx, int model, ReadoutKind kind, int nwords, double* out) {
 	HIP_TRY(hipSetDevice(ctx->device));
 	hipStream_t s = ctx->s_compute;
 	DevScratch<double> d_out;
-	HIP_TRY(d_out.alloc(kMomentumSums));
-	HIP_TRY(hipMemsetAsync(d_out.p, 0, sizeof(double) * kMomentumSums, s));
+	HIP_TRY(d_out.alloc(nwords));
+	HIP_TRY(hipMemsetAsync(d_out.p, 0, sizeof(double) * nwords, s));
 	for(int mi = model < 0 ? 0 : model; mi < (model < 0 ? (int) ctx->models.size() : model + 1); ++mi) {
 		Model& m = ctx->models[mi];
-		if(ctx->pbc && m.n) readout_kernel<kReadMomentum><<<ctx->pbc, kReadoutThreads, 0, s>>>(make_readout_args(ctx, m), ctx->grid[0], ReadoutOut {{}, 0, nullptr, (double) m.mc.mass, d_out.p});
+		if(m.n) launch_readout(ctx, m, kind, ReadoutOut {{}, 0, nullptr, (double) (kind == kReadMomentum ? m.mc.mass : m.mc.volume), d_out.p, m.material, m.mc}, s);
 		HIP_TRY(hipGetLastError());
 	}
-	HIP_TRY(hipMemcpyAsync(out, d_out.p, sizeof(double) * kMomentumSums, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(out, d_out.p, sizeof(double) * nwords, hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
+	if(kind == kReadStressTotals) {
+		float q;
+		std::memcpy(&q, out + kStressSums, sizeof(q));
+		out[kStressSums] = (double) q;
+	}
 	return MPM_OK;
+}
+static int readout_momentum(mpm_ctx* ctx, int model, double out[5]) {
+	return readout_totals(ctx, model, kReadMomentum, kMomentumSums, out);
 }
 
 // The state checks of the single-context readouts: NOT_READY, then INVALID for a context of a group and for a grid that holds velocities.
@@ -1309,6 +1330,21 @@ int mpm_particle_momentum(mpm_ctx* ctx, int model, double out[5]) {
 	if(model < -1 || model >= (int) ctx->models.size() || !out) return fail(ctx, MPM_ERR_INVALID, "mpm_particle_momentum: bad model or NULL output array");
 	if(int rc = readout_state(ctx, "mpm_particle_momentum")) return rc;
 	return readout_momentum(ctx, model, out);
+}
+
+// Per-particle Cauchy stress, J, pressure and von Mises stress (readout_kernel<kReadStress>; an extension, the reference has no stress
+// output): from the records alone, so with mpm_retrieve_state's preconditions - any ready context, of a group or not, whatever the grid holds.
+int mpm_retrieve_stress(mpm_ctx* ctx, int model, float* xyz, float* stress6, float* scalars3, size_t* n) {
+	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
+	if(model < 0 || model >= (int) ctx->models.size() || !n || !xyz) return fail(ctx, MPM_ERR_INVALID, "mpm_retrieve_stress: bad model or NULL output array");
+	float* const host[3] = {xyz, stress6, scalars3};
+	return readout_particles(ctx, model, kReadStress, host, n);
+}
+
+int mpm_stress_totals(mpm_ctx* ctx, int model, double out[8]) {
+	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
+	if(model < -1 || model >= (int) ctx->models.size() || !out) return fail(ctx, MPM_ERR_INVALID, "mpm_stress_totals: bad model or NULL output array");
+	return readout_totals(ctx, model, kReadStressTotals, kStressSums + 1, out);
 }
 
 int mpm_retrieve_positions(mpm_ctx* ctx, int model, float* xyz, size_t* n) {

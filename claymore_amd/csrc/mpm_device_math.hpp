@@ -293,13 +293,16 @@ MPM_DEV StressScale stress_scale(const MaterialConst& mc) {
 // compute_stress<FIXED_COROTATED>, Projects/GMPM/constitutive_models.cuh:36-73.
 // P F^T = U diag(P_hat_k sigma_k) U^T with P_hat_k sigma_k = 2 mu (sigma_k - 1) sigma_k + lambda (J - 1) J.
 // refl: det F < 0 - the smallest singular value carries the sign (svd.cuh:590-770).
+// J_out (every model; the stress readout, mpm_readout.hpp; null on the substep path, where it folds away): receives det F of the state
+// the returned stress belongs to, formed from the principal values that produced it.
 constexpr int kFcSites = kEigSites + 1;
 template<int BASE, class Hook>
-MPM_DEV void stress_fixed_corotated(const StressScale& ss, const float (&b)[6], bool refl, float (&PF)[9], Hook& hk) {
+MPM_DEV void stress_fixed_corotated(const StressScale& ss, const float (&b)[6], bool refl, float (&PF)[9], Hook& hk, float* J_out = nullptr) {
 	float lam[3], U[9];
 	bool undeformed;
 	sym_eig3<BASE>(b, lam, U, hk, undeformed);
 	if(undeformed && !__any(refl)) {// sigma_k = 1, J = 1: P F^T = 0 exactly
+		if(J_out) *J_out = 1.f;
 #pragma unroll
 		for(int d = 0; d < 9; ++d) PF[d] = 0.f;
 		hk.template at<BASE + kEigSites>();
@@ -315,6 +318,7 @@ MPM_DEV void stress_fixed_corotated(const StressScale& ss, const float (&b)[6], 
 		sig[2] = (!m0 && !m1) ? -sig[2] : sig[2];
 	}
 	const float J  = sig[0] * sig[1] * sig[2];
+	if(J_out) *J_out = J;
 	const float vl = ss.lamv * (J - 1.0f) * J;
 	const float vm = ss.mu2v;
 	float d[3], pf[6];
@@ -335,7 +339,7 @@ MPM_DEV void stress_fixed_corotated(const MaterialConst& mc, const float (&b)[6]
 // A reflected F (refl) enters through |S| (:262) and leaves with det > 0 (the projection rebuilds U S_new V^T with S_new > 0).
 constexpr int kSandSites = kEigSites + 3;
 template<int BASE, class Hook>
-MPM_DEV void stress_sand(const MaterialConst& mc, const StressScale& ss, float (&b)[6], bool& refl, float& log_jp, float (&PF)[9], Hook& hk) {
+MPM_DEV void stress_sand(const MaterialConst& mc, const StressScale& ss, float (&b)[6], bool& refl, float& log_jp, float (&PF)[9], Hook& hk, float* J_out = nullptr) {
 	float lam[3], U[9];
 	bool undeformed;
 	sym_eig3<BASE>(b, lam, U, hk, undeformed);
@@ -392,12 +396,14 @@ MPM_DEV void stress_sand(const MaterialConst& mc, const StressScale& ss, float (
 	hk.template at<BASE + kEigSites + 1>();
 	if(!skip) {
 		const float trace_log_S = lnS[0] + lnS[1] + lnS[2];
+		if(J_out) *J_out = exp_fast(trace_log_S);// J = exp(sum ln S_new)
 		float d[3], pf[6];
 #pragma unroll
 		for(int k = 0; k < 3; ++k) d[k] = ss.mu2v * lnS[k] + ss.lamv * trace_log_S;
 		sym_from_eig(U, d, pf);
 		sym_expand(pf, PF);
 	} else {
+		if(J_out) *J_out = 1.f;
 #pragma unroll
 		for(int d = 0; d < 9; ++d) PF[d] = 0.f;
 	}
@@ -414,7 +420,7 @@ MPM_DEV void stress_sand(const MaterialConst& mc, float (&b)[6], bool& refl, flo
 // (the reference binary's --use_fast_math does the same).  refl = det F < 0.
 constexpr int kNaccSites = kEigSites + 2;
 template<int BASE, class Hook>
-MPM_DEV void stress_nacc(const MaterialConst& mc, const StressScale& ss, float (&b)[6], bool& refl, float& log_jp, float (&PF)[9], Hook& hk) {
+MPM_DEV void stress_nacc(const MaterialConst& mc, const StressScale& ss, float (&b)[6], bool& refl, float& log_jp, float (&PF)[9], Hook& hk, float* J_out = nullptr) {
 	float lam[3], U[9];
 	bool undeformed;
 	sym_eig3<BASE>(b, lam, U, hk, undeformed);
@@ -488,6 +494,7 @@ MPM_DEV void stress_nacc(const MaterialConst& mc, const StressScale& ss, float (
 		const float lg2Jn	   = 0.5f * __builtin_amdgcn_logf(Bn[0] * Bn[1] * Bn[2]);
 		const float Jn_abs	   = __builtin_amdgcn_exp2f(lg2Jn);
 		const float J2		   = Jn_abs * Jn_abs;
+		if(J_out) *J_out = neg ? -Jn_abs : Jn_abs;
 		const float dev_b_coeff = neg ? __builtin_nanf("") : mc.mu * __builtin_amdgcn_exp2f(lg2Jn * (-2.f / 3.f));
 		const float i_coeff	   = bm * .5f * ((J2 - 1.f) * 0.5f - (neg ? __builtin_nanf("") : lg2Jn * 0.693147180559945f));
 		const float trBn3	   = (Bn[0] + Bn[1] + Bn[2]) * (1.f / 3.f);
@@ -497,6 +504,7 @@ MPM_DEV void stress_nacc(const MaterialConst& mc, const StressScale& ss, float (
 		sym_from_eig(U, d, pf);
 		sym_expand(pf, PF);
 	} else {
+		if(J_out) *J_out = 1.f;
 #pragma unroll
 		for(int d = 0; d < 9; ++d) PF[d] = 0.f;
 	}

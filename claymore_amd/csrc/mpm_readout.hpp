@@ -7,6 +7,10 @@
 //   v_i = p_i / m_i (m_i > 0, else 0)   - the state BEFORE the next grid update: no gravity, walls or collision object
 //   v_p = sum_i w_ip v_i                - 27-node quadratic B-spline stencil, base node and weights those of G2P (lround_pos, bspline_weight_cells)
 //   C_p = D^-1 sum_i w_ip v_i (x_i - x_p)^T, D^-1 = 4 / dx^2, column-major: C[3 * c + r] = C_rc (G2P2G's A, mpm_g2p2g.hpp)
+//   kReadStress    x, the Cauchy stress and {J, pressure, von Mises} (an extension: the stress exists only in registers of the substep
+//                  kernels): the model's stress function on the stored state with a zero velocity gradient (readout_stress below,
+//                  INTEGRATION.md section 5) - from the record and row alone, like kReadState; it writes no bin
+//   kReadStressTotals  {count, sum V0 tau (6), max von Mises} of the same evaluation, reduced instead of written
 // One workgroup (256 lanes) per particle block.  The gathers stage the 2x2x2 grid blocks the block's stencils reach once in LDS as
 // velocities (8 KiB; a block that is not registered, or beyond an upper face, stages zero) and read each particle's 27 nodes from there at
 // G2P's cube-local stencil base ((base - 1) & 3) + 1, which also gives particles of cells -2 / -1 the reference's wrapped key.  Output
@@ -19,8 +23,9 @@ namespace mpm {
 
 constexpr int kReadoutThreads = 256;
 constexpr int kMomentumSums	  = 5;
+constexpr int kStressSums	  = 7;// count and the six sums; the maximum is an eighth word of its own
 
-enum ReadoutKind { kReadState, kReadVelocity, kReadMomentum };
+enum ReadoutKind { kReadState, kReadVelocity, kReadMomentum, kReadStress, kReadStressTotals };
 
 // What every readout reads of a model: the block numberings, the list and the bins (make_readout_args, claymore_hip.hip).
 struct ReadoutArgs {
@@ -37,17 +42,22 @@ struct ReadoutArgs {
 	const float* bins;
 };
 
-// Where a readout puts its result.  kReadState / kReadVelocity: slot o of col[c] holds kReadoutWidth[K][c] floats of one particle - col[0] x
-// (never null), then state9 and log Jp, or v and C; a null column is not written -, slots at or beyond `capacity` are dropped, and *counter
-// (zeroed by the caller) ends at the number of particles.  kReadMomentum: sums[0..4] (zeroed by the caller) += the totals, m = mass.
+// Where a readout puts its result.  kReadState / kReadVelocity / kReadStress: slot o of col[c] holds kReadoutWidth[K][c] floats of one
+// particle - col[0] x (never null), then state9 and log Jp, or v and C, or stress6 and scalars3; a null column is not written -, slots at or
+// beyond `capacity` are dropped, and *counter (zeroed by the caller) ends at the number of particles.  kReadMomentum: sums[0..4] (zeroed by
+// the caller) += the totals, weight = the particle mass.  kReadStressTotals: sums[0..6] += {count, sum V0 tau}, weight = the particle volume
+// V0, and the first 32 bits of sums[7] (zeroed too) take the float32 bit pattern of the largest von Mises stress by an integer atomicMax
+// (q >= 0: the patterns order as the values do).  The stress kinds read the model's material and constants from here.
 struct ReadoutOut {
 	float* col[3];
 	unsigned long long capacity;
 	unsigned long long* counter;
-	double mass;
+	double weight;
 	double* sums;
+	int material;
+	MaterialConst mc;
 };
-constexpr int kReadoutWidth[2][3] = {{3, 9, 1}, {3, 3, 9}};
+constexpr int kReadoutWidth[4][3] = {{3, 9, 1}, {3, 3, 9}, {0, 0, 0}, {3, 6, 3}};
 
 // The pieces the readouts share - the list walk's liveness test, the record fetch, the cube staging and the 27-node gather - so that the
 // list layouts, the record format and the stencil, tie and face rules live in one place.
@@ -123,33 +133,92 @@ __device__ __forceinline__ void readout_gather(const float4* s_v, const float p[
 			}
 }
 
+// What the stress readouts report of one stored particle (record `src`, row `row` of readout_position): tau = P F^T per unit reference
+// volume as {xx, yy, zz, xy, xz, yz} (sym_expand's six-vector) and J = det F of the state tau belongs to.
+//   solids   the model's stress function (mpm_device_math.hpp) with StressScale {2 mu, lambda, 1} on b decoded as G2P2G decodes it (|b00|,
+//            the reflection mark in its sign, log Jp from the row) - i.e. compute_stress with a zero velocity gradient.  The projected b and
+//            log Jp that SAND and NACC hand back stay in registers and are dropped: J is the one of the projected state, as tau is.
+//   J-fluid  p = bulk (J^-gamma - 1), tau = -J p I: the Tait pressure alone.  The viscous part, viscosity (C_p + C_p^T), needs the velocity
+//            gradient, which lives on the grid (kReadVelocity's C_p and its preconditions).
+// The material is uniform over the launch: a scalar branch, each arm with its own register allocation (the kernel gets the largest).
+// The stress functions vote across the wave (the undeformed early exit, __any(refl), the sweeps of sym_eig3): this is called after the walk
+// has dropped its dead lanes, so the votes run over live lanes only, and a live lane's result does not depend on its neighbours - the
+// early exits return exactly what the general path gives for b = I, and sym_eig3 rotates a lane by the lane's own verdict.
+__device__ __forceinline__ void readout_stress(int material, const MaterialConst& mc, const float* src, const float* row, float (&tau)[6], float& J) {
+	float txx, tyy, tzz, txy = 0.f, txz = 0.f, tyz = 0.f, det;// (scalars, not tau[]: see readout_cauchy)
+	if(material == 0) {
+		det			  = src[3];
+		const float p = mc.bulk * (__builtin_amdgcn_exp2f(-mc.gamma * __builtin_amdgcn_logf(det)) - 1.f);// J^-gamma as stress_jfluid forms it
+		txx = tyy = tzz = -det * p;
+	} else {
+		const StressScale ss {2.0f * mc.mu, mc.lambda, 1.0f};
+		NoHook nh;
+		float b[6] = {fabsf(src[3]), src[4], src[5], src[6], src[7], row[0]}, PF[9];
+		bool refl  = (__float_as_uint(src[3]) & kReflBit) != 0u;
+		if(material == 1) {
+			stress_fixed_corotated<0>(ss, b, refl, PF, nh, &det);
+		} else {
+			float lj = row[1];
+			if(material == 2)
+				stress_sand<0>(mc, ss, b, refl, lj, PF, nh, &det);
+			else
+				stress_nacc<0>(mc, ss, b, refl, lj, PF, nh, &det);
+		}
+		txx = PF[0], tyy = PF[4], tzz = PF[8], txy = PF[1], txz = PF[2], tyz = PF[5];
+	}
+	tau[0] = txx, tau[1] = tyy, tau[2] = tzz, tau[3] = txy, tau[4] = txz, tau[5] = tyz;
+	J = det;
+}
+// Cauchy stress sigma = tau / J and {J, pressure = -tr sigma / 3, von Mises q = sqrt(3/2 dev sigma : dev sigma)}.  Both stress kinds call
+// this, and the largest q of kReadStressTotals equals the largest q kReadStress wrote bit for bit: so the roundings are spelled out
+// (IEEE division, no contraction the compiler could choose differently in two kernels).  (tau[] is written once, after the material branch,
+// and the arrays of the stress readouts are indexed by constants only: written in each arm, the compiler merged the arms' stores into one
+// with a variable index and kept three entries of tau in scratch.)
+__device__ __forceinline__ void readout_cauchy(const float (&tau)[6], float J, float (&sigma)[6], float (&scal)[3]) {
+#pragma clang fp contract(off)
+	sigma[0] = __fdiv_rn(tau[0], J), sigma[1] = __fdiv_rn(tau[1], J), sigma[2] = __fdiv_rn(tau[2], J);
+	sigma[3] = __fdiv_rn(tau[3], J), sigma[4] = __fdiv_rn(tau[4], J), sigma[5] = __fdiv_rn(tau[5], J);
+	const float mean = (sigma[0] + sigma[1] + sigma[2]) * (1.0f / 3.0f);
+	const float d0 = sigma[0] - mean, d1 = sigma[1] - mean, d2 = sigma[2] - mean;
+	const float dd = (d0 * d0 + d1 * d1 + d2 * d2) + 2.0f * (sigma[3] * sigma[3] + sigma[4] * sigma[4] + sigma[5] * sigma[5]);
+	scal[0]		   = J;
+	scal[1]		   = -mean;
+	scal[2]		   = __fsqrt_rn(1.5f * dd);
+}
+
 // One workgroup per particle block; the walk's bound is a multiple of 64 and its stride 256, so every lane of a wave takes the same trips
 // (the slot counter is taken per wave).  kReadMomentum: each lane sums in float64, a wave folds its 64 lanes with __shfl_xor (DPP /
 // ds_swizzle), the 4 waves meet in LDS, and ONE set of five float64 atomics per workgroup goes to global memory (global_atomic_add_f64);
-// the order of the workgroups' atomics is unspecified, so the last bits of the sums may differ from run to run.
+// the order of the workgroups' atomics is unspecified, so the last bits of the sums may differ from run to run.  kReadStressTotals sums
+// the same way (seven float64) and carries the largest q as a float32 bit pattern: wave fold, integer atomicMax in LDS, one in global memory.
 template<ReadoutKind K>
 __global__ __launch_bounds__(kReadoutThreads) void readout_kernel(ReadoutArgs a, const float* __restrict__ grid, ReadoutOut out) {
-	constexpr bool kGrid = K != kReadState;// (the state readout neither stages nor reads the grid)
+	constexpr bool kGrid  = K == kReadVelocity || K == kReadMomentum;// (the state and stress readouts neither stage nor read the grid)
+	constexpr bool kSlots = K != kReadMomentum && K != kReadStressTotals;// per-particle output (else: totals)
+	constexpr int kSums	  = K == kReadStressTotals ? kStressSums : kMomentumSums;
 	__shared__ float4 s_v[kGrid ? 512 : 1];// node (x, y, z) of the 8^3 cube at (x << 6) | (y << 3) | z, {vx, vy, vz, 0}
 	__shared__ unsigned long long s_first;// the block's output range [s_first, s_first + n)
 	__shared__ unsigned s_next;			  // slots of that range handed out so far
-	__shared__ double s_red[kReadoutThreads / 64][kMomentumSums];
+	__shared__ double s_red[kReadoutThreads / 64][kSums];
+	__shared__ unsigned s_qmax;// kReadStressTotals: the block's largest q (bit pattern)
 	const int b = blockIdx.x;
 	const int n = a.size[b];
 	if(n == 0) return;
 	// (the block's scalars are loaded before the first global store, the slot atomic: so the compiler knows them uniform and unclobbered)
 	const int kx = a.cur_keys[3 * b], ky = a.cur_keys[3 * b + 1], kz = a.cur_keys[3 * b + 2];
 	const int* list = a.list + (size_t) a.row_of[b] * a.cfg.ppb;
-	if(K != kReadMomentum && threadIdx.x == 0) {
+	if(kSlots && threadIdx.x == 0) {
 		s_first = atomicAdd(out.counter, (unsigned long long) n);
 		s_next	= 0u;
 	}
+	if(K == kReadStressTotals && threadIdx.x == 0) s_qmax = 0u;
 	if constexpr(kGrid) readout_stage_cube(a.cfg, a.cur_table, grid, kx, ky, kz, s_v);
 	__syncthreads();
-	double acc[kMomentumSums] = {0.0, 0.0, 0.0, 0.0, 0.0};
+	double acc[kSums] = {};
+	float qmax		  = 0.f;
 	for(int pidib = threadIdx.x; pidib < ((n + 63) & ~63); pidib += kReadoutThreads) {
 		const bool live = readout_live(n, pidib, a.dense);
-		if(K == kReadMomentum && !live) continue;// (no slots: the lanes of a wave need not agree)
+		if(!kSlots && !live) continue;// (no slots: the lanes of a wave need not agree)
 		float p[3]		 = {0.f, 0.f, 0.f};
 		const float *src = nullptr, *row = nullptr;
 		if(live) src = readout_position(a, list[pidib], kx, ky, kz, p, &row);
@@ -161,6 +230,14 @@ __global__ __launch_bounds__(kReadoutThreads) void readout_kernel(ReadoutArgs a,
 			acc[2] += (double) v[1];
 			acc[3] += (double) v[2];
 			acc[4] += (double) v[0] * v[0] + (double) v[1] * v[1] + (double) v[2] * v[2];
+		} else if constexpr(K == kReadStressTotals) {
+			float tau[6], sigma[6], scal[3], J;
+			readout_stress(out.material, out.mc, src, row, tau, J);
+			readout_cauchy(tau, J, sigma, scal);
+			acc[0] += 1.0;
+			acc[1] += (double) tau[0], acc[2] += (double) tau[1], acc[3] += (double) tau[2];
+			acc[4] += (double) tau[3], acc[5] += (double) tau[4], acc[6] += (double) tau[5];
+			qmax = fmaxf(qmax, scal[2]);
 		} else {
 			const unsigned long long live_mask = __ballot(live);
 			if(live_mask == 0ull) continue;
@@ -191,6 +268,19 @@ __global__ __launch_bounds__(kReadoutThreads) void readout_kernel(ReadoutArgs a,
 					}
 				}
 				if(logjp) logjp[o] = a.nch - rec_floats(a.nch) == 2 ? row[1] : 0.f;
+			} else if constexpr(K == kReadStress) {
+				float *stress6 = out.col[1], *scalars3 = out.col[2];
+				float tau[6], sigma[6], scal[3], J;
+				readout_stress(out.material, out.mc, src, row, tau, J);
+				readout_cauchy(tau, J, sigma, scal);
+				if(stress6) {
+					float* s = stress6 + 6 * o;
+					s[0] = sigma[0], s[1] = sigma[1], s[2] = sigma[2], s[3] = sigma[3], s[4] = sigma[4], s[5] = sigma[5];
+				}
+				if(scalars3) {
+					float* s = scalars3 + 3 * o;
+					s[0] = scal[0], s[1] = scal[1], s[2] = scal[2];
+				}
 			} else {
 				float *vel = out.col[1], *affine9 = out.col[2];
 				const float cdinv = a.cfg.d_inv * a.cfg.dx;// A is gathered in cell units: C = D^-1 A dx
@@ -204,20 +294,27 @@ __global__ __launch_bounds__(kReadoutThreads) void readout_kernel(ReadoutArgs a,
 			}
 		}
 	}
-	if constexpr(K == kReadMomentum) {
+	if constexpr(!kSlots) {
 #pragma unroll
-		for(int d = 0; d < kMomentumSums; ++d)
+		for(int d = 0; d < kSums; ++d)
 #pragma unroll
 			for(int off = 32; off > 0; off >>= 1) acc[d] += __shfl_xor(acc[d], off);
-		if((threadIdx.x & 63) == 0)
-			for(int d = 0; d < kMomentumSums; ++d) s_red[threadIdx.x >> 6][d] = acc[d];
+		if constexpr(K == kReadStressTotals) {
+#pragma unroll
+			for(int off = 32; off > 0; off >>= 1) qmax = fmaxf(qmax, __shfl_xor(qmax, off));
+		}
+		if((threadIdx.x & 63) == 0) {
+			for(int d = 0; d < kSums; ++d) s_red[threadIdx.x >> 6][d] = acc[d];
+			if(K == kReadStressTotals) atomicMax(&s_qmax, __float_as_uint(qmax));
+		}
 		__syncthreads();
-		if(threadIdx.x < kMomentumSums) {
+		if(threadIdx.x < kSums) {
 			double t = 0.0;
 			for(int w = 0; w < kReadoutThreads / 64; ++w) t += s_red[w][threadIdx.x];
-			const double scale = threadIdx.x == 0 ? 1.0 : threadIdx.x < 4 ? out.mass : 0.5 * out.mass;
+			const double scale = threadIdx.x == 0 ? 1.0 : K == kReadStressTotals || threadIdx.x < 4 ? out.weight : 0.5 * out.weight;
 			atomicAdd(out.sums + threadIdx.x, t * scale);
 		}
+		if(K == kReadStressTotals && threadIdx.x == 0) atomicMax(reinterpret_cast<unsigned*>(out.sums + kStressSums), s_qmax);
 	}
 }
 

@@ -20,6 +20,11 @@ def momentum_dict(out):
     return {"count": int(out[0]), "momentum": np.array(out[1:4], dtype=np.float64), "kinetic": float(out[4])}
 
 
+def stress_totals_dict(out):
+    """The eight doubles of mpm_stress_totals as a dict."""
+    return {"count": int(out[0]), "stress_integral": np.array(out[1:7], dtype=np.float64), "max_von_mises": float(out[7])}
+
+
 class Engine:
     """One simulation context on one device.
 
@@ -174,6 +179,26 @@ class Engine:
         out = (C.c_double * 5)()
         self._check(self.api.particle_momentum(self.ctx, -1 if model is None else int(model), out))
         return momentum_dict(out)
+
+    def retrieve_stress(self, model=0):
+        """Per-particle stress evaluated from the stored state (mpm_retrieve_stress, HIP library only): (xyz, stress6, scalars3) in one
+        particle order.  stress6: the Cauchy stress {xx, yy, zz, xy, xz, yz}; scalars3: {J, pressure = -tr sigma / 3, von Mises q}.  xyz has
+        the bits retrieve_state returns, so the two can be joined on them.  The J-fluid's stress is its Tait pressure alone."""
+        n = C.c_size_t(self.models[model]["n"])
+        xyz = np.empty((n.value, 3), dtype=np.float32)
+        s6 = np.empty((n.value, 6), dtype=np.float32)
+        sc = np.empty((n.value, 3), dtype=np.float32)
+        self._check(self.api.retrieve_stress(self.ctx, model, xyz.ctypes.data_as(C.c_void_p), s6.ctypes.data_as(C.c_void_p),
+                                             sc.ctypes.data_as(C.c_void_p), C.byref(n)))
+        k = n.value
+        return xyz[:k], s6[:k], sc[:k]
+
+    def stress_totals(self, model=None):
+        """Totals of the stress readout, reduced on the device (mpm_stress_totals, HIP library only): {"count", "stress_integral":
+        sum_p V0 tau_p = sum_p V_p sigma_p (6,), "max_von_mises"}; all models when model is None."""
+        out = (C.c_double * 8)()
+        self._check(self.api.stress_totals(self.ctx, -1 if model is None else int(model), out))
+        return stress_totals_dict(out)
 
     def counts(self):
         c = _ffi.Counts()

@@ -10,7 +10,12 @@
 // (text level set; sampled on the same lattice where phi < 0 - deterministic, unlike the reference's rand()-based
 // Poisson sampling, Library/MnSystem/IO/PoissonDisk/SampleGenerator.h:112-176).  simulation.output_velocity (default false):
 // every frame also carries a 3-float point attribute "v" (mpm_retrieve_velocity; frame 0: the model's initial velocity);
-// without it the frames are byte for byte the position-only ones.
+// without it the frames are byte for byte the position-only ones.  simulation.output_stress (default false): every frame also carries the
+// point attributes "stress" (6 floats: the Cauchy stress {xx, yy, zz, xy, xz, yz}), "J", "pressure" and "vonmises" (1 float each) of
+// mpm_retrieve_stress (frame 0: the stress-free initial state, J = 1).  With both keys the two readouts come back in different particle
+// orders: each is sorted on the bits of its positions (which are the same bits in both) and the stress rows are written in the order of the
+// velocity readout.
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -104,6 +109,19 @@ pio::Points sample_model(const mj::Value& model, int bits, const std::string& sc
 	std::exit(EXIT_FAILURE);
 }
 
+// The rows of xyz (n x 3 floats) in ascending order of their bits (x, then y, then z, as unsigned integers): two readouts of one state hold
+// the same position bits, so equal ranks are the same particle.
+std::vector<size_t> order_by_position_bits(const float* xyz, size_t n) {
+	std::vector<size_t> order(n);
+	for(size_t i = 0; i < n; ++i) order[i] = i;
+	std::sort(order.begin(), order.end(), [xyz](size_t a, size_t b) {
+		uint32_t ka[3], kb[3];
+		std::memcpy(ka, xyz + 3 * a, sizeof(ka));
+		std::memcpy(kb, xyz + 3 * b, sizeof(kb));
+		return ka[0] != kb[0] ? ka[0] < kb[0] : ka[1] != kb[1] ? ka[1] < kb[1] : ka[2] < kb[2];
+	});
+	return order;
+}
 }// namespace
 
 int main(int argc, char** argv) {
@@ -136,6 +154,7 @@ int main(int argc, char** argv) {
 	const int bits		 = (int) num(sim, "domain_bits", 8);
 	const std::string out_dir = sim.has("output_dir") ? sim["output_dir"].string() : ".";
 	const bool out_vel		  = sim.has("output_velocity") && sim["output_velocity"].type == mj::Value::Bool && sim["output_velocity"].b;
+	const bool out_stress	  = sim.has("output_stress") && sim["output_stress"].type == mj::Value::Bool && sim["output_stress"].b;
 	std::printf("simulation: gpuid[%d], defaultDt[%g], fps[%d], frames[%d]\n", gpuid, dt_def, fps, frames);
 
 	mpm_config cfg;
@@ -187,11 +206,13 @@ int main(int argc, char** argv) {
 		if(rc) die(ctx, rc);
 		std::printf("init %d-th model with %zu particles\n", id, pts.size());
 		const std::string frame0 = out_dir + "/model_id[" + std::to_string(id) + "]_frame[0].bgeo";
-		if(out_vel) {
-			std::vector<float> v(3 * pts.size());
-			for(size_t i = 0; i < pts.size(); ++i)
-				for(int d = 0; d < 3; ++d) v[3 * i + d] = v0[d];
-			pio::write_bgeo(frame0, pts.empty() ? nullptr : pts[0].data(), pts.size(), v.data());
+		if(out_vel || out_stress) {
+			std::vector<float> v(out_vel ? 3 * pts.size() : 0), s9(out_stress ? 9 * pts.size() : 0, 0.f);
+			for(size_t i = 0; i < pts.size(); ++i) {
+				for(int d = 0; d < 3 && out_vel; ++d) v[3 * i + d] = v0[d];
+				if(out_stress) s9[9 * i + 6] = 1.f;// J
+			}
+			pio::write_bgeo_frame(frame0, pts.empty() ? nullptr : pts[0].data(), pts.size(), out_vel ? v.data() : nullptr, out_stress ? s9.data() : nullptr);
 		} else
 			pio::write_bgeo(frame0, pts.empty() ? nullptr : pts[0].data(), pts.size());
 		counts.push_back(pts.size());
@@ -207,7 +228,7 @@ int main(int argc, char** argv) {
 	std::printf("block count on device %d: %d, %d, %d\n", gpuid, c.particle_blocks, c.neighbor_blocks, c.exterior_blocks);
 	float cur_time = 0.f;
 	long steps	   = 0;
-	std::vector<float> buf, vbuf;
+	std::vector<float> buf, vbuf, sbuf;
 	pio::AsyncWriter io;
 	const auto wall0 = std::chrono::steady_clock::now();
 	for(int frame = 1; frame <= frames; ++frame) {
@@ -232,18 +253,49 @@ int main(int argc, char** argv) {
 		std::printf("frame %d: t %.6f, %ld substeps, blocks %d/%d/%d, last substep: grid %.3f ms g2p2g %.3f ms partition %.3f ms\n", frame, cur_time, steps, c.particle_blocks, c.neighbor_blocks, c.exterior_blocks, tm.grid_update_ms, tm.g2p2g_ms, tm.partition_ms);
 		for(size_t mi = 0; mi < counts.size(); ++mi) {// output_model, :594-634
 			buf.resize(3 * counts[mi]);
+			vbuf.clear();
+			sbuf.clear();
 			size_t n = counts[mi];
 			if(out_vel) {
 				vbuf.resize(3 * counts[mi]);
 				rc = mpm_retrieve_velocity(ctx, (int) mi, buf.data(), vbuf.data(), nullptr, &n);
-			} else
+			} else if(!out_stress)
 				rc = mpm_retrieve_positions(ctx, (int) mi, buf.data(), &n);
 			if(rc) die(ctx, rc);
+			if(out_stress) {
+				std::vector<float> sx(3 * counts[mi]), s6(6 * counts[mi]), sc(3 * counts[mi]);
+				size_t ns = counts[mi];
+				rc		  = mpm_retrieve_stress(ctx, (int) mi, sx.data(), s6.data(), sc.data(), &ns);
+				if(rc) die(ctx, rc);
+				// row k of the stress readout goes where the velocity readout has the same position bits (alone: its own order)
+				std::vector<size_t> to(ns);
+				if(out_vel) {
+					const std::vector<size_t> ov = order_by_position_bits(buf.data(), n), os = order_by_position_bits(sx.data(), ns);
+					bool same = n == ns;
+					for(size_t k = 0; same && k < ns; ++k) {
+						same  = std::memcmp(&buf[3 * ov[k]], &sx[3 * os[k]], 3 * sizeof(float)) == 0;
+						to[os[k]] = ov[k];
+					}
+					if(!same) {
+						std::fprintf(stderr, "gmpm: the velocity and stress readouts of model %zu do not hold the same positions\n", mi);
+						die(ctx, MPM_ERR_INTERNAL);
+					}
+				} else {
+					for(size_t k = 0; k < ns; ++k) to[k] = k;
+					buf.swap(sx);
+					n = ns;
+				}
+				sbuf.resize(9 * ns);
+				for(size_t k = 0; k < ns; ++k) {
+					for(int d = 0; d < 6; ++d) sbuf[9 * to[k] + d] = s6[6 * k + d];
+					for(int d = 0; d < 3; ++d) sbuf[9 * to[k] + 6 + d] = sc[3 * k + d];
+				}
+			}
 			std::printf("total number of particles %zu\n", n);
 			// IO::insert_job (gmpm_simulator.cuh:626-632): the frame is written by the IO thread while the next frame is computed
 			const std::string fn = out_dir + "/model_id[" + std::to_string(mi) + "]_frame[" + std::to_string(frame) + "].bgeo";
-			if(out_vel)
-				io.write_bgeo_async(fn, buf, vbuf, n);
+			if(out_vel || out_stress)
+				io.write_bgeo_frame_async(fn, buf, vbuf, sbuf, n);
 			else
 				io.write_bgeo_async(fn, buf, n);
 		}

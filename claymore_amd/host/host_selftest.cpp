@@ -29,6 +29,19 @@ int main(int argc, char** argv) {
 		if(arr[0].size() != arr[1].size()) return 5;
 		return pio::write_bgeo(argv[4], arr[0].data(), arr[0].size() / 3, arr[1].data()) ? 0 : 4;
 	}
+	if(argc == 5 && !std::strcmp(argv[1], "--bgeo-stress-from")) {// host_selftest --bgeo-stress-from points.f32 stress9.f32 out.bgeo: "stress", "J", "pressure", "vonmises"
+		std::vector<float> arr[2];
+		for(int a = 0; a < 2; ++a) {
+			std::ifstream in(argv[2 + a], std::ios::binary | std::ios::ate);
+			if(!in) return 3;
+			const size_t bytes = (size_t) in.tellg();
+			arr[a].resize(bytes / sizeof(float));
+			in.seekg(0);
+			in.read(reinterpret_cast<char*>(arr[a].data()), (std::streamsize) bytes);
+		}
+		if(arr[0].size() * 3 != arr[1].size()) return 5;
+		return pio::write_bgeo_frame(argv[4], arr[0].data(), arr[0].size() / 3, nullptr, arr[1].data()) ? 0 : 4;
+	}
 	const char* text = R"({"simulation": {"gpuid": 0, "fps": 1200, "frames": 2, "default_dt": 5e-6},
 	  "models": [{"type": "particle", "file": "two_dragons.sdf", "constitutive": "jfluid", "offset": [0.1, 0.1, 0.1],
 	              "span": [1.0, 1.0, 1.0], "velocity": [0.0, -1.0, 0.0], "nested": {"a": [true, false, null, "s\"q"]}},

@@ -7,6 +7,9 @@
 // With a velocity array (gmpm's opt-in simulation.output_velocity) the frame is what partio writes for a second, VECTOR point attribute
 // "v" of 3 floats (BGEO.cpp:345-378): nPointAttrib 1, the attribute's definition behind the header - name as a big-endian 16-bit length and
 // its bytes, 16-bit size 3, 32-bit Houdini type 5 (vector), 3 zero defaults - and per point x y z w vx vy vz.
+// Further point attributes (gmpm's simulation.output_stress: "stress" of 6 floats, "J", "pressure", "vonmises" of 1) follow the same rule,
+// in the order they were added: a FLOAT attribute has Houdini type 0 and as many zero defaults as its size, and every point carries the
+// attributes' values behind w in that order.
 #pragma once
 #include <condition_variable>
 #include <deque>
@@ -37,32 +40,41 @@ inline void put_bef(std::vector<unsigned char>& o, float f) {
 	std::memcpy(&u, &f, 4);
 	put_be32(o, u);
 }
-inline bool write_bgeo(const std::string& filename, const float* xyz, size_t n, const float* vel = nullptr) {
+// A point attribute behind "position": `size` floats a point at data[size * i]; vector: partio's VECTOR (Houdini type 5), else FLOAT (0).
+struct BgeoAttr {
+	std::string name;
+	int size;
+	bool vector;
+	const float* data;
+};
+inline bool write_bgeo(const std::string& filename, const float* xyz, size_t n, const std::vector<BgeoAttr>& attrs) {
 	std::vector<unsigned char> o;
-	o.reserve(64 + n * (vel ? 28 : 16));
+	size_t width = 4;
+	for(const BgeoAttr& a: attrs) width += (size_t) a.size;
+	o.reserve(256 + n * 4 * width);
 	put_be32(o, ((((('B' << 8) | 'g') << 8) | 'e') << 8) | 'o');
 	o.push_back('V');
 	put_be32(o, 5);
 	put_be32(o, (uint32_t) n);// nPoints
 	for(int k = 0; k < 3; ++k) put_be32(o, 0);// nPrims, nPointGroups, nPrimGroups
-	put_be32(o, vel ? 1 : 0);				  // nPointAttrib
+	put_be32(o, (uint32_t) attrs.size());	  // nPointAttrib
 	for(int k = 0; k < 3; ++k) put_be32(o, 0);// nVertexAttrib, nPrimAttrib, nAttrib
-	if(vel) {
-		o.push_back(0);// name length 1 (16 bit), "v"
-		o.push_back(1);
-		o.push_back('v');
-		o.push_back(0);// size 3 (16 bit)
-		o.push_back(3);
-		put_be32(o, 5);// vector
-		for(int k = 0; k < 3; ++k) put_be32(o, 0);
+	for(const BgeoAttr& a: attrs) {
+		o.push_back((unsigned char) (a.name.size() >> 8));// name: 16-bit length and its bytes
+		o.push_back((unsigned char) a.name.size());
+		o.insert(o.end(), a.name.begin(), a.name.end());
+		o.push_back((unsigned char) (a.size >> 8));// 16-bit size
+		o.push_back((unsigned char) a.size);
+		put_be32(o, a.vector ? 5 : 0);
+		for(int k = 0; k < a.size; ++k) put_be32(o, 0);// defaults
 	}
 	for(size_t i = 0; i < n; ++i) {
 		put_bef(o, xyz[3 * i]);
 		put_bef(o, xyz[3 * i + 1]);
 		put_bef(o, xyz[3 * i + 2]);
 		put_bef(o, 1.0f);
-		if(vel)
-			for(int d = 0; d < 3; ++d) put_bef(o, vel[3 * i + d]);
+		for(const BgeoAttr& a: attrs)
+			for(int d = 0; d < a.size; ++d) put_bef(o, a.data[(size_t) a.size * i + d]);
 	}
 	o.push_back(0x00);// "beginExtra" / "endExtra" markers partio appends (BGEO.cpp:424-427)
 	o.push_back(0xff);
@@ -70,6 +82,32 @@ inline bool write_bgeo(const std::string& filename, const float* xyz, size_t n, 
 	if(!f) return false;
 	f.write((const char*) o.data(), (std::streamsize) o.size());
 	return (bool) f;
+}
+inline bool write_bgeo(const std::string& filename, const float* xyz, size_t n, const float* vel = nullptr) {
+	std::vector<BgeoAttr> attrs;
+	if(vel) attrs.push_back({"v", 3, true, vel});
+	return write_bgeo(filename, xyz, n, attrs);
+}
+// The point attributes of gmpm's frames: "v" from vel (may be null), then "stress", "J", "pressure", "vonmises" from stress6 and scalars3
+// of mpm_retrieve_stress, here as one array of 9 floats a point {stress6, J, pressure, vonmises} (may be null).  The scalar attributes are
+// strided views, so they are copied out first.
+inline bool write_bgeo_frame(const std::string& filename, const float* xyz, size_t n, const float* vel, const float* stress9) {
+	std::vector<BgeoAttr> attrs;
+	std::vector<float> s6, sc[3];
+	if(vel) attrs.push_back({"v", 3, true, vel});
+	if(stress9) {
+		s6.resize(6 * n);
+		for(auto& v: sc) v.resize(n);
+		for(size_t i = 0; i < n; ++i) {
+			for(int d = 0; d < 6; ++d) s6[6 * i + d] = stress9[9 * i + d];
+			for(int d = 0; d < 3; ++d) sc[d][i] = stress9[9 * i + 6 + d];
+		}
+		attrs.push_back({"stress", 6, false, s6.data()});
+		attrs.push_back({"J", 1, false, sc[0].data()});
+		attrs.push_back({"pressure", 1, false, sc[1].data()});
+		attrs.push_back({"vonmises", 1, false, sc[2].data()});
+	}
+	return write_bgeo(filename, xyz, n, attrs);
 }
 
 // The reference's lattice rule (Library/MnBase/Geometry/GeometrySampler.h:11-37): 8 particles per grid node at +-0.25 dx.
@@ -174,6 +212,11 @@ public:
 	}
 	void write_bgeo_async(std::string fn, std::vector<float> xyz, std::vector<float> vel, size_t n) {// with the "v" point attribute
 		insert_job([fn = std::move(fn), xyz = std::move(xyz), vel = std::move(vel), n] { write_bgeo(fn, xyz.data(), n, vel.data()); });
+	}
+	void write_bgeo_frame_async(std::string fn, std::vector<float> xyz, std::vector<float> vel, std::vector<float> stress9, size_t n) {// empty: attribute absent
+		insert_job([fn = std::move(fn), xyz = std::move(xyz), vel = std::move(vel), stress9 = std::move(stress9), n] {
+			write_bgeo_frame(fn, xyz.data(), n, vel.empty() ? nullptr : vel.data(), stress9.empty() ? nullptr : stress9.data());
+		});
 	}
 	void flush() {// IO::flush: wait until every queued job has been written
 		std::unique_lock<std::mutex> lk(mut_);

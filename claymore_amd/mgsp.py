@@ -440,6 +440,15 @@ class MgspGroupRank:
         self._check(self.api.group_particle_momentum(self.grp, -1 if model is None else int(model), out))
         return momentum_dict(out)
 
+    def retrieve_stress(self, model=0):
+        """This rank's particles of `model` as Engine.retrieve_stress (mpm_retrieve_stress of the rank's context, which a grouped context
+        does not refuse: the stress comes from the particle records alone).  Per rank, not collective."""
+        return self.eng.retrieve_stress(model)
+
+    def stress_totals(self, model=None):
+        """Engine.stress_totals over THIS rank's particles (per rank, not collective: sum the ranks' integrals, take the largest maximum)."""
+        return self.eng.stress_totals(model)
+
     def close(self):
         if self.grp:
             self.api.group_destroy(self.grp)

@@ -190,6 +190,30 @@ int mpm_retrieve_velocity(mpm_ctx* ctx, int model, float* xyz, float* vel, float
  *   (the mass the set-up P2G uses).  model = -1: all models.  Preconditions and errors those of mpm_retrieve_velocity (a NULL out is
  *   MPM_ERR_INVALID).  The order of the device's float64 additions is unspecified: the last bits may differ between calls. */
 int mpm_particle_momentum(mpm_ctx* ctx, int model, double out[5]);
+/* Extension (the reference has no stress output): what the material of a model is doing, per particle, evaluated from the stored state -
+ * b = F F^T with the sign of b00 marking a reflected F, and log Jp where the model has one (FC / SAND / NACC); J (J_FLUID).
+ *   tau (solids)  = P F^T per unit reference volume: the model's compute_stress on the stored state with a zero velocity gradient, by the
+ *                   device functions of the substep (claymore_amd/csrc/mpm_device_math.hpp, 2 mu / lambda unscaled).  SAND and NACC apply
+ *                   their return mapping to the stored state as a substep would; the projected b and log Jp are discarded (the readout
+ *                   writes no particle state), and tau and J are those of the projected state.
+ *   J (solids)    = det F from the principal stretches that produced tau (product of sigma_k = sqrt(lambda_k(b)), negative for a reflected
+ *                   F; SAND / NACC: of the projected stretches).
+ *   J_FLUID       p = bulk (J^-gamma - 1), sigma = -p I, tau = J sigma.  The viscous part is NOT included: it is
+ *                   viscosity (C_p + C_p^T) of mpm_retrieve_velocity's affine9, which needs the grid and has that call's preconditions.
+ *   stress6[6*i..]  the Cauchy stress sigma = tau / J in the order {xx, yy, zz, xy, xz, yz}; may be NULL.
+ *   scalars3[3*i..] {J, pressure = -tr sigma / 3, von Mises q = sqrt(3/2 dev sigma : dev sigma)}; may be NULL.
+ * xyz, stress6 and scalars3 share one order (unspecified); xyz is bit-identical to what mpm_retrieve_state returns for the same particle, so
+ * two readouts can be joined on the position bits.  *n: in = capacity in particles, out = particles written.
+ * Preconditions: those of mpm_retrieve_state - any context after set-up, member of a group or not, at any substep boundary, whatever the
+ * grid holds.  Errors: MPM_ERR_NOT_READY before mpm_initial_setup; MPM_ERR_INVALID for a bad model or a NULL xyz / n; MPM_ERR_CAPACITY
+ * when *n is too small (the first *n particles are written).  HIP library only. */
+int mpm_retrieve_stress(mpm_ctx* ctx, int model, float* xyz, float* stress6, float* scalars3, size_t* n);
+/* The totals of the same evaluation without per-particle output, reduced on the device:
+ *   out[0] = particle count, out[1..6] = sum_p V0 tau_p = sum_p V_p sigma_p in the order of stress6 (V0 = the model's `volume`; float64
+ *   sums), out[7] = max_p q (exactly the largest q mpm_retrieve_stress reports).  model = -1: all models.  Preconditions and errors those
+ *   of mpm_retrieve_stress (a NULL out is MPM_ERR_INVALID).  The order of the float64 additions is unspecified: the last bits of
+ *   out[1..6] may differ between calls. */
+int mpm_stress_totals(mpm_ctx* ctx, int model /* -1: all */, double out[8]);
 
 int mpm_get_counts(mpm_ctx* ctx, mpm_counts* counts);
 

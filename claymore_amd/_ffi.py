@@ -33,6 +33,16 @@ class CollisionObject(C.Structure):
                 ("rot_mat", C.c_float * 9), ("time", C.c_float), ("reserved", C.c_int * 3)]
 
 
+class CollisionShape(C.Structure):
+    _fields_ = [("kind", C.c_int), ("inside_out", C.c_int), ("a", C.c_float * 3), ("b", C.c_float * 3), ("radius", C.c_float),
+                ("reserved", C.c_int * 5)]
+
+
+SHAPE_HALFSPACE, SHAPE_SPHERE, SHAPE_BOX, SHAPE_CAPSULE = 1, 2, 3, 4
+SHAPE_NAMES = {"halfspace": SHAPE_HALFSPACE, "sphere": SHAPE_SPHERE, "box": SHAPE_BOX, "capsule": SHAPE_CAPSULE}
+MAX_COLLISION_SHAPES = 4
+
+
 class Counts(C.Structure):
     _fields_ = [("particle_blocks", C.c_int), ("neighbor_blocks", C.c_int), ("exterior_blocks", C.c_int),
                 ("model_count", C.c_int), ("bins", C.c_int64 * 8), ("particles", C.c_int64 * 8)]
@@ -110,6 +120,8 @@ HIP_ONLY = {
     "halo_dump": (_i, [_vp, _vp, _vp, _ip, _vp]),
     "set_collision_clock": (_i, [_vp, _i, _f]),
     "get_collision_time": (_i, [_vp, _fp, _ip]),
+    "set_collision_shape": (_i, [_vp, _i, _P(CollisionObject), _P(CollisionShape)]),
+    "test_collision_shape": (_i, [_P(CollisionObject), _P(CollisionShape), _f, _f, _vp, _sz, _vp, _i]),
     "checkpoint_size": (_i, [_vp, _P(_sz)]),
     "checkpoint_save": (_i, [_vp, _vp, _sz, _P(_sz)]),
     "checkpoint_load": (_i, [_vp, _vp, _sz]),

@@ -108,6 +108,9 @@ struct mpm_ctx {
 	CollisionObject collision {};// (collision.time is the clock: the time of the next grid update)
 	bool collision_running = false;// the clock advances by dt with every grid update (mpm_set_collision_clock)
 	float4* d_sdf = nullptr;
+	// analytic collision shapes (mpm_set_collision_shape): slot s is in use where shape[s].shape.kind != 0; they share the one clock above
+	ShapeSlot shape[kMaxShapes] {};
+	int shape_count = 0;// highest slot in use + 1
 	mpm_timers timers {};
 	float last_g2p2g_ms = 0.f;
 	// halo state (MGSP)
@@ -610,6 +613,20 @@ static CollisionArgs collision_tick(mpm_ctx* ctx, float dt) {
 	if(ctx->collision_running) ctx->collision.time = ctx->collision.time + dt;
 	return a;
 }
+// The same with analytic shapes installed: one pose per installed collider, all at the one clock's time T, which then advances once.
+static ShapeArgs shapes_tick(mpm_ctx* ctx, float dt) {
+	ShapeArgs a {};
+	const float T = ctx->collision.time;
+	a.count		  = ctx->shape_count;
+	a.has_field	  = ctx->has_collision ? 1 : 0;
+	if(ctx->has_collision) a.field = CollisionArgs {ctx->collision, collision_pose(ctx->collision, T)};
+	for(int i = 0; i < ctx->shape_count; ++i) {
+		a.slot[i] = ctx->shape[i];
+		if(a.slot[i].shape.kind) a.slot[i].pose = collision_pose(a.slot[i].obj, T);
+	}
+	if(ctx->collision_running) ctx->collision.time = T + dt;
+	return a;
+}
 
 // grid-update phase, gmpm_simulator.cuh:326-347
 static int launch_grid_update(mpm_ctx* ctx, float dt) {
@@ -623,7 +640,9 @@ static int launch_grid_update(mpm_ctx* ctx, float dt) {
 	HIP_TRY(hipMemsetAsync(ctx->d_maxvel, 0, sizeof(unsigned) * kMaxVelSlots * kMaxVelStride, s));
 	if(ctx->nbc) {
 		const int est = std::min(ctx->g.cap, ctx->nbc + ctx->nbc / 16 + 64);// (an estimate between two synchronisations of mpm_run_fixed)
-		if(ctx->has_collision)
+		if(ctx->shape_count)
+			grid_update_shapes_kernel<<<cdiv(est, 4), 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, shapes_tick(ctx, dt), ctx->d_maxvel);
+		else if(ctx->has_collision)
 			grid_update_collision_kernel<<<cdiv(est, 4), 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, collision_tick(ctx, dt), ctx->d_maxvel);
 		else
 			grid_update_kernel<<<cdiv(est, 16), 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, ctx->d_maxvel);
@@ -836,7 +855,9 @@ static int launch_rebuild(mpm_ctx* ctx, float fuse_dt = 0.f, bool without_prepar
 	const unsigned rg8 = std::max(1u, std::min(4096u, cdiv((size_t) ebc_est * 8, 256))), rg32 = std::max(1u, std::min(8192u, cdiv((size_t) ebc_est * 32, 256)));
 	register_blocks_kernel<0, 1><<<rg8, 256, 0, s>>>(g, &st[ST_CNT_P], nullptr, &st[ST_CNT_N], &st[ST_PBC], Pn.table, Pn.keys, st);
 	if(fused) {
-		if(ctx->has_collision)
+		if(ctx->shape_count)
+			carry_grid_shapes_kernel<<<2048, 256, 0, s>>>(g, st, Pn.keys, Pr.table, ctx->grid[1], ctx->grid[0], fuse_dt, ctx->d_maxvel, shapes_tick(ctx, fuse_dt));
+		else if(ctx->has_collision)
 			carry_grid_kernel<true, true><<<2048, 256, 0, s>>>(g, st, Pn.keys, Pr.table, ctx->grid[1], ctx->grid[0], fuse_dt, ctx->d_maxvel, collision_tick(ctx, fuse_dt));
 		else
 			carry_grid_kernel<true><<<2048, 256, 0, s>>>(g, st, Pn.keys, Pr.table, ctx->grid[1], ctx->grid[0], fuse_dt, ctx->d_maxvel, NoCollision {});
@@ -1182,16 +1203,82 @@ int mpm_set_collision_object(mpm_ctx* ctx, const mpm_collision_object* obj, cons
 	return MPM_OK;
 }
 
+// Analytic collision shapes ------------------------------------------------------------------------------------------------------------
+static bool shape_finite3(const float* v) {
+	return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]);
+}
+// mpm_collision_object + mpm_collision_shape -> the slot the kernels read; nullptr, or the message that names the offending field
+static const char* make_shape_slot(const mpm_collision_object* obj, const mpm_collision_shape* sh, ShapeSlot& out) {
+	if(sh->kind < MPM_SHAPE_HALFSPACE || sh->kind > MPM_SHAPE_CAPSULE) return "collision shape: unknown kind";
+	if(obj->type < MPM_BOUNDARY_STICKY || obj->type > MPM_BOUNDARY_SEPARATE) return "collision shape: boundary type outside 0..2";
+	for(int d = 0; d < 3; ++d)
+		if(sh->a[d] != sh->a[d]) return "collision shape: NaN in a";
+	if(sh->radius != sh->radius) return "collision shape: NaN in radius";
+	if(sh->kind != MPM_SHAPE_SPHERE)
+		for(int d = 0; d < 3; ++d)
+			if(sh->b[d] != sh->b[d]) return "collision shape: NaN in b";
+	ShapeSlot c {};
+	c.shape.kind	   = sh->kind;
+	c.shape.inside_out = sh->inside_out ? 1 : 0;
+	for(int d = 0; d < 3; ++d) c.shape.a[d] = sh->a[d], c.shape.b[d] = sh->b[d];
+	c.shape.radius = sh->radius;
+	if(sh->kind == MPM_SHAPE_SPHERE || sh->kind == MPM_SHAPE_CAPSULE) {
+		if(!(sh->radius > 0.f) || !std::isfinite(sh->radius)) return "collision shape: radius must be finite and > 0";
+	} else
+		c.shape.radius = 0.f;
+	if(sh->kind == MPM_SHAPE_SPHERE) c.shape.b[0] = c.shape.b[1] = c.shape.b[2] = 0.f;
+	if(sh->kind == MPM_SHAPE_HALFSPACE) {
+		if(!shape_finite3(sh->b)) return "collision shape: normal b must be finite";
+		const float len = sqrtf(sh->b[0] * sh->b[0] + sh->b[1] * sh->b[1] + sh->b[2] * sh->b[2]);
+		if(!(len > 0.f) || !std::isfinite(len)) return "collision shape: normal b must not be zero";
+		for(int d = 0; d < 3; ++d) c.shape.b[d] = sh->b[d] / len;// (a unit axis stays exactly itself)
+	}
+	if(sh->kind == MPM_SHAPE_BOX)
+		for(int d = 0; d < 3; ++d)
+			if(!(sh->b[d] > 0.f) || !std::isfinite(sh->b[d])) return "collision shape: half extents b must be finite and > 0";
+	if(sh->kind == MPM_SHAPE_CAPSULE && sh->a[0] == sh->b[0] && sh->a[1] == sh->b[1] && sh->a[2] == sh->b[2]) return "collision shape: capsule end points a and b coincide";
+	CollisionObject& o = c.obj;
+	o.type	   = obj->type;
+	o.friction = obj->friction;
+	o.scale	   = obj->scale;
+	o.dsdt	   = obj->dsdt;
+	for(int d = 0; d < 3; ++d) o.trans[d] = obj->trans[d], o.trans_vel[d] = obj->trans_vel[d], o.omega[d] = obj->omega[d];
+	for(int i = 0; i < 9; ++i) o.rot[i] = obj->rot_mat[i];
+	o.time	= obj->time;
+	o.field = nullptr;
+	out		= c;
+	return nullptr;
+}
+
+int mpm_set_collision_shape(mpm_ctx* ctx, int slot, const mpm_collision_object* obj, const mpm_collision_shape* shape) {
+	if(!ctx) return MPM_ERR_INVALID;
+	if(slot < 0 || slot >= MPM_MAX_COLLISION_SHAPES) return fail(ctx, MPM_ERR_INVALID, "collision shape: slot outside 0..3");
+	ShapeSlot c {};
+	if(obj) {
+		if(!shape) return fail(ctx, MPM_ERR_INVALID, "collision shape: obj without a shape");
+		if(const char* msg = make_shape_slot(obj, shape, c)) return fail(ctx, MPM_ERR_INVALID, msg);
+	}
+	HIP_TRY(hipSetDevice(ctx->device));
+	HIP_TRY(hipDeviceSynchronize());
+	ctx->shape[slot]	   = c;// (kind 0: empty)
+	ctx->collision_running = false;// installing or removing a collider stops the clock
+	if(obj) ctx->collision.time = obj->time;
+	ctx->shape_count = 0;
+	for(int i = 0; i < MPM_MAX_COLLISION_SHAPES; ++i)
+		if(ctx->shape[i].shape.kind) ctx->shape_count = i + 1;
+	return MPM_OK;
+}
+
 int mpm_set_collision_clock(mpm_ctx* ctx, int running, float time) {
 	if(!ctx) return MPM_ERR_INVALID;
-	if(!ctx->has_collision) return fail(ctx, MPM_ERR_INVALID, "no collision object installed");
+	if(!ctx->has_collision && !ctx->shape_count) return fail(ctx, MPM_ERR_INVALID, "no collision object installed");
 	ctx->collision.time	   = time;
 	ctx->collision_running = running != 0;
 	return MPM_OK;
 }
 int mpm_get_collision_time(mpm_ctx* ctx, float* time, int* running) {
 	if(!ctx) return MPM_ERR_INVALID;
-	if(!ctx->has_collision) return fail(ctx, MPM_ERR_INVALID, "no collision object installed");
+	if(!ctx->has_collision && !ctx->shape_count) return fail(ctx, MPM_ERR_INVALID, "no collision object installed");
 	if(time) *time = ctx->collision.time;
 	if(running) *running = ctx->collision_running ? 1 : 0;
 	return MPM_OK;
@@ -1425,6 +1512,23 @@ int mpm_test_stress(int material, const mpm_material_params* p, const float* F, 
 	test_stress_kernel<<<cdiv(n, 256), 256>>>(material, make_material_const(*p), n, dF.p, dL.p, dO.p, nullptr);
 	HIP_TRY0(hipGetLastError());
 	HIP_TRY0(hipMemcpy(out19, dO.p, sizeof(float) * 19 * n, hipMemcpyDeviceToHost));
+	return MPM_OK;
+}
+
+int mpm_test_collision_shape(const mpm_collision_object* obj, const mpm_collision_shape* shape, float time, float dx, const float* xyz, size_t n, float* out4, int device) {
+	(void) dx;// (positions are domain points already; kept for the call shape of the grid kernels)
+	if(!obj || !shape || !xyz || !out4 || n == 0) return MPM_ERR_INVALID;
+	ShapeSlot c {};
+	if(make_shape_slot(obj, shape, c)) return MPM_ERR_INVALID;
+	c.pose = collision_pose(c.obj, time);
+	HIP_TRY0(hipSetDevice(device));
+	DevScratch<float> dX, dO;
+	HIP_TRY0(dX.alloc(3 * n));
+	HIP_TRY0(dO.alloc(4 * n));
+	HIP_TRY0(hipMemcpy(dX.p, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
+	test_collision_shape_kernel<<<cdiv(n, 256), 256>>>(c, n, dX.p, dO.p);
+	HIP_TRY0(hipGetLastError());
+	HIP_TRY0(hipMemcpy(out4, dO.p, sizeof(float) * 4 * n, hipMemcpyDeviceToHost));
 	return MPM_OK;
 }
 

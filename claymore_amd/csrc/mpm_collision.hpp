@@ -80,12 +80,13 @@ inline CollisionPose collision_pose(const CollisionObject& o, float t) {
 	return p;
 }
 
-// detect_and_resolve_collision (:164-248) behind the pose; node = integer node coordinates; bc_lo / bc_hi = query_sdf's domain box (:141-146)
-MPM_DEV void collision_resolve(const CollisionObject& o, const CollisionPose& p, const int (&node)[3], float dx, int N, float bc_lo, float bc_hi, float (&vel)[3]) {
+// The material-point part of detect_and_resolve_collision (:164-187): a domain point X (a node: (float) node * dx) -> xmt = X - shift and its
+// position x in the coordinates the level set's samples (or an analytic shape, mpm_collision_shapes.hpp) are given in.
+MPM_DEV void collision_material_point(const CollisionObject& o, const CollisionPose& p, const float (&X)[3], float (&xmt)[3], float (&x)[3]) {
 #pragma clang fp contract(off)
-	float xmt[3], x0[3], x[3];
+	float x0[3];
 #pragma unroll
-	for(int d = 0; d < 3; ++d) xmt[d] = (float) node[d] * dx - p.shift[d];
+	for(int d = 0; d < 3; ++d) xmt[d] = X[d] - p.shift[d];
 	const float (&rot)[9] = p.rot;
 #pragma unroll
 	for(int d = 0; d < 3; ++d) x0[d] = xmt[d] * p.inv;
@@ -94,6 +95,17 @@ MPM_DEV void collision_resolve(const CollisionObject& o, const CollisionPose& p,
 	x[2] = rot[6] * x0[0] + rot[7] * x0[1] + rot[8] * x0[2];
 #pragma unroll
 	for(int d = 0; d < 3; ++d) x[d] = x[d] * o.scale + o.trans[d];
+}
+
+MPM_DEV void collision_respond(const CollisionObject& o, const CollisionPose& p, const float (&xmt)[3], const float (&x)[3], const float (&n)[3], float (&vel)[3]);
+
+// detect_and_resolve_collision (:164-248) behind the pose; node = integer node coordinates; bc_lo / bc_hi = query_sdf's domain box (:141-146)
+MPM_DEV void collision_resolve(const CollisionObject& o, const CollisionPose& p, const int (&node)[3], float dx, int N, float bc_lo, float bc_hi, float (&vel)[3]) {
+#pragma clang fp contract(off)
+	float X[3], xmt[3], x[3];
+#pragma unroll
+	for(int d = 0; d < 3; ++d) X[d] = (float) node[d] * dx;
+	collision_material_point(o, p, X, xmt, x);
 	// query_sdf
 	if(x[0] < bc_lo || x[0] >= bc_hi || x[1] < bc_lo || x[1] >= bc_hi || x[2] < bc_lo || x[2] >= bc_hi) return;
 	int cid[3];
@@ -123,6 +135,14 @@ MPM_DEV void collision_resolve(const CollisionObject& o, const CollisionPose& p,
 #pragma unroll
 	for(int d = 0; d < 3; ++d) n[d] /= nn;
 	if(!(sdis <= 0.f)) return;
+	collision_respond(o, p, xmt, x, n, vel);
+}
+
+// The response part (:197-248) for a touched node (sdis <= 0) with unit normal n in material coordinates: the level set's and every
+// analytic shape's.
+MPM_DEV void collision_respond(const CollisionObject& o, const CollisionPose& p, const float (&xmt)[3], const float (&x)[3], const float (&n)[3], float (&vel)[3]) {
+#pragma clang fp contract(off)
+	const float (&rot)[9] = p.rot;
 	// object velocity in deformation space (:197-204)
 	float v_obj[3], radius[3], mat_vel[3];
 	col_cross(v_obj, o.omega, xmt);

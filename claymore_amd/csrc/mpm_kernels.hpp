@@ -32,6 +32,7 @@
 
 #include "mpm_device_math.hpp"
 #include "mpm_collision.hpp"
+#include "mpm_collision_shapes.hpp"
 
 namespace mpm {
 
@@ -353,6 +354,89 @@ __global__ __launch_bounds__(256) void grid_update_collision_kernel(GridCfg cfg,
 		unsigned* slot		= max_vel_bits + (blockIdx.x & (kMaxVelSlots - 1)) * kMaxVelStride;
 		if(bits > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, bits);
 	}
+}
+
+// Grid update with analytic collision shapes (mpm_collision_shapes.hpp; an extension): per massed cell walls and gravity, then the level-set
+// object if one is installed, then slots 0 .. 3 in order, each acting on the velocity the previous collider left.  Everything travels by
+// value: count, has_field and the kinds are wave-uniform (scalar compares), and the slot loop is unrolled over the kernel arguments - no
+// runtime-indexed private copy.  Reports the collision kernels' doubled |v|^2 of the final velocity.
+struct ShapeSlot {
+	CollisionObject obj;// (obj.field unused)
+	CollisionPose pose;
+	CollisionShape shape;// kind 0: an empty slot
+};
+struct ShapeArgs {
+	int count;	  // slots [0, count) are looked at
+	int has_field;// the level-set object in `field` acts first
+	CollisionArgs field;
+	ShapeSlot slot[kMaxShapes];
+};
+// grid_cell_collision's prologue + the optional field object + the slot loop; the same statements in the stand-alone kernel and the carry-over
+MPM_DEV float grid_cell_shapes(const GridCfg& cfg, const ShapeArgs& col, int kx, int ky, int kz, int cell, float dt, float4& v) {
+#pragma clang fp contract(off)
+	const bool wx = kx < cfg.boundary || kx >= cfg.G - cfg.boundary;
+	const bool wy = ky < cfg.boundary || ky >= cfg.G - cfg.boundary;
+	const bool wz = kz < cfg.boundary || kz >= cfg.G - cfg.boundary;
+	const float mass_inv = 1.f / v.x;
+	float vel[3];
+	vel[0] = wx ? 0.0f : v.y * mass_inv;
+	vel[1] = (wy ? 0.0f : v.z * mass_inv) + cfg.gravity * dt;
+	vel[2] = wz ? 0.0f : v.w * mass_inv;
+	const int node[3] = {kx * 4 + (cell >> 4), ky * 4 + ((cell >> 2) & 3), kz * 4 + (cell & 3)};
+	if(col.has_field) collision_resolve(col.field.obj, col.field.pose, node, cfg.dx, cfg.G * 4, (float) cfg.boundary * cfg.dx * 4.f, (float) (cfg.G - cfg.boundary) * 4.f * cfg.dx, vel);
+	const float X[3] = {(float) node[0] * cfg.dx, (float) node[1] * cfg.dx, (float) node[2] * cfg.dx};
+#pragma nounroll
+	for(int s = 0; s < col.count; ++s)
+		if(col.slot[s].shape.kind != 0) shape_resolve(col.slot[s].obj, col.slot[s].pose, col.slot[s].shape, X, vel);
+	v.y		= vel[0];
+	v.z		= vel[1];
+	v.w		= vel[2];
+	float q = vel[0] * vel[0] + vel[1] * vel[1] + vel[2] * vel[2];
+	q += vel[0] * vel[0];
+	q += vel[1] * vel[1];
+	q += vel[2] * vel[2];
+	if(q != q) q = __builtin_inff();
+	return q;
+}
+// grid_update_collision_kernel's frame (one wave per grid block, lane = cell) around grid_cell_shapes: the kernel of the phase-level callers
+__global__ __launch_bounds__(256) void grid_update_shapes_kernel(GridCfg cfg, const int* __restrict__ nbc_ptr, float* __restrict__ grid, const int* __restrict__ keys, float dt, ShapeArgs col, unsigned* __restrict__ max_vel_bits) {
+	const int cell	  = threadIdx.x & 63;
+	const int nblocks = min(*nbc_ptr, cfg.cap);
+	float vel_sqr	  = 0.f;
+	for(int blockno = (blockIdx.x * 256 + threadIdx.x) >> 6; blockno < nblocks; blockno += gridDim.x * 4) {
+		const int kx = keys[3 * blockno], ky = keys[3 * blockno + 1], kz = keys[3 * blockno + 2];
+		float* g	 = grid + (size_t) blockno * 256 + cell;
+		float4 v	 = {g[0], 0.f, 0.f, 0.f};
+		if(v.x > 0.0f) {
+			v.y = g[64];
+			v.z = g[128];
+			v.w = g[192];
+			vel_sqr = fmaxf(vel_sqr, grid_cell_shapes(cfg, col, kx, ky, kz, cell, dt, v));
+			g[64]	= v.y;
+			g[128]	= v.z;
+			g[192]	= v.w;
+		}
+	}
+#pragma unroll
+	for(int off = 32; off > 0; off >>= 1) vel_sqr = fmaxf(vel_sqr, __shfl_xor(vel_sqr, off));
+	if((threadIdx.x & 63) == 0 && vel_sqr > 0.f) {
+		const unsigned bits = __float_as_uint(vel_sqr);
+		unsigned* slot		= max_vel_bits + (blockIdx.x & (kMaxVelSlots - 1)) * kMaxVelStride;
+		if(bits > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, bits);
+	}
+}
+// mpm_test_collision_shape: material point, signed distance and normal of one collider at arbitrary domain points
+__global__ void test_collision_shape_kernel(ShapeSlot c, size_t n, const float* __restrict__ xyz, float* __restrict__ out4) {
+	const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
+	if(i >= n) return;
+	const float X[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+	float xmt[3], x[3], nrm[3], sdis;
+	collision_material_point(c.obj, c.pose, X, xmt, x);
+	shape_query(c.shape, x, sdis, nrm);
+	out4[4 * i]		= sdis;
+	out4[4 * i + 1] = nrm[0];
+	out4[4 * i + 2] = nrm[1];
+	out4[4 * i + 3] = nrm[2];
 }
 
 // ---- checkpoint helpers (mpm_checkpoint.inc) ----
@@ -852,6 +936,37 @@ __global__ __launch_bounds__(256) void register_blocks_kernel(GridCfg cfg, const
 				atomicOr(&status[ST_OVERFLOW], 1);
 			}
 		}
+	}
+}
+
+// carry_grid_kernel<true, true>'s frame (below) around grid_cell_shapes: the grid update with analytic shapes riding on the carry-over between
+// the substeps of a run.  A kernel of its own, so that carry_grid_kernel keeps its template parameters and its code.
+__global__ __launch_bounds__(256) void carry_grid_shapes_kernel(GridCfg cfg, const int* __restrict__ status, const int* __restrict__ new_keys, const int* __restrict__ old_table, const float* __restrict__ p2g_grid, float* __restrict__ grid, float dt, unsigned* __restrict__ max_vel_bits, ShapeArgs col) {
+	const int nbc	  = min(status[ST_CNT_P] + status[ST_CNT_N], cfg.cap);
+	const int old_nbc = min(status[ST_NBC], cfg.cap);
+	const int lane = threadIdx.x & 63;
+	float vel_sqr  = 0.f;
+	for(int nb = blockIdx.x * 4 + (threadIdx.x >> 6); nb < nbc; nb += gridDim.x * 4) {
+		const int kx = new_keys[3 * nb], ky = new_keys[3 * nb + 1], kz = new_keys[3 * nb + 2];
+		const int old = table_query(cfg, old_table, kx, ky, kz);
+		float4 v	  = {0.f, 0.f, 0.f, 0.f};
+		if(old >= 0 && old < old_nbc) {
+			const float* s = p2g_grid + (size_t) old * 256;
+			v			   = {s[lane], s[64 + lane], s[128 + lane], s[192 + lane]};
+		}
+		if(v.x > 0.0f) vel_sqr = fmaxf(vel_sqr, grid_cell_shapes(cfg, col, kx, ky, kz, lane, dt, v));
+		float* d	  = grid + (size_t) nb * 256;
+		d[lane]		  = v.x;
+		d[64 + lane]  = v.y;
+		d[128 + lane] = v.z;
+		d[192 + lane] = v.w;
+	}
+#pragma unroll
+	for(int off = 32; off > 0; off >>= 1) vel_sqr = fmaxf(vel_sqr, __shfl_xor(vel_sqr, off));
+	if(lane == 0 && vel_sqr > 0.f) {
+		const unsigned bits = __float_as_uint(vel_sqr);
+		unsigned* slot		= max_vel_bits + (blockIdx.x & (kMaxVelSlots - 1)) * kMaxVelStride;
+		if(bits > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, bits);
 	}
 }
 

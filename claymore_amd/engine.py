@@ -231,6 +231,34 @@ class Engine:
         if animate:
             self.set_collision_clock(True, float(obj.time))
 
+    def set_collision_shape(self, slot, kind=None, *, a=(0.0, 0.0, 0.0), b=(0.0, 0.0, 0.0), radius=0.0, inside_out=False, animate=False, **fields):
+        """Install an analytic collision shape in slot 0 .. 3 (mpm_set_collision_shape, HIP engine only).  kind: "halfspace" (a: a point of
+        the plane, b: outward normal), "sphere" (a: centre, radius), "box" (a: centre, b: half extents), "capsule" (a, b: end points,
+        radius) or the MPM_SHAPE_* number; kind=None empties the slot.  fields: those of set_collision_object (type, friction, scale, dsdt,
+        trans, trans_vel, omega, rot_mat, time).  The shape is given in the coordinates a level set's samples would be given in.  Every
+        install leaves the one clock stopped at `time`: install all colliders, then start it - or pass animate=True with the last one."""
+        if kind is None:
+            self._check(self.api.set_collision_shape(self.ctx, int(slot), None, None))
+            return
+        obj = _ffi.CollisionObject()
+        self._check(self.api.default_collision_object(C.byref(obj)))
+        for k, v in fields.items():
+            cur = getattr(obj, k)
+            if hasattr(cur, "__len__"):
+                for i, x in enumerate(np.asarray(v, dtype=np.float32).ravel()):
+                    cur[i] = float(x)
+            else:
+                setattr(obj, k, v)
+        sh = _ffi.CollisionShape()
+        sh.kind = _ffi.SHAPE_NAMES[kind] if isinstance(kind, str) else int(kind)
+        sh.inside_out = 1 if inside_out else 0
+        for d in range(3):
+            sh.a[d], sh.b[d] = float(a[d]), float(b[d])
+        sh.radius = float(radius)
+        self._check(self.api.set_collision_shape(self.ctx, int(slot), C.byref(obj), C.byref(sh)))
+        if animate:
+            self.set_collision_clock(True, float(obj.time))
+
     def set_collision_clock(self, running=True, time=0.0):
         """Set the collision object's time and start (or stop) its clock: a running clock advances by dt with every grid update,
         the update of a substep sees the object at the time the substep starts (HIP engine only)."""
@@ -314,5 +342,12 @@ def build_engine(scene, device=0, api=None):
     for m in scene["models"]:
         eng.init_model(m["material"], m["xyz"], m.get("v0", (0, 0, 0)), **m.get("params", {}))
     if scene.get("collision"):
-        eng.set_collision_object(**scene["collision"])
+        eng.set_collision_object(**{**scene["collision"], "animate": False})
+    colliders = scene.get("colliders") or []
+    for slot, c in enumerate(colliders):
+        eng.set_collision_shape(slot, **{**c, "animate": False})
+    # one clock for all colliders: started once, after the last install (every install stops it)
+    moving = [c for c in ([scene["collision"]] if scene.get("collision") else []) + list(colliders) if c.get("animate")]
+    if moving:
+        eng.set_collision_clock(True, float(moving[0].get("time", 0.0)))
     return eng

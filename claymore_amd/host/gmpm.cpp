@@ -14,7 +14,7 @@
 // point attributes "stress" (6 floats: the Cauchy stress {xx, yy, zz, xy, xz, yz}), "J", "pressure" and "vonmises" (1 float each) of
 // mpm_retrieve_stress (frame 0: the stress-free initial state, J = 1).  With both keys the two readouts come back in different particle
 // orders: each is sorted on the bits of its positions (which are the same bits in both) and the stress rows are written in the order of the
-// velocity readout.
+// velocity readout.  A top-level "colliders" array installs analytic collision shapes (parse_collider below).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -107,6 +107,55 @@ pio::Points sample_model(const mj::Value& model, int bits, const std::string& sc
 	}
 	std::fprintf(stderr, "unknown model file '%s' (expected *.sdf, sphere or box)\n", file.c_str());
 	std::exit(EXIT_FAILURE);
+}
+
+bool vec3(const mj::Value& v, const char* k, float (&out)[3]) {
+	if(!v.has(k)) return false;
+	for(int d = 0; d < 3; ++d) out[d] = (float) v[k][d].number();
+	return true;
+}
+
+// One entry of "colliders": {"shape": "halfspace" ("point", "normal") | "sphere" ("center", "radius") | "box" ("center", "half_extents") |
+// "capsule" ("a", "b", "radius"), "type": "sticky|slip|separate", "friction", "velocity", "omega", "inside_out"}.  A collider with
+// "velocity" or "omega" moves: it translates, and turns about its point / center / a, with the context's clock, which then starts at 0.
+bool parse_collider(const mj::Value& c, mpm_collision_object& obj, mpm_collision_shape& sh, bool& moving) {
+	mpm_default_collision_object(&obj);
+	std::memset(&sh, 0, sizeof(sh));
+	const std::string shape = c.has("shape") ? c["shape"].string() : "";
+	bool ok = true;
+	if(shape == "halfspace") {
+		sh.kind = MPM_SHAPE_HALFSPACE;
+		ok		= vec3(c, "point", sh.a) && vec3(c, "normal", sh.b);
+	} else if(shape == "sphere") {
+		sh.kind = MPM_SHAPE_SPHERE;
+		ok		= vec3(c, "center", sh.a) && c.has("radius");
+	} else if(shape == "box") {
+		sh.kind = MPM_SHAPE_BOX;
+		ok		= vec3(c, "center", sh.a) && vec3(c, "half_extents", sh.b);
+	} else if(shape == "capsule") {
+		sh.kind = MPM_SHAPE_CAPSULE;
+		ok		= vec3(c, "a", sh.a) && vec3(c, "b", sh.b) && c.has("radius");
+	} else {
+		std::fprintf(stderr, "gmpm: unknown collider shape '%s' (expected halfspace, sphere, box or capsule)\n", shape.c_str());
+		return false;
+	}
+	if(!ok) {
+		std::fprintf(stderr, "gmpm: collider '%s' lacks a field\n", shape.c_str());
+		return false;
+	}
+	sh.radius			   = num(c, "radius", 0.f);
+	sh.inside_out		   = c.has("inside_out") && c["inside_out"].type == mj::Value::Bool && c["inside_out"].b;
+	const std::string type = c.has("type") ? c["type"].string() : "sticky";
+	obj.type			   = type == "sticky" ? MPM_BOUNDARY_STICKY : type == "slip" ? MPM_BOUNDARY_SLIP : type == "separate" ? MPM_BOUNDARY_SEPARATE : -1;
+	if(obj.type < 0) {
+		std::fprintf(stderr, "gmpm: unknown collider type '%s' (expected sticky, slip or separate)\n", type.c_str());
+		return false;
+	}
+	obj.friction = num(c, "friction", obj.friction);
+	for(int d = 0; d < 3; ++d) obj.trans[d] = sh.a[d];// the pivot of omega
+	if(vec3(c, "velocity", obj.trans_vel)) moving = true;
+	if(vec3(c, "omega", obj.omega)) moving = true;
+	return true;
 }
 
 // The rows of xyz (n x 3 floats) in ascending order of their bits (x, then y, then z, as unsigned integers): two readouts of one state hold
@@ -216,6 +265,25 @@ int main(int argc, char** argv) {
 		} else
 			pio::write_bgeo(frame0, pts.empty() ? nullptr : pts[0].data(), pts.size());
 		counts.push_back(pts.size());
+	}
+
+	// "colliders": analytic collision shapes (mpm_set_collision_shape), at most MPM_MAX_COLLISION_SHAPES, slot = position in the array
+	if(doc->has("colliders")) {
+		const mj::Value& cols = (*doc)["colliders"];
+		if(cols.arr.size() > (size_t) MPM_MAX_COLLISION_SHAPES) {
+			std::fprintf(stderr, "gmpm: %zu colliders, at most %d\n", cols.arr.size(), (int) MPM_MAX_COLLISION_SHAPES);
+			return 1;
+		}
+		bool moving = false;
+		for(size_t ci = 0; ci < cols.arr.size(); ++ci) {
+			mpm_collision_object obj;
+			mpm_collision_shape sh;
+			if(!parse_collider(cols[ci], obj, sh, moving)) return 1;
+			rc = mpm_set_collision_shape(ctx, (int) ci, &obj, &sh);
+			if(rc) die(ctx, rc);
+		}
+		std::printf("has %zu colliders%s\n", cols.arr.size(), moving ? ", clock running" : "");
+		if(moving && (rc = mpm_set_collision_clock(ctx, 1, 0.f))) die(ctx, rc);// one clock for all of them, started after the last install
 	}
 
 	// main_loop, gmpm_simulator.cuh:303-592

@@ -236,3 +236,49 @@ def sphere_through_block(bits=6, block_cells=(20, 10, 20), radius_cells=5.0, gap
             "models": [{"material": material, "xyz": lattice_box(bits, lo, hi), "v0": (0.0, 0.0, 0.0),
                         "params": {"volume": _vol(bits), "youngs_modulus": 5e3, "poisson_ratio": 0.4, "rho": 1e3}}],
             "collision": col}
+
+
+def _as_shape(scene, radius):
+    """The level-set sphere of a scene as the same sphere given in closed form: scene["colliders"] instead of scene["collision"].  The
+    level set is centred at the domain point `centre` and sampled in domain coordinates, so the shape's centre `a` is that point."""
+    col = scene.pop("collision")
+    centre = col.pop("centre")
+    shape = {k: v for k, v in col.items() if k not in ("sdf", "grad")}
+    shape.update(kind="sphere", a=tuple(float(c) for c in centre), radius=float(radius))
+    scene["colliders"] = [shape]
+    scene["name"] += "_analytic"
+    return scene
+
+
+def sphere_on_obstacle_analytic(bits=6, radius_cells=5.0, obstacle_cells=6.0, boundary="slip", friction=0.3, speed=1.0, material=FIXED_COROTATED):
+    """sphere_on_obstacle with the obstacle as an analytic sphere (Engine.set_collision_shape): no level set is rasterised or stored."""
+    sc = sphere_on_obstacle(bits, radius_cells, obstacle_cells, boundary, friction, speed, material)
+    sc["collision"]["centre"] = (0.5, 0.34, 0.5)
+    return _as_shape(sc, obstacle_cells / (1 << bits))
+
+
+def sphere_through_block_analytic(bits=6, block_cells=(20, 10, 20), radius_cells=5.0, gap_cells=2.0, speed=1.0, boundary="sticky", friction=0.3,
+                                  omega=(0.0, 0.0, 0.0), dsdt=0.0, rot_mat=None, animate=True, dt=1e-4, material=FIXED_COROTATED):
+    """sphere_through_block with the moving sphere as an analytic shape: same centre, radius, motion and clock."""
+    sc = sphere_through_block(bits, block_cells, radius_cells, gap_cells, speed, boundary, friction, omega, dsdt, rot_mat, animate, dt, material)
+    sc["collision"]["centre"] = sc["collision"]["trans"]
+    return _as_shape(sc, radius_cells / (1 << bits))
+
+
+def colliders_demo(bits=6, boundary="slip", friction=0.3, speed=1.0, dt=1e-4):
+    """One of each: an elastic block falls onto a tilted floor wedge (half-space) beside a sticky box and a fixed rod (capsule), while a sphere
+    sweeps through along +x; the clock runs.  Four analytic colliders, no level set."""
+    dx, n = 1.0 / (1 << bits), 1 << bits
+    lo, hi = [n // 2 - 6, n // 2 - 2, n // 2 - 6], [n // 2 + 6, n // 2 + 6, n // 2 + 6]
+    kind = {"sticky": 0, "slip": 1, "separate": 2}[boundary]
+    y0 = lo[1] * dx
+    cols = [{"kind": "halfspace", "a": (0.5, y0 - 3 * dx, 0.5), "b": (0.2, -1.0, 0.0), "inside_out": True, "type": kind, "friction": friction},
+            {"kind": "box", "a": (0.5 + 9 * dx, y0 - 2 * dx, 0.5), "b": (2 * dx, 3 * dx, 4 * dx), "type": 0},
+            {"kind": "capsule", "a": (0.5 - 8 * dx, y0 - 2 * dx, 0.5 - 6 * dx), "b": (0.5 - 8 * dx, y0 - 2 * dx, 0.5 + 6 * dx), "radius": 1.5 * dx, "type": kind,
+             "friction": friction},
+            {"kind": "sphere", "a": ((lo[0] - 7) * dx, 0.5 + 2 * dx, 0.5), "radius": 4 * dx, "type": kind, "friction": friction,
+             "trans_vel": (speed, 0.0, 0.0), "animate": True}]
+    return {"name": "colliders_demo", "bits": bits, "dt": dt, "config": {},
+            "models": [{"material": FIXED_COROTATED, "xyz": lattice_box(bits, lo, hi), "v0": (0.0, 0.0, 0.0),
+                        "params": {"volume": _vol(bits), "youngs_modulus": 5e3, "poisson_ratio": 0.4, "rho": 1e3}}],
+            "colliders": cols}

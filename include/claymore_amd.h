@@ -266,6 +266,44 @@ int mpm_set_collision_object(mpm_ctx* ctx, const mpm_collision_object* obj, cons
 int mpm_set_collision_clock(mpm_ctx* ctx, int running, float time);
 int mpm_get_collision_time(mpm_ctx* ctx, float* time, int* running); /* either pointer may be NULL */
 
+/* Extension (the reference knows level sets only): collision objects given in closed form.  They cost no device memory and no loads -
+ * a level set keeps a float4 per node of the whole domain, 2 GiB at domain_bits 9 - and up to MPM_MAX_COLLISION_SHAPES of them can be
+ * installed at once, beside the level-set object.  HIP library only.
+ * Geometry.  A shape lives in the coordinates a level set's samples would be given in: a node at X is taken to the material point
+ * x = R^T((X - shift) inv) scale + trans by the level set's own statements (the pose of mpm_set_collision_clock's comment), and the
+ * shape answers with a signed distance sdis and a unit normal n:
+ *   HALFSPACE  sdis = (x - a) . b^, n = b^                       (b^ = b / |b|, normalised on install)
+ *   SPHERE     d = x - a, sdis = |d| - radius, n = d / |d|
+ *   BOX        q = |x - a| - b per axis.  Inside (every q <= 0): sdis = max q, n = the axis of the largest q (ties: the lowest axis) with
+ *              the sign of (x - a) on it (sign(0) = +).  Outside: sdis = |max(q, 0)|, n its gradient.
+ *   CAPSULE    t = clamp((x - a) . (b - a) / |b - a|^2, 0, 1), d = x - (a + t (b - a)), sdis = |d| - radius, n = d / |d|
+ * Where |d| = 0, n = 0 (nothing is divided by zero); the response then does what it does for a level set's zero gradient, SEPARATE's
+ * early return included.  A node is touched when sdis <= 0; a NaN sdis touches nothing.  query_sdf's domain box does NOT apply: a
+ * shape exists everywhere, in the wall zones too.  inside_out = 1: the solid is the complement (a container): sdis and n change sign.
+ * Response.  From sdis <= 0 on, the level set's: object velocity in deformation space, STICKY / SLIP / SEPARATE, friction.
+ * Several colliders.  Per cell with mass: walls and gravity; the level-set object, if installed; slots 0 .. 3 in order, each acting on
+ * the velocity the previous one left.  With any collider installed mpm_grid_update reports the doubled |v|^2 of the final velocity.
+ * Clock.  One per context, the level set's.  Every install of either kind sets it to obj->time, stopped; every removal stops it: install
+ * all colliders, then call mpm_set_collision_clock once.  mpm_set_collision_clock / mpm_get_collision_time succeed when a level-set
+ * object or any shape is installed.  Shapes are not part of a checkpoint; a checkpoint load leaves the installed ones in place. */
+enum { MPM_SHAPE_HALFSPACE = 1, MPM_SHAPE_SPHERE = 2, MPM_SHAPE_BOX = 3, MPM_SHAPE_CAPSULE = 4 };
+enum { MPM_MAX_COLLISION_SHAPES = 4 };
+typedef struct mpm_collision_shape {
+	int kind;
+	int inside_out;	  /* 1: the solid is the complement (a container): sdis and n change sign */
+	float a[3];		  /* HALFSPACE: a point of the plane; SPHERE / BOX: centre; CAPSULE: first end point */
+	float b[3];		  /* HALFSPACE: outward normal (any length > 0; normalised on install); BOX: half extents (> 0); CAPSULE: second end point (!= a) */
+	float radius;	  /* SPHERE, CAPSULE (> 0) */
+	int reserved[5];
+} mpm_collision_shape;
+/* Install a shape in slot 0 .. 3 with the pose, motion and boundary fields of `obj`, or empty the slot (obj == NULL).  MPM_ERR_INVALID
+ * (mpm_last_error names the field): slot outside 0..3, unknown kind, boundary type outside 0..2, radius or half extent <= 0 or not
+ * finite, zero or non-finite normal, a capsule with a == b, a NaN anywhere in the shape. */
+int mpm_set_collision_shape(mpm_ctx* ctx, int slot, const mpm_collision_object* obj, const mpm_collision_shape* shape);
+/* Function-level entry point (as mpm_test_eig): on the device, for n arbitrary domain points xyz[n*3], the signed distance and normal the
+ * grid kernels would use for this collider at `time` - out4[n*4] = {sdis, nx, ny, nz}.  dx is not used by the evaluation. */
+int mpm_test_collision_shape(const mpm_collision_object* obj, const mpm_collision_shape* shape, float time, float dx, const float* xyz, size_t n, float* out4, int device);
+
 /* Current capacities and the number of times check_capacity() (gmpm_simulator.cuh:283-300) has grown them: blocks
  * (exterior count limit), bins per model (bin_capacity[8]).  HIP library only. */
 int mpm_get_capacity(mpm_ctx* ctx, int64_t* block_capacity, int64_t* bin_capacity, int* growth_events);

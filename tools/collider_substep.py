@@ -1,14 +1,19 @@
 #!/usr/bin/env python
-"""Per-phase substep times of mpm_run_fixed with a collision object: none / static / moving, for one or several prebuilt engine
+"""Per-phase substep times of mpm_run_fixed with a collision object: none / static / moving / shape / shapes4, for one or several prebuilt engine
 libraries in ONE process, interleaved (lib A, lib B, lib A, ...), so that a parent build and a branch build are compared on the same
 box under the same conditions.
 
-    python tools/collider_substep.py [--scene c2|c3] [--steps 200] [--warmup 50] [--reps 3] [--objects none,static,moving] [--out FILE] [lib.so ...]
+    python tools/collider_substep.py [--scene c2|c3] [--steps 200] [--warmup 50] [--reps 3] [--objects none,static,moving,shape,shapes4] [--phase 20]
+                                     [--out FILE] [lib.so ...]
 
 Scene: C2 (one elastic sphere of ~5 M particles dropped at 256^3; the level-set field is 256^3 float4 = 256 MiB) or C3 (the sand column at
 512^3; the field is 2 GiB).  The object is a sphere below the material, far enough that nothing touches it during the measurement: the
 kernel evaluates it at every grid node with mass either way, which is the cost in question.  A library without the clock's entry points
-(a parent build) runs `none` and `static` only.  Prints one JSON line per (rep, library, object) with the library's per-substep averages
+(a parent build) runs `none` and `static` only.  `shape`: the same sphere given in closed form (mpm_set_collision_shape: no field, no loads);
+`shapes4`: that sphere, a floor half-space, a box and a capsule in the four slots, all clear of the material.  A library without
+mpm_set_collision_shape skips both.  --phase N: after the run, N more substeps phase by phase (grid update, G2P2G, rebuild), whose median
+grid-update time is the stand-alone kernel's (`phase_grid_ms`); in mpm_run_fixed the update rides on the carry-over inside `partition_ms`.
+`object_bytes`: device memory taken by installing the collider (hipMemGetInfo before and after).  Prints one JSON line per (rep, library, object) with the library's per-substep averages
 (HIP events on the compute stream) and the wall-clock time per substep, then a summary of medians."""
 import argparse
 import ctypes as C
@@ -17,6 +22,8 @@ import os
 import statistics
 import sys
 import time
+
+import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -38,7 +45,8 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--objects", default="none,static,moving")
+    ap.add_argument("--objects", default="none,static,moving,shape,shapes4")
+    ap.add_argument("--phase", type=int, default=20)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     sc = scenes.sphere_drop() if a.scene == "c2" else scenes.sand_column()
@@ -50,21 +58,36 @@ def main():
     for rep in range(a.reps):
         for name, api in apis:
             for obj in a.objects.split(","):
-                if obj == "moving" and not hasattr(api, "set_collision_clock"):
+                if (obj == "moving" and not hasattr(api, "set_collision_clock")) or (obj in ("shape", "shapes4") and not hasattr(api, "set_collision_shape")):
                     continue
                 eng = build_engine(sc, api=api)
-                if obj != "none":
+                free0 = torch.cuda.mem_get_info()[0]
+                if obj in ("shape", "shapes4"):
+                    eng.set_collision_shape(0, "sphere", a=(0.5, 0.12, 0.5), radius=0.06, type=1, friction=0.3, trans=(0.5, 0.12, 0.5))
+                if obj == "shapes4":
+                    eng.set_collision_shape(1, "halfspace", a=(0.5, 0.02, 0.5), b=(0.0, -1.0, 0.0), inside_out=True, type=1, friction=0.3)
+                    eng.set_collision_shape(2, "box", a=(0.2, 0.1, 0.2), b=(0.05, 0.04, 0.05), type=0)
+                    eng.set_collision_shape(3, "capsule", a=(0.75, 0.1, 0.3), b=(0.75, 0.1, 0.7), radius=0.04, type=2, friction=0.3)
+                elif obj in ("static", "moving"):
                     eng.set_collision_object(**col, **({"trans_vel": (0.0, 0.05, 0.0), "omega": (1.0, 2.0, 3.0), "dsdt": 0.1} if obj == "moving" else {}))
                 if obj == "moving":
                     eng.set_collision_clock(True, 0.0)
+                object_bytes = free0 - torch.cuda.mem_get_info()[0]
                 eng.initial_setup()
                 eng.run_fixed(a.warmup, sc["dt"])
                 t0 = time.perf_counter()
                 eng.run_fixed(a.steps, sc["dt"])
                 wall = (time.perf_counter() - t0) * 1e3 / a.steps
                 t = eng.timers()
+                phase = []
+                for _ in range(a.phase):
+                    eng.grid_update(sc["dt"])
+                    phase.append(eng.timers().grid_update_ms)
+                    eng.g2p2g(sc["dt"], sc["dt"])
+                    eng.rebuild_partition()
                 row = {"rep": rep, "lib": name, "build": api.build_info().decode(), "scene": a.scene, "object": obj, "steps": a.steps, "wall_ms": round(wall, 5),
-                       "grid_ms": round(t.grid_update_ms, 5), "g2p2g_ms": round(t.g2p2g_ms, 5), "partition_ms": round(t.partition_ms, 5), "total_ms": round(t.total_ms, 5)}
+                       "grid_ms": round(t.grid_update_ms, 5), "g2p2g_ms": round(t.g2p2g_ms, 5), "partition_ms": round(t.partition_ms, 5), "total_ms": round(t.total_ms, 5),
+                       "phase_grid_ms": round(statistics.median(phase), 5) if phase else None, "object_bytes": int(object_bytes)}
                 eng.close()
                 rows.append(row)
                 lines.append(json.dumps(row))
@@ -73,7 +96,8 @@ def main():
         for obj in a.objects.split(","):
             sel = [r for r in rows if r["lib"] == name and r["object"] == obj]
             if sel:
-                med = {k: round(statistics.median(r[k] for r in sel), 5) for k in ("wall_ms", "grid_ms", "g2p2g_ms", "partition_ms", "total_ms")}
+                med = {k: round(statistics.median(r[k] for r in sel), 5) for k in ("wall_ms", "grid_ms", "g2p2g_ms", "partition_ms", "total_ms") + (("phase_grid_ms",) if a.phase else ())}
+                med.update(partition_lo=min(r["partition_ms"] for r in sel), partition_hi=max(r["partition_ms"] for r in sel), object_bytes=sel[0]["object_bytes"])
                 med.update(lo=min(r["wall_ms"] for r in sel), hi=max(r["wall_ms"] for r in sel))
                 lines.append(json.dumps({"summary": name, "object": obj, "n": len(sel), **med}))
                 print(lines[-1], flush=True)

@@ -117,3 +117,25 @@ def nacc(F9, logjp, mu, lam, volume, beta, xi, msqr, hardening_on):
         dev = b - np.trace(b, axis1=1, axis2=2)[:, None, None] / 3.0 * np.eye(3)
         PF = (mu * np.power(J, -2.0 / 3.0))[:, None, None] * dev + (bm * 0.5 * ((J * J - 1.0) * 0.5 - np.log(J)))[:, None, None] * np.eye(3)
     return to_flat(Fn), to_flat(PF * volume), lj_new, case
+
+
+def sand_branch(F9, logjp, mu, lam, cohesion, yield_surface):
+    """Which way the return mapping of `sand` goes: 0 = inside the yield surface (the strain stays), 1 = projected onto it, 2 = the tip."""
+    U, S, V = _svd_rot(to_mats(F9))
+    eps = np.log(np.maximum(np.abs(S), 1e-4)) - cohesion
+    tr = eps.sum(axis=1) + np.asarray(logjp, dtype=np.float64)
+    eps_hat = eps - tr[:, None] / 3
+    dg = np.sqrt((eps_hat ** 2).sum(axis=1)) + (3 * lam + 2 * mu) / (2 * mu) * tr * yield_surface
+    return np.where(tr >= 0, 2, np.where(dg > 0, 1, 0))
+
+
+def jfluid(J, A9, dt, d_inv, volume, bulk, gamma, viscosity):
+    """The J-fluid block inline in g2p2g, mgmpm_kernels.cuh:476-505: J <- J + tr(A) dt D^-1 J, clamped at 0.1 from below; Tait pressure
+    bulk (J^-gamma - 1) and the viscous term (A + A^T) D^-1 viscosity, times the current volume J * volume.  A9: the un-normalised APIC
+    matrix, column-major; returns (J_new, contrib 9 column-major)."""
+    A = to_mats(A9)
+    J = np.asarray(J, dtype=np.float64)
+    Jn = np.maximum(J + np.trace(A, axis1=1, axis2=2) * dt * d_inv * J, 0.1)
+    pressure = bulk * (np.power(Jn, -gamma) - 1.0)
+    c = ((A + A.transpose(0, 2, 1)) * d_inv * viscosity - pressure[:, None, None] * np.eye(3)) * (Jn * volume)[:, None, None]
+    return Jn, to_flat(c)

@@ -43,6 +43,14 @@ SHAPE_NAMES = {"halfspace": SHAPE_HALFSPACE, "sphere": SHAPE_SPHERE, "box": SHAP
 MAX_COLLISION_SHAPES = 4
 
 
+class Heightfield(C.Structure):
+    _fields_ = [("nx", C.c_int), ("nz", C.c_int), ("origin", C.c_float * 2), ("spacing", C.c_float), ("inside_out", C.c_int),
+                ("reserved", C.c_int * 6)]
+
+
+HEIGHTFIELD_MAX_SAMPLES = 4096
+
+
 class Counts(C.Structure):
     _fields_ = [("particle_blocks", C.c_int), ("neighbor_blocks", C.c_int), ("exterior_blocks", C.c_int),
                 ("model_count", C.c_int), ("bins", C.c_int64 * 8), ("particles", C.c_int64 * 8)]
@@ -122,6 +130,8 @@ HIP_ONLY = {
     "get_collision_time": (_i, [_vp, _fp, _ip]),
     "set_collision_shape": (_i, [_vp, _i, _P(CollisionObject), _P(CollisionShape)]),
     "test_collision_shape": (_i, [_P(CollisionObject), _P(CollisionShape), _f, _f, _vp, _sz, _vp, _i]),
+    "set_collision_heightfield": (_i, [_vp, _i, _P(CollisionObject), _P(Heightfield), _vp]),
+    "test_collision_heightfield": (_i, [_P(CollisionObject), _P(Heightfield), _vp, _f, _vp, _sz, _vp, _i]),
     "checkpoint_size": (_i, [_vp, _P(_sz)]),
     "checkpoint_save": (_i, [_vp, _vp, _sz, _P(_sz)]),
     "checkpoint_load": (_i, [_vp, _vp, _sz]),

@@ -111,6 +111,10 @@ struct mpm_ctx {
 	// analytic collision shapes (mpm_set_collision_shape): slot s is in use where shape[s].shape.kind != 0; they share the one clock above
 	ShapeSlot shape[kMaxShapes] {};
 	int shape_count = 0;// highest slot in use + 1
+	// heightfields (mpm_set_collision_heightfield): slot s holds one where shape[s].shape.kind == kShapeHeightfield; hf[s].table is owned
+	// by the context (freed on replace, on removal and in mpm_destroy).  hf_count > 0 selects the terrain kernels.
+	Heightfield hf[kMaxShapes] {};
+	int hf_count = 0;// slots that hold a heightfield
 	mpm_timers timers {};
 	float last_g2p2g_ms = 0.f;
 	// halo state (MGSP)
@@ -358,6 +362,7 @@ void mpm_destroy(mpm_ctx* ctx) {
 	hipSetDevice(ctx->device);
 	hipDeviceSynchronize();
 	hipFree(ctx->d_sdf);
+	for(int i = 0; i < kMaxShapes; ++i) hipFree(const_cast<float4*>(ctx->hf[i].table));
 	for(int i = 0; i < 2; ++i) {
 		hipFree(ctx->part[i].table);
 		hipFree(ctx->part[i].keys);
@@ -627,6 +632,13 @@ static ShapeArgs shapes_tick(mpm_ctx* ctx, float dt) {
 	if(ctx->collision_running) ctx->collision.time = T + dt;
 	return a;
 }
+// The same with a heightfield in a slot: shapes_tick's arguments (one pose per collider, the clock advanced once) and the tables beside them.
+static TerrainArgs terrain_tick(mpm_ctx* ctx, float dt) {
+	TerrainArgs a {};
+	a.col = shapes_tick(ctx, dt);
+	for(int i = 0; i < kMaxShapes; ++i) a.hf[i] = ctx->hf[i];
+	return a;
+}
 
 // grid-update phase, gmpm_simulator.cuh:326-347
 static int launch_grid_update(mpm_ctx* ctx, float dt) {
@@ -640,7 +652,9 @@ static int launch_grid_update(mpm_ctx* ctx, float dt) {
 	HIP_TRY(hipMemsetAsync(ctx->d_maxvel, 0, sizeof(unsigned) * kMaxVelSlots * kMaxVelStride, s));
 	if(ctx->nbc) {
 		const int est = std::min(ctx->g.cap, ctx->nbc + ctx->nbc / 16 + 64);// (an estimate between two synchronisations of mpm_run_fixed)
-		if(ctx->shape_count)
+		if(ctx->hf_count)
+			grid_update_terrain_kernel<<<cdiv(est, 4), 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, terrain_tick(ctx, dt), ctx->d_maxvel);
+		else if(ctx->shape_count)
 			grid_update_shapes_kernel<<<cdiv(est, 4), 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, shapes_tick(ctx, dt), ctx->d_maxvel);
 		else if(ctx->has_collision)
 			grid_update_collision_kernel<<<cdiv(est, 4), 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, collision_tick(ctx, dt), ctx->d_maxvel);
@@ -855,7 +869,9 @@ static int launch_rebuild(mpm_ctx* ctx, float fuse_dt = 0.f, bool without_prepar
 	const unsigned rg8 = std::max(1u, std::min(4096u, cdiv((size_t) ebc_est * 8, 256))), rg32 = std::max(1u, std::min(8192u, cdiv((size_t) ebc_est * 32, 256)));
 	register_blocks_kernel<0, 1><<<rg8, 256, 0, s>>>(g, &st[ST_CNT_P], nullptr, &st[ST_CNT_N], &st[ST_PBC], Pn.table, Pn.keys, st);
 	if(fused) {
-		if(ctx->shape_count)
+		if(ctx->hf_count)
+			carry_grid_terrain_kernel<<<2048, 256, 0, s>>>(g, st, Pn.keys, Pr.table, ctx->grid[1], ctx->grid[0], fuse_dt, ctx->d_maxvel, terrain_tick(ctx, fuse_dt));
+		else if(ctx->shape_count)
 			carry_grid_shapes_kernel<<<2048, 256, 0, s>>>(g, st, Pn.keys, Pr.table, ctx->grid[1], ctx->grid[0], fuse_dt, ctx->d_maxvel, shapes_tick(ctx, fuse_dt));
 		else if(ctx->has_collision)
 			carry_grid_kernel<true, true><<<2048, 256, 0, s>>>(g, st, Pn.keys, Pr.table, ctx->grid[1], ctx->grid[0], fuse_dt, ctx->d_maxvel, collision_tick(ctx, fuse_dt));
@@ -1207,6 +1223,19 @@ int mpm_set_collision_object(mpm_ctx* ctx, const mpm_collision_object* obj, cons
 static bool shape_finite3(const float* v) {
 	return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]);
 }
+// the pose, motion and boundary fields of mpm_collision_object as the kernels read them (no field: a slot's collider)
+static CollisionObject slot_object(const mpm_collision_object* obj) {
+	CollisionObject o {};
+	o.type	   = obj->type;
+	o.friction = obj->friction;
+	o.scale	   = obj->scale;
+	o.dsdt	   = obj->dsdt;
+	for(int d = 0; d < 3; ++d) o.trans[d] = obj->trans[d], o.trans_vel[d] = obj->trans_vel[d], o.omega[d] = obj->omega[d];
+	for(int i = 0; i < 9; ++i) o.rot[i] = obj->rot_mat[i];
+	o.time	= obj->time;
+	o.field = nullptr;
+	return o;
+}
 // mpm_collision_object + mpm_collision_shape -> the slot the kernels read; nullptr, or the message that names the offending field
 static const char* make_shape_slot(const mpm_collision_object* obj, const mpm_collision_shape* sh, ShapeSlot& out) {
 	if(sh->kind < MPM_SHAPE_HALFSPACE || sh->kind > MPM_SHAPE_CAPSULE) return "collision shape: unknown kind";
@@ -1237,17 +1266,42 @@ static const char* make_shape_slot(const mpm_collision_object* obj, const mpm_co
 		for(int d = 0; d < 3; ++d)
 			if(!(sh->b[d] > 0.f) || !std::isfinite(sh->b[d])) return "collision shape: half extents b must be finite and > 0";
 	if(sh->kind == MPM_SHAPE_CAPSULE && sh->a[0] == sh->b[0] && sh->a[1] == sh->b[1] && sh->a[2] == sh->b[2]) return "collision shape: capsule end points a and b coincide";
-	CollisionObject& o = c.obj;
-	o.type	   = obj->type;
-	o.friction = obj->friction;
-	o.scale	   = obj->scale;
-	o.dsdt	   = obj->dsdt;
-	for(int d = 0; d < 3; ++d) o.trans[d] = obj->trans[d], o.trans_vel[d] = obj->trans_vel[d], o.omega[d] = obj->omega[d];
-	for(int i = 0; i < 9; ++i) o.rot[i] = obj->rot_mat[i];
-	o.time	= obj->time;
-	o.field = nullptr;
-	out		= c;
+	c.obj = slot_object(obj);
+	out	  = c;
 	return nullptr;
+}
+
+static void count_slots(mpm_ctx* ctx) {
+	ctx->shape_count = ctx->hf_count = 0;
+	for(int i = 0; i < MPM_MAX_COLLISION_SHAPES; ++i) {
+		if(ctx->shape[i].shape.kind) ctx->shape_count = i + 1;
+		if(ctx->shape[i].shape.kind == kShapeHeightfield) ++ctx->hf_count;
+	}
+}
+// What every accepted install or removal of either kind does to slot `slot`: wait for the device, free the table of a heightfield that sat
+// there, put the new occupant in (c.shape.kind 0: empty; f.table: the new heightfield's, owned by the context from here on), stop the clock
+// and - on an install - set it to obj->time.
+static int install_slot(mpm_ctx* ctx, int slot, const ShapeSlot& c, const Heightfield& f, const mpm_collision_object* obj) {
+	hipError_t e = hipSetDevice(ctx->device);
+	if(e == hipSuccess) e = hipDeviceSynchronize();
+	if(e != hipSuccess) {// nothing was touched: the old occupant stays
+		if(f.table) hipFree(const_cast<float4*>(f.table));
+		return fail(ctx, MPM_ERR_DEVICE, std::string("collision slot: ") + hipGetErrorString(e));
+	}
+	// the old table goes first; should freeing it fail, its memory is in an unknown state, so the slot is emptied rather than left pointing at it
+	if(ctx->hf[slot].table && (e = hipFree(const_cast<float4*>(ctx->hf[slot].table))) != hipSuccess) {
+		if(f.table) hipFree(const_cast<float4*>(f.table));
+		ctx->hf[slot]	 = Heightfield {};
+		ctx->shape[slot] = ShapeSlot {};
+		count_slots(ctx);
+		return fail(ctx, MPM_ERR_DEVICE, std::string("collision slot: freeing the old table -> ") + hipGetErrorString(e) + " (the slot is now empty)");
+	}
+	ctx->hf[slot]		   = f;
+	ctx->shape[slot]	   = c;// (kind 0: empty)
+	ctx->collision_running = false;// installing or removing a collider stops the clock
+	if(obj) ctx->collision.time = obj->time;
+	count_slots(ctx);
+	return MPM_OK;
 }
 
 int mpm_set_collision_shape(mpm_ctx* ctx, int slot, const mpm_collision_object* obj, const mpm_collision_shape* shape) {
@@ -1258,15 +1312,53 @@ int mpm_set_collision_shape(mpm_ctx* ctx, int slot, const mpm_collision_object* 
 		if(!shape) return fail(ctx, MPM_ERR_INVALID, "collision shape: obj without a shape");
 		if(const char* msg = make_shape_slot(obj, shape, c)) return fail(ctx, MPM_ERR_INVALID, msg);
 	}
+	return install_slot(ctx, slot, c, Heightfield {}, obj);
+}
+
+// Heightfield ----------------------------------------------------------------------------------------------------------------------------
+// mpm_collision_object + mpm_heightfield -> the slot and the table's description (table = nullptr: the caller's); nullptr, or the message
+// that names the offending field
+static const char* make_heightfield_slot(const mpm_collision_object* obj, const mpm_heightfield* hf, ShapeSlot& out, Heightfield& f) {
+	if(hf->nx < kHeightfieldMinSamples || hf->nx > MPM_HEIGHTFIELD_MAX_SAMPLES) return "collision heightfield: nx outside 2..4096";
+	if(hf->nz < kHeightfieldMinSamples || hf->nz > MPM_HEIGHTFIELD_MAX_SAMPLES) return "collision heightfield: nz outside 2..4096";
+	if(!(hf->spacing > 0.f) || !std::isfinite(hf->spacing)) return "collision heightfield: spacing must be finite and > 0";
+	if(hf->origin[0] != hf->origin[0] || hf->origin[1] != hf->origin[1]) return "collision heightfield: NaN in origin";
+	if(obj->type < MPM_BOUNDARY_STICKY || obj->type > MPM_BOUNDARY_SEPARATE) return "collision heightfield: boundary type outside 0..2";
+	out					 = ShapeSlot {};
+	out.obj				 = slot_object(obj);
+	out.shape.kind		 = kShapeHeightfield;
+	out.shape.inside_out = hf->inside_out ? 1 : 0;
+	f					 = Heightfield {};
+	f.nx				 = hf->nx;
+	f.nz				 = hf->nz;
+	f.origin[0]			 = hf->origin[0];
+	f.origin[1]			 = hf->origin[1];
+	f.spacing			 = hf->spacing;
+	f.inside_out		 = out.shape.inside_out;
+	return nullptr;
+}
+
+int mpm_set_collision_heightfield(mpm_ctx* ctx, int slot, const mpm_collision_object* obj, const mpm_heightfield* hf, const float* heights) {
+	if(!ctx) return MPM_ERR_INVALID;
+	if(slot < 0 || slot >= MPM_MAX_COLLISION_SHAPES) return fail(ctx, MPM_ERR_INVALID, "collision heightfield: slot outside 0..3");
+	ShapeSlot c {};
+	Heightfield f {};
+	if(!obj) return install_slot(ctx, slot, c, f, nullptr);
+	if(!hf) return fail(ctx, MPM_ERR_INVALID, "collision heightfield: obj without hf");
+	if(!heights) return fail(ctx, MPM_ERR_INVALID, "collision heightfield: obj without heights");
+	if(const char* msg = make_heightfield_slot(obj, hf, c, f)) return fail(ctx, MPM_ERR_INVALID, msg);
+	const size_t n = (size_t) f.nx * f.nz;
+	std::vector<float4> table(n);
+	if(!heightfield_build(heights, f.nx, f.nz, f.spacing, table.data())) return fail(ctx, MPM_ERR_INVALID, "collision heightfield: a height or a derived table entry is not finite");
 	HIP_TRY(hipSetDevice(ctx->device));
-	HIP_TRY(hipDeviceSynchronize());
-	ctx->shape[slot]	   = c;// (kind 0: empty)
-	ctx->collision_running = false;// installing or removing a collider stops the clock
-	if(obj) ctx->collision.time = obj->time;
-	ctx->shape_count = 0;
-	for(int i = 0; i < MPM_MAX_COLLISION_SHAPES; ++i)
-		if(ctx->shape[i].shape.kind) ctx->shape_count = i + 1;
-	return MPM_OK;
+	float4* d = nullptr;
+	HIP_TRY(dalloc(&d, n));
+	if(hipError_t e = hipMemcpy(d, table.data(), sizeof(float4) * n, hipMemcpyHostToDevice)) {
+		hipFree(d);
+		return fail(ctx, MPM_ERR_DEVICE, std::string("collision heightfield: copying the table -> ") + hipGetErrorString(e));
+	}
+	f.table = d;
+	return install_slot(ctx, slot, c, f, obj);
 }
 
 int mpm_set_collision_clock(mpm_ctx* ctx, int running, float time) {
@@ -1527,6 +1619,30 @@ int mpm_test_collision_shape(const mpm_collision_object* obj, const mpm_collisio
 	HIP_TRY0(dO.alloc(4 * n));
 	HIP_TRY0(hipMemcpy(dX.p, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
 	test_collision_shape_kernel<<<cdiv(n, 256), 256>>>(c, n, dX.p, dO.p);
+	HIP_TRY0(hipGetLastError());
+	HIP_TRY0(hipMemcpy(out4, dO.p, sizeof(float) * 4 * n, hipMemcpyDeviceToHost));
+	return MPM_OK;
+}
+
+int mpm_test_collision_heightfield(const mpm_collision_object* obj, const mpm_heightfield* hf, const float* heights, float time, const float* xyz, size_t n, float* out4, int device) {
+	if(!obj || !hf || !heights || !xyz || !out4 || n == 0) return MPM_ERR_INVALID;
+	ShapeSlot c {};
+	Heightfield f {};
+	if(make_heightfield_slot(obj, hf, c, f)) return MPM_ERR_INVALID;
+	const size_t cells = (size_t) f.nx * f.nz;
+	std::vector<float4> table(cells);
+	if(!heightfield_build(heights, f.nx, f.nz, f.spacing, table.data())) return MPM_ERR_INVALID;
+	c.pose = collision_pose(c.obj, time);
+	HIP_TRY0(hipSetDevice(device));
+	DevScratch<float> dX, dO;
+	DevScratch<float4> dT;
+	HIP_TRY0(dX.alloc(3 * n));
+	HIP_TRY0(dO.alloc(4 * n));
+	HIP_TRY0(dT.alloc(cells));
+	HIP_TRY0(hipMemcpy(dX.p, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
+	HIP_TRY0(hipMemcpy(dT.p, table.data(), sizeof(float4) * cells, hipMemcpyHostToDevice));
+	f.table = dT.p;
+	test_collision_heightfield_kernel<<<cdiv(n, 256), 256>>>(c, f, n, dX.p, dO.p);
 	HIP_TRY0(hipGetLastError());
 	HIP_TRY0(hipMemcpy(out4, dO.p, sizeof(float) * 4 * n, hipMemcpyDeviceToHost));
 	return MPM_OK;

@@ -33,6 +33,7 @@
 #include "mpm_device_math.hpp"
 #include "mpm_collision.hpp"
 #include "mpm_collision_shapes.hpp"
+#include "mpm_collision_heightfield.hpp"
 
 namespace mpm {
 
@@ -303,20 +304,24 @@ struct CollisionArgs {
 	CollisionPose pose;
 };
 struct NoCollision {};
-// One cell with mass: v = {mass, momentum} in, {mass, velocity} out; returns the cell's (doubled) |v|^2.  Shared by the stand-alone
-// kernel and the fused carry-over, so that both are the same statements on the same data.
-MPM_DEV float grid_cell_collision(const GridCfg& cfg, const CollisionArgs& col, int kx, int ky, int kz, int cell, float dt, float4& v) {
+// The two ends every collision variant of the per-cell update shares (grid_cell_collision, grid_cell_shapes, grid_cell_terrain), so that a
+// change is made once.  Prologue: momentum -> velocity with the walls' zeroes and gravity, and the cell's node coordinates.
+MPM_DEV void grid_cell_walls_gravity(const GridCfg& cfg, int kx, int ky, int kz, int cell, float dt, const float4& v, float (&vel)[3], int (&node)[3]) {
 #pragma clang fp contract(off)
 	const bool wx = kx < cfg.boundary || kx >= cfg.G - cfg.boundary;
 	const bool wy = ky < cfg.boundary || ky >= cfg.G - cfg.boundary;
 	const bool wz = kz < cfg.boundary || kz >= cfg.G - cfg.boundary;
 	const float mass_inv = 1.f / v.x;
-	float vel[3];
 	vel[0] = wx ? 0.0f : v.y * mass_inv;
 	vel[1] = (wy ? 0.0f : v.z * mass_inv) + cfg.gravity * dt;
 	vel[2] = wz ? 0.0f : v.w * mass_inv;
-	const int node[3] = {kx * 4 + (cell >> 4), ky * 4 + ((cell >> 2) & 3), kz * 4 + (cell & 3)};
-	collision_resolve(col.obj, col.pose, node, cfg.dx, cfg.G * 4, (float) cfg.boundary * cfg.dx * 4.f, (float) (cfg.G - cfg.boundary) * 4.f * cfg.dx, vel);
+	node[0] = kx * 4 + (cell >> 4);
+	node[1] = ky * 4 + ((cell >> 2) & 3);
+	node[2] = kz * 4 + (cell & 3);
+}
+// Epilogue: the velocity into v, and the reference's doubled |v|^2 (inf for a NaN).
+MPM_DEV float grid_cell_store_doubled_q(const float (&vel)[3], float4& v) {
+#pragma clang fp contract(off)
 	v.y		= vel[0];
 	v.z		= vel[1];
 	v.w		= vel[2];
@@ -326,6 +331,26 @@ MPM_DEV float grid_cell_collision(const GridCfg& cfg, const CollisionArgs& col, 
 	q += vel[2] * vel[2];
 	if(q != q) q = __builtin_inff();
 	return q;
+}
+// The wave's maximum into one of the kMaxVelSlots slots (non-negative floats order as uints; a plain, possibly stale read filters most atomics out)
+MPM_DEV void wave_max_vel(float vel_sqr, unsigned* __restrict__ max_vel_bits) {
+#pragma unroll
+	for(int off = 32; off > 0; off >>= 1) vel_sqr = fmaxf(vel_sqr, __shfl_xor(vel_sqr, off));
+	if((threadIdx.x & 63) == 0 && vel_sqr > 0.f) {
+		const unsigned bits = __float_as_uint(vel_sqr);
+		unsigned* slot		= max_vel_bits + (blockIdx.x & (kMaxVelSlots - 1)) * kMaxVelStride;
+		if(bits > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, bits);
+	}
+}
+// One cell with mass: v = {mass, momentum} in, {mass, velocity} out; returns the cell's (doubled) |v|^2.  Shared by the stand-alone
+// kernel and the fused carry-over, so that both are the same statements on the same data.
+MPM_DEV float grid_cell_collision(const GridCfg& cfg, const CollisionArgs& col, int kx, int ky, int kz, int cell, float dt, float4& v) {
+#pragma clang fp contract(off)
+	float vel[3];
+	int node[3];
+	grid_cell_walls_gravity(cfg, kx, ky, kz, cell, dt, v, vel, node);
+	collision_resolve(col.obj, col.pose, node, cfg.dx, cfg.G * 4, (float) cfg.boundary * cfg.dx * 4.f, (float) (cfg.G - cfg.boundary) * 4.f * cfg.dx, vel);
+	return grid_cell_store_doubled_q(vel, v);
 }
 // One wave per grid block; the kernel of the phase-level callers (mpm_grid_update, mpm_substep, the first substep of a run): between
 // the substeps of a run the update rides on the carry-over (carry_grid_kernel<true, true>).
@@ -374,29 +399,15 @@ struct ShapeArgs {
 // grid_cell_collision's prologue + the optional field object + the slot loop; the same statements in the stand-alone kernel and the carry-over
 MPM_DEV float grid_cell_shapes(const GridCfg& cfg, const ShapeArgs& col, int kx, int ky, int kz, int cell, float dt, float4& v) {
 #pragma clang fp contract(off)
-	const bool wx = kx < cfg.boundary || kx >= cfg.G - cfg.boundary;
-	const bool wy = ky < cfg.boundary || ky >= cfg.G - cfg.boundary;
-	const bool wz = kz < cfg.boundary || kz >= cfg.G - cfg.boundary;
-	const float mass_inv = 1.f / v.x;
 	float vel[3];
-	vel[0] = wx ? 0.0f : v.y * mass_inv;
-	vel[1] = (wy ? 0.0f : v.z * mass_inv) + cfg.gravity * dt;
-	vel[2] = wz ? 0.0f : v.w * mass_inv;
-	const int node[3] = {kx * 4 + (cell >> 4), ky * 4 + ((cell >> 2) & 3), kz * 4 + (cell & 3)};
+	int node[3];
+	grid_cell_walls_gravity(cfg, kx, ky, kz, cell, dt, v, vel, node);
 	if(col.has_field) collision_resolve(col.field.obj, col.field.pose, node, cfg.dx, cfg.G * 4, (float) cfg.boundary * cfg.dx * 4.f, (float) (cfg.G - cfg.boundary) * 4.f * cfg.dx, vel);
 	const float X[3] = {(float) node[0] * cfg.dx, (float) node[1] * cfg.dx, (float) node[2] * cfg.dx};
 #pragma nounroll
 	for(int s = 0; s < col.count; ++s)
 		if(col.slot[s].shape.kind != 0) shape_resolve(col.slot[s].obj, col.slot[s].pose, col.slot[s].shape, X, vel);
-	v.y		= vel[0];
-	v.z		= vel[1];
-	v.w		= vel[2];
-	float q = vel[0] * vel[0] + vel[1] * vel[1] + vel[2] * vel[2];
-	q += vel[0] * vel[0];
-	q += vel[1] * vel[1];
-	q += vel[2] * vel[2];
-	if(q != q) q = __builtin_inff();
-	return q;
+	return grid_cell_store_doubled_q(vel, v);
 }
 // grid_update_collision_kernel's frame (one wave per grid block, lane = cell) around grid_cell_shapes: the kernel of the phase-level callers
 __global__ __launch_bounds__(256) void grid_update_shapes_kernel(GridCfg cfg, const int* __restrict__ nbc_ptr, float* __restrict__ grid, const int* __restrict__ keys, float dt, ShapeArgs col, unsigned* __restrict__ max_vel_bits) {
@@ -433,6 +444,69 @@ __global__ void test_collision_shape_kernel(ShapeSlot c, size_t n, const float* 
 	float xmt[3], x[3], nrm[3], sdis;
 	collision_material_point(c.obj, c.pose, X, xmt, x);
 	shape_query(c.shape, x, sdis, nrm);
+	out4[4 * i]		= sdis;
+	out4[4 * i + 1] = nrm[0];
+	out4[4 * i + 2] = nrm[1];
+	out4[4 * i + 3] = nrm[2];
+}
+
+// Grid update with a heightfield in at least one slot (mpm_collision_heightfield.hpp; an extension).  grid_update_shapes_kernel and
+// carry_grid_shapes_kernel keep their arguments and their code - a context without a heightfield launches them as before -; these are their
+// twins with one more collider kind.  A slot whose shape.kind is kShapeHeightfield (a number mpm_set_collision_shape refuses) reads
+// hf[slot]: the table pointer and its dimensions travel by value beside the slot, shape.inside_out is the heightfield's.  The kind is
+// wave-uniform (a scalar branch); the four corner loads are read-only float4 gathers, in range by heightfield_query's own check.
+constexpr int kShapeHeightfield = 5;
+struct TerrainArgs {
+	ShapeArgs col;
+	Heightfield hf[kMaxShapes];
+};
+// grid_cell_shapes plus the heightfield branch; the same statements in the stand-alone kernel and the carry-over
+MPM_DEV float grid_cell_terrain(const GridCfg& cfg, const TerrainArgs& ter, int kx, int ky, int kz, int cell, float dt, float4& v) {
+#pragma clang fp contract(off)
+	const ShapeArgs& col = ter.col;
+	float vel[3];
+	int node[3];
+	grid_cell_walls_gravity(cfg, kx, ky, kz, cell, dt, v, vel, node);
+	if(col.has_field) collision_resolve(col.field.obj, col.field.pose, node, cfg.dx, cfg.G * 4, (float) cfg.boundary * cfg.dx * 4.f, (float) (cfg.G - cfg.boundary) * 4.f * cfg.dx, vel);
+	const float X[3] = {(float) node[0] * cfg.dx, (float) node[1] * cfg.dx, (float) node[2] * cfg.dx};
+#pragma nounroll
+	for(int s = 0; s < col.count; ++s) {
+		if(col.slot[s].shape.kind == kShapeHeightfield)
+			heightfield_resolve(col.slot[s].obj, col.slot[s].pose, ter.hf[s], X, vel);
+		else if(col.slot[s].shape.kind != 0)
+			shape_resolve(col.slot[s].obj, col.slot[s].pose, col.slot[s].shape, X, vel);
+	}
+	return grid_cell_store_doubled_q(vel, v);
+}
+// grid_update_shapes_kernel's frame (one wave per grid block, lane = cell) around grid_cell_terrain: the kernel of the phase-level callers
+__global__ __launch_bounds__(256) void grid_update_terrain_kernel(GridCfg cfg, const int* __restrict__ nbc_ptr, float* __restrict__ grid, const int* __restrict__ keys, float dt, TerrainArgs ter, unsigned* __restrict__ max_vel_bits) {
+	const int cell	  = threadIdx.x & 63;
+	const int nblocks = min(*nbc_ptr, cfg.cap);
+	float vel_sqr	  = 0.f;
+	for(int blockno = (blockIdx.x * 256 + threadIdx.x) >> 6; blockno < nblocks; blockno += gridDim.x * 4) {
+		const int kx = keys[3 * blockno], ky = keys[3 * blockno + 1], kz = keys[3 * blockno + 2];
+		float* g	 = grid + (size_t) blockno * 256 + cell;
+		float4 v	 = {g[0], 0.f, 0.f, 0.f};
+		if(v.x > 0.0f) {
+			v.y = g[64];
+			v.z = g[128];
+			v.w = g[192];
+			vel_sqr = fmaxf(vel_sqr, grid_cell_terrain(cfg, ter, kx, ky, kz, cell, dt, v));
+			g[64]	= v.y;
+			g[128]	= v.z;
+			g[192]	= v.w;
+		}
+	}
+	wave_max_vel(vel_sqr, max_vel_bits);
+}
+// mpm_test_collision_heightfield: signed distance and normal of one heightfield at arbitrary domain points
+__global__ void test_collision_heightfield_kernel(ShapeSlot c, Heightfield f, size_t n, const float* __restrict__ xyz, float* __restrict__ out4) {
+	const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
+	if(i >= n) return;
+	const float X[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+	float xmt[3], x[3], nrm[3], sdis;
+	collision_material_point(c.obj, c.pose, X, xmt, x);
+	heightfield_query(f, x, sdis, nrm);
 	out4[4 * i]		= sdis;
 	out4[4 * i + 1] = nrm[0];
 	out4[4 * i + 2] = nrm[1];
@@ -968,6 +1042,30 @@ __global__ __launch_bounds__(256) void carry_grid_shapes_kernel(GridCfg cfg, con
 		unsigned* slot		= max_vel_bits + (blockIdx.x & (kMaxVelSlots - 1)) * kMaxVelStride;
 		if(bits > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, bits);
 	}
+}
+
+// carry_grid_shapes_kernel's frame around grid_cell_terrain: the grid update with a heightfield in a slot riding on the carry-over
+__global__ __launch_bounds__(256) void carry_grid_terrain_kernel(GridCfg cfg, const int* __restrict__ status, const int* __restrict__ new_keys, const int* __restrict__ old_table, const float* __restrict__ p2g_grid, float* __restrict__ grid, float dt, unsigned* __restrict__ max_vel_bits, TerrainArgs ter) {
+	const int nbc	  = min(status[ST_CNT_P] + status[ST_CNT_N], cfg.cap);
+	const int old_nbc = min(status[ST_NBC], cfg.cap);
+	const int lane = threadIdx.x & 63;
+	float vel_sqr  = 0.f;
+	for(int nb = blockIdx.x * 4 + (threadIdx.x >> 6); nb < nbc; nb += gridDim.x * 4) {
+		const int kx = new_keys[3 * nb], ky = new_keys[3 * nb + 1], kz = new_keys[3 * nb + 2];
+		const int old = table_query(cfg, old_table, kx, ky, kz);
+		float4 v	  = {0.f, 0.f, 0.f, 0.f};
+		if(old >= 0 && old < old_nbc) {
+			const float* s = p2g_grid + (size_t) old * 256;
+			v			   = {s[lane], s[64 + lane], s[128 + lane], s[192 + lane]};
+		}
+		if(v.x > 0.0f) vel_sqr = fmaxf(vel_sqr, grid_cell_terrain(cfg, ter, kx, ky, kz, lane, dt, v));
+		float* d	  = grid + (size_t) nb * 256;
+		d[lane]		  = v.x;
+		d[64 + lane]  = v.y;
+		d[128 + lane] = v.z;
+		d[192 + lane] = v.w;
+	}
+	wave_max_vel(vel_sqr, max_vel_bits);
 }
 
 // Carry the P2G result (old numbering) into the current grid (new numbering): every NEW neighbour block is written

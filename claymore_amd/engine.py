@@ -259,6 +259,38 @@ class Engine:
         if animate:
             self.set_collision_clock(True, float(obj.time))
 
+    def set_collision_heightfield(self, slot, heights=None, *, origin=(0.0, 0.0), spacing=None, inside_out=False, animate=False, **fields):
+        """Install a heightfield - terrain y = h(x, z) in material coordinates - in slot 0 .. 3 (mpm_set_collision_heightfield, HIP engine
+        only).  heights: a 2-D array of shape [nx, nz], sample (i, k) at material (origin[0] + i spacing, origin[1] + k spacing);
+        heights=None empties the slot.  inside_out: the solid is above the surface (a ceiling).  fields: those of set_collision_object (type,
+        friction, scale, dsdt, trans, trans_vel, omega, rot_mat, time).  Outside the table's footprint the collider touches nothing.  The
+        slots are the shapes' (set_collision_shape); every install leaves the one clock stopped at `time`."""
+        if heights is None:
+            self._check(self.api.set_collision_heightfield(self.ctx, int(slot), None, None, None))
+            return
+        if spacing is None:
+            raise ValueError("set_collision_heightfield: spacing is required")
+        obj = _ffi.CollisionObject()
+        self._check(self.api.default_collision_object(C.byref(obj)))
+        for k, v in fields.items():
+            cur = getattr(obj, k)
+            if hasattr(cur, "__len__"):
+                for i, x in enumerate(np.asarray(v, dtype=np.float32).ravel()):
+                    cur[i] = float(x)
+            else:
+                setattr(obj, k, v)
+        h = np.ascontiguousarray(heights, dtype=np.float32)
+        if h.ndim != 2:
+            raise ValueError(f"set_collision_heightfield: heights must be 2-D [nx, nz], got shape {h.shape}")
+        hf = _ffi.Heightfield()
+        hf.nx, hf.nz = h.shape
+        hf.origin[0], hf.origin[1] = float(origin[0]), float(origin[1])
+        hf.spacing = float(spacing)
+        hf.inside_out = 1 if inside_out else 0
+        self._check(self.api.set_collision_heightfield(self.ctx, int(slot), C.byref(obj), C.byref(hf), h.ctypes.data))
+        if animate:
+            self.set_collision_clock(True, float(obj.time))
+
     def set_collision_clock(self, running=True, time=0.0):
         """Set the collision object's time and start (or stop) its clock: a running clock advances by dt with every grid update,
         the update of a substep sees the object at the time the substep starts (HIP engine only)."""
@@ -345,7 +377,10 @@ def build_engine(scene, device=0, api=None):
         eng.set_collision_object(**{**scene["collision"], "animate": False})
     colliders = scene.get("colliders") or []
     for slot, c in enumerate(colliders):
-        eng.set_collision_shape(slot, **{**c, "animate": False})
+        if c.get("kind") == "heightfield":
+            eng.set_collision_heightfield(slot, **{**{k: v for k, v in c.items() if k != "kind"}, "animate": False})
+        else:
+            eng.set_collision_shape(slot, **{**c, "animate": False})
     # one clock for all colliders: started once, after the last install (every install stops it)
     moving = [c for c in ([scene["collision"]] if scene.get("collision") else []) + list(colliders) if c.get("animate")]
     if moving:

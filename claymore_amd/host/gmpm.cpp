@@ -116,14 +116,62 @@ bool vec3(const mj::Value& v, const char* k, float (&out)[3]) {
 }
 
 // One entry of "colliders": {"shape": "halfspace" ("point", "normal") | "sphere" ("center", "radius") | "box" ("center", "half_extents") |
-// "capsule" ("a", "b", "radius"), "type": "sticky|slip|separate", "friction", "velocity", "omega", "inside_out"}.  A collider with
+// "capsule" ("a", "b", "radius") | "heightfield" (below), "type": "sticky|slip|separate", "friction", "velocity", "omega", "inside_out"}.  A collider with
 // "velocity" or "omega" moves: it translates, and turns about its point / center / a, with the context's clock, which then starts at 0.
-bool parse_collider(const mj::Value& c, mpm_collision_object& obj, mpm_collision_shape& sh, bool& moving) {
+// {"shape": "heightfield", "nx", "nz", "origin": [x, z], "spacing", "heights": [nx nz numbers, sample (i, k) at i nz + k] | "file": "name.f32"
+// (raw little-endian float32, nx nz values, relative to the scene file)} with the same "type", "friction", "velocity", "omega", "inside_out"
+// installs a heightfield (mpm_set_collision_heightfield): `heights` is filled and hf.nx > 0 says so.  It turns about (origin x, 0, origin z).
+bool parse_collider(const mj::Value& c, mpm_collision_object& obj, mpm_collision_shape& sh, bool& moving, mpm_heightfield& hf, std::vector<float>& heights, const std::string& scene_dir) {
 	mpm_default_collision_object(&obj);
 	std::memset(&sh, 0, sizeof(sh));
+	std::memset(&hf, 0, sizeof(hf));
 	const std::string shape = c.has("shape") ? c["shape"].string() : "";
 	bool ok = true;
-	if(shape == "halfspace") {
+	if(shape == "heightfield") {
+		if(!c.has("nx") || !c.has("nz") || !c.has("spacing") || (!c.has("heights") && !c.has("file"))) {
+			std::fprintf(stderr, "gmpm: collider 'heightfield' lacks a field (nx, nz, spacing, heights or file)\n");
+			return false;
+		}
+		const float fx = num(c, "nx", 0.f), fz = num(c, "nz", 0.f);
+		hf.nx	   = (int) fx;
+		hf.nz	   = (int) fz;
+		hf.spacing = num(c, "spacing", 0.f);
+		if((float) hf.nx != fx || (float) hf.nz != fz) {
+			std::fprintf(stderr, "gmpm: heightfield nx, nz must be whole numbers\n");
+			return false;
+		}
+		if(c.has("origin")) {
+			if(c["origin"].type != mj::Value::Array || c["origin"].arr.size() != 2) {
+				std::fprintf(stderr, "gmpm: heightfield 'origin' must be [x, z]\n");
+				return false;
+			}
+			for(int d = 0; d < 2; ++d) hf.origin[d] = (float) c["origin"][d].number();
+		}
+		if(hf.nx < 2 || hf.nz < 2 || hf.nx > MPM_HEIGHTFIELD_MAX_SAMPLES || hf.nz > MPM_HEIGHTFIELD_MAX_SAMPLES) {
+			std::fprintf(stderr, "gmpm: heightfield nx, nz must be 2 .. %d\n", (int) MPM_HEIGHTFIELD_MAX_SAMPLES);
+			return false;
+		}
+		const size_t n = (size_t) hf.nx * hf.nz;
+		heights.assign(n, 0.f);
+		if(c.has("heights")) {
+			if(c["heights"].arr.size() != n) {
+				std::fprintf(stderr, "gmpm: heightfield 'heights' has %zu values, nx nz = %zu\n", c["heights"].arr.size(), n);
+				return false;
+			}
+			for(size_t i = 0; i < n; ++i) heights[i] = (float) c["heights"][i].number();
+		} else {
+			const std::string name = c["file"].string();
+			const std::string path = !name.empty() && name[0] == '/' ? name : scene_dir + "/" + name;
+			std::ifstream f(path, std::ios::binary);
+			if(!f || !f.read(reinterpret_cast<char*>(heights.data()), (std::streamsize) (n * sizeof(float))) || f.peek() != std::ifstream::traits_type::eof()) {
+				std::fprintf(stderr, "gmpm: heightfield file '%s' does not hold exactly %zu float32 values\n", path.c_str(), n);
+				return false;
+			}
+		}
+		sh.a[0] = hf.origin[0];// the pivot of omega
+		sh.a[2] = hf.origin[1];
+		hf.inside_out = c.has("inside_out") && c["inside_out"].type == mj::Value::Bool && c["inside_out"].b;
+	} else if(shape == "halfspace") {
 		sh.kind = MPM_SHAPE_HALFSPACE;
 		ok		= vec3(c, "point", sh.a) && vec3(c, "normal", sh.b);
 	} else if(shape == "sphere") {
@@ -136,7 +184,7 @@ bool parse_collider(const mj::Value& c, mpm_collision_object& obj, mpm_collision
 		sh.kind = MPM_SHAPE_CAPSULE;
 		ok		= vec3(c, "a", sh.a) && vec3(c, "b", sh.b) && c.has("radius");
 	} else {
-		std::fprintf(stderr, "gmpm: unknown collider shape '%s' (expected halfspace, sphere, box or capsule)\n", shape.c_str());
+		std::fprintf(stderr, "gmpm: unknown collider shape '%s' (expected halfspace, sphere, box, capsule or heightfield)\n", shape.c_str());
 		return false;
 	}
 	if(!ok) {
@@ -278,8 +326,10 @@ int main(int argc, char** argv) {
 		for(size_t ci = 0; ci < cols.arr.size(); ++ci) {
 			mpm_collision_object obj;
 			mpm_collision_shape sh;
-			if(!parse_collider(cols[ci], obj, sh, moving)) return 1;
-			rc = mpm_set_collision_shape(ctx, (int) ci, &obj, &sh);
+			mpm_heightfield hf;
+			std::vector<float> heights;
+			if(!parse_collider(cols[ci], obj, sh, moving, hf, heights, scene_dir)) return 1;
+			rc = hf.nx ? mpm_set_collision_heightfield(ctx, (int) ci, &obj, &hf, heights.data()) : mpm_set_collision_shape(ctx, (int) ci, &obj, &sh);
 			if(rc) die(ctx, rc);
 		}
 		std::printf("has %zu colliders%s\n", cols.arr.size(), moving ? ", clock running" : "");

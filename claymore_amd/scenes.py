@@ -282,3 +282,36 @@ def colliders_demo(bits=6, boundary="slip", friction=0.3, speed=1.0, dt=1e-4):
             "models": [{"material": FIXED_COROTATED, "xyz": lattice_box(bits, lo, hi), "v0": (0.0, 0.0, 0.0),
                         "params": {"volume": _vol(bits), "youngs_modulus": 5e3, "poisson_ratio": 0.4, "rho": 1e3}}],
             "colliders": cols}
+
+
+def ramp_heights(bits=6, slope=0.3, base_cells=None, berm_cells=1.5, berm_at_cells=-8.0, berm_width_cells=3.0, ripple_cells=0.25):
+    """The terrain of block_on_ramp: (N + 1) x (N + 1) heights at the grid nodes' (x, z) (spacing dx, origin 0), float32 [nx, nz].  A ramp that
+    rises along +x (downhill is -x) through `base_cells` at the domain's centre, a Gaussian berm across it `berm_at_cells` from the centre, and
+    a shallow ripple along z, so that neither gradient is zero anywhere near the block."""
+    n, dx = 1 << bits, 1.0 / (1 << bits)
+    base = (n // 2 - 1 if base_cells is None else base_cells) * dx
+    X, Z = np.meshgrid(np.arange(n + 1) * dx, np.arange(n + 1) * dx, indexing="ij")
+    h = base + slope * (X - 0.5)
+    h = h + berm_cells * dx * np.exp(-(((X - 0.5) - berm_at_cells * dx) / (berm_width_cells * dx)) ** 2)
+    h = h + ripple_cells * dx * np.sin(2 * np.pi * 3 * Z + 0.4)
+    return h.astype(np.float32)
+
+
+def block_on_ramp(bits=6, block_cells=(6, 4, 6), speed=0.5, boundary="slip", friction=0.1, slope=0.3, trans_vel=(0.0, 0.0, 0.0), animate=False, dt=1e-4,
+                  material=FIXED_COROTATED):
+    """A small elastic block dropped (v0 = (0, -speed, 0)) onto terrain given as a heightfield (Engine.set_collision_heightfield): a ramp with
+    a berm downhill of the block (ramp_heights).  The block's lowest particle layer starts within a cell of the highest ground under it, so
+    the contact begins in the first substeps; trans_vel / animate move the terrain.  No level set is rasterised or stored."""
+    n, dx = 1 << bits, 1.0 / (1 << bits)
+    heights = ramp_heights(bits, slope)
+    lo = [n // 2 - int(block_cells[0]) // 2, 0, n // 2 - int(block_cells[2]) // 2]
+    hi = [lo[0] + int(block_cells[0]), 0, lo[2] + int(block_cells[2])]
+    ground = float(heights[lo[0]:hi[0] + 1, lo[2]:hi[2] + 1].max())
+    lo[1] = int(np.floor(ground / dx)) + 1
+    hi[1] = lo[1] + int(block_cells[1])
+    col = {"kind": "heightfield", "heights": heights, "origin": (0.0, 0.0), "spacing": dx, "type": {"sticky": 0, "slip": 1, "separate": 2}[boundary],
+           "friction": friction, "trans_vel": trans_vel, "animate": animate}
+    return {"name": "block_on_ramp", "bits": bits, "dt": dt, "config": {},
+            "models": [{"material": material, "xyz": lattice_box(bits, lo, hi), "v0": (0.0, -speed, 0.0),
+                        "params": {"volume": _vol(bits), "youngs_modulus": 5e3, "poisson_ratio": 0.4, "rho": 1e3}}],
+            "colliders": [col]}

@@ -304,6 +304,39 @@ int mpm_set_collision_shape(mpm_ctx* ctx, int slot, const mpm_collision_object* 
  * grid kernels would use for this collider at `time` - out4[n*4] = {sdis, nx, ny, nz}.  dx is not used by the evaluation. */
 int mpm_test_collision_shape(const mpm_collision_object* obj, const mpm_collision_shape* shape, float time, float dx, const float* xyz, size_t n, float* out4, int device);
 
+/* Extension: a collision object given as a 2-D height table - terrain y = h(x, z) in material coordinates (up is material y; obj's rot_mat,
+ * trans and trans_vel tilt and move it).  A 512 x 512 table is 1 MiB as heights and 4 MiB as installed, where the level set of the same
+ * ground is a float4 per node of the whole domain.  HIP library only.
+ * A heightfield occupies one of the four slots of mpm_set_collision_shape; either kind may sit in any slot, installing either kind over
+ * the other replaces it (and frees the table), and mpm_set_collision_shape(ctx, slot, NULL, NULL) empties a heightfield slot too.  The
+ * heightfield is reachable only through mpm_set_collision_heightfield: mpm_set_collision_shape goes on refusing every kind but 1 .. 4.
+ * Everything the shapes' comment says about the pose, the response, the order of the colliders (field object, then slots 0 .. 3), the
+ * doubled |v|^2 and the one clock holds word for word; like a shape, a heightfield is not part of a checkpoint.  The context owns the
+ * table: it is freed on replace, on removal and in mpm_destroy.
+ * Install (on the host).  From the heights H(i, k) one float4 {H, gx, gz, 0} per sample: gx = (H(i+1,k) - H(i-1,k)) / (2.f * spacing) in
+ * the interior, (H(1,k) - H(0,k)) / spacing at i = 0, (H(nx-1,k) - H(nx-2,k)) / spacing at i = nx-1; gz the same along k.
+ * Query at the material point x.  u = (x0 - origin0) / spacing, w = (x2 - origin1) / spacing.  Outside the footprint the collider touches
+ * nothing, whatever inside_out says (sdis = NaN, n = 0): a point is outside unless 0 <= u <= (float) (nx-1) and 0 <= w <= (float) (nz-1); a
+ * NaN is outside.  i = min((int) u, nx-2), k likewise; fu = u - (float) i, fw = w - (float) k; weights (1-fu)(1-fw), fu(1-fw), (1-fu)fw,
+ * fu fw; each channel ((w00 t00 + w10 t10) + w01 t01) + w11 t11; len = sqrtf((gx gx + 1.f) + gz gz); n = (-gx, 1, -gz) / len;
+ * sdis = (x1 - h) / len - the distance to the tangent plane, not a Euclidean distance: the response uses its sign only.  inside_out
+ * changes the sign of sdis and n.  A node is touched when sdis <= 0. */
+enum { MPM_HEIGHTFIELD_MAX_SAMPLES = 4096 }; /* per axis */
+typedef struct mpm_heightfield {
+	int nx, nz;		 /* samples along material x and z, each 2 .. MPM_HEIGHTFIELD_MAX_SAMPLES */
+	float origin[2]; /* material (x, z) of sample (0, 0) */
+	float spacing;	 /* > 0, finite: sample (i, k) sits at (origin[0] + i spacing, origin[1] + k spacing) */
+	int inside_out;	 /* 1: the solid is ABOVE the surface (a ceiling) */
+	int reserved[6];
+} mpm_heightfield;
+/* Install a heightfield in slot 0 .. 3 with the pose, motion and boundary fields of `obj`, or empty the slot (obj == NULL).
+ * heights: nx * nz floats on the host, sample (i, k) at [i * nz + k]; copied during the call.  MPM_ERR_INVALID (mpm_last_error names the
+ * field): slot outside 0..3, nx or nz outside 2..4096, spacing <= 0 or not finite, a NaN origin, a NULL hf or heights with a non-NULL obj,
+ * boundary type outside 0..2, any height or derived table entry that is not finite.  A refused install leaves the slot's occupant in place. */
+int mpm_set_collision_heightfield(mpm_ctx* ctx, int slot, const mpm_collision_object* obj, const mpm_heightfield* hf, const float* heights);
+/* Function-level entry point (as mpm_test_collision_shape): out4[n*4] = {sdis, nx, ny, nz} at n arbitrary domain points xyz[n*3]. */
+int mpm_test_collision_heightfield(const mpm_collision_object* obj, const mpm_heightfield* hf, const float* heights, float time, const float* xyz, size_t n, float* out4, int device);
+
 /* Current capacities and the number of times check_capacity() (gmpm_simulator.cuh:283-300) has grown them: blocks
  * (exterior count limit), bins per model (bin_capacity[8]).  HIP library only. */
 int mpm_get_capacity(mpm_ctx* ctx, int64_t* block_capacity, int64_t* bin_capacity, int* growth_events);

@@ -3,7 +3,7 @@
 libraries in ONE process, interleaved (lib A, lib B, lib A, ...), so that a parent build and a branch build are compared on the same
 box under the same conditions.
 
-    python tools/collider_substep.py [--scene c2|c3] [--steps 200] [--warmup 50] [--reps 3] [--objects none,static,moving,shape,shapes4] [--phase 20]
+    python tools/collider_substep.py [--scene c2|c3] [--steps 200] [--warmup 50] [--reps 3] [--objects none,static,moving,shape,shapes4,ground_hf,ground_shape,ground_field] [--phase 20]
                                      [--out FILE] [lib.so ...]
 
 Scene: C2 (one elastic sphere of ~5 M particles dropped at 256^3; the level-set field is 256^3 float4 = 256 MiB) or C3 (the sand column at
@@ -11,7 +11,10 @@ Scene: C2 (one elastic sphere of ~5 M particles dropped at 256^3; the level-set 
 kernel evaluates it at every grid node with mass either way, which is the cost in question.  A library without the clock's entry points
 (a parent build) runs `none` and `static` only.  `shape`: the same sphere given in closed form (mpm_set_collision_shape: no field, no loads);
 `shapes4`: that sphere, a floor half-space, a box and a capsule in the four slots, all clear of the material.  A library without
-mpm_set_collision_shape skips both.  --phase N: after the run, N more substeps phase by phase (grid update, G2P2G, rebuild), whose median
+mpm_set_collision_shape skips both.  `ground_hf` / `ground_shape` / `ground_field`: one flat ground just under the material given three ways -
+a heightfield (mpm_set_collision_heightfield: an (N + 1)^2 table of constant height at spacing dx, four float4 gathers per massed cell), the
+half-space shape at that height, and the level set of the same plane (sdf = y - height, gradient +y) - the same physics (the level set
+alone stops at query_sdf's box); a library without mpm_set_collision_heightfield skips `ground_hf`.  --phase N: after the run, N more substeps phase by phase (grid update, G2P2G, rebuild), whose median
 grid-update time is the stand-alone kernel's (`phase_grid_ms`); in mpm_run_fixed the update rides on the carry-over inside `partition_ms`.
 `object_bytes`: device memory taken by installing the collider (hipMemGetInfo before and after).  Prints one JSON line per (rep, library, object) with the library's per-substep averages
 (HIP events on the compute stream) and the wall-clock time per substep, then a summary of medians."""
@@ -23,6 +26,7 @@ import statistics
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -53,12 +57,15 @@ def main():
     bits = sc["bits"]
     sdf, grad = scenes.sphere_level_set(bits, (0.5, 0.12, 0.5), 0.06)
     col = {"sdf": sdf, "grad": grad, "type": 1, "friction": 0.3, "trans": (0.5, 0.12, 0.5)}
+    ground, n = 0.02, 1 << bits
     apis = [(os.path.basename(os.path.dirname(os.path.abspath(p))) + "/" + os.path.basename(p), load(p)) for p in a.libs]
     rows, lines = [], []
     for rep in range(a.reps):
         for name, api in apis:
             for obj in a.objects.split(","):
                 if (obj == "moving" and not hasattr(api, "set_collision_clock")) or (obj in ("shape", "shapes4") and not hasattr(api, "set_collision_shape")):
+                    continue
+                if (obj == "ground_hf" and not hasattr(api, "set_collision_heightfield")) or (obj == "ground_shape" and not hasattr(api, "set_collision_shape")):
                     continue
                 eng = build_engine(sc, api=api)
                 free0 = torch.cuda.mem_get_info()[0]
@@ -68,6 +75,16 @@ def main():
                     eng.set_collision_shape(1, "halfspace", a=(0.5, 0.02, 0.5), b=(0.0, -1.0, 0.0), inside_out=True, type=1, friction=0.3)
                     eng.set_collision_shape(2, "box", a=(0.2, 0.1, 0.2), b=(0.05, 0.04, 0.05), type=0)
                     eng.set_collision_shape(3, "capsule", a=(0.75, 0.1, 0.3), b=(0.75, 0.1, 0.7), radius=0.04, type=2, friction=0.3)
+                elif obj == "ground_hf":
+                    eng.set_collision_heightfield(0, np.full((n + 1, n + 1), ground, np.float32), origin=(0.0, 0.0), spacing=1.0 / n, type=1, friction=0.3)
+                elif obj == "ground_shape":
+                    eng.set_collision_shape(0, "halfspace", a=(0.5, ground, 0.5), b=(0.0, 1.0, 0.0), type=1, friction=0.3)
+                elif obj == "ground_field":
+                    gsdf = np.broadcast_to((np.arange(n, dtype=np.float32) / np.float32(n) - np.float32(ground))[None, :, None], (n, n, n))
+                    ggrad = np.zeros((3, n, n, n), np.float32)
+                    ggrad[1] = 1.0
+                    eng.set_collision_object(sdf=gsdf, grad=ggrad, type=1, friction=0.3)
+                    del gsdf, ggrad
                 elif obj in ("static", "moving"):
                     eng.set_collision_object(**col, **({"trans_vel": (0.0, 0.05, 0.0), "omega": (1.0, 2.0, 3.0), "dsdt": 0.1} if obj == "moving" else {}))
                 if obj == "moving":

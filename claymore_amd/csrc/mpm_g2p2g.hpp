@@ -23,6 +23,7 @@
 // separate arenas (lane parity); what is left is decided by an owner table and goes through the serial path.
 #pragma once
 #include "mpm_device_math.hpp"
+#include "mpm_cube_lane.hpp"
 
 namespace mpm {
 
@@ -451,6 +452,81 @@ MPM_DEV int code_off(int c) {
 	return ((c & 15) - 1) * kP2GStrideX + (((c >> 4) & 15) - 1) * kP2GStrideY + ((c >> 8) - 1);
 }
 
+// ---- The node cube <-> the eight grid blocks, two octants per wave-instruction (the lane mapping: mpm_cube_lane.hpp).  Both kernels stage the grid
+//      velocities in and write the scatter arenas back with these.  The grid block numbers sit in lanes 54..61 of the info row and the lane is a
+//      compile-time constant per pass: v_readlane and a select per lane half, no ds_bpermute round trip in front of every load / atomic.
+static_assert(kG2PStrideX == 6 && kG2PStrideY == 1 && kG2PStrideZ == 36 && kP2GStrideX == 36 && kP2GStrideY == 6, "mpm_cube_lane.hpp states the arena strides");
+template<int PASS>
+MPM_DEV int cube_grid_block(int info, int lane) {// grid block of this lane's octant in pass PASS (-1: the block does not exist)
+	const int lo = __builtin_amdgcn_readlane(info, 54 + 2 * PASS), hi = __builtin_amdgcn_readlane(info, 55 + 2 * PASS);
+	return lane & 32 ? hi : lo;
+}
+// Staging in, first half: the 12 loads (four passes x vx, vy, vz; idle lanes and lanes of a missing block re-read a valid cell).  The caller puts its own
+// independent loads between this and cube_stage_store, which waits for them.
+struct CubeStage {
+	float v[4][3];
+	int nb[4];
+};
+MPM_DEV void cube_stage_load(const float* __restrict__ grid, int info, int lane, CubeStage& st) {
+	MPM_MARK("P_stage");
+	auto pass = [&](auto pc) {
+		constexpr int P = decltype(pc)::value;
+		const CubeLane c = cube_lane(P, lane);
+		st.nb[P]		 = cube_grid_block<P>(info, lane);
+		const float* gb	 = grid + (size_t) (st.nb[P] < 0 ? 0 : st.nb[P]) * 256 + c.cell;
+		st.v[P][0]		 = gb[64];
+		st.v[P][1]		 = gb[128];
+		st.v[P][2]		 = gb[192];
+	};
+	pass(std::integral_constant<int, 0> {});
+	pass(std::integral_constant<int, 1> {});
+	pass(std::integral_constant<int, 2> {});
+	pass(std::integral_constant<int, 3> {});
+}
+// second half: four ds_write_b128 into the gather arena, a node is {vx, vy, vz, vz} (gather_apic); zero for a missing block
+MPM_DEV void cube_stage_store(float4* __restrict__ g2p, int lane, const CubeStage& st) {
+#pragma unroll
+	for(int p = 0; p < 4; ++p) {
+		const CubeLane c = cube_lane(p, lane);
+		const bool have	 = st.nb[p] >= 0;
+		const float x = have ? st.v[p][0] : 0.f, y = have ? st.v[p][1] : 0.f, z = have ? st.v[p][2] : 0.f;
+		if(c.on) g2p[c.g2p] = make_float4(x, y, z, z);
+	}
+}
+// Write-back, arena -> next grid (:907-936): one hardware f32 atomic per touched node and channel.  All eight arena reads (four passes x two arenas) are in
+// flight before the first sum (the particle loop's registers are dead here); per node A + B as ever, so a block's contribution to a node is what it was
+// bit for bit; then 16 atomic instructions, 54 lanes each: two octants = (three-cell runs in) two 256-B channel rows per instruction.  A channel whose sum
+// is zero gets no atomic, tested per channel: a zero mass sum does not imply zero momentum (a weight product can flush m W to zero and leave W times a
+// large affine term).
+// (Walking the 216 arena nodes in arena order instead spreads each instruction over ~21 three-cell runs in up to eight blocks: five times the L2
+// atomic requests.)
+MPM_DEV void cube_writeback(const float4* __restrict__ p2g, int info, int lane, float* __restrict__ next_grid) {
+	MPM_MARK("P_writeback");
+	__asm__ volatile("" : "+v"(lane));// (the coordinates of the write-back are formed here: shared with the set-up's they would sit in registers through the particle loop)
+	float4 va[4], vb[4];
+#pragma unroll
+	for(int p = 0; p < 4; ++p) {
+		const CubeLane c = cube_lane(p, lane);
+		va[p] = p2g[c.p2g], vb[p] = p2g[kP2GArena2 + c.p2g];
+	}
+	auto pass = [&](auto pc) {
+		constexpr int P = decltype(pc)::value;
+		const CubeLane c = cube_lane(P, lane);
+		const int nb	 = cube_grid_block<P>(info, lane);
+		const float4 v	 = make_float4(va[P].x + vb[P].x, va[P].y + vb[P].y, va[P].z + vb[P].z, va[P].w + vb[P].w);
+		float* g		 = next_grid + (size_t) (nb < 0 ? 0 : nb) * 256 + c.cell;
+		const bool go	 = c.on && nb >= 0;
+		if(go && v.x != 0.f) unsafeAtomicAdd(g, v.x);
+		if(go && v.y != 0.f) unsafeAtomicAdd(g + 64, v.y);
+		if(go && v.z != 0.f) unsafeAtomicAdd(g + 128, v.z);
+		if(go && v.w != 0.f) unsafeAtomicAdd(g + 192, v.w);
+	};
+	pass(std::integral_constant<int, 0> {});
+	pass(std::integral_constant<int, 1> {});
+	pass(std::integral_constant<int, 2> {});
+	pass(std::integral_constant<int, 3> {});
+}
+
 template<int MAT>
 __global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? kG2P2GWavesFluid : kG2P2GWaves) void g2p2g_kernel(GridCfg cfg, ModelView mv, const int* __restrict__ cur_keys, const float* __restrict__ grid, float* __restrict__ next_grid, const int* __restrict__ block_list, const int* __restrict__ only_flag, const int* __restrict__ nblocks_ptr, int nblocks, float dt, float new_dt, StepConst sk, int* __restrict__ status) {
 	constexpr int NCH = MatTraits<MAT>::nch;// floats per particle in a bin
@@ -501,21 +577,17 @@ __global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? kG2P2GWavesFluid : kG2P2G
 	int rec_cur	   = list[min(lane, cnt_cur - 1)];
 	int rec_next   = list[(64 < size ? 64 : 0) + min(lane, cnt_next - 1)];
 	// (`info` stays in its register: lane l < 27 holds the bin offset of source block l, lanes 27..53 the destination block
-	//  numbers, lanes 54..61 the eight grid blocks; they are read with __shfl = ds_bpermute, which costs no LDS space)
-	for(int i = lane; i < kP2GArena2 + kP2GNodes; i += 64) p2g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-	__syncthreads();
-	// ---- round trip 3: the 8 grid blocks (lane = cell -> 256-B rows per channel, :699-727) and the first 64 particles
-	float4 gv[8];
-#pragma unroll
-	for(int lb = 0; lb < 8; ++lb) {
-		const int nb	= __shfl(info, 54 + lb);
-		const float* gb = grid + (size_t) (nb < 0 ? 0 : nb) * 256;
-		gv[lb].x		= gb[64 + lane];
-		gv[lb].y		= gb[128 + lane];
-		gv[lb].z		= gb[192 + lane];
-		if(nb < 0) gv[lb].x = gv[lb].y = gv[lb].z = 0.f;
-		gv[lb].w = gv[lb].z;
+	//  numbers, lanes 54..61 the eight grid blocks; they are read with __shfl = ds_bpermute, which costs no LDS space - the grid blocks, whose lane is a
+	//  compile-time constant, with v_readlane: cube_grid_block)
+	{
+		float zero = 0.f;
+		__asm__ volatile("" : "+v"(zero));// (formed per block: as a constant the zero quad is hoisted out of the block loop and sits in four registers through the particle loop)
+		for(int i = lane; i < kP2GArena2 + kP2GNodes; i += 64) p2g[i] = make_float4(zero, zero, zero, zero);
 	}
+	__syncthreads();
+	// ---- round trip 3: the 8 grid blocks (two octants per load, mpm_cube_lane.hpp; :699-727) and the first 64 particles
+	CubeStage gv;
+	cube_stage_load(grid, info, lane, gv);
 	// Software prefetch: the particle data of iteration i+1 is requested at the top of iteration i (HBM latency under load
 	// is 2-4 us).  The loads are unconditional - lanes past the end of the block re-read its last record - so that the
 	// compiler can count them in s_waitcnt; their arrival is implied by the list-append atomics' results being consumed
@@ -544,12 +616,7 @@ __global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? kG2P2GWavesFluid : kG2P2G
 	};
 	Prefetch pf;
 	fetch(rec_cur, pf);
-#pragma unroll
-	for(int lb = 0; lb < 8; ++lb) {
-		const int cx = lane >> 4, cy = (lane >> 2) & 3, cz = lane & 3;// lane == cell of a 4x4x4 block
-		const int ax = cx + ((lb & 4) ? 4 : 0) - 1, ay = cy + ((lb & 2) ? 4 : 0) - 1, az = cz + ((lb & 1) ? 4 : 0) - 1;
-		if(((unsigned) ax < 6u) & ((unsigned) ay < 6u) & ((unsigned) az < 6u)) g2p[ax * kG2PStrideX + ay * kG2PStrideY + az * kG2PStrideZ] = gv[lb];
-	}
+	cube_stage_store(g2p, lane, gv);
 	__syncthreads();
 	// Software pipeline: the scatter of iteration i-1 (an ordered chain of 27 LDS round trips) is issued inside the material
 	// update of iteration i; `pv` is the payload in flight, pv_code its stencil base (-1: none).
@@ -817,31 +884,8 @@ __global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? kG2P2GWavesFluid : kG2P2G
 		if(lane == 0) mv.keep[b] = settled ? size : -1;
 	}
 	__syncthreads();
-	// ---- arena -> next grid: one hardware f32 atomic per touched node and channel (:907-936).  Lane = cell of one of the
-	//      eight grid blocks, like the staging above: every atomic instruction covers (27 cells of) ONE 256-B channel row.
-	//      (Walking the 216 arena nodes in arena order instead spreads each instruction over ~21 three-cell runs in up to
-	//      eight blocks: five times the L2 atomic requests.)
-	int lane_wb = lane;
-	__asm__ volatile("" : "+v"(lane_wb));// (the cell coordinates and look-up lanes of the write-back are formed here: shared with the set-up's they would sit in ~15 registers through the particle loop)
-	const int cx = lane_wb >> 4, cy = (lane_wb >> 2) & 3, cz = lane_wb & 3;
-#pragma unroll
-	for(int lb = 0; lb < 8; ++lb) {
-		int sel = 54 + lb;
-		__asm__ volatile("" : "+s"(sel));
-		const int nb = __shfl(info, sel);
-		const int ax = cx + ((lb & 4) ? 4 : 0) - 1, ay = cy + ((lb & 2) ? 4 : 0) - 1, az = cz + ((lb & 1) ? 4 : 0) - 1;
-		const bool in = ((unsigned) ax < 6u) & ((unsigned) ay < 6u) & ((unsigned) az < 6u);
-		const int n	  = in ? ax * kP2GStrideX + ay * kP2GStrideY + az : 0;
-		const float4 va = p2g[n], vb = p2g[kP2GArena2 + n];
-		const float4 v	= make_float4(va.x + vb.x, va.y + vb.y, va.z + vb.z, va.w + vb.w);
-		if(in && nb >= 0) {
-			float* g = next_grid + (size_t) nb * 256 + lane_wb;
-			if(v.x != 0.f) unsafeAtomicAdd(g, v.x);
-			if(v.y != 0.f) unsafeAtomicAdd(g + 64, v.y);
-			if(v.z != 0.f) unsafeAtomicAdd(g + 128, v.z);
-			if(v.w != 0.f) unsafeAtomicAdd(g + 192, v.w);
-		}
-	}
+	// ---- arena -> next grid (:907-936)
+	cube_writeback(p2g, info, lane, next_grid);
 	__syncthreads();// (a further block of this workgroup starts by clearing the arenas)
 	}
 }

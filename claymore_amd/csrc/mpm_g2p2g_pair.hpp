@@ -201,19 +201,14 @@ __global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? kPairWavesFluid : kPairWa
 	read_slice(1, s_next);
 	load_recs(s_cur, rec_cur);
 	load_recs(s_next, rec_next);
-	for(int i = lane; i < kP2GArena2 + kP2GNodes; i += 64) p2g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-	__syncthreads();
-	float4 gv[8];
-#pragma unroll
-	for(int lb = 0; lb < 8; ++lb) {
-		const int nb	= __shfl(info, 54 + lb);
-		const float* gb = grid + (size_t) (nb < 0 ? 0 : nb) * 256;
-		gv[lb].x		= gb[64 + lane];
-		gv[lb].y		= gb[128 + lane];
-		gv[lb].z		= gb[192 + lane];
-		if(nb < 0) gv[lb].x = gv[lb].y = gv[lb].z = 0.f;
-		gv[lb].w = gv[lb].z;
+	{
+		float zero = 0.f;
+		__asm__ volatile("" : "+v"(zero));// (formed per block: as a constant the zero quad is hoisted out of the block loop and sits in four registers through the particle loop)
+		for(int i = lane; i < kP2GArena2 + kP2GNodes; i += 64) p2g[i] = make_float4(zero, zero, zero, zero);
 	}
+	__syncthreads();
+	CubeStage gv;
+	cube_stage_load(grid, info, lane, gv);
 	constexpr int ROW = NCH - REC;
 	struct Prefetch {
 		float4 q[REC / 4];
@@ -249,12 +244,7 @@ __global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? kPairWavesFluid : kPairWa
 	// and carried into the next iteration, whose record loads then start at once
 	int sb_next[2] = {0, 0};
 	if constexpr(!kLateFetch) sb_next[0] = source_bin(rec_next[0]), sb_next[1] = source_bin(rec_next[1]);
-#pragma unroll
-	for(int lb = 0; lb < 8; ++lb) {
-		const int cx = lane >> 4, cy = (lane >> 2) & 3, cz = lane & 3;
-		const int ax = cx + ((lb & 4) ? 4 : 0) - 1, ay = cy + ((lb & 2) ? 4 : 0) - 1, az = cz + ((lb & 1) ? 4 : 0) - 1;
-		if(((unsigned) ax < 6u) & ((unsigned) ay < 6u) & ((unsigned) az < 6u)) g2p[ax * kG2PStrideX + ay * kG2PStrideY + az * kG2PStrideZ] = gv[lb];
-	}
+	cube_stage_store(g2p, lane, gv);
 	__syncthreads();
 	int qn		 = 0;
 	bool settled = true;
@@ -542,27 +532,7 @@ __global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? kPairWavesFluid : kPairWa
 	if(lane < kPairChunks) mv.pairinfo_out[(size_t) b * kPairChunks + lane] = pinfo & 0xffff;
 	__syncthreads();
 	// ---- arena -> next grid (:907-936), as in g2p2g_kernel
-	int lane_wb = lane;
-	__asm__ volatile("" : "+v"(lane_wb));
-	const int cx = lane_wb >> 4, cy = (lane_wb >> 2) & 3, cz = lane_wb & 3;
-#pragma unroll
-	for(int lb = 0; lb < 8; ++lb) {
-		int sel = 54 + lb;
-		__asm__ volatile("" : "+s"(sel));
-		const int nb = __shfl(info, sel);
-		const int ax = cx + ((lb & 4) ? 4 : 0) - 1, ay = cy + ((lb & 2) ? 4 : 0) - 1, az = cz + ((lb & 1) ? 4 : 0) - 1;
-		const bool in = ((unsigned) ax < 6u) & ((unsigned) ay < 6u) & ((unsigned) az < 6u);
-		const int n	  = in ? ax * kP2GStrideX + ay * kP2GStrideY + az : 0;
-		const float4 va = p2g[n], vb = p2g[kP2GArena2 + n];
-		const float4 v	= make_float4(va.x + vb.x, va.y + vb.y, va.z + vb.z, va.w + vb.w);
-		if(in && nb >= 0) {
-			float* g = next_grid + (size_t) nb * 256 + lane_wb;
-			if(v.x != 0.f) unsafeAtomicAdd(g, v.x);
-			if(v.y != 0.f) unsafeAtomicAdd(g + 64, v.y);
-			if(v.z != 0.f) unsafeAtomicAdd(g + 128, v.z);
-			if(v.w != 0.f) unsafeAtomicAdd(g + 192, v.w);
-		}
-	}
+	cube_writeback(p2g, info, lane, next_grid);
 	__syncthreads();
 	}
 }

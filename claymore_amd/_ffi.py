@@ -135,6 +135,11 @@ HIP_ONLY = {
     "checkpoint_size": (_i, [_vp, _P(_sz)]),
     "checkpoint_save": (_i, [_vp, _vp, _sz, _P(_sz)]),
     "checkpoint_load": (_i, [_vp, _vp, _sz]),
+    "track_particle_ids": (_i, [_vp, _i]),
+    "retrieve_ids": (_i, [_vp, _i, _vp, _vp, _P(_sz)]),
+    "particle_ids_size": (_i, [_vp, _P(_sz)]),
+    "particle_ids_save": (_i, [_vp, _vp, _sz, _P(_sz)]),
+    "particle_ids_load": (_i, [_vp, _vp, _sz]),
     "group_unique_id": (_i, [_vp]),
     "group_create": (_i, [_vp, _i, _i, _vp, _P(_vp)]),
     "group_create_local": (_i, [_P(_vp), _i, _P(_vp)]),

@@ -16,6 +16,7 @@
 #include "../../include/claymore_amd.h"
 #include "mpm_kernels.hpp"
 #include "mpm_readout.hpp"
+#include "mpm_particle_ids.hpp"
 
 using namespace mpm;
 
@@ -40,6 +41,7 @@ struct Model {
 	float* d_xyz = nullptr;// initial particle array; also the staging buffer of retrieve
 	float v0[3]	 = {0, 0, 0};
 	float* bins[2]	 = {nullptr, nullptr};
+	int* ids[2]		 = {nullptr, nullptr};// tracked contexts only (mpm_track_particle_ids): one int32 per bin slot, rolled and regrown with bins[] (mpm_particle_ids.hpp)
 	size_t bin_cap	 = 0;
 	int* binoff[2]	 = {nullptr, nullptr};
 	int* list[2]	 = {nullptr, nullptr};
@@ -103,6 +105,8 @@ struct mpm_ctx {
 	unsigned long long* d_counter = nullptr;
 	bool ready = false;
 	int capacity_events = 0;// number of capacity growths so far (check_capacity)
+	bool track_ids = false;// mpm_track_particle_ids: every model carries ids[2], moved beside every G2P2G launch
+	bool ids_valid = false;// ids[rollid] names the particles of bins[rollid] (false between mpm_checkpoint_load and mpm_particle_ids_load)
 	long long books_bias = 0;// check_books: particles a loaded checkpoint's state lacked beyond this context's own lost / dropped counters
 	bool has_collision = false;// level-set collision object of the MGSP grid update
 	CollisionObject collision {};// (collision.time is the clock: the time of the next grid update)
@@ -376,6 +380,7 @@ void mpm_destroy(mpm_ctx* ctx) {
 		hipFree(m.pairinfo[1]);
 		for(int i = 0; i < 2; ++i) {
 			hipFree(m.bins[i]);
+			hipFree(m.ids[i]);
 			hipFree(m.binoff[i]);
 			hipFree(m.list[i]);
 		}
@@ -557,6 +562,7 @@ int mpm_initial_setup(mpm_ctx* ctx) {
 		m.bin_cap = m.n / kBin + cap + 1;
 		for(int i = 0; i < 2; ++i) {
 			HIP_TRY(dalloc(&m.bins[i], m.bin_cap * m.nch * kBin));
+			if(ctx->track_ids) HIP_TRY(dalloc(&m.ids[i], m.bin_cap * kBin));
 			HIP_TRY(dalloc(&m.binoff[i], cap + 1));
 			HIP_TRY(dalloc(&m.list[i], cap * (size_t) g.ppb));
 		}
@@ -575,6 +581,7 @@ int mpm_initial_setup(mpm_ctx* ctx) {
 		if(pbc) {
 			init_bins_kernel<<<cdiv(pbc, 256), 256, 0, s>>>(pbc, m.out_count, m.size, m.row_of, m.binoff[r], m.binoff[n], &ctx->d_status[ST_BINS0 + mi]);
 			fill_bins_kernel<<<pbc, 256, 0, s>>>(g, m.nch, m.mc.log_jp0, m.d_xyz, m.list[1], m.size, m.binoff[r], m.bins[r], m.list[0]);
+			if(ctx->track_ids) fill_ids_kernel<<<pbc, 256, 0, s>>>(g.ppb, m.list[1], m.size, m.binoff[r], m.ids[r]);
 		}
 		m.list_in = 0;
 	}
@@ -607,6 +614,7 @@ int mpm_initial_setup(mpm_ctx* ctx) {
 	HIP_TRY(hipStreamSynchronize(s));
 	ctx->ready		   = true;
 	ctx->grid_momentum = true;
+	ctx->ids_valid	   = ctx->track_ids;
 	return MPM_OK;
 }
 
@@ -710,7 +718,7 @@ static ModelView make_view(mpm_ctx* ctx, Model& m) {
 // Model m as every readout reads it (mpm_readout.hpp): its list and bins, in the numberings of the last rebuild.
 static ReadoutArgs make_readout_args(mpm_ctx* ctx, const Model& m) {
 	const int r = ctx->rollid;
-	return ReadoutArgs {ctx->g, m.nch, m.pair ? 1 : 0, ctx->part[r].keys, ctx->part[r].table, ctx->part[r ^ 1].table, m.size, m.row_of, m.list[m.list_in], m.binoff[r], m.bins[r]};
+	return ReadoutArgs {ctx->g, m.nch, m.pair ? 1 : 0, ctx->part[r].keys, ctx->part[r].table, ctx->part[r ^ 1].table, m.size, m.row_of, m.list[m.list_in], m.binoff[r], m.bins[r], m.ids[r]};
 }
 
 // a launch size for `n` (an estimate that may be a few substeps old) particle blocks: margin for growth, a multiple of 8 (XCDs)
@@ -745,6 +753,11 @@ static void launch_g2p2g_model(mpm_ctx* ctx, Model& m, const int* block_list, co
 		default: break;
 	}
 	kernel<<<nwg, kG2P2GThreads, 0, s>>>(ctx->g, v, cur_keys, ctx->grid[0], ctx->grid[1], block_list, only_flag, nblocks_ptr, nblocks, dt, next_dt, sk, ctx->d_status);
+	// tracked context: the identities take the same step, from what this launch has just been given (mpm_particle_ids.hpp)
+	if(ctx->track_ids && nwg > 0) {
+		const MoveIdsArgs a {g.ppb, g.pid_bits, g.cap, m.pair ? 1 : 0, v.size, v.row_of, v.list_in, v.binoff_dst, v.blockinfo, m.ids[r], m.ids[r ^ 1]};
+		move_ids_kernel<<<cdiv((size_t) nwg, kMoveIdsWaves), kMoveIdsThreads, 0, s>>>(a, block_list, only_flag, nblocks_ptr, nblocks);
+	}
 }
 
 // substep_clear_kernel: the P2G part precedes G2P2G (clear_grid + the bucket counters, gmpm_simulator.cuh:383,:389), the rebuild
@@ -934,6 +947,8 @@ static int grow_capacity(mpm_ctx* ctx) {
 			const size_t nb = std::max(need, (size_t) m.bincount * 4 > m.bin_cap * 3 ? m.bin_cap * 3 / 2 + 1 : m.bin_cap);
 			HIP_TRY(hipDeviceSynchronize());
 			for(int i = 0; i < 2; ++i) HIP_TRY(regrow(&m.bins[i], m.bin_cap * m.nch * kBin, nb * m.nch * kBin, s));
+			if(ctx->track_ids)
+				for(int i = 0; i < 2; ++i) HIP_TRY(regrow(&m.ids[i], m.bin_cap * kBin, nb * kBin, s));
 			m.bin_cap = nb;
 			ctx->capacity_events++;
 		}
@@ -1414,10 +1429,11 @@ static void launch_readout(mpm_ctx* ctx, const Model& m, ReadoutKind kind, const
 	case kReadMomentum: readout_kernel<kReadMomentum><<<ctx->pbc, kReadoutThreads, 0, s>>>(a, ctx->grid[0], out); break;
 	case kReadStress: readout_kernel<kReadStress><<<ctx->pbc, kReadoutThreads, 0, s>>>(a, nullptr, out); break;
 	case kReadStressTotals: readout_kernel<kReadStressTotals><<<ctx->pbc, kReadoutThreads, 0, s>>>(a, nullptr, out); break;
+	case kReadIds: readout_kernel<kReadIds><<<ctx->pbc, kReadoutThreads, 0, s>>>(a, nullptr, out); break;
 	}
 }
 
-// One per-particle readout of a model (readout_kernel<kind>: kReadState, kReadVelocity or kReadStress) into the caller's arrays: host[0] the positions,
+// One per-particle readout of a model (readout_kernel<kind>: kReadState, kReadVelocity, kReadStress or kReadIds - whose column 1 is the int32 id) into the caller's arrays: host[0] the positions,
 // host[1] and host[2] (null: not asked for) kReadoutWidth[kind][c] floats a particle.  Positions are staged in m.d_xyz, the other columns
 // in scratch released on every exit path (an output call, once per frame at most).  *n: the capacity of the arrays in, the particles
 // written out - MPM_ERR_CAPACITY if that is not all of them.
@@ -1433,6 +1449,7 @@ static int readout_particles(mpm_ctx* ctx, int model, ReadoutKind kind, float* c
 			HIP_TRY(scratch[c].alloc(kReadoutWidth[kind][c] * cap));
 			out.col[c] = scratch[c].p;
 		}
+	if(kind == kReadIds) out.ids = reinterpret_cast<int*>(out.col[1]);
 	HIP_TRY(hipMemsetAsync(ctx->d_counter, 0, sizeof(unsigned long long), s));
 	launch_readout(ctx, m, kind, out, s);
 	HIP_TRY(hipGetLastError());
@@ -1524,6 +1541,104 @@ int mpm_stress_totals(mpm_ctx* ctx, int model, double out[8]) {
 	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
 	if(model < -1 || model >= (int) ctx->models.size() || !out) return fail(ctx, MPM_ERR_INVALID, "mpm_stress_totals: bad model or NULL output array");
 	return readout_totals(ctx, model, kReadStressTotals, kStressSums + 1, out);
+}
+
+// Persistent particle identities (mpm_particle_ids.hpp; an extension, the reference has none) ------------------------------------------
+int mpm_track_particle_ids(mpm_ctx* ctx, int on) {
+	if(!ctx) return MPM_ERR_INVALID;
+	if(ctx->ready) return fail(ctx, MPM_ERR_INVALID, "mpm_track_particle_ids: tracking is chosen before mpm_initial_setup");
+	ctx->track_ids = on != 0;
+	return MPM_OK;
+}
+// what both the readout and the blob's writer ask first
+static int ids_usable(mpm_ctx* ctx, const char* who) {
+	if(!ctx->track_ids) return fail(ctx, MPM_ERR_INVALID, std::string(who) + ": the context does not track particle ids (mpm_track_particle_ids before mpm_initial_setup)");
+	if(!ctx->ids_valid) return fail(ctx, MPM_ERR_INVALID, std::string(who) + ": the ids are not valid: a checkpoint was loaded, load its ids with mpm_particle_ids_load");
+	return MPM_OK;
+}
+int mpm_retrieve_ids(mpm_ctx* ctx, int model, float* xyz, int32_t* ids, size_t* n) {
+	if(!ctx || !ctx->ready || model < 0 || model >= (int) ctx->models.size() || !n || !xyz) return MPM_ERR_INVALID;
+	if(!ids) return fail(ctx, MPM_ERR_INVALID, "mpm_retrieve_ids: NULL ids");
+	if(int rc = ids_usable(ctx, "mpm_retrieve_ids")) return rc;
+	static_assert(sizeof(int32_t) == sizeof(float), "the id column is staged like a float column");
+	float* const host[3] = {xyz, reinterpret_cast<float*>(ids), nullptr};
+	return readout_particles(ctx, model, kReadIds, host, n);
+}
+
+namespace {
+// The companion of a checkpoint: this header, then per model bincount_src * 64 int32 - one per slot of the source bins, in the slot order
+// of the checkpoint's bins section.
+struct IdsHeader {
+	uint64_t magic;// "MPMPIDS1"
+	int32_t nmodels, reserved;
+	struct {
+		int64_t n, bincount_src;
+	} models[8];
+};
+constexpr uint64_t kIdsMagic = 0x31534449504d504dull;
+static IdsHeader ids_header(const mpm_ctx* ctx) {
+	IdsHeader h {};
+	h.magic	  = kIdsMagic;
+	h.nmodels = (int32_t) ctx->models.size();
+	for(int m = 0; m < h.nmodels; ++m) h.models[m].n = (int64_t) ctx->models[m].n, h.models[m].bincount_src = ctx->models[m].bincount_src;
+	return h;
+}
+static size_t ids_bytes(const IdsHeader& h) {
+	size_t b = sizeof(IdsHeader);
+	for(int m = 0; m < h.nmodels; ++m) b += sizeof(int32_t) * (size_t) h.models[m].bincount_src * kBin;
+	return b;
+}
+}// namespace
+
+int mpm_particle_ids_size(mpm_ctx* ctx, size_t* bytes) {
+	if(!ctx || !ctx->ready || !bytes) return MPM_ERR_NOT_READY;
+	if(!ctx->track_ids) return fail(ctx, MPM_ERR_INVALID, "mpm_particle_ids_size: the context does not track particle ids");
+	*bytes = ids_bytes(ids_header(ctx));
+	return MPM_OK;
+}
+int mpm_particle_ids_save(mpm_ctx* ctx, void* buf, size_t capacity, size_t* written) {
+	if(!ctx || !ctx->ready || !buf) return MPM_ERR_NOT_READY;
+	if(int rc = ids_usable(ctx, "mpm_particle_ids_save")) return rc;
+	const IdsHeader h = ids_header(ctx);
+	const size_t need = ids_bytes(h);
+	if(capacity < need) return fail(ctx, MPM_ERR_CAPACITY, "particle id buffer too small: " + std::to_string(need) + " bytes needed");
+	HIP_TRY(hipSetDevice(ctx->device));
+	HIP_TRY(hipDeviceSynchronize());
+	char* out = (char*) buf;
+	memcpy(out, &h, sizeof(h));
+	size_t o = sizeof(h);
+	for(const Model& M: ctx->models) {
+		const size_t b = sizeof(int32_t) * (size_t) M.bincount_src * kBin;
+		if(b) HIP_TRY(hipMemcpy(out + o, M.ids[ctx->rollid], b, hipMemcpyDeviceToHost));
+		o += b;
+	}
+	if(written) *written = need;
+	return MPM_OK;
+}
+int mpm_particle_ids_load(mpm_ctx* ctx, const void* buf, size_t bytes) {
+	if(!ctx || !ctx->ready || !buf) return MPM_ERR_NOT_READY;
+	if(!ctx->track_ids) return fail(ctx, MPM_ERR_INVALID, "mpm_particle_ids_load: the context does not track particle ids");
+	if(bytes < sizeof(IdsHeader)) return fail(ctx, MPM_ERR_INVALID, "particle ids: truncated header");
+	IdsHeader h;
+	memcpy(&h, buf, sizeof(h));
+	const IdsHeader mine = ids_header(ctx);
+	if(h.magic != kIdsMagic) return fail(ctx, MPM_ERR_INVALID, "particle ids: bad magic");
+	if(h.nmodels != mine.nmodels) return fail(ctx, MPM_ERR_INVALID, "particle ids: model count differs from the context");
+	for(int m = 0; m < h.nmodels; ++m)
+		if(h.models[m].n != mine.models[m].n || h.models[m].bincount_src != mine.models[m].bincount_src)
+			return fail(ctx, MPM_ERR_INVALID, "particle ids: model " + std::to_string(m) + " differs from the context's current state (particle count or source bins)");
+	if(bytes < ids_bytes(mine)) return fail(ctx, MPM_ERR_INVALID, "particle ids: truncated");
+	HIP_TRY(hipSetDevice(ctx->device));
+	HIP_TRY(hipDeviceSynchronize());
+	const char* in = (const char*) buf;
+	size_t o	   = sizeof(h);
+	for(Model& M: ctx->models) {
+		const size_t b = sizeof(int32_t) * (size_t) M.bincount_src * kBin;
+		if(b) HIP_TRY(hipMemcpy(M.ids[ctx->rollid], in + o, b, hipMemcpyHostToDevice));
+		o += b;
+	}
+	ctx->ids_valid = true;
+	return MPM_OK;
 }
 
 int mpm_retrieve_positions(mpm_ctx* ctx, int model, float* xyz, size_t* n) {

@@ -307,6 +307,8 @@ int mpm_checkpoint_load(mpm_ctx* ctx, const void* buf, size_t bytes) {
 		const size_t nb = std::max<size_t>((size_t) h.models[m].bincount_src, (size_t) h.models[m].bincount);
 		if(nb > M.bin_cap) {
 			for(int i = 0; i < 2; ++i) HIP_TRY(regrow(&M.bins[i], M.bin_cap * M.nch * kBin, nb * M.nch * kBin, s));
+			if(ctx->track_ids)
+				for(int i = 0; i < 2; ++i) HIP_TRY(regrow(&M.ids[i], M.bin_cap * kBin, nb * kBin, s));
 			M.bin_cap = nb;
 		}
 	}
@@ -393,5 +395,6 @@ int mpm_checkpoint_load(mpm_ctx* ctx, const void* buf, size_t bytes) {
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipStreamSynchronize(s));
 	ctx->halo_tagged = false;
+	ctx->ids_valid	 = false;// ids are not part of the buffer: mpm_particle_ids_load brings them back
 	return MPM_OK;
 }

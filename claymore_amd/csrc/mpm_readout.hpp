@@ -11,6 +11,8 @@
 //                  kernels): the model's stress function on the stored state with a zero velocity gradient (readout_stress below,
 //                  INTEGRATION.md section 5) - from the record and row alone, like kReadState; it writes no bin
 //   kReadStressTotals  {count, sum V0 tau (6), max von Mises} of the same evaluation, reduced instead of written
+//   kReadIds       x and the particle's identity (an extension, tracked contexts only: mpm_particle_ids.hpp): kReadState's walk, the id read
+//                  from the side array at the record's source slot
 // One workgroup (256 lanes) per particle block.  The gathers stage the 2x2x2 grid blocks the block's stencils reach once in LDS as
 // velocities (8 KiB; a block that is not registered, or beyond an upper face, stages zero) and read each particle's 27 nodes from there at
 // G2P's cube-local stencil base ((base - 1) & 3) + 1, which also gives particles of cells -2 / -1 the reference's wrapped key.  Output
@@ -25,7 +27,7 @@ constexpr int kReadoutThreads = 256;
 constexpr int kMomentumSums	  = 5;
 constexpr int kStressSums	  = 7;// count and the six sums; the maximum is an eighth word of its own
 
-enum ReadoutKind { kReadState, kReadVelocity, kReadMomentum, kReadStress, kReadStressTotals };
+enum ReadoutKind { kReadState, kReadVelocity, kReadMomentum, kReadStress, kReadStressTotals, kReadIds };
 
 // What every readout reads of a model: the block numberings, the list and the bins (make_readout_args, claymore_hip.hip).
 struct ReadoutArgs {
@@ -40,6 +42,7 @@ struct ReadoutArgs {
 	const int* list;	  // advection records, cfg.ppb per row
 	const int* binoff;	  // first bin of a block, previous numbering
 	const float* bins;
+	const int* ids;		  // kReadIds: one id per bin slot, addressed like the bins (null in an untracked context)
 };
 
 // Where a readout puts its result.  kReadState / kReadVelocity / kReadStress: slot o of col[c] holds kReadoutWidth[K][c] floats of one
@@ -56,8 +59,9 @@ struct ReadoutOut {
 	double* sums;
 	int material;
 	MaterialConst mc;
+	int* ids = nullptr;// kReadIds: slot o takes the particle's id
 };
-constexpr int kReadoutWidth[4][3] = {{3, 9, 1}, {3, 3, 9}, {0, 0, 0}, {3, 6, 3}};
+constexpr int kReadoutWidth[6][3] = {{3, 9, 1}, {3, 3, 9}, {0, 0, 0}, {3, 6, 3}, {0, 0, 0}, {3, 1, 0}};// (kReadIds: column 1 is the int32 id, ReadoutOut::ids)
 
 // The pieces the readouts share - the list walk's liveness test, the record fetch, the cube staging and the 27-node gather - so that the
 // list layouts, the record format and the stencil, tie and face rules live in one place.
@@ -66,8 +70,9 @@ __device__ __forceinline__ bool readout_live(int n, int pidib, int dense) {
 	return dense ? pidib < n : (pidib & 63) < slice_records_at(n, pidib & ~63);
 }
 // Position (cell units) of the particle in record `rec` of block (kx, ky, kz), from the source bin the record's neighbour direction names.
-// Returns the particle's record (x, y, z, then J or five entries of b) and sets *row to its row (b21, log Jp; mpm_g2p2g.hpp).
-__device__ __forceinline__ const float* readout_position(const ReadoutArgs& a, int rec, int kx, int ky, int kz, float p[3], const float** row) {
+// Returns the particle's record (x, y, z, then J or five entries of b) and sets *row to its row (b21, log Jp; mpm_g2p2g.hpp); *slot (if
+// asked for): the particle's slot in the source bins, 64 per bin.
+__device__ __forceinline__ const float* readout_position(const ReadoutArgs& a, int rec, int kx, int ky, int kz, float p[3], const float** row, size_t* slot = nullptr) {
 	int ox, oy, oz;
 	dir_components((rec >> (a.cfg.pid_bits + kKeyBits)) & 31, ox, oy, oz);
 	const int sp	 = rec & (a.cfg.ppb - 1);
@@ -76,6 +81,7 @@ __device__ __forceinline__ const float* readout_position(const ReadoutArgs& a, i
 	const float* bin = a.bins + (size_t) (a.binoff[srcno] + (sp >> 6)) * (kBin * a.nch);
 	const float* src = bin + (sp & 63) * recf;
 	*row			 = bin + kBin * recf + (sp & 63) * (a.nch - recf);
+	if(slot) *slot = (size_t) (a.binoff[srcno] + (sp >> 6)) * kBin + (sp & 63);
 	p[0] = src[0], p[1] = src[1], p[2] = src[2];
 	return src;
 }
@@ -221,7 +227,8 @@ __global__ __launch_bounds__(kReadoutThreads) void readout_kernel(ReadoutArgs a,
 		if(!kSlots && !live) continue;// (no slots: the lanes of a wave need not agree)
 		float p[3]		 = {0.f, 0.f, 0.f};
 		const float *src = nullptr, *row = nullptr;
-		if(live) src = readout_position(a, list[pidib], kx, ky, kz, p, &row);
+		size_t sslot	 = 0;
+		if(live) src = readout_position(a, list[pidib], kx, ky, kz, p, &row, K == kReadIds ? &sslot : nullptr);
 		if constexpr(K == kReadMomentum) {
 			float v[3];
 			readout_gather<false>(s_v, p, v, nullptr);
@@ -268,6 +275,8 @@ __global__ __launch_bounds__(kReadoutThreads) void readout_kernel(ReadoutArgs a,
 					}
 				}
 				if(logjp) logjp[o] = a.nch - rec_floats(a.nch) == 2 ? row[1] : 0.f;
+			} else if constexpr(K == kReadIds) {
+				out.ids[o] = a.ids[sslot];
 			} else if constexpr(K == kReadStress) {
 				float *stress6 = out.col[1], *scalars3 = out.col[2];
 				float tau[6], sigma[6], scal[3], J;

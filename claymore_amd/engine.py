@@ -25,14 +25,39 @@ def stress_totals_dict(out):
     return {"count": int(out[0]), "stress_integral": np.array(out[1:7], dtype=np.float64), "max_von_mises": float(out[7])}
 
 
+def _position_keys(xyz):
+    """The position bits of every row as one sortable record."""
+    x = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+    return x.view(np.uint32).view([("x", np.uint32), ("y", np.uint32), ("z", np.uint32)]).ravel()
+
+
+def join_by_position(id_xyz, ids, xyz, *arrays):
+    """Rows (xyz, *arrays) of a readout joined to (id_xyz, ids) of retrieve_ids on the position bits; returns (ids, xyz, *arrays) in
+    ascending id order.  Both sides must hold the same multiset of positions.  Bit-identical positions are handed out in id order."""
+    ka, kb = _position_keys(id_xyz), _position_keys(xyz)
+    if ka.shape != kb.shape:
+        raise ValueError(f"order_by_id: {kb.shape[0]} rows against {ka.shape[0]} ids")
+    ids = np.asarray(ids)
+    oa = np.lexsort((ids, ka["z"], ka["y"], ka["x"]))  # by position, ties by id
+    ob = np.lexsort((kb["z"], kb["y"], kb["x"]))       # by position, stable: ties as they stand
+    if not np.array_equal(ka[oa], kb[ob]):
+        raise ValueError("order_by_id: the readout's positions are not those of retrieve_ids (taken at another substep boundary?)")
+    rank = np.argsort(ids[oa], kind="stable")
+    rows = ob[rank]
+    return (ids[oa][rank],) + tuple(np.asarray(a)[rows] for a in (xyz,) + arrays)
+
+
 class Engine:
     """One simulation context on one device.
 
     api: a bound _ffi.Api.  The product always uses the HIP library (`Engine(cfg)`); tests may hand in
     the oracle's Api to drive the checker through the same call sequence.
+
+    track_ids=True (HIP library only): every particle carries a persistent id - its index in the array its model was added with
+    (retrieve_ids, order_by_id).  Off by default: an untracked engine allocates and launches nothing for it.
     """
 
-    def __init__(self, cfg=None, device=0, api=None, domain_bits=None, **overrides):
+    def __init__(self, cfg=None, device=0, api=None, domain_bits=None, track_ids=False, **overrides):
         self.api = api if api is not None else _ffi.load_hip()
         if cfg is None:
             cfg = _ffi.Config()
@@ -45,6 +70,9 @@ class Engine:
         if rc != 0:
             raise EngineError(rc, "mpm_create failed (no usable HIP device? there is no CPU fallback)")
         self.dx = 1.0 / (1 << cfg.domain_bits)
+        self.track_ids = bool(track_ids)
+        if self.track_ids:
+            self._check(self.api.track_particle_ids(self.ctx, 1))
         self.models = []
         self.cur_time = 0.0
         self.dt = None
@@ -199,6 +227,37 @@ class Engine:
         out = (C.c_double * 8)()
         self._check(self.api.stress_totals(self.ctx, -1 if model is None else int(model), out))
         return stress_totals_dict(out)
+
+    def retrieve_ids(self, model=0):
+        """(xyz, ids) of every bucketed particle of `model` in one order (mpm_retrieve_ids; a track_ids=True engine only).  ids: int32, the
+        particle's index in the positions init_model was given; xyz has the bits every other readout returns for that particle."""
+        n = C.c_size_t(self.models[model]["n"])
+        xyz = np.empty((n.value, 3), dtype=np.float32)
+        ids = np.empty((n.value,), dtype=np.int32)
+        self._check(self.api.retrieve_ids(self.ctx, model, xyz.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return xyz[: n.value], ids[: n.value]
+
+    def order_by_id(self, model, xyz, *arrays):
+        """Join a readout of `model` - its positions `xyz` and any arrays in the same row order (retrieve_state, retrieve_velocity,
+        retrieve_stress, taken at the same substep boundary as this call) - to the ids on the position bits: returns (ids, xyz, *arrays)
+        with the rows in ascending id order.  Particles of one model whose positions are bit-identical cannot be told apart by the join:
+        among them the rows are handed out in ascending id order, as they stand in the readout."""
+        return join_by_position(*self.retrieve_ids(model), xyz, *arrays)
+
+    def save_particle_ids(self):
+        """The companion of save_checkpoint as a numpy byte array: one int32 per slot of every model's source bins behind a small
+        header (mpm_particle_ids_save).  The checkpoint buffer itself carries no ids."""
+        n = C.c_size_t(0)
+        self._check(self.api.particle_ids_size(self.ctx, C.byref(n)))
+        buf = np.empty(n.value, dtype=np.uint8)
+        w = C.c_size_t(0)
+        self._check(self.api.particle_ids_save(self.ctx, buf.ctypes.data, buf.size, C.byref(w)))
+        return buf[: w.value]
+
+    def load_particle_ids(self, buf):
+        """After load_checkpoint on a tracked engine: bring back the ids saved with that checkpoint (until then retrieve_ids refuses)."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        self._check(self.api.particle_ids_load(self.ctx, buf.ctypes.data, buf.size))
 
     def counts(self):
         c = _ffi.Counts()
@@ -362,7 +421,7 @@ class Engine:
 
 
 def build_engine(scene, device=0, api=None):
-    """Create an Engine for a scene dict (claymore_amd.scenes) and add its models (no setup yet)."""
+    """Create an Engine for a scene dict (claymore_amd.scenes) and add its models (no setup yet).  scene["track_ids"]: Engine's track_ids."""
     cfg = _ffi.Config()
     a = api if api is not None else _ffi.load_hip()
     rc = a.default_config(scene["bits"], C.byref(cfg))
@@ -370,7 +429,7 @@ def build_engine(scene, device=0, api=None):
         raise EngineError(rc, "default_config")
     for k, v in scene.get("config", {}).items():
         setattr(cfg, k, v)
-    eng = Engine(cfg=cfg, device=device, api=a)
+    eng = Engine(cfg=cfg, device=device, api=a, track_ids=bool(scene.get("track_ids", False)))
     for m in scene["models"]:
         eng.init_model(m["material"], m["xyz"], m.get("v0", (0, 0, 0)), **m.get("params", {}))
     if scene.get("collision"):

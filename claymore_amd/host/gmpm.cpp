@@ -14,7 +14,9 @@
 // point attributes "stress" (6 floats: the Cauchy stress {xx, yy, zz, xy, xz, yz}), "J", "pressure" and "vonmises" (1 float each) of
 // mpm_retrieve_stress (frame 0: the stress-free initial state, J = 1).  With both keys the two readouts come back in different particle
 // orders: each is sorted on the bits of its positions (which are the same bits in both) and the stress rows are written in the order of the
-// velocity readout.  A top-level "colliders" array installs analytic collision shapes (parse_collider below).
+// velocity readout.  simulation.output_ids (default false): the context tracks particle ids (mpm_track_particle_ids) and every frame also carries
+// the INT point attribute "id" - the particle's index among the model's sampled points - with the frame's points written in ascending id
+// order, so the point order is the same in every frame; the other attributes are joined to the ids on the position bits.  A top-level "colliders" array installs analytic collision shapes (parse_collider below).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -219,6 +221,44 @@ std::vector<size_t> order_by_position_bits(const float* xyz, size_t n) {
 	});
 	return order;
 }
+
+// The rows of a readout (xyz, n) in ascending id order: row src[j] of the readout is the particle with the j-th smallest id, which ids_sorted[j]
+// then holds.  (ixyz, ids, ni): mpm_retrieve_ids of the same state - the same position bits.  Bit-identical positions are handed out in id order.
+bool rows_by_id(const float* xyz, size_t n, const float* ixyz, const int32_t* ids, size_t ni, std::vector<size_t>& src, std::vector<int32_t>& ids_sorted) {
+	if(n != ni) return false;
+	auto less_bits = [](const float* a, const float* b) {
+		uint32_t ka[3], kb[3];
+		std::memcpy(ka, a, sizeof(ka));
+		std::memcpy(kb, b, sizeof(kb));
+		return ka[0] != kb[0] ? ka[0] < kb[0] : ka[1] != kb[1] ? ka[1] < kb[1] : ka[2] < kb[2];
+	};
+	std::vector<size_t> oa(n), ob(n);
+	for(size_t i = 0; i < n; ++i) oa[i] = ob[i] = i;
+	std::sort(oa.begin(), oa.end(), [&](size_t a, size_t b) {
+		if(less_bits(ixyz + 3 * a, ixyz + 3 * b)) return true;
+		if(less_bits(ixyz + 3 * b, ixyz + 3 * a)) return false;
+		return ids[a] < ids[b];
+	});
+	std::stable_sort(ob.begin(), ob.end(), [&](size_t a, size_t b) { return less_bits(xyz + 3 * a, xyz + 3 * b); });
+	std::vector<std::pair<int32_t, size_t>> pairs(n);
+	for(size_t k = 0; k < n; ++k) {
+		if(std::memcmp(ixyz + 3 * oa[k], xyz + 3 * ob[k], 3 * sizeof(float)) != 0) return false;
+		pairs[k] = {ids[oa[k]], ob[k]};
+	}
+	std::sort(pairs.begin(), pairs.end());
+	src.resize(n);
+	ids_sorted.resize(n);
+	for(size_t k = 0; k < n; ++k) ids_sorted[k] = pairs[k].first, src[k] = pairs[k].second;
+	return true;
+}
+template<typename T>
+void take_rows(std::vector<T>& a, int width, const std::vector<size_t>& src) {
+	if(a.empty()) return;
+	std::vector<T> out(src.size() * (size_t) width);
+	for(size_t k = 0; k < src.size(); ++k)
+		for(int d = 0; d < width; ++d) out[(size_t) width * k + d] = a[(size_t) width * src[k] + d];
+	a.swap(out);
+}
 }// namespace
 
 int main(int argc, char** argv) {
@@ -252,6 +292,7 @@ int main(int argc, char** argv) {
 	const std::string out_dir = sim.has("output_dir") ? sim["output_dir"].string() : ".";
 	const bool out_vel		  = sim.has("output_velocity") && sim["output_velocity"].type == mj::Value::Bool && sim["output_velocity"].b;
 	const bool out_stress	  = sim.has("output_stress") && sim["output_stress"].type == mj::Value::Bool && sim["output_stress"].b;
+	const bool out_ids		  = sim.has("output_ids") && sim["output_ids"].type == mj::Value::Bool && sim["output_ids"].b;
 	std::printf("simulation: gpuid[%d], defaultDt[%g], fps[%d], frames[%d]\n", gpuid, dt_def, fps, frames);
 
 	mpm_config cfg;
@@ -261,6 +302,7 @@ int main(int argc, char** argv) {
 	mpm_ctx* ctx = nullptr;
 	int rc		 = mpm_create(&cfg, gpuid, &ctx);
 	if(rc) die(nullptr, rc);
+	if(out_ids && (rc = mpm_track_particle_ids(ctx, 1))) die(ctx, rc);
 
 	const mj::Value& models = (*doc)["models"];
 	std::printf("has %zu models\n", models.arr.size());
@@ -303,13 +345,15 @@ int main(int argc, char** argv) {
 		if(rc) die(ctx, rc);
 		std::printf("init %d-th model with %zu particles\n", id, pts.size());
 		const std::string frame0 = out_dir + "/model_id[" + std::to_string(id) + "]_frame[0].bgeo";
-		if(out_vel || out_stress) {
+		if(out_vel || out_stress || out_ids) {
 			std::vector<float> v(out_vel ? 3 * pts.size() : 0), s9(out_stress ? 9 * pts.size() : 0, 0.f);
+			std::vector<int32_t> id0(out_ids ? pts.size() : 0);// (the sampled points are the input array: id = index)
+			for(size_t i = 0; i < id0.size(); ++i) id0[i] = (int32_t) i;
 			for(size_t i = 0; i < pts.size(); ++i) {
 				for(int d = 0; d < 3 && out_vel; ++d) v[3 * i + d] = v0[d];
 				if(out_stress) s9[9 * i + 6] = 1.f;// J
 			}
-			pio::write_bgeo_frame(frame0, pts.empty() ? nullptr : pts[0].data(), pts.size(), out_vel ? v.data() : nullptr, out_stress ? s9.data() : nullptr);
+			pio::write_bgeo_frame(frame0, pts.empty() ? nullptr : pts[0].data(), pts.size(), out_vel ? v.data() : nullptr, out_stress ? s9.data() : nullptr, out_ids && !id0.empty() ? id0.data() : nullptr);
 		} else
 			pio::write_bgeo(frame0, pts.empty() ? nullptr : pts[0].data(), pts.size());
 		counts.push_back(pts.size());
@@ -377,7 +421,7 @@ int main(int argc, char** argv) {
 			if(out_vel) {
 				vbuf.resize(3 * counts[mi]);
 				rc = mpm_retrieve_velocity(ctx, (int) mi, buf.data(), vbuf.data(), nullptr, &n);
-			} else if(!out_stress)
+			} else if(!out_stress && !out_ids)
 				rc = mpm_retrieve_positions(ctx, (int) mi, buf.data(), &n);
 			if(rc) die(ctx, rc);
 			if(out_stress) {
@@ -409,11 +453,33 @@ int main(int argc, char** argv) {
 					for(int d = 0; d < 3; ++d) sbuf[9 * to[k] + 6 + d] = sc[3 * k + d];
 				}
 			}
+			std::vector<int32_t> ibuf;
+			if(out_ids) {// the frame's rows in ascending id order
+				std::vector<float> ix(3 * counts[mi]);
+				std::vector<int32_t> ids(counts[mi]);
+				size_t ni = counts[mi];
+				rc		  = mpm_retrieve_ids(ctx, (int) mi, ix.data(), ids.data(), &ni);
+				if(rc) die(ctx, rc);
+				if(!out_vel && !out_stress) {
+					buf = ix;
+					n	= ni;
+				}
+				std::vector<size_t> src;
+				if(!rows_by_id(buf.data(), n, ix.data(), ids.data(), ni, src, ibuf)) {
+					std::fprintf(stderr, "gmpm: the id readout of model %zu does not hold the positions of the frame\n", mi);
+					die(ctx, MPM_ERR_INTERNAL);
+				}
+				buf.resize(3 * n);
+				take_rows(buf, 3, src);
+				if(!vbuf.empty()) vbuf.resize(3 * n);
+				take_rows(vbuf, 3, src);
+				take_rows(sbuf, 9, src);
+			}
 			std::printf("total number of particles %zu\n", n);
 			// IO::insert_job (gmpm_simulator.cuh:626-632): the frame is written by the IO thread while the next frame is computed
 			const std::string fn = out_dir + "/model_id[" + std::to_string(mi) + "]_frame[" + std::to_string(frame) + "].bgeo";
-			if(out_vel || out_stress)
-				io.write_bgeo_frame_async(fn, buf, vbuf, sbuf, n);
+			if(out_vel || out_stress || out_ids)
+				io.write_bgeo_frame_async(fn, buf, vbuf, sbuf, n, ibuf);
 			else
 				io.write_bgeo_async(fn, buf, n);
 		}

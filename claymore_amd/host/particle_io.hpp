@@ -9,7 +9,8 @@
 // its bytes, 16-bit size 3, 32-bit Houdini type 5 (vector), 3 zero defaults - and per point x y z w vx vy vz.
 // Further point attributes (gmpm's simulation.output_stress: "stress" of 6 floats, "J", "pressure", "vonmises" of 1) follow the same rule,
 // in the order they were added: a FLOAT attribute has Houdini type 0 and as many zero defaults as its size, and every point carries the
-// attributes' values behind w in that order.
+// attributes' values behind w in that order.  An INT attribute (gmpm's simulation.output_ids: "id" of 1 int) is partio's INT (BGEO.cpp:360-373,
+// :396-400): Houdini type 1, the same 16-bit size and zero defaults, its values big-endian int32 where a FLOAT's float32 stand.
 #pragma once
 #include <condition_variable>
 #include <deque>
@@ -20,6 +21,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <fstream>
 #include <stdexcept>
 #include <string>
@@ -41,11 +43,13 @@ inline void put_bef(std::vector<unsigned char>& o, float f) {
 	put_be32(o, u);
 }
 // A point attribute behind "position": `size` floats a point at data[size * i]; vector: partio's VECTOR (Houdini type 5), else FLOAT (0).
+// idata set (data then null): partio's INT (Houdini type 1), `size` int32 a point at idata[size * i].
 struct BgeoAttr {
 	std::string name;
 	int size;
 	bool vector;
 	const float* data;
+	const int32_t* idata = nullptr;
 };
 inline bool write_bgeo(const std::string& filename, const float* xyz, size_t n, const std::vector<BgeoAttr>& attrs) {
 	std::vector<unsigned char> o;
@@ -65,7 +69,7 @@ inline bool write_bgeo(const std::string& filename, const float* xyz, size_t n, 
 		o.insert(o.end(), a.name.begin(), a.name.end());
 		o.push_back((unsigned char) (a.size >> 8));// 16-bit size
 		o.push_back((unsigned char) a.size);
-		put_be32(o, a.vector ? 5 : 0);
+		put_be32(o, a.idata ? 1 : a.vector ? 5 : 0);
 		for(int k = 0; k < a.size; ++k) put_be32(o, 0);// defaults
 	}
 	for(size_t i = 0; i < n; ++i) {
@@ -74,7 +78,12 @@ inline bool write_bgeo(const std::string& filename, const float* xyz, size_t n, 
 		put_bef(o, xyz[3 * i + 2]);
 		put_bef(o, 1.0f);
 		for(const BgeoAttr& a: attrs)
-			for(int d = 0; d < a.size; ++d) put_bef(o, a.data[(size_t) a.size * i + d]);
+			for(int d = 0; d < a.size; ++d) {
+				if(a.idata)
+					put_be32(o, (uint32_t) a.idata[(size_t) a.size * i + d]);
+				else
+					put_bef(o, a.data[(size_t) a.size * i + d]);
+			}
 	}
 	o.push_back(0x00);// "beginExtra" / "endExtra" markers partio appends (BGEO.cpp:424-427)
 	o.push_back(0xff);
@@ -90,8 +99,8 @@ inline bool write_bgeo(const std::string& filename, const float* xyz, size_t n, 
 }
 // The point attributes of gmpm's frames: "v" from vel (may be null), then "stress", "J", "pressure", "vonmises" from stress6 and scalars3
 // of mpm_retrieve_stress, here as one array of 9 floats a point {stress6, J, pressure, vonmises} (may be null).  The scalar attributes are
-// strided views, so they are copied out first.
-inline bool write_bgeo_frame(const std::string& filename, const float* xyz, size_t n, const float* vel, const float* stress9) {
+// strided views, so they are copied out first.  Last, "id" from ids (may be null): one INT a point.
+inline bool write_bgeo_frame(const std::string& filename, const float* xyz, size_t n, const float* vel, const float* stress9, const int32_t* ids = nullptr) {
 	std::vector<BgeoAttr> attrs;
 	std::vector<float> s6, sc[3];
 	if(vel) attrs.push_back({"v", 3, true, vel});
@@ -107,6 +116,7 @@ inline bool write_bgeo_frame(const std::string& filename, const float* xyz, size
 		attrs.push_back({"pressure", 1, false, sc[1].data()});
 		attrs.push_back({"vonmises", 1, false, sc[2].data()});
 	}
+	if(ids) attrs.push_back({"id", 1, false, nullptr, ids});
 	return write_bgeo(filename, xyz, n, attrs);
 }
 
@@ -213,9 +223,9 @@ public:
 	void write_bgeo_async(std::string fn, std::vector<float> xyz, std::vector<float> vel, size_t n) {// with the "v" point attribute
 		insert_job([fn = std::move(fn), xyz = std::move(xyz), vel = std::move(vel), n] { write_bgeo(fn, xyz.data(), n, vel.data()); });
 	}
-	void write_bgeo_frame_async(std::string fn, std::vector<float> xyz, std::vector<float> vel, std::vector<float> stress9, size_t n) {// empty: attribute absent
-		insert_job([fn = std::move(fn), xyz = std::move(xyz), vel = std::move(vel), stress9 = std::move(stress9), n] {
-			write_bgeo_frame(fn, xyz.data(), n, vel.empty() ? nullptr : vel.data(), stress9.empty() ? nullptr : stress9.data());
+	void write_bgeo_frame_async(std::string fn, std::vector<float> xyz, std::vector<float> vel, std::vector<float> stress9, size_t n, std::vector<int32_t> ids = {}) {// empty: attribute absent
+		insert_job([fn = std::move(fn), xyz = std::move(xyz), vel = std::move(vel), stress9 = std::move(stress9), n, ids = std::move(ids)] {
+			write_bgeo_frame(fn, xyz.data(), n, vel.empty() ? nullptr : vel.data(), stress9.empty() ? nullptr : stress9.data(), ids.empty() ? nullptr : ids.data());
 		});
 	}
 	void flush() {// IO::flush: wait until every queued job has been written

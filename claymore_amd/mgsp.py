@@ -445,6 +445,11 @@ class MgspGroupRank:
         does not refuse: the stress comes from the particle records alone).  Per rank, not collective."""
         return self.eng.retrieve_stress(model)
 
+    def retrieve_ids(self, model=0):
+        """This rank's particles of `model` as Engine.retrieve_ids (a scene with "track_ids": True).  The ids are rank-local: they index
+        the positions THIS rank's share of the model was added with (partition_scene(scene, rank, world)).  Per rank, not collective."""
+        return self.eng.retrieve_ids(model)
+
     def stress_totals(self, model=None):
         """Engine.stress_totals over THIS rank's particles (per rank, not collective: sum the ranks' integrals, take the largest maximum)."""
         return self.eng.stress_totals(model)

@@ -226,6 +226,31 @@ int mpm_checkpoint_size(mpm_ctx* ctx, size_t* bytes);
 int mpm_checkpoint_save(mpm_ctx* ctx, void* buf, size_t capacity, size_t* written);
 int mpm_checkpoint_load(mpm_ctx* ctx, const void* buf, size_t bytes);
 
+/* Extension (the reference has no particle identity): a persistent 32-bit id per particle.  Every per-particle output of this engine comes
+ * back in an unspecified order that changes from call to call; a tracked context can say which input particle a row is.
+ *   id   the particle's index in the xyz array its model was given to mpm_add_model: 0 .. n-1 per model (for a group's ranks: each rank's
+ *        ids index that rank's own arrays).  An id lives as long as its particle: lost, dropped and overflow-dropped particles take theirs
+ *        with them, and the ids present are always distinct.
+ * mpm_track_particle_ids switches tracking on (on != 0) or off; callable between mpm_create and mpm_initial_setup, MPM_ERR_INVALID after
+ * set-up.  The default is off, and an untracked context allocates, launches and computes nothing more than before.  A tracked one carries
+ * 2 x 4 B per bin slot and moves the ids with a small kernel beside every G2P2G launch.
+ * mpm_retrieve_ids returns the positions and the id of every bucketed particle of a model in one shared order (unspecified).  xyz is
+ * bit-identical to what mpm_retrieve_state returns for the same particle, so every other readout can be joined to the ids on the position
+ * bits.  *n: in = capacity in particles, out = particles written.  Preconditions and errors: those of mpm_retrieve_state, and
+ * MPM_ERR_INVALID for a NULL ids, for a context that does not track, and for ids that are not valid (below).
+ * Ids, like colliders, are not part of the checkpoint buffer; their companion blob is: a header {uint64 magic "MPMPIDS1", int32 model count,
+ * int32 0, then for each of 8 models int64 n, int64 bincount_src}, then per model one int32 per slot of the source bins (64 per bin,
+ * bincount_src bins), in the slot order of the checkpoint's bins section.  Slots that hold no live particle carry an unspecified value on
+ * save and are ignored on load.  mpm_checkpoint_load on a tracked context marks the ids invalid; mpm_retrieve_ids and
+ * mpm_particle_ids_save then refuse until mpm_particle_ids_load succeeds.  The load validates the header against the context's current
+ * state - the model count and every model's n and bincount_src - and refuses with MPM_ERR_INVALID otherwise: load the checkpoint first,
+ * then the ids saved with it.  HIP library only. */
+int mpm_track_particle_ids(mpm_ctx* ctx, int on);
+int mpm_retrieve_ids(mpm_ctx* ctx, int model, float* xyz, int32_t* ids, size_t* n);
+int mpm_particle_ids_size(mpm_ctx* ctx, size_t* bytes);
+int mpm_particle_ids_save(mpm_ctx* ctx, void* buf, size_t capacity, size_t* written);
+int mpm_particle_ids_load(mpm_ctx* ctx, const void* buf, size_t bytes);
+
 /* Level-set collision object of the MGSP grid update (Projects/MGSP/boundary_condition.cuh:25-250, the second
  * update_grid_velocity_query_max overload Projects/MGSP/mgmpm_kernels.cuh:323-399, set up by
  * MgspBenchmark::init_boundary mgsp_benchmark.cuh:257-266).  Field values of SignedDistanceGrid. */

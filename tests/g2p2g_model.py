@@ -268,6 +268,16 @@ def pack_nodes(nodes):
     return (n[..., 0] << 40) | (n[..., 1] << 20) | n[..., 2]
 
 
+def gather_grid(pos_cells, keys, blocks):
+    """vn of step() from a dumped grid (keys (n, 3), blocks (n, 4, 64), channels 1 .. 3 = the node velocities): every stencil node of every
+    particle must lie in a dumped block."""
+    index = {tuple(k): i for i, k in enumerate(np.asarray(keys).astype(np.int64).tolist())}
+    nodes = stencil_base(pos_cells)[:, None, :] + OFFS[None, :, :]
+    blk = np.array([index[tuple(k)] for k in (nodes // 4).reshape(-1, 3).tolist()], np.int64).reshape(nodes.shape[:2])
+    cell = (nodes[..., 0] & 3) * 16 + (nodes[..., 1] & 3) * 4 + (nodes[..., 2] & 3)
+    return np.stack([np.asarray(blocks)[blk, c, cell] for c in (1, 2, 3)], axis=-1)
+
+
 def unpack_nodes(k):
     k = np.asarray(k, np.int64)
     return np.stack([k >> 40, (k >> 20) & 0xFFFFF, k & 0xFFFFF], axis=-1)
@@ -296,6 +306,32 @@ def assemble(outs, stencil_bounds):
     np.add.at(out["abs"], inv, np.abs(vals))
     np.add.at(out["E"], inv, errs)
     return out
+
+
+def add_contribution(exp, keys, vals):
+    """assemble()'s result with one more exact addend per node: vals (k, 4) at the packed nodes keys (k,), each at most once.  It counts as a
+    contribution with E = 0: sum += r, abs += |r|, n += 1; a node nobody else contributes to becomes an expected node."""
+    keys, vals = np.asarray(keys, np.int64), np.asarray(vals, np.float64).reshape(-1, 4)
+    assert np.unique(keys).size == keys.size
+    uk = np.union1d(exp["key"], keys)
+    out = {"key": uk, "sum": np.zeros((uk.size, 4)), "abs": np.zeros((uk.size, 4)), "E": np.zeros((uk.size, 4)), "n": np.zeros(uk.size, np.int64)}
+    ie, ik = np.searchsorted(uk, exp["key"]), np.searchsorted(uk, keys)
+    for f in ("sum", "abs", "E", "n"):
+        out[f][ie] = exp[f]
+    out["sum"][ik] += vals
+    out["abs"][ik] += np.abs(vals)
+    out["n"][ik] += 1
+    return out
+
+
+def restrict(exp, keep):
+    """assemble()'s result on the nodes selected by the bool mask `keep` over exp["key"]."""
+    return {f: v[keep] for f, v in exp.items()}
+
+
+def in_blocks(node_keys, block_keys3):
+    """Mask over packed node keys: the node lies in one of the grid blocks `block_keys3` (n, 3)."""
+    return np.isin(pack_nodes(unpack_nodes(node_keys) // 4), pack_nodes(np.asarray(block_keys3).reshape(-1, 3)))
 
 
 def grid_nodes(keys, blocks):
@@ -413,8 +449,21 @@ def scene_torn(seed=5):
     return np.concatenate([scene_isolated(seed), block_particles(SITES[50], 129, rng, planted=8)])
 
 
-SCENE_SEED = {"isolated": 11, "block_sizes": 12, "one_cell": 13, "cluster": 14, "torn": 15}
+SLAB = [(5 + x, 6 + y, 6 + z) for x in range(4) for y in (0, 1) for z in (0, 1)]
+
+
+def scene_slab(seed=6, lo=185, hi=215):
+    """A 4 x 2 x 2 slab of adjacent particle blocks, drawn like the cluster: long enough along x to be cut in two with a halo and an interior layer
+    of blocks on either side (tests/test_g2p2g_split_gpu.py)."""
+    rng = np.random.default_rng(seed)
+    return np.concatenate([block_particles(k, int(rng.integers(lo, hi + 1)), rng) for k in SLAB])
+
+
+SCENE_SEED = {"isolated": 11, "block_sizes": 12, "one_cell": 13, "cluster": 14, "torn": 15, "slab": 16}
 SCENES = {"isolated": scene_isolated, "block_sizes": scene_block_sizes, "one_cell": scene_one_cell, "cluster": scene_cluster, "torn": scene_torn}
+# Scenes that scene_state() serves but that stay out of the yardstick: test_g2p2g_model_cpu.measure_generated iterates SCENES and check_constants
+# pins Y to what it measures there.  A scene here is licensed by a CPU test of its own, which holds the reference side to bound() on it.
+EXTRA_SCENES = {"slab": scene_slab}
 BANDS = ((0.97, 1.03), (0.9, 1.1), (0.75, 1.3))
 BAND_SHARE = (0.5, 0.25, 0.25)                 # half of the draws from the innermost band: NACC's case 0 (inside the yield surface) lives there
 # A float32 SVD that has converged reproduces F to a few ulp: the median residual max |U S V^T - F| of the reference's 4-sweep SVD (svd.cuh:167)
@@ -563,7 +612,7 @@ def scene_state(name, material):
     ill_posed on any tier get the state of a further draw, until none is left: no scene holds a row on the brink of a branch, or one whose
     trial F the reference cannot decompose."""
     if (name, material) not in _SCENE_STATES:
-        pos = SCENES[name]()
+        pos = (SCENES[name] if name in SCENES else EXTRA_SCENES[name])()
         st = make_state(material, pos.shape[0], SCENE_SEED[name])
         for draw in range(1, 12):
             bad = ill_posed(material, pos, st)

@@ -110,9 +110,9 @@ class Bench:
                     state=[self.read(i) for i in range(len(self.parts))])
 
 
-def check(bench, res, models, tier, tag=""):
-    """The step's result against the model outputs `models` (one step() dict per model of the bench).  Prints every figure before it asserts."""
-    fails = []
+def check_particles(bench, res, models, tier, tag, fails):
+    """The per-particle half of check(): counts, state and position of every particle of every model against `models`, and the books (particle
+    blocks, lost, discarded).  Appends to `fails`; returns the per-model stencil bounds the grid comparison needs."""
     blocks = set()
     n_disc = 0
     sbs = []
@@ -151,9 +151,13 @@ def check(bench, res, models, tier, tag=""):
         fails.append(("particle_blocks", int(res["counts"].particle_blocks), len(blocks)))
     if res["lost"] != 0 or res["discarded"] != n_disc:
         fails.append(("books", res["lost"], res["discarded"], n_disc))
-    # the grid
-    exp = gm.assemble(models, sbs)
-    gk, gv = gm.grid_nodes(*res["grid"])
+    return sbs
+
+
+def check_grid(exp, grid, tier, tag, fails):
+    """The grid half of check(): the dumped grid against the assembled expectation `exp` (g2p2g_model.assemble) node by node over the union of
+    expected and returned nodes, and the total mass.  Appends to `fails`."""
+    gk, gv = gm.grid_nodes(*grid)
     ratio, bad, what = gm.compare_grid(exp, gk, gv)
     print(f"{tag} {tier} grid: {exp['key'].size} expected nodes, {gk.size} returned, up to {int(exp['n'].max())} contributions per node, worst |diff| / bound {ratio:.3g} at {what}")
     if bad:
@@ -161,6 +165,18 @@ def check(bench, res, models, tier, tag=""):
     mass_bound = float(((exp["n"] + 1) * 2.0 ** -23 * exp["abs"][:, 0]).sum())          # the summation term alone: a particle's 27 weights add up to its mass whatever its position
     if not abs(gv[:, 0].sum() - exp["sum"][:, 0].sum()) <= mass_bound:
         fails.append(("total mass", float(gv[:, 0].sum()), float(exp["sum"][:, 0].sum()), mass_bound))
+
+
+def check(bench, res, models, tier, tag="", grid_extra=None):
+    """The step's result against the model outputs `models` (one step() dict per model of the bench).  Prints every figure before it asserts.
+    grid_extra: (packed node keys, (k, 4) values) that something other than the models' particles has added to the grid, once per node
+    (g2p2g_model.add_contribution); default: nothing."""
+    fails = []
+    sbs = check_particles(bench, res, models, tier, tag, fails)
+    exp = gm.assemble(models, sbs)
+    if grid_extra is not None:
+        exp = gm.add_contribution(exp, *grid_extra)
+    check_grid(exp, res["grid"], tier, tag, fails)
     assert not fails, (tag, tier, fails)
 
 

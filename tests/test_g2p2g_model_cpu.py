@@ -198,6 +198,48 @@ def test_the_generator_covers_what_it_claims(generated):
     assert np.array_equal(gm.grid_of(k + 1, "flow")[0].reshape(3, 4, 4, 4), gm.cube_of(k[0], "flow")[:, 4:, 4:, 4:])
 
 
+@pytest.mark.parametrize("material", gm.MATERIALS)
+def test_the_slab_scene_keeps_the_reference_inside_the_gpu_bounds(material):
+    """The slab of tests/test_g2p2g_split_gpu.py is not one of the yardstick's scenes (g2p2g_model.EXTRA_SCENES: Y stays what the others measure).
+    What licenses it: on rest, flow and fast the oracle agrees with the model in every integer output with no row left out, the final positions
+    are at least 1e-3 cell apart, and the oracle's own deviation from the model stays within the bound the GPU test applies, g2p2g_model.bound().
+    The scene is long enough to be cut: particles change block on flow and fast, some across the plane between the x-keys 6 and 7."""
+    assert "slab" not in gm.SCENES and "slab" in gm.EXTRA_SCENES
+    pos, st = gm.scene_state("slab", material)
+    keys, counts = np.unique(gm.block_keys(pos), axis=0, return_counts=True)
+    assert sorted(map(tuple, keys.tolist())) == sorted(gm.SLAB) and counts.min() >= 185 and counts.max() <= 215
+    for tier in ("rest", "flow", "fast"):
+        m = gm.model_scene(material, pos, st, tier)
+        of, oi = gm.oracle_scene(material, pos, st, tier)
+        o = gm.oracle_view(material, of, oi)
+        assert m["finite"].all() and np.isfinite(of).all() and not m["unstable"].any() and not m["discarded"].any(), (tier, "a row would have to be left out")
+        keep = np.ones(pos.shape[0], bool)
+        ties = integers_agree(m, o, keep)
+        sep = gm.min_separation(m["pos"])
+        moved = int((m["dirtag"] != 13).sum())
+        cut = int(((gm.block_keys(pos)[:, 0] <= 6) != (gm.block_keys(m["pos"])[:, 0] <= 6)).sum())
+        print(f"slab {gm.NAMES[material]} {tier}: {pos.shape[0]} rows, ties {ties}, changed block {moved}, across the cut {cut}, min separation {sep:.3g}")
+        assert ties == 0 and sep >= 1e-3
+        if tier != "rest":
+            assert moved >= 0.03 * pos.shape[0] and cut >= 10
+        for q, v in deviations(material, m, o, keep).items():
+            bnd = gm.bound(q, tier, material)
+            print(f"    {q}: measured {v:.3g} = {v / gm.Y[q, tier, gm.NAMES[material]]:.2f} Y, bound {bnd:.3g} ({v / bnd:.2f} of it)")
+            assert v <= bnd, (tier, q, v, bnd)
+
+
+def test_the_grid_gather_reads_what_the_field_wrote():
+    """gather_grid() on blocks filled by grid_of() returns gather_field(): the velocities a model run is fed from a dumped grid."""
+    pos = gm.scene_cluster()
+    keys = np.unique(np.concatenate([gm.block_keys(pos) + np.array(d) for d in [(i, j, k) for i in (0, 1) for j in (0, 1) for k in (0, 1)]]), axis=0)
+    blocks = np.zeros((len(keys), 4, 64), np.float32)
+    blocks[:, 1:4] = gm.grid_of(keys, "flow", seed=3)
+    perm = np.random.default_rng(0).permutation(len(keys))
+    assert np.array_equal(gm.gather_grid(pos, keys[perm], blocks[perm]), gm.gather_field(pos, "flow", seed=3))
+    with pytest.raises(KeyError):
+        gm.gather_grid(pos, keys[1:], blocks[1:])
+
+
 def test_the_assembler_and_the_grid_comparison():
     """assemble() sums the kept particles' stencils per node; compare_grid() accepts that sum, rejects one node moved by more than its bound, a
     node nobody contributes to, and a missing node."""

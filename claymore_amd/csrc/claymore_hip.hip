@@ -89,6 +89,10 @@ struct mpm_ctx {
 	float fuse_dt_once	 = 0.f;// set by a driver that knows the next substep's dt (mpm_group_run_fixed): consumed by the next rebuild
 	// Between two host synchronisations of mpm_run_fixed the block counts below are ESTIMATES (the values of the last
 	// synchronisation): launches are sized by them with a margin, every kernel reads the true counts from the status block.
+	// The data was (re-)laid on the host - initial set-up, a checkpoint load, a capacity growth - since the last rebuild: that rebuild is not offered
+	// the still path (mpm_kernels.hpp), whatever G2P2G says.  Cleared by every rebuild.
+	bool relaid = true;
+	int allow_still = 0;// what the rebuild in flight was offered: launch_rebuild sets it for its own kernels and for launch_rebuild_prepare
 	bool rebuild_cleared = false;// the rebuild's part of substep_clear_kernel has been issued together with the P2G part
 	std::vector<hipEvent_t> ev_ring;// 3 events per substep of a window (substep start, G2P2G start / end; its end is the next one's start) + the window's closing event
 	Partition part[2];
@@ -522,8 +526,8 @@ int mpm_initial_setup(mpm_ctx* ctx) {
 	}
 	// (one-time set-up: the phase counters start from the activation's count; the published counts are formed on the host below)
 	HIP_TRY(hipMemcpyAsync(&ctx->d_status[ST_CNT_P], P.count, sizeof(int), hipMemcpyDeviceToDevice, s));
-	register_blocks_kernel<0, 1><<<std::max(1u, std::min(4096u, cdiv((size_t) pbc * 8, 256))), 256, 0, s>>>(g, &ctx->d_status[ST_CNT_P], nullptr, &ctx->d_status[ST_CNT_N], &ctx->d_status[ST_PBC], P.table, P.keys, ctx->d_status);
-	register_blocks_kernel<-1, 1><<<std::max(1u, std::min(8192u, cdiv((size_t) pbc * 32, 256))), 256, 0, s>>>(g, &ctx->d_status[ST_CNT_P], &ctx->d_status[ST_CNT_N], &ctx->d_status[ST_CNT_E], &ctx->d_status[ST_NBC], P.table, P.keys, ctx->d_status);
+	register_blocks_kernel<0, 1><<<std::max(1u, std::min(4096u, cdiv((size_t) pbc * 8, 256))), 256, 0, s>>>(g, &ctx->d_status[ST_CNT_P], nullptr, &ctx->d_status[ST_CNT_N], &ctx->d_status[ST_PBC], P.table, P.keys, ctx->d_status, 0);
+	register_blocks_kernel<-1, 1><<<std::max(1u, std::min(8192u, cdiv((size_t) pbc * 32, 256))), 256, 0, s>>>(g, &ctx->d_status[ST_CNT_P], &ctx->d_status[ST_CNT_N], &ctx->d_status[ST_CNT_E], &ctx->d_status[ST_NBC], P.table, P.keys, ctx->d_status, 0);
 	{
 		int rc0 = read_status(ctx);
 		if(rc0) return rc0;
@@ -613,6 +617,7 @@ int mpm_initial_setup(mpm_ctx* ctx) {
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipStreamSynchronize(s));
 	ctx->ready		   = true;
+	ctx->relaid		   = true;
 	ctx->grid_momentum = true;
 	ctx->ids_valid	   = ctx->track_ids;
 	return MPM_OK;
@@ -836,10 +841,11 @@ static int launch_prepare(mpm_ctx* ctx, int cur, int prev, bool list_is_out, int
 	}
 	const int nwg = std::max(1, std::min(ctx->g.cap, nblocks_est + nblocks_est / 16 + 64));
 	int* pub	  = publish ? ctx->d_status : nullptr;
+	const int still = publish && sort && list_is_out ? ctx->allow_still : 0;// (the rebuild's own call only)
 	if(sort)
-		prepare_blocks_kernel<true><<<nwg, 64, 0, ctx->s_compute>>>(ctx->g, pm, pbc_ptr, ctx->part[cur].table, ctx->part[cur].keys, ctx->part[prev].table, pub, ctx->part[cur].count);
+		prepare_blocks_kernel<true><<<nwg, 64, 0, ctx->s_compute>>>(ctx->g, pm, pbc_ptr, ctx->part[cur].table, ctx->part[cur].keys, ctx->part[prev].table, pub, ctx->part[cur].count, still);
 	else
-		prepare_blocks_kernel<false><<<nwg, 64, 0, ctx->s_compute>>>(ctx->g, pm, pbc_ptr, ctx->part[cur].table, ctx->part[cur].keys, ctx->part[prev].table, pub, ctx->part[cur].count);
+		prepare_blocks_kernel<false><<<nwg, 64, 0, ctx->s_compute>>>(ctx->g, pm, pbc_ptr, ctx->part[cur].table, ctx->part[cur].keys, ctx->part[prev].table, pub, ctx->part[cur].count, still);
 	return MPM_OK;
 }
 
@@ -854,7 +860,8 @@ static int launch_rebuild_prepare(mpm_ctx* ctx) {
 	const int ebc_est = std::min(ctx->g.cap, ctx->ebc + ctx->ebc / 16 + 1024);
 	return launch_prepare(ctx, n, r, true, n, &ctx->d_status[ST_CNT_P], ebc_est, true, true);
 }
-static int launch_rebuild(mpm_ctx* ctx, float fuse_dt = 0.f, bool without_prepare = false) {
+// allow_still: the kernels may take the still path (mpm_kernels.hpp) if G2P2G has moved nobody to another block - offered by mpm_run_fixed alone
+static int launch_rebuild(mpm_ctx* ctx, float fuse_dt = 0.f, bool without_prepare = false, bool allow_still = false) {
 	if(fuse_dt == 0.f) fuse_dt = ctx->fuse_dt_once;
 	ctx->fuse_dt_once = 0.f;
 	hipStream_t s = ctx->s_compute;
@@ -863,6 +870,9 @@ static int launch_rebuild(mpm_ctx* ctx, float fuse_dt = 0.f, bool without_prepar
 	Partition& Pn = ctx->part[n];
 	Partition& Pr = ctx->part[r];
 	const bool fused = fuse_dt > 0.f;
+	const int still	 = allow_still && !ctx->relaid ? 1 : 0;
+	ctx->allow_still = still;
+	ctx->relaid		 = false;
 	ctx->grid_momentum = !fused;// the carry-over below writes grid[0]: the P2G's mass and momentum, or (fused) the updated velocities
 	int rc			 = launch_clear(ctx, kClearRebuild | (fused ? kClearMaxVel : 0));// un-insert the old keys of Pn (reset_table, hash_table.cuh:110-112), counters, totals
 	if(rc) return rc;
@@ -874,13 +884,14 @@ static int launch_rebuild(mpm_ctx* ctx, float fuse_dt = 0.f, bool without_prepar
 		rm.size[mi]		 = m.size;
 		rm.row_of[mi]	 = m.row_of;
 		rm.binoff[mi]	 = m.binoff[r];// becomes the destination offsets after the roll
+		rm.binoff_cur[mi] = m.binoff[n];
 		rm.bin_cap[mi]	 = (long long) m.bin_cap;
 	}
 	int* st			  = ctx->d_status;
 	const int ebc_est = std::min(g.cap, ctx->ebc + ctx->ebc / 16 + 1024);
-	compact_blocks_kernel<<<std::max(1u, cdiv(ebc_est, 1024)), 1024, 0, s>>>(g, rm, Pr.keys, Pn.keys, Pn.table, st);
+	compact_blocks_kernel<<<std::max(1u, cdiv(ebc_est, 1024)), 1024, 0, s>>>(g, rm, Pr.keys, Pn.keys, Pn.table, st, still);
 	const unsigned rg8 = std::max(1u, std::min(4096u, cdiv((size_t) ebc_est * 8, 256))), rg32 = std::max(1u, std::min(8192u, cdiv((size_t) ebc_est * 32, 256)));
-	register_blocks_kernel<0, 1><<<rg8, 256, 0, s>>>(g, &st[ST_CNT_P], nullptr, &st[ST_CNT_N], &st[ST_PBC], Pn.table, Pn.keys, st);
+	register_blocks_kernel<0, 1><<<rg8, 256, 0, s>>>(g, &st[ST_CNT_P], nullptr, &st[ST_CNT_N], &st[ST_PBC], Pn.table, Pn.keys, st, still);
 	if(fused) {
 		if(ctx->hf_count)
 			carry_grid_terrain_kernel<<<2048, 256, 0, s>>>(g, st, Pn.keys, Pr.table, ctx->grid[1], ctx->grid[0], fuse_dt, ctx->d_maxvel, terrain_tick(ctx, fuse_dt));
@@ -894,7 +905,7 @@ static int launch_rebuild(mpm_ctx* ctx, float fuse_dt = 0.f, bool without_prepar
 		ctx->preupdate_dt	 = fuse_dt;
 	} else
 		carry_grid_kernel<false><<<2048, 256, 0, s>>>(g, st, Pn.keys, Pr.table, ctx->grid[1], ctx->grid[0], 0.f, nullptr, NoCollision {});
-	register_blocks_kernel<-1, 1><<<rg32, 256, 0, s>>>(g, &st[ST_CNT_P], &st[ST_CNT_N], &st[ST_CNT_E], &st[ST_NBC], Pn.table, Pn.keys, st);
+	register_blocks_kernel<-1, 1><<<rg32, 256, 0, s>>>(g, &st[ST_CNT_P], &st[ST_CNT_N], &st[ST_CNT_E], &st[ST_NBC], Pn.table, Pn.keys, st, still);
 	// the next G2P2G runs in the new numbering n with the particle data laid out in r: sort its lists (the ones the last
 	// G2P2G appended to), look up its blocks' neighbours; this last kernel also publishes the exterior block count
 	if(without_prepare) return MPM_OK;
@@ -938,6 +949,7 @@ static int grow_capacity(mpm_ctx* ctx) {
 		for(int p = 0; p < 32; ++p)
 			if(ctx->d_send_ids[p]) HIP_TRY(regrow(&ctx->d_send_ids[p], cap + 1, ncap + 1, s));
 		ctx->g.cap = (int) ncap;
+		ctx->relaid = true;
 		ctx->capacity_events++;
 	}
 	for(auto& m: ctx->models) {
@@ -950,6 +962,7 @@ static int grow_capacity(mpm_ctx* ctx) {
 			if(ctx->track_ids)
 				for(int i = 0; i < 2; ++i) HIP_TRY(regrow(&m.ids[i], m.bin_cap * kBin, nb * kBin, s));
 			m.bin_cap = nb;
+			ctx->relaid = true;
 			ctx->capacity_events++;
 		}
 	}
@@ -1083,6 +1096,7 @@ int mpm_run_fixed(mpm_ctx* ctx, int nsteps, float dt) {
 	hipStream_t s = ctx->s_compute;
 	const int K = ctx->cfg.sync_interval > 0 ? std::min(ctx->cfg.sync_interval, 64) : 8;// (clamped to 64: claymore_amd.h)
 	FlagGuard guard {ctx};
+	const bool still_on = ctx->cfg.still_rebuild != -1 && ctx->group_refs == 0;// (a grouped context's rebuilds belong to the group loop)
 	while((int) ctx->ev_ring.size() < 3 * K + 1) {
 		hipEvent_t e = nullptr;
 		HIP_TRY(hipEventCreate(&e));
@@ -1104,7 +1118,7 @@ int mpm_run_fixed(mpm_ctx* ctx, int nsteps, float dt) {
 		const bool fuse_next = it + 1 < nsteps;// the last substep leaves the canonical state behind
 		rc = launch_g2p2g(ctx, dt, dt, ev[1], ev[2], true, fuse_next);
 		if(rc) return rc;
-		rc = launch_rebuild(ctx, fuse_next ? dt : 0.f);
+		rc = launch_rebuild(ctx, fuse_next ? dt : 0.f, false, still_on);
 		if(rc) return rc;
 		HIP_TRY(hipEventRecord(ev[3], s));
 		roll_partition(ctx);
@@ -1407,8 +1421,9 @@ int mpm_get_diagnostics(mpm_ctx* ctx, mpm_diagnostics* d) {
 	d->discarded_p2g  = ctx->h_status[ST_ARENA];
 	d->overflow_flags = ctx->h_status[ST_OVERFLOW];
 	d->dropped_particles = ctx->h_status[ST_DROPPED];
+	d->still_rebuilds	 = ctx->h_status[ST_STILL];
 #ifdef MPM_G2P2G_STATS
-	for(int i = 0; i < 4; ++i) d->reserved[i] = ctx->h_status[24 + i];// cumulative: iterations, loser lanes, edge lanes, iterations with a retry
+	for(int i = 0; i < 3; ++i) d->reserved[i] = ctx->h_status[24 + i];// cumulative: iterations, loser lanes, edge lanes (the fourth, iterations with a retry: the bits of mpm_timers.reserved[0])
 #endif
 	return MPM_OK;
 }
@@ -1416,6 +1431,9 @@ int mpm_get_diagnostics(mpm_ctx* ctx, mpm_diagnostics* d) {
 int mpm_get_timers(mpm_ctx* ctx, mpm_timers* t) {
 	if(!ctx || !t) return MPM_ERR_INVALID;
 	*t = ctx->timers;
+#ifdef MPM_G2P2G_STATS
+	if(ctx->h_status) memcpy(&t->reserved[0], &ctx->h_status[27], sizeof(int));// cumulative iterations with a retry: the int's BITS (tools/g2p2g_stats_run.py)
+#endif
 	return MPM_OK;
 }
 

@@ -395,6 +395,7 @@ int mpm_checkpoint_load(mpm_ctx* ctx, const void* buf, size_t bytes) {
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipStreamSynchronize(s));
 	ctx->halo_tagged = false;
+	ctx->relaid		 = true;
 	ctx->ids_valid	 = false;// ids are not part of the buffer: mpm_particle_ids_load brings them back
 	return MPM_OK;
 }

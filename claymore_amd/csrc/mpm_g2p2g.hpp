@@ -754,6 +754,7 @@ __global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? kG2P2GWavesFluid : kG2P2G
 			if(stay_m != 0ull && lane == stay_leader) raw_stay = atomicAdd(&mv.out_count[b_opaque], __popcll(stay_m));
 			if(dno >= 0 && !stay) raw_move = atomicAdd(&mv.out_count[dno], 1);
 			if(active) {
+				if(!stay) status[ST_MOVED] = 1;// somebody changed block (or was lost): the rebuild that follows cannot take its still path
 				if(dno < 0) atomicAdd(&status[ST_LOST], 1);// reference: particle silently lost (particle_buffer.cuh:105-113)
 				if(!in_arena) atomicAdd(&status[ST_ARENA], 1);// (:877-885) contribution discarded
 			}

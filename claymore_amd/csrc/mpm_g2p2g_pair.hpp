@@ -369,6 +369,7 @@ __global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? kPairWavesFluid : kPairWa
 			for(int h = 0; h < 2; ++h) {
 				if(dno[h] >= 0 && !stay[h]) raw_move[h] = atomicAdd(&mv.out_count[dno[h]], 1);
 				if(active[h]) {
+					if(!stay[h]) status[ST_MOVED] = 1;// somebody changed block (or was lost): the rebuild that follows cannot take its still path
 					if(dno[h] < 0) atomicAdd(&status[ST_LOST], 1);// reference: particle silently lost (particle_buffer.cuh:105-113)
 					if(!in_arena[h]) atomicAdd(&status[ST_ARENA], 1);// (:877-885) contribution discarded
 				}

@@ -51,8 +51,20 @@ constexpr int kStay		  = 13; // dir_offset(0,0,0), utility_funcs.hpp:25-27
 // take three 4-byte device-to-device copies for that) - and each count is published by the first kernel that runs after its phase.
 enum {
 	ST_PBC = 0, ST_NBC = 1, ST_EBC = 2, ST_OVERFLOW = 3, ST_LOST = 4, ST_ARENA = 5, ST_DROPPED = 6, ST_NONFINITE = 7, ST_BINS0 = 8, ST_PART0 = 16,
-	/* 24..28: MPM_G2P2G_STATS */ ST_CNT_P = 29, ST_CNT_N = 30, ST_CNT_E = 31, ST_BINSPREV = 32, ST_PBCPREV = 40, ST_WORDS = 64
+	/* 24..28: MPM_G2P2G_STATS */ ST_CNT_P = 29, ST_CNT_N = 30, ST_CNT_E = 31, ST_BINSPREV = 32, ST_PBCPREV = 40, /* 41: MPM_G2P2G_STATS */
+	ST_MOVED = 42,// set by G2P2G when an active particle does not stay in its block (a lost one included), cleared with the P2G grid
+	ST_STILL = 43,// rebuilds that took the still path since set-up (mpm_diagnostics.still_rebuilds)
+	ST_STREAK = 44,// ... and how many of them in a row up to now: bumped by the still compaction, zeroed by the full one
+	ST_WORDS = 64
 };
+// The STILL PATH of the rebuild (compact / register / prepare; launch_rebuild offers it with allow_still, mpm_run_fixed on a single context only).
+// When no particle changed its block in the G2P2G just run, the particle blocks are those of the partition it ran in - and with them the neighbour
+// and exterior blocks, every block's size and bins and every look-up row.  The new partition is then the old one under the IDENTITY numbering:
+// keys and table entries are copied, the registration kernels return, and prepare derives its row from the one that stands.  Every kernel of the
+// chain takes the decision itself, from the same two words.
+__device__ __forceinline__ bool rebuild_is_still(int allow_still, const int* status) {
+	return allow_still && status[ST_MOVED] == 0;
+}
 
 struct GridCfg {
 	int G;		  // blocks per axis
@@ -586,8 +598,9 @@ struct PrepareModels {
 // mpm_run_fixed); the true count is read from device memory and a workgroup walks over blocks b, b + gridDim.x, ... (one trip
 // when the estimate holds).  publish (the status block, or null): the rebuild's exterior phase is over by now - workgroup 0
 // publishes the exterior block count (status[ST_EBC], *part_count).
+// (amdgpu_waves_per_eu(6): the sort runs at 79 vector registers, six waves per SIMD; the still path's few scalars would otherwise spill into an 81st and cost the sixth wave)
 template<bool SORT>
-__global__ __launch_bounds__(64) void prepare_blocks_kernel(GridCfg cfg, PrepareModels pm, const int* __restrict__ pbc_ptr, const int* __restrict__ cur_table, const int* __restrict__ cur_keys, const int* __restrict__ prev_table, int* __restrict__ publish, int* __restrict__ part_count) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6))) void prepare_blocks_kernel(GridCfg cfg, PrepareModels pm, const int* __restrict__ pbc_ptr, const int* __restrict__ cur_table, const int* __restrict__ cur_keys, const int* __restrict__ prev_table, int* __restrict__ publish, int* __restrict__ part_count, int allow_still) {
 	// records are sorted in chunks of 512 (8 per lane): every 64-slot slice of a chunk is one G2P2G iteration
 	constexpr int kPrepChunk = kListChunk;
 	__shared__ int s_sorted[kPairChunkMax];// (the pair layout's last chunk of a block may hold kPairChunkMax records)
@@ -602,8 +615,15 @@ __global__ __launch_bounds__(64) void prepare_blocks_kernel(GridCfg cfg, Prepare
 		*part_count		 = ebc;
 	}
 	const int pbc = min(*pbc_ptr, cfg.cap);
-	for(int b = blockIdx.x; b < pbc; b += gridDim.x) {
-	const int kx = cur_keys[3 * b], ky = cur_keys[3 * b + 1], kz = cur_keys[3 * b + 2];
+	// (allow_still comes with publish only: the rebuild's own call)
+	const bool still = rebuild_is_still(allow_still, publish);
+	// From the second still rebuild in a row on, the two bin-offset buffers hold the same numbers, so a block's row is already the one this kernel would write,
+	// and a settled block's pair counts are the ones it would copy: such a block needs nothing.  One LANE looks at a block then (its size against G2P2G's
+	// verdict, two coalesced loads per model), and the wave works off the few blocks of its 64 that are not settled.
+	const bool skip = still && publish[ST_STREAK] >= 2;
+	auto prepare_block = [&](const int b) {
+	int kx = 0, ky = 0, kz = 0;
+	if(!still) kx = cur_keys[3 * b], ky = cur_keys[3 * b + 1], kz = cur_keys[3 * b + 2];
 	// (a settled block's work is two chains of dependent loads - key -> table -> bin offset, and size / row -> keep -> handed-on pair counts -; the first model's
 	//  second chain is started HERE, beside the first one, instead of behind it: the kernel is latency-bound at rest)
 	int size0 = 0, row0 = 0, keep0 = -2, hand0 = 0;
@@ -617,7 +637,16 @@ __global__ __launch_bounds__(64) void prepare_blocks_kernel(GridCfg cfg, Prepare
 	}
 	// ---- look-ups (model independent except for the bin offsets)
 	int srcno = -1, other = -1;
-	if(lane < 27) {
+	if(still) {
+		// identity numbering: the destination and grid block numbers (lanes 27-61) stand, and the source block in direction d is the destination block
+		// in direction -d of the row that stands - dir(26 - j) = -dir(j), so lane l < 27 takes what lane 53 - l holds (-1 stays -1)
+		const int stand	 = pm.n > 0 ? pm.blockinfo[0][(size_t) b * kInfoRow + lane] : -1;// the row of the block's (unchanged) number: lanes 27-61 are model independent
+		const int mirror = __shfl(stand, (53 - lane) & 63);
+		if(lane < 27)
+			srcno = mirror;
+		else if(lane < 62)
+			other = stand;
+	} else if(lane < 27) {
 		int ox, oy, oz;
 		dir_components(lane, ox, oy, oz);
 		srcno = table_query(cfg, prev_table, kx + ox, ky + oy, kz + oz);
@@ -838,7 +867,21 @@ __global__ __launch_bounds__(64) void prepare_blocks_kernel(GridCfg cfg, Prepare
 		}
 		pm.blockinfo[m][(size_t) b * kInfoRow + lane] = info;
 	}
+	};
+	if(skip) {
+		for(long long base = (long long) blockIdx.x * 64; base < pbc; base += (long long) gridDim.x * 64) {
+			const int c = (int) base + lane;
+			bool done	= true;
+			if(c < pbc)
+				for(int m = 0; m < pm.n; ++m) {
+					const int size = pm.size[m][c], tail = size & (kPrepChunk - 1);// (row_of is the identity)
+					done = done && (size == 0 || (pm.keep[m][c] == size && (pm.pairinfo[m] || tail <= 64 || (tail & 63) == 0)));
+				}
+			for(unsigned long long todo = __ballot(!done); todo != 0ull; todo &= todo - 1ull) prepare_block((int) base + __ffsll((long long) todo) - 1);
+		}
+		return;
 	}
+	for(int b = blockIdx.x; b < pbc; b += gridDim.x) prepare_block(b);
 }
 
 }// namespace mpm
@@ -855,6 +898,7 @@ struct RebuildModels {
 	int* size[kMaxModels];
 	int* row_of[kMaxModels];
 	int* binoff[kMaxModels];// destination bin offsets for the NEXT step (new numbering)
+	const int* binoff_cur[kMaxModels];// ... and the ones G2P2G has just written by (old numbering): the still path hands them on; both buffers have the same capacity
 	long long bin_cap[kMaxModels];
 };
 
@@ -886,6 +930,7 @@ __global__ __launch_bounds__(256) void substep_clear_kernel(GridCfg cfg, ClearAr
 		const int nbc = min(a.status[ST_NBC], cfg.cap), ebc = min(a.status[ST_EBC], cfg.cap);
 		float4* g	  = reinterpret_cast<float4*>(a.p2g_grid);
 		for(int i = tid; i < nbc * 64; i += nthreads) g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+		if(tid == 0) a.status[ST_MOVED] = 0;
 		for(int m = 0; m < a.nmodels; ++m)
 			for(int i = tid; i <= ebc; i += nthreads) a.out_count[m][i] = 0, a.keep[m][i] = -1;
 	}
@@ -914,12 +959,28 @@ __global__ __launch_bounds__(256) void substep_clear_kernel(GridCfg cfg, ClearAr
 // particles get a new number (workgroup-aggregated atomic), their key goes into the new table, their bins are
 // allocated.  Order of the new numbering is arbitrary (as it is in the reference: insert order of atomics).
 // The old exterior block count is read from the status block; the launch is sized by a host-side estimate of it.
-__global__ __launch_bounds__(1024) void compact_blocks_kernel(GridCfg cfg, RebuildModels rm, const int* __restrict__ old_keys, int* __restrict__ new_keys, int* __restrict__ new_table, int* __restrict__ status) {
+__global__ __launch_bounds__(1024) void compact_blocks_kernel(GridCfg cfg, RebuildModels rm, const int* __restrict__ old_keys, int* __restrict__ new_keys, int* __restrict__ new_table, int* __restrict__ status, int allow_still) {
 	// The three counters of this kernel (new block numbers, bins, particle totals) share a cache line: same-line atomics
 	// serialise in L2 at ~11 ns each, so they are issued once per 1024-thread workgroup (3 x 95 at C3), not once per wave
 	// (3 x 1516 = 33 us, which was the kernel's whole run time).
 	__shared__ int s_part[kMaxModels];
 	const int ebc = min(status[ST_EBC], cfg.cap);
+	// still (uniform over the launch): every block keeps its number, its key and its bins; the phase counters are set from the published counts
+	// (nobody writes those before this kernel ends), the bin totals from the previous ones (substep_clear_kernel has moved them there)
+	const bool still = rebuild_is_still(allow_still, status);
+	const int pbc	 = min(status[ST_PBC], cfg.cap);
+	if(still && blockIdx.x == 0) {
+		if(threadIdx.x < kMaxModels) status[ST_BINS0 + threadIdx.x] = status[ST_BINSPREV + threadIdx.x];
+		if(threadIdx.x == 64) {
+			const int p = status[ST_PBC], n = status[ST_NBC];
+			status[ST_CNT_P] = p;
+			status[ST_CNT_N] = n - p;
+			status[ST_CNT_E] = status[ST_EBC] - n;
+			status[ST_STILL] += 1;
+			status[ST_STREAK] += 1;
+		}
+	} else if(blockIdx.x == 0 && threadIdx.x == 64)
+		status[ST_STREAK] = 0;
 	for(int b0 = blockIdx.x * blockDim.x; b0 < ebc; b0 += gridDim.x * blockDim.x) {// uniform trip count per workgroup (block_append has barriers)
 		const int b = b0 + threadIdx.x;
 		int c[kMaxModels];
@@ -945,6 +1006,22 @@ __global__ __launch_bounds__(1024) void compact_blocks_kernel(GridCfg cfg, Rebui
 		}
 		__syncthreads();
 		if((int) threadIdx.x < rm.n && s_part[threadIdx.x]) atomicAdd(&status[ST_PART0 + threadIdx.x], s_part[threadIdx.x]);
+		if(still) {
+			if(b < ebc) {
+				const int kx = old_keys[3 * b], ky = old_keys[3 * b + 1], kz = old_keys[3 * b + 2];
+				new_keys[3 * b]						  = kx;
+				new_keys[3 * b + 1]					  = ky;
+				new_keys[3 * b + 2]					  = kz;
+				new_table[key_index(cfg, kx, ky, kz)] = b;
+				if(b < pbc)
+					for(int m = 0; m < rm.n; ++m) {
+						rm.size[m][b]	= c[m];
+						rm.row_of[m][b] = b;
+						rm.binoff[m][b] = rm.binoff_cur[m][b];
+					}
+			}
+			continue;
+		}
 		const int nb = block_append(&status[ST_CNT_P], any ? 1 : 0);
 		int kx = 0, ky = 0, kz = 0;
 		if(any) {
@@ -974,13 +1051,14 @@ __global__ __launch_bounds__(1024) void compact_blocks_kernel(GridCfg cfg, Rebui
 // A newly registered block gets the number *pbc_ptr (+ *base2_ptr) + its rank in this phase's own counter; `publish` (may be
 // null) receives that base - the count the PREVIOUS phase ended with.
 template<int LO, int HI>
-__global__ __launch_bounds__(256) void register_blocks_kernel(GridCfg cfg, const int* __restrict__ pbc_ptr, const int* __restrict__ base2_ptr, int* counter, int* publish, int* table, int* keys, int* status) {
+__global__ __launch_bounds__(256) void register_blocks_kernel(GridCfg cfg, const int* __restrict__ pbc_ptr, const int* __restrict__ base2_ptr, int* counter, int* publish, int* table, int* keys, int* status, int allow_still) {
 	constexpr int W	   = HI - LO + 1;
 	constexpr int NOFF = W * W * W;
 	constexpr int LPB  = NOFF <= 8 ? 8 : 32;// lanes per block (27 padded to 32)
 	const int pbc	   = min(*pbc_ptr, cfg.cap);
 	const int base	   = *pbc_ptr + (base2_ptr ? *base2_ptr : 0);
 	if(publish && blockIdx.x == 0 && threadIdx.x == 0) *publish = base;
+	if(rebuild_is_still(allow_still, status)) return;// (the compaction has carried every block over)
 	const long long total = (long long) pbc * LPB;
 	const long long bound = (total + blockDim.x - 1) / blockDim.x * blockDim.x;// whole workgroups stay in the loop together (block_append has barriers)
 	for(long long t = (long long) blockIdx.x * blockDim.x + threadIdx.x; t < bound; t += (long long) gridDim.x * blockDim.x) {

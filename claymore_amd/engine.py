@@ -391,7 +391,8 @@ class Engine:
         return float(np.float32(p.volume) * np.float32(p.rho))
 
     def diagnostics(self):
-        """Particles / P2G contributions the reference would have lost silently (HIP library only)."""
+        """Particles / P2G contributions the reference would have lost silently, and `still_rebuilds`: the rebuilds of run_fixed that kept the
+        partition because no particle had changed its block (config `still_rebuild=-1` switches that off).  HIP library only."""
         d = _ffi.Diagnostics()
         self._check(self.api.get_diagnostics(self.ctx, C.byref(d)))
         return d

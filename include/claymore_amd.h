@@ -67,7 +67,9 @@ typedef struct mpm_config {
 	int sync_interval;	 /* mpm_run_fixed: substeps enqueued between two host synchronisations (the kernels read their block counts from
 							device memory; errors raised in between are reported at the next synchronisation).  0 = default (8), 1 = one
 							synchronisation per substep.  The reference synchronises six times per substep (gmpm_simulator.cuh:398-564) */
-	int reserved[3];
+	int still_rebuild;	 /* mpm_run_fixed on a single context: a substep in which no particle changed its block keeps the partition as it is
+							(same blocks under the same numbers) instead of rebuilding it.  0 = default = on, -1 = off.  HIP library only */
+	int reserved[2];
 } mpm_config;
 
 /* Material parameter block (Projects/GMPM/particle_buffer.cuh:141-264).  Unused fields are ignored. */
@@ -375,7 +377,8 @@ typedef struct mpm_diagnostics {
 	int64_t discarded_p2g;
 	int overflow_flags; /* bit 0: block capacity, bit 1: particles per block (MPM_ERR_CAPACITY, unless bit 1 with drop_overflow) */
 	int dropped_particles; /* cumulative; only with mpm_config.drop_overflow */
-	int reserved[4];
+	int reserved[3];
+	int still_rebuilds; /* rebuilds since initial_setup that kept the partition (mpm_config.still_rebuild), as of the last synchronisation */
 } mpm_diagnostics;
 int mpm_get_diagnostics(mpm_ctx* ctx, mpm_diagnostics* d);
 /* Sum over the current grid of {mass, momentum x, y, z} (the reference's sum_grid_mass debug kernel,

@@ -16,6 +16,7 @@
 #include "../../include/claymore_amd.h"
 #include "mpm_kernels.hpp"
 #include "mpm_readout.hpp"
+#include "mpm_grid_field.hpp"
 #include "mpm_particle_ids.hpp"
 
 using namespace mpm;
@@ -1701,6 +1702,100 @@ int mpm_dump_grid(mpm_ctx* ctx, int* keys, float* blocks, size_t* nblocks) {
 	if(keys) HIP_TRY(hipMemcpy(keys, ctx->part[ctx->rollid].keys, sizeof(int) * 3 * (size_t) ctx->nbc, hipMemcpyDeviceToHost));
 	if(blocks) HIP_TRY(hipMemcpy(blocks, ctx->grid[0], sizeof(float) * 256 * (size_t) ctx->nbc, hipMemcpyDeviceToHost));
 	*nblocks = ctx->nbc;
+	return MPM_OK;
+}
+
+// Eulerian readouts (mpm_grid_field.hpp; an extension, the reference has none): point samples, dense volumes and box totals of grid[0], the
+// mass and momentum of the last P2G.  Preconditions those of mpm_retrieve_velocity (readout_state).  Read-only; temporaries are scratch
+// released on every exit path, so a context that never calls these allocates and launches nothing for them.
+int mpm_sample_grid(mpm_ctx* ctx, const float* xyz, size_t n, float* out4) {
+	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
+	if(n && (!xyz || !out4)) return fail(ctx, MPM_ERR_INVALID, "mpm_sample_grid: NULL array");
+	if(n > ((size_t) 1 << 31)) return fail(ctx, MPM_ERR_INVALID, "mpm_sample_grid: more than 2^31 points in one call");
+	if(int rc = readout_state(ctx, "mpm_sample_grid")) return rc;
+	if(!n) return MPM_OK;
+	HIP_TRY(hipSetDevice(ctx->device));
+	hipStream_t s = ctx->s_compute;
+	DevScratch<float> d_xyz, d_out;
+	if(d_xyz.alloc(3 * n) != hipSuccess || d_out.alloc(4 * n) != hipSuccess) {
+		(void) hipGetLastError();
+		return fail(ctx, MPM_ERR_CAPACITY, "mpm_sample_grid: no device memory for " + std::to_string(n) + " points");
+	}
+	HIP_TRY(hipMemcpyAsync(d_xyz.p, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, s));
+	grid_sample_kernel<<<cdiv(n, kGridFieldThreads), kGridFieldThreads, 0, s>>>(ctx->g, ctx->nbc, ctx->part[ctx->rollid].table, ctx->grid[0], d_xyz.p, n, d_out.p);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(out4, d_out.p, sizeof(float) * 4 * n, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	return MPM_OK;
+}
+
+int mpm_grid_volume(mpm_ctx* ctx, const int origin[3], const int dims[3], int stride, float* out) {
+	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
+	if(!origin || !dims || !out) return fail(ctx, MPM_ERR_INVALID, "mpm_grid_volume: NULL argument");
+	if(stride != 1 && stride != 2 && stride != 4) return fail(ctx, MPM_ERR_INVALID, "mpm_grid_volume: stride " + std::to_string(stride) + " (1, 2 or 4)");
+	if(dims[0] < 1 || dims[1] < 1 || dims[2] < 1) return fail(ctx, MPM_ERR_INVALID, "mpm_grid_volume: every entry of dims must be at least 1");
+	size_t cells = (size_t) dims[0];
+	for(int d = 1; d < 3; ++d) {
+		if(cells > SIZE_MAX / (size_t) dims[d]) return fail(ctx, MPM_ERR_INVALID, "mpm_grid_volume: the box overflows size_t");
+		cells *= (size_t) dims[d];
+	}
+	if(cells > SIZE_MAX / 16) return fail(ctx, MPM_ERR_INVALID, "mpm_grid_volume: the box overflows size_t");
+	if(int rc = readout_state(ctx, "mpm_grid_volume")) return rc;
+	HIP_TRY(hipSetDevice(ctx->device));
+	hipStream_t s = ctx->s_compute;
+	DevScratch<float> d_out;
+	if(d_out.alloc(4 * cells) != hipSuccess) {
+		(void) hipGetLastError();// (the context stays usable)
+		return fail(ctx, MPM_ERR_CAPACITY, "mpm_grid_volume: no device memory for " + std::to_string(16 * cells) + " bytes");
+	}
+	VolumeArgs a {};
+	const int tile[3] = {kVolTileX / stride, kVolTileY / stride, kVolTileZ / stride};
+	unsigned long long ntiles = 1;
+	for(int d = 0; d < 3; ++d) {
+		a.origin[d] = origin[d];
+		a.dims[d]	= dims[d];
+		a.tiles[d]	= ((long long) dims[d] + tile[d] - 1) / tile[d];
+		ntiles *= (unsigned long long) a.tiles[d];// (<= cells)
+	}
+	const unsigned nwg = (unsigned) std::min<unsigned long long>(ntiles, 1u << 20);// the kernel strides over the tiles
+	const int* table   = ctx->part[ctx->rollid].table;
+	if(stride == 1)
+		grid_volume_kernel<1><<<nwg, kGridFieldThreads, 0, s>>>(ctx->g, ctx->nbc, table, ctx->grid[0], a, d_out.p);
+	else if(stride == 2)
+		grid_volume_kernel<2><<<nwg, kGridFieldThreads, 0, s>>>(ctx->g, ctx->nbc, table, ctx->grid[0], a, d_out.p);
+	else
+		grid_volume_kernel<4><<<nwg, kGridFieldThreads, 0, s>>>(ctx->g, ctx->nbc, table, ctx->grid[0], a, d_out.p);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(out, d_out.p, 16 * cells, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	return MPM_OK;
+}
+
+int mpm_grid_box_totals(mpm_ctx* ctx, const int lo[3], const int hi[3], double out[5]) {
+	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
+	if(!lo || !hi || !out) return fail(ctx, MPM_ERR_INVALID, "mpm_grid_box_totals: NULL argument");
+	if(int rc = readout_state(ctx, "mpm_grid_box_totals")) return rc;
+	BoxArgs box {};
+	bool empty = ctx->nbc == 0;
+	for(int d = 0; d < 3; ++d) {
+		box.lo[d] = std::max(lo[d], 0);
+		box.hi[d] = std::min(hi[d], 4 * ctx->g.G);
+		empty	  = empty || box.lo[d] >= box.hi[d];
+	}
+	for(int d = 0; d < kBoxSums; ++d) out[d] = 0.0;
+	if(empty) return MPM_OK;
+	HIP_TRY(hipSetDevice(ctx->device));
+	hipStream_t s = ctx->s_compute;
+	DevScratch<double> d_out;
+	if(d_out.alloc(kBoxSums) != hipSuccess) {
+		(void) hipGetLastError();
+		return fail(ctx, MPM_ERR_CAPACITY, "mpm_grid_box_totals: no device memory");
+	}
+	HIP_TRY(hipMemsetAsync(d_out.p, 0, sizeof(double) * kBoxSums, s));
+	grid_box_totals_kernel<<<std::min(256u, cdiv(ctx->nbc, kGridFieldThreads / 64)), kGridFieldThreads, 0, s>>>(ctx->nbc, ctx->part[ctx->rollid].keys, ctx->grid[0], box, d_out.p);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(out, d_out.p, sizeof(double) * kBoxSums, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
 	return MPM_OK;
 }
 

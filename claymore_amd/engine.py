@@ -415,6 +415,44 @@ class Engine:
         self._check(self.api.dump_grid(self.ctx, keys.ctypes.data_as(C.c_void_p), blocks.ctypes.data_as(C.c_void_p), C.byref(n)))
         return keys[: n.value], blocks[: n.value]
 
+    # ---- Eulerian readouts (mpm_sample_grid, mpm_grid_volume, mpm_grid_box_totals; HIP library only) ------------------------------
+    def sample_grid(self, xyz):
+        """The grid of the last P2G sampled at arbitrary world-space points with G2P's 27-node B-spline stencil (mpm_sample_grid):
+        {"mass": sum W m (n,) float32, "momentum": sum W p (n, 3) float32, "density": mass / dx^3 (n,) float64, "velocity": momentum / mass
+        where mass > 0, else 0 (n, 3) float64 - the mass-weighted velocity, not retrieve_velocity's sum W (p / m)}.  Points outside the
+        domain (or not finite) give zeros."""
+        pts = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros((pts.shape[0], 4), dtype=np.float32)
+        self._check(self.api.sample_grid(self.ctx, pts.ctypes.data_as(C.c_void_p), pts.shape[0], out.ctypes.data_as(C.c_void_p)))
+        mass, mom = out[:, 0].copy(), out[:, 1:4].copy()
+        m64 = mass.astype(np.float64)
+        vel = np.zeros(mom.shape, dtype=np.float64)
+        np.divide(mom.astype(np.float64), m64[:, None], out=vel, where=(m64 > 0)[:, None])
+        return {"mass": mass, "momentum": mom, "density": m64 / self.dx ** 3, "velocity": vel}
+
+    def grid_volume(self, origin=(0, 0, 0), shape=None, stride=1):
+        """A dense box of the grid of the last P2G (mpm_grid_volume): a (4, d0, d1, d2) float32 array {mass, px, py, pz}, cell (X, Y, Z) the
+        sum over the stride^3 nodes at origin + stride (X, Y, Z) (stride 1: the node's words, bit for bit).  shape=None: the whole domain
+        at that stride, from `origin` (0, 0, 0).  Nodes outside the domain or in no registered block read zero."""
+        stride = int(stride)
+        if shape is None:
+            if stride not in (1, 2, 4):
+                raise EngineError(_ffi.MPM_ERR_INVALID, f"grid_volume: stride {stride} (1, 2 or 4)")
+            shape = ((1 << self.cfg.domain_bits) // stride,) * 3
+        o = (C.c_int * 3)(*[int(v) for v in origin])
+        d = (C.c_int * 3)(*[int(v) for v in shape])
+        # (a dims entry < 1 is the library's to refuse, before it writes anything: it gets a one-word array)
+        out = np.empty((4,) + tuple(d) if min(d) >= 1 else (1,), dtype=np.float32)
+        self._check(self.api.grid_volume(self.ctx, o, d, stride, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def grid_box_totals(self, lo, hi):
+        """Totals over the nodes of the half-open node box [lo, hi), clipped to the domain (mpm_grid_box_totals), in float64: {"mass",
+        "momentum" (3,), "kinetic": sum over nodes with mass > 0 of |p|^2 / (2 m)}."""
+        out = (C.c_double * 5)()
+        self._check(self.api.grid_box_totals(self.ctx, (C.c_int * 3)(*[int(v) for v in lo]), (C.c_int * 3)(*[int(v) for v in hi]), out))
+        return {"mass": float(out[0]), "momentum": np.array(out[1:4], dtype=np.float64), "kinetic": float(out[4])}
+
     def last_g2p2g_ms(self):
         ms = C.c_float(0)
         self._check(self.api.last_g2p2g_ms(self.ctx, C.byref(ms)))

@@ -293,6 +293,16 @@ int main(int argc, char** argv) {
 	const bool out_vel		  = sim.has("output_velocity") && sim["output_velocity"].type == mj::Value::Bool && sim["output_velocity"].b;
 	const bool out_stress	  = sim.has("output_stress") && sim["output_stress"].type == mj::Value::Bool && sim["output_stress"].b;
 	const bool out_ids		  = sim.has("output_ids") && sim["output_ids"].type == mj::Value::Bool && sim["output_ids"].b;
+	int grid_stride			  = 0;// simulation.output_grid: 0 = no grid files
+	if(sim.has("output_grid")) {
+		const mj::Value& og = sim["output_grid"];
+		const float fs		= og.type == mj::Value::Object ? num(og, "stride", 1.f) : 0.f;
+		grid_stride			= (int) fs;
+		if((float) grid_stride != fs || (grid_stride != 1 && grid_stride != 2 && grid_stride != 4)) {
+			std::fprintf(stderr, "gmpm: simulation.output_grid must be {\"stride\": 1, 2 or 4}\n");
+			return 1;
+		}
+	}
 	std::printf("simulation: gpuid[%d], defaultDt[%g], fps[%d], frames[%d]\n", gpuid, dt_def, fps, frames);
 
 	mpm_config cfg;
@@ -413,6 +423,15 @@ int main(int argc, char** argv) {
 		mpm_timers tm;
 		mpm_get_timers(ctx, &tm);
 		std::printf("frame %d: t %.6f, %ld substeps, blocks %d/%d/%d, last substep: grid %.3f ms g2p2g %.3f ms partition %.3f ms\n", frame, cur_time, steps, c.particle_blocks, c.neighbor_blocks, c.exterior_blocks, tm.grid_update_ms, tm.g2p2g_ms, tm.partition_ms);
+		if(grid_stride) {// the Eulerian side of the frame: the whole domain at the asked stride
+			const int origin[3] = {0, 0, 0};
+			const int cells		= (1 << bits) / grid_stride;
+			const int dims[3]	= {cells, cells, cells};
+			std::vector<float> vol((size_t) 4 * cells * cells * cells);
+			rc = mpm_grid_volume(ctx, origin, dims, grid_stride, vol.data());
+			if(rc) die(ctx, rc);
+			io.write_npy_f32_async(out_dir + "/grid_frame[" + std::to_string(frame) + "].npy", std::move(vol), {4, (size_t) cells, (size_t) cells, (size_t) cells});
+		}
 		for(size_t mi = 0; mi < counts.size(); ++mi) {// output_model, :594-634
 			buf.resize(3 * counts[mi]);
 			vbuf.clear();

@@ -1,5 +1,6 @@
 // host_selftest.cpp — exercises the pieces of the host drivers that need no GPU (JSON reader, lattice sampler, BGEO
-// writer).  usage: host_selftest <out.bgeo>  -> prints "json_ok <n_models> <dt>", "sphere <count>", "bgeo <bytes>"
+// writer, NumPy writer).  usage: host_selftest <out.bgeo>  -> prints "json_ok <n_models> <dt>", "sphere <count>", "bgeo <bytes>"
+#include <cstdlib>
 #include <cstring>
 #include <iostream>
 
@@ -41,6 +42,18 @@ int main(int argc, char** argv) {
 		}
 		if(arr[0].size() * 3 != arr[1].size()) return 5;
 		return pio::write_bgeo_frame(argv[4], arr[0].data(), arr[0].size() / 3, nullptr, arr[1].data()) ? 0 : 4;
+	}
+	if(argc == 7 && !std::strcmp(argv[1], "--npy-from")) {// host_selftest --npy-from raw.f32 d0 d1 d2 out.npy: 4 d0 d1 d2 raw float32 values -> a grid volume's NumPy file, shape (4, d0, d1, d2)
+		std::ifstream in(argv[2], std::ios::binary | std::ios::ate);
+		if(!in) return 3;
+		const size_t bytes = (size_t) in.tellg();
+		std::vector<float> v(bytes / sizeof(float));
+		in.seekg(0);
+		in.read(reinterpret_cast<char*>(v.data()), (std::streamsize) bytes);
+		std::vector<size_t> shape {4};
+		for(int a = 3; a < 6; ++a) shape.push_back((size_t) std::strtoull(argv[a], nullptr, 10));
+		if(4 * shape[1] * shape[2] * shape[3] != v.size()) return 5;
+		return pio::write_npy_f32(argv[6], v.data(), shape) ? 0 : 4;
 	}
 	const char* text = R"({"simulation": {"gpuid": 0, "fps": 1200, "frames": 2, "default_dt": 5e-6},
 	  "models": [{"type": "particle", "file": "two_dragons.sdf", "constitutive": "jfluid", "offset": [0.1, 0.1, 0.1],

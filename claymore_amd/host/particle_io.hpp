@@ -11,6 +11,7 @@
 // in the order they were added: a FLOAT attribute has Houdini type 0 and as many zero defaults as its size, and every point carries the
 // attributes' values behind w in that order.  An INT attribute (gmpm's simulation.output_ids: "id" of 1 int) is partio's INT (BGEO.cpp:360-373,
 // :396-400): Houdini type 1, the same 16-bit size and zero defaults, its values big-endian int32 where a FLOAT's float32 stand.
+// write_npy_f32: a float32 array as a NumPy .npy file (gmpm's simulation.output_grid).
 #pragma once
 #include <condition_variable>
 #include <deque>
@@ -120,6 +121,36 @@ inline bool write_bgeo_frame(const std::string& filename, const float* xyz, size
 	return write_bgeo(filename, xyz, n, attrs);
 }
 
+// A float32 array as a NumPy file (gmpm's simulation.output_grid: the grid volume of mpm_grid_volume beside a frame's BGEO files): format 1.0 -
+// the magic "\x93NUMPY", the version bytes 1 0, a little-endian 16-bit header length, the header {'descr': '<f4', 'fortran_order': False,
+// 'shape': (d0, d1, ...), } padded with spaces to a newline so that the data starts at a multiple of 64 bytes - then the values in C order
+// (last index fastest), little-endian as the host holds them.
+inline bool write_npy_f32(const std::string& filename, const float* data, const std::vector<size_t>& shape) {
+	std::string dict = "{'descr': '<f4', 'fortran_order': False, 'shape': (";
+	size_t count	 = 1;
+	for(size_t i = 0; i < shape.size(); ++i) {
+		dict += std::to_string(shape[i]) + (i + 1 < shape.size() ? ", " : shape.size() == 1 ? "," : "");
+		count *= shape[i];
+	}
+	dict += "), }";
+	const size_t unpadded = 10 + dict.size() + 1;// magic 6, version 2, length 2, the dictionary, the newline
+	dict.append((64 - unpadded % 64) % 64, ' ');
+	dict += '\n';
+	if(dict.size() > 0xffff) return false;
+	std::ofstream f(filename, std::ios::binary);
+	if(!f) return false;
+	const unsigned char head[10] = {0x93, 'N', 'U', 'M', 'P', 'Y', 1, 0, (unsigned char) (dict.size() & 0xff), (unsigned char) (dict.size() >> 8)};
+	f.write((const char*) head, sizeof(head));
+	f.write(dict.data(), (std::streamsize) dict.size());
+	static_assert(sizeof(float) == 4, "");
+	const uint16_t probe = 1;
+	unsigned char first;
+	std::memcpy(&first, &probe, 1);
+	if(first != 1) return false;// (a big-endian host would have to swap: none of the targets is one)
+	if(count) f.write((const char*) data, (std::streamsize) (count * sizeof(float)));
+	return (bool) f;
+}
+
 // The reference's lattice rule (Library/MnBase/Geometry/GeometrySampler.h:11-37): 8 particles per grid node at +-0.25 dx.
 template<typename Inside>
 inline Points sample_lattice(float dx, const int lo[3], const int hi[3], Inside inside) {
@@ -227,6 +258,9 @@ public:
 		insert_job([fn = std::move(fn), xyz = std::move(xyz), vel = std::move(vel), stress9 = std::move(stress9), n, ids = std::move(ids)] {
 			write_bgeo_frame(fn, xyz.data(), n, vel.empty() ? nullptr : vel.data(), stress9.empty() ? nullptr : stress9.data(), ids.empty() ? nullptr : ids.data());
 		});
+	}
+	void write_npy_f32_async(std::string fn, std::vector<float> data, std::vector<size_t> shape) {
+		insert_job([fn = std::move(fn), data = std::move(data), shape = std::move(shape)] { write_npy_f32(fn, data.data(), shape); });
 	}
 	void flush() {// IO::flush: wait until every queued job has been written
 		std::unique_lock<std::mutex> lk(mut_);

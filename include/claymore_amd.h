@@ -390,6 +390,32 @@ int mpm_check_table(mpm_ctx* ctx);
 /* Dense dump of the current grid for parity tests: for every neighbor block, key (3 ints) and 256 floats
  * {mass[64], mvx[64], mvy[64], mvz[64]} (grid_buffer.cuh:12-14 layout). *nblocks in = capacity, out = count. */
 int mpm_dump_grid(mpm_ctx* ctx, int* keys, float* blocks, size_t* nblocks);
+/* Extension (the reference has no Eulerian output): what the grid holds between two substeps - the mass m_i and momentum p_i of the last
+ * P2G - read out by position instead of by particle.  N = 2^domain_bits nodes per axis; node (i, j, k) sits at
+ * (i, j, k) dx.  A node holds a value only if it lies in [0, N)^3 AND its block (i >> 2, j >> 2, k >> 2) is in the current partition's table
+ * AND that block's number is below neighbor_blocks (the numbering mpm_dump_grid reports): the exterior blocks, numbers neighbor_blocks ..
+ * exterior_blocks - 1, are known to the table but have no grid rows.  Every other node reads as +0.
+ * mpm_sample_grid: out4[4 q .. 4 q + 3] = sum_i W_i(x_q) {m_i, p_i x, y, z} for each of n world-space points xyz[3 q ..], over the 27-node
+ *   quadratic B-spline stencil formed exactly as G2P forms it: p_d = x_d * 2^domain_bits in one float32 multiply, base_d = lround(p_d) - 1
+ *   (ties away from zero), weights of p_d - base_d, W = w0[i] w1[j] w2[k] at node base + (i, j, k).  A point with any p_d not finite, < 0
+ *   or >= N gets four zeros.  n = 0 is legal and launches nothing.  The outputs are raw sums in mass and momentum units: / dx^3 gives
+ *   densities, and sum W p / sum W m the mass-weighted velocity - deliberately NOT the sum W (p_i / m_i) of mpm_retrieve_velocity, which
+ *   at a point without particles is biased toward zero by the empty nodes of the stencil.
+ * mpm_grid_volume: out as [4][dims[0]][dims[1]][dims[2]] float32 (channel-major: mass, px, py, pz; z fastest).  Output cell (X, Y, Z)
+ *   covers the stride^3 nodes origin + stride (X, Y, Z) + [0, stride)^3.  stride 1: the node's four words, copied bit for bit.  stride 2
+ *   or 4: acc = +0.0f, acc += value over the covered nodes in float32, x slowest and z fastest - a sum, so totals are conserved.  origin
+ *   may be negative and the box may leave the domain (those nodes read zero).  MPM_ERR_INVALID for a stride other than 1, 2, 4, a dims
+ *   entry < 1 or 16 dims[0] dims[1] dims[2] overflowing size_t; MPM_ERR_CAPACITY when the device cannot hold the box (the context stays usable).
+ * mpm_grid_box_totals: out = {sum m, sum px, sum py, sum pz, sum_{m > 0} |p|^2 / (2 m)} over the nodes of the half-open node box [lo, hi),
+ *   clipped to the domain; float64 sums of the float32 node values, in an unspecified order (the last bits may differ between calls).  An
+ *   empty box gives five zeros.  For [0, N)^3 the first four are mpm_grid_totals' up to summation order.
+ * Preconditions and errors: those of mpm_retrieve_velocity - MPM_ERR_NOT_READY before mpm_initial_setup; MPM_ERR_INVALID for a NULL array,
+ * for a grid that holds velocities (between mpm_grid_update and the next mpm_rebuild_partition) and, permanently, for a context that has
+ * ever joined an mpm_group or been through the halo tagging: there is no group form of these calls.  They read only: no state, checkpoint
+ * or later substep changes.  HIP library only. */
+int mpm_sample_grid(mpm_ctx* ctx, const float* xyz, size_t n, float* out4);
+int mpm_grid_volume(mpm_ctx* ctx, const int origin[3], const int dims[3], int stride, float* out);
+int mpm_grid_box_totals(mpm_ctx* ctx, const int lo[3], const int hi[3], double out[5]);
 /* How the library was built: "claymore_hip <abi> experiment=<none | list of -D switches>".  A product library reports
  * experiment=none (claymore_amd/csrc/mpm_device_math.hpp: the switches that change what the kernels compute only exist under
  * -DMPM_EXPERIMENT); tests/test_abi.py asserts it for the shipped library.  Needs no device. */

@@ -129,6 +129,7 @@ HIP_ONLY = {
     "sample_grid": (_i, [_vp, _vp, _sz, _vp]),
     "grid_volume": (_i, [_vp, _P(C.c_int), _P(C.c_int), _i, _vp]),
     "grid_box_totals": (_i, [_vp, _P(C.c_int), _P(C.c_int), _P(C.c_double)]),
+    "grid_isosurface": (_i, [_vp, _f, _P(C.c_int), _P(C.c_int), _vp, _vp, _P(_sz)]),
     "halo_dump": (_i, [_vp, _vp, _vp, _ip, _vp]),
     "set_collision_clock": (_i, [_vp, _i, _f]),
     "get_collision_time": (_i, [_vp, _fp, _ip]),

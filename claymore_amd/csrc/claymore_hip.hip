@@ -17,6 +17,7 @@
 #include "mpm_kernels.hpp"
 #include "mpm_readout.hpp"
 #include "mpm_grid_field.hpp"
+#include "mpm_grid_isosurface.hpp"
 #include "mpm_particle_ids.hpp"
 
 using namespace mpm;
@@ -1799,8 +1800,59 @@ int mpm_grid_box_totals(mpm_ctx* ctx, const int lo[3], const int hi[3], double o
 	return MPM_OK;
 }
 
+// The iso-surface f = iso_mass of the mass channel (mpm_grid_isosurface.hpp): mpm_grid_volume's preconditions, mpm_halo_keys' capacity
+// protocol.  The triangles are staged in device scratch sized by the caller's capacity and released on every exit path; the count runs in
+// d_counter.  A count-only call (tri_xyz NULL, or a capacity of 0) allocates nothing.
+int mpm_grid_isosurface(mpm_ctx* ctx, float iso_mass, const int lo[3], const int hi[3], float* tri_xyz, float* tri_vel, size_t* n) {
+	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
+	if(!n) return fail(ctx, MPM_ERR_INVALID, "mpm_grid_isosurface: NULL n");
+	if(!(iso_mass > 0.f) || !std::isfinite(iso_mass)) return fail(ctx, MPM_ERR_INVALID, "mpm_grid_isosurface: iso_mass must be finite and > 0");
+	if((lo == nullptr) != (hi == nullptr)) return fail(ctx, MPM_ERR_INVALID, "mpm_grid_isosurface: lo and hi are given together or not at all");
+	if(!tri_xyz && tri_vel) return fail(ctx, MPM_ERR_INVALID, "mpm_grid_isosurface: tri_vel without tri_xyz");
+	if(int rc = readout_state(ctx, "mpm_grid_isosurface")) return rc;
+	const size_t cap = tri_xyz ? *n : 0;
+	if(cap > SIZE_MAX / (36 * sizeof(float))) return fail(ctx, MPM_ERR_CAPACITY, "mpm_grid_isosurface: no device memory for " + std::to_string(cap) + " triangles");
+	if(!ctx->nbc) {
+		*n = 0;
+		return MPM_OK;
+	}
+	HIP_TRY(hipSetDevice(ctx->device));
+	hipStream_t s = ctx->s_compute;
+	DevScratch<float> d_xyz, d_vel;
+	if(cap && (d_xyz.alloc(9 * cap) != hipSuccess || (tri_vel && d_vel.alloc(9 * cap) != hipSuccess))) {
+		(void) hipGetLastError();// (the context stays usable; *n is left as it was)
+		return fail(ctx, MPM_ERR_CAPACITY, "mpm_grid_isosurface: no device memory for " + std::to_string(cap) + " triangles");
+	}
+	IsoArgs a {};
+	for(int d = 0; d < 3; ++d) {
+		a.lo[d] = lo ? lo[d] : -1;
+		a.hi[d] = hi ? hi[d] : 4 * ctx->g.G;
+	}
+	a.iso	   = iso_mass;
+	a.capacity = cap;
+	HIP_TRY(hipMemsetAsync(ctx->d_counter, 0, sizeof(unsigned long long), s));
+	const unsigned nwg	 = std::min(2048u, (unsigned) ctx->nbc);// the kernel strides over the blocks
+	const Partition& P = ctx->part[ctx->rollid];
+	if(tri_vel && cap)
+		grid_isosurface_kernel<true><<<nwg, kIsoThreads, 0, s>>>(ctx->g, ctx->nbc, P.keys, P.table, ctx->grid[0], a, d_xyz.p, d_vel.p, ctx->d_counter);
+	else
+		grid_isosurface_kernel<false><<<nwg, kIsoThreads, 0, s>>>(ctx->g, ctx->nbc, P.keys, P.table, ctx->grid[0], a, d_xyz.p, nullptr, ctx->d_counter);
+	HIP_TRY(hipGetLastError());
+	unsigned long long count = 0;
+	HIP_TRY(hipMemcpyAsync(&count, ctx->d_counter, sizeof(count), hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	const size_t got = (size_t) std::min<unsigned long long>(count, cap);
+	if(got) {
+		HIP_TRY(hipMemcpy(tri_xyz, d_xyz.p, sizeof(float) * 9 * got, hipMemcpyDeviceToHost));
+		if(tri_vel) HIP_TRY(hipMemcpy(tri_vel, d_vel.p, sizeof(float) * 9 * got, hipMemcpyDeviceToHost));
+	}
+	*n = (size_t) count;
+	if(tri_xyz && count > cap) return fail(ctx, MPM_ERR_CAPACITY, "mpm_grid_isosurface: the surface has " + std::to_string(count) + " triangles, the buffers hold " + std::to_string(cap));
+	return MPM_OK;
+}
+
 // ---- function-level tests ---------------------------------------------------------------------------
-#define HIP_TRY0(expr)                         \
+#define HIP_TRY0(expr)                       \
 	do {                                       \
 		if((expr) != hipSuccess) return MPM_ERR_DEVICE; \
 	} while(0)

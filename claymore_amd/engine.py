@@ -453,10 +453,49 @@ class Engine:
         self._check(self.api.grid_box_totals(self.ctx, (C.c_int * 3)(*[int(v) for v in lo]), (C.c_int * 3)(*[int(v) for v in hi]), out))
         return {"mass": float(out[0]), "momentum": np.array(out[1:4], dtype=np.float64), "kinetic": float(out[4])}
 
+    def isosurface(self, density=None, iso_mass=None, box=None, velocity=False, weld=True):
+        """The iso-surface of the mass grid of the last P2G (mpm_grid_isosurface): marching tetrahedra over the registered blocks, watertight.
+        Exactly one of `density` (mass per volume; the iso value is density * dx^3) and `iso_mass` (node mass) is given.  box = (lo, hi): only
+        the cells lo <= (i, j, k) < hi.  weld=True: (V (nv, 3) float32, F (nf, 3) int32[, vel (nv, 3) float32]) - vertices welded on their
+        position bits (shared edges give identical bits), the velocity of a vertex taken from its first occurrence, triangles with two
+        equal indices dropped; the normals point out of the material.  weld=False: the raw soup (nt, 3, 3) float32[, velocities (nt, 3, 3)]."""
+        if (density is None) == (iso_mass is None):
+            raise EngineError(_ffi.MPM_ERR_INVALID, "isosurface: give exactly one of density and iso_mass")
+        iso = float(np.float32(iso_mass if density is None else density * self.dx ** 3))
+        lo = hi = None
+        if box is not None:
+            lo, hi = ((C.c_int * 3)(*[int(v) for v in b]) for b in box)
+        n = C.c_size_t(0)
+        self._check(self.api.grid_isosurface(self.ctx, iso, lo, hi, None, None, C.byref(n)))          # count, then fetch
+        tris = np.empty((n.value, 3, 3), dtype=np.float32)
+        vel = np.empty((n.value, 3, 3), dtype=np.float32) if velocity else None
+        if n.value:
+            self._check(self.api.grid_isosurface(self.ctx, iso, lo, hi, tris.ctypes.data_as(C.c_void_p),
+                                                 vel.ctypes.data_as(C.c_void_p) if velocity else None, C.byref(n)))
+        if not weld:
+            return (tris, vel) if velocity else tris
+        return weld_triangles(tris, vel)
+
     def last_g2p2g_ms(self):
         ms = C.c_float(0)
         self._check(self.api.last_g2p2g_ms(self.ctx, C.byref(ms)))
         return ms.value
+
+
+def weld_triangles(tris, vel=None):
+    """A triangle soup (nt, 3, 3) float32 as an indexed mesh: (V (nv, 3) float32, F (nf, 3) int32[, vel (nv, 3) float32]).  Vertices are equal
+    when their position bits are; V is sorted by those bits; a vertex's velocity is that of its first occurrence in the soup; triangles
+    with two equal indices are dropped."""
+    pts = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 3)
+    if pts.shape[0] == 0:
+        empty = (pts.copy(), np.zeros((0, 3), dtype=np.int32))
+        return empty if vel is None else empty + (np.zeros((0, 3), dtype=np.float32),)
+    _, first, inverse = np.unique(pts.view(np.uint32), axis=0, return_index=True, return_inverse=True)
+    faces = inverse.reshape(-1, 3).astype(np.int32)
+    faces = faces[(faces[:, 0] != faces[:, 1]) & (faces[:, 1] != faces[:, 2]) & (faces[:, 0] != faces[:, 2])]
+    if vel is None:
+        return pts[first], faces
+    return pts[first], faces, np.ascontiguousarray(vel, dtype=np.float32).reshape(-1, 3)[first]
 
 
 def build_engine(scene, device=0, api=None):

@@ -303,6 +303,17 @@ int main(int argc, char** argv) {
 			return 1;
 		}
 	}
+	float surface_iso = 0.f;// simulation.output_surface: the iso value as a node mass, density * dx^3; 0 = no surface files
+	if(sim.has("output_surface")) {
+		const mj::Value& os = sim["output_surface"];
+		const double rho	= os.type == mj::Value::Object ? (double) num(os, "density", 0.f) : 0.0;
+		const double dx		= 1.0 / (double) (1 << bits);
+		surface_iso			= (float) (rho * dx * dx * dx);
+		if(!(surface_iso > 0.f) || !std::isfinite(surface_iso)) {
+			std::fprintf(stderr, "gmpm: simulation.output_surface must be {\"density\": a positive number}\n");
+			return 1;
+		}
+	}
 	std::printf("simulation: gpuid[%d], defaultDt[%g], fps[%d], frames[%d]\n", gpuid, dt_def, fps, frames);
 
 	mpm_config cfg;
@@ -402,6 +413,16 @@ int main(int argc, char** argv) {
 	long steps	   = 0;
 	std::vector<float> buf, vbuf, sbuf;
 	pio::AsyncWriter io;
+	// simulation.output_surface: the iso-surface of the mass grid beside the frame (frame 0: the grid of the set-up's P2G): count, then fetch
+	auto write_surface = [&](int frame) {
+		size_t nt = 0;
+		int rs	  = mpm_grid_isosurface(ctx, surface_iso, nullptr, nullptr, nullptr, nullptr, &nt);
+		if(rs) die(ctx, rs);
+		std::vector<float> tris(9 * nt);
+		if(nt && (rs = mpm_grid_isosurface(ctx, surface_iso, nullptr, nullptr, tris.data(), nullptr, &nt))) die(ctx, rs);
+		io.write_obj_surface_async(out_dir + "/surface_frame[" + std::to_string(frame) + "].obj", std::move(tris));
+	};
+	if(surface_iso > 0.f) write_surface(0);
 	const auto wall0 = std::chrono::steady_clock::now();
 	for(int frame = 1; frame <= frames; ++frame) {
 		for(float t = 0.f; t < spf;) {
@@ -432,6 +453,7 @@ int main(int argc, char** argv) {
 			if(rc) die(ctx, rc);
 			io.write_npy_f32_async(out_dir + "/grid_frame[" + std::to_string(frame) + "].npy", std::move(vol), {4, (size_t) cells, (size_t) cells, (size_t) cells});
 		}
+		if(surface_iso > 0.f) write_surface(frame);
 		for(size_t mi = 0; mi < counts.size(); ++mi) {// output_model, :594-634
 			buf.resize(3 * counts[mi]);
 			vbuf.clear();

@@ -55,6 +55,16 @@ int main(int argc, char** argv) {
 		if(4 * shape[1] * shape[2] * shape[3] != v.size()) return 5;
 		return pio::write_npy_f32(argv[6], v.data(), shape) ? 0 : 4;
 	}
+	if(argc == 4 && !std::strcmp(argv[1], "--obj-from")) {// host_selftest --obj-from soup.f32 out.obj: 9 raw float32 values a triangle -> the welded OBJ file of a surface
+		std::ifstream in(argv[2], std::ios::binary | std::ios::ate);
+		if(!in) return 3;
+		const size_t bytes = (size_t) in.tellg();
+		std::vector<float> v(bytes / sizeof(float));
+		in.seekg(0);
+		in.read(reinterpret_cast<char*>(v.data()), (std::streamsize) bytes);
+		if(v.size() % 9) return 5;
+		return pio::write_obj_surface(argv[3], v.data(), v.size() / 9) ? 0 : 4;
+	}
 	const char* text = R"({"simulation": {"gpuid": 0, "fps": 1200, "frames": 2, "default_dt": 5e-6},
 	  "models": [{"type": "particle", "file": "two_dragons.sdf", "constitutive": "jfluid", "offset": [0.1, 0.1, 0.1],
 	              "span": [1.0, 1.0, 1.0], "velocity": [0.0, -1.0, 0.0], "nested": {"a": [true, false, null, "s\"q"]}},

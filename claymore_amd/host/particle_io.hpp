@@ -12,7 +12,9 @@
 // attributes' values behind w in that order.  An INT attribute (gmpm's simulation.output_ids: "id" of 1 int) is partio's INT (BGEO.cpp:360-373,
 // :396-400): Houdini type 1, the same 16-bit size and zero defaults, its values big-endian int32 where a FLOAT's float32 stand.
 // write_npy_f32: a float32 array as a NumPy .npy file (gmpm's simulation.output_grid).
+// write_obj_surface: a triangle soup as a welded Wavefront OBJ file (gmpm's simulation.output_surface).
 #pragma once
+#include <algorithm>
 #include <condition_variable>
 #include <deque>
 #include <functional>
@@ -151,6 +153,35 @@ inline bool write_npy_f32(const std::string& filename, const float* data, const 
 	return (bool) f;
 }
 
+// A triangle soup (mpm_grid_isosurface: nine floats a triangle) as a Wavefront OBJ file (gmpm's simulation.output_surface), welded the way
+// Engine.isosurface welds: vertices are equal when their position bits are - the surface readout gives triangles that share an edge
+// identical bits -, the "v" lines are sorted by those bits (x, then y, then z, as unsigned words), triangles with two equal indices are
+// dropped, and the "f" lines keep the soup's order and winding with 1-based indices.  Coordinates are printed with nine significant digits,
+// which give the float32 back.
+inline bool write_obj_surface(const std::string& filename, const float* tris, size_t ntris) {
+	const size_t nv = 3 * ntris;
+	std::vector<std::array<uint32_t, 3>> bits(nv);
+	if(nv) std::memcpy(bits.data(), tris, nv * 3 * sizeof(float));
+	std::vector<uint32_t> order(nv), index(nv);
+	for(size_t i = 0; i < nv; ++i) order[i] = (uint32_t) i;
+	std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return bits[a] < bits[b]; });
+	std::FILE* f = std::fopen(filename.c_str(), "w");
+	if(!f) return false;
+	uint32_t count = 0;
+	for(size_t i = 0; i < nv; ++i) {
+		if(i == 0 || bits[order[i]] != bits[order[i - 1]]) {
+			++count;
+			std::fprintf(f, "v %.9g %.9g %.9g\n", tris[3 * (size_t) order[i]], tris[3 * (size_t) order[i] + 1], tris[3 * (size_t) order[i] + 2]);
+		}
+		index[order[i]] = count;// 1-based
+	}
+	for(size_t q = 0; q < ntris; ++q) {
+		const uint32_t a = index[3 * q], b = index[3 * q + 1], c = index[3 * q + 2];
+		if(a != b && b != c && a != c) std::fprintf(f, "f %u %u %u\n", a, b, c);
+	}
+	return std::fclose(f) == 0;
+}
+
 // The reference's lattice rule (Library/MnBase/Geometry/GeometrySampler.h:11-37): 8 particles per grid node at +-0.25 dx.
 template<typename Inside>
 inline Points sample_lattice(float dx, const int lo[3], const int hi[3], Inside inside) {
@@ -261,6 +292,9 @@ public:
 	}
 	void write_npy_f32_async(std::string fn, std::vector<float> data, std::vector<size_t> shape) {
 		insert_job([fn = std::move(fn), data = std::move(data), shape = std::move(shape)] { write_npy_f32(fn, data.data(), shape); });
+	}
+	void write_obj_surface_async(std::string fn, std::vector<float> tris) {
+		insert_job([fn = std::move(fn), tris = std::move(tris)] { write_obj_surface(fn, tris.data(), tris.size() / 9); });
 	}
 	void flush() {// IO::flush: wait until every queued job has been written
 		std::unique_lock<std::mutex> lk(mut_);

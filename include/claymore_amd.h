@@ -416,6 +416,42 @@ int mpm_dump_grid(mpm_ctx* ctx, int* keys, float* blocks, size_t* nblocks);
 int mpm_sample_grid(mpm_ctx* ctx, const float* xyz, size_t n, float* out4);
 int mpm_grid_volume(mpm_ctx* ctx, const int origin[3], const int dims[3], int stride, float* out);
 int mpm_grid_box_totals(mpm_ctx* ctx, const int lo[3], const int hi[3], double out[5]);
+/* Extension: the iso-surface of the mass grid - a watertight triangle soup, by marching tetrahedra over the valued blocks only.
+ * Field: f(i, j, k) is the mass word of node (i, j, k) as mpm_grid_volume at stride 1 reads it: the valued nodes are those above, every
+ *   other node - exterior or absent blocks, the nodes -1 and N just outside the domain - reads +0.  A node is INSIDE iff f > iso_mass (a
+ *   NaN is outside).  iso_mass must be finite and > 0 (else MPM_ERR_INVALID): the field is 0 outside a bounded set, so the surface of the
+ *   whole grid is closed.  Density is f / dx^3.
+ * Cells: cell (i, j, k), i, j, k in [-1, N - 1], has the eight corner nodes (i, j, k) + {0, 1}^3.  lo and hi both NULL: every cell.  Both
+ *   given: the cells with lo <= (i, j, k) < hi only - a half-open CELL box that may leave the domain; the surface is open where the box
+ *   cuts it.  Exactly one of them NULL: MPM_ERR_INVALID.
+ * Tetrahedra: the six Kuhn tetrahedra of the cell, one per permutation (a, b, c) of the axes, with the corners c0 = (0, 0, 0), c1 = c0 +
+ *   e_a, c2 = c1 + e_b, c3 = (1, 1, 1).  All share the main diagonal; the decomposition is the same in every cell, so neighbouring cells
+ *   agree on the diagonals of their common face.
+ * Vertices: an edge (A, B) of a tetrahedron, A the corner that is componentwise <= B (B - A is in {0, 1}^3), carries a vertex iff exactly
+ *   one end is inside.  t = (iso_mass - f(A)) / (f(B) - f(A)): two float32 subtractions and one correctly rounded float32 division, in
+ *   [0, 1] whenever both masses are finite.  In node units the vertex is (float) A_d + t on the axes with B_d - A_d = 1 (one float32 add)
+ *   and (float) A_d on the others; the world position is that times dx (exact).  The value depends on the edge's two nodes only, so
+ *   triangles that share an edge get BIT-IDENTICAL vertices: a caller welds on the position bits.
+ * Triangles: one inside corner I and outside corners O0 < O1 < O2 (in the tetrahedron's corner order): P(I, O0) P(I, O1) P(I, O2); three
+ *   inside: the mirror case P(I0, O) P(I1, O) P(I2, O); two inside I0 < I1, outside O0 < O1: the quad P(I0, O0) P(I0, O1) P(I1, O1)
+ *   P(I1, O0) split along P(I0, O0) - P(I1, O1).  Winding: the normal (v1 - v0) x (v2 - v0) points from the inside corners to the outside
+ *   corners, decided from the CORNER coordinates - the sign of det[O0 - I, O1 - I, O2 - I], for the quad the same test on the edge
+ *   midpoints - never from interpolated positions: the order above is kept or reversed.  Degenerate triangles (t rounded to 0 or 1) so
+ *   keep a defined winding; they are kept, not filtered.  Which vertex of a triangle comes first, and the order of the triangles, are
+ *   unspecified.
+ * Output: tri_xyz[9 q ..] the three world-space vertices of triangle q; tri_vel[9 q ..] (may be NULL) per vertex (p(A) + t (p(B) - p(A)))
+ *   / iso_mass per momentum channel - the mass-weighted velocity there, the interpolated mass being iso_mass - in float32, in any
+ *   association.  *n in: the capacity in triangles; out: the number of triangles the surface HAS.  tri_xyz NULL: count only (tri_vel
+ *   must be NULL too), nothing but the count is computed.  A count above the capacity: MPM_ERR_CAPACITY, *n the true count, the buffers
+ *   hold `capacity` triangles of the surface, unspecified which; the context stays usable and the caller retries (mpm_halo_keys'
+ *   protocol).  MPM_ERR_CAPACITY also when the device cannot hold the staging buffer of 72 (with tri_vel 144) bytes a triangle (*n is
+ *   then left as it was).
+ * Non-finite masses: inside or outside by the comparison above, so the count is always defined; the positions and velocities of the
+ *   vertices on an edge with a non-finite end are unspecified.
+ * Preconditions and errors: those of mpm_grid_volume - MPM_ERR_NOT_READY before mpm_initial_setup; MPM_ERR_INVALID for a NULL n, for a
+ * grid that holds velocities and, permanently, for a context that has ever joined an mpm_group or been through the halo tagging.  Reads
+ * only: no state, checkpoint or later substep changes.  HIP library only. */
+int mpm_grid_isosurface(mpm_ctx* ctx, float iso_mass, const int lo[3], const int hi[3], float* tri_xyz, float* tri_vel, size_t* n);
 /* How the library was built: "claymore_hip <abi> experiment=<none | list of -D switches>".  A product library reports
  * experiment=none (claymore_amd/csrc/mpm_device_math.hpp: the switches that change what the kernels compute only exist under
  * -DMPM_EXPERIMENT); tests/test_abi.py asserts it for the shipped library.  Needs no device. */

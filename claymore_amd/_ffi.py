@@ -52,6 +52,13 @@ class Heightfield(C.Structure):
 HEIGHTFIELD_MAX_SAMPLES = 4096
 
 
+class CollisionMesh(C.Structure):
+    _fields_ = [("inside_out", C.c_int), ("reserved", C.c_int * 7)]
+
+
+MESH_MAX_TRIANGLES = MESH_MAX_VERTICES = 1 << 22
+
+
 class Counts(C.Structure):
     _fields_ = [("particle_blocks", C.c_int), ("neighbor_blocks", C.c_int), ("exterior_blocks", C.c_int),
                 ("model_count", C.c_int), ("bins", C.c_int64 * 8), ("particles", C.c_int64 * 8)]
@@ -137,6 +144,8 @@ HIP_ONLY = {
     "test_collision_shape": (_i, [_P(CollisionObject), _P(CollisionShape), _f, _f, _vp, _sz, _vp, _i]),
     "set_collision_heightfield": (_i, [_vp, _i, _P(CollisionObject), _P(Heightfield), _vp]),
     "test_collision_heightfield": (_i, [_P(CollisionObject), _P(Heightfield), _vp, _f, _vp, _sz, _vp, _i]),
+    "set_collision_mesh": (_i, [_vp, _P(CollisionObject), _P(CollisionMesh), _vp, _sz, _vp, _sz]),
+    "get_collision_field": (_i, [_vp, _P(C.c_int), _P(C.c_int), _vp]),
     "checkpoint_size": (_i, [_vp, _P(_sz)]),
     "checkpoint_save": (_i, [_vp, _vp, _sz, _P(_sz)]),
     "checkpoint_load": (_i, [_vp, _vp, _sz]),

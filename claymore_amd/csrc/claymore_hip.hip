@@ -18,6 +18,7 @@
 #include "mpm_readout.hpp"
 #include "mpm_grid_field.hpp"
 #include "mpm_grid_isosurface.hpp"
+#include "mpm_collision_mesh.hpp"
 #include "mpm_particle_ids.hpp"
 
 using namespace mpm;
@@ -1390,6 +1391,80 @@ int mpm_set_collision_heightfield(mpm_ctx* ctx, int slot, const mpm_collision_ob
 	}
 	f.table = d;
 	return install_slot(ctx, slot, c, f, obj);
+}
+
+// Triangle mesh -> level-set field (mpm_collision_mesh.hpp) --------------------------------------------------------------------------------
+// Order: every host check, then the new field and the records are allocated beside the installed field, filled, and only then does the old
+// field go: a refusal - invalid mesh, no memory, a device error - leaves the context as it was.  Replacing a field so needs room for two
+// for the duration of the call.
+int mpm_set_collision_mesh(mpm_ctx* ctx, const mpm_collision_object* obj, const mpm_collision_mesh* opt, const float* verts, size_t nv, const int32_t* tris, size_t nt) {
+	if(!ctx) return MPM_ERR_INVALID;
+	if(!obj) return fail(ctx, MPM_ERR_INVALID, "collision mesh: NULL obj (mpm_set_collision_object(ctx, NULL, ...) removes the object)");
+	if(!verts || !tris) return fail(ctx, MPM_ERR_INVALID, "collision mesh: NULL verts or tris");
+	if(obj->type < MPM_BOUNDARY_STICKY || obj->type > MPM_BOUNDARY_SEPARATE) return fail(ctx, MPM_ERR_INVALID, "collision mesh: boundary type outside 0..2");
+	std::vector<MeshTri> rec;
+	std::vector<MeshPseudo> pseudo;
+	MeshReport rep;
+	mesh_build(verts, nv, tris, nt, MPM_MESH_MAX_VERTICES, MPM_MESH_MAX_TRIANGLES, rec, pseudo, rep);
+	if(!rep.reason.empty()) return fail(ctx, MPM_ERR_INVALID, rep.reason);
+	float extent = 1.f;// largest coordinate magnitude in play: the domain's 1 or a vertex's
+	for(size_t i = 0; i < 3 * nv; ++i) extent = std::max(extent, std::fabs(verts[i]));
+	HIP_TRY(hipSetDevice(ctx->device));
+	HIP_TRY(hipDeviceSynchronize());
+	const int N	   = 1 << ctx->cfg.domain_bits;
+	const size_t n = (size_t) N * N * N;
+	float4* field  = nullptr;
+	DevScratch<MeshTri> d_rec;
+	DevScratch<MeshPseudo> d_pseudo;
+	if(dalloc(&field, n) != hipSuccess || dalloc(&d_rec.p, nt) != hipSuccess || dalloc(&d_pseudo.p, nt) != hipSuccess) {
+		(void) hipGetLastError();
+		if(field) hipFree(field);
+		return fail(ctx, MPM_ERR_CAPACITY, "collision mesh: no device memory for the field of " + std::to_string(n) + " nodes and " + std::to_string(nt) + " triangle records");
+	}
+	hipError_t e = hipMemcpy(d_rec.p, rec.data(), sizeof(MeshTri) * nt, hipMemcpyHostToDevice);
+	if(e == hipSuccess) e = hipMemcpy(d_pseudo.p, pseudo.data(), sizeof(MeshPseudo) * nt, hipMemcpyHostToDevice);
+	if(e == hipSuccess) {
+		const float dx	  = 1.f / (float) N;
+		const float slack = std::max(0.25f * dx, extent * 0x1p-12f);
+		const unsigned tiles = (unsigned) (N >> 2);
+		collision_mesh_field_kernel<<<tiles * tiles * tiles, 64, 0, ctx->s_compute>>>(d_rec.p, d_pseudo.p, (int) nt, N, dx, slack, opt && opt->inside_out ? 1 : 0, field);
+		e = hipGetLastError();
+	}
+	if(e == hipSuccess) e = hipStreamSynchronize(ctx->s_compute);
+	if(e != hipSuccess) {
+		hipFree(field);
+		return fail(ctx, MPM_ERR_DEVICE, std::string("collision mesh: building the field -> ") + hipGetErrorString(e));
+	}
+	if(ctx->d_sdf) hipFree(ctx->d_sdf);
+	ctx->d_sdf			   = field;
+	ctx->collision		   = slot_object(obj);
+	ctx->collision.field   = field;
+	ctx->has_collision	   = true;
+	ctx->collision_running = false;// installing an object stops the clock
+	return MPM_OK;
+}
+
+int mpm_get_collision_field(mpm_ctx* ctx, const int lo[3], const int dims[3], float* out4) {
+	if(!ctx) return MPM_ERR_INVALID;
+	if(!lo || !dims || !out4) return fail(ctx, MPM_ERR_INVALID, "mpm_get_collision_field: NULL argument");
+	if(!ctx->has_collision || !ctx->d_sdf) return fail(ctx, MPM_ERR_INVALID, "mpm_get_collision_field: no level-set collision object installed");
+	const int N = 1 << ctx->cfg.domain_bits;
+	for(int d = 0; d < 3; ++d) {
+		if(dims[d] < 1) return fail(ctx, MPM_ERR_INVALID, "mpm_get_collision_field: a dims entry < 1");
+		if(lo[d] < 0 || lo[d] >= N || dims[d] > N - lo[d]) return fail(ctx, MPM_ERR_INVALID, "mpm_get_collision_field: the box leaves [0, N)^3");
+	}
+	const size_t n = (size_t) dims[0] * (size_t) dims[1] * (size_t) dims[2];
+	HIP_TRY(hipSetDevice(ctx->device));
+	DevScratch<float4> stage;
+	if(dalloc(&stage.p, n) != hipSuccess) {
+		(void) hipGetLastError();
+		return fail(ctx, MPM_ERR_CAPACITY, "mpm_get_collision_field: no device memory for the box");
+	}
+	collision_field_box_kernel<<<cdiv(n, 256), 256, 0, ctx->s_compute>>>(ctx->d_sdf, N, lo[0], lo[1], lo[2], dims[0], dims[1], dims[2], stage.p);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipStreamSynchronize(ctx->s_compute));
+	HIP_TRY(hipMemcpy(out4, stage.p, sizeof(float4) * n, hipMemcpyDeviceToHost));
+	return MPM_OK;
 }
 
 int mpm_set_collision_clock(mpm_ctx* ctx, int running, float time) {

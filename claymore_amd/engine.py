@@ -350,6 +350,41 @@ class Engine:
         if animate:
             self.set_collision_clock(True, float(obj.time))
 
+    def set_collision_mesh(self, vertices, faces, inside_out=False, animate=False, **fields):
+        """Install the level-set collision object from a closed triangle mesh (mpm_set_collision_mesh, HIP engine only): the field is built
+        on the device - exact point-triangle distance, sign from angle-weighted pseudonormals - with no N^3 host array.  vertices: (nv, 3)
+        in the coordinates a level set's samples are given in (node (i, j, k) samples (i, j, k) dx); faces: (nt, 3) vertex indices,
+        counter-clockwise seen from outside - what isosurface(weld=True) returns.  inside_out: the solid is the complement (a container).
+        fields: those of set_collision_object.  It replaces a level-set object installed either way; set_collision_object() removes it."""
+        obj = _ffi.CollisionObject()
+        self._check(self.api.default_collision_object(C.byref(obj)))
+        for k, v in fields.items():
+            cur = getattr(obj, k)
+            if hasattr(cur, "__len__"):
+                for i, x in enumerate(np.asarray(v, dtype=np.float32).ravel()):
+                    cur[i] = float(x)
+            else:
+                setattr(obj, k, v)
+        v = np.ascontiguousarray(vertices, dtype=np.float32)
+        f = np.ascontiguousarray(faces, dtype=np.int32)
+        if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+            raise ValueError(f"set_collision_mesh: vertices must be (nv, 3) and faces (nt, 3), got {v.shape} and {f.shape}")
+        opt = _ffi.CollisionMesh()
+        opt.inside_out = 1 if inside_out else 0
+        self._check(self.api.set_collision_mesh(self.ctx, C.byref(obj), C.byref(opt), v.ctypes.data, v.shape[0], f.ctypes.data, f.shape[0]))
+        if animate:
+            self.set_collision_clock(True, float(obj.time))
+
+    def collision_field(self, lo=(0, 0, 0), shape=None):
+        """The installed level-set field, however it was installed (mpm_get_collision_field): (d0, d1, d2, 4) float32 {sdis, gx, gy, gz} of
+        the nodes lo + [0, shape), bit for bit.  shape=None: from lo to the end of the domain."""
+        n = 1 << self.cfg.domain_bits
+        lo = [int(v) for v in lo]
+        shape = [n - v for v in lo] if shape is None else [int(v) for v in shape]
+        out = np.empty(tuple(shape) + (4,) if min(shape) >= 1 else (1,), dtype=np.float32)
+        self._check(self.api.get_collision_field(self.ctx, (C.c_int * 3)(*lo), (C.c_int * 3)(*shape), out.ctypes.data))
+        return out
+
     def set_collision_clock(self, running=True, time=0.0):
         """Set the collision object's time and start (or stop) its clock: a running clock advances by dt with every grid update,
         the update of a substep sees the object at the time the substep starts (HIP engine only)."""
@@ -512,6 +547,8 @@ def build_engine(scene, device=0, api=None):
         eng.init_model(m["material"], m["xyz"], m.get("v0", (0, 0, 0)), **m.get("params", {}))
     if scene.get("collision"):
         eng.set_collision_object(**{**scene["collision"], "animate": False})
+    if scene.get("collision_mesh"):  # the level-set object from a triangle mesh (it and "collision" are one object: the later install wins)
+        eng.set_collision_mesh(**{**scene["collision_mesh"], "animate": False})
     colliders = scene.get("colliders") or []
     for slot, c in enumerate(colliders):
         if c.get("kind") == "heightfield":
@@ -519,7 +556,8 @@ def build_engine(scene, device=0, api=None):
         else:
             eng.set_collision_shape(slot, **{**c, "animate": False})
     # one clock for all colliders: started once, after the last install (every install stops it)
-    moving = [c for c in ([scene["collision"]] if scene.get("collision") else []) + list(colliders) if c.get("animate")]
+    fields = [scene[k] for k in ("collision", "collision_mesh") if scene.get(k)]
+    moving = [c for c in fields + list(colliders) if c.get("animate")]
     if moving:
         eng.set_collision_clock(True, float(moving[0].get("time", 0.0)))
     return eng

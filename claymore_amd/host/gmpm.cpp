@@ -17,6 +17,7 @@
 // velocity readout.  simulation.output_ids (default false): the context tracks particle ids (mpm_track_particle_ids) and every frame also carries
 // the INT point attribute "id" - the particle's index among the model's sampled points - with the frame's points written in ascending id
 // order, so the point order is the same in every frame; the other attributes are joined to the ids on the position bits.  A top-level "colliders" array installs analytic collision shapes (parse_collider below).
+// A top-level "collision_mesh" object installs the level-set collision object from an OBJ file (mpm_set_collision_mesh; in main below).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -380,6 +381,46 @@ int main(int argc, char** argv) {
 		counts.push_back(pts.size());
 	}
 
+	// "collision_mesh": {"file": "body.obj", "type": "sticky|slip|separate", "friction", "velocity", "omega", "inside_out", "scale": s, "offset": [x, y, z]}
+	// installs the level-set collision object from a closed triangle mesh (mpm_set_collision_mesh): the OBJ file's vertices, times the uniform
+	// scale, plus the offset.  It is a key of its own, not a collider: the mesh occupies the level-set object, not a slot.  It moves - about
+	// the origin - with "velocity" or "omega", which start the clock as a moving collider does.
+	bool mesh_moving = false;
+	if(doc->has("collision_mesh")) {
+		const mj::Value& cm = (*doc)["collision_mesh"];
+		if(cm.type != mj::Value::Object || !cm.has("file")) {
+			std::fprintf(stderr, "gmpm: collision_mesh must be an object with a \"file\"\n");
+			return 1;
+		}
+		const std::string path = scene_dir + "/" + cm["file"].string();
+		std::vector<float> verts;
+		std::vector<int32_t> tris;
+		if(!pio::read_obj_mesh(path, verts, tris)) {
+			std::fprintf(stderr, "gmpm: collision_mesh file '%s' cannot be read as an OBJ mesh\n", path.c_str());
+			return 1;
+		}
+		const float scale = num(cm, "scale", 1.f);
+		float offset[3]	  = {0.f, 0.f, 0.f};
+		vec3(cm, "offset", offset);
+		for(size_t i = 0; i < verts.size(); ++i) verts[i] = verts[i] * scale + offset[i % 3];
+		mpm_collision_object obj;
+		mpm_default_collision_object(&obj);
+		const std::string type = cm.has("type") ? cm["type"].string() : "sticky";
+		obj.type			   = type == "sticky" ? MPM_BOUNDARY_STICKY : type == "slip" ? MPM_BOUNDARY_SLIP : type == "separate" ? MPM_BOUNDARY_SEPARATE : -1;
+		if(obj.type < 0) {
+			std::fprintf(stderr, "gmpm: unknown collision_mesh type '%s' (expected sticky, slip or separate)\n", type.c_str());
+			return 1;
+		}
+		obj.friction = num(cm, "friction", obj.friction);
+		if(vec3(cm, "velocity", obj.trans_vel)) mesh_moving = true;
+		if(vec3(cm, "omega", obj.omega)) mesh_moving = true;
+		mpm_collision_mesh opt;
+		std::memset(&opt, 0, sizeof(opt));
+		opt.inside_out = cm.has("inside_out") && cm["inside_out"].type == mj::Value::Bool && cm["inside_out"].b;
+		if((rc = mpm_set_collision_mesh(ctx, &obj, &opt, verts.data(), verts.size() / 3, tris.data(), tris.size() / 3))) die(ctx, rc);
+		std::printf("has a collision mesh of %zu triangles%s\n", tris.size() / 3, mesh_moving ? ", clock running" : "");
+	}
+
 	// "colliders": analytic collision shapes (mpm_set_collision_shape), at most MPM_MAX_COLLISION_SHAPES, slot = position in the array
 	if(doc->has("colliders")) {
 		const mj::Value& cols = (*doc)["colliders"];
@@ -400,6 +441,7 @@ int main(int argc, char** argv) {
 		std::printf("has %zu colliders%s\n", cols.arr.size(), moving ? ", clock running" : "");
 		if(moving && (rc = mpm_set_collision_clock(ctx, 1, 0.f))) die(ctx, rc);// one clock for all of them, started after the last install
 	}
+	if(mesh_moving && (rc = mpm_set_collision_clock(ctx, 1, 0.f))) die(ctx, rc);// (every install above stopped it)
 
 	// main_loop, gmpm_simulator.cuh:303-592
 	const float spf = 1.f / (float) fps;

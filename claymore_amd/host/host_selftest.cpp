@@ -1,11 +1,12 @@
 // host_selftest.cpp — exercises the pieces of the host drivers that need no GPU (JSON reader, lattice sampler, BGEO
-// writer, NumPy writer).  usage: host_selftest <out.bgeo>  -> prints "json_ok <n_models> <dt>", "sphere <count>", "bgeo <bytes>"
+// writer, NumPy writer, OBJ reader, the collision mesh's validation and closest-point functions).  usage: host_selftest <out.bgeo>  -> prints "json_ok <n_models> <dt>", "sphere <count>", "bgeo <bytes>"
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
 
 #include "mini_json.hpp"
 #include "particle_io.hpp"
+#include "../csrc/mpm_collision_mesh.hpp"
 
 int main(int argc, char** argv) {
 	if(argc == 4 && !std::strcmp(argv[1], "--bgeo-from")) {// host_selftest --bgeo-from points.f32 out.bgeo: raw float32 xyz -> BGEO frame
@@ -64,6 +65,45 @@ int main(int argc, char** argv) {
 		in.read(reinterpret_cast<char*>(v.data()), (std::streamsize) bytes);
 		if(v.size() % 9) return 5;
 		return pio::write_obj_surface(argv[3], v.data(), v.size() / 9) ? 0 : 4;
+	}
+	if(argc == 3 && !std::strcmp(argv[1], "--mesh-check")) {// host_selftest --mesh-check FILE.obj: what mpm_set_collision_mesh's validation says about a mesh
+		std::vector<float> verts;
+		std::vector<int32_t> tris;
+		if(!pio::read_obj_mesh(argv[2], verts, tris)) return 3;
+		std::vector<mpm::MeshTri> rec;
+		std::vector<mpm::MeshPseudo> pseudo;
+		mpm::MeshReport rep;
+		mpm::mesh_build(verts.data(), verts.size() / 3, tris.data(), tris.size() / 3, (size_t) 1 << 22, (size_t) 1 << 22, rec, pseudo, rep);
+		std::printf("nv %zu\nnt %zu\nclosed %d\nvolume %.17g\nverdict %s\n", verts.size() / 3, tris.size() / 3, rep.closed ? 1 : 0, rep.volume, rep.reason.empty() ? "ok" : rep.reason.c_str());
+		return 0;
+	}
+	if(argc == 4 && !std::strcmp(argv[1], "--mesh-closest")) {// host_selftest --mesh-closest FILE.obj POINTS.f32: per point "T feature q sdis gx gy gz" (the floats as
+		std::vector<float> verts;								// their bits in hex) from the x86 build of the kernel's own functions; any mesh, closed or not
+		std::vector<int32_t> tris;
+		if(!pio::read_obj_mesh(argv[2], verts, tris)) return 3;
+		std::ifstream in(argv[3], std::ios::binary | std::ios::ate);
+		if(!in) return 3;
+		const size_t bytes = (size_t) in.tellg();
+		std::vector<float> pts(bytes / sizeof(float));
+		in.seekg(0);
+		in.read(reinterpret_cast<char*>(pts.data()), (std::streamsize) bytes);
+		if(pts.size() % 3) return 5;
+		std::vector<mpm::MeshTri> rec;
+		std::vector<mpm::MeshPseudo> pseudo;
+		mpm::MeshReport rep;
+		mpm::mesh_build(verts.data(), verts.size() / 3, tris.data(), tris.size() / 3, (size_t) 1 << 22, (size_t) 1 << 22, rec, pseudo, rep);
+		if(rec.empty()) return 6;
+		for(size_t i = 0; i < pts.size() / 3; ++i) {
+			const float p[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
+			float out[4], q;
+			int feature;
+			const int T = mpm::mesh_point_query(rec, pseudo, p, 0, out, feature, q);
+			uint32_t w[5];
+			std::memcpy(&w[0], &q, 4);
+			std::memcpy(&w[1], out, 16);
+			std::printf("%d %d %08x %08x %08x %08x %08x\n", T, feature, w[0], w[1], w[2], w[3], w[4]);
+		}
+		return 0;
 	}
 	const char* text = R"({"simulation": {"gpuid": 0, "fps": 1200, "frames": 2, "default_dt": 5e-6},
 	  "models": [{"type": "particle", "file": "two_dragons.sdf", "constitutive": "jfluid", "offset": [0.1, 0.1, 0.1],

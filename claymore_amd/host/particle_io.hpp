@@ -13,6 +13,7 @@
 // :396-400): Houdini type 1, the same 16-bit size and zero defaults, its values big-endian int32 where a FLOAT's float32 stand.
 // write_npy_f32: a float32 array as a NumPy .npy file (gmpm's simulation.output_grid).
 // write_obj_surface: a triangle soup as a welded Wavefront OBJ file (gmpm's simulation.output_surface).
+// read_obj_mesh: its inverse - the vertices and triangles of an OBJ file (gmpm's collision_mesh).
 #pragma once
 #include <algorithm>
 #include <condition_variable>
@@ -180,6 +181,49 @@ inline bool write_obj_surface(const std::string& filename, const float* tris, si
 		if(a != b && b != c && a != c) std::fprintf(f, "f %u %u %u\n", a, b, c);
 	}
 	return std::fclose(f) == 0;
+}
+
+// The inverse of write_obj_surface, for gmpm's "collision_mesh": the "v x y z" and "f ..." lines of a Wavefront OBJ file as nv x 3 floats and
+// nt x 3 zero-based indices.  An "f" entry may carry "/vt/vn" suffixes (ignored), an index may be negative (-1: the last vertex read so
+// far), a polygon is fan-triangulated (i0 i1 i2, i0 i2 i3 ...).  Every other line is skipped.  false: the file cannot be read, a "v" or
+// "f" line cannot be parsed, or an index points at no vertex read so far.
+inline bool read_obj_mesh(const std::string& filename, std::vector<float>& verts, std::vector<int32_t>& tris) {
+	verts.clear();
+	tris.clear();
+	std::ifstream f(filename);
+	if(!f) return false;
+	std::string line;
+	while(std::getline(f, line)) {
+		const char* s = line.c_str();
+		while(*s == ' ' || *s == '\t') ++s;
+		if(s[0] == 'v' && (s[1] == ' ' || s[1] == '\t')) {
+			float x[3];
+			if(std::sscanf(s + 1, "%f %f %f", &x[0], &x[1], &x[2]) != 3) return false;
+			verts.insert(verts.end(), x, x + 3);
+		} else if(s[0] == 'f' && (s[1] == ' ' || s[1] == '\t')) {
+			std::vector<int32_t> poly;
+			const int64_t nv = (int64_t) (verts.size() / 3);
+			for(s += 1;;) {
+				while(*s == ' ' || *s == '\t' || *s == '\r') ++s;
+				if(!*s) break;
+				char* end	   = nullptr;
+				const long long i = std::strtoll(s, &end, 10);
+				if(end == s) return false;
+				const int64_t idx = i < 0 ? nv + i : i - 1;
+				if(i == 0 || idx < 0 || idx >= nv) return false;
+				poly.push_back((int32_t) idx);
+				s = end;
+				while(*s && *s != ' ' && *s != '\t' && *s != '\r') ++s;// "/vt/vn"
+			}
+			if(poly.size() < 3) return false;
+			for(size_t k = 1; k + 1 < poly.size(); ++k) {
+				tris.push_back(poly[0]);
+				tris.push_back(poly[k]);
+				tris.push_back(poly[k + 1]);
+			}
+		}
+	}
+	return true;
 }
 
 // The reference's lattice rule (Library/MnBase/Geometry/GeometrySampler.h:11-37): 8 particles per grid node at +-0.25 dx.

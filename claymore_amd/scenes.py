@@ -315,3 +315,61 @@ def block_on_ramp(bits=6, block_cells=(6, 4, 6), speed=0.5, boundary="slip", fri
             "models": [{"material": material, "xyz": lattice_box(bits, lo, hi), "v0": (0.0, -speed, 0.0),
                         "params": {"volume": _vol(bits), "youngs_modulus": 5e3, "poisson_ratio": 0.4, "rho": 1e3}}],
             "colliders": [col]}
+
+
+def box_mesh(lo, hi):
+    """The box lo .. hi as a closed triangle mesh for Engine.set_collision_mesh: (8, 3) float32 vertices - vertex 4 i + 2 j + k takes hi on the
+    axes whose bit is set - and (12, 3) int32 faces, two per side, counter-clockwise seen from outside."""
+    lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+    v = np.array([[(hi if i else lo)[0], (hi if j else lo)[1], (hi if k else lo)[2]] for i in (0, 1) for j in (0, 1) for k in (0, 1)], dtype=np.float32)
+    quads = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]  # -x, +x, -y, +y, -z, +z
+    f = np.array([t for a, b, c, d in quads for t in ((a, b, c), (a, c, d))], dtype=np.int32)
+    return v, f
+
+
+def icosphere(centre, radius, subdivisions):
+    """A sphere as a closed triangle mesh: the icosahedron, every triangle split in four `subdivisions` times with the new vertices pushed
+    onto the sphere (20 x 4^subdivisions faces, welded, counter-clockwise seen from outside).  Returns (nv, 3) float32, (nt, 3) int32."""
+    g = (1.0 + np.sqrt(5.0)) / 2.0
+    v = [(-1, g, 0), (1, g, 0), (-1, -g, 0), (1, -g, 0), (0, -1, g), (0, 1, g), (0, -1, -g), (0, 1, -g), (g, 0, -1), (g, 0, 1), (-g, 0, -1), (-g, 0, 1)]
+    v = [np.array(p, dtype=np.float64) / np.sqrt(1.0 + g * g) for p in v]
+    f = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+         (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
+    for _ in range(int(subdivisions)):
+        mid = {}
+
+        def midpoint(a, b):
+            key = (min(a, b), max(a, b))
+            if key not in mid:
+                m = v[a] + v[b]
+                v.append(m / np.linalg.norm(m))
+                mid[key] = len(v) - 1
+            return mid[key]
+
+        nf = []
+        for a, b, c in f:
+            ab, bc, ca = midpoint(a, b), midpoint(b, c), midpoint(c, a)
+            nf += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        f = nf
+    verts = np.asarray(centre, dtype=np.float64)[None, :] + float(radius) * np.array(v)
+    return verts.astype(np.float32), np.array(f, dtype=np.int32)
+
+
+def sphere_on_obstacle_mesh(bits=6, radius_cells=5.0, obstacle_cells=6.0, boundary="slip", friction=0.3, speed=1.0, material=FIXED_COROTATED, subdivisions=3,
+                            body_cells=None, **motion):
+    """sphere_on_obstacle with the obstacle as an icosphere mesh (Engine.set_collision_mesh) instead of sphere_level_set: the field is built on
+    the device.  motion: further fields of the object (trans_vel, omega, animate ...).  body_cells = (cx, 2, cz): the thrown body is a small
+    lattice block resting on the obstacle's top instead of the sphere, its two node layers in y inside one particle block (with cx, cz = 2 the
+    whole block is: a body on which the engine is deterministic)."""
+    sc = sphere_on_obstacle(bits, radius_cells, obstacle_cells, boundary, friction, speed, material)
+    col = {k: v for k, v in sc.pop("collision").items() if k not in ("sdf", "grad")}
+    vertices, faces = icosphere((0.5, 0.34, 0.5), obstacle_cells / (1 << bits), subdivisions)
+    sc["collision_mesh"] = {**col, **motion, "vertices": vertices, "faces": faces}
+    sc["name"] += "_mesh"
+    if body_cells is not None:
+        n = 1 << bits
+        j = int(np.ceil(0.34 * n + obstacle_cells))
+        j += 1 if j % 4 == 1 else 0  # nodes j, j + 1 share a particle block (block_faces) unless j = 1 mod 4
+        lo = [n // 2 - int(body_cells[0]) // 2, j, n // 2 - int(body_cells[2]) // 2]
+        sc["models"][0]["xyz"] = lattice_box(bits, lo, [lo[0] + int(body_cells[0]), j + int(body_cells[1]), lo[2] + int(body_cells[2])])
+    return sc

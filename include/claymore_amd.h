@@ -364,6 +364,45 @@ int mpm_set_collision_heightfield(mpm_ctx* ctx, int slot, const mpm_collision_ob
 /* Function-level entry point (as mpm_test_collision_shape): out4[n*4] = {sdis, nx, ny, nz} at n arbitrary domain points xyz[n*3]. */
 int mpm_test_collision_heightfield(const mpm_collision_object* obj, const mpm_heightfield* hf, const float* heights, float time, const float* xyz, size_t n, float* out4, int device);
 
+/* Extension: the level-set collision object built on the device from a closed triangle mesh.  mpm_set_collision_mesh installs the object
+ * mpm_set_collision_object installs - it replaces whichever of the two was there, sets the clock to obj->time, stopped, acts before slots
+ * 0 .. 3 and is removed by mpm_set_collision_object(ctx, NULL, ...) - with the field computed by a kernel straight into the context's
+ * float4 field: no N^3 host array and no staging.  HIP library only.
+ * verts: nv x 3 floats in the coordinates a level set's samples are given in - node (i, j, k) samples the point ((float) i dx, (float) j dx,
+ * (float) k dx); tris: nt x 3 vertex indices, counter-clockwise seen from outside.  Both are copied during the call.
+ * Definition of the field (claymore_amd/csrc/mpm_collision_mesh.hpp; every float32 operation in the order written there, no contraction,
+ * correctly rounded / and sqrtf):
+ *   record of triangle t (host, float32): a, ab = b - a, ac = c - a, n^ = n / sqrtf(n . n) with n = ab x ac; for the sign only (float64,
+ *     stored as float32, not bit-defined) a pseudonormal per edge - n^ of this triangle + n^ of the one across - and per corner - the sum
+ *     over the triangles around the vertex of (interior angle at the vertex) x n^ (Baerentzen & Aanaes' angle-weighted normal);
+ *   closest point c_t(p) by the Voronoi-region walk (Ericson's ClosestPtPointTriangle: d1 .. d6, va / vb / vc), which also yields the
+ *     feature: corner a / b / c, edge ab / ac / bc, or face; q_t = |p - c_t|^2 as ((dx^2 + dy^2) + dz^2);
+ *   nearest triangle T(p): the lowest t among the triangles with the smallest q_t (float32, strict < in index order);
+ *   plane rule, where T's feature is the face or q_T < 2^-40 (a node on, or numerically on, the surface): sdis = (p - a) . n^ as
+ *     ((x + y) + z), g = n^;
+ *   radial rule elsewhere: d = sqrtf(q_T), s = +1 if (p - c_T) . m >= 0 else -1 with m the pseudonormal of T's feature, sdis = s d,
+ *     g_k = s (p_k - c_k) / d;
+ *   inside_out negates sdis and g.
+ * The field covers every node of [0, N)^3 exactly: no band, no clamp.
+ * Validation (host; MPM_ERR_INVALID, mpm_last_error names the reason; a refused install changes nothing: the installed object, if any,
+ * stays): a NULL ctx / obj / verts / tris; boundary type outside 0..2; nt < 4, nt or nv above the limits; an index outside [0, nv); a
+ * vertex that is not finite; a triangle whose n . n is zero or not finite in float32; a mesh that is not a closed, consistently oriented
+ * manifold - every directed edge (u, v) must occur exactly once and its reverse (v, u) exactly once; a signed volume sum a . (b x c) / 6
+ * (float64) <= 0 (flip the winding or use inside_out).  MPM_ERR_CAPACITY when the device cannot hold the new field (allocated while the
+ * old one is still installed) or the triangle records, which live on the device for the duration of the call only; the context stays
+ * usable and the old object stays installed. */
+enum { MPM_MESH_MAX_TRIANGLES = 1 << 22, MPM_MESH_MAX_VERTICES = 1 << 22 };
+typedef struct mpm_collision_mesh {
+	int inside_out; /* 1: the solid is the complement (a container): sdis and g change sign */
+	int reserved[7];
+} mpm_collision_mesh;
+int mpm_set_collision_mesh(mpm_ctx* ctx, const mpm_collision_object* obj, const mpm_collision_mesh* opt /* may be NULL */, const float* verts, size_t nv, const int32_t* tris, size_t nt);
+/* The four words {sdis, gx, gy, gz} of the nodes of the box lo + [0, dims) of the installed level-set field, whichever call installed it,
+ * bit for bit: node lo + (x, y, z) at out4[((x dims[1] + y) dims[2] + z) 4 ..].  MPM_ERR_INVALID without an installed level-set object, for
+ * a NULL argument, a dims entry < 1 or a box that leaves [0, N)^3.  Reads only.  It is also how a built field is saved, to be installed
+ * again through mpm_set_collision_object.  HIP library only. */
+int mpm_get_collision_field(mpm_ctx* ctx, const int lo[3], const int dims[3], float* out4);
+
 /* Current capacities and the number of times check_capacity() (gmpm_simulator.cuh:283-300) has grown them: blocks
  * (exterior count limit), bins per model (bin_capacity[8]).  HIP library only. */
 int mpm_get_capacity(mpm_ctx* ctx, int64_t* block_capacity, int64_t* bin_capacity, int* growth_events);

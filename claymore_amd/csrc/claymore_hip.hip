@@ -251,6 +251,36 @@ static inline unsigned cdiv(size_t a, size_t b) {
 	return (unsigned) ((a + b - 1) / b);
 }
 
+// The installed colliders as the grid update that is being enqueued sees them, handed to `launch` in the type of their kernels: TerrainArgs
+// with a heightfield in a slot, ShapeArgs with analytic shapes alone, CollisionArgs with the level-set object alone, NoCollision without any.
+// One pose per installed collider, all at the one clock's current time T (the start of the substep), by value; a running clock then moves
+// on, T = T + dt in one float32 addition (the drivers' own cur_time += dt).  Called once per applied grid update - by the stand-alone
+// kernel's launch or by the fused carry-over's, never by both.
+template<class F>
+static void with_collider(mpm_ctx* ctx, float dt, F&& launch) {
+	if(!ctx->has_collision && !ctx->shape_count) {
+		launch(NoCollision {});
+		return;
+	}
+	const float T = ctx->collision.time;
+	TerrainArgs a {};
+	a.col.count		= ctx->shape_count;
+	a.col.has_field = ctx->has_collision ? 1 : 0;
+	if(ctx->has_collision) a.col.field = CollisionArgs {ctx->collision, collision_pose(ctx->collision, T)};
+	for(int i = 0; i < ctx->shape_count; ++i) {
+		a.col.slot[i] = ctx->shape[i];
+		if(a.col.slot[i].shape.kind) a.col.slot[i].pose = collision_pose(a.col.slot[i].obj, T);
+	}
+	for(int i = 0; i < kMaxShapes; ++i) a.hf[i] = ctx->hf[i];
+	if(ctx->collision_running) ctx->collision.time = T + dt;
+	if(ctx->hf_count)
+		launch(a);
+	else if(ctx->shape_count)
+		launch(a.col);
+	else
+		launch(a.col.field);
+}
+
 extern "C" {
 
 int mpm_default_config(int domain_bits, mpm_config* cfg) {
@@ -626,36 +656,6 @@ int mpm_initial_setup(mpm_ctx* ctx) {
 	return MPM_OK;
 }
 
-// The collision object as the grid update that is being enqueued sees it: the pose at the current time T (the start of the substep), by
-// value; a running clock then moves on, T = T + dt in one float32 addition (the drivers' own cur_time += dt).  Called once per
-// applied grid update - by the stand-alone kernel's launch or by the fused carry-over's, never by both.
-static CollisionArgs collision_tick(mpm_ctx* ctx, float dt) {
-	CollisionArgs a {ctx->collision, collision_pose(ctx->collision, ctx->collision.time)};
-	if(ctx->collision_running) ctx->collision.time = ctx->collision.time + dt;
-	return a;
-}
-// The same with analytic shapes installed: one pose per installed collider, all at the one clock's time T, which then advances once.
-static ShapeArgs shapes_tick(mpm_ctx* ctx, float dt) {
-	ShapeArgs a {};
-	const float T = ctx->collision.time;
-	a.count		  = ctx->shape_count;
-	a.has_field	  = ctx->has_collision ? 1 : 0;
-	if(ctx->has_collision) a.field = CollisionArgs {ctx->collision, collision_pose(ctx->collision, T)};
-	for(int i = 0; i < ctx->shape_count; ++i) {
-		a.slot[i] = ctx->shape[i];
-		if(a.slot[i].shape.kind) a.slot[i].pose = collision_pose(a.slot[i].obj, T);
-	}
-	if(ctx->collision_running) ctx->collision.time = T + dt;
-	return a;
-}
-// The same with a heightfield in a slot: shapes_tick's arguments (one pose per collider, the clock advanced once) and the tables beside them.
-static TerrainArgs terrain_tick(mpm_ctx* ctx, float dt) {
-	TerrainArgs a {};
-	a.col = shapes_tick(ctx, dt);
-	for(int i = 0; i < kMaxShapes; ++i) a.hf[i] = ctx->hf[i];
-	return a;
-}
-
 // grid-update phase, gmpm_simulator.cuh:326-347
 static int launch_grid_update(mpm_ctx* ctx, float dt) {
 	hipStream_t s = ctx->s_compute;
@@ -668,14 +668,12 @@ static int launch_grid_update(mpm_ctx* ctx, float dt) {
 	HIP_TRY(hipMemsetAsync(ctx->d_maxvel, 0, sizeof(unsigned) * kMaxVelSlots * kMaxVelStride, s));
 	if(ctx->nbc) {
 		const int est = std::min(ctx->g.cap, ctx->nbc + ctx->nbc / 16 + 64);// (an estimate between two synchronisations of mpm_run_fixed)
-		if(ctx->hf_count)
-			grid_update_terrain_kernel<<<cdiv(est, 4), 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, terrain_tick(ctx, dt), ctx->d_maxvel);
-		else if(ctx->shape_count)
-			grid_update_shapes_kernel<<<cdiv(est, 4), 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, shapes_tick(ctx, dt), ctx->d_maxvel);
-		else if(ctx->has_collision)
-			grid_update_collision_kernel<<<cdiv(est, 4), 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, collision_tick(ctx, dt), ctx->d_maxvel);
-		else
-			grid_update_kernel<<<cdiv(est, 16), 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, ctx->d_maxvel);
+		with_collider(ctx, dt, [&](const auto& col) {
+			if constexpr(std::is_same_v<std::decay_t<decltype(col)>, NoCollision>)
+				grid_update_kernel<<<cdiv(est, 16), 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, ctx->d_maxvel);
+			else
+				grid_update_collider_kernel<<<cdiv(est, 4), 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, col, ctx->d_maxvel);
+		});
 	}
 	return MPM_OK;
 }
@@ -896,14 +894,9 @@ static int launch_rebuild(mpm_ctx* ctx, float fuse_dt = 0.f, bool without_prepar
 	const unsigned rg8 = std::max(1u, std::min(4096u, cdiv((size_t) ebc_est * 8, 256))), rg32 = std::max(1u, std::min(8192u, cdiv((size_t) ebc_est * 32, 256)));
 	register_blocks_kernel<0, 1><<<rg8, 256, 0, s>>>(g, &st[ST_CNT_P], nullptr, &st[ST_CNT_N], &st[ST_PBC], Pn.table, Pn.keys, st, still);
 	if(fused) {
-		if(ctx->hf_count)
-			carry_grid_terrain_kernel<<<2048, 256, 0, s>>>(g, st, Pn.keys, Pr.table, ctx->grid[1], ctx->grid[0], fuse_dt, ctx->d_maxvel, terrain_tick(ctx, fuse_dt));
-		else if(ctx->shape_count)
-			carry_grid_shapes_kernel<<<2048, 256, 0, s>>>(g, st, Pn.keys, Pr.table, ctx->grid[1], ctx->grid[0], fuse_dt, ctx->d_maxvel, shapes_tick(ctx, fuse_dt));
-		else if(ctx->has_collision)
-			carry_grid_kernel<true, true><<<2048, 256, 0, s>>>(g, st, Pn.keys, Pr.table, ctx->grid[1], ctx->grid[0], fuse_dt, ctx->d_maxvel, collision_tick(ctx, fuse_dt));
-		else
-			carry_grid_kernel<true><<<2048, 256, 0, s>>>(g, st, Pn.keys, Pr.table, ctx->grid[1], ctx->grid[0], fuse_dt, ctx->d_maxvel, NoCollision {});
+		with_collider(ctx, fuse_dt, [&](const auto& col) {
+			carry_grid_kernel<true, std::decay_t<decltype(col)>><<<2048, 256, 0, s>>>(g, st, Pn.keys, Pr.table, ctx->grid[1], ctx->grid[0], fuse_dt, ctx->d_maxvel, col);
+		});
 		ctx->grid_preupdated = true;
 		ctx->preupdate_dt	 = fuse_dt;
 	} else
@@ -1962,21 +1955,26 @@ int mpm_test_stress(int material, const mpm_material_params* p, const float* F, 
 	return MPM_OK;
 }
 
+// The shared half of the two collider queries below: points up, test_collision_query_kernel, four floats per point down
+static int test_collision_query(ShapeSlot c, const Heightfield& f, float time, const float* xyz, size_t n, float* out4) {
+	c.pose = collision_pose(c.obj, time);
+	DevScratch<float> dX, dO;
+	HIP_TRY0(dX.alloc(3 * n));
+	HIP_TRY0(dO.alloc(4 * n));
+	HIP_TRY0(hipMemcpy(dX.p, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
+	test_collision_query_kernel<<<cdiv(n, 256), 256>>>(c, f, n, dX.p, dO.p);
+	HIP_TRY0(hipGetLastError());
+	HIP_TRY0(hipMemcpy(out4, dO.p, sizeof(float) * 4 * n, hipMemcpyDeviceToHost));
+	return MPM_OK;
+}
+
 int mpm_test_collision_shape(const mpm_collision_object* obj, const mpm_collision_shape* shape, float time, float dx, const float* xyz, size_t n, float* out4, int device) {
 	(void) dx;// (positions are domain points already; kept for the call shape of the grid kernels)
 	if(!obj || !shape || !xyz || !out4 || n == 0) return MPM_ERR_INVALID;
 	ShapeSlot c {};
 	if(make_shape_slot(obj, shape, c)) return MPM_ERR_INVALID;
-	c.pose = collision_pose(c.obj, time);
 	HIP_TRY0(hipSetDevice(device));
-	DevScratch<float> dX, dO;
-	HIP_TRY0(dX.alloc(3 * n));
-	HIP_TRY0(dO.alloc(4 * n));
-	HIP_TRY0(hipMemcpy(dX.p, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
-	test_collision_shape_kernel<<<cdiv(n, 256), 256>>>(c, n, dX.p, dO.p);
-	HIP_TRY0(hipGetLastError());
-	HIP_TRY0(hipMemcpy(out4, dO.p, sizeof(float) * 4 * n, hipMemcpyDeviceToHost));
-	return MPM_OK;
+	return test_collision_query(c, Heightfield {}, time, xyz, n, out4);
 }
 
 int mpm_test_collision_heightfield(const mpm_collision_object* obj, const mpm_heightfield* hf, const float* heights, float time, const float* xyz, size_t n, float* out4, int device) {
@@ -1987,20 +1985,12 @@ int mpm_test_collision_heightfield(const mpm_collision_object* obj, const mpm_he
 	const size_t cells = (size_t) f.nx * f.nz;
 	std::vector<float4> table(cells);
 	if(!heightfield_build(heights, f.nx, f.nz, f.spacing, table.data())) return MPM_ERR_INVALID;
-	c.pose = collision_pose(c.obj, time);
 	HIP_TRY0(hipSetDevice(device));
-	DevScratch<float> dX, dO;
 	DevScratch<float4> dT;
-	HIP_TRY0(dX.alloc(3 * n));
-	HIP_TRY0(dO.alloc(4 * n));
 	HIP_TRY0(dT.alloc(cells));
-	HIP_TRY0(hipMemcpy(dX.p, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
 	HIP_TRY0(hipMemcpy(dT.p, table.data(), sizeof(float4) * cells, hipMemcpyHostToDevice));
 	f.table = dT.p;
-	test_collision_heightfield_kernel<<<cdiv(n, 256), 256>>>(c, f, n, dX.p, dO.p);
-	HIP_TRY0(hipGetLastError());
-	HIP_TRY0(hipMemcpy(out4, dO.p, sizeof(float) * 4 * n, hipMemcpyDeviceToHost));
-	return MPM_OK;
+	return test_collision_query(c, f, time, xyz, n, out4);
 }
 
 int mpm_streams(mpm_ctx* ctx, void** compute_stream, void** comm_stream) {

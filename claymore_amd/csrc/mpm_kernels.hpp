@@ -308,16 +308,45 @@ __global__ __launch_bounds__(256) void grid_update_kernel(GridCfg cfg, const int
 	}
 }
 
-// Grid update with a level-set collision object (second update_grid_velocity_query_max overload,
-// Projects/MGSP/mgmpm_kernels.cuh:323-399): lane = cell.  Reports the reference's doubled |v|^2 (vel.dot(vel) followed by the
-// three += of the plain overload, :365-373).  The object and its pose at the time of this update travel by value.
+// Grid update with a collider (the level-set collision object; analytic shapes and heightfields: extensions).  The kinds differ in what
+// travels by value to the kernel - CollisionArgs, ShapeArgs, TerrainArgs - and in the grid_cell overload that treats one cell with it; the
+// two frames around a cell (grid_update_collider_kernel here, carry_grid_kernel behind the rebuild's kernels) are written once.
+//
+// Level-set collision object (second update_grid_velocity_query_max overload, Projects/MGSP/mgmpm_kernels.cuh:323-399): reports the
+// reference's doubled |v|^2 (vel.dot(vel) followed by the three += of the plain overload, :365-373).  The object and its pose at the
+// time of this update travel by value.
 struct CollisionArgs {
 	CollisionObject obj;
 	CollisionPose pose;
 };
 struct NoCollision {};
-// The two ends every collision variant of the per-cell update shares (grid_cell_collision, grid_cell_shapes, grid_cell_terrain), so that a
-// change is made once.  Prologue: momentum -> velocity with the walls' zeroes and gravity, and the cell's node coordinates.
+// Analytic collision shapes (mpm_collision_shapes.hpp): per massed cell walls and gravity, then the level-set object if one is installed,
+// then slots 0 .. 3 in order, each acting on the velocity the previous collider left.  Everything travels by value: count, has_field and
+// the kinds are wave-uniform (scalar compares); the slot loop is a real loop (#pragma nounroll) that reads the slot it is at from the
+// kernel arguments - no runtime-indexed private copy.  Reports the collision kernels' doubled |v|^2 of the final velocity.
+struct ShapeSlot {
+	CollisionObject obj;// (obj.field unused)
+	CollisionPose pose;
+	CollisionShape shape;// kind 0: an empty slot
+};
+struct ShapeArgs {
+	int count;	  // slots [0, count) are looked at
+	int has_field;// the level-set object in `field` acts first
+	CollisionArgs field;
+	ShapeSlot slot[kMaxShapes];
+};
+// A heightfield in at least one slot (mpm_collision_heightfield.hpp): a slot whose shape.kind is kShapeHeightfield (a number
+// mpm_set_collision_shape refuses) reads hf[slot]: the table pointer and its dimensions travel by value beside the slot, shape.inside_out
+// is the heightfield's.  The kind is wave-uniform (a scalar branch); the four corner loads are read-only float4 gathers, in range by
+// heightfield_query's own check.  A context without a heightfield passes ShapeArgs, whose code has no such branch.
+constexpr int kShapeHeightfield = 5;
+struct TerrainArgs {
+	ShapeArgs col;
+	Heightfield hf[kMaxShapes];
+};
+
+// The two ends every grid_cell overload shares, so that a change is made once.  Prologue: momentum -> velocity with the walls' zeroes and
+// gravity, and the cell's node coordinates.
 MPM_DEV void grid_cell_walls_gravity(const GridCfg& cfg, int kx, int ky, int kz, int cell, float dt, const float4& v, float (&vel)[3], int (&node)[3]) {
 #pragma clang fp contract(off)
 	const bool wx = kx < cfg.boundary || kx >= cfg.G - cfg.boundary;
@@ -355,8 +384,8 @@ MPM_DEV void wave_max_vel(float vel_sqr, unsigned* __restrict__ max_vel_bits) {
 	}
 }
 // One cell with mass: v = {mass, momentum} in, {mass, velocity} out; returns the cell's (doubled) |v|^2.  Shared by the stand-alone
-// kernel and the fused carry-over, so that both are the same statements on the same data.
-MPM_DEV float grid_cell_collision(const GridCfg& cfg, const CollisionArgs& col, int kx, int ky, int kz, int cell, float dt, float4& v) {
+// frame and the carry-over, so that both are the same statements on the same data.
+MPM_DEV float grid_cell(const GridCfg& cfg, const CollisionArgs& col, int kx, int ky, int kz, int cell, float dt, float4& v) {
 #pragma clang fp contract(off)
 	float vel[3];
 	int node[3];
@@ -364,118 +393,15 @@ MPM_DEV float grid_cell_collision(const GridCfg& cfg, const CollisionArgs& col, 
 	collision_resolve(col.obj, col.pose, node, cfg.dx, cfg.G * 4, (float) cfg.boundary * cfg.dx * 4.f, (float) (cfg.G - cfg.boundary) * 4.f * cfg.dx, vel);
 	return grid_cell_store_doubled_q(vel, v);
 }
-// One wave per grid block; the kernel of the phase-level callers (mpm_grid_update, mpm_substep, the first substep of a run): between
-// the substeps of a run the update rides on the carry-over (carry_grid_kernel<true, true>).
-__global__ __launch_bounds__(256) void grid_update_collision_kernel(GridCfg cfg, const int* __restrict__ nbc_ptr, float* __restrict__ grid, const int* __restrict__ keys, float dt, CollisionArgs col, unsigned* __restrict__ max_vel_bits) {
-	const int cell	  = threadIdx.x & 63;
-	const int nblocks = min(*nbc_ptr, cfg.cap);
-	float vel_sqr	  = 0.f;
-	for(int blockno = (blockIdx.x * 256 + threadIdx.x) >> 6; blockno < nblocks; blockno += gridDim.x * 4) {
-		const int kx = keys[3 * blockno], ky = keys[3 * blockno + 1], kz = keys[3 * blockno + 2];
-		float* g	 = grid + (size_t) blockno * 256 + cell;
-		float4 v	 = {g[0], 0.f, 0.f, 0.f};
-		if(v.x > 0.0f) {
-			v.y = g[64];
-			v.z = g[128];
-			v.w = g[192];
-			vel_sqr = fmaxf(vel_sqr, grid_cell_collision(cfg, col, kx, ky, kz, cell, dt, v));
-			g[64]	= v.y;
-			g[128]	= v.z;
-			g[192]	= v.w;
-		}
-	}
-#pragma unroll
-	for(int off = 32; off > 0; off >>= 1) vel_sqr = fmaxf(vel_sqr, __shfl_xor(vel_sqr, off));
-	if((threadIdx.x & 63) == 0 && vel_sqr > 0.f) {
-		const unsigned bits = __float_as_uint(vel_sqr);
-		unsigned* slot		= max_vel_bits + (blockIdx.x & (kMaxVelSlots - 1)) * kMaxVelStride;
-		if(bits > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, bits);
-	}
-}
-
-// Grid update with analytic collision shapes (mpm_collision_shapes.hpp; an extension): per massed cell walls and gravity, then the level-set
-// object if one is installed, then slots 0 .. 3 in order, each acting on the velocity the previous collider left.  Everything travels by
-// value: count, has_field and the kinds are wave-uniform (scalar compares), and the slot loop is unrolled over the kernel arguments - no
-// runtime-indexed private copy.  Reports the collision kernels' doubled |v|^2 of the final velocity.
-struct ShapeSlot {
-	CollisionObject obj;// (obj.field unused)
-	CollisionPose pose;
-	CollisionShape shape;// kind 0: an empty slot
-};
-struct ShapeArgs {
-	int count;	  // slots [0, count) are looked at
-	int has_field;// the level-set object in `field` acts first
-	CollisionArgs field;
-	ShapeSlot slot[kMaxShapes];
-};
-// grid_cell_collision's prologue + the optional field object + the slot loop; the same statements in the stand-alone kernel and the carry-over
-MPM_DEV float grid_cell_shapes(const GridCfg& cfg, const ShapeArgs& col, int kx, int ky, int kz, int cell, float dt, float4& v) {
+// The same for ShapeArgs and for TerrainArgs, one function: the prologue + the optional field object + the slot loop.  The heightfield branch
+// is compiled in for TerrainArgs alone (no run-time test of a table pointer), so without a heightfield the code is that of the analytic shapes.
+MPM_DEV const ShapeArgs& shape_args(const ShapeArgs& a) { return a; }
+MPM_DEV const ShapeArgs& shape_args(const TerrainArgs& a) { return a.col; }
+template<class Args>
+MPM_DEV float grid_cell(const GridCfg& cfg, const Args& a, int kx, int ky, int kz, int cell, float dt, float4& v) {
 #pragma clang fp contract(off)
-	float vel[3];
-	int node[3];
-	grid_cell_walls_gravity(cfg, kx, ky, kz, cell, dt, v, vel, node);
-	if(col.has_field) collision_resolve(col.field.obj, col.field.pose, node, cfg.dx, cfg.G * 4, (float) cfg.boundary * cfg.dx * 4.f, (float) (cfg.G - cfg.boundary) * 4.f * cfg.dx, vel);
-	const float X[3] = {(float) node[0] * cfg.dx, (float) node[1] * cfg.dx, (float) node[2] * cfg.dx};
-#pragma nounroll
-	for(int s = 0; s < col.count; ++s)
-		if(col.slot[s].shape.kind != 0) shape_resolve(col.slot[s].obj, col.slot[s].pose, col.slot[s].shape, X, vel);
-	return grid_cell_store_doubled_q(vel, v);
-}
-// grid_update_collision_kernel's frame (one wave per grid block, lane = cell) around grid_cell_shapes: the kernel of the phase-level callers
-__global__ __launch_bounds__(256) void grid_update_shapes_kernel(GridCfg cfg, const int* __restrict__ nbc_ptr, float* __restrict__ grid, const int* __restrict__ keys, float dt, ShapeArgs col, unsigned* __restrict__ max_vel_bits) {
-	const int cell	  = threadIdx.x & 63;
-	const int nblocks = min(*nbc_ptr, cfg.cap);
-	float vel_sqr	  = 0.f;
-	for(int blockno = (blockIdx.x * 256 + threadIdx.x) >> 6; blockno < nblocks; blockno += gridDim.x * 4) {
-		const int kx = keys[3 * blockno], ky = keys[3 * blockno + 1], kz = keys[3 * blockno + 2];
-		float* g	 = grid + (size_t) blockno * 256 + cell;
-		float4 v	 = {g[0], 0.f, 0.f, 0.f};
-		if(v.x > 0.0f) {
-			v.y = g[64];
-			v.z = g[128];
-			v.w = g[192];
-			vel_sqr = fmaxf(vel_sqr, grid_cell_shapes(cfg, col, kx, ky, kz, cell, dt, v));
-			g[64]	= v.y;
-			g[128]	= v.z;
-			g[192]	= v.w;
-		}
-	}
-#pragma unroll
-	for(int off = 32; off > 0; off >>= 1) vel_sqr = fmaxf(vel_sqr, __shfl_xor(vel_sqr, off));
-	if((threadIdx.x & 63) == 0 && vel_sqr > 0.f) {
-		const unsigned bits = __float_as_uint(vel_sqr);
-		unsigned* slot		= max_vel_bits + (blockIdx.x & (kMaxVelSlots - 1)) * kMaxVelStride;
-		if(bits > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, bits);
-	}
-}
-// mpm_test_collision_shape: material point, signed distance and normal of one collider at arbitrary domain points
-__global__ void test_collision_shape_kernel(ShapeSlot c, size_t n, const float* __restrict__ xyz, float* __restrict__ out4) {
-	const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
-	if(i >= n) return;
-	const float X[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
-	float xmt[3], x[3], nrm[3], sdis;
-	collision_material_point(c.obj, c.pose, X, xmt, x);
-	shape_query(c.shape, x, sdis, nrm);
-	out4[4 * i]		= sdis;
-	out4[4 * i + 1] = nrm[0];
-	out4[4 * i + 2] = nrm[1];
-	out4[4 * i + 3] = nrm[2];
-}
-
-// Grid update with a heightfield in at least one slot (mpm_collision_heightfield.hpp; an extension).  grid_update_shapes_kernel and
-// carry_grid_shapes_kernel keep their arguments and their code - a context without a heightfield launches them as before -; these are their
-// twins with one more collider kind.  A slot whose shape.kind is kShapeHeightfield (a number mpm_set_collision_shape refuses) reads
-// hf[slot]: the table pointer and its dimensions travel by value beside the slot, shape.inside_out is the heightfield's.  The kind is
-// wave-uniform (a scalar branch); the four corner loads are read-only float4 gathers, in range by heightfield_query's own check.
-constexpr int kShapeHeightfield = 5;
-struct TerrainArgs {
-	ShapeArgs col;
-	Heightfield hf[kMaxShapes];
-};
-// grid_cell_shapes plus the heightfield branch; the same statements in the stand-alone kernel and the carry-over
-MPM_DEV float grid_cell_terrain(const GridCfg& cfg, const TerrainArgs& ter, int kx, int ky, int kz, int cell, float dt, float4& v) {
-#pragma clang fp contract(off)
-	const ShapeArgs& col = ter.col;
+	static_assert(std::is_same_v<Args, ShapeArgs> || std::is_same_v<Args, TerrainArgs>, "a collider kind needs its grid_cell");
+	const ShapeArgs& col = shape_args(a);
 	float vel[3];
 	int node[3];
 	grid_cell_walls_gravity(cfg, kx, ky, kz, cell, dt, v, vel, node);
@@ -483,15 +409,19 @@ MPM_DEV float grid_cell_terrain(const GridCfg& cfg, const TerrainArgs& ter, int 
 	const float X[3] = {(float) node[0] * cfg.dx, (float) node[1] * cfg.dx, (float) node[2] * cfg.dx};
 #pragma nounroll
 	for(int s = 0; s < col.count; ++s) {
-		if(col.slot[s].shape.kind == kShapeHeightfield)
-			heightfield_resolve(col.slot[s].obj, col.slot[s].pose, ter.hf[s], X, vel);
-		else if(col.slot[s].shape.kind != 0)
-			shape_resolve(col.slot[s].obj, col.slot[s].pose, col.slot[s].shape, X, vel);
+		if constexpr(std::is_same_v<Args, TerrainArgs>)
+			if(col.slot[s].shape.kind == kShapeHeightfield) {
+				heightfield_resolve(col.slot[s].obj, col.slot[s].pose, a.hf[s], X, vel);
+				continue;
+			}
+		if(col.slot[s].shape.kind != 0) shape_resolve(col.slot[s].obj, col.slot[s].pose, col.slot[s].shape, X, vel);
 	}
 	return grid_cell_store_doubled_q(vel, v);
 }
-// grid_update_shapes_kernel's frame (one wave per grid block, lane = cell) around grid_cell_terrain: the kernel of the phase-level callers
-__global__ __launch_bounds__(256) void grid_update_terrain_kernel(GridCfg cfg, const int* __restrict__ nbc_ptr, float* __restrict__ grid, const int* __restrict__ keys, float dt, TerrainArgs ter, unsigned* __restrict__ max_vel_bits) {
+// The stand-alone frame: one wave per grid block, lane = cell.  The kernel of the phase-level callers (mpm_grid_update, mpm_substep, the
+// first substep of a run): between the substeps of a run the update rides on the carry-over (carry_grid_kernel<true, Collider>).
+template<class Collider>
+__global__ __launch_bounds__(256) void grid_update_collider_kernel(GridCfg cfg, const int* __restrict__ nbc_ptr, float* __restrict__ grid, const int* __restrict__ keys, float dt, Collider col, unsigned* __restrict__ max_vel_bits) {
 	const int cell	  = threadIdx.x & 63;
 	const int nblocks = min(*nbc_ptr, cfg.cap);
 	float vel_sqr	  = 0.f;
@@ -503,7 +433,7 @@ __global__ __launch_bounds__(256) void grid_update_terrain_kernel(GridCfg cfg, c
 			v.y = g[64];
 			v.z = g[128];
 			v.w = g[192];
-			vel_sqr = fmaxf(vel_sqr, grid_cell_terrain(cfg, ter, kx, ky, kz, cell, dt, v));
+			vel_sqr = fmaxf(vel_sqr, grid_cell(cfg, col, kx, ky, kz, cell, dt, v));
 			g[64]	= v.y;
 			g[128]	= v.z;
 			g[192]	= v.w;
@@ -511,14 +441,18 @@ __global__ __launch_bounds__(256) void grid_update_terrain_kernel(GridCfg cfg, c
 	}
 	wave_max_vel(vel_sqr, max_vel_bits);
 }
-// mpm_test_collision_heightfield: signed distance and normal of one heightfield at arbitrary domain points
-__global__ void test_collision_heightfield_kernel(ShapeSlot c, Heightfield f, size_t n, const float* __restrict__ xyz, float* __restrict__ out4) {
+// mpm_test_collision_shape, mpm_test_collision_heightfield: signed distance and normal of one collider (a heightfield where the slot's kind
+// says so, with its table in f) at arbitrary domain points, through the collider's material point
+__global__ void test_collision_query_kernel(ShapeSlot c, Heightfield f, size_t n, const float* __restrict__ xyz, float* __restrict__ out4) {
 	const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
 	if(i >= n) return;
 	const float X[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
 	float xmt[3], x[3], nrm[3], sdis;
 	collision_material_point(c.obj, c.pose, X, xmt, x);
-	heightfield_query(f, x, sdis, nrm);
+	if(c.shape.kind == kShapeHeightfield)
+		heightfield_query(f, x, sdis, nrm);
+	else
+		shape_query(c.shape, x, sdis, nrm);
 	out4[4 * i]		= sdis;
 	out4[4 * i + 1] = nrm[0];
 	out4[4 * i + 2] = nrm[1];
@@ -1091,61 +1025,6 @@ __global__ __launch_bounds__(256) void register_blocks_kernel(GridCfg cfg, const
 	}
 }
 
-// carry_grid_kernel<true, true>'s frame (below) around grid_cell_shapes: the grid update with analytic shapes riding on the carry-over between
-// the substeps of a run.  A kernel of its own, so that carry_grid_kernel keeps its template parameters and its code.
-__global__ __launch_bounds__(256) void carry_grid_shapes_kernel(GridCfg cfg, const int* __restrict__ status, const int* __restrict__ new_keys, const int* __restrict__ old_table, const float* __restrict__ p2g_grid, float* __restrict__ grid, float dt, unsigned* __restrict__ max_vel_bits, ShapeArgs col) {
-	const int nbc	  = min(status[ST_CNT_P] + status[ST_CNT_N], cfg.cap);
-	const int old_nbc = min(status[ST_NBC], cfg.cap);
-	const int lane = threadIdx.x & 63;
-	float vel_sqr  = 0.f;
-	for(int nb = blockIdx.x * 4 + (threadIdx.x >> 6); nb < nbc; nb += gridDim.x * 4) {
-		const int kx = new_keys[3 * nb], ky = new_keys[3 * nb + 1], kz = new_keys[3 * nb + 2];
-		const int old = table_query(cfg, old_table, kx, ky, kz);
-		float4 v	  = {0.f, 0.f, 0.f, 0.f};
-		if(old >= 0 && old < old_nbc) {
-			const float* s = p2g_grid + (size_t) old * 256;
-			v			   = {s[lane], s[64 + lane], s[128 + lane], s[192 + lane]};
-		}
-		if(v.x > 0.0f) vel_sqr = fmaxf(vel_sqr, grid_cell_shapes(cfg, col, kx, ky, kz, lane, dt, v));
-		float* d	  = grid + (size_t) nb * 256;
-		d[lane]		  = v.x;
-		d[64 + lane]  = v.y;
-		d[128 + lane] = v.z;
-		d[192 + lane] = v.w;
-	}
-#pragma unroll
-	for(int off = 32; off > 0; off >>= 1) vel_sqr = fmaxf(vel_sqr, __shfl_xor(vel_sqr, off));
-	if(lane == 0 && vel_sqr > 0.f) {
-		const unsigned bits = __float_as_uint(vel_sqr);
-		unsigned* slot		= max_vel_bits + (blockIdx.x & (kMaxVelSlots - 1)) * kMaxVelStride;
-		if(bits > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, bits);
-	}
-}
-
-// carry_grid_shapes_kernel's frame around grid_cell_terrain: the grid update with a heightfield in a slot riding on the carry-over
-__global__ __launch_bounds__(256) void carry_grid_terrain_kernel(GridCfg cfg, const int* __restrict__ status, const int* __restrict__ new_keys, const int* __restrict__ old_table, const float* __restrict__ p2g_grid, float* __restrict__ grid, float dt, unsigned* __restrict__ max_vel_bits, TerrainArgs ter) {
-	const int nbc	  = min(status[ST_CNT_P] + status[ST_CNT_N], cfg.cap);
-	const int old_nbc = min(status[ST_NBC], cfg.cap);
-	const int lane = threadIdx.x & 63;
-	float vel_sqr  = 0.f;
-	for(int nb = blockIdx.x * 4 + (threadIdx.x >> 6); nb < nbc; nb += gridDim.x * 4) {
-		const int kx = new_keys[3 * nb], ky = new_keys[3 * nb + 1], kz = new_keys[3 * nb + 2];
-		const int old = table_query(cfg, old_table, kx, ky, kz);
-		float4 v	  = {0.f, 0.f, 0.f, 0.f};
-		if(old >= 0 && old < old_nbc) {
-			const float* s = p2g_grid + (size_t) old * 256;
-			v			   = {s[lane], s[64 + lane], s[128 + lane], s[192 + lane]};
-		}
-		if(v.x > 0.0f) vel_sqr = fmaxf(vel_sqr, grid_cell_terrain(cfg, ter, kx, ky, kz, lane, dt, v));
-		float* d	  = grid + (size_t) nb * 256;
-		d[lane]		  = v.x;
-		d[64 + lane]  = v.y;
-		d[128 + lane] = v.z;
-		d[192 + lane] = v.w;
-	}
-	wave_max_vel(vel_sqr, max_vel_bits);
-}
-
 // Carry the P2G result (old numbering) into the current grid (new numbering): every NEW neighbour block is written
 // exactly once - copied from its old block if it existed, zero otherwise.  Replaces clear_grid +
 // mark_active_grid_blocks + copy_selected_grid_blocks (gmpm_simulator.cuh:436-446, :536-541).  One wave per block.
@@ -1154,10 +1033,11 @@ __global__ __launch_bounds__(256) void carry_grid_terrain_kernel(GridCfg cfg, co
 // grid.  Used between the substeps of mpm_run_fixed, where the next dt is known and nobody looks at the grid in between.
 // Runs between the neighbour and the exterior registration: the new neighbour count is the sum of the first two phase counters, the
 // published status[ST_NBC] is still the OLD one (the exterior registration publishes the new one).
-// COLLIDE (with UPDATE): the update is the collision object's (grid_cell_collision, the statements of grid_update_collision_kernel) with
-// the object and its pose in `col`; without it `col` is an empty struct and the kernel is the plain one, instruction for instruction.
-template<bool UPDATE, bool COLLIDE = false>
-__global__ __launch_bounds__(256) void carry_grid_kernel(GridCfg cfg, const int* __restrict__ status, const int* __restrict__ new_keys, const int* __restrict__ old_table, const float* __restrict__ p2g_grid, float* __restrict__ grid, float dt, unsigned* __restrict__ max_vel_bits, std::conditional_t<COLLIDE, CollisionArgs, NoCollision> col) {
+// Collider (with UPDATE) CollisionArgs, ShapeArgs or TerrainArgs: the update is that collider's (its grid_cell overload, the statements of
+// grid_update_collider_kernel<Collider>) with what it needs in `col`; NoCollision is an empty struct and the kernel is the plain one.
+template<bool UPDATE, class Collider = NoCollision>
+__global__ __launch_bounds__(256) void carry_grid_kernel(GridCfg cfg, const int* __restrict__ status, const int* __restrict__ new_keys, const int* __restrict__ old_table, const float* __restrict__ p2g_grid, float* __restrict__ grid, float dt, unsigned* __restrict__ max_vel_bits, Collider col) {
+	constexpr bool COLLIDE = !std::is_same_v<Collider, NoCollision>;
 	static_assert(UPDATE || !COLLIDE, "the collision object belongs to the grid update");
 	const int nbc	  = min(status[ST_CNT_P] + status[ST_CNT_N], cfg.cap);
 	const int old_nbc = min(status[ST_NBC], cfg.cap);
@@ -1172,7 +1052,7 @@ __global__ __launch_bounds__(256) void carry_grid_kernel(GridCfg cfg, const int*
 			v			   = {s[lane], s[64 + lane], s[128 + lane], s[192 + lane]};
 		}
 		if constexpr(COLLIDE) {
-			if(v.x > 0.0f) vel_sqr = fmaxf(vel_sqr, grid_cell_collision(cfg, col, kx, ky, kz, lane, dt, v));
+			if(v.x > 0.0f) vel_sqr = fmaxf(vel_sqr, grid_cell(cfg, col, kx, ky, kz, lane, dt, v));
 		} else if constexpr(UPDATE) {
 			if(v.x > 0.0f) {
 				const bool wx = kx < cfg.boundary || kx >= cfg.G - cfg.boundary;
@@ -1196,15 +1076,7 @@ __global__ __launch_bounds__(256) void carry_grid_kernel(GridCfg cfg, const int*
 		d[128 + lane] = v.z;
 		d[192 + lane] = v.w;
 	}
-	if constexpr(UPDATE) {
-#pragma unroll
-		for(int off = 32; off > 0; off >>= 1) vel_sqr = fmaxf(vel_sqr, __shfl_xor(vel_sqr, off));
-		if(lane == 0 && vel_sqr > 0.f) {
-			const unsigned bits = __float_as_uint(vel_sqr);
-			unsigned* slot		= max_vel_bits + (blockIdx.x & (kMaxVelSlots - 1)) * kMaxVelStride;
-			if(bits > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, bits);
-		}
-	}
+	if constexpr(UPDATE) wave_max_vel(vel_sqr, max_vel_bits);
 }
 
 // ------------------------------------------------------------------------------------------------------

@@ -214,7 +214,7 @@ def sample_field(c, N, dx):
 
 
 def grid_update(keys, G, boundary, gravity, dt, grid, colliders, t, dx, field=None):
-    """grid_cell_shapes over a whole grid: walls and gravity (the strict statements), the level-set object `field` = (collider, sdf, grad) if
+    """grid_cell(ShapeArgs) over a whole grid: walls and gravity (the strict statements), the level-set object `field` = (collider, sdf, grad) if
     given, then the colliders in order (None: an empty slot), all at time t.  -> live, the grid afterwards, the returned doubled maximum, and
     per collider the touched live cells (nbc, 64)."""
     live, out, _ = gm.plain(keys, G, boundary, gravity, dt, grid)

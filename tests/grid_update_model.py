@@ -2,7 +2,7 @@
 tests/test_grid_update_kernels_gpu.py.  Judged against the reference's golden cells in tests/test_grid_update_model_cpu.py, not against
 the kernels.
 
-The statements (grid_update_kernel, grid_cell_collision, carry_grid_kernel in claymore_amd/csrc/mpm_kernels.hpp; orc_grid_cell in
+The statements (grid_update_kernel, grid_cell(CollisionArgs), carry_grid_kernel in claymore_amd/csrc/mpm_kernels.hpp; orc_grid_cell in
 oracle/mpm_oracle.c) for a cell with mass m > 0 - IEEE '>': +0, -0, negative and NaN masses skip the cell, which then keeps all four
 channels bit for bit; FLT_MIN, denormals and +inf do not:
 
@@ -19,7 +19,7 @@ in float64 FROM THE VELOCITIES THE KERNEL WROTE and bounds the kernel's float32 
 sum roundings of non-negative terms; every intermediate is at most Q (up to its own rounding), so each rounding is at most 1/2 ulp32(Q):
 |q - Q| <= 2.5 ulp32(Q).  fmaxf, the shuffles and atomicMax on the bit patterns of non-negative floats are exact and monotone, so the
 maximum obeys the same bound: |ret - max Q| <= 2.5 ulp32(max Q) (PLAIN_MAX_ULPS).  A NaN q counts as +inf.
-The collision path is compiled with contraction off: its q is the float32 statement order of grid_cell_collision,
+The collision path is compiled with contraction off: its q is the float32 statement order of grid_cell(CollisionArgs),
 ((v0 v0 + v1 v1) + v2 v2) + v0 v0 + v1 v1 + v2 v2 (the reference's doubled |v|^2), bit for bit (collision_q32).
 
 NaNs.  IEEE 754 leaves sign and payload of a NaN that an operation produces (or propagates from two NaN operands) to the implementation;
@@ -139,7 +139,7 @@ def plain_q32(v0, v1, v2):
 
 
 def collision_q32(v0, v1, v2):
-    """grid_cell_collision's q: vel.dot(vel), then the three += of the plain overload; NaN -> +inf."""
+    """grid_cell(CollisionArgs)'s q: vel.dot(vel), then the three += of the plain overload; NaN -> +inf."""
     with np.errstate(all="ignore"):
         a, b, c = (v0 * v0).astype(np.float32), (v1 * v1).astype(np.float32), (v2 * v2).astype(np.float32)
         q = ((a + b).astype(np.float32) + c).astype(np.float32)

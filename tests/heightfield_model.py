@@ -91,7 +91,7 @@ def resolve(c, t, X, vel):
 
 
 def grid_update(keys, G, boundary, gravity, dt, grid, colliders, t, dx, field=None):
-    """grid_cell_terrain over a whole grid: collision_shape_model.grid_update with shape and heightfield colliders mixed in slot order.
+    """grid_cell(TerrainArgs) over a whole grid: collision_shape_model.grid_update with shape and heightfield colliders mixed in slot order.
     -> live, the grid afterwards, the returned doubled maximum, and per collider (the field first) the touched live cells (nbc, 64)."""
     live, out, _ = gm.plain(keys, G, boundary, gravity, dt, grid)
     out = out.copy()

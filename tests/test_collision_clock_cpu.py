@@ -1,5 +1,6 @@
 """Moving collision object, CPU side: the clock's ABI surface, the `sphere_through_block` scene on the oracle, the pose / per-node split of
-claymore_amd/csrc/mpm_collision.hpp on x86 against the oracle's detect_and_resolve_collision, and the ISA of the fused carry-over."""
+claymore_amd/csrc/mpm_collision.hpp on x86 against the oracle's detect_and_resolve_collision.  (The ISA of the fused carry-over:
+tests/test_grid_update_isa.py.)"""
 import ctypes as C
 import os
 import re
@@ -150,30 +151,3 @@ def test_pose_split_matches_the_oracle_on_g14(host_collision):
     finally:
         api.destroy(ctx)
     assert moving == 6
-
-
-@pytest.fixture(scope="module")
-def device_asm(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("isa") / "claymore_hip.s")
-    flags = [f for f in entry.HIP_FLAGS if f not in ("-shared", "-fPIC")]
-    cmd = [entry.HIPCC] + flags + ["--offload-device-only", "-S", "-o", out, os.path.join(entry.CSRC, "claymore_hip.hip")]
-    r = subprocess.run(cmd, cwd=entry.CSRC, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return open(out).read().splitlines()
-
-
-def test_collision_grid_kernels_use_no_scratch_and_the_plain_carry_keeps_its_registers(device_asm):
-    """The fused carry-over with a collision object (carry_grid_kernel<true, true>) and the stand-alone grid_update_collision_kernel: no
-    scratch segment, no scratch instruction, and registers for at least six waves per SIMD (<= 80 VGPRs; the per-node sinf / cosf version
-    of the stand-alone kernel needed 81).  The plain carry_grid_kernel<true> keeps the 22 VGPRs it had before it shared a template."""
-    from test_isa_invariants import directive, instr, kernel_body
-    names = {"carry+collision": "_ZN3mpm17carry_grid_kernelILb1ELb1EE", "stand-alone": "_ZN3mpm28grid_update_collision_kernelE", "carry": "_ZN3mpm17carry_grid_kernelILb1ELb0EE"}
-    for kind, sym in names.items():
-        body = kernel_body(device_asm, sym)
-        vgpr = directive(body, ".amdhsa_next_free_vgpr")
-        print(kind, "vgpr", vgpr, "sgpr", directive(body, ".amdhsa_next_free_sgpr"), "scratch", directive(body, ".amdhsa_private_segment_fixed_size"))
-        assert directive(body, ".amdhsa_private_segment_fixed_size") == 0, kind
-        assert not any(instr(l).startswith("scratch_") for l in body), kind
-        assert vgpr <= (22 if kind == "carry" else 80), (kind, vgpr)
-        if kind != "carry":                                                      # the pose comes from the host: no range reduction, no polynomial
-            assert not any("v_sin_f32" in l or "v_cos_f32" in l for l in body), kind

@@ -87,8 +87,8 @@ SPARSE_STEPS = 60
 @pytest.mark.parametrize("sync_interval", [1, None])
 @pytest.mark.parametrize("boundary", ["slip", "separate"])
 def test_run_fixed_equals_the_phase_level_loop_bit_for_bit(boundary, sync_interval):
-    """mpm_run_fixed(n) - every grid update but the first rides on the carry-over (carry_grid_kernel<true, true>), windowed - against the
-    same n substeps phase by phase (grid_update_collision_kernel), moving + turning + growing object: the same statements on the same data,
+    """mpm_run_fixed(n) - every grid update but the first rides on the carry-over (carry_grid_kernel<true, CollisionArgs>), windowed - against the
+    same n substeps phase by phase (grid_update_collider_kernel<CollisionArgs>), moving + turning + growing object: the same statements on the same data,
     positions equal bit for bit after matching.  The data are the same only where the engine is deterministic: on the dense block two
     phase-level runs of one scene already differ from each other in the last bits (float atomics in P2G; measured 3-8e-7), so the comparison runs on sparse_scene, whose two phase-level runs are
     required to be identical first; the dense block is compared below under the bound two runs of one scene have to meet."""

@@ -1,7 +1,7 @@
 """The heightfield collider, CPU side: the ABI surface, the x86 build of claymore_amd/csrc/mpm_collision_heightfield.hpp
 (tools/hostcheck/check_heightfield.cpp) against the float32 model of tests/heightfield_model.py bit for bit, that model against the float64
-closed form within a counted bound, a flat table against the half-space shape, the index arithmetic under a sanitizer in a stand-alone
-program, and the ISA of the two new grid kernels."""
+closed form within a counted bound, a flat table against the half-space shape, and the index arithmetic under a sanitizer in a stand-alone
+program.  (The ISA of the grid kernels: tests/test_grid_update_isa.py.)"""
 import ctypes as C
 import os
 import re
@@ -24,7 +24,6 @@ import __graft_entry__ as entry  # noqa: E402
 DX = sm.DX
 HOSTCHECK = os.path.join(ROOT, "tools", "hostcheck")
 TABLES = ("2x2", "5x3", "65x65", "33x17")
-VGPR_STEP = 80          # the occupancy step the two terrain kernels are built in (six waves per SIMD)
 
 
 def ptr(a):
@@ -253,22 +252,3 @@ def test_selftest_runs_clean_under_address_and_undefined_sanitizers(tmp_path):
                            "-I" + entry.CSRC, "-o", exe, os.path.join(HOSTCHECK, "heightfield_selftest.cpp")])
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "heightfield_selftest ok" in r.stdout, (r.returncode, r.stdout[-500:], r.stderr[-2000:])
-
-
-# ---- 6. the ISA of the new kernels -------------------------------------------------------------------------------------------------------------
-def test_terrain_grid_kernels_use_no_scratch_and_stay_in_their_occupancy_step():
-    """grid_update_terrain_kernel and carry_grid_terrain_kernel through their .amdhsa_ directives: private segment 0, and the VGPR count within
-    the occupancy step the built kernels land in (80: six waves per SIMD, the step of the shapes kernels).  Built: 72 / 75."""
-    from test_isa_invariants import directive, kernel_body
-    out = os.path.join(os.environ.get("TMPDIR", "/tmp"), f"claymore_terrain_isa_{os.getpid()}.s")
-    flags = [f for f in entry.HIP_FLAGS if f not in ("-shared", "-fPIC")]
-    r = subprocess.run([entry.HIPCC] + flags + ["--offload-device-only", "-S", "-o", out, os.path.join(entry.CSRC, "claymore_hip.hip")], cwd=entry.CSRC,
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    asm = open(out).read().splitlines()
-    os.remove(out)
-    for sym in ("_ZN3mpm26grid_update_terrain_kernelE", "_ZN3mpm25carry_grid_terrain_kernelE"):
-        body = kernel_body(asm, sym)
-        vgpr, scratch = directive(body, ".amdhsa_next_free_vgpr"), directive(body, ".amdhsa_private_segment_fixed_size")
-        print(sym, "vgpr", vgpr, "sgpr", directive(body, ".amdhsa_next_free_sgpr"), "private segment", scratch)
-        assert scratch == 0 and vgpr <= VGPR_STEP, (sym, vgpr, scratch)

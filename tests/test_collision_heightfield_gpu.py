@@ -1,4 +1,4 @@
-"""The heightfield collider on the GPU (claymore_amd/csrc/mpm_collision_heightfield.hpp; grid_update_terrain_kernel, carry_grid_terrain_kernel,
+"""The heightfield collider on the GPU (claymore_amd/csrc/mpm_collision_heightfield.hpp; grid_update_collider_kernel<TerrainArgs>, carry_grid_kernel<true, TerrainArgs>,
 mpm_test_collision_heightfield) against tests/heightfield_model.py, which tests/test_collision_heightfield_cpu.py judges on the CPU.  The grids
 are injected through the checkpoint port of tests/test_collision_shapes_gpu.py (its ShapeCtx): grid_update_model's 28-particle scene at bits 6
 with 222 neighbour blocks in all 27 wall classes, the generator's finite tier.  Every comparison with the model is on uint32 bit patterns;
@@ -106,7 +106,7 @@ def test_device_query_equals_the_model(name, moved, inside_out):
 @pytest.mark.parametrize("typ", sorted(TYPES))
 @pytest.mark.parametrize("name", sorted(TERRAINS))
 def test_cell_by_cell(ctx, name, typ, moved):
-    """grid_update_terrain_kernel with one heightfield (a seeded ramp plus bumps: 65 x 65 at spacing dx, and 81 x 81 at spacing 0.013) on a
+    """grid_update_collider_kernel<TerrainArgs> with one heightfield (a seeded ramp plus bumps: 65 x 65 at spacing dx, and 81 x 81 at spacing 0.013) on a
     generated grid: every velocity and the returned (doubled) maximum equal the model bit for bit.  On the model alone: the surface touches
     between 10 % and 90 % of the live cells and cuts interior and wall-zone blocks."""
     c = TERRAINS[name](moved, type=TYPES[typ], friction=0.3)
@@ -151,8 +151,8 @@ def test_heightfield_kernel_equals_the_level_set_kernel(ctx, typ):
 @pytest.mark.parametrize("typ", sorted(TYPES))
 @pytest.mark.parametrize("case", ["65x65-identity", "9x9-moved"])
 def test_flat_table_equals_the_halfspace_shape_kernel(ctx, case, typ):
-    """A table of constant height 32 dx against the shape halfspace(a = (., 32 dx, .), b = +y) on the whole grid: grid_update_terrain_kernel and
-    grid_update_shapes_kernel leave the same bits in every channel and return the same maximum.  65 x 65 samples on the nodes at identity
+    """A table of constant height 32 dx against the shape halfspace(a = (., 32 dx, .), b = +y) on the whole grid: grid_update_collider_kernel<TerrainArgs> and
+    grid_update_collider_kernel<ShapeArgs> leave the same bits in every channel and return the same maximum.  65 x 65 samples on the nodes at identity
     pose; 9 x 9 samples one unit apart about the domain at the moved pose (every node's material point lies in its footprint)."""
     cst, moved = np.float32(32 * DX), case.endswith("moved")
     mv = sm.MOVED if moved else {}
@@ -264,8 +264,8 @@ def run(sc, n, how):
 
 @pytest.mark.parametrize("sync_interval", [1, 8])
 def test_run_fixed_equals_the_phase_level_loop(sync_interval):
-    """mpm_run_fixed(n) - every grid update but the first rides on carry_grid_terrain_kernel - against grid update, g2p2g, rebuild phase by
-    phase (grid_update_terrain_kernel) with a moving terrain and a running clock, on the sparse scene and step count of
+    """mpm_run_fixed(n) - every grid update but the first rides on carry_grid_kernel<true, TerrainArgs> - against grid update, g2p2g, rebuild phase by
+    phase (grid_update_collider_kernel<TerrainArgs>) with a moving terrain and a running clock, on the sparse scene and step count of
     test_collision_clock_cpu: positions, the grid the run leaves behind and the clock bit for bit."""
     sc = sparse_terrain("slip")
     sc["config"]["sync_interval"] = sync_interval

@@ -1,6 +1,6 @@
 """Analytic collision shapes, CPU side: the ABI surface, the x86 build of claymore_amd/csrc/mpm_collision_shapes.hpp (tools/hostcheck/check_shapes.cpp)
 against the float32 model of tests/collision_shape_model.py bit for bit, that model's class against the float64 closed forms, the shape
-response against the oracle's level-set response on a field sampled from the model, and the ISA of the two new grid kernels."""
+response against the oracle's level-set response on a field sampled from the model.  (The ISA of the grid kernels: tests/test_grid_update_isa.py.)"""
 import ctypes as C
 import os
 import re
@@ -247,23 +247,3 @@ def test_shape_response_equals_the_oracles_level_set_response(host_shapes, oracl
         err = np.abs(got.astype(np.float64) - want).max() / max(1.0, np.abs(want).max())
         print(f"{name} type {typ} friction {friction}: max |shape - level set| = {err:.3e} (relative to max(1, |v|max))")
         assert err <= ROUND_BOUND, err
-
-
-# ---- 5. the ISA of the new kernels -------------------------------------------------------------------------------------------------------------
-def test_shape_grid_kernels_use_no_scratch_and_at_most_80_vgprs():
-    """grid_update_shapes_kernel and carry_grid_shapes_kernel through their .amdhsa_ directives: private segment 0 and <= 80 VGPRs (six waves
-    per SIMD, the budget of the level-set collision kernels; the slot loop is a real loop over the kernel arguments, so four slots cost the
-    registers of one).  Built: 72 / 74."""
-    from test_isa_invariants import directive, kernel_body
-    out = os.path.join(os.environ.get("TMPDIR", "/tmp"), f"claymore_shapes_isa_{os.getpid()}.s")
-    flags = [f for f in entry.HIP_FLAGS if f not in ("-shared", "-fPIC")]
-    r = subprocess.run([entry.HIPCC] + flags + ["--offload-device-only", "-S", "-o", out, os.path.join(entry.CSRC, "claymore_hip.hip")], cwd=entry.CSRC,
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    asm = open(out).read().splitlines()
-    os.remove(out)
-    for sym in ("_ZN3mpm25grid_update_shapes_kernelE", "_ZN3mpm24carry_grid_shapes_kernelE"):
-        body = kernel_body(asm, sym)
-        vgpr, scratch = directive(body, ".amdhsa_next_free_vgpr"), directive(body, ".amdhsa_private_segment_fixed_size")
-        print(sym, "vgpr", vgpr, "sgpr", directive(body, ".amdhsa_next_free_sgpr"), "private segment", scratch)
-        assert scratch == 0 and vgpr <= 80, (sym, vgpr, scratch)

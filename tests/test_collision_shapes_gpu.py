@@ -1,4 +1,4 @@
-"""Analytic collision shapes on the GPU (claymore_amd/csrc/mpm_collision_shapes.hpp; grid_update_shapes_kernel, carry_grid_shapes_kernel,
+"""Analytic collision shapes on the GPU (claymore_amd/csrc/mpm_collision_shapes.hpp; grid_update_collider_kernel<ShapeArgs>, carry_grid_kernel<true, ShapeArgs>,
 mpm_test_collision_shape) against tests/collision_shape_model.py, which tests/test_collision_shapes_cpu.py judges on the CPU.  The grids are
 injected through the checkpoint port of tests/test_grid_update_kernels_gpu.py: grid_update_model's 28-particle scene at bits 6 with 222
 neighbour blocks in all 27 wall classes, the generator's finite tier.  Every comparison with the model is on uint32 bit patterns; computed
@@ -12,8 +12,8 @@ tests named are the ones expected to fail, from reading the code:
   capsule clamp dropped (shape_capsule)                      ..._bit_for_bit[capsule-*] (the special points beyond both ends); test_cell_by_cell[capsule-*]
   box tie rule `>` -> `>=` (shape_box)                       ..._bit_for_bit[box-*] (nodes with |y - 32| == |z - 32|: the normal's axis); test_cell_by_cell[box-slip-*]
   `sdis < 0` instead of `<=` (shape_resolve)                 ..._bit_for_bit[halfspace-False-*], [box-False-*] (nodes ON the surface); test_cell_by_cell[halfspace-*-identity]
-  slot order reversed (grid_cell_shapes)                     test_slots_act_in_order (the two orders give the model's two different grids)
-  the clock advanced once per collider (shapes_tick)         test_run_fixed_equals_the_phase_level_loop (clock == the float32 sum of n dt) and
+  slot order reversed (grid_cell(ShapeArgs))                 test_slots_act_in_order (the two orders give the model's two different grids)
+  the clock advanced once per collider (with_collider)       test_run_fixed_equals_the_phase_level_loop (clock == the float32 sum of n dt) and
                                                              test_errors_and_the_clocks_book_keeping (two shapes, one grid update: T + dt)"""
 import ctypes as C
 import json
@@ -137,7 +137,7 @@ def test_device_query_equals_the_model(name, moved):
 @pytest.mark.parametrize("typ", sorted(TYPES))
 @pytest.mark.parametrize("name", sm.KIND_CASES)
 def test_cell_by_cell(ctx, name, typ, moved):
-    """grid_update_shapes_kernel with one shape on a generated grid: every velocity and the returned (doubled) maximum equal the model bit for
+    """grid_update_collider_kernel<ShapeArgs> with one shape on a generated grid: every velocity and the returned (doubled) maximum equal the model bit for
     bit; the shape cuts interior and wall-zone blocks and touches between 10 % and 90 % of the live cells (checked on the model)."""
     c = sm.make(name, moved, type=TYPES[typ], friction=0.3)
     t = sm.T_MOVED if moved else 0.0
@@ -160,7 +160,7 @@ def test_cell_by_cell(ctx, name, typ, moved):
 @pytest.mark.parametrize("name", ["halfspace", "box"])
 def test_shape_kernel_equals_the_level_set_kernel(ctx, name, typ):
     """The axis half-space and the box at identity pose on one injected grid: through mpm_set_collision_object with the field sampled from the
-    model (grid_update_collision_kernel) and through the shape (grid_update_shapes_kernel).  Bit-identical at the nodes inside query_sdf's box;
+    model (grid_update_collider_kernel<CollisionArgs>) and through the shape (grid_update_collider_kernel<ShapeArgs>).  Bit-identical at the nodes inside query_sdf's box;
     outside it the level set acts on nothing, the shape on every node - those cells equal the model."""
     c = sm.make(name, type=TYPES[typ], friction=0.3, trans_vel=(0.25, -0.5, 0.125), omega=(0.5, 1.0, -0.25))
     sdf, grad = sm.sample_field(c, N, DX)
@@ -285,8 +285,8 @@ def run(sc, n, how):
 @pytest.mark.parametrize("sync_interval", [1, 8])
 @pytest.mark.parametrize("boundary", ["slip", "separate"])
 def test_run_fixed_equals_the_phase_level_loop(boundary, sync_interval):
-    """mpm_run_fixed(n) - every grid update but the first rides on carry_grid_shapes_kernel - against grid update, g2p2g, rebuild phase by phase
-    (grid_update_shapes_kernel) with a moving, turning, growing analytic sphere and a running clock: positions, the grid the run leaves behind
+    """mpm_run_fixed(n) - every grid update but the first rides on carry_grid_kernel<true, ShapeArgs> - against grid update, g2p2g, rebuild phase by phase
+    (grid_update_collider_kernel<ShapeArgs>) with a moving, turning, growing analytic sphere and a running clock: positions, the grid the run leaves behind
     and the clock bit for bit."""
     sc = sparse_analytic(boundary=boundary, **MOTION)
     sc["config"]["sync_interval"] = sync_interval

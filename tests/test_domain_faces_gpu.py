@@ -122,7 +122,7 @@ def test_lower_face_materials_with_both_g2p2g_kernels(mask):
 
 @pytest.mark.parametrize("boundary", ["sticky", "slip", "separate"])
 def test_collision_object_in_a_wall_zone_corner(boundary):
-    """A level-set sphere in the x = 0 / y = 0 edge, a body against x = 0 falling onto it: grid_update_collision_kernel sees object nodes in
+    """A level-set sphere in the x = 0 / y = 0 edge, a body against x = 0 falling onto it: grid_update_collider_kernel<CollisionArgs> sees object nodes in
     wall-zone blocks (left to the slip walls) and next to them (resolved).  Positions after 80 substeps, the grid and its velocities node by
     node (velocities: the suite's bound beyond 10 substeps, test_parity_gpu.py::test_grid_velocity_parity_over_many_substeps)."""
     sc = F.corner_obstacle_scene(5, boundary)

@@ -1,5 +1,5 @@
-"""The grid-update kernels of claymore_amd/csrc/mpm_kernels.hpp cell by cell - grid_update_kernel, grid_update_collision_kernel and, through
-mpm_run_fixed, carry_grid_kernel<true, false> - on INJECTED grids against tests/grid_update_model.py, which tests/test_grid_update_model_cpu.py
+"""The grid-update kernels of claymore_amd/csrc/mpm_kernels.hpp cell by cell - grid_update_kernel, grid_update_collider_kernel<CollisionArgs> and, through
+mpm_run_fixed, carry_grid_kernel<true> - on INJECTED grids against tests/grid_update_model.py, which tests/test_grid_update_model_cpu.py
 judges against the reference's golden cells.  The injection port: mpm_checkpoint_load validates every index of a checkpoint and copies the grid
 section verbatim, so a checkpoint saved after set-up with its grid section overwritten (tests/ckpt_format.py) puts any bit pattern into any cell
 of any neighbour block; mpm_grid_update + mpm_dump_grid show what the kernel made of it.
@@ -18,11 +18,11 @@ built, no run of them has been made.  The tests each one is EXPECTED to fail, fr
   `m.c >= 0.0f`                                              test_plain_kernel_cell_by_cell (cells of mass +0 / -0 change)
   `q != q` test removed (grid_update_kernel)                 test_maximum_from_every_position (the NaN cell no longer gives +inf; the full tier of
                                                              test_plain_kernel_cell_by_cell still returns +inf from its overflowing cells)
-  `cell >> 4` <-> `cell & 3` in grid_cell_collision          test_collision_kernel_node_mapping, axes 0 and 2
+  `cell >> 4` <-> `cell & 3` in grid_cell(CollisionArgs)     test_collision_kernel_node_mapping, axes 0 and 2
   `nb < nbc - 1` in carry_grid_kernel                        test_run_fixed_equals_the_phase_level_loop_* through the grid the run leaves behind
-  the wall rule of carry_grid_kernel<true, false>            test_run_fixed_equals_the_phase_level_loop_in_the_wall_zones
+  the wall rule of carry_grid_kernel<true>                   test_run_fixed_equals_the_phase_level_loop_in_the_wall_zones
   (`wy` from `kx`; `>=` -> `>`)
-  `q != q` test removed in carry_grid_kernel<true, false>    expected to survive: a P2G result cannot be injected, and a NaN that arises in a run
+  `q != q` test removed in carry_grid_kernel<true>           expected to survive: a P2G result cannot be injected, and a NaN that arises in a run
                                                              reaches the stand-alone kernel's test first; no handle short of a new entry point"""
 import numpy as np
 import pytest
@@ -202,7 +202,7 @@ def test_maximum_from_every_position(ctxs, block):
 
 @pytest.mark.parametrize("block", [0, 1, 15, 16, -2, -1])
 def test_maximum_from_every_position_collision_kernel(ctxs, block):
-    """The same placement through grid_update_collision_kernel (lane = cell, four blocks per workgroup, nbc % 4 = 2: the last workgroup is half
+    """The same placement through grid_update_collider_kernel<CollisionArgs> (lane = cell, four blocks per workgroup, nbc % 4 = 2: the last workgroup is half
     idle) with the object that touches nothing: the returned maximum is the dominating cell's doubled |v|^2 in the strict float32 statement
     order, bit for bit; a NaN there gives +inf.  The trilinear stencil of query_sdf stays inside the field only behind a wall zone, so this runs
     with boundary_blocks 1, where the eight corner blocks are all-wall and cannot dominate: if the block asked for is one of them, the nearest
@@ -274,7 +274,7 @@ def test_nonfinite_grid_raises_and_the_context_recovers():
 # ---- (d) the collision kernel with an object that touches nothing -------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", [0, 1, 2], ids=["sticky", "slip", "separate"])
 def test_collision_kernel_far_object(ctxs, kind):
-    """grid_update_collision_kernel with sdf = +1 everywhere: every cell and the doubled maximum equal the strict float32 statements bit for
+    """grid_update_collider_kernel<CollisionArgs> with sdf = +1 everywhere: every cell and the doubled maximum equal the strict float32 statements bit for
     bit (the path is compiled without contraction); skipped cells untouched; the full tier returns +inf."""
     c = ctxs()
     c.install(kind, *FAR)
@@ -361,7 +361,7 @@ def assert_fused_equals_phase(runs):
 @pytest.mark.parametrize("sync_interval", [1, None])
 @pytest.mark.parametrize("material", [_ffi.FIXED_COROTATED, _ffi.SAND], ids=["fixed_corotated", "sand"])
 def test_run_fixed_equals_the_phase_level_loop_without_an_object(material, sync_interval, gravity):
-    """mpm_run_fixed(12) - every grid update but the first rides on carry_grid_kernel<true, false> - against grid update, g2p2g, rebuild
+    """mpm_run_fixed(12) - every grid update but the first rides on carry_grid_kernel<true> - against grid update, g2p2g, rebuild
     phase by phase (grid_update_kernel) on the deterministic sparse scene of tests/test_collision_clock_gpu.py with no object: positions,
     mpm_retrieve_state and the grid the run leaves behind (every neighbour block, by key) bit for bit.  The scene has no gravity, where p1 * inv + g dt cannot show a contraction; the same scene under gravity
     -9.8 can."""
@@ -379,7 +379,7 @@ def test_run_fixed_equals_the_phase_level_loop_without_an_object(material, sync_
 @pytest.mark.parametrize("sync_interval", [1, None])
 def test_run_fixed_equals_the_phase_level_loop_in_the_wall_zones(sync_interval):
     """The same comparison on this file's own scene - gravity -9.8, particles and their grid nodes in all 27 wall classes, no two particles on
-    one node -, which the sparse scene, in the middle of the domain, cannot give: the wall rule and g dt of carry_grid_kernel<true, false> against
+    one node -, which the sparse scene, in the middle of the domain, cannot give: the wall rule and g dt of carry_grid_kernel<true> against
     grid_update_kernel's, in positions, state and the grid the run leaves behind."""
     sc = scene(-9.8, 2)
     if sync_interval is not None:

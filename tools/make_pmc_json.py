@@ -21,6 +21,8 @@ def counters(path):
 def window(path, particles):
     c = counters(path)
     g = next(v for k, v in c.items() if "g2p2g" in k)
+    # (the collider instantiations carry_grid_kernel<true, CollisionArgs / ShapeArgs / TerrainArgs> share this name, but C3 has no collider:
+    # its traces hold the plain carry_grid_kernel<..., NoCollision> alone, and that is the one calibrated on)
     carry = next(v for k, v in c.items() if "carry_grid" in k)
     calib = carry["WRITE_SIZE"] / carry["FETCH_SIZE"]           # KiB written (= blocks carried) / KiB the fetch counter saw for the same blocks
     read = g["FETCH_SIZE"] * 1024 * calib

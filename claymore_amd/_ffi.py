@@ -59,6 +59,10 @@ class CollisionMesh(C.Structure):
 MESH_MAX_TRIANGLES = MESH_MAX_VERTICES = 1 << 22
 
 
+class MeshFill(C.Structure):
+    _fields_ = [("margin", C.c_float), ("lo", C.c_int * 3), ("hi", C.c_int * 3), ("use_box", C.c_int), ("reserved", C.c_int * 8)]
+
+
 class Counts(C.Structure):
     _fields_ = [("particle_blocks", C.c_int), ("neighbor_blocks", C.c_int), ("exterior_blocks", C.c_int),
                 ("model_count", C.c_int), ("bins", C.c_int64 * 8), ("particles", C.c_int64 * 8)]
@@ -146,6 +150,9 @@ HIP_ONLY = {
     "test_collision_heightfield": (_i, [_P(CollisionObject), _P(Heightfield), _vp, _f, _vp, _sz, _vp, _i]),
     "set_collision_mesh": (_i, [_vp, _P(CollisionObject), _P(CollisionMesh), _vp, _sz, _vp, _sz]),
     "get_collision_field": (_i, [_vp, _P(C.c_int), _P(C.c_int), _vp]),
+    "sample_mesh": (_i, [_i, _vp, _sz, _vp, _sz, _P(MeshFill), _vp, _P(_sz), _i]),
+    "add_model_mesh": (_i, [_vp, _i, _P(MaterialParams), _vp, _sz, _vp, _sz, _P(MeshFill), _fp, _ip, _P(_sz)]),
+    "test_mesh_fill": (_i, [_i, _vp, _sz, _vp, _sz, _P(MeshFill), _P(C.c_double), _i]),
     "checkpoint_size": (_i, [_vp, _P(_sz)]),
     "checkpoint_save": (_i, [_vp, _vp, _sz, _P(_sz)]),
     "checkpoint_load": (_i, [_vp, _vp, _sz]),

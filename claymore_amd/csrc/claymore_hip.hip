@@ -19,6 +19,7 @@
 #include "mpm_grid_field.hpp"
 #include "mpm_grid_isosurface.hpp"
 #include "mpm_collision_mesh.hpp"
+#include "mpm_mesh_fill.hpp"
 #include "mpm_particle_ids.hpp"
 
 using namespace mpm;
@@ -1457,6 +1458,194 @@ int mpm_get_collision_field(mpm_ctx* ctx, const int lo[3], const int dims[3], fl
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipStreamSynchronize(ctx->s_compute));
 	HIP_TRY(hipMemcpy(out4, stage.p, sizeof(float4) * n, hipMemcpyDeviceToHost));
+	return MPM_OK;
+}
+
+// Mesh-sampled models (mpm_mesh_fill.hpp) -------------------------------------------------------------------------------------------------
+// One host routine in two halves for both entry points: mesh_fill_count validates, uploads the records, classifies the tiles and scans
+// their counts - the total is the only value read back -, mesh_fill_emit writes the points into an array of that size.  Everything the
+// plan owns (records, masks, counts, offsets) is released with it, on every exit path.
+namespace {
+struct MeshFillPlan {
+	MeshFillArgs a {};
+	unsigned ntiles = 0, ngroups = 0;
+	unsigned long long total = 0, shortcuts = 0;
+	DevScratch<MeshTri> rec;
+	DevScratch<MeshPseudo> pseudo;
+	DevScratch<unsigned char> masks;
+	DevScratch<unsigned> counts, bsum;
+	DevScratch<unsigned long long> boff;// [ngroups] the groups' offsets, [ngroups] the total, [ngroups + 1] the shortcut tiles (statistics)
+	float ms[3] = {0.f, 0.f, 0.f};		// classify, scan, emit - measured only when asked for
+};
+// Events around the kernels of a timed call; released with the scope
+struct MeshFillEvents {
+	hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+	bool on			= false;
+	explicit MeshFillEvents(bool timed) {
+		on = timed;
+		for(int i = 0; on && i < 3; ++i) on = hipEventCreate(&e[i]) == hipSuccess;
+	}
+	~MeshFillEvents() {
+		for(hipEvent_t x: e)
+			if(x) hipEventDestroy(x);
+	}
+	void mark(int i, hipStream_t s) {
+		if(on) hipEventRecord(e[i], s);
+	}
+	float between(int i, int j) {
+		float ms = 0.f;
+		if(on) hipEventElapsedTime(&ms, e[i], e[j]);
+		return ms;
+	}
+};
+}// namespace
+
+#define FILL_TRY(expr)                                                                        \
+	do {                                                                                      \
+		hipError_t e_ = (expr);                                                               \
+		if(e_ != hipSuccess) {                                                                \
+			err = std::string(who) + ": " + #expr + " -> " + hipGetErrorString(e_);           \
+			return MPM_ERR_DEVICE;                                                            \
+		}                                                                                     \
+	} while(0)
+
+static int mesh_fill_count(std::string& err, const char* who, int bits, const float* verts, size_t nv, const int32_t* tris, size_t nt, const mpm_mesh_fill* opt, hipStream_t s,
+						   MeshFillPlan& P, bool timed) {
+	auto refuse = [&](int code, const std::string& why) {
+		err = std::string(who) + ": " + why;
+		return code;
+	};
+	if(!verts || !tris) return refuse(MPM_ERR_INVALID, "NULL verts or tris");
+	const float margin = opt ? opt->margin : 0.f;
+	if(!(margin >= 0.f) || !std::isfinite(margin)) return refuse(MPM_ERR_INVALID, "margin must be finite and >= 0");
+	std::vector<MeshTri> rec;
+	std::vector<MeshPseudo> pseudo;
+	MeshReport rep;
+	mesh_build(verts, nv, tris, nt, MPM_MESH_MAX_VERTICES, MPM_MESH_MAX_TRIANGLES, rec, pseudo, rep);
+	if(!rep.reason.empty()) return refuse(MPM_ERR_INVALID, rep.reason);
+	const int N		   = 1 << bits;
+	const bool use_box = opt && opt->use_box;
+	MeshFillRange r;
+	if(!mesh_fill_range(N, verts, nv, use_box ? opt->lo : nullptr, use_box ? opt->hi : nullptr, r)) return refuse(MPM_ERR_INVALID, "lo / hi outside [0, N]");
+	float extent = 1.f;// as for the field: the largest coordinate magnitude in play
+	for(size_t i = 0; i < 3 * nv; ++i) extent = std::max(extent, std::fabs(verts[i]));
+	P.a.dx	   = 1.f / (float) N;
+	P.a.slack  = std::max(0.25f * P.a.dx, extent * 0x1p-12f);
+	P.a.margin = margin;
+	for(int d = 0; d < 3; ++d) P.a.lo[d] = r.lo[d], P.a.hi[d] = r.hi[d], P.a.tlo[d] = r.tlo[d], P.a.tn[d] = r.tn[d];
+	P.ntiles = (unsigned) r.tn[0] * (unsigned) r.tn[1] * (unsigned) r.tn[2];// at most 256^3
+	P.total = P.shortcuts = 0;
+	if(!P.ntiles) return MPM_OK;
+	P.ngroups = cdiv(P.ntiles, kMeshFillGroup);
+	if(P.rec.alloc(nt) != hipSuccess || P.pseudo.alloc(nt) != hipSuccess || P.masks.alloc((size_t) P.ntiles * 64) != hipSuccess || P.counts.alloc(P.ntiles) != hipSuccess
+	   || P.bsum.alloc(P.ngroups) != hipSuccess || P.boff.alloc((size_t) P.ngroups + 2) != hipSuccess) {
+		(void) hipGetLastError();
+		return refuse(MPM_ERR_CAPACITY, "no device memory for the work buffers of " + std::to_string(P.ntiles) + " tiles and " + std::to_string(nt) + " triangle records");
+	}
+	FILL_TRY(hipMemcpy(P.rec.p, rec.data(), sizeof(MeshTri) * nt, hipMemcpyHostToDevice));
+	FILL_TRY(hipMemcpy(P.pseudo.p, pseudo.data(), sizeof(MeshPseudo) * nt, hipMemcpyHostToDevice));
+	FILL_TRY(hipMemsetAsync(P.boff.p, 0, sizeof(unsigned long long) * ((size_t) P.ngroups + 2), s));
+	MeshFillEvents ev(timed);
+	ev.mark(0, s);
+	mesh_fill_classify_kernel<<<P.ntiles, 64, 0, s>>>(P.rec.p, P.pseudo.p, (int) nt, P.a, P.masks.p, P.counts.p, P.boff.p + P.ngroups + 1);
+	FILL_TRY(hipGetLastError());
+	ev.mark(1, s);
+	mesh_fill_scan_block_kernel<<<P.ngroups, 256, 0, s>>>(P.counts.p, P.ntiles, P.bsum.p);
+	FILL_TRY(hipGetLastError());
+	mesh_fill_scan_top_kernel<<<1, 1024, 0, s>>>(P.bsum.p, P.ngroups, P.boff.p);
+	FILL_TRY(hipGetLastError());
+	ev.mark(2, s);
+	unsigned long long tail[2] = {0, 0};
+	FILL_TRY(hipMemcpyAsync(tail, P.boff.p + P.ngroups, sizeof(tail), hipMemcpyDeviceToHost, s));
+	FILL_TRY(hipStreamSynchronize(s));
+	P.total		= tail[0];
+	P.shortcuts = tail[1];
+	P.ms[0]		= ev.between(0, 1);
+	P.ms[1]		= ev.between(1, 2);
+	return MPM_OK;
+}
+
+// d_xyz: 3 P.total floats on the device
+static int mesh_fill_emit(std::string& err, const char* who, MeshFillPlan& P, float* d_xyz, hipStream_t s, bool timed) {
+	if(!P.total) return MPM_OK;
+	MeshFillEvents ev(timed);
+	ev.mark(0, s);
+	mesh_fill_emit_kernel<<<P.ntiles, 64, 0, s>>>(P.masks.p, P.counts.p, P.boff.p, P.a, d_xyz, P.total);
+	FILL_TRY(hipGetLastError());
+	ev.mark(1, s);
+	FILL_TRY(hipStreamSynchronize(s));
+	P.ms[2] = ev.between(0, 1);
+	return MPM_OK;
+}
+#undef FILL_TRY
+
+// out8 (may be NULL): {points, tiles, shortcut tiles, classify ms, scan ms, emit ms, 0, 0} of a timed call
+static int sample_mesh(int domain_bits, const float* verts, size_t nv, const int32_t* tris, size_t nt, const mpm_mesh_fill* opt, float* xyz, size_t* n, int device, double* out8) {
+	if(!n || domain_bits < 4 || domain_bits > 10) return MPM_ERR_INVALID;
+	if(hipSetDevice(device) != hipSuccess) return MPM_ERR_DEVICE;
+	std::string err;
+	MeshFillPlan P;
+	if(int rc = mesh_fill_count(err, "mpm_sample_mesh", domain_bits, verts, nv, tris, nt, opt, nullptr, P, out8 != nullptr)) return rc;
+	const size_t cap = xyz ? *n : 0;
+	if(P.total > SIZE_MAX / (3 * sizeof(float))) return MPM_ERR_CAPACITY;
+	*n = (size_t) P.total;
+	if(xyz && P.total > cap) return MPM_ERR_CAPACITY;
+	if((xyz || out8) && P.total) {
+		DevScratch<float> d_xyz;
+		if(d_xyz.alloc(3 * (size_t) P.total) != hipSuccess) {
+			(void) hipGetLastError();
+			return MPM_ERR_CAPACITY;
+		}
+		if(int rc = mesh_fill_emit(err, "mpm_sample_mesh", P, d_xyz.p, nullptr, out8 != nullptr)) return rc;
+		if(xyz && hipMemcpy(xyz, d_xyz.p, sizeof(float) * 3 * (size_t) P.total, hipMemcpyDeviceToHost) != hipSuccess) return MPM_ERR_DEVICE;
+	}
+	if(out8) {
+		const double v[8] = {(double) P.total, (double) P.ntiles, (double) P.shortcuts, P.ms[0], P.ms[1], P.ms[2], 0., 0.};
+		std::copy(v, v + 8, out8);
+	}
+	return MPM_OK;
+}
+
+int mpm_sample_mesh(int domain_bits, const float* verts, size_t nv, const int32_t* tris, size_t nt, const mpm_mesh_fill* opt, float* xyz, size_t* n, int device) {
+	return sample_mesh(domain_bits, verts, nv, tris, nt, opt, xyz, n, device, nullptr);
+}
+
+int mpm_test_mesh_fill(int domain_bits, const float* verts, size_t nv, const int32_t* tris, size_t nt, const mpm_mesh_fill* opt, double* out8, int device) {
+	if(!out8) return MPM_ERR_INVALID;
+	size_t n = 0;
+	return sample_mesh(domain_bits, verts, nv, tris, nt, opt, nullptr, &n, device, out8);
+}
+
+int mpm_add_model_mesh(mpm_ctx* ctx, int material, const mpm_material_params* params, const float* verts, size_t nv, const int32_t* tris, size_t nt, const mpm_mesh_fill* opt,
+					   const float v0[3], int* model_id, size_t* n_out) {
+	if(!ctx) return MPM_ERR_INVALID;
+	if(!params) return fail(ctx, MPM_ERR_INVALID, "mpm_add_model_mesh: material parameters are missing");
+	if(ctx->ready) return fail(ctx, MPM_ERR_INVALID, "mpm_add_model_mesh: models must be added before mpm_initial_setup");
+	if(material < 0 || material > 3) return fail(ctx, MPM_ERR_INVALID, "unknown material");
+	if((int) ctx->models.size() >= kMaxModels) return fail(ctx, MPM_ERR_CAPACITY, "too many models");
+	HIP_TRY(hipSetDevice(ctx->device));
+	std::string err;
+	MeshFillPlan P;
+	if(int rc = mesh_fill_count(err, "mpm_add_model_mesh", ctx->cfg.domain_bits, verts, nv, tris, nt, opt, ctx->s_compute, P, false)) return fail(ctx, rc, err);
+	if(P.total > SIZE_MAX / (3 * sizeof(float))) return fail(ctx, MPM_ERR_CAPACITY, "mpm_add_model_mesh: no device memory for " + std::to_string(P.total) + " positions");
+	Model m;
+	m.material = material;
+	m.p		   = *params;
+	m.mc	   = make_material_const(*params);
+	m.nch	   = material == MPM_J_FLUID ? 4 : (material == MPM_FIXED_COROTATED ? 9 : 10);// as mpm_add_model
+	m.n		   = (size_t) P.total;
+	for(int d = 0; d < 3; ++d) m.v0[d] = v0 ? v0[d] : 0.f;
+	if(dalloc(&m.d_xyz, 3 * m.n) != hipSuccess) {// the model's own array: the emit kernel writes into it
+		(void) hipGetLastError();
+		return fail(ctx, MPM_ERR_CAPACITY, "mpm_add_model_mesh: no device memory for " + std::to_string(P.total) + " positions");
+	}
+	if(int rc = mesh_fill_emit(err, "mpm_add_model_mesh", P, m.d_xyz, ctx->s_compute, false)) {
+		hipFree(m.d_xyz);
+		return fail(ctx, rc, err);
+	}
+	if(model_id) *model_id = (int) ctx->models.size();
+	if(n_out) *n_out = m.n;
+	ctx->models.push_back(m);
 	return MPM_OK;
 }
 

@@ -112,6 +112,53 @@ class Engine:
         self.models.append({"material": int(material), "n": xyz.shape[0], "params": p})
         return mid.value
 
+    @staticmethod
+    def _mesh_fill_args(vertices, faces, margin, box, who):
+        v = np.ascontiguousarray(vertices, dtype=np.float32)
+        f = np.ascontiguousarray(faces, dtype=np.int32)
+        if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+            raise ValueError(f"{who}: vertices must be (nv, 3) and faces (nt, 3), got {v.shape} and {f.shape}")
+        opt = _ffi.MeshFill()
+        opt.margin = float(margin)
+        if box is not None:
+            opt.use_box = 1
+            for d in range(3):
+                opt.lo[d], opt.hi[d] = int(box[0][d]), int(box[1][d])
+        return v, f, opt
+
+    @staticmethod
+    def sample_mesh(domain_bits, vertices, faces, margin=0.0, box=None, device=0, api=None):
+        """The lattice particles inside a closed triangle mesh, sampled on the device (mpm_sample_mesh, HIP library only; needs no engine):
+        (n, 3) float32 in the order that is the particles' id - tiles of 4^3 nodes ascending, nodes in a tile, the 8 candidates of a node
+        (include/claymore_amd.h).  vertices / faces: as for set_collision_mesh.  margin >= 0 keeps particles off the surface (inside <=>
+        sdis < -margin); box = (lo, hi): only the nodes lo <= (i, j, k) < hi.  For several GPUs: scenes.split_slabs on the result, then
+        init_model per rank."""
+        api = api if api is not None else _ffi.load_hip()
+        v, f, opt = Engine._mesh_fill_args(vertices, faces, margin, box, "sample_mesh")
+        n = C.c_size_t(0)
+        args = (int(domain_bits), v.ctypes.data, v.shape[0], f.ctypes.data, f.shape[0], C.byref(opt))
+        rc = api.sample_mesh(*args, None, C.byref(n), int(device))                                    # count, then fetch
+        xyz = np.empty((n.value, 3), dtype=np.float32)
+        if rc == 0 and n.value:
+            rc = api.sample_mesh(*args, xyz.ctypes.data, C.byref(n), int(device))
+        if rc != 0:
+            raise EngineError(rc, "mpm_sample_mesh refused the call (an invalid mesh, margin or box; or no device memory)")
+        return xyz
+
+    def init_model_mesh(self, material, vertices, faces, v0=(0.0, 0.0, 0.0), margin=0.0, box=None, params=None, **param_overrides):
+        """init_model with the positions sampled inside a closed triangle mesh on the device, straight into the model's array
+        (mpm_add_model_mesh, HIP library only): the particles and their order are sample_mesh's.  Returns the model id."""
+        v, f, opt = self._mesh_fill_args(vertices, faces, margin, box, "init_model_mesh")
+        p = params if params is not None else self.default_material(material)
+        for k, val in param_overrides.items():
+            setattr(p, k, val)
+        vel = (C.c_float * 3)(*[float(x) for x in v0])
+        mid, n = C.c_int(-1), C.c_size_t(0)
+        self._check(self.api.add_model_mesh(self.ctx, int(material), C.byref(p), v.ctypes.data, v.shape[0], f.ctypes.data, f.shape[0], C.byref(opt),
+                                            vel, C.byref(mid), C.byref(n)))
+        self.models.append({"material": int(material), "n": int(n.value), "params": p})
+        return mid.value
+
     def initial_setup(self):
         self._check(self.api.initial_setup(self.ctx))
 
@@ -544,7 +591,10 @@ def build_engine(scene, device=0, api=None):
         setattr(cfg, k, v)
     eng = Engine(cfg=cfg, device=device, api=a, track_ids=bool(scene.get("track_ids", False)))
     for m in scene["models"]:
-        eng.init_model(m["material"], m["xyz"], m.get("v0", (0, 0, 0)), **m.get("params", {}))
+        if "mesh" in m:  # {"vertices", "faces"[, "margin", "box"]}: filled on the device (init_model_mesh)
+            eng.init_model_mesh(m["material"], v0=m.get("v0", (0, 0, 0)), **m["mesh"], **m.get("params", {}))
+        else:
+            eng.init_model(m["material"], m["xyz"], m.get("v0", (0, 0, 0)), **m.get("params", {}))
     if scene.get("collision"):
         eng.set_collision_object(**{**scene["collision"], "animate": False})
     if scene.get("collision_mesh"):  # the level-set object from a triangle mesh (it and "collision" are one object: the later install wins)

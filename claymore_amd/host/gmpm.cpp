@@ -108,7 +108,7 @@ pio::Points sample_model(const mj::Value& model, int bits, const std::string& sc
 			return sdf.sample(q[0], q[1], q[2]) < 0.f;
 		});
 	}
-	std::fprintf(stderr, "unknown model file '%s' (expected *.sdf, sphere or box)\n", file.c_str());
+	std::fprintf(stderr, "unknown model file '%s' (expected *.sdf, *.obj, sphere or box)\n", file.c_str());
 	std::exit(EXIT_FAILURE);
 }
 
@@ -358,13 +358,43 @@ int main(int argc, char** argv) {
 			p.beta = num(m, "beta", p.beta);
 			p.xi   = num(m, "xi", p.xi);
 		}
-		pio::Points pts = sample_model(m, bits, scene_dir);
 		float v0[3];
 		for(int d = 0; d < 3; ++d) v0[d] = (float) m["velocity"][d].number();
 		max_v0 = std::max(max_v0, std::sqrt(v0[0] * v0[0] + v0[1] * v0[1] + v0[2] * v0[2]));
 		int id = -1;
-		rc	   = mpm_add_model(ctx, mat, &p, pts.empty() ? nullptr : pts[0].data(), pts.size(), v0, &id);
-		if(rc) die(ctx, rc);
+		pio::Points pts;
+		const std::string file = m["file"].string();
+		if(file.size() > 4 && file.substr(file.size() - 4) == ".obj") {
+			// "file": "name.obj" (relative to the scene file), optional "margin": a closed triangle mesh filled with lattice particles on the device
+			// (mpm_add_model_mesh).  As for a level set, the mesh's bounding box is scaled uniformly into `span` and moved to `offset`:
+			// v' = (v - mn) s + offset per axis in float32, s = min over the axes of span / (mx - mn).
+			const std::string path = !file.empty() && file[0] == '/' ? file : scene_dir + "/" + file;
+			std::vector<float> verts;
+			std::vector<int32_t> tris;
+			if(!pio::read_obj_mesh(path, verts, tris) || verts.empty()) {
+				std::fprintf(stderr, "gmpm: model file '%s' cannot be read as an OBJ mesh\n", path.c_str());
+				return 1;
+			}
+			float mn[3] = {verts[0], verts[1], verts[2]}, mx[3] = {verts[0], verts[1], verts[2]}, scale = 1e30f;
+			for(size_t i = 0; i < verts.size(); ++i) mn[i % 3] = std::min(mn[i % 3], verts[i]), mx[i % 3] = std::max(mx[i % 3], verts[i]);
+			for(int d = 0; d < 3; ++d) scale = std::min(scale, (float) m["span"][d].number() / (mx[d] - mn[d]));
+			for(size_t i = 0; i < verts.size(); ++i) {
+				const float rel = verts[i] - mn[i % 3], scaled = rel * scale;
+				verts[i]		= scaled + (float) m["offset"][i % 3].number();
+			}
+			mpm_mesh_fill opt;
+			std::memset(&opt, 0, sizeof(opt));
+			opt.margin = num(m, "margin", 0.f);
+			size_t n   = 0;
+			rc		   = mpm_add_model_mesh(ctx, mat, &p, verts.data(), verts.size() / 3, tris.data(), tris.size() / 3, &opt, v0, &id, &n);
+			if(rc) die(ctx, rc);
+			pts.resize(n);// frame 0 is written from the same sampler's points: the model's own array stays on the device
+			if(n && (rc = mpm_sample_mesh(bits, verts.data(), verts.size() / 3, tris.data(), tris.size() / 3, &opt, pts[0].data(), &n, gpuid))) die(nullptr, rc);
+		} else {
+			pts = sample_model(m, bits, scene_dir);
+			rc	= mpm_add_model(ctx, mat, &p, pts.empty() ? nullptr : pts[0].data(), pts.size(), v0, &id);
+			if(rc) die(ctx, rc);
+		}
 		std::printf("init %d-th model with %zu particles\n", id, pts.size());
 		const std::string frame0 = out_dir + "/model_id[" + std::to_string(id) + "]_frame[0].bgeo";
 		if(out_vel || out_stress || out_ids) {

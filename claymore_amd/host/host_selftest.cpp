@@ -1,5 +1,5 @@
 // host_selftest.cpp — exercises the pieces of the host drivers that need no GPU (JSON reader, lattice sampler, BGEO
-// writer, NumPy writer, OBJ reader, the collision mesh's validation and closest-point functions).  usage: host_selftest <out.bgeo>  -> prints "json_ok <n_models> <dt>", "sphere <count>", "bgeo <bytes>"
+// writer, NumPy writer, OBJ reader, the collision mesh's validation and closest-point functions, the mesh-sampled model per point).  usage: host_selftest <out.bgeo>  -> prints "json_ok <n_models> <dt>", "sphere <count>", "bgeo <bytes>"
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -7,6 +7,7 @@
 #include "mini_json.hpp"
 #include "particle_io.hpp"
 #include "../csrc/mpm_collision_mesh.hpp"
+#include "../csrc/mpm_mesh_fill.hpp"
 
 int main(int argc, char** argv) {
 	if(argc == 4 && !std::strcmp(argv[1], "--bgeo-from")) {// host_selftest --bgeo-from points.f32 out.bgeo: raw float32 xyz -> BGEO frame
@@ -102,6 +103,36 @@ int main(int argc, char** argv) {
 			std::memcpy(&w[0], &q, 4);
 			std::memcpy(&w[1], out, 16);
 			std::printf("%d %d %08x %08x %08x %08x %08x\n", T, feature, w[0], w[1], w[2], w[3], w[4]);
+		}
+		return 0;
+	}
+	if((argc == 4 || argc == 5 || argc == 11) && !std::strcmp(argv[1], "--mesh-fill")) {// host_selftest --mesh-fill FILE.obj BITS [MARGIN [lo0 lo1 lo2 hi0 hi1 hi2]]: the mesh-sampled
+		std::vector<float> verts;														  // model per point (mesh_fill_host): "count N" or "refused WHY", then per point "x y z" as bits in hex
+		std::vector<int32_t> tris;
+		if(!pio::read_obj_mesh(argv[2], verts, tris)) return 3;
+		const int bits	   = std::atoi(argv[3]);
+		const float margin = argc >= 5 ? std::strtof(argv[4], nullptr) : 0.f;
+		if(bits < 4 || bits > 10) return 5;
+		int box[6];
+		for(int i = 0; argc == 11 && i < 6; ++i) box[i] = std::atoi(argv[5 + i]);
+		std::vector<mpm::MeshTri> rec;
+		std::vector<mpm::MeshPseudo> pseudo;
+		mpm::MeshReport rep;
+		mpm::mesh_build(verts.data(), verts.size() / 3, tris.data(), tris.size() / 3, (size_t) 1 << 22, (size_t) 1 << 22, rec, pseudo, rep);
+		mpm::MeshFillRange r;
+		if(rep.reason.empty() && (!(margin >= 0.f) || !std::isfinite(margin))) rep.reason = "margin must be finite and >= 0";
+		if(rep.reason.empty() && !mpm::mesh_fill_range(1 << bits, verts.data(), verts.size() / 3, argc == 11 ? box : nullptr, argc == 11 ? box + 3 : nullptr, r)) rep.reason = "lo / hi outside [0, N]";
+		if(!rep.reason.empty()) {
+			std::printf("refused %s\n", rep.reason.c_str());
+			return 0;
+		}
+		std::vector<float> xyz;
+		mpm::mesh_fill_host(rec, pseudo, 1 << bits, r, margin, xyz);
+		std::printf("count %zu\n", xyz.size() / 3);
+		for(size_t i = 0; i < xyz.size() / 3; ++i) {
+			uint32_t w[3];
+			std::memcpy(w, &xyz[3 * i], 12);
+			std::printf("%08x %08x %08x\n", w[0], w[1], w[2]);
 		}
 		return 0;
 	}

@@ -373,3 +373,14 @@ def sphere_on_obstacle_mesh(bits=6, radius_cells=5.0, obstacle_cells=6.0, bounda
         lo = [n // 2 - int(body_cells[0]) // 2, j, n // 2 - int(body_cells[2]) // 2]
         sc["models"][0]["xyz"] = lattice_box(bits, lo, [lo[0] + int(body_cells[0]), j + int(body_cells[1]), lo[2] + int(body_cells[2])])
     return sc
+
+
+def mesh_drop(bits=6, radius_cells=9.0, center=(0.5, 0.3, 0.5), material=FIXED_COROTATED, subdivisions=3, margin=0.0):
+    """sphere_drop with the body given as a triangle mesh: an icosphere of radius_cells about `center`, filled with lattice particles on the
+    device (Engine.init_model_mesh) and dropped on the floor under gravity.  Same centre, radius, material and volume as
+    sphere_drop(bits, radius_cells, center) - lattice_sphere's particles less the thin shell between the polyhedron and its sphere - so the
+    two runs are directly comparable.  The model carries "mesh" instead of "xyz": its particle count is known once the engine has added it."""
+    prm = {"volume": _vol(bits)} if material != SAND else {}
+    vertices, faces = icosphere(center, radius_cells / (1 << bits), subdivisions)
+    return {"name": "mesh_drop", "bits": bits, "dt": 1e-4, "config": {"max_ppc": 128},
+            "models": [{"material": material, "mesh": {"vertices": vertices, "faces": faces, "margin": margin}, "v0": (0, 0, 0), "params": prm}]}

@@ -403,6 +403,41 @@ int mpm_set_collision_mesh(mpm_ctx* ctx, const mpm_collision_object* obj, const 
  * again through mpm_set_collision_object.  HIP library only. */
 int mpm_get_collision_field(mpm_ctx* ctx, const int lo[3], const int dims[3], float* out4);
 
+/* Extension: a model whose particles fill a closed triangle mesh, sampled on the device (claymore_amd/csrc/mpm_mesh_fill.hpp).  HIP library only.
+ * verts / tris: as for mpm_set_collision_mesh, same coordinates, same validation.
+ * Lattice (the reference's sample_uniform_box rule): node (i, j, k) carries 8 candidates at (((float) i + a 0.25f) dx, ((float) j + b 0.25f) dx,
+ *   ((float) k + c 0.25f) dx), a, b, c in {-1, +1}; exact in float32.
+ * Clip box: the nodes lo <= (i, j, k) < hi - opt->lo / opt->hi when opt->use_box, else [0, N)^3 -, cut per axis to
+ *   floor(mn N) <= i < floor(mx N) + 2 with [mn, mx] the mesh's bounding box (float64 on the float32 vertices): the nodes that can carry a
+ *   candidate inside the bounding box.  A particle in the wall zone is treated by mpm_initial_setup as one given to mpm_add_model.
+ * Inside: inside(p) <=> sdis(p) < -margin, sdis the first word of mpm_set_collision_mesh's field definition evaluated at the candidate p
+ *   with inside_out = 0 (nearest triangle, lowest index among equals; plane or radial rule); margin >= 0 keeps particles off the surface.
+ *   |sdis| is bit-defined, its sign is the float64 pseudonormals' (not bit-defined where (p - c) . m is a rounding away from 0).
+ * Order (it is the particle's id under mpm_track_particle_ids - the index in the array the model was added with): tiles of 4 x 4 x 4 nodes,
+ *   aligned to the domain (tile = node >> 2), ascending with x slowest and z fastest; in a tile the nodes by (x 4 + y) 4 + z of their low
+ *   bits; in a node a slowest, c fastest, -1 before +1.
+ * MPM_ERR_INVALID: what mpm_set_collision_mesh refuses in a mesh; a margin that is negative or not finite; a lo / hi entry outside [0, N].
+ * hi <= lo on an axis, or a mesh that holds no candidate, gives 0 points (an empty model is legal).  MPM_ERR_CAPACITY when the device
+ * cannot hold the work buffers (64 B + 4 B per tile of the clipped range, the triangle records) or the positions.  A refused call changes
+ * nothing, the context stays usable; every work buffer is released before the call returns. */
+typedef struct mpm_mesh_fill {
+	float margin;
+	int lo[3], hi[3];
+	int use_box; /* 0: the whole domain */
+	int reserved[8];
+} mpm_mesh_fill;
+/* The points only, without a context (N = 2^domain_bits, dx = 1 / N, domain_bits 4 .. 10): count, then fetch - mpm_grid_isosurface's
+ * protocol.  xyz NULL: *n receives the count.  Else *n is the capacity of xyz (points) on entry and the count on return; MPM_ERR_CAPACITY
+ * with the true count in *n, and nothing written, when it is too small. */
+int mpm_sample_mesh(int domain_bits, const float* verts, size_t nv, const int32_t* tris, size_t nt, const mpm_mesh_fill* opt /* may be NULL */, float* xyz, size_t* n, int device);
+/* mpm_add_model with the positions sampled straight into the model's own device array (no host array, no staging); its preconditions
+ * (before mpm_initial_setup, at most 8 models, the material range).  *n_out (may be NULL): the particle count. */
+int mpm_add_model_mesh(mpm_ctx* ctx, int material, const mpm_material_params* params, const float* verts, size_t nv, const int32_t* tris, size_t nt,
+					   const mpm_mesh_fill* opt /* may be NULL */, const float v0[3], int* model_id, size_t* n_out);
+/* Function-level entry point: a timed mpm_sample_mesh that keeps the points on the device.  out8 = {points, tiles of the clipped range,
+ * tiles decided from their centre, classify ms, scan ms, emit ms, 0, 0}. */
+int mpm_test_mesh_fill(int domain_bits, const float* verts, size_t nv, const int32_t* tris, size_t nt, const mpm_mesh_fill* opt /* may be NULL */, double* out8, int device);
+
 /* Current capacities and the number of times check_capacity() (gmpm_simulator.cuh:283-300) has grown them: blocks
  * (exterior count limit), bins per model (bin_capacity[8]).  HIP library only. */
 int mpm_get_capacity(mpm_ctx* ctx, int64_t* block_capacity, int64_t* bin_capacity, int* growth_events);

@@ -59,6 +59,14 @@ class CollisionMesh(C.Structure):
 MESH_MAX_TRIANGLES = MESH_MAX_VERTICES = 1 << 22
 
 
+class CollisionVolume(C.Structure):
+    _fields_ = [("dims", C.c_int * 3), ("origin", C.c_float * 3), ("spacing", C.c_float), ("inside_out", C.c_int), ("pad", C.c_int),
+                ("reserved", C.c_int * 7)]
+
+
+VOLUME_MAX_SAMPLES = 1024
+
+
 class MeshFill(C.Structure):
     _fields_ = [("margin", C.c_float), ("lo", C.c_int * 3), ("hi", C.c_int * 3), ("use_box", C.c_int), ("reserved", C.c_int * 8)]
 
@@ -150,6 +158,10 @@ HIP_ONLY = {
     "test_collision_heightfield": (_i, [_P(CollisionObject), _P(Heightfield), _vp, _f, _vp, _sz, _vp, _i]),
     "set_collision_mesh": (_i, [_vp, _P(CollisionObject), _P(CollisionMesh), _vp, _sz, _vp, _sz]),
     "get_collision_field": (_i, [_vp, _P(C.c_int), _P(C.c_int), _vp]),
+    "set_collision_volume": (_i, [_vp, _i, _P(CollisionObject), _P(CollisionVolume), _vp]),
+    "set_collision_volume_mesh": (_i, [_vp, _i, _P(CollisionObject), _P(CollisionVolume), _vp, _sz, _vp, _sz]),
+    "get_collision_volume": (_i, [_vp, _i, _P(CollisionVolume), _P(C.c_int), _P(C.c_int), _vp]),
+    "test_collision_volume": (_i, [_P(CollisionObject), _P(CollisionVolume), _vp, _f, _vp, _sz, _vp, _i]),
     "sample_mesh": (_i, [_i, _vp, _sz, _vp, _sz, _P(MeshFill), _vp, _P(_sz), _i]),
     "add_model_mesh": (_i, [_vp, _i, _P(MaterialParams), _vp, _sz, _vp, _sz, _P(MeshFill), _fp, _ip, _P(_sz)]),
     "test_mesh_fill": (_i, [_i, _vp, _sz, _vp, _sz, _P(MeshFill), _P(C.c_double), _i]),

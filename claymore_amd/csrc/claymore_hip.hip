@@ -127,6 +127,12 @@ struct mpm_ctx {
 	// by the context (freed on replace, on removal and in mpm_destroy).  hf_count > 0 selects the terrain kernels.
 	Heightfield hf[kMaxShapes] {};
 	int hf_count = 0;// slots that hold a heightfield
+	// volumes (mpm_set_collision_volume, mpm_set_collision_volume_mesh): slot s holds one where shape[s].shape.kind == kShapeVolume; vol[s].table is
+	// owned by the context like a heightfield's; vol_desc[s] is the descriptor as installed (mpm_get_collision_volume).  vol_count > 0 selects
+	// the volume kernels.
+	Volume vol[kMaxShapes] {};
+	mpm_collision_volume vol_desc[kMaxShapes] {};
+	int vol_count = 0;// slots that hold a volume
 	mpm_timers timers {};
 	float last_g2p2g_ms = 0.f;
 	// halo state (MGSP)
@@ -252,8 +258,8 @@ static inline unsigned cdiv(size_t a, size_t b) {
 	return (unsigned) ((a + b - 1) / b);
 }
 
-// The installed colliders as the grid update that is being enqueued sees them, handed to `launch` in the type of their kernels: TerrainArgs
-// with a heightfield in a slot, ShapeArgs with analytic shapes alone, CollisionArgs with the level-set object alone, NoCollision without any.
+// The installed colliders as the grid update that is being enqueued sees them, handed to `launch` in the type of their kernels: VolumeColliderArgs
+// with a volume in a slot, else TerrainArgs with a heightfield in a slot, ShapeArgs with analytic shapes alone, CollisionArgs with the level-set object alone, NoCollision without any.
 // One pose per installed collider, all at the one clock's current time T (the start of the substep), by value; a running clock then moves
 // on, T = T + dt in one float32 addition (the drivers' own cur_time += dt).  Called once per applied grid update - by the stand-alone
 // kernel's launch or by the fused carry-over's, never by both.
@@ -264,7 +270,8 @@ static void with_collider(mpm_ctx* ctx, float dt, F&& launch) {
 		return;
 	}
 	const float T = ctx->collision.time;
-	TerrainArgs a {};
+	VolumeColliderArgs va {};
+	TerrainArgs& a	= va.ter;
 	a.col.count		= ctx->shape_count;
 	a.col.has_field = ctx->has_collision ? 1 : 0;
 	if(ctx->has_collision) a.col.field = CollisionArgs {ctx->collision, collision_pose(ctx->collision, T)};
@@ -272,9 +279,11 @@ static void with_collider(mpm_ctx* ctx, float dt, F&& launch) {
 		a.col.slot[i] = ctx->shape[i];
 		if(a.col.slot[i].shape.kind) a.col.slot[i].pose = collision_pose(a.col.slot[i].obj, T);
 	}
-	for(int i = 0; i < kMaxShapes; ++i) a.hf[i] = ctx->hf[i];
+	for(int i = 0; i < kMaxShapes; ++i) a.hf[i] = ctx->hf[i], va.vol[i] = ctx->vol[i];
 	if(ctx->collision_running) ctx->collision.time = T + dt;
-	if(ctx->hf_count)
+	if(ctx->vol_count)
+		launch(va);
+	else if(ctx->hf_count)
 		launch(a);
 	else if(ctx->shape_count)
 		launch(a.col);
@@ -404,7 +413,7 @@ void mpm_destroy(mpm_ctx* ctx) {
 	hipSetDevice(ctx->device);
 	hipDeviceSynchronize();
 	hipFree(ctx->d_sdf);
-	for(int i = 0; i < kMaxShapes; ++i) hipFree(const_cast<float4*>(ctx->hf[i].table));
+	for(int i = 0; i < kMaxShapes; ++i) hipFree(const_cast<float4*>(ctx->hf[i].table)), hipFree(const_cast<float4*>(ctx->vol[i].table));
 	for(int i = 0; i < 2; ++i) {
 		hipFree(ctx->part[i].table);
 		hipFree(ctx->part[i].keys);
@@ -1298,31 +1307,38 @@ static const char* make_shape_slot(const mpm_collision_object* obj, const mpm_co
 }
 
 static void count_slots(mpm_ctx* ctx) {
-	ctx->shape_count = ctx->hf_count = 0;
+	ctx->shape_count = ctx->hf_count = ctx->vol_count = 0;
 	for(int i = 0; i < MPM_MAX_COLLISION_SHAPES; ++i) {
 		if(ctx->shape[i].shape.kind) ctx->shape_count = i + 1;
 		if(ctx->shape[i].shape.kind == kShapeHeightfield) ++ctx->hf_count;
+		if(ctx->shape[i].shape.kind == kShapeVolume) ++ctx->vol_count;
 	}
 }
-// What every accepted install or removal of either kind does to slot `slot`: wait for the device, free the table of a heightfield that sat
-// there, put the new occupant in (c.shape.kind 0: empty; f.table: the new heightfield's, owned by the context from here on), stop the clock
-// and - on an install - set it to obj->time.
-static int install_slot(mpm_ctx* ctx, int slot, const ShapeSlot& c, const Heightfield& f, const mpm_collision_object* obj) {
-	hipError_t e = hipSetDevice(ctx->device);
+// What every accepted install or removal of any kind does to slot `slot`: wait for the device, free the table of a heightfield or a volume
+// that sat there, put the new occupant in (c.shape.kind 0: empty; f.table / v.table: the new heightfield's / volume's, owned by the context
+// from here on; desc: the volume's descriptor as installed), stop the clock and - on an install - set it to obj->time.
+static int install_slot(mpm_ctx* ctx, int slot, const ShapeSlot& c, const Heightfield& f, const mpm_collision_object* obj, const Volume& v = Volume {}, const mpm_collision_volume* desc = nullptr) {
+	const float4* fresh = f.table ? f.table : v.table;
+	hipError_t e		= hipSetDevice(ctx->device);
 	if(e == hipSuccess) e = hipDeviceSynchronize();
 	if(e != hipSuccess) {// nothing was touched: the old occupant stays
-		if(f.table) hipFree(const_cast<float4*>(f.table));
+		if(fresh) hipFree(const_cast<float4*>(fresh));
 		return fail(ctx, MPM_ERR_DEVICE, std::string("collision slot: ") + hipGetErrorString(e));
 	}
 	// the old table goes first; should freeing it fail, its memory is in an unknown state, so the slot is emptied rather than left pointing at it
-	if(ctx->hf[slot].table && (e = hipFree(const_cast<float4*>(ctx->hf[slot].table))) != hipSuccess) {
-		if(f.table) hipFree(const_cast<float4*>(f.table));
-		ctx->hf[slot]	 = Heightfield {};
-		ctx->shape[slot] = ShapeSlot {};
+	const float4* old = ctx->hf[slot].table ? ctx->hf[slot].table : ctx->vol[slot].table;
+	if(old && (e = hipFree(const_cast<float4*>(old))) != hipSuccess) {
+		if(fresh) hipFree(const_cast<float4*>(fresh));
+		ctx->hf[slot]		= Heightfield {};
+		ctx->vol[slot]		= Volume {};
+		ctx->vol_desc[slot] = mpm_collision_volume {};
+		ctx->shape[slot]	= ShapeSlot {};
 		count_slots(ctx);
 		return fail(ctx, MPM_ERR_DEVICE, std::string("collision slot: freeing the old table -> ") + hipGetErrorString(e) + " (the slot is now empty)");
 	}
 	ctx->hf[slot]		   = f;
+	ctx->vol[slot]		   = v;
+	ctx->vol_desc[slot]	   = desc ? *desc : mpm_collision_volume {};
 	ctx->shape[slot]	   = c;// (kind 0: empty)
 	ctx->collision_running = false;// installing or removing a collider stops the clock
 	if(obj) ctx->collision.time = obj->time;
@@ -1455,6 +1471,160 @@ int mpm_get_collision_field(mpm_ctx* ctx, const int lo[3], const int dims[3], fl
 		return fail(ctx, MPM_ERR_CAPACITY, "mpm_get_collision_field: no device memory for the box");
 	}
 	collision_field_box_kernel<<<cdiv(n, 256), 256, 0, ctx->s_compute>>>(ctx->d_sdf, N, lo[0], lo[1], lo[2], dims[0], dims[1], dims[2], stage.p);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipStreamSynchronize(ctx->s_compute));
+	HIP_TRY(hipMemcpy(out4, stage.p, sizeof(float4) * n, hipMemcpyDeviceToHost));
+	return MPM_OK;
+}
+
+// Volume: a local level-set box in a slot (mpm_collision_volume.hpp) ----------------------------------------------------------------------------
+// mpm_collision_object + mpm_collision_volume -> the slot and the table's description (table = nullptr: the caller's); nullptr, or the message
+// that names the offending field.  zero_dims_ok: a mesh install, whose dims {0, 0, 0} ask for the box to be sized from the mesh.
+static const char* make_volume_slot(const mpm_collision_object* obj, const mpm_collision_volume* vol, bool zero_dims_ok, ShapeSlot& out, Volume& v) {
+	const bool zero = vol->dims[0] == 0 && vol->dims[1] == 0 && vol->dims[2] == 0;
+	if(zero && !zero_dims_ok) return "collision volume: dims are all zero without a mesh to size the box from";
+	if(!zero) {
+		long long total = 1;
+		for(int d = 0; d < 3; ++d) {
+			if(vol->dims[d] < kVolumeMinSamples || vol->dims[d] > MPM_VOLUME_MAX_SAMPLES) return "collision volume: a dims entry outside 2..1024";
+			total *= vol->dims[d];
+		}
+		if(total > kVolumeMaxTable) return "collision volume: dims whose product exceeds 2^27 samples";
+	}
+	if(!(vol->spacing > 0.f) || !std::isfinite(vol->spacing)) return "collision volume: spacing must be finite and > 0";
+	for(int d = 0; d < 3; ++d)
+		if(vol->origin[d] != vol->origin[d]) return "collision volume: NaN in origin";
+	if(vol->pad < 0) return "collision volume: pad < 0";
+	if(obj->type < MPM_BOUNDARY_STICKY || obj->type > MPM_BOUNDARY_SEPARATE) return "collision volume: boundary type outside 0..2";
+	out					 = ShapeSlot {};
+	out.obj				 = slot_object(obj);
+	out.shape.kind		 = kShapeVolume;
+	out.shape.inside_out = vol->inside_out ? 1 : 0;
+	v					 = Volume {};
+	for(int d = 0; d < 3; ++d) v.dims[d] = vol->dims[d], v.origin[d] = vol->origin[d];
+	v.spacing	 = vol->spacing;
+	v.inside_out = out.shape.inside_out;
+	return nullptr;
+}
+// (x - x == 0 exactly for every finite x, NaN for an infinity or a NaN)
+static bool volume_samples_finite(const float* field4, size_t cells) {
+	for(size_t i = 0; i < 4 * cells; ++i)
+		if(!(field4[i] - field4[i] == 0.f)) return false;
+	return true;
+}
+// the descriptor as installed: what mpm_get_collision_volume hands back
+static mpm_collision_volume volume_descriptor(const Volume& v, int pad) {
+	mpm_collision_volume d {};
+	for(int k = 0; k < 3; ++k) d.dims[k] = v.dims[k], d.origin[k] = v.origin[k];
+	d.spacing	 = v.spacing;
+	d.inside_out = v.inside_out;
+	d.pad		 = pad;
+	return d;
+}
+
+int mpm_set_collision_volume(mpm_ctx* ctx, int slot, const mpm_collision_object* obj, const mpm_collision_volume* vol, const float* field4) {
+	if(!ctx) return MPM_ERR_INVALID;
+	if(slot < 0 || slot >= MPM_MAX_COLLISION_SHAPES) return fail(ctx, MPM_ERR_INVALID, "collision volume: slot outside 0..3");
+	ShapeSlot c {};
+	Volume v {};
+	if(!obj) return install_slot(ctx, slot, c, Heightfield {}, nullptr);
+	if(!vol) return fail(ctx, MPM_ERR_INVALID, "collision volume: obj without vol");
+	if(!field4) return fail(ctx, MPM_ERR_INVALID, "collision volume: obj without field4");
+	if(const char* msg = make_volume_slot(obj, vol, false, c, v)) return fail(ctx, MPM_ERR_INVALID, msg);
+	const size_t n = (size_t) v.dims[0] * (size_t) v.dims[1] * (size_t) v.dims[2];
+	if(!volume_samples_finite(field4, n)) return fail(ctx, MPM_ERR_INVALID, "collision volume: a sample of field4 is not finite");
+	HIP_TRY(hipSetDevice(ctx->device));
+	float4* d = nullptr;
+	if(dalloc(&d, n) != hipSuccess) {
+		(void) hipGetLastError();
+		return fail(ctx, MPM_ERR_CAPACITY, "collision volume: no device memory for the table of " + std::to_string(n) + " samples");
+	}
+	if(hipError_t e = hipMemcpy(d, field4, sizeof(float4) * n, hipMemcpyHostToDevice)) {
+		hipFree(d);
+		return fail(ctx, MPM_ERR_DEVICE, std::string("collision volume: copying the table -> ") + hipGetErrorString(e));
+	}
+	v.table						  = d;
+	const mpm_collision_volume dsc = volume_descriptor(v, vol->pad);
+	return install_slot(ctx, slot, c, Heightfield {}, obj, v, &dsc);
+}
+
+// Order, as for mpm_set_collision_mesh: every host check, then the table and the records are allocated beside the slot's old occupant, the
+// table is filled, and only then does install_slot free the old occupant's: a refusal - invalid mesh or box, no memory, a device error -
+// leaves the slot, the clock and every other slot as they were.
+int mpm_set_collision_volume_mesh(mpm_ctx* ctx, int slot, const mpm_collision_object* obj, const mpm_collision_volume* vol, const float* verts, size_t nv, const int32_t* tris, size_t nt) {
+	if(!ctx) return MPM_ERR_INVALID;
+	if(slot < 0 || slot >= MPM_MAX_COLLISION_SHAPES) return fail(ctx, MPM_ERR_INVALID, "collision volume: slot outside 0..3");
+	if(!obj) return install_slot(ctx, slot, ShapeSlot {}, Heightfield {}, nullptr);
+	if(!vol) return fail(ctx, MPM_ERR_INVALID, "collision volume: obj without vol");
+	if(!verts || !tris) return fail(ctx, MPM_ERR_INVALID, "collision volume: NULL verts or tris");
+	ShapeSlot c {};
+	Volume v {};
+	if(const char* msg = make_volume_slot(obj, vol, true, c, v)) return fail(ctx, MPM_ERR_INVALID, msg);
+	std::vector<MeshTri> rec;
+	std::vector<MeshPseudo> pseudo;
+	MeshReport rep;
+	mesh_build(verts, nv, tris, nt, MPM_MESH_MAX_VERTICES, MPM_MESH_MAX_TRIANGLES, rec, pseudo, rep);
+	if(!rep.reason.empty()) return fail(ctx, MPM_ERR_INVALID, "collision volume: " + rep.reason);
+	int pad = vol->pad;
+	if(v.dims[0] == 0) {
+		pad = pad ? pad : 2;
+		if(!volume_autosize(verts, nv, v.spacing, pad, v.origin, v.dims))
+			return fail(ctx, MPM_ERR_INVALID, "collision volume: dims sized from the mesh's bounding box, spacing and pad leave 2..1024 per axis or 2^27 samples");
+	}
+	float extent = 0.f;// largest coordinate magnitude in play: a vertex's or a box corner's
+	for(size_t i = 0; i < 3 * nv; ++i) extent = std::max(extent, std::fabs(verts[i]));
+	for(int d = 0; d < 3; ++d) extent = std::max(extent, std::max(std::fabs(v.origin[d]), std::fabs(v.origin[d] + (float) (v.dims[d] - 1) * v.spacing)));
+	HIP_TRY(hipSetDevice(ctx->device));
+	HIP_TRY(hipDeviceSynchronize());
+	const size_t n = (size_t) v.dims[0] * (size_t) v.dims[1] * (size_t) v.dims[2];
+	float4* table  = nullptr;
+	DevScratch<MeshTri> d_rec;
+	DevScratch<MeshPseudo> d_pseudo;
+	if(dalloc(&table, n) != hipSuccess || dalloc(&d_rec.p, nt) != hipSuccess || dalloc(&d_pseudo.p, nt) != hipSuccess) {
+		(void) hipGetLastError();
+		if(table) hipFree(table);
+		return fail(ctx, MPM_ERR_CAPACITY, "collision volume: no device memory for the table of " + std::to_string(n) + " samples and " + std::to_string(nt) + " triangle records");
+	}
+	hipError_t e = hipMemcpy(d_rec.p, rec.data(), sizeof(MeshTri) * nt, hipMemcpyHostToDevice);
+	if(e == hipSuccess) e = hipMemcpy(d_pseudo.p, pseudo.data(), sizeof(MeshPseudo) * nt, hipMemcpyHostToDevice);
+	if(e == hipSuccess) {
+		const float slack	 = std::max(0.25f * v.spacing, extent * 0x1p-12f);
+		const unsigned tiles = (unsigned) ((v.dims[0] + 3) >> 2) * (unsigned) ((v.dims[1] + 3) >> 2) * (unsigned) ((v.dims[2] + 3) >> 2);
+		collision_volume_mesh_kernel<<<tiles, 64, 0, ctx->s_compute>>>(d_rec.p, d_pseudo.p, (int) nt, v.dims[0], v.dims[1], v.dims[2], v.origin[0], v.origin[1], v.origin[2], v.spacing, slack, table);
+		e = hipGetLastError();
+	}
+	if(e == hipSuccess) e = hipStreamSynchronize(ctx->s_compute);
+	if(e != hipSuccess) {
+		hipFree(table);
+		return fail(ctx, MPM_ERR_DEVICE, std::string("collision volume: building the table -> ") + hipGetErrorString(e));
+	}
+	v.table						  = table;
+	const mpm_collision_volume dsc = volume_descriptor(v, pad);
+	return install_slot(ctx, slot, c, Heightfield {}, obj, v, &dsc);
+}
+
+int mpm_get_collision_volume(mpm_ctx* ctx, int slot, mpm_collision_volume* vol_out, const int lo[3], const int dims[3], float* out4) {
+	if(!ctx) return MPM_ERR_INVALID;
+	if(slot < 0 || slot >= MPM_MAX_COLLISION_SHAPES) return fail(ctx, MPM_ERR_INVALID, "collision volume: slot outside 0..3");
+	if(ctx->shape[slot].shape.kind != kShapeVolume || !ctx->vol[slot].table) return fail(ctx, MPM_ERR_INVALID, "collision volume: the slot holds no volume");
+	const Volume& v = ctx->vol[slot];
+	if(out4) {
+		if(!lo || !dims) return fail(ctx, MPM_ERR_INVALID, "collision volume: out4 without lo or dims");
+		for(int d = 0; d < 3; ++d) {
+			if(dims[d] < 1) return fail(ctx, MPM_ERR_INVALID, "collision volume: a dims entry of the box < 1");
+			if(lo[d] < 0 || lo[d] >= v.dims[d] || dims[d] > v.dims[d] - lo[d]) return fail(ctx, MPM_ERR_INVALID, "collision volume: the box leaves the table");
+		}
+	}
+	if(vol_out) *vol_out = ctx->vol_desc[slot];
+	if(!out4) return MPM_OK;
+	const size_t n = (size_t) dims[0] * (size_t) dims[1] * (size_t) dims[2];
+	HIP_TRY(hipSetDevice(ctx->device));
+	DevScratch<float4> stage;
+	if(dalloc(&stage.p, n) != hipSuccess) {
+		(void) hipGetLastError();
+		return fail(ctx, MPM_ERR_CAPACITY, "collision volume: no device memory for the box");
+	}
+	collision_volume_box_kernel<<<cdiv(n, 256), 256, 0, ctx->s_compute>>>(v.table, v.dims[1], v.dims[2], lo[0], lo[1], lo[2], dims[0], dims[1], dims[2], stage.p);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipStreamSynchronize(ctx->s_compute));
 	HIP_TRY(hipMemcpy(out4, stage.p, sizeof(float4) * n, hipMemcpyDeviceToHost));
@@ -2144,14 +2314,14 @@ int mpm_test_stress(int material, const mpm_material_params* p, const float* F, 
 	return MPM_OK;
 }
 
-// The shared half of the two collider queries below: points up, test_collision_query_kernel, four floats per point down
-static int test_collision_query(ShapeSlot c, const Heightfield& f, float time, const float* xyz, size_t n, float* out4) {
+// The shared half of the three collider queries below: points up, test_collision_query_kernel, four floats per point down
+static int test_collision_query(ShapeSlot c, const Heightfield& f, float time, const float* xyz, size_t n, float* out4, const Volume& vol = Volume {}) {
 	c.pose = collision_pose(c.obj, time);
 	DevScratch<float> dX, dO;
 	HIP_TRY0(dX.alloc(3 * n));
 	HIP_TRY0(dO.alloc(4 * n));
 	HIP_TRY0(hipMemcpy(dX.p, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
-	test_collision_query_kernel<<<cdiv(n, 256), 256>>>(c, f, n, dX.p, dO.p);
+	test_collision_query_kernel<<<cdiv(n, 256), 256>>>(c, f, vol, n, dX.p, dO.p);
 	HIP_TRY0(hipGetLastError());
 	HIP_TRY0(hipMemcpy(out4, dO.p, sizeof(float) * 4 * n, hipMemcpyDeviceToHost));
 	return MPM_OK;
@@ -2180,6 +2350,21 @@ int mpm_test_collision_heightfield(const mpm_collision_object* obj, const mpm_he
 	HIP_TRY0(hipMemcpy(dT.p, table.data(), sizeof(float4) * cells, hipMemcpyHostToDevice));
 	f.table = dT.p;
 	return test_collision_query(c, f, time, xyz, n, out4);
+}
+
+int mpm_test_collision_volume(const mpm_collision_object* obj, const mpm_collision_volume* vol, const float* field4, float time, const float* xyz, size_t n, float* out4, int device) {
+	if(!obj || !vol || !field4 || !xyz || !out4 || n == 0) return MPM_ERR_INVALID;
+	ShapeSlot c {};
+	Volume v {};
+	if(make_volume_slot(obj, vol, false, c, v)) return MPM_ERR_INVALID;
+	const size_t cells = (size_t) v.dims[0] * (size_t) v.dims[1] * (size_t) v.dims[2];
+	if(!volume_samples_finite(field4, cells)) return MPM_ERR_INVALID;
+	HIP_TRY0(hipSetDevice(device));
+	DevScratch<float4> dT;
+	HIP_TRY0(dT.alloc(cells));
+	HIP_TRY0(hipMemcpy(dT.p, field4, sizeof(float4) * cells, hipMemcpyHostToDevice));
+	v.table = dT.p;
+	return test_collision_query(c, Heightfield {}, time, xyz, n, out4, v);
 }
 
 int mpm_streams(mpm_ctx* ctx, void** compute_stream, void** comm_stream) {

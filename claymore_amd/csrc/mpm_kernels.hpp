@@ -34,6 +34,7 @@
 #include "mpm_collision.hpp"
 #include "mpm_collision_shapes.hpp"
 #include "mpm_collision_heightfield.hpp"
+#include "mpm_collision_volume.hpp"
 
 namespace mpm {
 
@@ -308,8 +309,8 @@ __global__ __launch_bounds__(256) void grid_update_kernel(GridCfg cfg, const int
 	}
 }
 
-// Grid update with a collider (the level-set collision object; analytic shapes and heightfields: extensions).  The kinds differ in what
-// travels by value to the kernel - CollisionArgs, ShapeArgs, TerrainArgs - and in the grid_cell overload that treats one cell with it; the
+// Grid update with a collider (the level-set collision object; analytic shapes, heightfields and volumes: extensions).  The kinds differ in what
+// travels by value to the kernel - CollisionArgs, ShapeArgs, TerrainArgs, VolumeColliderArgs - and in the grid_cell overload that treats one cell with it; the
 // two frames around a cell (grid_update_collider_kernel here, carry_grid_kernel behind the rebuild's kernels) are written once.
 //
 // Level-set collision object (second update_grid_velocity_query_max overload, Projects/MGSP/mgmpm_kernels.cuh:323-399): reports the
@@ -343,6 +344,15 @@ constexpr int kShapeHeightfield = 5;
 struct TerrainArgs {
 	ShapeArgs col;
 	Heightfield hf[kMaxShapes];
+};
+// A volume in at least one slot (mpm_collision_volume.hpp): a slot whose shape.kind is kShapeVolume (another number mpm_set_collision_shape
+// refuses) reads vol[slot]: the table pointer, dims, origin and spacing travel by value beside the slot.  The kind is wave-uniform (a scalar
+// branch); the eight corner loads are read-only float4 gathers, in range by volume_query's own footprint check.  Heightfields may sit in the
+// other slots, so the terrain's arguments ride along; a context without a volume passes one of the types above, whose code has no such branch.
+constexpr int kShapeVolume = 6;
+struct VolumeColliderArgs {
+	TerrainArgs ter;
+	Volume vol[kMaxShapes];
 };
 
 // The two ends every grid_cell overload shares, so that a change is made once.  Prologue: momentum -> velocity with the walls' zeroes and
@@ -393,14 +403,18 @@ MPM_DEV float grid_cell(const GridCfg& cfg, const CollisionArgs& col, int kx, in
 	collision_resolve(col.obj, col.pose, node, cfg.dx, cfg.G * 4, (float) cfg.boundary * cfg.dx * 4.f, (float) (cfg.G - cfg.boundary) * 4.f * cfg.dx, vel);
 	return grid_cell_store_doubled_q(vel, v);
 }
-// The same for ShapeArgs and for TerrainArgs, one function: the prologue + the optional field object + the slot loop.  The heightfield branch
-// is compiled in for TerrainArgs alone (no run-time test of a table pointer), so without a heightfield the code is that of the analytic shapes.
+// The same for ShapeArgs, TerrainArgs and VolumeColliderArgs, one function: the prologue + the optional field object + the slot loop.  The heightfield
+// branch is compiled in for TerrainArgs (and VolumeColliderArgs, which carries one) alone, the volume branch for VolumeColliderArgs alone (no run-time test of
+// a table pointer), so without a heightfield the code is that of the analytic shapes and without a volume that of the terrain.
 MPM_DEV const ShapeArgs& shape_args(const ShapeArgs& a) { return a; }
 MPM_DEV const ShapeArgs& shape_args(const TerrainArgs& a) { return a.col; }
+MPM_DEV const ShapeArgs& shape_args(const VolumeColliderArgs& a) { return a.ter.col; }
+MPM_DEV const TerrainArgs& terrain_args(const TerrainArgs& a) { return a; }
+MPM_DEV const TerrainArgs& terrain_args(const VolumeColliderArgs& a) { return a.ter; }
 template<class Args>
 MPM_DEV float grid_cell(const GridCfg& cfg, const Args& a, int kx, int ky, int kz, int cell, float dt, float4& v) {
 #pragma clang fp contract(off)
-	static_assert(std::is_same_v<Args, ShapeArgs> || std::is_same_v<Args, TerrainArgs>, "a collider kind needs its grid_cell");
+	static_assert(std::is_same_v<Args, ShapeArgs> || std::is_same_v<Args, TerrainArgs> || std::is_same_v<Args, VolumeColliderArgs>, "a collider kind needs its grid_cell");
 	const ShapeArgs& col = shape_args(a);
 	float vel[3];
 	int node[3];
@@ -409,9 +423,14 @@ MPM_DEV float grid_cell(const GridCfg& cfg, const Args& a, int kx, int ky, int k
 	const float X[3] = {(float) node[0] * cfg.dx, (float) node[1] * cfg.dx, (float) node[2] * cfg.dx};
 #pragma nounroll
 	for(int s = 0; s < col.count; ++s) {
-		if constexpr(std::is_same_v<Args, TerrainArgs>)
+		if constexpr(std::is_same_v<Args, TerrainArgs> || std::is_same_v<Args, VolumeColliderArgs>)
 			if(col.slot[s].shape.kind == kShapeHeightfield) {
-				heightfield_resolve(col.slot[s].obj, col.slot[s].pose, a.hf[s], X, vel);
+				heightfield_resolve(col.slot[s].obj, col.slot[s].pose, terrain_args(a).hf[s], X, vel);
+				continue;
+			}
+		if constexpr(std::is_same_v<Args, VolumeColliderArgs>)
+			if(col.slot[s].shape.kind == kShapeVolume) {
+				volume_resolve(col.slot[s].obj, col.slot[s].pose, a.vol[s], X, vel);
 				continue;
 			}
 		if(col.slot[s].shape.kind != 0) shape_resolve(col.slot[s].obj, col.slot[s].pose, col.slot[s].shape, X, vel);
@@ -441,9 +460,9 @@ __global__ __launch_bounds__(256) void grid_update_collider_kernel(GridCfg cfg, 
 	}
 	wave_max_vel(vel_sqr, max_vel_bits);
 }
-// mpm_test_collision_shape, mpm_test_collision_heightfield: signed distance and normal of one collider (a heightfield where the slot's kind
-// says so, with its table in f) at arbitrary domain points, through the collider's material point
-__global__ void test_collision_query_kernel(ShapeSlot c, Heightfield f, size_t n, const float* __restrict__ xyz, float* __restrict__ out4) {
+// mpm_test_collision_shape, mpm_test_collision_heightfield, mpm_test_collision_volume: signed distance and normal of one collider (a heightfield
+// or a volume where the slot's kind says so, with its table in f or in vol) at arbitrary domain points, through the collider's material point
+__global__ void test_collision_query_kernel(ShapeSlot c, Heightfield f, Volume vol, size_t n, const float* __restrict__ xyz, float* __restrict__ out4) {
 	const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
 	if(i >= n) return;
 	const float X[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
@@ -451,6 +470,8 @@ __global__ void test_collision_query_kernel(ShapeSlot c, Heightfield f, size_t n
 	collision_material_point(c.obj, c.pose, X, xmt, x);
 	if(c.shape.kind == kShapeHeightfield)
 		heightfield_query(f, x, sdis, nrm);
+	else if(c.shape.kind == kShapeVolume)
+		volume_query(vol, x, sdis, nrm);
 	else
 		shape_query(c.shape, x, sdis, nrm);
 	out4[4 * i]		= sdis;
@@ -1033,7 +1054,7 @@ __global__ __launch_bounds__(256) void register_blocks_kernel(GridCfg cfg, const
 // grid.  Used between the substeps of mpm_run_fixed, where the next dt is known and nobody looks at the grid in between.
 // Runs between the neighbour and the exterior registration: the new neighbour count is the sum of the first two phase counters, the
 // published status[ST_NBC] is still the OLD one (the exterior registration publishes the new one).
-// Collider (with UPDATE) CollisionArgs, ShapeArgs or TerrainArgs: the update is that collider's (its grid_cell overload, the statements of
+// Collider (with UPDATE) CollisionArgs, ShapeArgs, TerrainArgs or VolumeColliderArgs: the update is that collider's (its grid_cell overload, the statements of
 // grid_update_collider_kernel<Collider>) with what it needs in `col`; NoCollision is an empty struct and the kernel is the plain one.
 template<bool UPDATE, class Collider = NoCollision>
 __global__ __launch_bounds__(256) void carry_grid_kernel(GridCfg cfg, const int* __restrict__ status, const int* __restrict__ new_keys, const int* __restrict__ old_table, const float* __restrict__ p2g_grid, float* __restrict__ grid, float dt, unsigned* __restrict__ max_vel_bits, Collider col) {

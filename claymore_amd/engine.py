@@ -422,6 +422,80 @@ class Engine:
         if animate:
             self.set_collision_clock(True, float(obj.time))
 
+    def _collision_obj(self, fields):
+        obj = _ffi.CollisionObject()
+        self._check(self.api.default_collision_object(C.byref(obj)))
+        for k, v in fields.items():
+            cur = getattr(obj, k)
+            if hasattr(cur, "__len__"):
+                for i, x in enumerate(np.asarray(v, dtype=np.float32).ravel()):
+                    cur[i] = float(x)
+            else:
+                setattr(obj, k, v)
+        return obj
+
+    def set_collision_volume(self, slot, field4=None, *, origin=(0.0, 0.0, 0.0), spacing=None, inside_out=False, animate=False, **fields):
+        """Install a volume - a local level-set box - in slot 0 .. 3 (mpm_set_collision_volume, HIP engine only).  field4: an array of shape
+        [d0, d1, d2, 4] = {sdis, gx, gy, gz} per sample, sample (i, j, k) at material origin + (i, j, k) spacing; field4=None empties the
+        slot.  inside_out: sdis and n change sign at the query.  fields: those of set_collision_object (type, friction, scale, dsdt, trans,
+        trans_vel, omega, rot_mat, time).  Outside the table's footprint the collider touches nothing.  The slots are the shapes'
+        (set_collision_shape); every install leaves the one clock stopped at `time`."""
+        if field4 is None:
+            self._check(self.api.set_collision_volume(self.ctx, int(slot), None, None, None))
+            return
+        if spacing is None:
+            raise ValueError("set_collision_volume: spacing is required")
+        obj = self._collision_obj(fields)
+        t = np.ascontiguousarray(field4, dtype=np.float32)
+        if t.ndim != 4 or t.shape[3] != 4:
+            raise ValueError(f"set_collision_volume: field4 must be [d0, d1, d2, 4], got shape {t.shape}")
+        vol = _ffi.CollisionVolume()
+        for d in range(3):
+            vol.dims[d], vol.origin[d] = t.shape[d], float(origin[d])
+        vol.spacing = float(spacing)
+        vol.inside_out = 1 if inside_out else 0
+        self._check(self.api.set_collision_volume(self.ctx, int(slot), C.byref(obj), C.byref(vol), t.ctypes.data))
+        if animate:
+            self.set_collision_clock(True, float(obj.time))
+
+    def set_collision_volume_mesh(self, slot, vertices, faces, *, spacing=None, origin=None, dims=None, pad=2, inside_out=False, animate=False, **fields):
+        """Install a volume built on the device from a closed triangle mesh (mpm_set_collision_volume_mesh, HIP engine only).  vertices: (nv, 3)
+        in material coordinates; faces: (nt, 3), counter-clockwise seen from outside.  dims=None: the box is sized from the mesh's bounding
+        box with `pad` cells of margin (origin is then not used); else origin and dims give the box.  collision_volume(slot) returns the
+        descriptor as installed.  fields: those of set_collision_object."""
+        if spacing is None:
+            raise ValueError("set_collision_volume_mesh: spacing is required")
+        if dims is not None and origin is None:
+            raise ValueError("set_collision_volume_mesh: dims without origin")
+        obj = self._collision_obj(fields)
+        v = np.ascontiguousarray(vertices, dtype=np.float32)
+        f = np.ascontiguousarray(faces, dtype=np.int32)
+        if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+            raise ValueError(f"set_collision_volume_mesh: vertices must be (nv, 3) and faces (nt, 3), got {v.shape} and {f.shape}")
+        vol = _ffi.CollisionVolume()
+        for d in range(3):
+            vol.dims[d] = 0 if dims is None else int(dims[d])
+            vol.origin[d] = 0.0 if dims is None else float(origin[d])
+        vol.spacing = float(spacing)
+        vol.inside_out = 1 if inside_out else 0
+        vol.pad = int(pad)
+        self._check(self.api.set_collision_volume_mesh(self.ctx, int(slot), C.byref(obj), C.byref(vol), v.ctypes.data, v.shape[0], f.ctypes.data, f.shape[0]))
+        if animate:
+            self.set_collision_clock(True, float(obj.time))
+
+    def collision_volume(self, slot, lo=None, shape=None):
+        """The volume in `slot` (mpm_get_collision_volume): (descriptor, array) with descriptor = dict(dims, origin, spacing, inside_out, pad)
+        as installed and array = (b0, b1, b2, 4) float32 {sdis, gx, gy, gz} of the samples lo + [0, shape), bit for bit.  lo=None: from
+        sample (0, 0, 0); shape=None: to the end of the table."""
+        vol = _ffi.CollisionVolume()
+        self._check(self.api.get_collision_volume(self.ctx, int(slot), C.byref(vol), None, None, None))
+        desc = dict(dims=tuple(vol.dims), origin=tuple(np.float32(x) for x in vol.origin), spacing=np.float32(vol.spacing), inside_out=bool(vol.inside_out), pad=int(vol.pad))
+        lo = [0, 0, 0] if lo is None else [int(x) for x in lo]
+        shape = [desc["dims"][d] - lo[d] for d in range(3)] if shape is None else [int(x) for x in shape]
+        out = np.empty(tuple(shape) + (4,) if min(shape) >= 1 else (1,), dtype=np.float32)
+        self._check(self.api.get_collision_volume(self.ctx, int(slot), None, (C.c_int * 3)(*lo), (C.c_int * 3)(*shape), out.ctypes.data))
+        return desc, out
+
     def collision_field(self, lo=(0, 0, 0), shape=None):
         """The installed level-set field, however it was installed (mpm_get_collision_field): (d0, d1, d2, 4) float32 {sdis, gx, gy, gz} of
         the nodes lo + [0, shape), bit for bit.  shape=None: from lo to the end of the domain."""
@@ -603,6 +677,10 @@ def build_engine(scene, device=0, api=None):
     for slot, c in enumerate(colliders):
         if c.get("kind") == "heightfield":
             eng.set_collision_heightfield(slot, **{**{k: v for k, v in c.items() if k != "kind"}, "animate": False})
+        elif c.get("kind") == "volume":
+            eng.set_collision_volume(slot, **{**{k: v for k, v in c.items() if k != "kind"}, "animate": False})
+        elif c.get("kind") == "volume_mesh":
+            eng.set_collision_volume_mesh(slot, **{**{k: v for k, v in c.items() if k != "kind"}, "animate": False})
         else:
             eng.set_collision_shape(slot, **{**c, "animate": False})
     # one clock for all colliders: started once, after the last install (every install stops it)

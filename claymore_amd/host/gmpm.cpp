@@ -118,8 +118,75 @@ bool vec3(const mj::Value& v, const char* k, float (&out)[3]) {
 	return true;
 }
 
+// The fields every entry of "colliders" shares: "type": "sticky|slip|separate", "friction", "velocity", "omega" (either of the last two makes it move).
+bool parse_collider_motion(const mj::Value& c, mpm_collision_object& obj, bool& moving) {
+	const std::string type = c.has("type") ? c["type"].string() : "sticky";
+	obj.type			   = type == "sticky" ? MPM_BOUNDARY_STICKY : type == "slip" ? MPM_BOUNDARY_SLIP : type == "separate" ? MPM_BOUNDARY_SEPARATE : -1;
+	if(obj.type < 0) {
+		std::fprintf(stderr, "gmpm: unknown collider type '%s' (expected sticky, slip or separate)\n", type.c_str());
+		return false;
+	}
+	obj.friction = num(c, "friction", obj.friction);
+	if(vec3(c, "velocity", obj.trans_vel)) moving = true;
+	if(vec3(c, "omega", obj.omega)) moving = true;
+	return true;
+}
+
+// The two entries of "colliders" that install a volume - a local level-set box (mpm_set_collision_volume_mesh / mpm_set_collision_volume):
+// {"shape": "mesh", "file": "body.obj", "spacing": s, "pad": 2, "scale": .., "offset": [..]}: the OBJ file's vertices, times the uniform scale,
+//   plus the offset, sampled `spacing` apart in a box sized from the mesh with `pad` cells of margin; fills verts / tris;
+// {"shape": "volume", "dims": [d0, d1, d2], "origin": [x, y, z], "spacing": s, "file": "body.f32"}: d0 d1 d2 samples {sdis, gx, gy, gz} of raw
+//   little-endian float32, sample (i, j, k) at (i d1 + j) d2 + k; fills field4;
+// both with the shared "type", "friction", "velocity", "omega" and "inside_out"; files are relative to the scene file.  They turn about the origin.
+bool parse_volume_collider(const mj::Value& c, const std::string& shape, mpm_collision_object& obj, mpm_collision_volume& vol, bool& moving, std::vector<float>& verts, std::vector<int32_t>& tris,
+						   std::vector<float>& field4, const std::string& scene_dir) {
+	mpm_default_collision_object(&obj);
+	std::memset(&vol, 0, sizeof(vol));
+	if(!c.has("file") || !c.has("spacing")) {
+		std::fprintf(stderr, "gmpm: collider '%s' lacks a field (file, spacing)\n", shape.c_str());
+		return false;
+	}
+	const std::string name = c["file"].string();
+	const std::string path = !name.empty() && name[0] == '/' ? name : scene_dir + "/" + name;
+	vol.spacing			   = num(c, "spacing", 0.f);
+	vol.inside_out		   = c.has("inside_out") && c["inside_out"].type == mj::Value::Bool && c["inside_out"].b;
+	if(shape == "mesh") {
+		if(!pio::read_obj_mesh(path, verts, tris) || verts.empty()) {
+			std::fprintf(stderr, "gmpm: collider mesh file '%s' cannot be read as an OBJ mesh\n", path.c_str());
+			return false;
+		}
+		const float scale = num(c, "scale", 1.f);
+		float offset[3]	  = {0.f, 0.f, 0.f};
+		vec3(c, "offset", offset);
+		for(size_t i = 0; i < verts.size(); ++i) verts[i] = verts[i] * scale + offset[i % 3];
+		vol.pad = (int) num(c, "pad", 2.f);
+	} else {
+		if(!c.has("dims") || c["dims"].type != mj::Value::Array || c["dims"].arr.size() != 3 || !vec3(c, "origin", vol.origin)) {
+			std::fprintf(stderr, "gmpm: collider 'volume' needs \"dims\": [d0, d1, d2] and \"origin\": [x, y, z]\n");
+			return false;
+		}
+		size_t n = 4;
+		for(int d = 0; d < 3; ++d) {
+			const double v = c["dims"][d].number();
+			vol.dims[d]	   = (int) v;
+			if((double) vol.dims[d] != v || vol.dims[d] < 2 || vol.dims[d] > MPM_VOLUME_MAX_SAMPLES) {
+				std::fprintf(stderr, "gmpm: volume dims must be whole numbers 2 .. %d\n", (int) MPM_VOLUME_MAX_SAMPLES);
+				return false;
+			}
+			n *= (size_t) vol.dims[d];
+		}
+		field4.assign(n, 0.f);
+		std::ifstream f(path, std::ios::binary);
+		if(!f || !f.read(reinterpret_cast<char*>(field4.data()), (std::streamsize) (n * sizeof(float))) || f.peek() != std::ifstream::traits_type::eof()) {
+			std::fprintf(stderr, "gmpm: volume file '%s' does not hold exactly %zu float32 values\n", path.c_str(), n);
+			return false;
+		}
+	}
+	return parse_collider_motion(c, obj, moving);
+}
+
 // One entry of "colliders": {"shape": "halfspace" ("point", "normal") | "sphere" ("center", "radius") | "box" ("center", "half_extents") |
-// "capsule" ("a", "b", "radius") | "heightfield" (below), "type": "sticky|slip|separate", "friction", "velocity", "omega", "inside_out"}.  A collider with
+// "capsule" ("a", "b", "radius") | "heightfield" (below) | "mesh" | "volume" (parse_volume_collider above), "type": "sticky|slip|separate", "friction", "velocity", "omega", "inside_out"}.  A collider with
 // "velocity" or "omega" moves: it translates, and turns about its point / center / a, with the context's clock, which then starts at 0.
 // {"shape": "heightfield", "nx", "nz", "origin": [x, z], "spacing", "heights": [nx nz numbers, sample (i, k) at i nz + k] | "file": "name.f32"
 // (raw little-endian float32, nx nz values, relative to the scene file)} with the same "type", "friction", "velocity", "omega", "inside_out"
@@ -187,7 +254,7 @@ bool parse_collider(const mj::Value& c, mpm_collision_object& obj, mpm_collision
 		sh.kind = MPM_SHAPE_CAPSULE;
 		ok		= vec3(c, "a", sh.a) && vec3(c, "b", sh.b) && c.has("radius");
 	} else {
-		std::fprintf(stderr, "gmpm: unknown collider shape '%s' (expected halfspace, sphere, box, capsule or heightfield)\n", shape.c_str());
+		std::fprintf(stderr, "gmpm: unknown collider shape '%s' (expected halfspace, sphere, box, capsule, heightfield, mesh or volume)\n", shape.c_str());
 		return false;
 	}
 	if(!ok) {
@@ -196,17 +263,8 @@ bool parse_collider(const mj::Value& c, mpm_collision_object& obj, mpm_collision
 	}
 	sh.radius			   = num(c, "radius", 0.f);
 	sh.inside_out		   = c.has("inside_out") && c["inside_out"].type == mj::Value::Bool && c["inside_out"].b;
-	const std::string type = c.has("type") ? c["type"].string() : "sticky";
-	obj.type			   = type == "sticky" ? MPM_BOUNDARY_STICKY : type == "slip" ? MPM_BOUNDARY_SLIP : type == "separate" ? MPM_BOUNDARY_SEPARATE : -1;
-	if(obj.type < 0) {
-		std::fprintf(stderr, "gmpm: unknown collider type '%s' (expected sticky, slip or separate)\n", type.c_str());
-		return false;
-	}
-	obj.friction = num(c, "friction", obj.friction);
 	for(int d = 0; d < 3; ++d) obj.trans[d] = sh.a[d];// the pivot of omega
-	if(vec3(c, "velocity", obj.trans_vel)) moving = true;
-	if(vec3(c, "omega", obj.omega)) moving = true;
-	return true;
+	return parse_collider_motion(c, obj, moving);
 }
 
 // The rows of xyz (n x 3 floats) in ascending order of their bits (x, then y, then z, as unsigned integers): two readouts of one state hold
@@ -464,6 +522,17 @@ int main(int argc, char** argv) {
 			mpm_collision_shape sh;
 			mpm_heightfield hf;
 			std::vector<float> heights;
+			const std::string shape = cols[ci].has("shape") ? cols[ci]["shape"].string() : "";
+			if(shape == "mesh" || shape == "volume") {// a volume in this slot, built from an OBJ mesh or given as samples
+				mpm_collision_volume vol;
+				std::vector<float> verts, field4;
+				std::vector<int32_t> tris;
+				if(!parse_volume_collider(cols[ci], shape, obj, vol, moving, verts, tris, field4, scene_dir)) return 1;
+				rc = shape == "mesh" ? mpm_set_collision_volume_mesh(ctx, (int) ci, &obj, &vol, verts.data(), verts.size() / 3, tris.data(), tris.size() / 3)
+									 : mpm_set_collision_volume(ctx, (int) ci, &obj, &vol, field4.data());
+				if(rc) die(ctx, rc);
+				continue;
+			}
 			if(!parse_collider(cols[ci], obj, sh, moving, hf, heights, scene_dir)) return 1;
 			rc = hf.nx ? mpm_set_collision_heightfield(ctx, (int) ci, &obj, &hf, heights.data()) : mpm_set_collision_shape(ctx, (int) ci, &obj, &sh);
 			if(rc) die(ctx, rc);

@@ -1,5 +1,5 @@
 // host_selftest.cpp — exercises the pieces of the host drivers that need no GPU (JSON reader, lattice sampler, BGEO
-// writer, NumPy writer, OBJ reader, the collision mesh's validation and closest-point functions, the mesh-sampled model per point).  usage: host_selftest <out.bgeo>  -> prints "json_ok <n_models> <dt>", "sphere <count>", "bgeo <bytes>"
+// writer, NumPy writer, OBJ reader, the collision mesh's validation and closest-point functions, the mesh-sampled model per point, the volume collider's query per point).  usage: host_selftest <out.bgeo>  -> prints "json_ok <n_models> <dt>", "sphere <count>", "bgeo <bytes>"
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -8,6 +8,12 @@
 #include "particle_io.hpp"
 #include "../csrc/mpm_collision_mesh.hpp"
 #include "../csrc/mpm_mesh_fill.hpp"
+#if !defined(__HIPCC__)
+struct float4 {
+	float x, y, z, w;
+};
+#endif
+#include "../csrc/mpm_collision_volume.hpp"
 
 int main(int argc, char** argv) {
 	if(argc == 4 && !std::strcmp(argv[1], "--bgeo-from")) {// host_selftest --bgeo-from points.f32 out.bgeo: raw float32 xyz -> BGEO frame
@@ -103,6 +109,37 @@ int main(int argc, char** argv) {
 			std::memcpy(&w[0], &q, 4);
 			std::memcpy(&w[1], out, 16);
 			std::printf("%d %d %08x %08x %08x %08x %08x\n", T, feature, w[0], w[1], w[2], w[3], w[4]);
+		}
+		return 0;
+	}
+	if(argc == 12 && !std::strcmp(argv[1], "--volume-query")) {// host_selftest --volume-query TABLE.f32 d0 d1 d2 o0 o1 o2 SPACING INSIDE_OUT POINTS.f32: per material
+		mpm::Volume f {};										 // point "sdis nx ny nz" (their bits in hex) from the x86 build of the kernels' own volume_query
+		for(int d = 0; d < 3; ++d) {
+			f.dims[d]	= std::atoi(argv[3 + d]);
+			f.origin[d] = std::strtof(argv[6 + d], nullptr);
+			if(f.dims[d] < mpm::kVolumeMinSamples || f.dims[d] > mpm::kVolumeMaxSamples) return 5;
+		}
+		f.spacing	 = std::strtof(argv[9], nullptr);
+		f.inside_out = std::atoi(argv[10]) ? 1 : 0;
+		std::vector<float> arr[2];
+		for(int a = 0; a < 2; ++a) {
+			std::ifstream in(argv[a ? 11 : 2], std::ios::binary | std::ios::ate);
+			if(!in) return 3;
+			const size_t bytes = (size_t) in.tellg();
+			arr[a].resize(bytes / sizeof(float));
+			in.seekg(0);
+			in.read(reinterpret_cast<char*>(arr[a].data()), (std::streamsize) bytes);
+		}
+		if(arr[0].size() != 4 * (size_t) f.dims[0] * (size_t) f.dims[1] * (size_t) f.dims[2] || arr[1].size() % 3) return 5;
+		f.table = reinterpret_cast<const float4*>(arr[0].data());
+		for(size_t i = 0; i < arr[1].size() / 3; ++i) {
+			const float x[3] = {arr[1][3 * i], arr[1][3 * i + 1], arr[1][3 * i + 2]};
+			float w[4], n[3];
+			mpm::volume_query(f, x, w[0], n);
+			std::memcpy(&w[1], n, 12);
+			uint32_t b[4];
+			std::memcpy(b, w, 16);
+			std::printf("%08x %08x %08x %08x\n", b[0], b[1], b[2], b[3]);
 		}
 		return 0;
 	}

@@ -384,3 +384,25 @@ def mesh_drop(bits=6, radius_cells=9.0, center=(0.5, 0.3, 0.5), material=FIXED_C
     vertices, faces = icosphere(center, radius_cells / (1 << bits), subdivisions)
     return {"name": "mesh_drop", "bits": bits, "dt": 1e-4, "config": {"max_ppc": 128},
             "models": [{"material": material, "mesh": {"vertices": vertices, "faces": faces, "margin": margin}, "v0": (0, 0, 0), "params": prm}]}
+
+
+def two_paddles(bits=6, radius_cells=6.0, paddle_cells=(3.0, 10.0, 10.0), gap_cells=2.0, speed=1.0, boundary="slip", friction=0.3, spacing_cells=0.5, pad=2,
+                material=FIXED_COROTATED, shape="box", subdivisions=2, dt=1e-4):
+    """A sphere_drop-sized ball at rest between two mesh bodies - volumes in slots 0 and 1 (Engine.set_collision_volume_mesh), each built on
+    the device from a box_mesh (shape="box") or an icosphere (shape="icosphere", radius paddle_cells[1] / 2) sampled spacing_cells dx apart -
+    that move toward each other along x at +-speed on the one running clock: two mesh colliders in one context, each with its own trans_vel.
+    The paddles start gap_cells dx off the ball; no gravity, so the material's x momentum comes from the paddles alone."""
+    n = 1 << bits
+    dx = 1.0 / n
+    prm = {"volume": _vol(bits)} if material != SAND else {}
+    c = np.array([0.5, 0.5, 0.5])
+    half = np.asarray(paddle_cells, dtype=np.float64) * dx / 2
+    off = (radius_cells + gap_cells) * dx + half[0]
+    colliders = []
+    for side in (-1.0, 1.0):
+        centre = c + np.array([side * off, 0.0, 0.0])
+        vertices, faces = box_mesh(centre - half, centre + half) if shape == "box" else icosphere(centre, half[1], subdivisions)
+        colliders.append({"kind": "volume_mesh", "vertices": vertices, "faces": faces, "spacing": spacing_cells * dx, "pad": pad, "type": {"sticky": 0, "slip": 1, "separate": 2}[boundary],
+                          "friction": friction, "trans_vel": (-side * speed, 0.0, 0.0), "animate": True})
+    return {"name": "two_paddles", "bits": bits, "dt": dt, "config": {"max_ppc": 128, "gravity": 0.0},
+            "models": [{"material": material, "xyz": lattice_sphere(bits, tuple(c), radius_cells), "v0": (0, 0, 0), "params": prm}], "colliders": colliders}

@@ -403,6 +403,59 @@ int mpm_set_collision_mesh(mpm_ctx* ctx, const mpm_collision_object* obj, const 
  * again through mpm_set_collision_object.  HIP library only. */
 int mpm_get_collision_field(mpm_ctx* ctx, const int lo[3], const int dims[3], float* out4);
 
+/* Extension: a collision object given as a local level-set box - a "volume": a dense table of {sdis, gx, gy, gz} samples with its own origin,
+ * spacing and dimensions in material coordinates, in one of the four slots of mpm_set_collision_shape.  It is the heightfield's idea in three
+ * dimensions: where the level-set object is one float4 per node of the whole domain (2 GiB at domain_bits 9), at the grid's resolution, once
+ * per context, a volume of 96^3 samples is 14 MiB, its resolution is its own, and up to four of them - each with its own trans_vel, omega
+ * and start pose, all on the context's one clock - act beside the level-set object.  HIP library only.
+ * Any kind (shape, heightfield, volume) may sit in any slot; installing any kind over any other replaces it and frees its table, and
+ * mpm_set_collision_shape(ctx, slot, NULL, NULL) empties a volume slot too.  A volume is reachable only through the two setters below:
+ * mpm_set_collision_shape goes on refusing every kind but 1 .. 4.  Everything the shapes' comment says about the pose, the response, the
+ * order of the colliders (field object, then slots 0 .. 3), the doubled |v|^2 and the one clock holds word for word; like a shape, a volume
+ * is not part of a checkpoint.  The context owns the table: it is freed on replace, on removal and in mpm_destroy.
+ * Table.  One float4 {sdis, gx, gy, gz} per sample, sample (i, j, k) at [(i * dims[1] + j) * dims[2] + k], at the material position
+ * origin + ((float) i, (float) j, (float) k) * spacing (one multiplication, one addition per axis).
+ * Query at the material point x (claymore_amd/csrc/mpm_collision_volume.hpp; float32, every operation in the order written, no contraction).
+ * Per axis d: xl_d = x_d - origin_d, u_d = xl_d / spacing.  Outside the footprint the collider touches nothing, whatever inside_out says
+ * (sdis = NaN, n = 0, nothing is loaded): a point is outside unless 0 <= u_d <= (float) (dims_d - 1) on all three axes; a NaN is outside.
+ * Cell and weights are query_sdf's own statements on xl: cid_d = min((int) u_d, dims_d - 2), dis = xl_d - (float) cid_d * spacing,
+ * w[d][0] = 1.f - dis / spacing, w[d][1] = dis / spacing.  The eight corners are summed in the level set's i, j, k loop order:
+ * w = w[0][i] * w[1][j] * w[2][k]; sdis and the three gradient channels each start from 0.f and do += w * v.  nn = sqrtf(n0 n0 + n1 n1 +
+ * n2 n2), n_d /= nn (a zero gradient gives what it gives in the level set); inside_out then negates sdis and n.  A node is touched when
+ * sdis <= 0; a NaN touches nothing.  query_sdf's domain box does NOT apply: a volume exists wherever its footprint is.  With origin 0,
+ * spacing dx and dims N these are the level-set kernel's statements on the same numbers. */
+enum { MPM_VOLUME_MAX_SAMPLES = 1024 }; /* per axis */
+typedef struct mpm_collision_volume {
+	int dims[3];	 /* samples along material x, y, z: each 2 .. MPM_VOLUME_MAX_SAMPLES, product <= 2^27;
+						all three 0 (mesh install only): size the box from the mesh, see below */
+	float origin[3]; /* material position of sample (0, 0, 0) */
+	float spacing;	 /* > 0, finite: sample (i, j, k) sits at origin + ((float) i, (float) j, (float) k) * spacing */
+	int inside_out;	 /* 1: sdis and n change sign at the query */
+	int pad;		 /* mesh install with dims 0: cells of margin around the mesh's bounding box; 0 means 2 */
+	int reserved[7];
+} mpm_collision_volume; /* 64 bytes */
+/* Install a volume in slot 0 .. 3 with the pose, motion and boundary fields of `obj`, or empty the slot (obj == NULL).  field4:
+ * dims[0] * dims[1] * dims[2] * 4 floats on the host, copied during the call.  MPM_ERR_INVALID (mpm_last_error starts "collision volume:"
+ * and names the field): slot outside 0..3, a dim outside 2..1024 or a product above 2^27, zero dims, spacing <= 0 or not finite, a NaN
+ * origin, pad < 0, boundary type outside 0..2, a NULL vol or field4 with a non-NULL obj, any sample that is not finite.  MPM_ERR_CAPACITY
+ * when the device cannot hold the table, which is allocated beside the slot's old occupant.  A refused or failed install leaves the slot,
+ * the clock and every other slot as they were. */
+int mpm_set_collision_volume(mpm_ctx* ctx, int slot, const mpm_collision_object* obj, const mpm_collision_volume* vol, const float* field4);
+/* The same with the table built on the device from a closed triangle mesh given in material coordinates (verts / tris and their validation:
+ * mpm_set_collision_mesh's, every reason of which is reported behind "collision volume: ").  Sample (i, j, k) gets mpm_set_collision_mesh's
+ * field definition - exact point-triangle distance by the Voronoi walk, the nearest triangle by strict < in index order, the plane or the
+ * radial rule, the sign from the pseudonormals - evaluated at p_d = origin_d + (float) i_d * spacing, always outward-signed: vol->inside_out
+ * acts at the query only.  With dims == {0, 0, 0} the host sizes the box from the mesh's bounding box [min, max] in float64 and stores the
+ * origin as float32: origin_d = min_d - pad * spacing, dims_d = ceil((max_d - min_d) / spacing) + 2 * pad + 1 (pad 0 means 2; vol->origin is
+ * not used); MPM_ERR_INVALID if that leaves the limits.  MPM_ERR_CAPACITY when the device cannot hold the table or the triangle records. */
+int mpm_set_collision_volume_mesh(mpm_ctx* ctx, int slot, const mpm_collision_object* obj, const mpm_collision_volume* vol, const float* verts, size_t nv, const int32_t* tris, size_t nt);
+/* The descriptor as installed (vol_out, may be NULL) and, unless out4 == NULL, the samples of the box lo + [0, dims) of the slot's table
+ * bit for bit: sample lo + (x, y, z) at out4[((x dims[1] + y) dims[2] + z) 4 ..].  MPM_ERR_INVALID for a slot that holds no volume or a
+ * box that leaves the table.  Reads only.  It is how a mesh-built volume is saved, to be installed again through mpm_set_collision_volume. */
+int mpm_get_collision_volume(mpm_ctx* ctx, int slot, mpm_collision_volume* vol_out, const int lo[3], const int dims[3], float* out4);
+/* Function-level entry point (as mpm_test_collision_heightfield): out4[n*4] = {sdis, nx, ny, nz} at n arbitrary domain points xyz[n*3]. */
+int mpm_test_collision_volume(const mpm_collision_object* obj, const mpm_collision_volume* vol, const float* field4, float time, const float* xyz, size_t n, float* out4, int device);
+
 /* Extension: a model whose particles fill a closed triangle mesh, sampled on the device (claymore_amd/csrc/mpm_mesh_fill.hpp).  HIP library only.
  * verts / tris: as for mpm_set_collision_mesh, same coordinates, same validation.
  * Lattice (the reference's sample_uniform_box rule): node (i, j, k) carries 8 candidates at (((float) i + a 0.25f) dx, ((float) j + b 0.25f) dx,

@@ -3,7 +3,7 @@
 libraries in ONE process, interleaved (lib A, lib B, lib A, ...), so that a parent build and a branch build are compared on the same
 box under the same conditions.
 
-    python tools/collider_substep.py [--scene c2|c3] [--steps 200] [--warmup 50] [--reps 3] [--objects none,static,moving,shape,shapes4,ground_hf,ground_shape,ground_field] [--phase 20]
+    python tools/collider_substep.py [--scene c1|c2|c3] [--steps 200] [--warmup 50] [--reps 3] [--objects none,static,moving,shape,shapes4,ground_hf,ground_shape,ground_field,vol_mesh,vol_mesh4,field_mesh] [--phase 20]
                                      [--out FILE] [lib.so ...]
 
 Scene: C2 (one elastic sphere of ~5 M particles dropped at 256^3; the level-set field is 256^3 float4 = 256 MiB) or C3 (the sand column at
@@ -16,6 +16,9 @@ a heightfield (mpm_set_collision_heightfield: an (N + 1)^2 table of constant hei
 half-space shape at that height, and the level set of the same plane (sdf = y - height, gradient +y) - the same physics (the level set
 alone stops at query_sdf's box); a library without mpm_set_collision_heightfield skips `ground_hf`.  --phase N: after the run, N more substeps phase by phase (grid update, G2P2G, rebuild), whose median
 grid-update time is the stand-alone kernel's (`phase_grid_ms`); in mpm_run_fixed the update rides on the carry-over inside `partition_ms`.
+`vol_mesh` / `vol_mesh4` / `field_mesh`: a subdivision-5 icosphere (20 480 triangles) of the sphere's place and size as a volume at
+spacing dx built on the device (mpm_set_collision_volume_mesh), four such bodies in the four slots, and the same body through mpm_set_collision_mesh (the level-set
+object: a float4 per node of the whole domain); `install_ms` is the wall-clock time of the installs.  `--scene c1`: C2's sphere at 128^3.
 `object_bytes`: device memory taken by installing the collider (hipMemGetInfo before and after).  Prints one JSON line per (rep, library, object) with the library's per-substep averages
 (HIP events on the compute stream) and the wall-clock time per substep, then a summary of medians."""
 import argparse
@@ -45,7 +48,7 @@ def load(path):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("libs", nargs="*", default=[_ffi.HIP_LIB_PATH])
-    ap.add_argument("--scene", default="c2", choices=["c2", "c3"])
+    ap.add_argument("--scene", default="c2", choices=["c1", "c2", "c3"])
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--reps", type=int, default=3)
@@ -53,11 +56,13 @@ def main():
     ap.add_argument("--phase", type=int, default=20)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    sc = scenes.sphere_drop() if a.scene == "c2" else scenes.sand_column()
+    sc = scenes.sphere_drop() if a.scene == "c2" else scenes.sphere_drop(bits=7, radius_cells=26.5) if a.scene == "c1" else scenes.sand_column()
     bits = sc["bits"]
     sdf, grad = scenes.sphere_level_set(bits, (0.5, 0.12, 0.5), 0.06)
     col = {"sdf": sdf, "grad": grad, "type": 1, "friction": 0.3, "trans": (0.5, 0.12, 0.5)}
     ground, n = 0.02, 1 << bits
+    bodies = [((0.5, 0.12, 0.5), 0.06), ((0.2, 0.1, 0.2), 0.05), ((0.75, 0.1, 0.3), 0.04), ((0.3, 0.1, 0.75), 0.04)]
+    meshes = [scenes.icosphere(c, r, 5) for c, r in bodies] if any(o in a.objects.split(",") for o in ("vol_mesh", "vol_mesh4", "field_mesh")) else []
     apis = [(os.path.basename(os.path.dirname(os.path.abspath(p))) + "/" + os.path.basename(p), load(p)) for p in a.libs]
     rows, lines = [], []
     for rep in range(a.reps):
@@ -65,10 +70,13 @@ def main():
             for obj in a.objects.split(","):
                 if (obj == "moving" and not hasattr(api, "set_collision_clock")) or (obj in ("shape", "shapes4") and not hasattr(api, "set_collision_shape")):
                     continue
+                if obj in ("vol_mesh", "vol_mesh4") and not hasattr(api, "set_collision_volume_mesh"):
+                    continue
                 if (obj == "ground_hf" and not hasattr(api, "set_collision_heightfield")) or (obj == "ground_shape" and not hasattr(api, "set_collision_shape")):
                     continue
                 eng = build_engine(sc, api=api)
                 free0 = torch.cuda.mem_get_info()[0]
+                t_install = time.perf_counter()
                 if obj in ("shape", "shapes4"):
                     eng.set_collision_shape(0, "sphere", a=(0.5, 0.12, 0.5), radius=0.06, type=1, friction=0.3, trans=(0.5, 0.12, 0.5))
                 if obj == "shapes4":
@@ -85,10 +93,16 @@ def main():
                     ggrad[1] = 1.0
                     eng.set_collision_object(sdf=gsdf, grad=ggrad, type=1, friction=0.3)
                     del gsdf, ggrad
+                elif obj in ("vol_mesh", "vol_mesh4"):
+                    for slot, mesh in enumerate(meshes[:4 if obj == "vol_mesh4" else 1]):
+                        eng.set_collision_volume_mesh(slot, *mesh, spacing=1.0 / n, pad=2, type=1, friction=0.3)
+                elif obj == "field_mesh":
+                    eng.set_collision_mesh(*meshes[0], type=1, friction=0.3)
                 elif obj in ("static", "moving"):
                     eng.set_collision_object(**col, **({"trans_vel": (0.0, 0.05, 0.0), "omega": (1.0, 2.0, 3.0), "dsdt": 0.1} if obj == "moving" else {}))
                 if obj == "moving":
                     eng.set_collision_clock(True, 0.0)
+                install_ms = (time.perf_counter() - t_install) * 1e3
                 object_bytes = free0 - torch.cuda.mem_get_info()[0]
                 eng.initial_setup()
                 eng.run_fixed(a.warmup, sc["dt"])
@@ -104,7 +118,7 @@ def main():
                     eng.rebuild_partition()
                 row = {"rep": rep, "lib": name, "build": api.build_info().decode(), "scene": a.scene, "object": obj, "steps": a.steps, "wall_ms": round(wall, 5),
                        "grid_ms": round(t.grid_update_ms, 5), "g2p2g_ms": round(t.g2p2g_ms, 5), "partition_ms": round(t.partition_ms, 5), "total_ms": round(t.total_ms, 5),
-                       "phase_grid_ms": round(statistics.median(phase), 5) if phase else None, "object_bytes": int(object_bytes)}
+                       "phase_grid_ms": round(statistics.median(phase), 5) if phase else None, "object_bytes": int(object_bytes), "install_ms": round(install_ms, 3)}
                 eng.close()
                 rows.append(row)
                 lines.append(json.dumps(row))
@@ -114,7 +128,7 @@ def main():
             sel = [r for r in rows if r["lib"] == name and r["object"] == obj]
             if sel:
                 med = {k: round(statistics.median(r[k] for r in sel), 5) for k in ("wall_ms", "grid_ms", "g2p2g_ms", "partition_ms", "total_ms") + (("phase_grid_ms",) if a.phase else ())}
-                med.update(partition_lo=min(r["partition_ms"] for r in sel), partition_hi=max(r["partition_ms"] for r in sel), object_bytes=sel[0]["object_bytes"])
+                med.update(partition_lo=min(r["partition_ms"] for r in sel), partition_hi=max(r["partition_ms"] for r in sel), object_bytes=sel[0]["object_bytes"], install_ms=round(statistics.median(r["install_ms"] for r in sel), 3))
                 med.update(lo=min(r["wall_ms"] for r in sel), hi=max(r["wall_ms"] for r in sel))
                 lines.append(json.dumps({"summary": name, "object": obj, "n": len(sel), **med}))
                 print(lines[-1], flush=True)

@@ -150,6 +150,7 @@ HIP_ONLY = {
     "grid_box_totals": (_i, [_vp, _P(C.c_int), _P(C.c_int), _P(C.c_double)]),
     "grid_isosurface": (_i, [_vp, _f, _P(C.c_int), _P(C.c_int), _vp, _vp, _P(_sz)]),
     "halo_dump": (_i, [_vp, _vp, _vp, _ip, _vp]),
+    "dump_block_rows": (_i, [_vp, _i, _vp, _P(_sz)]),
     "set_collision_clock": (_i, [_vp, _i, _f]),
     "get_collision_time": (_i, [_vp, _fp, _ip]),
     "set_collision_shape": (_i, [_vp, _i, _P(CollisionObject), _P(CollisionShape)]),

@@ -2133,6 +2133,17 @@ int mpm_dump_grid(mpm_ctx* ctx, int* keys, float* blocks, size_t* nblocks) {
 	return MPM_OK;
 }
 
+int mpm_dump_block_rows(mpm_ctx* ctx, int model, int32_t* rows, size_t* nblocks) {
+	if(!ctx || !ctx->ready || !nblocks) return MPM_ERR_NOT_READY;
+	if(model < 0 || model >= (int) ctx->models.size()) return fail(ctx, MPM_ERR_INVALID, "mpm_dump_block_rows: no such model");
+	if(*nblocks < (size_t) ctx->pbc) return fail(ctx, MPM_ERR_CAPACITY, "block row dump too small");
+	HIP_TRY(hipSetDevice(ctx->device));
+	HIP_TRY(hipStreamSynchronize(ctx->s_compute));
+	if(rows && ctx->pbc) HIP_TRY(hipMemcpy(rows, ctx->models[model].blockinfo, sizeof(int) * (size_t) kInfoRow * (size_t) ctx->pbc, hipMemcpyDeviceToHost));
+	*nblocks = ctx->pbc;
+	return MPM_OK;
+}
+
 // Eulerian readouts (mpm_grid_field.hpp; an extension, the reference has none): point samples, dense volumes and box totals of grid[0], the
 // mass and momentum of the last P2G.  Preconditions those of mpm_retrieve_velocity (readout_state).  Read-only; temporaries are scratch
 // released on every exit path, so a context that never calls these allocates and launches nothing for them.

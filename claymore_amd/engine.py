@@ -571,6 +571,14 @@ class Engine:
         self._check(self.api.dump_grid(self.ctx, keys.ctypes.data_as(C.c_void_p), blocks.ctypes.data_as(C.c_void_p), C.byref(n)))
         return keys[: n.value], blocks[: n.value]
 
+    def dump_block_rows(self, model=0):
+        """The 64-int look-up rows of `model`, one per particle block of the current numbering (mpm_dump_block_rows; HIP library only):
+        (particle blocks, 64) int32 - [0, 27) source bin offsets, [27, 54) destination block numbers, [54, 62) grid block numbers."""
+        n = C.c_size_t(self.counts().particle_blocks)
+        rows = np.empty((n.value, 64), dtype=np.int32)
+        self._check(self.api.dump_block_rows(self.ctx, int(model), rows.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return rows[: n.value]
+
     # ---- Eulerian readouts (mpm_sample_grid, mpm_grid_volume, mpm_grid_box_totals; HIP library only) ------------------------------
     def sample_grid(self, xyz):
         """The grid of the last P2G sampled at arbitrary world-space points with G2P's 27-node B-spline stencil (mpm_sample_grid):

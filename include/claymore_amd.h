@@ -517,6 +517,10 @@ int mpm_check_table(mpm_ctx* ctx);
 /* Dense dump of the current grid for parity tests: for every neighbor block, key (3 ints) and 256 floats
  * {mass[64], mvx[64], mvy[64], mvz[64]} (grid_buffer.cuh:12-14 layout). *nblocks in = capacity, out = count. */
 int mpm_dump_grid(mpm_ctx* ctx, int* keys, float* blocks, size_t* nblocks);
+/* Debug read-out of the per-block look-up rows of `model` in the current numbering (HIP library only; read-only, synchronises the compute
+ * stream like mpm_dump_grid): for every particle block 64 ints - [0, 27) the first source bin per direction, [27, 54) the destination block
+ * numbers, [54, 62) the grid block numbers, 62 / 63 unused.  *nblocks in = capacity in blocks, out = the particle block count. */
+int mpm_dump_block_rows(mpm_ctx* ctx, int model, int32_t* rows, size_t* nblocks);
 /* Extension (the reference has no Eulerian output): what the grid holds between two substeps - the mass m_i and momentum p_i of the last
  * P2G - read out by position instead of by particle.  N = 2^domain_bits nodes per axis; node (i, j, k) sits at
  * (i, j, k) dx.  A node holds a value only if it lies in [0, N)^3 AND its block (i >> 2, j >> 2, k >> 2) is in the current partition's table

@@ -10,7 +10,10 @@ them every list, size and pair count - as they were (tests/test_g2p2g_blocks_gpu
 
 A bin (fill_bins_kernel, claymore_amd/csrc/mpm_kernels.hpp) holds 64 records of `rec` floats - 4 for the J-fluid {x/dx, y/dx, z/dx, J}, 8 for
 the solids {x/dx, y/dx, z/dx, b00, b11, b22, b10, b20} - and behind them one row entry of nch - rec floats per slot: b21 (fixed-corotated),
-{b21, log Jp} (sand, NACC).  The sign bit of b00 marks a reflected F."""
+{b21, log Jp} (sand, NACC).  The sign bit of b00 marks a reflected F.
+
+list_records / record_positions / source_extents / key_map read the advection lists field by field without judging them: the verifier of
+tests/rebuild_books.py reports what particle_slots would assert."""
 import numpy as np
 
 HEADER_BYTES = 448
@@ -213,4 +216,71 @@ def with_particle_state(buf, m, xyz_cells, b=None, logjp=None, J=None, reflected
     if logjp is not None:
         assert row == 2, "this material carries no log Jp"
         B[bi, K_BIN * rec + sl * row + 1] = np.asarray(logjp, np.float32).reshape(n)
+    return out
+
+
+DIRS = np.array([(t // 9 - 1, (t // 3) % 3 - 1, t % 3 - 1) for t in range(27)], dtype=np.int64)      # dir_components: z fastest
+K_ARENA_BIT = 30                      # the scatter arena of a record in the pair layout (kArenaBit)
+
+
+def key_map(keys):
+    """{block key: its number} of a key list (n, 3); a key held twice keeps its first number."""
+    out = {}
+    for i, k in enumerate(np.asarray(keys).reshape(-1, 3).tolist()):
+        out.setdefault(tuple(k), i)
+    return out
+
+
+def source_extents(buf, m):
+    """Bins each particle block of the PREVIOUS numbering holds for model m, read off binoff_src the way mpm_checkpoint_load reads them: the
+    distance to the next larger offset (bins are handed out without gaps; empty blocks share an offset), at most max_ppc.  (prev_pbc,) int64."""
+    h = parse(buf)
+    n = h["prev_pbc"]
+    bsrc = section(buf, h, ("binoff_src", m), np.int32)[:n].astype(np.int64)
+    ends = np.unique(np.concatenate([bsrc, [h["models"][m]["bincount_src"]]]))
+    at = np.searchsorted(ends, bsrc, side="right")
+    nxt = np.where(at < ends.size, ends[np.minimum(at, ends.size - 1)], bsrc)      # (an offset at or behind the end of the bins: no extent)
+    return np.minimum(nxt - bsrc, h["max_ppc"])
+
+
+def list_records(buf, m):
+    """Every record of model m's packed advection lists, field by field and WITHOUT judging any of it (particle_slots asserts; this does not):
+    {"raw" uint32, "blk": the block of the current numbering whose list holds it (by size[]), "tag", "key": the sort key field, "slot": the
+    slot in the source block, "arena": bit 30, "top": bit 31, "src": the block of the previous numbering at key(blk) + dir(tag) or -1 (also
+    for a tag above 26), "ok": tag <= 26 and src is a particle block of the previous numbering and the slot lies within its bins, "bin",
+    "lane": where the particle lives (meaningful where ok)}.  Records that size[] leaves no room for in the section are left out."""
+    h = parse(buf)
+    ppb = K_BIN * h["max_ppc"]
+    pid_bits = ppb.bit_length() - 1
+    size = np.clip(section(buf, h, ("size", m), np.int32)[:h["pbc"]].astype(np.int64), 0, None)
+    raw = section(buf, h, ("lists", m), np.int32).view(np.uint32)
+    blk = np.repeat(np.arange(h["pbc"]), size)[:raw.size]
+    raw = raw[:blk.size]
+    r = raw.astype(np.int64)
+    tag = (r >> (pid_bits + K_KEY_BITS)) & 31
+    slot = r & (ppb - 1)
+    keys = section(buf, h, "cur_keys", np.int32).reshape(-1, 3).astype(np.int64)
+    prev = key_map(section(buf, h, "prev_keys", np.int32).reshape(-1, 3))
+    src_key = keys[blk] + DIRS[np.minimum(tag, 26)]
+    src = np.array([prev.get(tuple(k), -1) for k in src_key.tolist()], dtype=np.int64).reshape(-1)
+    src[tag > 26] = -1
+    ext = source_extents(buf, m)
+    inside = (src >= 0) & (src < h["prev_pbc"])
+    ok = inside.copy()
+    ok[inside] = (slot[inside] >> 6) < ext[src[inside]]
+    binoff = section(buf, h, ("binoff_src", m), np.int32).astype(np.int64)
+    bin_ = np.where(ok, binoff[np.where(ok, src, 0)] + (slot >> 6), 0)
+    ok &= bin_ < h["models"][m]["bincount_src"]
+    return {"raw": raw, "blk": blk, "tag": tag, "key": (r >> pid_bits) & ((1 << K_KEY_BITS) - 1), "slot": slot, "arena": (r >> K_ARENA_BIT) & 1,
+            "top": r >> 31, "src": src, "ok": ok, "bin": bin_, "lane": slot & 63}
+
+
+def record_positions(buf, m, recs=None):
+    """Positions in cells (n, 3) float32 of the particles list_records names (NaN where a record is not ok)."""
+    recs = list_records(buf, m) if recs is None else recs
+    rec = rec_floats(parse(buf)["models"][m]["nch"])
+    B = bins(buf, m)
+    out = np.full((recs["raw"].size, 3), np.nan, np.float32)
+    ok = recs["ok"]
+    out[ok] = B[recs["bin"][ok][:, None], recs["lane"][ok][:, None] * rec + np.arange(3)[None, :]]
     return out

@@ -248,6 +248,11 @@ def step(c, pos_cells, vn, b6=None, reflected=None, logjp=None, J=None, dt=DT, n
         st[:, :, 0] = mass * W2
         st[:, :, 1:] = (mass * W2)[:, :, None] * vel[:, None, :] + np.einsum("nrc,nsc->nsr", Cm, xp) * W2[:, :, None]
         st[disc] = 0.0
+        # the sort key of the NEXT step (mpm_g2p2g.hpp): the stencil base predicted after one more advection with the current velocity, in the
+        # node cube of the block the particle is in after THIS step, clamped to 0 .. 5 per axis and packed y * 36 + x * 6 + z
+        sort_arg = nfd + vel * (new_dt / dx)
+        pk = np.clip(((narena - 1) & 3) + np.rint(np.where(np.isfinite(sort_arg), sort_arg, 0.0)).astype(np.int64), 0, 5)
+        out.update(sort_key=pk[:, 1] * 36 + pk[:, 0] * 6 + pk[:, 2], sort_arg=sort_arg)
     out.update(new_base=nbase, narena=narena, discarded=disc, dirtag=(dirv[:, 0] + 1) * 9 + (dirv[:, 1] + 1) * 3 + dirv[:, 2] + 1,
                dir_ok=(np.abs(dirv) <= 1).all(axis=1), nodes=nbase[:, None, :] + OFFS[None, :, :], stencil=st)
     fin = np.isfinite(pos).all(axis=1) & np.isfinite(st).all(axis=(1, 2))

@@ -1263,57 +1263,11 @@ def test_the_sort_writes_the_pair_layout_it_promises():
     blocks = _ckpt_lists(eng, ppb)
     eng.close()
     pid_bits = 13
-    from test_pair_layout_model import pair_chunks
+    from rebuild_books import pair_layout_findings
     seen = dict(chunks=0, pairs=0, mismatched=0, singles=0, multi_chunk=0, full_slices=0, merged=0)
-    for size, recs, pinfo in blocks:
-        chunks = pair_chunks(size)                                   # 512-record chunks, the last one with a tail of up to 256 records more
-        seen["multi_chunk"] += len(chunks) > 1
-        seen["merged"] += bool(chunks) and chunks[-1][1] > 512
-        for c, (first, n) in enumerate(chunks):
-            assert first == 512 * c
-            r = recs[first:first + n]
-            key, arena = (r >> pid_bits) & 255, (r >> 30) & 1
-            pf = int(pinfo[c])
-            n1 = n - 2 * pf
-            assert 0 <= pf and n1 >= 0
-            S = (n + 127) // 128
-            X = max(0, pf + n1 - 64 * S)
-            px, L = pf + X, pf + n1 - X
-            assert L <= 64 * S and L + px == n
-            pos = 0
-            slot_key = {}
-            for d in range(S):
-                ca, cb = L // S + (d < L % S), px // S + (d < px % S)
-                ka, kb = key[pos:pos + ca], key[pos + ca:pos + ca + cb]
-                aa, ab = arena[pos:pos + ca], arena[pos + ca:pos + ca + cb]
-                for ln in range(ca):
-                    slot_key[ln * S + d] = (int(ka[ln]), int(kb[ln]) if ln < cb else None, int(aa[ln]), ln, int(ab[ln]) if ln < cb else None)
-                pos += ca + cb
-                seen["full_slices"] += ca == 64
-            assert pos == n and sorted(slot_key) == list(range(L))
-            pair_keys = [slot_key[p][0] for p in range(pf)]
-            assert all(slot_key[p][0] == slot_key[p][1] for p in range(pf))                       # a pair slot: two records of one key
-            assert pair_keys == sorted(pair_keys)                                                 # key-major order
-            assert all(slot_key[p][2] == slot_key[p][4] == (slot_key[p][3] & 1) for p in range(pf))   # its arena, on both members: the lane parity (the kernel reads A's bit: a mismatched slot's B carries its own key's, unused)
-            assert all(slot_key[p][1] is not None and slot_key[p][0] != slot_key[p][1] for p in range(pf, px))   # a mismatched slot: two singles of different keys
-            assert all(slot_key[p][1] is None for p in range(px, L))                              # a single slot: A only
-            singles = [slot_key[p][0] for p in range(pf, L)] + [slot_key[p][1] for p in range(pf, px)]
-            assert len(singles) == len(set(singles)) == n1                                        # one single per key at most
-            from collections import Counter
-            cnt = Counter(pair_keys)
-            assert all(2 * cnt.get(k, 0) + (k in set(singles)) == int((key == k).sum()) for k in set(key.tolist()))
-            # the arena of a single (and of a mismatched slot, which carries its A's rule): not the one its key's pair slot of the same slice uses
-            by_slice = {}
-            for p in range(pf):
-                by_slice.setdefault((p % S, slot_key[p][0]), []).append(slot_key[p][2])
-            for p in range(pf, L):
-                used = by_slice.get((p % S, slot_key[p][0]), [])
-                if len(used) == 1:
-                    assert slot_key[p][2] != used[0]
-            seen["chunks"] += 1
-            seen["pairs"] += pf
-            seen["mismatched"] += X
-            seen["singles"] += n1
+    for b, (size, recs, pinfo) in enumerate(blocks):
+        found = pair_layout_findings(size, recs, pinfo, pid_bits, seen=seen, where=(("block", b),))      # (the checks this test used to make itself)
+        assert not found, found[:5]
     print("pair layout seen:", seen)
     assert seen["chunks"] > 30 and seen["pairs"] > 2000 and seen["singles"] > 100 and seen["mismatched"] > 0 and seen["multi_chunk"] > 0 and seen["merged"] > 0, seen
 

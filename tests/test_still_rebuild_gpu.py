@@ -84,9 +84,20 @@ def oracle_fall():
     return {"res": out, "crossing": crossing, "margins": margins, "census": census[-1]}
 
 
-def hip_fall(still, stops=(), sync_interval=0, track_ids=False, steps=STEPS):
+def book_findings(eng):
+    """tests/rebuild_books.check_books on the context as it stands: everything the last rebuild wrote, the look-up rows included"""
+    import rebuild_books
+    assert eng.api.check_table(eng.ctx) == 0
+    cnt = eng.counts()
+    return rebuild_books.check_books(eng.save_checkpoint().copy(), [eng.dump_block_rows(0)], BITS, eng.cfg.max_ppc, counts=[int(cnt.particles[0])])
+
+
+def hip_fall(still, stops=(), sync_interval=0, track_ids=False, steps=STEPS, books=False):
     """The falling box on the HIP engine.  stops: substep numbers after which the run is interrupted to read the counter and the positions.
-    Returns the parity_util-style result, the readings {substep: (still_rebuilds, census)} and the engine's own block sets."""
+    Returns the parity_util-style result, the readings {substep: (still_rebuilds, census)} and the engine's own block sets.  books: the books
+    and look-up rows are verified (book_findings) at the first stop, which lies in a still streak of two or more, at the first stop whose
+    substep moved a particle to another block, and at the first stop after that whose substep moved nobody (a streak of one); the readings
+    {what: (substep, growth of still_rebuilds in it, findings)} come back as out["books"]."""
     from test_parity_gpu import _hip_block_sets
     cfg = {"still_rebuild": still}
     if sync_interval:
@@ -101,6 +112,19 @@ def hip_fall(still, stops=(), sync_interval=0, track_ids=False, steps=STEPS):
         eng.run_fixed(s - done, DT)
         done = s
         seen[s] = (still_count(eng), block_census(eng.retrieve_positions(0)))
+        if books:
+            checked = out.setdefault("books", {})
+            what = None
+            if not checked:
+                what = "streak"
+            elif s - 1 in seen:
+                moved = seen[s][1] != seen[s - 1][1]
+                if moved and "crossing" not in checked:
+                    what = "crossing"
+                elif not moved and "crossing" in checked and "streak of one" not in checked:
+                    what = "streak of one"
+            if what:
+                checked[what] = (s, seen[s][0] - seen[s - 1][0] if s - 1 in seen else None, book_findings(eng))
     out.update(counts=eng.counts(), totals=eng.grid_totals(), state=[eng.retrieve_state(0)], diag=eng.diagnostics())
     assert eng.api.check_table(eng.ctx) == 0
     assert out["diag"].lost_particles == 0 and out["diag"].discarded_p2g == 0 and out["diag"].dropped_particles == 0
@@ -125,7 +149,7 @@ def test_still_then_crossing_then_still(oracle_fall):
     # the final state decides nothing by a rounding tie: no coordinate within 1e-3 dx of a cell face (a substep moves a particle by 3.7e-3 dx)
     assert oracle_fall["margins"][STEPS - 1] > 1e-3, oracle_fall["margins"][STEPS - 1]
     window = range(first - 3, cross[-1] + 4)
-    on, seen, sets_on = hip_fall(0, stops=window)
+    on, seen, sets_on = hip_fall(0, stops=window, books=True)
     off, seen_off, sets_off = hip_fall(-1)
     assert seen_off[STEPS][0] == 0
     slow = []
@@ -148,6 +172,12 @@ def test_still_then_crossing_then_still(oracle_fall):
         print(err)
         assert err["n"] == 32768 and err["pos_rel"] < POS_TOL, err
     assert sets_on == sets_off == oracle_fall["census"]
+    # the books and look-up rows the rebuild left (tests/rebuild_books.py): in a still streak of two or more (rows passed over), after a full
+    # rebuild (the crossing), and after the first still rebuild behind it (rows derived from the ones that stand)
+    bk = on["books"]
+    print("books verified at", {k: v[:2] for k, v in bk.items()})
+    assert set(bk) == {"streak", "crossing", "streak of one"} and bk["streak"][0] == window[0] >= 3 and bk["crossing"][1] == 0 and bk["streak of one"][1] == 1
+    assert all(not v[2] for v in bk.values()), {k: v[2][:5] for k, v in bk.items()}
 
 
 def test_sync_interval(oracle_fall):

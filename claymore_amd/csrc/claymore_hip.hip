@@ -1216,47 +1216,12 @@ int mpm_default_collision_object(mpm_collision_object* o) {
 	return MPM_OK;
 }
 
-int mpm_set_collision_object(mpm_ctx* ctx, const mpm_collision_object* obj, const float* sdf, const float* gx, const float* gy, const float* gz) {
-	if(!ctx) return MPM_ERR_INVALID;
-	HIP_TRY(hipSetDevice(ctx->device));
-	HIP_TRY(hipDeviceSynchronize());
-	if(ctx->d_sdf) HIP_TRY(hipFree(ctx->d_sdf));
-	ctx->d_sdf			   = nullptr;
-	ctx->has_collision	   = false;
-	ctx->collision_running = false;// installing or removing an object stops the clock
-	if(!obj) return MPM_OK;
-	if(!sdf || !gx || !gy || !gz) return fail(ctx, MPM_ERR_INVALID, "collision object without a signed distance field");
-	if(obj->type < MPM_BOUNDARY_STICKY || obj->type > MPM_BOUNDARY_SEPARATE) return fail(ctx, MPM_ERR_INVALID, "[ERROR] Wrong Boundary Type!");// boundary_condition.cuh:244
-	const size_t N = (size_t) 1 << ctx->cfg.domain_bits, n = N * N * N;
-	float* stage = nullptr;
-	HIP_TRY(dalloc(&stage, 4 * n));
-	HIP_TRY(dalloc(&ctx->d_sdf, n));
-	const float* src[4] = {sdf, gx, gy, gz};
-	for(int c = 0; c < 4; ++c) HIP_TRY(hipMemcpy(stage + c * n, src[c], sizeof(float) * n, hipMemcpyHostToDevice));
-	pack_sdf_kernel<<<cdiv(n, 256), 256, 0, ctx->s_compute>>>(n, stage, stage + n, stage + 2 * n, stage + 3 * n, ctx->d_sdf);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipStreamSynchronize(ctx->s_compute));
-	HIP_TRY(hipFree(stage));
-	CollisionObject& c = ctx->collision;
-	c.type	   = obj->type;
-	c.friction = obj->friction;
-	c.scale	   = obj->scale;
-	c.dsdt	   = obj->dsdt;
-	for(int d = 0; d < 3; ++d) {
-		c.trans[d]	   = obj->trans[d];
-		c.trans_vel[d] = obj->trans_vel[d];
-		c.omega[d]	   = obj->omega[d];
-	}
-	for(int i = 0; i < 9; ++i) c.rot[i] = obj->rot_mat[i];
-	c.time			   = obj->time;
-	c.field			   = ctx->d_sdf;
-	ctx->has_collision = true;
-	return MPM_OK;
+// the two range checks every collider install makes (the messages carry the API's prefix, so they stay with the callers)
+static bool boundary_type_ok(const mpm_collision_object* obj) {
+	return obj->type >= MPM_BOUNDARY_STICKY && obj->type <= MPM_BOUNDARY_SEPARATE;
 }
-
-// Analytic collision shapes ------------------------------------------------------------------------------------------------------------
-static bool shape_finite3(const float* v) {
-	return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]);
+static bool slot_ok(int slot) {
+	return slot >= 0 && slot < MPM_MAX_COLLISION_SHAPES;
 }
 // the pose, motion and boundary fields of mpm_collision_object as the kernels read them (no field: a slot's collider)
 static CollisionObject slot_object(const mpm_collision_object* obj) {
@@ -1271,10 +1236,42 @@ static CollisionObject slot_object(const mpm_collision_object* obj) {
 	o.field = nullptr;
 	return o;
 }
+
+int mpm_set_collision_object(mpm_ctx* ctx, const mpm_collision_object* obj, const float* sdf, const float* gx, const float* gy, const float* gz) {
+	if(!ctx) return MPM_ERR_INVALID;
+	HIP_TRY(hipSetDevice(ctx->device));
+	HIP_TRY(hipDeviceSynchronize());
+	if(ctx->d_sdf) HIP_TRY(hipFree(ctx->d_sdf));
+	ctx->d_sdf			   = nullptr;
+	ctx->has_collision	   = false;
+	ctx->collision_running = false;// installing or removing an object stops the clock
+	if(!obj) return MPM_OK;
+	if(!sdf || !gx || !gy || !gz) return fail(ctx, MPM_ERR_INVALID, "collision object without a signed distance field");
+	if(!boundary_type_ok(obj)) return fail(ctx, MPM_ERR_INVALID, "[ERROR] Wrong Boundary Type!");// boundary_condition.cuh:244
+	const size_t N = (size_t) 1 << ctx->cfg.domain_bits, n = N * N * N;
+	float* stage = nullptr;
+	HIP_TRY(dalloc(&stage, 4 * n));
+	HIP_TRY(dalloc(&ctx->d_sdf, n));
+	const float* src[4] = {sdf, gx, gy, gz};
+	for(int c = 0; c < 4; ++c) HIP_TRY(hipMemcpy(stage + c * n, src[c], sizeof(float) * n, hipMemcpyHostToDevice));
+	pack_sdf_kernel<<<cdiv(n, 256), 256, 0, ctx->s_compute>>>(n, stage, stage + n, stage + 2 * n, stage + 3 * n, ctx->d_sdf);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipStreamSynchronize(ctx->s_compute));
+	HIP_TRY(hipFree(stage));
+	ctx->collision		 = slot_object(obj);
+	ctx->collision.field = ctx->d_sdf;
+	ctx->has_collision	 = true;
+	return MPM_OK;
+}
+
+// Analytic collision shapes ------------------------------------------------------------------------------------------------------------
+static bool shape_finite3(const float* v) {
+	return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]);
+}
 // mpm_collision_object + mpm_collision_shape -> the slot the kernels read; nullptr, or the message that names the offending field
 static const char* make_shape_slot(const mpm_collision_object* obj, const mpm_collision_shape* sh, ShapeSlot& out) {
 	if(sh->kind < MPM_SHAPE_HALFSPACE || sh->kind > MPM_SHAPE_CAPSULE) return "collision shape: unknown kind";
-	if(obj->type < MPM_BOUNDARY_STICKY || obj->type > MPM_BOUNDARY_SEPARATE) return "collision shape: boundary type outside 0..2";
+	if(!boundary_type_ok(obj)) return "collision shape: boundary type outside 0..2";
 	for(int d = 0; d < 3; ++d)
 		if(sh->a[d] != sh->a[d]) return "collision shape: NaN in a";
 	if(sh->radius != sh->radius) return "collision shape: NaN in radius";
@@ -1314,11 +1311,19 @@ static void count_slots(mpm_ctx* ctx) {
 		if(ctx->shape[i].shape.kind == kShapeVolume) ++ctx->vol_count;
 	}
 }
+// What sits in a slot.  All empty: nothing (shape.shape.kind 0); an analytic shape fills `shape` alone; a heightfield `shape` and `hf`; a volume
+// `shape`, `vol` and `desc`, its descriptor as installed.
+struct SlotOccupant {
+	ShapeSlot shape {};
+	Heightfield hf {};
+	Volume vol {};
+	mpm_collision_volume desc {};
+};
 // What every accepted install or removal of any kind does to slot `slot`: wait for the device, free the table of a heightfield or a volume
-// that sat there, put the new occupant in (c.shape.kind 0: empty; f.table / v.table: the new heightfield's / volume's, owned by the context
-// from here on; desc: the volume's descriptor as installed), stop the clock and - on an install - set it to obj->time.
-static int install_slot(mpm_ctx* ctx, int slot, const ShapeSlot& c, const Heightfield& f, const mpm_collision_object* obj, const Volume& v = Volume {}, const mpm_collision_volume* desc = nullptr) {
-	const float4* fresh = f.table ? f.table : v.table;
+// that sat there, put the new occupant in (o.hf.table / o.vol.table: the new heightfield's / volume's, owned by the context from here on),
+// stop the clock and - on an install - set it to obj->time.
+static int install_slot(mpm_ctx* ctx, int slot, const SlotOccupant& o, const mpm_collision_object* obj) {
+	const float4* fresh = o.hf.table ? o.hf.table : o.vol.table;
 	hipError_t e		= hipSetDevice(ctx->device);
 	if(e == hipSuccess) e = hipDeviceSynchronize();
 	if(e != hipSuccess) {// nothing was touched: the old occupant stays
@@ -1336,10 +1341,10 @@ static int install_slot(mpm_ctx* ctx, int slot, const ShapeSlot& c, const Height
 		count_slots(ctx);
 		return fail(ctx, MPM_ERR_DEVICE, std::string("collision slot: freeing the old table -> ") + hipGetErrorString(e) + " (the slot is now empty)");
 	}
-	ctx->hf[slot]		   = f;
-	ctx->vol[slot]		   = v;
-	ctx->vol_desc[slot]	   = desc ? *desc : mpm_collision_volume {};
-	ctx->shape[slot]	   = c;// (kind 0: empty)
+	ctx->hf[slot]		   = o.hf;
+	ctx->vol[slot]		   = o.vol;
+	ctx->vol_desc[slot]	   = o.desc;
+	ctx->shape[slot]	   = o.shape;// (kind 0: empty)
 	ctx->collision_running = false;// installing or removing a collider stops the clock
 	if(obj) ctx->collision.time = obj->time;
 	count_slots(ctx);
@@ -1348,13 +1353,13 @@ static int install_slot(mpm_ctx* ctx, int slot, const ShapeSlot& c, const Height
 
 int mpm_set_collision_shape(mpm_ctx* ctx, int slot, const mpm_collision_object* obj, const mpm_collision_shape* shape) {
 	if(!ctx) return MPM_ERR_INVALID;
-	if(slot < 0 || slot >= MPM_MAX_COLLISION_SHAPES) return fail(ctx, MPM_ERR_INVALID, "collision shape: slot outside 0..3");
-	ShapeSlot c {};
+	if(!slot_ok(slot)) return fail(ctx, MPM_ERR_INVALID, "collision shape: slot outside 0..3");
+	SlotOccupant o;
 	if(obj) {
 		if(!shape) return fail(ctx, MPM_ERR_INVALID, "collision shape: obj without a shape");
-		if(const char* msg = make_shape_slot(obj, shape, c)) return fail(ctx, MPM_ERR_INVALID, msg);
+		if(const char* msg = make_shape_slot(obj, shape, o.shape)) return fail(ctx, MPM_ERR_INVALID, msg);
 	}
-	return install_slot(ctx, slot, c, Heightfield {}, obj);
+	return install_slot(ctx, slot, o, obj);
 }
 
 // Heightfield ----------------------------------------------------------------------------------------------------------------------------
@@ -1365,7 +1370,7 @@ static const char* make_heightfield_slot(const mpm_collision_object* obj, const 
 	if(hf->nz < kHeightfieldMinSamples || hf->nz > MPM_HEIGHTFIELD_MAX_SAMPLES) return "collision heightfield: nz outside 2..4096";
 	if(!(hf->spacing > 0.f) || !std::isfinite(hf->spacing)) return "collision heightfield: spacing must be finite and > 0";
 	if(hf->origin[0] != hf->origin[0] || hf->origin[1] != hf->origin[1]) return "collision heightfield: NaN in origin";
-	if(obj->type < MPM_BOUNDARY_STICKY || obj->type > MPM_BOUNDARY_SEPARATE) return "collision heightfield: boundary type outside 0..2";
+	if(!boundary_type_ok(obj)) return "collision heightfield: boundary type outside 0..2";
 	out					 = ShapeSlot {};
 	out.obj				 = slot_object(obj);
 	out.shape.kind		 = kShapeHeightfield;
@@ -1382,13 +1387,13 @@ static const char* make_heightfield_slot(const mpm_collision_object* obj, const 
 
 int mpm_set_collision_heightfield(mpm_ctx* ctx, int slot, const mpm_collision_object* obj, const mpm_heightfield* hf, const float* heights) {
 	if(!ctx) return MPM_ERR_INVALID;
-	if(slot < 0 || slot >= MPM_MAX_COLLISION_SHAPES) return fail(ctx, MPM_ERR_INVALID, "collision heightfield: slot outside 0..3");
-	ShapeSlot c {};
-	Heightfield f {};
-	if(!obj) return install_slot(ctx, slot, c, f, nullptr);
+	if(!slot_ok(slot)) return fail(ctx, MPM_ERR_INVALID, "collision heightfield: slot outside 0..3");
+	SlotOccupant o;
+	if(!obj) return install_slot(ctx, slot, o, nullptr);
 	if(!hf) return fail(ctx, MPM_ERR_INVALID, "collision heightfield: obj without hf");
 	if(!heights) return fail(ctx, MPM_ERR_INVALID, "collision heightfield: obj without heights");
-	if(const char* msg = make_heightfield_slot(obj, hf, c, f)) return fail(ctx, MPM_ERR_INVALID, msg);
+	Heightfield& f = o.hf;
+	if(const char* msg = make_heightfield_slot(obj, hf, o.shape, f)) return fail(ctx, MPM_ERR_INVALID, msg);
 	const size_t n = (size_t) f.nx * f.nz;
 	std::vector<float4> table(n);
 	if(!heightfield_build(heights, f.nx, f.nz, f.spacing, table.data())) return fail(ctx, MPM_ERR_INVALID, "collision heightfield: a height or a derived table entry is not finite");
@@ -1400,10 +1405,66 @@ int mpm_set_collision_heightfield(mpm_ctx* ctx, int slot, const mpm_collision_ob
 		return fail(ctx, MPM_ERR_DEVICE, std::string("collision heightfield: copying the table -> ") + hipGetErrorString(e));
 	}
 	f.table = d;
-	return install_slot(ctx, slot, c, f, obj);
+	return install_slot(ctx, slot, o, obj);
 }
 
 // Triangle mesh -> level-set field (mpm_collision_mesh.hpp) --------------------------------------------------------------------------------
+// What the three consumers of a mesh (this field, a volume's table, the mesh fill) do with it on the host: mesh_build under the API's two
+// limits, the extent behind the walk's slack, and the records on the device - released with the scope that owns this.
+struct MeshRecords {
+	std::vector<MeshTri> rec;
+	std::vector<MeshPseudo> pseudo;
+	DevScratch<MeshTri> d_rec;
+	DevScratch<MeshPseudo> d_pseudo;
+	float extent = 0.f;// largest coordinate magnitude in play: the caller's starting value (the domain's 1, or 0 and a box's corners later) or a vertex's
+	// empty, or why the mesh is refused ("collision mesh: ...", mesh_build's)
+	std::string build(const float* verts, size_t nv, const int32_t* tris, size_t nt, float extent0) {
+		MeshReport rep;
+		mesh_build(verts, nv, tris, nt, MPM_MESH_MAX_VERTICES, MPM_MESH_MAX_TRIANGLES, rec, pseudo, rep);
+		extent = extent0;
+		for(size_t i = 0; rep.reason.empty() && i < 3 * nv; ++i) extent = std::max(extent, std::fabs(verts[i]));
+		return rep.reason;
+	}
+	hipError_t alloc() {
+		const hipError_t e = d_rec.alloc(rec.size());
+		return e == hipSuccess ? d_pseudo.alloc(rec.size()) : e;
+	}
+	hipError_t upload() {
+		const hipError_t e = hipMemcpy(d_rec.p, rec.data(), sizeof(MeshTri) * rec.size(), hipMemcpyHostToDevice);
+		return e == hipSuccess ? hipMemcpy(d_pseudo.p, pseudo.data(), sizeof(MeshPseudo) * rec.size(), hipMemcpyHostToDevice) : e;
+	}
+	float slack(float spacing) const { return std::max(0.25f * spacing, extent * 0x1p-12f); }
+};
+
+// The table of `box` (dims, origin, spacing; its inside_out is the query's, the argument is what goes into the words) from a built mesh:
+// wait for the device, allocate the table and the records, upload, run collision_mesh_table_kernel.  MPM_OK: *out is the caller's table.
+// Anything else: the table is freed (the records go with m) and the context is untouched; the message reads "<who>: ... the <noun> of n <unit> ...".
+static int mesh_table_build(mpm_ctx* ctx, MeshRecords& m, const Volume& box, int inside_out, const char* who, const char* noun, const char* unit, float4** out) {
+	HIP_TRY(hipSetDevice(ctx->device));
+	HIP_TRY(hipDeviceSynchronize());
+	const size_t n = (size_t) box.dims[0] * (size_t) box.dims[1] * (size_t) box.dims[2], nt = m.rec.size();
+	float4* table  = nullptr;
+	if(dalloc(&table, n) != hipSuccess || m.alloc() != hipSuccess) {
+		(void) hipGetLastError();
+		if(table) hipFree(table);
+		return fail(ctx, MPM_ERR_CAPACITY, std::string(who) + ": no device memory for the " + noun + " of " + std::to_string(n) + " " + unit + " and " + std::to_string(nt) + " triangle records");
+	}
+	hipError_t e = m.upload();
+	if(e == hipSuccess) {
+		const unsigned tiles = (unsigned) ((box.dims[0] + 3) >> 2) * (unsigned) ((box.dims[1] + 3) >> 2) * (unsigned) ((box.dims[2] + 3) >> 2);
+		collision_mesh_table_kernel<<<tiles, 64, 0, ctx->s_compute>>>(m.d_rec.p, m.d_pseudo.p, (int) nt, box.dims[0], box.dims[1], box.dims[2], box.origin[0], box.origin[1], box.origin[2], box.spacing,
+																	  m.slack(box.spacing), inside_out, table);
+		e = hipGetLastError();
+	}
+	if(e == hipSuccess) e = hipStreamSynchronize(ctx->s_compute);
+	if(e != hipSuccess) {
+		hipFree(table);
+		return fail(ctx, MPM_ERR_DEVICE, std::string(who) + ": building the " + noun + " -> " + hipGetErrorString(e));
+	}
+	*out = table;
+	return MPM_OK;
+}
+
 // Order: every host check, then the new field and the records are allocated beside the installed field, filled, and only then does the old
 // field go: a refusal - invalid mesh, no memory, a device error - leaves the context as it was.  Replacing a field so needs room for two
 // for the duration of the call.
@@ -1411,46 +1472,38 @@ int mpm_set_collision_mesh(mpm_ctx* ctx, const mpm_collision_object* obj, const 
 	if(!ctx) return MPM_ERR_INVALID;
 	if(!obj) return fail(ctx, MPM_ERR_INVALID, "collision mesh: NULL obj (mpm_set_collision_object(ctx, NULL, ...) removes the object)");
 	if(!verts || !tris) return fail(ctx, MPM_ERR_INVALID, "collision mesh: NULL verts or tris");
-	if(obj->type < MPM_BOUNDARY_STICKY || obj->type > MPM_BOUNDARY_SEPARATE) return fail(ctx, MPM_ERR_INVALID, "collision mesh: boundary type outside 0..2");
-	std::vector<MeshTri> rec;
-	std::vector<MeshPseudo> pseudo;
-	MeshReport rep;
-	mesh_build(verts, nv, tris, nt, MPM_MESH_MAX_VERTICES, MPM_MESH_MAX_TRIANGLES, rec, pseudo, rep);
-	if(!rep.reason.empty()) return fail(ctx, MPM_ERR_INVALID, rep.reason);
-	float extent = 1.f;// largest coordinate magnitude in play: the domain's 1 or a vertex's
-	for(size_t i = 0; i < 3 * nv; ++i) extent = std::max(extent, std::fabs(verts[i]));
-	HIP_TRY(hipSetDevice(ctx->device));
-	HIP_TRY(hipDeviceSynchronize());
-	const int N	   = 1 << ctx->cfg.domain_bits;
-	const size_t n = (size_t) N * N * N;
-	float4* field  = nullptr;
-	DevScratch<MeshTri> d_rec;
-	DevScratch<MeshPseudo> d_pseudo;
-	if(dalloc(&field, n) != hipSuccess || dalloc(&d_rec.p, nt) != hipSuccess || dalloc(&d_pseudo.p, nt) != hipSuccess) {
-		(void) hipGetLastError();
-		if(field) hipFree(field);
-		return fail(ctx, MPM_ERR_CAPACITY, "collision mesh: no device memory for the field of " + std::to_string(n) + " nodes and " + std::to_string(nt) + " triangle records");
-	}
-	hipError_t e = hipMemcpy(d_rec.p, rec.data(), sizeof(MeshTri) * nt, hipMemcpyHostToDevice);
-	if(e == hipSuccess) e = hipMemcpy(d_pseudo.p, pseudo.data(), sizeof(MeshPseudo) * nt, hipMemcpyHostToDevice);
-	if(e == hipSuccess) {
-		const float dx	  = 1.f / (float) N;
-		const float slack = std::max(0.25f * dx, extent * 0x1p-12f);
-		const unsigned tiles = (unsigned) (N >> 2);
-		collision_mesh_field_kernel<<<tiles * tiles * tiles, 64, 0, ctx->s_compute>>>(d_rec.p, d_pseudo.p, (int) nt, N, dx, slack, opt && opt->inside_out ? 1 : 0, field);
-		e = hipGetLastError();
-	}
-	if(e == hipSuccess) e = hipStreamSynchronize(ctx->s_compute);
-	if(e != hipSuccess) {
-		hipFree(field);
-		return fail(ctx, MPM_ERR_DEVICE, std::string("collision mesh: building the field -> ") + hipGetErrorString(e));
-	}
+	if(!boundary_type_ok(obj)) return fail(ctx, MPM_ERR_INVALID, "collision mesh: boundary type outside 0..2");
+	MeshRecords m;
+	const std::string why = m.build(verts, nv, tris, nt, 1.f);
+	if(!why.empty()) return fail(ctx, MPM_ERR_INVALID, why);
+	const int N = 1 << ctx->cfg.domain_bits;
+	Volume nodes {};// the domain's nodes as a table: N^3 samples dx apart from 0
+	nodes.dims[0] = nodes.dims[1] = nodes.dims[2] = N;
+	nodes.spacing = 1.f / (float) N;
+	float4* field = nullptr;
+	if(int rc = mesh_table_build(ctx, m, nodes, opt && opt->inside_out ? 1 : 0, "collision mesh", "field", "nodes", &field)) return rc;
 	if(ctx->d_sdf) hipFree(ctx->d_sdf);
 	ctx->d_sdf			   = field;
 	ctx->collision		   = slot_object(obj);
 	ctx->collision.field   = field;
 	ctx->has_collision	   = true;
 	ctx->collision_running = false;// installing an object stops the clock
+	return MPM_OK;
+}
+
+// The box lo + [0, dims) of a device table of (., d1, d2) entries to the host (the caller has checked that it lies inside the table)
+static int read_table_box(mpm_ctx* ctx, const char* who, const float4* table, int d1, int d2, const int lo[3], const int dims[3], float* out4) {
+	const size_t n = (size_t) dims[0] * (size_t) dims[1] * (size_t) dims[2];
+	HIP_TRY(hipSetDevice(ctx->device));
+	DevScratch<float4> stage;
+	if(dalloc(&stage.p, n) != hipSuccess) {
+		(void) hipGetLastError();
+		return fail(ctx, MPM_ERR_CAPACITY, std::string(who) + ": no device memory for the box");
+	}
+	collision_table_box_kernel<<<cdiv(n, 256), 256, 0, ctx->s_compute>>>(table, d1, d2, lo[0], lo[1], lo[2], dims[0], dims[1], dims[2], stage.p);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipStreamSynchronize(ctx->s_compute));
+	HIP_TRY(hipMemcpy(out4, stage.p, sizeof(float4) * n, hipMemcpyDeviceToHost));
 	return MPM_OK;
 }
 
@@ -1463,18 +1516,7 @@ int mpm_get_collision_field(mpm_ctx* ctx, const int lo[3], const int dims[3], fl
 		if(dims[d] < 1) return fail(ctx, MPM_ERR_INVALID, "mpm_get_collision_field: a dims entry < 1");
 		if(lo[d] < 0 || lo[d] >= N || dims[d] > N - lo[d]) return fail(ctx, MPM_ERR_INVALID, "mpm_get_collision_field: the box leaves [0, N)^3");
 	}
-	const size_t n = (size_t) dims[0] * (size_t) dims[1] * (size_t) dims[2];
-	HIP_TRY(hipSetDevice(ctx->device));
-	DevScratch<float4> stage;
-	if(dalloc(&stage.p, n) != hipSuccess) {
-		(void) hipGetLastError();
-		return fail(ctx, MPM_ERR_CAPACITY, "mpm_get_collision_field: no device memory for the box");
-	}
-	collision_field_box_kernel<<<cdiv(n, 256), 256, 0, ctx->s_compute>>>(ctx->d_sdf, N, lo[0], lo[1], lo[2], dims[0], dims[1], dims[2], stage.p);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipStreamSynchronize(ctx->s_compute));
-	HIP_TRY(hipMemcpy(out4, stage.p, sizeof(float4) * n, hipMemcpyDeviceToHost));
-	return MPM_OK;
+	return read_table_box(ctx, "mpm_get_collision_field", ctx->d_sdf, N, N, lo, dims, out4);
 }
 
 // Volume: a local level-set box in a slot (mpm_collision_volume.hpp) ----------------------------------------------------------------------------
@@ -1495,7 +1537,7 @@ static const char* make_volume_slot(const mpm_collision_object* obj, const mpm_c
 	for(int d = 0; d < 3; ++d)
 		if(vol->origin[d] != vol->origin[d]) return "collision volume: NaN in origin";
 	if(vol->pad < 0) return "collision volume: pad < 0";
-	if(obj->type < MPM_BOUNDARY_STICKY || obj->type > MPM_BOUNDARY_SEPARATE) return "collision volume: boundary type outside 0..2";
+	if(!boundary_type_ok(obj)) return "collision volume: boundary type outside 0..2";
 	out					 = ShapeSlot {};
 	out.obj				 = slot_object(obj);
 	out.shape.kind		 = kShapeVolume;
@@ -1524,13 +1566,13 @@ static mpm_collision_volume volume_descriptor(const Volume& v, int pad) {
 
 int mpm_set_collision_volume(mpm_ctx* ctx, int slot, const mpm_collision_object* obj, const mpm_collision_volume* vol, const float* field4) {
 	if(!ctx) return MPM_ERR_INVALID;
-	if(slot < 0 || slot >= MPM_MAX_COLLISION_SHAPES) return fail(ctx, MPM_ERR_INVALID, "collision volume: slot outside 0..3");
-	ShapeSlot c {};
-	Volume v {};
-	if(!obj) return install_slot(ctx, slot, c, Heightfield {}, nullptr);
+	if(!slot_ok(slot)) return fail(ctx, MPM_ERR_INVALID, "collision volume: slot outside 0..3");
+	SlotOccupant o;
+	if(!obj) return install_slot(ctx, slot, o, nullptr);
 	if(!vol) return fail(ctx, MPM_ERR_INVALID, "collision volume: obj without vol");
 	if(!field4) return fail(ctx, MPM_ERR_INVALID, "collision volume: obj without field4");
-	if(const char* msg = make_volume_slot(obj, vol, false, c, v)) return fail(ctx, MPM_ERR_INVALID, msg);
+	Volume& v = o.vol;
+	if(const char* msg = make_volume_slot(obj, vol, false, o.shape, v)) return fail(ctx, MPM_ERR_INVALID, msg);
 	const size_t n = (size_t) v.dims[0] * (size_t) v.dims[1] * (size_t) v.dims[2];
 	if(!volume_samples_finite(field4, n)) return fail(ctx, MPM_ERR_INVALID, "collision volume: a sample of field4 is not finite");
 	HIP_TRY(hipSetDevice(ctx->device));
@@ -1543,9 +1585,9 @@ int mpm_set_collision_volume(mpm_ctx* ctx, int slot, const mpm_collision_object*
 		hipFree(d);
 		return fail(ctx, MPM_ERR_DEVICE, std::string("collision volume: copying the table -> ") + hipGetErrorString(e));
 	}
-	v.table						  = d;
-	const mpm_collision_volume dsc = volume_descriptor(v, vol->pad);
-	return install_slot(ctx, slot, c, Heightfield {}, obj, v, &dsc);
+	v.table = d;
+	o.desc	= volume_descriptor(v, vol->pad);
+	return install_slot(ctx, slot, o, obj);
 }
 
 // Order, as for mpm_set_collision_mesh: every host check, then the table and the records are allocated beside the slot's old occupant, the
@@ -1553,59 +1595,33 @@ int mpm_set_collision_volume(mpm_ctx* ctx, int slot, const mpm_collision_object*
 // leaves the slot, the clock and every other slot as they were.
 int mpm_set_collision_volume_mesh(mpm_ctx* ctx, int slot, const mpm_collision_object* obj, const mpm_collision_volume* vol, const float* verts, size_t nv, const int32_t* tris, size_t nt) {
 	if(!ctx) return MPM_ERR_INVALID;
-	if(slot < 0 || slot >= MPM_MAX_COLLISION_SHAPES) return fail(ctx, MPM_ERR_INVALID, "collision volume: slot outside 0..3");
-	if(!obj) return install_slot(ctx, slot, ShapeSlot {}, Heightfield {}, nullptr);
+	if(!slot_ok(slot)) return fail(ctx, MPM_ERR_INVALID, "collision volume: slot outside 0..3");
+	SlotOccupant o;
+	if(!obj) return install_slot(ctx, slot, o, nullptr);
 	if(!vol) return fail(ctx, MPM_ERR_INVALID, "collision volume: obj without vol");
 	if(!verts || !tris) return fail(ctx, MPM_ERR_INVALID, "collision volume: NULL verts or tris");
-	ShapeSlot c {};
-	Volume v {};
-	if(const char* msg = make_volume_slot(obj, vol, true, c, v)) return fail(ctx, MPM_ERR_INVALID, msg);
-	std::vector<MeshTri> rec;
-	std::vector<MeshPseudo> pseudo;
-	MeshReport rep;
-	mesh_build(verts, nv, tris, nt, MPM_MESH_MAX_VERTICES, MPM_MESH_MAX_TRIANGLES, rec, pseudo, rep);
-	if(!rep.reason.empty()) return fail(ctx, MPM_ERR_INVALID, "collision volume: " + rep.reason);
+	Volume& v = o.vol;
+	if(const char* msg = make_volume_slot(obj, vol, true, o.shape, v)) return fail(ctx, MPM_ERR_INVALID, msg);
+	MeshRecords m;
+	const std::string why = m.build(verts, nv, tris, nt, 0.f);
+	if(!why.empty()) return fail(ctx, MPM_ERR_INVALID, "collision volume: " + why);
 	int pad = vol->pad;
 	if(v.dims[0] == 0) {
 		pad = pad ? pad : 2;
 		if(!volume_autosize(verts, nv, v.spacing, pad, v.origin, v.dims))
 			return fail(ctx, MPM_ERR_INVALID, "collision volume: dims sized from the mesh's bounding box, spacing and pad leave 2..1024 per axis or 2^27 samples");
 	}
-	float extent = 0.f;// largest coordinate magnitude in play: a vertex's or a box corner's
-	for(size_t i = 0; i < 3 * nv; ++i) extent = std::max(extent, std::fabs(verts[i]));
-	for(int d = 0; d < 3; ++d) extent = std::max(extent, std::max(std::fabs(v.origin[d]), std::fabs(v.origin[d] + (float) (v.dims[d] - 1) * v.spacing)));
-	HIP_TRY(hipSetDevice(ctx->device));
-	HIP_TRY(hipDeviceSynchronize());
-	const size_t n = (size_t) v.dims[0] * (size_t) v.dims[1] * (size_t) v.dims[2];
-	float4* table  = nullptr;
-	DevScratch<MeshTri> d_rec;
-	DevScratch<MeshPseudo> d_pseudo;
-	if(dalloc(&table, n) != hipSuccess || dalloc(&d_rec.p, nt) != hipSuccess || dalloc(&d_pseudo.p, nt) != hipSuccess) {
-		(void) hipGetLastError();
-		if(table) hipFree(table);
-		return fail(ctx, MPM_ERR_CAPACITY, "collision volume: no device memory for the table of " + std::to_string(n) + " samples and " + std::to_string(nt) + " triangle records");
-	}
-	hipError_t e = hipMemcpy(d_rec.p, rec.data(), sizeof(MeshTri) * nt, hipMemcpyHostToDevice);
-	if(e == hipSuccess) e = hipMemcpy(d_pseudo.p, pseudo.data(), sizeof(MeshPseudo) * nt, hipMemcpyHostToDevice);
-	if(e == hipSuccess) {
-		const float slack	 = std::max(0.25f * v.spacing, extent * 0x1p-12f);
-		const unsigned tiles = (unsigned) ((v.dims[0] + 3) >> 2) * (unsigned) ((v.dims[1] + 3) >> 2) * (unsigned) ((v.dims[2] + 3) >> 2);
-		collision_volume_mesh_kernel<<<tiles, 64, 0, ctx->s_compute>>>(d_rec.p, d_pseudo.p, (int) nt, v.dims[0], v.dims[1], v.dims[2], v.origin[0], v.origin[1], v.origin[2], v.spacing, slack, table);
-		e = hipGetLastError();
-	}
-	if(e == hipSuccess) e = hipStreamSynchronize(ctx->s_compute);
-	if(e != hipSuccess) {
-		hipFree(table);
-		return fail(ctx, MPM_ERR_DEVICE, std::string("collision volume: building the table -> ") + hipGetErrorString(e));
-	}
-	v.table						  = table;
-	const mpm_collision_volume dsc = volume_descriptor(v, pad);
-	return install_slot(ctx, slot, c, Heightfield {}, obj, v, &dsc);
+	for(int d = 0; d < 3; ++d) m.extent = std::max(m.extent, std::max(std::fabs(v.origin[d]), std::fabs(v.origin[d] + (float) (v.dims[d] - 1) * v.spacing)));// the box's corners count too
+	float4* table = nullptr;
+	if(int rc = mesh_table_build(ctx, m, v, 0, "collision volume", "table", "samples", &table)) return rc;
+	v.table = table;
+	o.desc	= volume_descriptor(v, pad);
+	return install_slot(ctx, slot, o, obj);
 }
 
 int mpm_get_collision_volume(mpm_ctx* ctx, int slot, mpm_collision_volume* vol_out, const int lo[3], const int dims[3], float* out4) {
 	if(!ctx) return MPM_ERR_INVALID;
-	if(slot < 0 || slot >= MPM_MAX_COLLISION_SHAPES) return fail(ctx, MPM_ERR_INVALID, "collision volume: slot outside 0..3");
+	if(!slot_ok(slot)) return fail(ctx, MPM_ERR_INVALID, "collision volume: slot outside 0..3");
 	if(ctx->shape[slot].shape.kind != kShapeVolume || !ctx->vol[slot].table) return fail(ctx, MPM_ERR_INVALID, "collision volume: the slot holds no volume");
 	const Volume& v = ctx->vol[slot];
 	if(out4) {
@@ -1616,19 +1632,7 @@ int mpm_get_collision_volume(mpm_ctx* ctx, int slot, mpm_collision_volume* vol_o
 		}
 	}
 	if(vol_out) *vol_out = ctx->vol_desc[slot];
-	if(!out4) return MPM_OK;
-	const size_t n = (size_t) dims[0] * (size_t) dims[1] * (size_t) dims[2];
-	HIP_TRY(hipSetDevice(ctx->device));
-	DevScratch<float4> stage;
-	if(dalloc(&stage.p, n) != hipSuccess) {
-		(void) hipGetLastError();
-		return fail(ctx, MPM_ERR_CAPACITY, "collision volume: no device memory for the box");
-	}
-	collision_volume_box_kernel<<<cdiv(n, 256), 256, 0, ctx->s_compute>>>(v.table, v.dims[1], v.dims[2], lo[0], lo[1], lo[2], dims[0], dims[1], dims[2], stage.p);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipStreamSynchronize(ctx->s_compute));
-	HIP_TRY(hipMemcpy(out4, stage.p, sizeof(float4) * n, hipMemcpyDeviceToHost));
-	return MPM_OK;
+	return out4 ? read_table_box(ctx, "collision volume", v.table, v.dims[1], v.dims[2], lo, dims, out4) : MPM_OK;
 }
 
 // Mesh-sampled models (mpm_mesh_fill.hpp) -------------------------------------------------------------------------------------------------
@@ -1640,8 +1644,7 @@ struct MeshFillPlan {
 	MeshFillArgs a {};
 	unsigned ntiles = 0, ngroups = 0;
 	unsigned long long total = 0, shortcuts = 0;
-	DevScratch<MeshTri> rec;
-	DevScratch<MeshPseudo> pseudo;
+	MeshRecords mesh;
 	DevScratch<unsigned char> masks;
 	DevScratch<unsigned> counts, bsum;
 	DevScratch<unsigned long long> boff;// [ngroups] the groups' offsets, [ngroups] the total, [ngroups + 1] the shortcut tiles (statistics)
@@ -1688,36 +1691,30 @@ static int mesh_fill_count(std::string& err, const char* who, int bits, const fl
 	if(!verts || !tris) return refuse(MPM_ERR_INVALID, "NULL verts or tris");
 	const float margin = opt ? opt->margin : 0.f;
 	if(!(margin >= 0.f) || !std::isfinite(margin)) return refuse(MPM_ERR_INVALID, "margin must be finite and >= 0");
-	std::vector<MeshTri> rec;
-	std::vector<MeshPseudo> pseudo;
-	MeshReport rep;
-	mesh_build(verts, nv, tris, nt, MPM_MESH_MAX_VERTICES, MPM_MESH_MAX_TRIANGLES, rec, pseudo, rep);
-	if(!rep.reason.empty()) return refuse(MPM_ERR_INVALID, rep.reason);
+	const std::string why = P.mesh.build(verts, nv, tris, nt, 1.f);// (the extent starts at the domain's 1, as for the field)
+	if(!why.empty()) return refuse(MPM_ERR_INVALID, why);
 	const int N		   = 1 << bits;
 	const bool use_box = opt && opt->use_box;
 	MeshFillRange r;
 	if(!mesh_fill_range(N, verts, nv, use_box ? opt->lo : nullptr, use_box ? opt->hi : nullptr, r)) return refuse(MPM_ERR_INVALID, "lo / hi outside [0, N]");
-	float extent = 1.f;// as for the field: the largest coordinate magnitude in play
-	for(size_t i = 0; i < 3 * nv; ++i) extent = std::max(extent, std::fabs(verts[i]));
 	P.a.dx	   = 1.f / (float) N;
-	P.a.slack  = std::max(0.25f * P.a.dx, extent * 0x1p-12f);
+	P.a.slack  = P.mesh.slack(P.a.dx);
 	P.a.margin = margin;
 	for(int d = 0; d < 3; ++d) P.a.lo[d] = r.lo[d], P.a.hi[d] = r.hi[d], P.a.tlo[d] = r.tlo[d], P.a.tn[d] = r.tn[d];
 	P.ntiles = (unsigned) r.tn[0] * (unsigned) r.tn[1] * (unsigned) r.tn[2];// at most 256^3
 	P.total = P.shortcuts = 0;
 	if(!P.ntiles) return MPM_OK;
 	P.ngroups = cdiv(P.ntiles, kMeshFillGroup);
-	if(P.rec.alloc(nt) != hipSuccess || P.pseudo.alloc(nt) != hipSuccess || P.masks.alloc((size_t) P.ntiles * 64) != hipSuccess || P.counts.alloc(P.ntiles) != hipSuccess
+	if(P.mesh.alloc() != hipSuccess || P.masks.alloc((size_t) P.ntiles * 64) != hipSuccess || P.counts.alloc(P.ntiles) != hipSuccess
 	   || P.bsum.alloc(P.ngroups) != hipSuccess || P.boff.alloc((size_t) P.ngroups + 2) != hipSuccess) {
 		(void) hipGetLastError();
 		return refuse(MPM_ERR_CAPACITY, "no device memory for the work buffers of " + std::to_string(P.ntiles) + " tiles and " + std::to_string(nt) + " triangle records");
 	}
-	FILL_TRY(hipMemcpy(P.rec.p, rec.data(), sizeof(MeshTri) * nt, hipMemcpyHostToDevice));
-	FILL_TRY(hipMemcpy(P.pseudo.p, pseudo.data(), sizeof(MeshPseudo) * nt, hipMemcpyHostToDevice));
+	FILL_TRY(P.mesh.upload());
 	FILL_TRY(hipMemsetAsync(P.boff.p, 0, sizeof(unsigned long long) * ((size_t) P.ngroups + 2), s));
 	MeshFillEvents ev(timed);
 	ev.mark(0, s);
-	mesh_fill_classify_kernel<<<P.ntiles, 64, 0, s>>>(P.rec.p, P.pseudo.p, (int) nt, P.a, P.masks.p, P.counts.p, P.boff.p + P.ngroups + 1);
+	mesh_fill_classify_kernel<<<P.ntiles, 64, 0, s>>>(P.mesh.d_rec.p, P.mesh.d_pseudo.p, (int) nt, P.a, P.masks.p, P.counts.p, P.boff.p + P.ngroups + 1);
 	FILL_TRY(hipGetLastError());
 	ev.mark(1, s);
 	mesh_fill_scan_block_kernel<<<P.ngroups, 256, 0, s>>>(P.counts.p, P.ntiles, P.bsum.p);

@@ -6,7 +6,9 @@
 //   1. the definition - mesh_closest / mesh_field_value - MPM_DEV, float32 in one written-down order without contraction; it builds on x86
 //      too (claymore_amd/host/host_selftest.cpp --mesh-closest, tests/collision_mesh_model.py restates it in NumPy);
 //   2. the host side of an install - mesh_build: validation, adjacency, the per-triangle records - plain C++, no HIP;
-//   3. the kernel (HIP only): one wave per 4 x 4 x 4 node tile, triangles culled per tile.
+//   3. the tile walk (HIP only) - one wave per 4 x 4 x 4 tile of points, triangles culled per tile - as device functions, and the two kernels
+//      on it that every mesh-built table shares: collision_mesh_table_kernel (this field, and a volume's table: mpm_collision_volume.hpp) and
+//      the box read-back collision_table_box_kernel.  mpm_mesh_fill.hpp's classify kernel is the walk's third caller.
 // The definition is in include/claymore_amd.h and INTEGRATION.md section 5.
 #pragma once
 #if defined(__HIPCC__)
@@ -283,7 +285,7 @@ inline int mesh_point_query(const std::vector<MeshTri>& rec, const std::vector<M
 #endif
 
 #if defined(__HIPCC__)
-// ---- the kernel ------------------------------------------------------------------------------------------------------------------------
+// ---- the tile walk and its kernels -------------------------------------------------------------------------------------------------------
 // One wave (a 64-thread block) per 4 x 4 x 4 node tile, one node per lane (lane = (x 4 + y) 4 + z: four 64-byte runs of the field).
 //   1. Bound.  The lanes stride over the triangles and evaluate q at the tile's centre; a wave-min gives D = sqrtf(min q).  With r the
 //      half diagonal of the tile's nodes (1.5 sqrt(3) dx) every node is within D + r of the mesh.
@@ -300,47 +302,58 @@ inline int mesh_point_query(const std::vector<MeshTri>& rec, const std::vector<M
 // candidates per tile and nothing else: a triangle that passes needlessly loses the strict < comparison.
 // Budget.  LDS: kMeshChunk x (48 B record + 4 B index) = 6.5 KiB per block, stated here and checked by tests/test_collision_mesh_isa.py with the
 // kernel's scratch (none: every array is indexed by constants).  No atomics.
+// The walk exists once, as the functions below; its callers are collision_mesh_table_kernel (one point per lane) and
+// mesh_fill_classify_kernel (mpm_mesh_fill.hpp: eight points per lane, a larger r).  Both declare the chunk themselves and pass it in.
 constexpr int kMeshChunk = 128;
 
-__global__ __launch_bounds__(64) void collision_mesh_field_kernel(const MeshTri* __restrict__ tris, const MeshPseudo* __restrict__ pseudo, int nt, int N, float dx, float slack, int inside_out,
-																   float4* __restrict__ field) {
-	__shared__ float4 s_rec[kMeshChunk * 3];
-	__shared__ int s_idx[kMeshChunk];
-	const int lane	= (int) threadIdx.x;
-	const int tiles = N >> 2;
-	const int bz = (int) (blockIdx.x % (unsigned) tiles), by = (int) ((blockIdx.x / (unsigned) tiles) % (unsigned) tiles), bx = (int) (blockIdx.x / ((unsigned) tiles * (unsigned) tiles));
-	const int node[3] = {4 * bx + (lane >> 4), 4 * by + ((lane >> 2) & 3), 4 * bz + (lane & 3)};
-	const float p[3]	  = {(float) node[0] * dx, (float) node[1] * dx, (float) node[2] * dx};
-	const float centre[3] = {((float) (4 * bx) + 1.5f) * dx, ((float) (4 * by) + 1.5f) * dx, ((float) (4 * bz) + 1.5f) * dx};
-	const float4* tris4	  = reinterpret_cast<const float4*>(tris);
-	auto load_tri = [&](const float4* src, MeshTri& t) {
-		const float4 r0 = src[0], r1 = src[1], r2 = src[2];
-		t.a[0] = r0.x, t.a[1] = r0.y, t.a[2] = r0.z, t.ab[0] = r0.w;
-		t.ab[1] = r1.x, t.ab[2] = r1.y, t.ac[0] = r1.z, t.ac[1] = r1.w;
-		t.ac[2] = r2.x, t.nh[0] = r2.y, t.nh[1] = r2.z, t.nh[2] = r2.w;
-	};
-	// 1. bound
+// A record as the kernels fetch it: three 16-byte loads, from global memory or from the chunk
+MPM_DEV void mesh_load_tri(const float4* src, MeshTri& t) {
+	const float4 r0 = src[0], r1 = src[1], r2 = src[2];
+	t.a[0] = r0.x, t.a[1] = r0.y, t.a[2] = r0.z, t.ab[0] = r0.w;
+	t.ab[1] = r1.x, t.ab[2] = r1.y, t.ac[0] = r1.z, t.ac[1] = r1.w;
+	t.ac[2] = r2.x, t.nh[0] = r2.y, t.nh[1] = r2.z, t.nh[2] = r2.w;
+}
+
+// 1. Bound: min q at the tile's centre over all triangles, the same in every lane, and in tmin the lowest index that attains it (a caller
+// that ignores tmin pays nothing for it: qmin does not depend on it).  The lanes past the end of the last 64 repeat triangle nt - 1.
+MPM_DEV float mesh_centre_bound(const float4* __restrict__ tris4, int nt, int lane, const float (&centre)[3], int& tmin) {
 	float qmin = INFINITY;
+	tmin	   = 0;
 	for(int base = 0; base < nt; base += 64) {
 		const int t = min(base + lane, nt - 1);
 		MeshTri tri;
-		load_tri(tris4 + 3 * (size_t) t, tri);
+		mesh_load_tri(tris4 + 3 * (size_t) t, tri);
 		float c[3];
 		int f;
-		qmin = fminf(qmin, mesh_closest(tri, centre, c, f));
+		const float q = mesh_closest(tri, centre, c, f);
+		if(q < qmin) qmin = q, tmin = t;
 	}
-	for(int off = 32; off > 0; off >>= 1) qmin = fminf(qmin, __shfl_xor(qmin, off));
-	const float thr	 = (sqrtf(qmin) + 2.f * (2.598076211f * dx)) * 1.015625f + slack;
-	const float thr2 = thr * thr;
-	// 2. candidates
-	float best_q = INFINITY;
-	int best_t	 = 0;
-	int fill	 = 0;// wave-uniform
+	for(int off = 32; off > 0; off >>= 1) {
+		const float oq = __shfl_xor(qmin, off);
+		const int ot   = __shfl_xor(tmin, off);
+		tmin		   = oq < qmin || (oq == qmin && ot < tmin) ? ot : tmin;
+		qmin		   = oq < qmin ? oq : qmin;
+	}
+	return qmin;
+}
+
+// The test's threshold on q(centre), squared: D = sqrtf(min q), r the half diagonal of the tile's points about the centre
+MPM_DEV float mesh_threshold2(float D, float r, float slack) {
+	const float thr = (D + 2.f * r) * 1.015625f + slack;
+	return thr * thr;
+}
+
+// 2. Candidates: the triangles with q(centre) <= thr2, 64 at a time in index order, compacted in that order into the chunk s_rec / s_idx
+// (kMeshChunk records); consume(fill) runs between two barriers whenever another 64 might not fit, and at the end.  Every lane of the
+// block calls this (fill is wave-uniform).  consume is taken by value: behind a reference, the arrays a lambda captures went to scratch.
+template<typename Consume>
+MPM_DEV void mesh_sweep_candidates(const float4* __restrict__ tris4, int nt, int lane, const float (&centre)[3], float thr2, float4* s_rec, int* s_idx, Consume consume) {
+	int fill = 0;
 	for(int base = 0; base < nt; base += 64) {
 		const int t	  = base + lane;
 		const bool in = t < nt;
 		MeshTri tri;
-		load_tri(tris4 + 3 * (size_t) (in ? t : nt - 1), tri);
+		mesh_load_tri(tris4 + 3 * (size_t) (in ? t : nt - 1), tri);
 		float c[3];
 		int f;
 		const float qc				  = mesh_closest(tri, centre, c, f);
@@ -348,7 +361,7 @@ __global__ __launch_bounds__(64) void collision_mesh_field_kernel(const MeshTri*
 		const unsigned long long mask = __ballot(cand);
 		if(cand) {
 			const int pos = fill + (int) __popcll(mask & ((1ull << lane) - 1ull));// < fill + 64 <= kMeshChunk
-			const float4* src = tris4 + 3 * (size_t) t;
+			const float4* src  = tris4 + 3 * (size_t) t;
 			s_rec[3 * pos]	   = src[0];
 			s_rec[3 * pos + 1] = src[1];
 			s_rec[3 * pos + 2] = src[2];
@@ -357,31 +370,73 @@ __global__ __launch_bounds__(64) void collision_mesh_field_kernel(const MeshTri*
 		fill += (int) __popcll(mask);
 		if(fill > kMeshChunk - 64 || base + 64 >= nt) {
 			__syncthreads();
-			for(int i = 0; i < fill; ++i) {
-				MeshTri ct;
-				load_tri(s_rec + 3 * i, ct);
-				const float qt = mesh_closest(ct, p, c, f);
-				if(qt < best_q) best_q = qt, best_t = s_idx[i];
-			}
+			consume(fill);
 			__syncthreads();
 			fill = 0;
 		}
 	}
+}
+
+// One point against the chunk, in order, strict <: (best_q, best_t) carry over from chunk to chunk
+MPM_DEV void mesh_walk_chunk(const float4* s_rec, const int* s_idx, int fill, const float (&p)[3], float& best_q, int& best_t) {
+	for(int i = 0; i < fill; ++i) {
+		MeshTri ct;
+		mesh_load_tri(s_rec + 3 * i, ct);
+		float c[3];
+		int f;
+		const float qt = mesh_closest(ct, p, c, f);
+		if(qt < best_q) best_q = qt, best_t = s_idx[i];
+	}
+}
+
+// Position of sample i along an axis: volume_sample_point's two statements (mpm_collision_volume.hpp, which includes this file)
+MPM_DEV float mesh_table_point(float origin, float spacing, int i) {
+	MPM_MESH_NO_CONTRACT
+	const float s = (float) i * spacing;
+	return origin + s;
+}
+
+// A table of d0 x d1 x d2 samples `spacing` apart from (o0, o1, o2), sample (i, j, k) at [(i d1 + j) d2 + k] and p_d = origin_d +
+// (float) i_d * spacing: the three steps above with `spacing` for dx and the samples for the nodes.  Both mesh-built colliders are this kernel:
+//   the level-set field (mpm_set_collision_mesh): dims {N, N, N}, origin 0, spacing dx - p is (float) node * dx exactly -, inside_out baked
+//     into the words by mesh_field_value;
+//   a volume's table (mpm_set_collision_volume_mesh): the box's own numbers, inside_out 0 - a volume is flipped at the query -, slack taken
+//     over the vertices and the box's corners.
+// dims need not be multiples of 4: the lanes of a partial tile whose sample lies outside the table take part in the culling (their point
+// is still within r of the centre) and do not store.
+__global__ __launch_bounds__(64) void collision_mesh_table_kernel(const MeshTri* __restrict__ tris, const MeshPseudo* __restrict__ pseudo, int nt, int d0, int d1, int d2, float o0, float o1,
+																   float o2, float spacing, float slack, int inside_out, float4* __restrict__ table) {
+	__shared__ float4 s_rec[kMeshChunk * 3];
+	__shared__ int s_idx[kMeshChunk];
+	const int lane	  = (int) threadIdx.x;
+	const unsigned t1 = (unsigned) ((d1 + 3) >> 2), t2 = (unsigned) ((d2 + 3) >> 2);
+	const int bz = (int) (blockIdx.x % t2), by = (int) ((blockIdx.x / t2) % t1), bx = (int) (blockIdx.x / (t2 * t1));
+	const int idx[3]	  = {4 * bx + (lane >> 4), 4 * by + ((lane >> 2) & 3), 4 * bz + (lane & 3)};
+	const bool stores	  = idx[0] < d0 && idx[1] < d1 && idx[2] < d2;
+	const float p[3]	  = {mesh_table_point(o0, spacing, idx[0]), mesh_table_point(o1, spacing, idx[1]), mesh_table_point(o2, spacing, idx[2])};
+	const float centre[3] = {o0 + ((float) (4 * bx) + 1.5f) * spacing, o1 + ((float) (4 * by) + 1.5f) * spacing, o2 + ((float) (4 * bz) + 1.5f) * spacing};
+	const float4* tris4	  = reinterpret_cast<const float4*>(tris);
+	int tmin;
+	const float D = sqrtf(mesh_centre_bound(tris4, nt, lane, centre, tmin));
+	float best_q  = INFINITY;
+	int best_t	  = 0;
+	mesh_sweep_candidates(tris4, nt, lane, centre, mesh_threshold2(D, 2.598076211f * spacing, slack), s_rec, s_idx, [&](int fill) { mesh_walk_chunk(s_rec, s_idx, fill, p, best_q, best_t); });
 	// 3. rule and store
 	MeshTri win;
-	load_tri(tris4 + 3 * (size_t) best_t, win);
+	mesh_load_tri(tris4 + 3 * (size_t) best_t, win);
 	float out[4], q;
 	int feature;
 	mesh_field_value(win, pseudo[best_t], p, inside_out, out, feature, q);
-	field[((size_t) node[0] * (size_t) N + (size_t) node[1]) * (size_t) N + (size_t) node[2]] = make_float4(out[0], out[1], out[2], out[3]);
+	if(stores) table[((size_t) idx[0] * (size_t) d1 + (size_t) idx[1]) * (size_t) d2 + (size_t) idx[2]] = make_float4(out[0], out[1], out[2], out[3]);
 }
 
-// mpm_get_collision_field: the box lo + [0, dims) of the field, x slowest, z fastest (bounds are the host's to check)
-__global__ void collision_field_box_kernel(const float4* __restrict__ field, int N, int lo0, int lo1, int lo2, int d0, int d1, int d2, float4* __restrict__ out) {
+// mpm_get_collision_field, mpm_get_collision_volume: the box lo + [0, b) of a table of (., d1, d2) entries, x slowest, z fastest (bounds
+// are the host's to check)
+__global__ void collision_table_box_kernel(const float4* __restrict__ table, int d1, int d2, int lo0, int lo1, int lo2, int b0, int b1, int b2, float4* __restrict__ out) {
 	const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
-	if(i >= (size_t) d0 * (size_t) d1 * (size_t) d2) return;
-	const int z = (int) (i % (size_t) d2), y = (int) ((i / (size_t) d2) % (size_t) d1), x = (int) (i / ((size_t) d2 * (size_t) d1));
-	out[i]		= field[((size_t) (lo0 + x) * (size_t) N + (size_t) (lo1 + y)) * (size_t) N + (size_t) (lo2 + z)];
+	if(i >= (size_t) b0 * (size_t) b1 * (size_t) b2) return;
+	const int z = (int) (i % (size_t) b2), y = (int) ((i / (size_t) b2) % (size_t) b1), x = (int) (i / ((size_t) b2 * (size_t) b1));
+	out[i]		= table[((size_t) (lo0 + x) * (size_t) d1 + (size_t) (lo1 + y)) * (size_t) d2 + (size_t) (lo2 + z)];
 }
 #endif// __HIPCC__
 

@@ -11,8 +11,8 @@
 //   1. the definition - volume_query / volume_resolve / volume_sample_point / volume_autosize - MPM_DEV or plain C++, float32 in one written-down
 //      order without contraction; it builds on x86 too (tools/hostcheck/check_volume.cpp; tests/collision_volume_model.py restates it in NumPy);
 //   2. the install-time kernel that fills a table from a closed triangle mesh (HIP only): mpm_collision_mesh.hpp's field definition evaluated at
-//      the table's samples, one wave per 4 x 4 x 4 sample tile;
-//   3. the read-back kernel of mpm_get_collision_volume (HIP only).
+//      the table's samples, one wave per 4 x 4 x 4 sample tile - collision_mesh_table_kernel, in that file;
+//   3. the read-back kernel of mpm_get_collision_volume (HIP only): collision_table_box_kernel, in that file too.
 // The definition is in include/claymore_amd.h and INTEGRATION.md section 5.
 #pragma once
 // The response (volume_resolve) needs mpm_collision.hpp and with it a HIP runtime header - the real one, or tools/hostcheck's stand-in.  A plain
@@ -158,101 +158,8 @@ inline bool volume_autosize(const float* verts, size_t nv, float spacing, int pa
 #endif
 
 #if defined(__HIPCC__)
+// Parts 2 and 3 are mpm_collision_mesh.hpp's: collision_mesh_table_kernel fills a table from a closed mesh - it is the kernel of the domain-wide
+// field, given the box's origin, spacing and dimensions and inside_out 0 (a volume is flipped at the query); the argument, the partial tiles
+// and the budget are written there (tests/test_collision_volume_isa.py) - and collision_table_box_kernel reads a box of a table back.
 #include "mpm_collision_mesh.hpp"
-
-namespace mpm {
-
-// ---- a table from a closed mesh ----------------------------------------------------------------------------------------------------------
-// collision_mesh_field_kernel's scheme (mpm_collision_mesh.hpp: bound, candidates, rule and store - its comment carries the argument) on the
-// table's samples instead of the domain's nodes: one wave per 4 x 4 x 4 sample tile, lane = (x 4 + y) 4 + z, sample (i, j, k) at
-// p_d = origin_d + (float) i_d * spacing.  `spacing` stands for dx in the bound: r = 1.5 sqrt(3) spacing is the half diagonal of a tile's
-// samples about its centre origin_d + ((float) (4 b_d) + 1.5f) * spacing, and slack = max(spacing / 4, 2^-12 max |coordinate|) with the
-// maximum taken over the vertices and the box's corners (the host's).  dims need not be multiples of 4: the lanes of a partial tile whose
-// sample lies outside the table take part in the culling (their point is still within r of the centre) and do not store.  The result does
-// not depend on the culling: a triangle that passes needlessly loses the strict < comparison.  Always outward-signed (inside_out acts at the
-// query).  LDS: kMeshChunk x (48 B record + 4 B index) = 6.5 KiB per block, no scratch, no atomics (tests/test_collision_volume_isa.py).
-__global__ __launch_bounds__(64) void collision_volume_mesh_kernel(const MeshTri* __restrict__ tris, const MeshPseudo* __restrict__ pseudo, int nt, int d0, int d1, int d2, float o0, float o1,
-																	float o2, float spacing, float slack, float4* __restrict__ table) {
-	__shared__ float4 s_rec[kMeshChunk * 3];
-	__shared__ int s_idx[kMeshChunk];
-	const int lane = (int) threadIdx.x;
-	const unsigned t1 = (unsigned) ((d1 + 3) >> 2), t2 = (unsigned) ((d2 + 3) >> 2);
-	const int bz = (int) (blockIdx.x % t2), by = (int) ((blockIdx.x / t2) % t1), bx = (int) (blockIdx.x / (t2 * t1));
-	const int idx[3]	  = {4 * bx + (lane >> 4), 4 * by + ((lane >> 2) & 3), 4 * bz + (lane & 3)};
-	const bool stores	  = idx[0] < d0 && idx[1] < d1 && idx[2] < d2;
-	const float p[3]	  = {volume_sample_point(o0, spacing, idx[0]), volume_sample_point(o1, spacing, idx[1]), volume_sample_point(o2, spacing, idx[2])};
-	const float centre[3] = {o0 + ((float) (4 * bx) + 1.5f) * spacing, o1 + ((float) (4 * by) + 1.5f) * spacing, o2 + ((float) (4 * bz) + 1.5f) * spacing};
-	const float4* tris4	  = reinterpret_cast<const float4*>(tris);
-	auto load_tri = [&](const float4* src, MeshTri& t) {
-		const float4 r0 = src[0], r1 = src[1], r2 = src[2];
-		t.a[0] = r0.x, t.a[1] = r0.y, t.a[2] = r0.z, t.ab[0] = r0.w;
-		t.ab[1] = r1.x, t.ab[2] = r1.y, t.ac[0] = r1.z, t.ac[1] = r1.w;
-		t.ac[2] = r2.x, t.nh[0] = r2.y, t.nh[1] = r2.z, t.nh[2] = r2.w;
-	};
-	// 1. bound
-	float qmin = INFINITY;
-	for(int base = 0; base < nt; base += 64) {
-		const int t = min(base + lane, nt - 1);
-		MeshTri tri;
-		load_tri(tris4 + 3 * (size_t) t, tri);
-		float c[3];
-		int f;
-		qmin = fminf(qmin, mesh_closest(tri, centre, c, f));
-	}
-	for(int off = 32; off > 0; off >>= 1) qmin = fminf(qmin, __shfl_xor(qmin, off));
-	const float thr	 = (sqrtf(qmin) + 2.f * (2.598076211f * spacing)) * 1.015625f + slack;
-	const float thr2 = thr * thr;
-	// 2. candidates
-	float best_q = INFINITY;
-	int best_t	 = 0;
-	int fill	 = 0;// wave-uniform
-	for(int base = 0; base < nt; base += 64) {
-		const int t	  = base + lane;
-		const bool in = t < nt;
-		MeshTri tri;
-		load_tri(tris4 + 3 * (size_t) (in ? t : nt - 1), tri);
-		float c[3];
-		int f;
-		const float qc				  = mesh_closest(tri, centre, c, f);
-		const bool cand				  = in && qc <= thr2;
-		const unsigned long long mask = __ballot(cand);
-		if(cand) {
-			const int pos = fill + (int) __popcll(mask & ((1ull << lane) - 1ull));// < fill + 64 <= kMeshChunk
-			const float4* src = tris4 + 3 * (size_t) t;
-			s_rec[3 * pos]	   = src[0];
-			s_rec[3 * pos + 1] = src[1];
-			s_rec[3 * pos + 2] = src[2];
-			s_idx[pos]		   = t;
-		}
-		fill += (int) __popcll(mask);
-		if(fill > kMeshChunk - 64 || base + 64 >= nt) {
-			__syncthreads();
-			for(int i = 0; i < fill; ++i) {
-				MeshTri ct;
-				load_tri(s_rec + 3 * i, ct);
-				const float qt = mesh_closest(ct, p, c, f);
-				if(qt < best_q) best_q = qt, best_t = s_idx[i];
-			}
-			__syncthreads();
-			fill = 0;
-		}
-	}
-	// 3. rule and store
-	MeshTri win;
-	load_tri(tris4 + 3 * (size_t) best_t, win);
-	float out[4], q;
-	int feature;
-	mesh_field_value(win, pseudo[best_t], p, 0, out, feature, q);
-	if(stores) table[((size_t) idx[0] * (size_t) d1 + (size_t) idx[1]) * (size_t) d2 + (size_t) idx[2]] = make_float4(out[0], out[1], out[2], out[3]);
-}
-
-// mpm_get_collision_volume: the box lo + [0, b) of a table of (., d1, d2) samples, x slowest, z fastest (bounds are the host's to check)
-__global__ void collision_volume_box_kernel(const float4* __restrict__ table, int d1, int d2, int lo0, int lo1, int lo2, int b0, int b1, int b2, float4* __restrict__ out) {
-	const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
-	if(i >= (size_t) b0 * (size_t) b1 * (size_t) b2) return;
-	const int z = (int) (i % (size_t) b2), y = (int) ((i / (size_t) b2) % (size_t) b1), x = (int) (i / ((size_t) b2 * (size_t) b1));
-	out[i]		= table[((size_t) (lo0 + x) * (size_t) d1 + (size_t) (lo1 + y)) * (size_t) d2 + (size_t) (lo2 + z)];
-}
-
-}// namespace mpm
 #endif// __HIPCC__

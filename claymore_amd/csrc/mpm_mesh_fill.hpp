@@ -4,7 +4,8 @@
 // the hits are compacted in a fixed order - it is the particle's id - without atomics.  Three parts, as in mpm_collision_mesh.hpp:
 //   1. the definition - the candidate lattice, the clip rule mesh_fill_range, the order - in plain C++ that builds on x86 too;
 //      mesh_fill_host restates the whole sampler per point (claymore_amd/host/host_selftest.cpp --mesh-fill, tests/mesh_fill_model.py in NumPy);
-//   2. the kernels (HIP only): classify (one wave per 4 x 4 x 4 node tile), an exclusive scan of the tile counts, emit;
+//   2. the kernels (HIP only): classify (one wave per 4 x 4 x 4 node tile, on mpm_collision_mesh.hpp's tile walk), an exclusive scan of the
+//      tile counts, emit;
 //   3. the host routine is in claymore_hip.hip (mesh_fill_count / mesh_fill_emit): both entry points run the same kernels.
 // The definition is in include/claymore_amd.h and INTEGRATION.md section 5.
 #pragma once
@@ -82,8 +83,9 @@ struct MeshFillArgs {
 	int tlo[3], tn[3]; // its tiles
 };
 
-// Classify.  One wave (a 64-thread block) per tile of the clipped range, one node per lane as in collision_mesh_field_kernel, and the same
-// three steps with the node replaced by its 8 candidates:
+// Classify.  One wave (a 64-thread block) per tile of the clipped range, one node per lane as in collision_mesh_table_kernel, and the same
+// three steps - mpm_collision_mesh.hpp's walk: mesh_centre_bound, mesh_sweep_candidates, mesh_walk_chunk; the argument is written there -
+// with the node replaced by its 8 candidates:
 //   1. Bound.  q at the tile's centre over all triangles, a wave-min with the lowest index among equals: D = sqrtf(min q) and T(centre).
 //      Every candidate of the tile is within r = (1.5 + 0.25) sqrt(3) dx of the centre: the nodes' half diagonal plus the candidates' offset.
 //   2. Candidates, once per tile.  A triangle nearest to a candidate is within D + 2 r of the centre; the test, its float32 safety margin
@@ -118,89 +120,37 @@ __global__ __launch_bounds__(64) void mesh_fill_classify_kernel(const MeshTri* _
 	const float py0 = mesh_fill_coord(node[1], 0, dx), py1 = mesh_fill_coord(node[1], 1, dx);
 	const float pz0 = mesh_fill_coord(node[2], 0, dx), pz1 = mesh_fill_coord(node[2], 1, dx);
 	const float4* tris4 = reinterpret_cast<const float4*>(tris);
-	auto load_tri = [&](const float4* src, MeshTri& t) {
-		const float4 r0 = src[0], r1 = src[1], r2 = src[2];
-		t.a[0] = r0.x, t.a[1] = r0.y, t.a[2] = r0.z, t.ab[0] = r0.w;
-		t.ab[1] = r1.x, t.ab[2] = r1.y, t.ac[0] = r1.z, t.ac[1] = r1.w;
-		t.ac[2] = r2.x, t.nh[0] = r2.y, t.nh[1] = r2.z, t.nh[2] = r2.w;
-	};
 	unsigned mask = 0;
 	// 1. bound, and the centre's nearest triangle
-	float qmin = INFINITY;
-	int tmin   = 0;
-	for(int base = 0; base < nt; base += 64) {
-		const int t = min(base + lane, nt - 1);
-		MeshTri tri;
-		load_tri(tris4 + 3 * (size_t) t, tri);
-		float c[3];
-		int f;
-		const float q = mesh_closest(tri, centre, c, f);
-		if(q < qmin) qmin = q, tmin = t;
-	}
-	for(int off = 32; off > 0; off >>= 1) {
-		const float oq = __shfl_xor(qmin, off);
-		const int ot   = __shfl_xor(tmin, off);
-		if(oq < qmin || (oq == qmin && ot < tmin)) qmin = oq, tmin = ot;
-	}
-	const float D = sqrtf(qmin);
+	int tmin;
+	const float D = sqrtf(mesh_centre_bound(tris4, nt, lane, centre, tmin));
 	const float r = kMeshFillRadius * dx;
 	if(D > (r + a.margin) * 1.015625f + a.slack) {// wave-uniform: the tile is all in or all out
 		MeshTri win;
-		load_tri(tris4 + 3 * (size_t) tmin, win);
+		mesh_load_tri(tris4 + 3 * (size_t) tmin, win);
 		float out[4], q;
 		int feature;
 		mesh_field_value(win, pseudo[tmin], centre, 0, out, feature, q);
 		mask = live && out[0] < -a.margin ? 0xFFu : 0u;
 		if(lane == 0) atomicAdd(shortcuts, 1ull);
 	} else {
-		const float thr	 = (D + 2.f * r) * 1.015625f + a.slack;
-		const float thr2 = thr * thr;
 		// 2. candidates
 		float best_q[8];
 		int best_t[8];
 		MPM_MESH_UNROLL
 		for(int j = 0; j < 8; ++j) best_q[j] = INFINITY, best_t[j] = 0;
-		int fill = 0;// wave-uniform
-		for(int base = 0; base < nt; base += 64) {
-			const int t	  = base + lane;
-			const bool in = t < nt;
-			MeshTri tri;
-			load_tri(tris4 + 3 * (size_t) (in ? t : nt - 1), tri);
-			float c[3];
-			int f;
-			const float qc				  = mesh_closest(tri, centre, c, f);
-			const bool cand				  = in && qc <= thr2;
-			const unsigned long long hits = __ballot(cand);
-			if(cand) {
-				const int pos = fill + (int) __popcll(hits & ((1ull << lane) - 1ull));// < fill + 64 <= kMeshChunk
-				const float4* src  = tris4 + 3 * (size_t) t;
-				s_rec[3 * pos]	   = src[0];
-				s_rec[3 * pos + 1] = src[1];
-				s_rec[3 * pos + 2] = src[2];
-				s_idx[pos]		   = t;
+		mesh_sweep_candidates(tris4, nt, lane, centre, mesh_threshold2(D, r, a.slack), s_rec, s_idx, [&](int fill) {
+			_Pragma("unroll 1") for(int k = 0; k < 8; ++k) {
+				const float p[3] = {k & 4 ? px1 : px0, k & 2 ? py1 : py0, k & 1 ? pz1 : pz0};
+				float bq		 = best_q[0];
+				int bt			 = best_t[0];
+				MPM_MESH_UNROLL
+				for(int j = 1; j < 8; ++j) bq = k == j ? best_q[j] : bq, bt = k == j ? best_t[j] : bt;
+				mesh_walk_chunk(s_rec, s_idx, fill, p, bq, bt);
+				MPM_MESH_UNROLL
+				for(int j = 0; j < 8; ++j) best_q[j] = k == j ? bq : best_q[j], best_t[j] = k == j ? bt : best_t[j];
 			}
-			fill += (int) __popcll(hits);
-			if(fill > kMeshChunk - 64 || base + 64 >= nt) {
-				__syncthreads();
-				_Pragma("unroll 1") for(int k = 0; k < 8; ++k) {
-					const float p[3] = {k & 4 ? px1 : px0, k & 2 ? py1 : py0, k & 1 ? pz1 : pz0};
-					float bq		 = best_q[0];
-					int bt			 = best_t[0];
-					MPM_MESH_UNROLL
-					for(int j = 1; j < 8; ++j) bq = k == j ? best_q[j] : bq, bt = k == j ? best_t[j] : bt;
-					for(int i = 0; i < fill; ++i) {
-						MeshTri ct;
-						load_tri(s_rec + 3 * i, ct);
-						const float qt = mesh_closest(ct, p, c, f);
-						if(qt < bq) bq = qt, bt = s_idx[i];
-					}
-					MPM_MESH_UNROLL
-					for(int j = 0; j < 8; ++j) best_q[j] = k == j ? bq : best_q[j], best_t[j] = k == j ? bt : best_t[j];
-				}
-				__syncthreads();
-				fill = 0;
-			}
-		}
+		});
 		// 3. rule
 		_Pragma("unroll 1") for(int k = 0; k < 8; ++k) {
 			const float p[3] = {k & 4 ? px1 : px0, k & 2 ? py1 : py0, k & 1 ? pz1 : pz0};
@@ -208,7 +158,7 @@ __global__ __launch_bounds__(64) void mesh_fill_classify_kernel(const MeshTri* _
 			MPM_MESH_UNROLL
 			for(int j = 1; j < 8; ++j) bt = k == j ? best_t[j] : bt;
 			MeshTri win;
-			load_tri(tris4 + 3 * (size_t) bt, win);
+			mesh_load_tri(tris4 + 3 * (size_t) bt, win);
 			float out[4], q;
 			int feature;
 			mesh_field_value(win, pseudo[bt], p, 0, out, feature, q);

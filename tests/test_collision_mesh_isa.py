@@ -3,7 +3,7 @@ flags produce (CPU only, as tests/test_grid_isosurface_isa.py does): no scratch 
 pseudonormal is read by address - and the LDS the file states: one chunk of 128 records of 48 bytes with their 4-byte indices."""
 from test_isa_invariants import device_asm, directive, instr, kernel_body  # noqa: F401  (device_asm: the module-scoped cross-compile fixture)
 
-KERNEL = "_ZN3mpm27collision_mesh_field_kernelE"
+KERNEL = "_ZN3mpm27collision_mesh_table_kernelE"
 
 
 def test_collision_mesh_kernel_uses_no_scratch_and_its_stated_lds(device_asm):

@@ -1,5 +1,5 @@
 """The volume collider on the GPU (claymore_amd/csrc/mpm_collision_volume.hpp; grid_update_collider_kernel<VolumeColliderArgs>,
-carry_grid_kernel<true, VolumeColliderArgs>, collision_volume_mesh_kernel, mpm_test_collision_volume) against tests/collision_volume_model.py,
+carry_grid_kernel<true, VolumeColliderArgs>, collision_mesh_table_kernel, mpm_test_collision_volume) against tests/collision_volume_model.py,
 which tests/test_collision_volume_cpu.py judges on the CPU.  The grids are injected through the checkpoint port of
 tests/test_collision_shapes_gpu.py (its ShapeCtx): grid_update_model's 28-particle scene at bits 6 with 222 neighbour blocks in all 27 wall
 classes, the generator's finite tier.  Every comparison with the model is on uint32 bit patterns; computed NaNs compare as NaNs
@@ -156,6 +156,8 @@ MESHES = {
     "box": dict(mesh=lambda: scenes.box_mesh(*BOX), origin=(0.2331, 0.3517, 0.1823), spacing=0.0371, dims=(13, 9, 18)),
     # 320 triangles: more than one kMeshChunk flush per tile
     "icosphere": dict(mesh=lambda: scenes.icosphere((0.47, 0.52, 0.55), 0.21, 2), origin=(0.2231, 0.2617, 0.2923), spacing=0.0271, dims=(19, 20, 21)),
+    # 80 triangles, no multiple of 64: the walk's last sweep is partly filled (the bound's lanes clamped to nt - 1, the candidate test's excluded)
+    "icosphere80": dict(mesh=lambda: scenes.icosphere((0.47, 0.52, 0.55), 0.21, 1), origin=(0.2231, 0.2617, 0.2923), spacing=0.0471, dims=(10, 11, 9)),
     # dims = 0: the box is the host's
     "auto": dict(mesh=lambda: scenes.icosphere((0.47, 0.52, 0.55), 0.11, 2), origin=None, spacing=0.0171, dims=None),
 }

@@ -8,7 +8,7 @@ from test_isa_invariants import device_asm, directive, instr, kernel_body  # noq
 
 VGPR_STEP = 80          # six waves per SIMD: tests/test_grid_update_isa.py's budget of every collider kernel
 GRID = {"stand-alone": "_ZN3mpm27grid_update_collider_kernelINS_18VolumeColliderArgsEEE", "carry": "_ZN3mpm17carry_grid_kernelILb1ENS_18VolumeColliderArgsEEE"}
-BUILD = "_ZN3mpm28collision_volume_mesh_kernelE"
+BUILD = "_ZN3mpm27collision_mesh_table_kernelE"    # the level-set field's kernel too (claymore_amd/csrc/mpm_collision_mesh.hpp)
 
 
 @pytest.mark.parametrize("name", sorted(GRID))

@@ -25,6 +25,8 @@ PRM = {"volume": scenes._vol(BITS), "youngs_modulus": 5e3, "poisson_ratio": 0.4,
 CASES = {name: (mesh, 0.0, None) for name, mesh in MESHES.items()}
 CASES.update({name + ", margin": (mesh, 0.75 * DX, None) for name, mesh in MESHES.items()})
 CASES["icosphere 3"] = (lambda: scenes.icosphere((0.47, 0.53, 0.51), 6.0 / 64, 3), 0.0, None)
+# 80 triangles, no multiple of 64: the walk's last sweep is partly filled (the bound's lanes clamped to nt - 1, the candidate test's excluded)
+CASES["icosphere 1, 80 triangles"] = (lambda: scenes.icosphere((0.47, 0.52, 0.55), 0.21, 1), 0.0, None)
 CASES["octahedron, box through tiles"] = (MESHES["octahedron"], 0.0, ((0, 30, 0), (N, 39, 35)))
 CASES["L prism, box and margin"] = (MESHES["L prism"], 0.3 * DX, ((19, 0, 21), (38, N, 30)))
 TINY = ((0.505, 0.505, 0.505), (0.510, 0.510, 0.510))                                              # between two candidates: holds none

@@ -269,6 +269,21 @@ MPM_DEV void sym_expand(const float (&s)[6], float (&m)[9]) {
 	m[6] = s[4], m[7] = s[5], m[8] = s[2];
 }
 
+// det b of {b00, b11, b22, b10, b20, b21}: the 2 x 2 minors as differences of products with the rounding error of one product recovered by an fma
+// (Kahan), so that det b - and with it J = sqrt(det b) - is good to an ulp or two.  The eigenvalues' product is not: every rotation rounds, and with
+// lambda >> mu (nu -> 0.5) the volumetric stress carries the error of J amplified by lambda / E.
+MPM_DEV float diff_of_products(float a, float b, float c, float d) {// a b - c d
+	const float w = c * d;
+	const float e = fmaf(-c, d, w);
+	return fmaf(a, b, -w) + e;
+}
+MPM_DEV float sym_det3(const float (&b)[6]) {
+	const float m0 = diff_of_products(b[1], b[2], b[5], b[5]);
+	const float m1 = diff_of_products(b[3], b[2], b[5], b[4]);
+	const float m2 = diff_of_products(b[3], b[5], b[1], b[4]);
+	return fmaf(b[0], m0, fmaf(-b[3], m1, b[4] * m2));
+}
+
 // The scale the stress leaves a model with, as uniform factors formed on the host (gfx950 has no scalar float ALU: a uniform product
 // formed in the kernel costs a vector instruction per iteration or a vector register for the whole loop).  Function-level tests pass
 // {2 mu vol, lambda vol, vol}: P F^T vol as the reference returns it; G2P2G passes the same times -new_dt D^-1 dx, so that the P2G
@@ -317,14 +332,19 @@ MPM_DEV void stress_fixed_corotated(const StressScale& ss, const float (&b)[6], 
 		sig[1] = m1 ? -sig[1] : sig[1];
 		sig[2] = (!m0 && !m1) ? -sig[2] : sig[2];
 	}
-	const float J  = sig[0] * sig[1] * sig[2];
+	// |J| = sqrt(det b) with det b from b itself (sym_det3), not the product of three rooted eigenvalues, and the volumetric term lambda (J - 1) J -
+	// isotropic - goes onto the diagonal directly, not through U diag(.) U^T, where it would pick up U's departure from orthogonality: with
+	// lambda >> mu (nu -> 0.5) both errors reach P F^T amplified by lambda / E.
+	const float Jabs = __builtin_amdgcn_sqrtf(fmaxf(sym_det3(b), 0.f));
+	const float J	 = refl ? -Jabs : Jabs;
 	if(J_out) *J_out = J;
 	const float vl = ss.lamv * (J - 1.0f) * J;
 	const float vm = ss.mu2v;
 	float d[3], pf[6];
 #pragma unroll
-	for(int k = 0; k < 3; ++k) d[k] = fmaf(vm, lam[k] - sig[k], vl);
+	for(int k = 0; k < 3; ++k) d[k] = vm * (lam[k] - sig[k]);
 	sym_from_eig(U, d, pf);
+	pf[0] += vl, pf[1] += vl, pf[2] += vl;
 	sym_expand(pf, PF);
 	hk.template at<BASE + kEigSites>();
 }
@@ -348,14 +368,18 @@ MPM_DEV void stress_sand(const MaterialConst& mc, const StressScale& ss, float (
 	const bool skip = undeformed && mc.cohesion == 0.f && __all((log_jp >= 0.f) & !refl);
 	const float scaled_mu = 2.0f * mc.mu;
 	float lns[3], epsilon[3], epsilon_hat[3], lnS[3];
-	float sum_epsilon = 0.f, trace_epsilon = 0.f, epsilon_hat_norm = 0.f;
+	float sum_epsilon = 0.f, trace_epsilon = 0.f, epsilon_hat_norm = 0.f, sum_lns = 0.f, trace_log_S = 0.f;
 	if(!skip) {
 #pragma unroll
 		for(int i = 0; i < 3; i++) {
 			lns[i]	   = 0.5f * log_fast(fmaxf(lam[i], 1e-8f));// ln max(|S|, 1e-4) (:262)
 			epsilon[i] = lns[i] - mc.cohesion;
 		}
-		sum_epsilon	  = epsilon[0] + epsilon[1] + epsilon[2];
+		// sum ln sigma = 0.5 ln det b from b itself (sym_det3) rather than from three eigenvalues that each carry the rotations' rounding: the trace
+		// reaches P F^T times lambda.  Near a singular b (the clamp of :262 at work, or a det b that rounding may have made <= 0) the plain sum stands.
+		const float det = sym_det3(b);
+		sum_lns			= (fminf(fminf(lam[0], lam[1]), lam[2]) > 1e-3f && det > 0.f) ? 0.5f * log_fast(det) : lns[0] + lns[1] + lns[2];
+		sum_epsilon	  = sum_lns - 3.0f * mc.cohesion;
 		trace_epsilon = sum_epsilon + log_jp;
 #pragma unroll
 		for(int i = 0; i < 3; i++) epsilon_hat[i] = epsilon[i] - (trace_epsilon * (1.0f / 3.0f));
@@ -377,6 +401,8 @@ MPM_DEV void stress_sand(const MaterialConst& mc, const StressScale& ss, float (
 			moved |= dl != 0.f;
 			lnS[i] = dead ? -__builtin_inff() : lns[i] + dl;
 		}
+		// tr ln S_new: off the tip sum dl = -r sum epsilon_hat = r log Jp (sum epsilon_hat = sum epsilon - trace epsilon), added to the sum above
+		trace_log_S = (tip | dead) ? lnS[0] + lnS[1] + lnS[2] : fmaf(r, log_jp, sum_lns);
 		log_jp = tip ? (mc.volume_correction ? mc.beta * sum_epsilon + log_jp : log_jp) : (dead ? log_jp : 0.f);
 		// The projected b = U diag(exp(2 ln S_new)) U^T.  While every particle of the wave is inside the cone (dl = 0 exactly: elastic, the
 		// state of a column at rest; or at the tip with zero strain: free fall) the trial b stands and the rebuild is skipped for the
@@ -395,12 +421,13 @@ MPM_DEV void stress_sand(const MaterialConst& mc, const StressScale& ss, float (
 	}
 	hk.template at<BASE + kEigSites + 1>();
 	if(!skip) {
-		const float trace_log_S = lnS[0] + lnS[1] + lnS[2];
 		if(J_out) *J_out = exp_fast(trace_log_S);// J = exp(sum ln S_new)
 		float d[3], pf[6];
 #pragma unroll
-		for(int k = 0; k < 3; ++k) d[k] = ss.mu2v * lnS[k] + ss.lamv * trace_log_S;
+		for(int k = 0; k < 3; ++k) d[k] = ss.mu2v * lnS[k];
 		sym_from_eig(U, d, pf);
+		const float vl = ss.lamv * trace_log_S;// (isotropic: onto the diagonal directly, see stress_fixed_corotated)
+		pf[0] += vl, pf[1] += vl, pf[2] += vl;
 		sym_expand(pf, PF);
 	} else {
 		if(J_out) *J_out = 1.f;

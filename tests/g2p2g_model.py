@@ -464,11 +464,11 @@ def scene_slab(seed=6, lo=185, hi=215):
     return np.concatenate([block_particles(k, int(rng.integers(lo, hi + 1)), rng) for k in SLAB])
 
 
-SCENE_SEED = {"isolated": 11, "block_sizes": 12, "one_cell": 13, "cluster": 14, "torn": 15, "slab": 16}
+SCENE_SEED = {"isolated": 11, "block_sizes": 12, "one_cell": 13, "cluster": 14, "torn": 15, "slab": 16, "cluster_b": 44}
 SCENES = {"isolated": scene_isolated, "block_sizes": scene_block_sizes, "one_cell": scene_one_cell, "cluster": scene_cluster, "torn": scene_torn}
 # Scenes that scene_state() serves but that stay out of the yardstick: test_g2p2g_model_cpu.measure_generated iterates SCENES and check_constants
 # pins Y to what it measures there.  A scene here is licensed by a CPU test of its own, which holds the reference side to bound() on it.
-EXTRA_SCENES = {"slab": scene_slab}
+EXTRA_SCENES = {"slab": scene_slab, "cluster_b": lambda: scene_cluster(seed=44, lo=90, hi=110)}     # cluster_b: a second, thinner model in the cluster's blocks
 BANDS = ((0.97, 1.03), (0.9, 1.1), (0.75, 1.3))
 BAND_SHARE = (0.5, 0.25, 0.25)                 # half of the draws from the innermost band: NACC's case 0 (inside the yield surface) lives there
 # A float32 SVD that has converged reproduces F to a few ulp: the median residual max |U S V^T - F| of the reference's 4-sweep SVD (svd.cuh:167)
@@ -512,9 +512,9 @@ def make_state(material, n, seed):
     return st
 
 
-def model_scene(material, pos_cells, st, tier, seed=0, dt=DT, new_dt=NEW_DT):
-    """step() on a scene with the field of `tier`."""
-    c = constants(material, material_overrides(material))
+def model_scene(material, pos_cells, st, tier, seed=0, dt=DT, new_dt=NEW_DT, overrides=None):
+    """step() on a scene with the field of `tier`.  overrides: the model's parameters (None: material_overrides)."""
+    c = constants(material, material_overrides(material) if overrides is None else overrides)
     return step(c, pos_cells, gather_field(pos_cells, tier, seed), b6=st["b6"], reflected=st["reflected"], logjp=st["logjp"], J=st["J"], dt=dt, new_dt=new_dt)
 
 
@@ -543,11 +543,11 @@ def oracle_rows(material, params, bits, arena, rows13, dt, new_dt):
     return of, oi
 
 
-def oracle_scene(material, pos_cells, st, tier, seed=0, dt=DT, new_dt=NEW_DT, bits=BITS):
+def oracle_scene(material, pos_cells, st, tier, seed=0, dt=DT, new_dt=NEW_DT, bits=BITS, overrides=None):
     """The oracle's particle body on a scene, block by block (the particles of a block share its velocity arena)."""
     pos_cells = np.asarray(pos_cells, np.float32)
     n = pos_cells.shape[0]
-    params = oracle_params(material, material_overrides(material, bits), bits)
+    params = oracle_params(material, material_overrides(material, bits) if overrides is None else overrides, bits)
     rows = np.zeros((n, 13), np.float32)
     rows[:, :3] = pos_cells * np.float32(0.5 ** bits)
     if material == J_FLUID:
@@ -594,15 +594,15 @@ def reference_svd_residual(F):
     return np.abs(R - F64).max(axis=(1, 2)) / np.maximum(1.0, np.abs(F64).max(axis=(1, 2)))
 
 
-def ill_posed(material, pos_cells, st, tiers=tuple(TIERS), seed=0, bits=BITS):
-    """The rows of a scene that cannot be held to a float bound on some tier: the sand branch / NACC case changes when the trial F is scaled by
-    1 +- 1e-5 (step's "unstable"), or the reference's SVD has not converged on the trial F (SVD_RESIDUAL)."""
+def ill_posed(material, pos_cells, st, tiers=tuple(TIERS), seed=0, bits=BITS, overrides=None):
+    """The rows of a scene that cannot be held to a float bound on some tier: the sand branch / NACC case - at the parameters `overrides` - changes
+    when the trial F is scaled by 1 +- 1e-5 (step's "unstable"), or the reference's SVD has not converged on the trial F (SVD_RESIDUAL)."""
     bad = np.zeros(np.asarray(pos_cells).shape[0], bool)
     if material == J_FLUID:
         return bad
     dx = 0.5 ** bits
     for tier in tiers:
-        m = model_scene(material, pos_cells, st, tier, seed)
+        m = model_scene(material, pos_cells, st, tier, seed, overrides=overrides)
         G = np.eye(3)[None] + DT * (4.0 / (dx * dx)) * m["A"]
         bad |= m["unstable"] | ~m["finite"] if tier != "torn" else m["unstable"]
         bad |= reference_svd_residual(G @ st["F32"].astype(np.float64)) > SVD_RESIDUAL
@@ -612,24 +612,25 @@ def ill_posed(material, pos_cells, st, tiers=tuple(TIERS), seed=0, bits=BITS):
 _SCENE_STATES = {}
 
 
-def scene_state(name, material):
-    """The positions (cells, float32) and the state of scene `name` for a material: one fixed draw per scene and material.  Rows that are
-    ill_posed on any tier get the state of a further draw, until none is left: no scene holds a row on the brink of a branch, or one whose
-    trial F the reference cannot decompose."""
-    if (name, material) not in _SCENE_STATES:
+def scene_state(name, material, overrides=None):
+    """The positions (cells, float32) and the state of scene `name` for a material: one fixed draw per scene, material and parameter set
+    (overrides; None: material_overrides).  Rows that are ill_posed on any tier get the state of a further draw, until none is left: no scene
+    holds a row on the brink of a branch of ITS parameters, or one whose trial F the reference cannot decompose."""
+    key = (name, material) if overrides is None else (name, material, tuple(sorted(overrides.items())))
+    if key not in _SCENE_STATES:
         pos = (SCENES[name] if name in SCENES else EXTRA_SCENES[name])()
         st = make_state(material, pos.shape[0], SCENE_SEED[name])
         for draw in range(1, 12):
-            bad = ill_posed(material, pos, st)
+            bad = ill_posed(material, pos, st, overrides=overrides)
             if not bad.any():
                 break
             new = make_state(material, pos.shape[0], SCENE_SEED[name] + 100 * draw)
             for k in ("F32", "b6", "reflected", "logjp"):
                 if st[k] is not None:
                     st[k][bad] = new[k][bad]
-        assert not ill_posed(material, pos, st).any()
-        _SCENE_STATES[name, material] = (pos, st)
-    pos, st = _SCENE_STATES[name, material]
+        assert not ill_posed(material, pos, st, overrides=overrides).any()
+        _SCENE_STATES[key] = (pos, st)
+    pos, st = _SCENE_STATES[key]
     return pos.copy(), {k: (v.copy() if v is not None else None) for k, v in st.items()}
 
 

@@ -121,6 +121,34 @@ def test_checkpoint_rejects_other_physics_and_corrupt_headers():
     d.close()
 
 
+@pytest.mark.parametrize("material,field,value,loads", [(_ffi.SAND, "cohesion", 0.01, False), (_ffi.SAND, "volume_correction", 0, False),
+                                                        (_ffi.NACC, "hardening_on", 0, False), (_ffi.FIXED_COROTATED, "cohesion", 0.01, True)])
+def test_checkpoint_hash_covers_the_constitutive_parameters(material, field, value, loads):
+    """A checkpoint saved at the default parameters is refused by a context whose model differs in ONE constitutive parameter its material
+    consumes (sand: cohesion, volume_correction; NACC: hardening_on) - and still loads where the material ignores the field (fixed-corotated:
+    cohesion)."""
+    def scene(params):
+        sc = scenes.sphere_drop(bits=6, radius_cells=4.0, center=(0.5, 0.4, 0.5), material=material)
+        sc["models"][0]["params"] = params
+        return sc
+    a = build_engine(scene({}))
+    a.initial_setup()
+    a.run_fixed(2, 1e-4)
+    ckpt = a.save_checkpoint().copy()
+    saved = getattr(a.models[0]["params"], field)
+    a.close()
+    b = build_engine(scene({field: value}))
+    b.initial_setup()
+    assert getattr(b.models[0]["params"], field) != saved
+    if loads:
+        b.load_checkpoint(ckpt)
+        b.run_fixed(1, 1e-4)
+    else:
+        with pytest.raises(Exception):
+            b.load_checkpoint(ckpt)
+    b.close()
+
+
 def test_checkpoint_into_a_smaller_capacity_grows_it():
     """The checkpoint needs more blocks than the loading context has: the load grows the capacity (check_capacity path)."""
     # a sphere centred on a block corner occupies 2^3 particle blocks; two cells further along the diagonal it straddles 3^3

@@ -42,9 +42,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 DX = 0.5 ** gm.BITS
 
 
-def check_particles(bench, res, models, tier, tag, fails):
+def check_particles(bench, res, models, tier, tag, fails, bound_of=None):
     """The per-particle half of check(): counts, state and position of every particle of every model against `models`, and the books (particle
-    blocks, lost, discarded).  Appends to `fails`; returns the per-model stencil bounds the grid comparison needs."""
+    blocks, lost, discarded).  Appends to `fails`; returns the per-model stencil bounds the grid comparison needs.  bound_of(i, quantity, tier,
+    material): the bound of model i (default: g2p2g_model.bound for every model)."""
+    if bound_of is None:
+        bound_of = lambda i, q, t, mat: gm.bound(q, t, mat)
     blocks = set()
     n_disc = 0
     sbs = []
@@ -69,14 +72,14 @@ def check_particles(bench, res, models, tier, tag, fails):
             if material != gm.FC:
                 figs["logjp"] = np.abs(got["logjp"][idx].astype(np.float64) - m["logjp"][rows])[keep]
         for q, e in figs.items():
-            bnd = gm.bound(q, tier, material)
+            bnd = bound_of(i, q, tier, material)
             worst = float(e.max()) if e.size else 0.0
             print(f"{tag} {name} {tier} {q}: worst {worst:.3g} bound {bnd:.3g} (Y {gm.Y[q, tier, name]:.3g}) over {e.size} particles")
             if not worst <= bnd:
                 fails.append((name, q, worst, bnd, int((e > bnd).sum())))
         blocks.update(map(tuple, gm.block_keys(got["pos"]).tolist()))
         n_disc += int(m["discarded"][fin].sum())
-        sbs.append(gm.bound("stencil", tier, material))
+        sbs.append(bound_of(i, "stencil", tier, material))
     # the books
     print(f"{tag} {tier}: particle blocks {res['counts'].particle_blocks} (positions say {len(blocks)}), lost {res['lost']}, discarded {res['discarded']} (model {n_disc})")
     if res["counts"].particle_blocks != len(blocks):
@@ -99,12 +102,12 @@ def check_grid(exp, grid, tier, tag, fails):
         fails.append(("total mass", float(gv[:, 0].sum()), float(exp["sum"][:, 0].sum()), mass_bound))
 
 
-def check(bench, res, models, tier, tag="", grid_extra=None):
+def check(bench, res, models, tier, tag="", grid_extra=None, bound_of=None):
     """The step's result against the model outputs `models` (one step() dict per model of the bench).  Prints every figure before it asserts.
     grid_extra: (packed node keys, (k, 4) values) that something other than the models' particles has added to the grid, once per node
-    (g2p2g_model.add_contribution); default: nothing."""
+    (g2p2g_model.add_contribution); default: nothing.  bound_of: see check_particles."""
     fails = []
-    sbs = check_particles(bench, res, models, tier, tag, fails)
+    sbs = check_particles(bench, res, models, tier, tag, fails, bound_of)
     exp = gm.assemble(models, sbs)
     if grid_extra is not None:
         exp = gm.add_contribution(exp, *grid_extra)

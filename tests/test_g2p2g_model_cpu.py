@@ -269,15 +269,15 @@ def test_the_assembler_and_the_grid_comparison():
 
 
 # ---- the GPU file's comparison, with the oracle standing in for the engine ----------------------------------------------------------------
-def oracle_as_engine(parts_states, tier):
+def oracle_as_engine(parts_states, tier, overrides=None):
     """What Bench.step() of tests/test_g2p2g_blocks_gpu.py returns, made from the oracle's particle body: the particles in another order, the grid
-    summed in float32 and cut into 4^3 blocks, the books."""
+    summed in float32 and cut into 4^3 blocks, the books.  overrides: per model the parameters the oracle runs at (default: the scenes')."""
     import types
 
     import exact_models as em
     state, allk, allv, disc = [], [], [], 0
-    for material, pos, st in parts_states:
-        of, oi = gm.oracle_scene(material, pos, st, tier)
+    for i, (material, pos, st) in enumerate(parts_states):
+        of, oi = gm.oracle_scene(material, pos, st, tier, overrides=overrides[i] if overrides else None)
         o = gm.oracle_view(material, of, oi)
         perm = np.random.default_rng(5).permutation(pos.shape[0])
         d = dict(pos=(of[:, 12:15] * np.float32(2.0 ** gm.BITS))[perm], logjp=of[perm, 24], J=of[perm, 15], b6=np.zeros((pos.shape[0], 6), np.float32), reflected=np.zeros(pos.shape[0], bool))

@@ -99,7 +99,7 @@ def test_device_fixed_corotated_vs_reference_golden():
 def test_device_sand_vs_reference_golden_and_closed_form():
     """Drucker-Prager return mapping: the projected state (b = F F^T of the projected F: the engine carries b, mpm_device_math.hpp),
     P F^T and log Jp against the float64 closed form, with the reference's own golden output as the yardstick (see the
-    fixed-corotated test)."""
+    fixed-corotated test).  The rows `sel` skips (cohesion 0.01, volume correction off): tests/test_material_params_gpu.py."""
     import exact_models as X
     hip = _ffi.load_hip()
     F = f32("g3_F_in.f32").reshape(-1, 9)
@@ -135,7 +135,8 @@ def test_device_nacc_vs_closed_form_and_reference_golden():
     """NACC (flagged unstable in the reference, constitutive_models.cuh:80): projected F, P F^T and log Jp against the float64
     closed form (tests/exact_models.py: nacc, which itself reproduces the reference's golden output to 1.1e-5 of vol * E), like the
     fixed-corotated and sand tests.  The model is discontinuous in its case selection (tips / surface / inside), so rows whose case
-    changes under a 3e-6 perturbation of F are left out; what remains covers all four cases."""
+    changes under a 3e-6 perturbation of F are left out; what remains covers all four cases.  The rows `sel` skips (hardening off):
+    tests/test_material_params_gpu.py."""
     import exact_models as X
     hip = _ffi.load_hip()
     F = f32("g3_F_in.f32").reshape(-1, 9)
@@ -297,6 +298,21 @@ def test_other_materials_parity(material, steps):
     sc["models"][0]["params"] = {}
     res = run_pair(sc, steps, 1e-4)
     err = match_and_compare(res)
+    assert err["pos_rel"] < POS_TOL, err
+    assert err["logjp_abs"] < 1e-4, err
+
+
+@pytest.mark.parametrize("vid,steps", [("S3", 40), ("N1", 20), ("F2", 40)])
+def test_other_materials_parity_off_the_default_parameters(vid, steps):
+    """test_other_materials_parity with the model's parameters set to a variant of tests/material_variants.py: cohesive sand at a 20 degree friction
+    angle (S3), NACC without hardening (N1), a soft, cubic, viscous J-fluid (F2).  Same scene, step counts and bounds."""
+    import material_variants as mv
+    material, delta = mv.BY_ID[vid]
+    sc = scenes.sphere_drop(bits=6, radius_cells=6.0, center=(0.5, 0.3, 0.5), material=material)
+    sc["models"][0]["params"] = dict(delta)
+    res = run_pair(sc, steps, 1e-4)
+    err = match_and_compare(res)
+    print(vid, err)
     assert err["pos_rel"] < POS_TOL, err
     assert err["logjp_abs"] < 1e-4, err
 

@@ -137,6 +137,7 @@ SIGNATURES.update(HALO)
 HIP_ONLY = {
     "build_info": (C.c_char_p, []),
     "last_g2p2g_ms": (_i, [_vp, _fp]),
+    "still_launch_sizes": (_i, [C.c_char_p, _i, _i, _i, _ip, _ip]),
     "streams": (_i, [_vp, _P(_vp), _P(_vp)]),
     "sync": (_i, [_vp]),
     "get_capacity": (_i, [_vp, _P(C.c_int64), _P(C.c_int64), _ip]),

@@ -28,7 +28,12 @@ namespace {
 // ONE device block (and its pinned mirror) holds everything the host reads back at a synchronisation: the status words, the MGSP halo
 // counters + the peers' key-list lengths, and the max |v|^2 slots - one device-to-host copy instead of three.
 constexpr int kHaloWords	 = 128;// 2 + 32 send counts + 32 peer list lengths + 32 peer status words, padded
-constexpr int kStatusBlock = ST_WORDS + kHaloWords + kMaxVelSlots * kMaxVelStride;// in 4-byte words
+constexpr int kStatusCore  = ST_WORDS + kHaloWords + kMaxVelSlots * kMaxVelStride;// in 4-byte words
+// ... and behind them the phase stamps of mpm_run_fixed (mpm_kernels.hpp): one row per substep of the longest window (sync_interval is clamped to 64) and the row
+// that closes it, 64-bit values, so they come back with the same copy
+constexpr int kStampRows   = 64 + 1;
+constexpr int kStatusBlock = kStatusCore + kStampRows * kStampRow * 2;
+static_assert(kStatusCore % 2 == 0, "the stamps are 8-byte values");
 
 struct Partition {
 	int* table = nullptr;
@@ -60,6 +65,11 @@ struct Model {
 	int64_t bincount_src = 0;// bins in use in bins[rollid] (the source of the next g2p2g): the previous bincount
 	int64_t bucketed = 0;// particles currently in the advection lists (device-counted at each rebuild)
 	int list_in		 = 0;// which list buffer g2p2g reads next
+};
+
+// workgroups of the rebuild's own prepare launch and of its two registration launches, 0 = the full size (still_launch_rule)
+struct StillLaunch {
+	int prepare = 0, reg = 0;
 };
 
 }// namespace
@@ -98,6 +108,18 @@ struct mpm_ctx {
 	bool relaid = true;
 	int allow_still = 0;// what the rebuild in flight was offered: launch_rebuild sets it for its own kernels and for launch_rebuild_prepare
 	bool rebuild_cleared = false;// the rebuild's part of substep_clear_kernel has been issued together with the P2G part
+	// mpm_run_fixed's phase times come from stamps the kernels write (mpm_kernels.hpp: phase_stamp) unless MPM_PHASE_TIMERS=events asks for the HIP events of
+	// old on every substep (read once, at creation: the A/B reference and the tests' comparison).  stamp_row: the row of the substep being enqueued - what
+	// launch_clear, the first model's G2P2G launch and the compaction pass on - or null: this substep is timed with events.
+	bool phase_events = false;
+	int wall_clock_khz = 0;
+	unsigned long long* d_stamps = nullptr;// kStampRows rows of kStampRow, behind the max |v|^2 slots of the status block
+	const unsigned long long* h_stamps = nullptr;
+	unsigned long long* stamp_row = nullptr;
+	// MPM_STILL_LAUNCH (read at creation; still_launch_rule): -1 auto, 0 full, N > 0 always thin with N workgroups.  streak_seen: ST_STREAK at the last read-back
+	int still_launch = -1;
+	int streak_seen	 = 0;
+	StillLaunch thin;// what the rebuild being enqueued launches with: launch_rebuild sets it for its own kernels and for launch_rebuild_prepare
 	std::vector<hipEvent_t> ev_ring;// 3 events per substep of a window (substep start, G2P2G start / end; its end is the next one's start) + the window's closing event
 	Partition part[2];
 	float* grid[2] = {nullptr, nullptr};
@@ -258,6 +280,36 @@ static inline unsigned cdiv(size_t a, size_t b) {
 	return (unsigned) ((a + b - 1) / b);
 }
 
+// LAUNCH SIZES THAT FOLLOW THE STILL STREAK.  From the second still rebuild in a row on, prepare_blocks_kernel<true> looks at 64 blocks per wave and finds next
+// to nothing to do; sized by the block estimate - one workgroup per exterior block, 89 000 at C3, of which 1 310 look at anything - its launch costs 24 us for
+// work that fits into the 4.7 us a launch takes at the least.  The kernel walks grid-stride over a count it reads from the status block, so any launch size
+// computes the same: when the streak was two or more at the last read-back (and the still path is on) the next window launches it THIN, with kThinPrepare
+// workgroups - never fewer than one per 64 particle blocks (the streak path stays one trip), and enough to fill the chip's wave slots when a thin window
+// meets a mover and runs the full path (six waves per SIMD: 6 144).  The next read-back then finds the streak at 0 and the launch goes back to full size.
+// Measured at C3 (profiles/substep_fixed_cost.txt): 1 024, 4 096, 8 192 and 16 384 workgroups all run in 4.7 us, 256 in 7.9 us.  The two registration
+// kernels, which return behind their first loads on a still substep, take those 4.7 us at their present 4 096 / 8 192 workgroups as at 256: they keep
+// their sizes (the second number is for MPM_STILL_LAUNCH=thin:N alone).
+// override_n (MPM_STILL_LAUNCH): -1 auto = this rule, 0 full = never thin, N > 0 always N workgroups for prepare and both registrations (tests and A/B only).
+// Returns workgroup counts, 0 = the full size; the caller never launches more than the full size.
+constexpr int kThinPrepare = 8192;
+static StillLaunch still_launch_rule(int streak, bool still_on, int pbc_est, int override_n) {
+	if(override_n > 0) return {override_n, override_n};
+	if(override_n == 0 || !still_on || streak < 2) return {0, 0};
+	const long long looked = (long long) std::max(pbc_est, 0) + std::max(pbc_est, 0) / 16 + 64;// (the margin of hint_blocks)
+	return {(int) std::max<long long>(kThinPrepare, (looked + 63) / 64), 0};
+}
+// "auto" (or nothing, or anything else) -1, "full" 0, "thin:N" N >= 1
+static int still_launch_override(const char* e) {
+	if(!e) return -1;
+	if(std::strcmp(e, "full") == 0) return 0;
+	if(std::strncmp(e, "thin:", 5) == 0) {
+		char* end	 = nullptr;
+		const long n = std::strtol(e + 5, &end, 10);
+		if(end != e + 5 && *end == 0 && n >= 1 && n <= (1 << 20)) return (int) n;
+	}
+	return -1;
+}
+
 // The installed colliders as the grid update that is being enqueued sees them, handed to `launch` in the type of their kernels: VolumeColliderArgs
 // with a volume in a slot, else TerrainArgs with a heightfield in a slot, ShapeArgs with analytic shapes alone, CollisionArgs with the level-set object alone, NoCollision without any.
 // One pose per installed collider, all at the one clock's current time T (the start of the substep), by value; a running clock then moves
@@ -404,6 +456,13 @@ int mpm_create(const mpm_config* cfg, int device, mpm_ctx** out) {
 		mpm_destroy(ctx);// frees whatever was created (null handles are skipped)
 		return MPM_ERR_DEVICE;
 	}
+	{
+		const char* e = std::getenv("MPM_PHASE_TIMERS");
+		ctx->phase_events = e && std::strcmp(e, "events") == 0;
+		// (the stamps are ticks of the constant wall clock: a runtime that does not report its rate leaves the events)
+		if(hipDeviceGetAttribute(&ctx->wall_clock_khz, hipDeviceAttributeWallClockRate, device) != hipSuccess || ctx->wall_clock_khz <= 0) ctx->phase_events = true;
+		ctx->still_launch = still_launch_override(std::getenv("MPM_STILL_LAUNCH"));
+	}
 	*out = ctx;
 	return MPM_OK;
 }
@@ -529,6 +588,8 @@ int mpm_initial_setup(mpm_ctx* ctx) {
 	ctx->h_peer_rows   = ctx->h_halo_counts + 2 + 32;
 	ctx->d_maxvel	   = reinterpret_cast<unsigned*>(ctx->d_status + ST_WORDS + kHaloWords);
 	ctx->h_maxvel	   = reinterpret_cast<float*>(ctx->h_status + ST_WORDS + kHaloWords);
+	ctx->d_stamps	   = reinterpret_cast<unsigned long long*>(ctx->d_status + kStatusCore);
+	ctx->h_stamps	   = reinterpret_cast<const unsigned long long*>(ctx->h_status + kStatusCore);
 	HIP_TRY(dalloc(&ctx->d_totals, 4));
 	HIP_TRY(dalloc(&ctx->d_counter, 1));
 	HIP_TRY(hipMemsetAsync(ctx->d_status, 0, sizeof(int) * kStatusBlock, s));
@@ -760,6 +821,7 @@ static void launch_g2p2g_model(mpm_ctx* ctx, Model& m, const int* block_list, co
 	sk.refl_lim = sk.dts > 0.f ? (1.f / 3.f) / sk.dts : 3.0e38f;
 	sk.jdiv		= g.dx * dt * g.d_inv;
 	sk.jvisc	= g.dx * g.d_inv * m.mc.viscosity;
+	sk.stamp	= ctx->stamp_row && &m == &ctx->models.front() ? ctx->stamp_row + 1 : nullptr;
 	const int nwg = nblocks_ptr ? hint_blocks(ctx, nblocks) : nblocks;
 	auto kernel = g2p2g_for<3>(m.pair);
 	switch(m.material) {
@@ -795,6 +857,7 @@ static int launch_clear(mpm_ctx* ctx, int flags) {
 	a.old_table	   = Pn.table;
 	a.old_keys	   = Pn.keys;
 	a.old_count	   = Pn.count;
+	a.stamp		   = (flags & kClearP2G) ? ctx->stamp_row : nullptr;// (the substep's first launch)
 	substep_clear_kernel<<<1024, 256, 0, ctx->s_compute>>>(ctx->g, a);
 	return MPM_OK;
 }
@@ -810,10 +873,10 @@ static int launch_g2p2g(mpm_ctx* ctx, float dt, float next_dt, hipEvent_t e0, hi
 	hipStream_t s = ctx->s_compute;
 	int rc		  = launch_g2p2g_prologue(ctx, with_rebuild_clear, fused_update);
 	if(rc) return rc;
-	HIP_TRY(hipEventRecord(e0, s));
+	if(e0) HIP_TRY(hipEventRecord(e0, s));// (null events: a substep of mpm_run_fixed whose kernels stamp their phases)
 	if(ctx->pbc)
 		for(auto& m: ctx->models) launch_g2p2g_model(ctx, m, nullptr, &ctx->d_status[ST_PBC], ctx->pbc, dt, next_dt, s);
-	HIP_TRY(hipEventRecord(e1, s));
+	if(e1) HIP_TRY(hipEventRecord(e1, s));
 	return MPM_OK;
 }
 
@@ -850,9 +913,10 @@ static int launch_prepare(mpm_ctx* ctx, int cur, int prev, bool list_is_out, int
 		pm.pairinfo[mi]	  = m.pair ? m.pairinfo[0] : nullptr;
 		pm.pairhand[mi]	  = m.pairinfo[1];
 	}
-	const int nwg = std::max(1, std::min(ctx->g.cap, nblocks_est + nblocks_est / 16 + 64));
+	int nwg		  = std::max(1, std::min(ctx->g.cap, nblocks_est + nblocks_est / 16 + 64));
 	int* pub	  = publish ? ctx->d_status : nullptr;
 	const int still = publish && sort && list_is_out ? ctx->allow_still : 0;// (the rebuild's own call only)
+	if(publish && sort && list_is_out && ctx->thin.prepare > 0) nwg = std::min(nwg, ctx->thin.prepare);// (... and it alone follows the still streak: still_launch_rule)
 	if(sort)
 		prepare_blocks_kernel<true><<<nwg, 64, 0, ctx->s_compute>>>(ctx->g, pm, pbc_ptr, ctx->part[cur].table, ctx->part[cur].keys, ctx->part[prev].table, pub, ctx->part[cur].count, still);
 	else
@@ -900,8 +964,12 @@ static int launch_rebuild(mpm_ctx* ctx, float fuse_dt = 0.f, bool without_prepar
 	}
 	int* st			  = ctx->d_status;
 	const int ebc_est = std::min(g.cap, ctx->ebc + ctx->ebc / 16 + 1024);
-	compact_blocks_kernel<<<std::max(1u, cdiv(ebc_est, 1024)), 1024, 0, s>>>(g, rm, Pr.keys, Pn.keys, Pn.table, st, still);
-	const unsigned rg8 = std::max(1u, std::min(4096u, cdiv((size_t) ebc_est * 8, 256))), rg32 = std::max(1u, std::min(8192u, cdiv((size_t) ebc_est * 32, 256)));
+	compact_blocks_kernel<<<std::max(1u, cdiv(ebc_est, 1024)), 1024, 0, s>>>(g, rm, Pr.keys, Pn.keys, Pn.table, st, still, ctx->stamp_row ? ctx->stamp_row + 2 : nullptr);
+	// (a rebuild that is not offered the still path - the host laid the data out anew, or another driver's - ends the streak whatever the last read-back said)
+	if(!still) ctx->streak_seen = 0;
+	ctx->thin = still_launch_rule(ctx->streak_seen, still != 0, ctx->pbc, ctx->still_launch);
+	unsigned rg8 = std::max(1u, std::min(4096u, cdiv((size_t) ebc_est * 8, 256))), rg32 = std::max(1u, std::min(8192u, cdiv((size_t) ebc_est * 32, 256)));
+	if(ctx->thin.reg > 0) rg8 = std::min(rg8, (unsigned) ctx->thin.reg), rg32 = std::min(rg32, (unsigned) ctx->thin.reg);
 	register_blocks_kernel<0, 1><<<rg8, 256, 0, s>>>(g, &st[ST_CNT_P], nullptr, &st[ST_CNT_N], &st[ST_PBC], Pn.table, Pn.keys, st, still);
 	if(fused) {
 		with_collider(ctx, fuse_dt, [&](const auto& col) {
@@ -1023,6 +1091,7 @@ static int apply_status(mpm_ctx* ctx, mpm_counts* counts) {
 	ctx->nbc = ctx->h_status[ST_NBC];
 	ctx->ebc = ctx->h_status[ST_EBC];
 	ctx->pbc_prev = ctx->h_status[ST_PBCPREV];
+	ctx->streak_seen = ctx->h_status[ST_STREAK];
 	if(ctx->ebc > ctx->g.cap) return fail(ctx, MPM_ERR_CAPACITY, "Too much exterior blocks: " + std::to_string(ctx->ebc));
 	for(size_t mi = 0; mi < ctx->models.size(); ++mi) {
 		Model& m	   = ctx->models[mi];
@@ -1114,19 +1183,45 @@ int mpm_run_fixed(mpm_ctx* ctx, int nsteps, float dt) {
 	}
 	double acc_grid = 0, acc_g2p2g = 0, acc_part = 0, acc_total = 0;
 	int in_window = 0;
+	// Where a substep's four times come from.  STAMPS (the default): the kernels that open its phases write the wall clock into the substep's row of the ring behind
+	// the status block (mpm_kernels.hpp: phase_stamp) - substep_clear_kernel, its first launch, the start; G2P2G's first launch and compact_blocks_kernel the
+	// phase boundaries; its end is the next row's start, written by the next substep's clear or, behind the last substep of a window, by a one-thread launch -
+	// and the rows come back with the window's status read-back: nothing is put on the stream for the timers but that one launch per window.  EVENTS
+	// (MPM_PHASE_TIMERS=events: every substep; otherwise the substep that launches the stand-alone grid update - the first of a call - and a context without
+	// particle blocks, whose G2P2G launches nothing): three per substep - start, G2P2G start, G2P2G end -, its end is the next substep's start or an event
+	// of its own.  An event between two kernels is a barrier packet of its own, 5-6 us on the stream (profiles/r06_rank_alone_seq.txt).
+	struct StampGuard {// (no launch outside this loop stamps, whichever way the call ends)
+		mpm_ctx* ctx;
+		~StampGuard() { ctx->stamp_row = nullptr; }
+	} stamp_guard {ctx};
+	bool stamped[64] = {};// per substep of the window
+	bool open_row	 = false;// the previous substep of this window was stamped and nobody has written its end yet
+	auto close_row = [&]() {// the end of the window's substep in_window - 1 = the start of row in_window
+		if(open_row) phase_stamp_kernel<<<1, 1, 0, s>>>(ctx->d_stamps + (size_t) in_window * kStampRow);
+		open_row = false;
+	};
+	const double ms_per_tick = ctx->wall_clock_khz > 0 ? 1.0 / ctx->wall_clock_khz : 0.0;
 	for(int it = 0; it < nsteps; ++it) {
-		// three events per substep - start, G2P2G start, G2P2G end -; its end is the next substep's start (or the window's closing event): an event between two
-		// kernels is a barrier packet of its own, 5-6 us on the stream (profiles/r06_rank_alone_seq.txt), a tenth of a 0.2 ms substep when there were four
-		hipEvent_t* ev = &ctx->ev_ring[3 * in_window];
-		if(in_window == 0) HIP_TRY(hipEventRecord(ev[0], s));
+		const bool by_stamps = !ctx->phase_events && ctx->grid_preupdated && ctx->pbc > 0;
+		stamped[in_window]	 = by_stamps;
+		hipEvent_t* ev		 = &ctx->ev_ring[3 * in_window];
+		if(by_stamps)
+			ctx->stamp_row = ctx->d_stamps + (size_t) in_window * kStampRow;// (its clear writes the previous substep's end)
+		else {
+			ctx->stamp_row = nullptr;
+			close_row();
+			if(in_window == 0 || stamped[in_window - 1]) HIP_TRY(hipEventRecord(ev[0], s));
+		}
 		int rc = launch_grid_update(ctx, dt);
 		if(rc) return rc;
 		const bool fuse_next = it + 1 < nsteps;// the last substep leaves the canonical state behind
-		rc = launch_g2p2g(ctx, dt, dt, ev[1], ev[2], true, fuse_next);
+		rc = launch_g2p2g(ctx, dt, dt, by_stamps ? nullptr : ev[1], by_stamps ? nullptr : ev[2], true, fuse_next);
 		if(rc) return rc;
 		rc = launch_rebuild(ctx, fuse_next ? dt : 0.f, false, still_on);
 		if(rc) return rc;
-		HIP_TRY(hipEventRecord(ev[3], s));
+		ctx->stamp_row = nullptr;
+		if(!by_stamps) HIP_TRY(hipEventRecord(ev[3], s));
+		open_row = by_stamps;
 		roll_partition(ctx);
 		++in_window;
 		// Capacities grow only at a synchronisation (by 3/2 per look, at 3/4 fill): a context whose blocks fill more than 7/10 of the capacity
@@ -1135,17 +1230,25 @@ int mpm_run_fixed(mpm_ctx* ctx, int nsteps, float dt) {
 		const bool tight = ctx->cfg.grow && (long long) ctx->ebc * 10 > (long long) ctx->g.cap * 7 &&
 						   (size_t) ctx->g.cap < (size_t) ctx->g.G * ctx->g.G * ctx->g.G;// (a capacity that has reached the table size cannot grow: nothing to look for)
 		if(in_window == K || it + 1 == nsteps || tight) {
+			close_row();
 			HIP_TRY(hipGetLastError());
-			rc = sync_counts(ctx, nullptr);// (one read-back: status, halo counters, max |v|^2 slots)
+			rc = sync_counts(ctx, nullptr);// (one read-back: status, halo counters, max |v|^2 slots, phase stamps)
 			if(rc) return rc;
 			if(std::isinf(host_maxvel(ctx))) return fail(ctx, MPM_ERR_NONFINITE, "Maximum velocity is infinity");
 			for(int w = 0; w < in_window; ++w) {
-				hipEvent_t* e = &ctx->ev_ring[3 * w];
 				float t_grid = 0, t_g = 0, t_part = 0, t_tot = 0;
-				HIP_TRY(hipEventElapsedTime(&t_grid, e[0], e[1]));
-				HIP_TRY(hipEventElapsedTime(&t_g, e[1], e[2]));
-				HIP_TRY(hipEventElapsedTime(&t_part, e[2], e[3]));
-				HIP_TRY(hipEventElapsedTime(&t_tot, e[0], e[3]));
+				if(stamped[w]) {
+					const unsigned long long* r = ctx->h_stamps + (size_t) w * kStampRow;
+					const unsigned long long t0 = r[0], t1 = r[1], t2 = r[2], t3 = r[kStampRow];
+					auto ms = [&](unsigned long long a, unsigned long long b) { return b > a ? (float) ((double) (b - a) * ms_per_tick) : 0.f; };
+					t_grid = ms(t0, t1), t_g = ms(t1, t2), t_part = ms(t2, t3), t_tot = ms(t0, t3);
+				} else {
+					hipEvent_t* e = &ctx->ev_ring[3 * w];
+					HIP_TRY(hipEventElapsedTime(&t_grid, e[0], e[1]));
+					HIP_TRY(hipEventElapsedTime(&t_g, e[1], e[2]));
+					HIP_TRY(hipEventElapsedTime(&t_part, e[2], e[3]));
+					HIP_TRY(hipEventElapsedTime(&t_tot, e[0], e[3]));
+				}
 				acc_grid += t_grid;
 				acc_g2p2g += t_g;
 				acc_part += t_part;
@@ -1155,7 +1258,7 @@ int mpm_run_fixed(mpm_ctx* ctx, int nsteps, float dt) {
 			in_window = 0;
 		}
 	}
-	if(nsteps > 0) {// per-substep averages over this call, HIP events on the compute stream
+	if(nsteps > 0) {// per-substep averages over this call, on the compute stream's own time (phase stamps or HIP events, above)
 		ctx->timers.grid_update_ms = (float) (acc_grid / nsteps);
 		ctx->timers.g2p2g_ms	   = (float) (acc_g2p2g / nsteps);
 		ctx->timers.partition_ms   = (float) (acc_part / nsteps);
@@ -1188,6 +1291,14 @@ const char* mpm_build_info(void) {
 int mpm_last_g2p2g_ms(mpm_ctx* ctx, float* ms) {
 	if(!ctx || !ms) return MPM_ERR_INVALID;
 	*ms = ctx->last_g2p2g_ms;
+	return MPM_OK;
+}
+
+int mpm_still_launch_sizes(const char* setting, int streak, int still_on, int particle_blocks, int* prepare_workgroups, int* register_workgroups) {
+	if(!prepare_workgroups || !register_workgroups) return MPM_ERR_INVALID;
+	const StillLaunch t	 = still_launch_rule(streak, still_on != 0, particle_blocks, still_launch_override(setting));
+	*prepare_workgroups	 = t.prepare;
+	*register_workgroups = t.reg;
 	return MPM_OK;
 }
 

@@ -438,6 +438,7 @@ struct StepConst {
 	StressScale ss;// {2 mu, lambda, 1} * volume * (-new_dt D^-1 dx): the stress arrives as its P2G term (mpm_device_math.hpp)
 	float jdiv, jvisc;// J-fluid: dx dt D^-1, dx D^-1 viscosity (stress_jfluid)
 	float refl_lim;// (1/3) / dts: an entry of A beyond it could make det(I + dt grad v) <= 0 (the reflection bit of b, mpm_device_math.hpp)
+	unsigned long long* stamp = nullptr;// phase_stamp (mpm_kernels.hpp): where this launch leaves the time G2P2G started at; null for every launch but the one mpm_run_fixed stamps
 };
 
 // packed stencil base in the node cube (x | y << 4 | z << 8), -1 = outside (contribution discarded, :877-885)
@@ -542,6 +543,7 @@ __global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? kG2P2GWavesFluid : kG2P2G
 	__shared__ float4 s_queue[kQueue ? 4 * kSerialQueue : 1];// payloads of the lanes that could not take the scatter chain (serial_push / serial_flush)
 
 	const int lane0 = threadIdx.x;
+	phase_stamp(sk.stamp);// (mpm_kernels.hpp; complete before the block loop: no scalar memory operation of it is outstanding at the loop's hand-placed LDS waits)
 	// Workgroups are dealt round-robin to the 8 XCDs (each with its own L2).  Consecutive block numbers are spatial
 	// neighbours (they share grid blocks: reads in the set-up, atomics in the write-back), so every XCD gets one contiguous
 	// eighth of the block range instead of every eighth block.

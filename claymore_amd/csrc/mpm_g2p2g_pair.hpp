@@ -132,6 +132,7 @@ __global__ __launch_bounds__(kG2P2GThreads, MAT == 0 ? kPairWavesFluid : kPairWa
 	__shared__ float4 s_queue[kQueue ? 4 * kSerialQueue : 1];
 
 	const int lane0 = threadIdx.x;
+	phase_stamp(sk.stamp);
 	const int total = nblocks_ptr ? min(*nblocks_ptr, cfg.cap) : nblocks;
 	const int xcd = (int) (blockIdx.x & 7u), nq = nblocks_ptr ? (int) (gridDim.x >> 3) : 0x40000000;
 	const int share = (total >> 3) + (xcd < (total & 7) ? 1 : 0);

@@ -67,6 +67,20 @@ __device__ __forceinline__ bool rebuild_is_still(int allow_still, const int* sta
 	return allow_still && status[ST_MOVED] == 0;
 }
 
+// PHASE STAMPS of mpm_run_fixed: the kernel that opens a phase of a substep - substep_clear_kernel the substep, G2P2G (its first model's launch) the transfer,
+// compact_blocks_kernel the rebuild - leaves the constant-rate wall clock (100 MHz counter; the host takes its rate from hipDeviceAttributeWallClockRate)
+// in that substep's row of a small ring the host reads back with the status block, instead of the stream carrying an event - a barrier packet of its own,
+// 5-6 us - in front of it.  `slot` is the address the host passed with this launch (null: this launch stamps nothing); the first workgroup's first lane
+// stores.  The clock read is a scalar-memory operation whose result the store waits for, inside this branch: none is outstanding behind it.
+constexpr int kStampRow = 4;// 64-bit stamps per row: substep start, G2P2G start, rebuild start, one spare (the substep's end is the next row's start)
+__device__ __forceinline__ void phase_stamp(unsigned long long* slot) {
+	if(slot && blockIdx.x == 0 && threadIdx.x == 0) *slot = wall_clock64();
+}
+// ... and the one-thread launch that closes a window: the end of its last substep
+__global__ void phase_stamp_kernel(unsigned long long* slot) {
+	phase_stamp(slot);
+}
+
 struct GridCfg {
 	int G;		  // blocks per axis
 	int gbits;	  // log2(G)
@@ -878,8 +892,10 @@ struct ClearArgs {
 	int* old_table;		  // table of the partition about to be rebuilt
 	const int* old_keys;  // its key list
 	const int* old_count; // its exterior block count
+	unsigned long long* stamp;// (may be null) phase_stamp: the substep starts here
 };
 __global__ __launch_bounds__(256) void substep_clear_kernel(GridCfg cfg, ClearArgs a) {
+	phase_stamp(a.stamp);
 	const int tid = blockIdx.x * 256 + threadIdx.x, nthreads = gridDim.x * 256;
 	if(a.flags & kClearP2G) {
 		const int nbc = min(a.status[ST_NBC], cfg.cap), ebc = min(a.status[ST_EBC], cfg.cap);
@@ -914,7 +930,8 @@ __global__ __launch_bounds__(256) void substep_clear_kernel(GridCfg cfg, ClearAr
 // particles get a new number (workgroup-aggregated atomic), their key goes into the new table, their bins are
 // allocated.  Order of the new numbering is arbitrary (as it is in the reference: insert order of atomics).
 // The old exterior block count is read from the status block; the launch is sized by a host-side estimate of it.
-__global__ __launch_bounds__(1024) void compact_blocks_kernel(GridCfg cfg, RebuildModels rm, const int* __restrict__ old_keys, int* __restrict__ new_keys, int* __restrict__ new_table, int* __restrict__ status, int allow_still) {
+__global__ __launch_bounds__(1024) void compact_blocks_kernel(GridCfg cfg, RebuildModels rm, const int* __restrict__ old_keys, int* __restrict__ new_keys, int* __restrict__ new_table, int* __restrict__ status, int allow_still, unsigned long long* stamp) {
+	phase_stamp(stamp);// (may be null) the rebuild starts here
 	// The three counters of this kernel (new block numbers, bins, particle totals) share a cache line: same-line atomics
 	// serialise in L2 at ~11 ns each, so they are issued once per 1024-thread workgroup (3 x 95 at C3), not once per wave
 	// (3 x 1516 = 33 us, which was the kernel's whole run time).

@@ -587,8 +587,14 @@ int mpm_grid_isosurface(mpm_ctx* ctx, float iso_mass, const int lo[3], const int
  * experiment=none (claymore_amd/csrc/mpm_device_math.hpp: the switches that change what the kernels compute only exist under
  * -DMPM_EXPERIMENT); tests/test_abi.py asserts it for the shipped library.  Needs no device. */
 const char* mpm_build_info(void);
-/* G2P2G kernel time of the last call as measured with HIP events on the compute stream. */
+/* G2P2G kernel time of the last call on the compute stream's own clock (mpm_run_fixed: of the last substep, from the phase stamps its kernels
+ * write; MPM_PHASE_TIMERS=events in the environment at mpm_create keeps HIP events for every substep). */
 int mpm_last_g2p2g_ms(mpm_ctx* ctx, float* ms);
+/* The launch-size rule of the rebuild's three kernels that only look and leave on a still substep (mpm_run_fixed): workgroups of its prepare launch and
+ * of its two registration launches, 0 = the full size, given the still streak at the last read-back, whether the still path is on, the particle block
+ * count and the setting MPM_STILL_LAUNCH=auto|full|thin:N would give (null = unset = auto, which leaves the registrations at their full size; thin:N
+ * is for tests and A/B).  Needs no device. */
+int mpm_still_launch_sizes(const char* setting, int streak, int still_on, int particle_blocks, int* prepare_workgroups, int* register_workgroups);
 
 /* ---- function-level entry points used by the parity tests (device versions of the per-particle math) ---- */
 /* What the constitutive models take from math::svd (Library/MnBase/Math/Matrix/svd.cuh:27-1123; they need U and the singular

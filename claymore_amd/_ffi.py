@@ -71,6 +71,14 @@ class MeshFill(C.Structure):
     _fields_ = [("margin", C.c_float), ("lo", C.c_int * 3), ("hi", C.c_int * 3), ("use_box", C.c_int), ("reserved", C.c_int * 8)]
 
 
+LOAD_ROWS = 6                          # MPM_LOAD_ROWS
+LOAD_ROW_NAMES = ("field", "slot0", "slot1", "slot2", "slot3", "walls")
+
+
+class LoadOptions(C.Structure):
+    _fields_ = [("has_pivot", C.c_int * LOAD_ROWS), ("pivot", C.c_float * 3 * LOAD_ROWS)]
+
+
 class Counts(C.Structure):
     _fields_ = [("particle_blocks", C.c_int), ("neighbor_blocks", C.c_int), ("exterior_blocks", C.c_int),
                 ("model_count", C.c_int), ("bins", C.c_int64 * 8), ("particles", C.c_int64 * 8)]
@@ -150,6 +158,10 @@ HIP_ONLY = {
     "grid_volume": (_i, [_vp, _P(C.c_int), _P(C.c_int), _i, _vp]),
     "grid_box_totals": (_i, [_vp, _P(C.c_int), _P(C.c_int), _P(C.c_double)]),
     "grid_isosurface": (_i, [_vp, _f, _P(C.c_int), _P(C.c_int), _vp, _vp, _P(_sz)]),
+    "collider_loads": (_i, [_vp, _f, _P(LoadOptions), _P(C.c_double * 8)]),
+    "collider_contacts": (_i, [_vp, _f, _vp, _vp, _P(_sz)]),
+    "load_gauge": (_i, [_vp, _i, _P(LoadOptions)]),
+    "load_gauge_read": (_i, [_vp, _P(C.c_double * 8), _P(C.c_double), _ip, _i]),
     "halo_dump": (_i, [_vp, _vp, _vp, _ip, _vp]),
     "dump_block_rows": (_i, [_vp, _i, _vp, _P(_sz)]),
     "set_collision_clock": (_i, [_vp, _i, _f]),

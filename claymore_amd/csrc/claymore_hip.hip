@@ -21,6 +21,7 @@
 #include "mpm_collision_mesh.hpp"
 #include "mpm_mesh_fill.hpp"
 #include "mpm_particle_ids.hpp"
+#include "mpm_collider_loads.hpp"
 
 using namespace mpm;
 
@@ -171,6 +172,12 @@ struct mpm_ctx {
 	// grid[0] holds the mass and momentum summed over the group's ranks on every node this rank's particles reach: set by a group call
 	// that completed (mpm_group.inc), cleared at the start of every group call and by every phase-level call (phase_call)
 	bool group_summed  = false;
+	// the load gauge (mpm_load_gauge; mpm_collider_loads.hpp): on, launch_grid_update adds every stand-alone update's loads to d_load_acc first and
+	// mpm_run_fixed keeps the update out of the carry-over.  Both arrays exist only while it is on.
+	bool load_gauge = false;
+	mpm_load_options load_opt {};
+	double* d_load_partials = nullptr;// kLoadGroups x [kLoadRows][kLoadSums]
+	double* d_load_acc		= nullptr;// kLoadAccDoubles
 	int group_refs	   = 0;// mpm_group handles on this context (grp_common_init / mpm_group_destroy): the single-context readouts refuse it
 	int* d_send_ids[32] = {nullptr};
 	int n_halo = 0, n_inner = 0;
@@ -342,6 +349,14 @@ static void with_collider(mpm_ctx* ctx, float dt, F&& launch) {
 	else
 		launch(a.col.field);
 }
+// The installed colliders at the clock's current time T as with_collider hands them out, without its side effect: the clock stays where it is.
+// What a readout of the coming grid update needs (mpm_collider_loads.hpp); the two launches that apply an update call with_collider itself.
+template<class F>
+static void with_collider_at_clock(mpm_ctx* ctx, F&& launch) {
+	const float T = ctx->collision.time;
+	with_collider(ctx, 0.f, launch);
+	ctx->collision.time = T;
+}
 
 extern "C" {
 
@@ -498,6 +513,8 @@ void mpm_destroy(mpm_ctx* ctx) {
 	hipFree(ctx->d_status);
 	hipFree(ctx->d_totals);
 	hipFree(ctx->d_counter);
+	hipFree(ctx->d_load_partials);
+	hipFree(ctx->d_load_acc);
 	hipFree(ctx->d_overlap);
 	hipFree(ctx->d_halo_list);
 	hipFree(ctx->d_inner_list);
@@ -727,9 +744,42 @@ int mpm_initial_setup(mpm_ctx* ctx) {
 	return MPM_OK;
 }
 
+// The pivots of the load rows: the collider's shift at T (collision_pose's own statement) unless the caller gave one; the walls' default is the origin.
+static LoadPivots load_pivots(const mpm_ctx* ctx, const mpm_load_options* opt) {
+	LoadPivots piv {};
+	const float T = ctx->collision.time;
+	for(int r = 0; r < kLoadRows; ++r) {
+		const CollisionObject* o = nullptr;// the row's collider, if one is installed
+		if(r == 0 && ctx->has_collision) o = &ctx->collision;
+		if(r >= 1 && r <= kMaxShapes && r - 1 < ctx->shape_count && ctx->shape[r - 1].shape.kind) o = &ctx->shape[r - 1].obj;
+		for(int d = 0; d < 3; ++d) {
+			if(opt && opt->has_pivot[r])
+				piv.p[r][d] = (double) opt->pivot[r][d];
+			else if(o)
+				piv.p[r][d] = (double) collision_pose(*o, T).shift[d];
+		}
+	}
+	return piv;
+}
+// collider_loads_kernel and its reduction on the compute stream: the totals of the update that dt would apply now into out (accumulate 0) or
+// added to out, with dt and the call count behind them (accumulate 1).  partials: kLoadGroups x [kLoadRows][kLoadSums] doubles.
+static int launch_collider_loads(mpm_ctx* ctx, float dt, const mpm_load_options* opt, double* partials, double* out, int accumulate) {
+	hipStream_t s		 = ctx->s_compute;
+	const LoadPivots piv = load_pivots(ctx, opt);
+	with_collider_at_clock(ctx, [&](const auto& col) {
+		collider_loads_kernel<<<kLoadGroups, 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, col, piv, partials);
+	});
+	collider_loads_reduce_kernel<<<1, kLoadReduceThreads, 0, s>>>(partials, kLoadGroups, out, accumulate, (double) dt);
+	HIP_TRY(hipGetLastError());
+	return MPM_OK;
+}
+
 // grid-update phase, gmpm_simulator.cuh:326-347
 static int launch_grid_update(mpm_ctx* ctx, float dt) {
 	hipStream_t s = ctx->s_compute;
+	// the load gauge reads the momenta this update is about to turn into velocities (a grid that holds none, or a grouped context's, is not read)
+	if(ctx->load_gauge && ctx->grid_momentum && !ctx->grid_preupdated && ctx->group_refs == 0 && ctx->mgsp_rank < 0 && !ctx->halo_tagged)
+		if(int rc = launch_collider_loads(ctx, dt, &ctx->load_opt, ctx->d_load_partials, ctx->d_load_acc, 1)) return rc;
 	ctx->grid_momentum = false;// (from here on grid[0] holds velocities, until a rebuild carries the next P2G over)
 	if(ctx->grid_preupdated) {
 		ctx->grid_preupdated = false;
@@ -1214,7 +1264,7 @@ int mpm_run_fixed(mpm_ctx* ctx, int nsteps, float dt) {
 		}
 		int rc = launch_grid_update(ctx, dt);
 		if(rc) return rc;
-		const bool fuse_next = it + 1 < nsteps;// the last substep leaves the canonical state behind
+		const bool fuse_next = it + 1 < nsteps && !ctx->load_gauge;// the last substep leaves the canonical state behind; the load gauge reads every update's momenta first
 		rc = launch_g2p2g(ctx, dt, dt, by_stamps ? nullptr : ev[1], by_stamps ? nullptr : ev[2], true, fuse_next);
 		if(rc) return rc;
 		rc = launch_rebuild(ctx, fuse_next ? dt : 0.f, false, still_on);
@@ -2397,8 +2447,110 @@ int mpm_grid_isosurface(mpm_ctx* ctx, float iso_mass, const int lo[3], const int
 	return MPM_OK;
 }
 
+// Collider loads (mpm_collider_loads.hpp): mpm_grid_volume's preconditions and dt > 0.  The one-shot calls stage in scratch released on every exit
+// path; the gauge owns its two arrays while it is on, so a context that never asks allocates and launches nothing for any of this.
+static int loads_state(mpm_ctx* ctx, float dt, const char* who) {
+	if(!(dt > 0.f)) return fail(ctx, MPM_ERR_INVALID, std::string(who) + ": dt must be > 0");
+	return readout_state(ctx, who);
+}
+int mpm_collider_loads(mpm_ctx* ctx, float dt, const mpm_load_options* opt, double out[MPM_LOAD_ROWS][8]) {
+	static_assert(MPM_LOAD_ROWS == kLoadRows && kLoadSums == 8, "the ABI's rows are the kernels'");
+	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
+	if(!out) return fail(ctx, MPM_ERR_INVALID, "mpm_collider_loads: NULL out");
+	if(int rc = loads_state(ctx, dt, "mpm_collider_loads")) return rc;
+	HIP_TRY(hipSetDevice(ctx->device));
+	hipStream_t s = ctx->s_compute;
+	DevScratch<double> d_part, d_out;
+	if(d_part.alloc((size_t) kLoadGroups * kLoadRows * kLoadSums) != hipSuccess || d_out.alloc(kLoadRows * kLoadSums) != hipSuccess) {
+		(void) hipGetLastError();
+		return fail(ctx, MPM_ERR_CAPACITY, "mpm_collider_loads: no device memory");
+	}
+	if(int rc = launch_collider_loads(ctx, dt, opt, d_part.p, d_out.p, 0)) return rc;
+	HIP_TRY(hipMemcpyAsync(&out[0][0], d_out.p, sizeof(double) * kLoadRows * kLoadSums, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	return MPM_OK;
+}
+
+int mpm_collider_contacts(mpm_ctx* ctx, float dt, int32_t* node_row4, float* rec8, size_t* n) {
+	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
+	if(!n) return fail(ctx, MPM_ERR_INVALID, "mpm_collider_contacts: NULL n");
+	if((node_row4 == nullptr) != (rec8 == nullptr)) return fail(ctx, MPM_ERR_INVALID, "mpm_collider_contacts: node_row4 and rec8 are given together or not at all");
+	if(int rc = loads_state(ctx, dt, "mpm_collider_contacts")) return rc;
+	const size_t cap = node_row4 ? *n : 0;
+	if(cap > SIZE_MAX / (8 * sizeof(float))) return fail(ctx, MPM_ERR_CAPACITY, "mpm_collider_contacts: no device memory for " + std::to_string(cap) + " records");
+	HIP_TRY(hipSetDevice(ctx->device));
+	hipStream_t s = ctx->s_compute;
+	DevScratch<int> d_nr;
+	DevScratch<float> d_rec;
+	if(cap && (d_nr.alloc(4 * cap) != hipSuccess || d_rec.alloc(8 * cap) != hipSuccess)) {
+		(void) hipGetLastError();// (the context stays usable; *n is left as it was)
+		return fail(ctx, MPM_ERR_CAPACITY, "mpm_collider_contacts: no device memory for " + std::to_string(cap) + " records");
+	}
+	HIP_TRY(hipMemsetAsync(ctx->d_counter, 0, sizeof(unsigned long long), s));
+	with_collider_at_clock(ctx, [&](const auto& col) {
+		collider_contacts_kernel<<<kLoadGroups, 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, col, (unsigned long long) cap, d_nr.p, d_rec.p, ctx->d_counter);
+	});
+	HIP_TRY(hipGetLastError());
+	unsigned long long count = 0;
+	HIP_TRY(hipMemcpyAsync(&count, ctx->d_counter, sizeof(count), hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	const size_t got = (size_t) std::min<unsigned long long>(count, cap);
+	if(got) {
+		HIP_TRY(hipMemcpy(node_row4, d_nr.p, sizeof(int32_t) * 4 * got, hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(rec8, d_rec.p, sizeof(float) * 8 * got, hipMemcpyDeviceToHost));
+	}
+	*n = (size_t) count;
+	if(node_row4 && count > cap) return fail(ctx, MPM_ERR_CAPACITY, "mpm_collider_contacts: there are " + std::to_string(count) + " records, the buffers hold " + std::to_string(cap));
+	return MPM_OK;
+}
+
+int mpm_load_gauge(mpm_ctx* ctx, int on, const mpm_load_options* opt) {
+	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
+	if(on && (ctx->group_refs > 0 || ctx->mgsp_rank >= 0 || ctx->halo_tagged)) return fail(ctx, MPM_ERR_INVALID, "mpm_load_gauge: the context belongs (or belonged) to a multi-GPU group; group-wide loads are not computed");
+	HIP_TRY(hipSetDevice(ctx->device));
+	if(!on) {
+		HIP_TRY(hipStreamSynchronize(ctx->s_compute));
+		hipFree(ctx->d_load_partials);
+		hipFree(ctx->d_load_acc);
+		ctx->d_load_partials = ctx->d_load_acc = nullptr;
+		ctx->load_gauge						   = false;
+		return MPM_OK;
+	}
+	if(!ctx->d_load_partials && dalloc(&ctx->d_load_partials, (size_t) kLoadGroups * kLoadRows * kLoadSums) != hipSuccess) {
+		(void) hipGetLastError();
+		return fail(ctx, MPM_ERR_CAPACITY, "mpm_load_gauge: no device memory");
+	}
+	if(!ctx->d_load_acc && dalloc(&ctx->d_load_acc, kLoadAccDoubles) != hipSuccess) {
+		(void) hipGetLastError();
+		return fail(ctx, MPM_ERR_CAPACITY, "mpm_load_gauge: no device memory");
+	}
+	HIP_TRY(hipMemsetAsync(ctx->d_load_acc, 0, sizeof(double) * kLoadAccDoubles, ctx->s_compute));
+	ctx->load_opt = opt ? *opt : mpm_load_options {};
+	ctx->load_gauge = true;
+	return MPM_OK;
+}
+
+int mpm_load_gauge_read(mpm_ctx* ctx, double out[MPM_LOAD_ROWS][8], double* elapsed, int* updates, int reset) {
+	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
+	if(!ctx->load_gauge) return fail(ctx, MPM_ERR_INVALID, "mpm_load_gauge_read: the gauge is off (mpm_load_gauge)");
+	HIP_TRY(hipSetDevice(ctx->device));
+	hipStream_t s = ctx->s_compute;
+	double acc[kLoadAccDoubles];
+	HIP_TRY(hipMemcpyAsync(acc, ctx->d_load_acc, sizeof(acc), hipMemcpyDeviceToHost, s));
+	if(reset) HIP_TRY(hipMemsetAsync(ctx->d_load_acc, 0, sizeof(acc), s));
+	HIP_TRY(hipStreamSynchronize(s));
+	if(out) memcpy(&out[0][0], acc, sizeof(double) * kLoadRows * kLoadSums);
+	if(elapsed) *elapsed = acc[kLoadRows * kLoadSums];
+	if(updates) {
+		long long count = 0;
+		memcpy(&count, &acc[kLoadRows * kLoadSums + 1], sizeof(count));
+		*updates = (int) std::min<long long>(count, INT32_MAX);
+	}
+	return MPM_OK;
+}
+
 // ---- function-level tests ---------------------------------------------------------------------------
-#define HIP_TRY0(expr)                       \
+#define HIP_TRY0(expr)                      \
 	do {                                       \
 		if((expr) != hipSuccess) return MPM_ERR_DEVICE; \
 	} while(0)

@@ -317,6 +317,7 @@ int mpm_checkpoint_load(mpm_ctx* ctx, const void* buf, size_t bytes) {
 	ctx->fuse_dt_once	 = 0.f;
 	ctx->rebuild_cleared = false;
 	ctx->grid_momentum	 = h.grid_velocity == 0;
+	if(ctx->load_gauge) HIP_TRY(hipMemsetAsync(ctx->d_load_acc, 0, sizeof(double) * kLoadAccDoubles, s));// (the gauge is no part of a checkpoint: it starts over)
 	ctx->rollid	   = h.rollid;
 	ctx->pbc	   = h.pbc;
 	ctx->nbc	   = h.nbc;

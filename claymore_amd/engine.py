@@ -640,6 +640,63 @@ class Engine:
             return (tris, vel) if velocity else tris
         return weld_triangles(tris, vel)
 
+    # ---- collider loads (mpm_collider_loads.hpp) ----
+    @staticmethod
+    def _load_options(pivots):
+        """pivots: None, or {row name or number: (x, y, z)} -> mpm_load_options or None."""
+        if not pivots:
+            return None
+        opt = _ffi.LoadOptions()
+        for key, p in pivots.items():
+            r = _ffi.LOAD_ROW_NAMES.index(key) if isinstance(key, str) else int(key)
+            if not 0 <= r < _ffi.LOAD_ROWS:
+                raise EngineError(_ffi.MPM_ERR_INVALID, f"collider loads: no row {key!r}")
+            opt.has_pivot[r] = 1
+            for d in range(3):
+                opt.pivot[r][d] = float(p[d])
+        return C.byref(opt)
+
+    @staticmethod
+    def _load_rows(out, seconds):
+        """[row][8] impulses -> {row name: {count, impulse, angular_impulse, force, torque, mass}}; force and torque are the impulses over `seconds`."""
+        a = np.ctypeslib.as_array(out).reshape(_ffi.LOAD_ROWS, 8).astype(np.float64)
+        with np.errstate(all="ignore"):
+            return {name: {"count": int(a[r, 0]) if np.isfinite(a[r, 0]) else a[r, 0], "impulse": a[r, 1:4].copy(), "angular_impulse": a[r, 4:7].copy(),
+                           "force": a[r, 1:4] / seconds, "torque": a[r, 4:7] / seconds, "mass": float(a[r, 7])} for r, name in enumerate(_ffi.LOAD_ROW_NAMES)}
+
+    def collider_loads(self, dt, pivots=None):
+        """What the next grid update with this dt will put on every collider (mpm_collider_loads; read-only, the grid must hold the last P2G's
+        momenta): {"field", "slot0" .. "slot3", "walls"} -> {count: touched nodes, impulse (3,), angular_impulse (3,) about the row's pivot,
+        force = impulse / dt, torque = angular_impulse / dt, mass: touched mass}, all float64, the loads ON the collider.  pivots: {row: (x, y, z)}
+        replaces a row's default pivot (the collider's trans + trans_vel T; the origin for the walls)."""
+        out = (C.c_double * 8 * _ffi.LOAD_ROWS)()
+        self._check(self.api.collider_loads(self.ctx, float(dt), self._load_options(pivots), out))
+        return self._load_rows(out, float(np.float32(dt)))
+
+    def collider_contacts(self, dt):
+        """The contact map behind collider_loads (mpm_collider_contacts): (nodes (n, 3) int32, rows (n,) int32, mass (n,) float32, dv (n, 3)
+        float32, v_after (n, 3) float32), one entry per touched (node, row), in no particular order."""
+        n = C.c_size_t(0)
+        self._check(self.api.collider_contacts(self.ctx, float(dt), None, None, C.byref(n)))               # count, then fetch
+        nr = np.empty((n.value, 4), dtype=np.int32)
+        rec = np.empty((n.value, 8), dtype=np.float32)
+        if n.value:
+            self._check(self.api.collider_contacts(self.ctx, float(dt), nr.ctypes.data_as(C.c_void_p), rec.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return nr[:, :3].copy(), nr[:, 3].copy(), rec[:, 0].copy(), rec[:, 1:4].copy(), rec[:, 4:7].copy()
+
+    def load_gauge(self, on=True, pivots=None):
+        """Switch the load gauge (mpm_load_gauge): on, every grid update of grid_update / substep / run_fixed adds its loads to accumulators on
+        the device first, and run_fixed applies every update in a kernel of its own (same results).  Switching it on zeroes the accumulators."""
+        self._check(self.api.load_gauge(self.ctx, 1 if on else 0, self._load_options(pivots)))
+
+    def read_load_gauge(self, reset=True):
+        """-> (rows, elapsed, updates): collider_loads' rows summed over the `updates` grid updates since the gauge was zeroed, force and torque
+        the impulses over `elapsed`, the float64 sum of their dts (nan before the first update)."""
+        out = (C.c_double * 8 * _ffi.LOAD_ROWS)()
+        elapsed, updates = C.c_double(0), C.c_int(0)
+        self._check(self.api.load_gauge_read(self.ctx, out, C.byref(elapsed), C.byref(updates), 1 if reset else 0))
+        return self._load_rows(out, elapsed.value), elapsed.value, updates.value
+
     def last_g2p2g_ms(self):
         ms = C.c_float(0)
         self._check(self.api.last_g2p2g_ms(self.ctx, C.byref(ms)))

@@ -18,6 +18,9 @@
 // the INT point attribute "id" - the particle's index among the model's sampled points - with the frame's points written in ascending id
 // order, so the point order is the same in every frame; the other attributes are joined to the ids on the position bits.  A top-level "colliders" array installs analytic collision shapes (parse_collider below).
 // A top-level "collision_mesh" object installs the level-set collision object from an OBJ file (mpm_set_collision_mesh; in main below).
+// simulation.output_loads (default false): the load gauge runs (mpm_load_gauge) and `loads_frame[f].json` beside each frame holds, per row (the
+// level-set object, the four slots, the domain walls), the force and torque on the collider averaged over the frame, the touched-node count and
+// the elapsed time (mpm_load_gauge_read at the frame's end).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -352,6 +355,7 @@ int main(int argc, char** argv) {
 	const bool out_vel		  = sim.has("output_velocity") && sim["output_velocity"].type == mj::Value::Bool && sim["output_velocity"].b;
 	const bool out_stress	  = sim.has("output_stress") && sim["output_stress"].type == mj::Value::Bool && sim["output_stress"].b;
 	const bool out_ids		  = sim.has("output_ids") && sim["output_ids"].type == mj::Value::Bool && sim["output_ids"].b;
+	const bool out_loads	  = sim.has("output_loads") && sim["output_loads"].type == mj::Value::Bool && sim["output_loads"].b;
 	int grid_stride			  = 0;// simulation.output_grid: 0 = no grid files
 	if(sim.has("output_grid")) {
 		const mj::Value& og = sim["output_grid"];
@@ -564,6 +568,30 @@ int main(int argc, char** argv) {
 		io.write_obj_surface_async(out_dir + "/surface_frame[" + std::to_string(frame) + "].obj", std::move(tris));
 	};
 	if(surface_iso > 0.f) write_surface(0);
+	// simulation.output_loads: the load gauge (mpm_load_gauge) runs over every frame; loads_frame[f].json holds, per row, the force and torque on the
+	// collider averaged over the frame's substeps, the touched-node count summed over them and the elapsed time, read and zeroed at the frame's end
+	if(out_loads && (rc = mpm_load_gauge(ctx, 1, nullptr))) die(ctx, rc);
+	auto write_loads = [&](int frame) {
+		double rows[MPM_LOAD_ROWS][8], elapsed = 0.0;
+		int updates = 0;
+		int rs		= mpm_load_gauge_read(ctx, rows, &elapsed, &updates, 1);
+		if(rs) die(ctx, rs);
+		static const char* names[MPM_LOAD_ROWS] = {"field", "slot0", "slot1", "slot2", "slot3", "walls"};
+		FILE* f = std::fopen((out_dir + "/loads_frame[" + std::to_string(frame) + "].json").c_str(), "w");
+		if(!f) {
+			std::fprintf(stderr, "gmpm: cannot write the loads of frame %d\n", frame);
+			std::exit(1);
+		}
+		std::fprintf(f, "{\"frame\": %d, \"elapsed\": %.17g, \"updates\": %d, \"rows\": {", frame, elapsed, updates);
+		for(int r = 0; r < MPM_LOAD_ROWS; ++r) {
+			const double* a = rows[r];
+			auto per = [&](double x) { return elapsed > 0.0 ? x / elapsed : 0.0; };
+			std::fprintf(f, "%s\n  \"%s\": {\"count\": %.17g, \"mass\": %.17g, \"impulse\": [%.17g, %.17g, %.17g], \"angular_impulse\": [%.17g, %.17g, %.17g], \"force\": [%.17g, %.17g, %.17g], \"torque\": [%.17g, %.17g, %.17g]}", r ? "," : "",
+						 names[r], a[0], a[7], a[1], a[2], a[3], a[4], a[5], a[6], per(a[1]), per(a[2]), per(a[3]), per(a[4]), per(a[5]), per(a[6]));
+		}
+		std::fprintf(f, "\n}}\n");
+		std::fclose(f);
+	};
 	const auto wall0 = std::chrono::steady_clock::now();
 	for(int frame = 1; frame <= frames; ++frame) {
 		for(float t = 0.f; t < spf;) {
@@ -595,6 +623,7 @@ int main(int argc, char** argv) {
 			io.write_npy_f32_async(out_dir + "/grid_frame[" + std::to_string(frame) + "].npy", std::move(vol), {4, (size_t) cells, (size_t) cells, (size_t) cells});
 		}
 		if(surface_iso > 0.f) write_surface(frame);
+		if(out_loads) write_loads(frame);
 		for(size_t mi = 0; mi < counts.size(); ++mi) {// output_model, :594-634
 			buf.resize(3 * counts[mi]);
 			vbuf.clear();

@@ -583,6 +583,36 @@ int mpm_grid_box_totals(mpm_ctx* ctx, const int lo[3], const int hi[3], double o
  * grid that holds velocities and, permanently, for a context that has ever joined an mpm_group or been through the halo tagging.  Reads
  * only: no state, checkpoint or later substep changes.  HIP library only. */
 int mpm_grid_isosurface(mpm_ctx* ctx, float iso_mass, const int lo[3], const int hi[3], float* tri_xyz, float* tri_vel, size_t* n);
+/* Collider loads (an extension, the reference has none): what the NEXT grid update with this dt will do to every massed
+ * node, collider by collider - read off grid[0] while it holds the mass and momentum of the last P2G, with the colliders as installed and their
+ * poses at the clock's current time.  Nothing is written: not the grid, not the clock.
+ * Rows: 0 the level-set object, 1 .. 4 the slots 0 .. 3, 5 the domain walls (gravity belongs to no row).  Per node and row, in the grid update's
+ *   own float32 statements: dv = v_after - v_before (the wall row: 0 - p / m on each axis a wall zeroes); the node is touched where a component of
+ *   dv is non-zero or NaN.  j = (double) m * (double) dv is the impulse on the material, -j the load on the collider, r x (-j) its torque with
+ *   r = (double) ((float) node * dx) - pivot.
+ * mpm_collider_loads: out[row] = {touched nodes, Jx, Jy, Jz, Lx, Ly, Lz, touched mass}, J = sum(-j), L = sum r x (-j); force and torque over the
+ *   step are J / dt and L / dt.  Pivots: a row's default is its collider's shift at the clock's time (trans + trans_vel T), the wall row's the
+ *   origin; opt (may be NULL) replaces those whose has_pivot is non-zero.  float64 sums in a fixed order without atomics: the same state
+ *   gives the same bits on every call.  Non-finite grids get no special treatment.
+ * mpm_collider_contacts: one record per touched (node, row): node_row4 int32 {i, j, k, row}, rec8 float32 {m, dv[3], v_after[3], 0}, in no
+ *   particular order.  mpm_grid_isosurface's protocol: *n in: the capacity in records (node_row4 NULL: count only); out: the number there ARE;
+ *   a count above the capacity is MPM_ERR_CAPACITY with the true count.
+ * mpm_load_gauge: on != 0 zeroes the accumulators and from then on every stand-alone grid update (mpm_grid_update, mpm_substep, mpm_run_fixed,
+ *   which then no longer fuses the next update into the carry-over: same results, bit for bit) first adds its loads, its dt and 1 to them, on
+ *   the stream, without a host synchronisation; opt as above, kept and applied at every update (a default pivot follows its collider).  on == 0 releases it.  Off (the default) nothing is
+ *   allocated or launched.  Not part of a checkpoint: mpm_checkpoint_load zeroes the accumulators.
+ * mpm_load_gauge_read: the accumulated rows, the float64 sum of the dts and the number of updates (any pointer may be NULL); reset != 0 zeroes them.
+ * Errors: MPM_ERR_NOT_READY before mpm_initial_setup; MPM_ERR_INVALID for a NULL out / n, dt <= 0 or NaN, a grid that holds velocities, a context
+ *   that has ever joined an mpm_group or been through the halo tagging, mpm_load_gauge_read with the gauge off.  HIP library only. */
+#define MPM_LOAD_ROWS 6
+typedef struct mpm_load_options {
+	int has_pivot[MPM_LOAD_ROWS];
+	float pivot[MPM_LOAD_ROWS][3];
+} mpm_load_options;
+int mpm_collider_loads(mpm_ctx* ctx, float dt, const mpm_load_options* opt, double out[MPM_LOAD_ROWS][8]);
+int mpm_collider_contacts(mpm_ctx* ctx, float dt, int32_t* node_row4, float* rec8, size_t* n);
+int mpm_load_gauge(mpm_ctx* ctx, int on, const mpm_load_options* opt);
+int mpm_load_gauge_read(mpm_ctx* ctx, double out[MPM_LOAD_ROWS][8], double* elapsed, int* updates, int reset);
 /* How the library was built: "claymore_hip <abi> experiment=<none | list of -D switches>".  A product library reports
  * experiment=none (claymore_amd/csrc/mpm_device_math.hpp: the switches that change what the kernels compute only exist under
  * -DMPM_EXPERIMENT); tests/test_abi.py asserts it for the shipped library.  Needs no device. */

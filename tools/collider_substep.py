@@ -4,7 +4,7 @@ libraries in ONE process, interleaved (lib A, lib B, lib A, ...), so that a pare
 box under the same conditions.
 
     python tools/collider_substep.py [--scene c1|c2|c3] [--steps 200] [--warmup 50] [--reps 3] [--objects none,static,moving,shape,shapes4,ground_hf,ground_shape,ground_field,vol_mesh,vol_mesh4,field_mesh] [--phase 20]
-                                     [--out FILE] [lib.so ...]
+                                     [--loads] [--out FILE] [lib.so ...]
 
 Scene: C2 (one elastic sphere of ~5 M particles dropped at 256^3; the level-set field is 256^3 float4 = 256 MiB) or C3 (the sand column at
 512^3; the field is 2 GiB).  The object is a sphere below the material, far enough that nothing touches it during the measurement: the
@@ -20,7 +20,9 @@ grid-update time is the stand-alone kernel's (`phase_grid_ms`); in mpm_run_fixed
 spacing dx built on the device (mpm_set_collision_volume_mesh), four such bodies in the four slots, and the same body through mpm_set_collision_mesh (the level-set
 object: a float4 per node of the whole domain); `install_ms` is the wall-clock time of the installs.  `--scene c1`: C2's sphere at 128^3.
 `object_bytes`: device memory taken by installing the collider (hipMemGetInfo before and after).  Prints one JSON line per (rep, library, object) with the library's per-substep averages
-(HIP events on the compute stream) and the wall-clock time per substep, then a summary of medians."""
+(HIP events on the compute stream) and the wall-clock time per substep, then a summary of medians.  --loads: a library with mpm_load_gauge then switches the
+load gauge on and measures again - `loads_*`: mpm_run_fixed with every grid update a kernel of its own behind collider_loads_kernel and its reduction (no fused
+carry-over), and the phase-level grid update, whose time then holds the readout's two kernels as well: `loads_phase_grid_ms - phase_grid_ms` is their cost."""
 import argparse
 import ctypes as C
 import json
@@ -54,6 +56,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--objects", default="none,static,moving,shape,shapes4")
     ap.add_argument("--phase", type=int, default=20)
+    ap.add_argument("--loads", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     sc = scenes.sphere_drop() if a.scene == "c2" else scenes.sphere_drop(bits=7, radius_cells=26.5) if a.scene == "c1" else scenes.sand_column()
@@ -119,6 +122,23 @@ def main():
                 row = {"rep": rep, "lib": name, "build": api.build_info().decode(), "scene": a.scene, "object": obj, "steps": a.steps, "wall_ms": round(wall, 5),
                        "grid_ms": round(t.grid_update_ms, 5), "g2p2g_ms": round(t.g2p2g_ms, 5), "partition_ms": round(t.partition_ms, 5), "total_ms": round(t.total_ms, 5),
                        "phase_grid_ms": round(statistics.median(phase), 5) if phase else None, "object_bytes": int(object_bytes), "install_ms": round(install_ms, 3)}
+                if a.loads and hasattr(api, "load_gauge"):
+                    eng.load_gauge(True)
+                    eng.run_fixed(a.warmup, sc["dt"])
+                    t0 = time.perf_counter()
+                    eng.run_fixed(a.steps, sc["dt"])
+                    wall = (time.perf_counter() - t0) * 1e3 / a.steps
+                    t = eng.timers()
+                    phase = []
+                    for _ in range(a.phase):
+                        eng.grid_update(sc["dt"])
+                        phase.append(eng.timers().grid_update_ms)
+                        eng.g2p2g(sc["dt"], sc["dt"])
+                        eng.rebuild_partition()
+                    gauge_rows, _, updates = eng.read_load_gauge()
+                    row.update(loads_wall_ms=round(wall, 5), loads_grid_ms=round(t.grid_update_ms, 5), loads_g2p2g_ms=round(t.g2p2g_ms, 5), loads_partition_ms=round(t.partition_ms, 5),
+                               loads_total_ms=round(t.total_ms, 5), loads_phase_grid_ms=round(statistics.median(phase), 5) if phase else None, loads_updates=updates,
+                               loads_touched=sum(int(r["count"]) for r in gauge_rows.values()))
                 eng.close()
                 rows.append(row)
                 lines.append(json.dumps(row))
@@ -130,6 +150,8 @@ def main():
                 med = {k: round(statistics.median(r[k] for r in sel), 5) for k in ("wall_ms", "grid_ms", "g2p2g_ms", "partition_ms", "total_ms") + (("phase_grid_ms",) if a.phase else ())}
                 med.update(partition_lo=min(r["partition_ms"] for r in sel), partition_hi=max(r["partition_ms"] for r in sel), object_bytes=sel[0]["object_bytes"], install_ms=round(statistics.median(r["install_ms"] for r in sel), 3))
                 med.update(lo=min(r["wall_ms"] for r in sel), hi=max(r["wall_ms"] for r in sel))
+                if "loads_wall_ms" in sel[0]:
+                    med.update({k: round(statistics.median(r[k] for r in sel), 5) for k in ("loads_wall_ms", "loads_grid_ms", "loads_g2p2g_ms", "loads_partition_ms", "loads_total_ms") + (("loads_phase_grid_ms",) if a.phase else ())})
                 lines.append(json.dumps({"summary": name, "object": obj, "n": len(sel), **med}))
                 print(lines[-1], flush=True)
     if a.out:

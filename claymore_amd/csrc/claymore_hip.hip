@@ -68,9 +68,10 @@ struct Model {
 	int list_in		 = 0;// which list buffer g2p2g reads next
 };
 
-// workgroups of the rebuild's own prepare launch and of its two registration launches, 0 = the full size (still_launch_rule)
+// How one rebuild launches, as launch_rebuild resolves it for its kernels, the last one (launch_rebuild_prepare) included: the workgroups of its own
+// prepare launch and of its two registration launches, 0 = the full size (still_launch_rule); still: they may take the still path (mpm_kernels.hpp)
 struct StillLaunch {
-	int prepare = 0, reg = 0;
+	int prepare = 0, reg = 0, still = 0;
 };
 
 }// namespace
@@ -80,6 +81,24 @@ struct SubstepEvents {
 	hipEvent_t start = nullptr, g2p2g_start = nullptr, g2p2g_end = nullptr, end = nullptr;
 };
 
+// What the launches of ONE substep are offered.  The driver that enqueues the substep fills it once, every launch_* / mgsp_* / grp_* function below it
+// takes it by const reference: none of it lives on the context, so no call inherits another call's offer.  The public phase-level entries use the defaults.
+struct SubstepPlan {
+	float dt = 0.f, next_dt = 0.f;
+	SubstepEvents ev;// the events to record (single context: null G2P2G events are not recorded - a stamped substep)
+	float fuse_dt = 0.f;// > 0: the driver knows the next substep's dt - the rebuild's carry-over applies that grid update too (and this substep's clear resets the max |v|^2 slots for it)
+	bool offer_still = false;// the rebuild may take the still path (mpm_kernels.hpp) if G2P2G has moved nobody to another block: mpm_run_fixed on a single context alone
+	bool rebuild_clear = false;// the rebuild follows in the same substep and nobody looks at the old table in between: its clear rides on the G2P2G prologue
+	bool counts_pending = false;// the read-back of the last tagging's counts is outstanding (the deferred group loop): the halo launches size themselves from device memory
+	// the windowed group loop in its deferred order: a substep records three events on the compute stream instead of seven (an event between two kernels is a barrier packet
+	// of its own, 5-6 us: profiles/r06_rank_alone_seq.txt) - no start event (it is timed from the previous one's end), the end event doubles as the read-back's, one halo event
+	bool lean_events = false;
+	// mpm_run_fixed alone: the substep's row of the stamp ring, which launch_clear, the first model's G2P2G launch and the compaction pass on; null: timed with events
+	unsigned long long* stamp_row = nullptr;
+};
+// What a prepare_blocks_kernel launch is for (launch_prepare derives its buffers, its template argument and its options from this alone).
+enum class PrepareFor { Setup, CheckpointLoad, Rebuild };
+
 struct mpm_ctx {
 	mpm_config cfg {};
 	GridCfg g {};
@@ -88,11 +107,7 @@ struct mpm_ctx {
 	SubstepEvents ev;// (a group's windowed loop times its substeps with two sets of its own: mpm_group.inc)
 	hipEvent_t ev_comm = nullptr, ev_halo = nullptr;
 	hipEvent_t ev_tag0 = nullptr, ev_tag1 = nullptr;// group loop: key list exported (compute -> comm) / tagging complete (comm -> compute); created on first use
-	// lean_events (the windowed group loop in its deferred order): a substep records three events on the compute stream instead of seven - an event between two
-	// kernels is a barrier packet of its own, 5-6 us each (profiles/r06_rank_alone_seq.txt) -: no start event (a substep's time is end-to-end of the previous one's),
-	// the end event doubles as the read-back's, the halo event is recorded once.  ev_pending: the event the outstanding read-back completes with.
-	bool lean_events = false;
-	hipEvent_t ev_pending = nullptr;
+	hipEvent_t ev_pending = nullptr;// the event the outstanding read-back completes with (SubstepPlan::lean_events: the substep's own end event)
 	hipEvent_t ev_status = nullptr;
 	// grid[0] already holds the velocities of the coming substep (the rebuild's carry-over applied the grid update for this dt):
 	// only inside mpm_run_fixed, never when a call returns
@@ -101,26 +116,23 @@ struct mpm_ctx {
 	// reads; a grid update turns the momenta into velocities in place, and a fused carry-over leaves velocities too: false until the next plain rebuild
 	bool grid_momentum = false;
 	float preupdate_dt	 = 0.f;
-	float fuse_dt_once	 = 0.f;// set by a driver that knows the next substep's dt (mpm_group_run_fixed): consumed by the next rebuild
 	// Between two host synchronisations of mpm_run_fixed the block counts below are ESTIMATES (the values of the last
 	// synchronisation): launches are sized by them with a margin, every kernel reads the true counts from the status block.
 	// The data was (re-)laid on the host - initial set-up, a checkpoint load, a capacity growth - since the last rebuild: that rebuild is not offered
 	// the still path (mpm_kernels.hpp), whatever G2P2G says.  Cleared by every rebuild.
 	bool relaid = true;
-	int allow_still = 0;// what the rebuild in flight was offered: launch_rebuild sets it for its own kernels and for launch_rebuild_prepare
-	bool rebuild_cleared = false;// the rebuild's part of substep_clear_kernel has been issued together with the P2G part
+	// The rebuild's part of substep_clear_kernel has been issued together with the P2G part: the next rebuild's own clear skips it.  State of the device
+	// data, not of a call: it must survive between the public calls mpm_mgsp_begin and mpm_mgsp_rebuild_export, which the Python MGSP driver issues separately.
+	bool rebuild_cleared = false;
 	// mpm_run_fixed's phase times come from stamps the kernels write (mpm_kernels.hpp: phase_stamp) unless MPM_PHASE_TIMERS=events asks for the HIP events of
-	// old on every substep (read once, at creation: the A/B reference and the tests' comparison).  stamp_row: the row of the substep being enqueued - what
-	// launch_clear, the first model's G2P2G launch and the compaction pass on - or null: this substep is timed with events.
+	// old on every substep (read once, at creation: the A/B reference and the tests' comparison).
 	bool phase_events = false;
 	int wall_clock_khz = 0;
 	unsigned long long* d_stamps = nullptr;// kStampRows rows of kStampRow, behind the max |v|^2 slots of the status block
 	const unsigned long long* h_stamps = nullptr;
-	unsigned long long* stamp_row = nullptr;
 	// MPM_STILL_LAUNCH (read at creation; still_launch_rule): -1 auto, 0 full, N > 0 always thin with N workgroups.  streak_seen: ST_STREAK at the last read-back
 	int still_launch = -1;
 	int streak_seen	 = 0;
-	StillLaunch thin;// what the rebuild being enqueued launches with: launch_rebuild sets it for its own kernels and for launch_rebuild_prepare
 	std::vector<hipEvent_t> ev_ring;// 3 events per substep of a window (substep start, G2P2G start / end; its end is the next one's start) + the window's closing event
 	Partition part[2];
 	float* grid[2] = {nullptr, nullptr};
@@ -185,18 +197,18 @@ struct mpm_ctx {
 	std::string err;
 };
 
-// An interrupted call leaves no promise about the grid behind (a checkpoint load restores a canonical one): the three flags that span
-// kernels - grid already updated for the next dt, rebuild clear already issued, next dt known - are reset on EVERY error exit (HIP_TRY
-// returns included), by scope.
+// The plan of a public phase-level entry, and what every driver starts from: the context's own events, nothing offered.
+static SubstepPlan default_plan(const mpm_ctx* ctx, float dt = 0.f, float next_dt = 0.f) {
+	return {dt, next_dt, ctx->ev};
+}
+
+// An interrupted call leaves no promise about the grid behind (a checkpoint load restores a canonical one): the two flags that span
+// kernels - grid already updated for the next dt, rebuild clear already issued - are reset on EVERY error exit (HIP_TRY returns included), by scope.
 struct FlagGuard {
 	mpm_ctx* ctx;
 	bool armed = true;
 	~FlagGuard() {
-		if(armed) {
-			ctx->grid_preupdated = false;
-			ctx->fuse_dt_once	 = 0.f;
-			ctx->rebuild_cleared = false;
-		}
+		if(armed) ctx->grid_preupdated = ctx->rebuild_cleared = false;
 	}
 };
 
@@ -235,7 +247,7 @@ static auto g2p2g_for(bool pair) {
 	return pair ? g2p2g_pair_kernel<M> : g2p2g_kernel<M>;
 }
 
-static int launch_prepare(mpm_ctx* ctx, int cur, int prev, bool list_is_out, int binoff_sel, const int* pbc_ptr, int nblocks_est, bool sort, bool publish);
+static int launch_prepare(mpm_ctx* ctx, PrepareFor why, const StillLaunch& thin = {});
 
 static int fail(mpm_ctx* ctx, int code, const std::string& msg) {
 	ctx->err = msg;
@@ -733,7 +745,7 @@ int mpm_initial_setup(mpm_ctx* ctx) {
 	for(auto& m: ctx->models)// (m.list[1] still holds the particle ids by block that bucket_particles_kernel wrote; every particle of the model is in a block: ST_LOST was checked above)
 		if(m.n && pbc) rasterize_blocks_kernel<<<pbc, 256, 0, s>>>(g, m.d_xyz, m.list[1], m.size, ctx->part[r].keys, ctx->part[r].table, ctx->grid[0], m.mc.mass, m.v0[0], m.v0[1], m.v0[2]);
 	// the first G2P2G: current == previous numbering (roll r), lists as filled above
-	rc = launch_prepare(ctx, r, n, false, r, &ctx->d_status[ST_PBC], ctx->pbc, true, false);
+	rc = launch_prepare(ctx, PrepareFor::Setup);
 	if(rc) return rc;
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipStreamSynchronize(s));
@@ -856,8 +868,9 @@ static inline int hint_blocks(const mpm_ctx* ctx, int n) {
 
 // nblocks_ptr != nullptr: the block count is read from device memory, `nblocks` is the host's estimate of it (launch size);
 // otherwise `nblocks` is exact (the halo / interior lists of the MGSP path, whose lengths the host has read back)
-static void launch_g2p2g_model(mpm_ctx* ctx, Model& m, const int* block_list, const int* nblocks_ptr, int nblocks, float dt, float next_dt, hipStream_t s, const int* only_flag = nullptr) {
+static void launch_g2p2g_model(mpm_ctx* ctx, const SubstepPlan& plan, Model& m, const int* block_list, const int* nblocks_ptr, int nblocks, hipStream_t s, const int* only_flag = nullptr) {
 	const int r = ctx->rollid;
+	const float dt = plan.dt, next_dt = plan.next_dt;
 	ModelView v = make_view(ctx, m);
 	const int* cur_keys	  = ctx->part[r].keys;
 	const GridCfg& g = ctx->g;
@@ -871,7 +884,7 @@ static void launch_g2p2g_model(mpm_ctx* ctx, Model& m, const int* block_list, co
 	sk.refl_lim = sk.dts > 0.f ? (1.f / 3.f) / sk.dts : 3.0e38f;
 	sk.jdiv		= g.dx * dt * g.d_inv;
 	sk.jvisc	= g.dx * g.d_inv * m.mc.viscosity;
-	sk.stamp	= ctx->stamp_row && &m == &ctx->models.front() ? ctx->stamp_row + 1 : nullptr;
+	sk.stamp	= plan.stamp_row && &m == &ctx->models.front() ? plan.stamp_row + 1 : nullptr;
 	const int nwg = nblocks_ptr ? hint_blocks(ctx, nblocks) : nblocks;
 	auto kernel = g2p2g_for<3>(m.pair);
 	switch(m.material) {
@@ -889,8 +902,8 @@ static void launch_g2p2g_model(mpm_ctx* ctx, Model& m, const int* block_list, co
 }
 
 // substep_clear_kernel: the P2G part precedes G2P2G (clear_grid + the bucket counters, gmpm_simulator.cuh:383,:389), the rebuild
-// part precedes the rebuild (reset_table + the counters, :436-446); with_rebuild issues both in one launch
-static int launch_clear(mpm_ctx* ctx, int flags) {
+// part precedes the rebuild (reset_table + the counters, :436-446); plan.rebuild_clear issues both in one launch
+static int launch_clear(mpm_ctx* ctx, const SubstepPlan& plan, int flags) {
 	if((flags & kClearRebuild) && !(flags & kClearP2G)) {// called by the rebuild itself
 		if(ctx->rebuild_cleared) flags &= ~(kClearRebuild | kClearMaxVel);// (already issued with this substep's P2G part)
 		ctx->rebuild_cleared = false;
@@ -907,26 +920,25 @@ static int launch_clear(mpm_ctx* ctx, int flags) {
 	a.old_table	   = Pn.table;
 	a.old_keys	   = Pn.keys;
 	a.old_count	   = Pn.count;
-	a.stamp		   = (flags & kClearP2G) ? ctx->stamp_row : nullptr;// (the substep's first launch)
+	a.stamp		   = (flags & kClearP2G) ? plan.stamp_row : nullptr;// (the substep's first launch)
 	substep_clear_kernel<<<1024, 256, 0, ctx->s_compute>>>(ctx->g, a);
 	return MPM_OK;
 }
-// with_rebuild: the rebuild's clear rides along (nobody looks at the old table before the rebuild); fused_update: that rebuild's
-// carry-over applies the next grid update, i.e. writes the max |v|^2 slots
-static int launch_g2p2g_prologue(mpm_ctx* ctx, bool with_rebuild = false, bool fused_update = false) {
-	int rc = launch_clear(ctx, with_rebuild ? (kClearP2G | kClearRebuild | (fused_update ? kClearMaxVel : 0)) : kClearP2G);
-	if(rc == MPM_OK && with_rebuild) ctx->rebuild_cleared = true;
+// (with plan.fuse_dt the rebuild's carry-over applies the next grid update, i.e. writes the max |v|^2 slots: the clear that rides along resets them)
+static int launch_g2p2g_prologue(mpm_ctx* ctx, const SubstepPlan& plan) {
+	int rc = launch_clear(ctx, plan, plan.rebuild_clear ? (kClearP2G | kClearRebuild | (plan.fuse_dt > 0.f ? kClearMaxVel : 0)) : kClearP2G);
+	if(rc == MPM_OK && plan.rebuild_clear) ctx->rebuild_cleared = true;
 	return rc;
 }
 
-static int launch_g2p2g(mpm_ctx* ctx, float dt, float next_dt, hipEvent_t e0, hipEvent_t e1, bool with_rebuild_clear = false, bool fused_update = false) {
+static int launch_g2p2g(mpm_ctx* ctx, const SubstepPlan& plan) {
 	hipStream_t s = ctx->s_compute;
-	int rc		  = launch_g2p2g_prologue(ctx, with_rebuild_clear, fused_update);
+	int rc		  = launch_g2p2g_prologue(ctx, plan);
 	if(rc) return rc;
-	if(e0) HIP_TRY(hipEventRecord(e0, s));// (null events: a substep of mpm_run_fixed whose kernels stamp their phases)
+	if(plan.ev.g2p2g_start) HIP_TRY(hipEventRecord(plan.ev.g2p2g_start, s));// (null events: a substep of mpm_run_fixed whose kernels stamp their phases)
 	if(ctx->pbc)
-		for(auto& m: ctx->models) launch_g2p2g_model(ctx, m, nullptr, &ctx->d_status[ST_PBC], ctx->pbc, dt, next_dt, s);
-	if(e1) HIP_TRY(hipEventRecord(e1, s));
+		for(auto& m: ctx->models) launch_g2p2g_model(ctx, plan, m, nullptr, &ctx->d_status[ST_PBC], ctx->pbc, s);
+	if(plan.ev.g2p2g_end) HIP_TRY(hipEventRecord(plan.ev.g2p2g_end, s));
 	return MPM_OK;
 }
 
@@ -934,7 +946,7 @@ int mpm_g2p2g(mpm_ctx* ctx, float dt, float next_dt) {
 	phase_call(ctx);
 	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
 	HIP_TRY(hipSetDevice(ctx->device));
-	int rc = launch_g2p2g(ctx, dt, next_dt, ctx->ev.g2p2g_start, ctx->ev.g2p2g_end);
+	int rc = launch_g2p2g(ctx, default_plan(ctx, dt, next_dt));
 	if(rc) return rc;
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipStreamSynchronize(ctx->s_compute));
@@ -943,63 +955,59 @@ int mpm_g2p2g(mpm_ctx* ctx, float dt, float next_dt) {
 	return MPM_OK;
 }
 
-// Per-block preparation of the next G2P2G (prepare_blocks_kernel): `cur` is the numbering that G2P2G will run in, `prev`
-// the numbering the particle data is laid out in; `list_sel` / `binoff_sel` select the list and bin-offset buffers that
-// G2P2G will read (they differ before and after the roll).  nblocks_est: the host's estimate of the particle block count
-// *pbc_ptr (the launch size; the kernel walks over what is beyond it).  publish: the rebuild's last kernel publishes the
-// exterior block count.
-static int launch_prepare(mpm_ctx* ctx, int cur, int prev, bool list_is_out, int binoff_sel, const int* pbc_ptr, int nblocks_est, bool sort, bool publish) {
-	if(nblocks_est <= 0 && !publish) return MPM_OK;
+// Per-block preparation of the next G2P2G (prepare_blocks_kernel).  Set-up and a checkpoint load prepare the current numbering r, in which the
+// particle data is laid out too, from the lists G2P2G reads next (set-up sorts them, a checkpoint's are sorted).  The rebuild's last kernel prepares
+// the new numbering n with the data laid out in r: it sorts the lists the last G2P2G appended to (the only call that hands on `keep`), publishes the
+// exterior block count, may take the still path and follows the still streak (thin: what launch_rebuild resolved).  The launch is sized by the host's
+// estimate of the block count the kernel reads from the status block; the kernel walks over what is beyond it.
+static int launch_prepare(mpm_ctx* ctx, PrepareFor why, const StillLaunch& thin) {
+	const bool rebuild = why == PrepareFor::Rebuild;
+	const int r = ctx->rollid, cur = rebuild ? r ^ 1 : r, prev = cur ^ 1;
+	const int nblocks_est = rebuild ? std::min(ctx->g.cap, ctx->ebc + ctx->ebc / 16 + 1024) : ctx->pbc;
+	if(nblocks_est <= 0 && !rebuild) return MPM_OK;
 	PrepareModels pm {};
 	pm.n = (int) ctx->models.size();
 	for(int mi = 0; mi < pm.n; ++mi) {
 		Model& m		  = ctx->models[mi];
-		pm.list[mi]		  = m.list[list_is_out ? (m.list_in ^ 1) : m.list_in];
+		pm.list[mi]		  = m.list[rebuild ? (m.list_in ^ 1) : m.list_in];
 		pm.size[mi]		  = m.size;
 		pm.row_of[mi]	  = m.row_of;
-		pm.binoff_src[mi] = m.binoff[binoff_sel];
+		pm.binoff_src[mi] = m.binoff[cur];
 		pm.blockinfo[mi]  = m.blockinfo;
-		pm.keep[mi]		  = sort && list_is_out ? m.keep : nullptr;// (only the rebuild's call sorts lists G2P2G has just written)
+		pm.keep[mi]		  = rebuild ? m.keep : nullptr;
 		pm.pairinfo[mi]	  = m.pair ? m.pairinfo[0] : nullptr;
 		pm.pairhand[mi]	  = m.pairinfo[1];
 	}
-	int nwg		  = std::max(1, std::min(ctx->g.cap, nblocks_est + nblocks_est / 16 + 64));
-	int* pub	  = publish ? ctx->d_status : nullptr;
-	const int still = publish && sort && list_is_out ? ctx->allow_still : 0;// (the rebuild's own call only)
-	if(publish && sort && list_is_out && ctx->thin.prepare > 0) nwg = std::min(nwg, ctx->thin.prepare);// (... and it alone follows the still streak: still_launch_rule)
-	if(sort)
-		prepare_blocks_kernel<true><<<nwg, 64, 0, ctx->s_compute>>>(ctx->g, pm, pbc_ptr, ctx->part[cur].table, ctx->part[cur].keys, ctx->part[prev].table, pub, ctx->part[cur].count, still);
-	else
-		prepare_blocks_kernel<false><<<nwg, 64, 0, ctx->s_compute>>>(ctx->g, pm, pbc_ptr, ctx->part[cur].table, ctx->part[cur].keys, ctx->part[prev].table, pub, ctx->part[cur].count, still);
+	int nwg = std::max(1, std::min(ctx->g.cap, nblocks_est + nblocks_est / 16 + 64));
+	if(rebuild && thin.prepare > 0) nwg = std::min(nwg, thin.prepare);// (still_launch_rule)
+	const int* pbc_ptr = &ctx->d_status[rebuild ? ST_CNT_P : ST_PBC];
+	int* pub		   = rebuild ? ctx->d_status : nullptr;// (... and publishes the exterior block count)
+	auto kernel		   = why != PrepareFor::CheckpointLoad ? prepare_blocks_kernel<true> : prepare_blocks_kernel<false>;// (a checkpoint's lists are sorted)
+	kernel<<<nwg, 64, 0, ctx->s_compute>>>(ctx->g, pm, pbc_ptr, ctx->part[cur].table, ctx->part[cur].keys, ctx->part[prev].table, pub, ctx->part[cur].count, rebuild ? thin.still : 0);
 	return MPM_OK;
 }
 
 // partition rebuild, gmpm_simulator.cuh:415-579 (launches only: no host round trip, no runtime fill / copy commands; launch sizes
 // from the host's estimates of the block counts, true counts from the status block)
-// fuse_dt > 0: the carry-over applies the grid update of the next substep (dt = fuse_dt) as well
-// without_prepare: everything but the last kernel (prepare_blocks_kernel: list sort, look-up rows, publication of the exterior block count), which
-// launch_rebuild_prepare issues - the group loop puts the tagging's key export in between, so that the key all-gather and the tagging kernels
-// run on the comm stream beside it
-static int launch_rebuild_prepare(mpm_ctx* ctx) {
-	const int r = ctx->rollid, n = r ^ 1;
-	const int ebc_est = std::min(ctx->g.cap, ctx->ebc + ctx->ebc / 16 + 1024);
-	return launch_prepare(ctx, n, r, true, n, &ctx->d_status[ST_CNT_P], ebc_est, true, true);
+// (plan.fuse_dt, plan.offer_still: SubstepPlan; the still path is not taken when the data was laid out anew since the last rebuild)
+// tail != null: everything but the last kernel (prepare_blocks_kernel: list sort, look-up rows, publication of the exterior block count), which
+// launch_rebuild_prepare issues with *tail - the group loop puts the tagging's key export in between, so that the key all-gather and the tagging
+// kernels run on the comm stream beside it
+static int launch_rebuild_prepare(mpm_ctx* ctx, const StillLaunch& thin) {
+	return launch_prepare(ctx, PrepareFor::Rebuild, thin);
 }
-// allow_still: the kernels may take the still path (mpm_kernels.hpp) if G2P2G has moved nobody to another block - offered by mpm_run_fixed alone
-static int launch_rebuild(mpm_ctx* ctx, float fuse_dt = 0.f, bool without_prepare = false, bool allow_still = false) {
-	if(fuse_dt == 0.f) fuse_dt = ctx->fuse_dt_once;
-	ctx->fuse_dt_once = 0.f;
+static int launch_rebuild(mpm_ctx* ctx, const SubstepPlan& plan, StillLaunch* tail) {
+	const float fuse_dt = plan.fuse_dt;
 	hipStream_t s = ctx->s_compute;
 	GridCfg& g	  = ctx->g;
 	const int r = ctx->rollid, n = r ^ 1;
 	Partition& Pn = ctx->part[n];
 	Partition& Pr = ctx->part[r];
 	const bool fused = fuse_dt > 0.f;
-	const int still	 = allow_still && !ctx->relaid ? 1 : 0;
-	ctx->allow_still = still;
-	ctx->relaid		 = false;
+	const int still = plan.offer_still && !ctx->relaid ? 1 : 0;
+	ctx->relaid		= false;
 	ctx->grid_momentum = !fused;// the carry-over below writes grid[0]: the P2G's mass and momentum, or (fused) the updated velocities
-	int rc			 = launch_clear(ctx, kClearRebuild | (fused ? kClearMaxVel : 0));// un-insert the old keys of Pn (reset_table, hash_table.cuh:110-112), counters, totals
+	int rc			 = launch_clear(ctx, plan, kClearRebuild | (fused ? kClearMaxVel : 0));// un-insert the old keys of Pn (reset_table, hash_table.cuh:110-112), counters, totals
 	if(rc) return rc;
 	RebuildModels rm {};
 	rm.n = (int) ctx->models.size();
@@ -1014,12 +1022,13 @@ static int launch_rebuild(mpm_ctx* ctx, float fuse_dt = 0.f, bool without_prepar
 	}
 	int* st			  = ctx->d_status;
 	const int ebc_est = std::min(g.cap, ctx->ebc + ctx->ebc / 16 + 1024);
-	compact_blocks_kernel<<<std::max(1u, cdiv(ebc_est, 1024)), 1024, 0, s>>>(g, rm, Pr.keys, Pn.keys, Pn.table, st, still, ctx->stamp_row ? ctx->stamp_row + 2 : nullptr);
+	compact_blocks_kernel<<<std::max(1u, cdiv(ebc_est, 1024)), 1024, 0, s>>>(g, rm, Pr.keys, Pn.keys, Pn.table, st, still, plan.stamp_row ? plan.stamp_row + 2 : nullptr);
 	// (a rebuild that is not offered the still path - the host laid the data out anew, or another driver's - ends the streak whatever the last read-back said)
 	if(!still) ctx->streak_seen = 0;
-	ctx->thin = still_launch_rule(ctx->streak_seen, still != 0, ctx->pbc, ctx->still_launch);
+	StillLaunch thin = still_launch_rule(ctx->streak_seen, still != 0, ctx->pbc, ctx->still_launch);
+	thin.still		 = still;
 	unsigned rg8 = std::max(1u, std::min(4096u, cdiv((size_t) ebc_est * 8, 256))), rg32 = std::max(1u, std::min(8192u, cdiv((size_t) ebc_est * 32, 256)));
-	if(ctx->thin.reg > 0) rg8 = std::min(rg8, (unsigned) ctx->thin.reg), rg32 = std::min(rg32, (unsigned) ctx->thin.reg);
+	if(thin.reg > 0) rg8 = std::min(rg8, (unsigned) thin.reg), rg32 = std::min(rg32, (unsigned) thin.reg);
 	register_blocks_kernel<0, 1><<<rg8, 256, 0, s>>>(g, &st[ST_CNT_P], nullptr, &st[ST_CNT_N], &st[ST_PBC], Pn.table, Pn.keys, st, still);
 	if(fused) {
 		with_collider(ctx, fuse_dt, [&](const auto& col) {
@@ -1032,8 +1041,8 @@ static int launch_rebuild(mpm_ctx* ctx, float fuse_dt = 0.f, bool without_prepar
 	register_blocks_kernel<-1, 1><<<rg32, 256, 0, s>>>(g, &st[ST_CNT_P], &st[ST_CNT_N], &st[ST_CNT_E], &st[ST_NBC], Pn.table, Pn.keys, st, still);
 	// the next G2P2G runs in the new numbering n with the particle data laid out in r: sort its lists (the ones the last
 	// G2P2G appended to), look up its blocks' neighbours; this last kernel also publishes the exterior block count
-	if(without_prepare) return MPM_OK;
-	return launch_prepare(ctx, n, r, true, n, &st[ST_CNT_P], ebc_est, true, true);
+	if(tail) return *tail = thin, MPM_OK;
+	return launch_prepare(ctx, PrepareFor::Rebuild, thin);
 }
 
 // check_capacity() (gmpm_simulator.cuh:283-300): once the exterior block count / a model's bin count passes 3/4 of its
@@ -1158,32 +1167,32 @@ static int apply_status(mpm_ctx* ctx, mpm_counts* counts) {
 	if(counts) return mpm_get_counts(ctx, counts);
 	return MPM_OK;
 }
-static int finish_rebuild(mpm_ctx* ctx, mpm_counts* counts) {
+// a rebuild of its own with its host synchronisation, timed between ev.start and ev.end (mpm_rebuild_partition, the tail of mpm_substep)
+static int rebuild_and_sync(mpm_ctx* ctx, const SubstepPlan& plan, mpm_counts* counts) {
+	hipStream_t s = ctx->s_compute;
+	HIP_TRY(hipEventRecord(ctx->ev.start, s));
+	int rc = launch_rebuild(ctx, plan, nullptr);
+	if(rc) return rc;
+	HIP_TRY(hipEventRecord(ctx->ev.end, s));
+	HIP_TRY(hipGetLastError());
 	roll_partition(ctx);
-	return sync_counts(ctx, counts);
+	rc = sync_counts(ctx, counts);
+	if(rc) return rc;
+	HIP_TRY(hipEventElapsedTime(&ctx->timers.partition_ms, ctx->ev.start, ctx->ev.end));
+	return MPM_OK;
 }
 
 int mpm_rebuild_partition(mpm_ctx* ctx, mpm_counts* counts) {
 	phase_call(ctx);
 	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
 	HIP_TRY(hipSetDevice(ctx->device));
-	hipStream_t s = ctx->s_compute;
-	HIP_TRY(hipEventRecord(ctx->ev.start, s));
-	int rc = launch_rebuild(ctx);
-	if(rc) return rc;
-	HIP_TRY(hipEventRecord(ctx->ev.end, s));
-	HIP_TRY(hipGetLastError());
-	rc = finish_rebuild(ctx, counts);
-	if(rc) return rc;
-	HIP_TRY(hipEventElapsedTime(&ctx->timers.partition_ms, ctx->ev.start, ctx->ev.end));
-	return MPM_OK;
+	return rebuild_and_sync(ctx, default_plan(ctx), counts);
 }
 
 int mpm_substep(mpm_ctx* ctx, float dt, float step_time, float frame_time, float dt_default, float* next_dt, float* max_vel) {
 	phase_call(ctx);
 	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
 	FlagGuard guard {ctx};
-	ctx->fuse_dt_once = 0.f;// (this path keeps the grid update a kernel of its own: the rebuild below must not apply one)
 	float mv2 = 0.f;
 	int rc	  = mpm_grid_update(ctx, dt, &mv2);
 	if(rc) return rc;
@@ -1192,18 +1201,10 @@ int mpm_substep(mpm_ctx* ctx, float dt, float step_time, float frame_time, float
 	const float nd = mpm_compute_dt(ctx, mv, step_time, frame_time, dt_default);
 	if(max_vel) *max_vel = mv;
 	if(next_dt) *next_dt = nd;
-	rc = launch_g2p2g(ctx, dt, nd, ctx->ev.g2p2g_start, ctx->ev.g2p2g_end, true);
-	if(rc) return rc;
-	hipStream_t s = ctx->s_compute;
-	HIP_TRY(hipEventRecord(ctx->ev.start, s));
-	rc = launch_rebuild(ctx);
-	if(rc) return rc;
-	HIP_TRY(hipEventRecord(ctx->ev.end, s));
-	HIP_TRY(hipGetLastError());
-	rc = finish_rebuild(ctx, nullptr);
-	if(rc) return rc;
+	SubstepPlan plan   = default_plan(ctx, dt, nd);// (this path keeps the grid update a kernel of its own: no fuse_dt)
+	plan.rebuild_clear = true;
+	if((rc = launch_g2p2g(ctx, plan)) || (rc = rebuild_and_sync(ctx, plan, nullptr))) return rc;
 	HIP_TRY(hipEventElapsedTime(&ctx->last_g2p2g_ms, ctx->ev.g2p2g_start, ctx->ev.g2p2g_end));
-	HIP_TRY(hipEventElapsedTime(&ctx->timers.partition_ms, ctx->ev.start, ctx->ev.end));
 	ctx->timers.g2p2g_ms = ctx->last_g2p2g_ms;
 	ctx->timers.total_ms = ctx->timers.grid_update_ms + ctx->timers.g2p2g_ms + ctx->timers.partition_ms;
 	guard.armed = false;
@@ -1240,10 +1241,6 @@ int mpm_run_fixed(mpm_ctx* ctx, int nsteps, float dt) {
 	// (MPM_PHASE_TIMERS=events: every substep; otherwise the substep that launches the stand-alone grid update - the first of a call - and a context without
 	// particle blocks, whose G2P2G launches nothing): three per substep - start, G2P2G start, G2P2G end -, its end is the next substep's start or an event
 	// of its own.  An event between two kernels is a barrier packet of its own, 5-6 us on the stream (profiles/r06_rank_alone_seq.txt).
-	struct StampGuard {// (no launch outside this loop stamps, whichever way the call ends)
-		mpm_ctx* ctx;
-		~StampGuard() { ctx->stamp_row = nullptr; }
-	} stamp_guard {ctx};
 	bool stamped[64] = {};// per substep of the window
 	bool open_row	 = false;// the previous substep of this window was stamped and nobody has written its end yet
 	auto close_row = [&]() {// the end of the window's substep in_window - 1 = the start of row in_window
@@ -1255,21 +1252,18 @@ int mpm_run_fixed(mpm_ctx* ctx, int nsteps, float dt) {
 		const bool by_stamps = !ctx->phase_events && ctx->grid_preupdated && ctx->pbc > 0;
 		stamped[in_window]	 = by_stamps;
 		hipEvent_t* ev		 = &ctx->ev_ring[3 * in_window];
+		SubstepPlan plan {dt, dt};
+		plan.offer_still = still_on, plan.rebuild_clear = true;
+		if(it + 1 < nsteps && !ctx->load_gauge) plan.fuse_dt = dt;// the last substep leaves the canonical state behind; the load gauge reads every update's momenta first
 		if(by_stamps)
-			ctx->stamp_row = ctx->d_stamps + (size_t) in_window * kStampRow;// (its clear writes the previous substep's end)
+			plan.stamp_row = ctx->d_stamps + (size_t) in_window * kStampRow;// (its clear writes the previous substep's end)
 		else {
-			ctx->stamp_row = nullptr;
+			plan.ev.g2p2g_start = ev[1], plan.ev.g2p2g_end = ev[2];
 			close_row();
 			if(in_window == 0 || stamped[in_window - 1]) HIP_TRY(hipEventRecord(ev[0], s));
 		}
 		int rc = launch_grid_update(ctx, dt);
-		if(rc) return rc;
-		const bool fuse_next = it + 1 < nsteps && !ctx->load_gauge;// the last substep leaves the canonical state behind; the load gauge reads every update's momenta first
-		rc = launch_g2p2g(ctx, dt, dt, by_stamps ? nullptr : ev[1], by_stamps ? nullptr : ev[2], true, fuse_next);
-		if(rc) return rc;
-		rc = launch_rebuild(ctx, fuse_next ? dt : 0.f, false, still_on);
-		if(rc) return rc;
-		ctx->stamp_row = nullptr;
+		if(rc || (rc = launch_g2p2g(ctx, plan)) || (rc = launch_rebuild(ctx, plan, nullptr))) return rc;
 		if(!by_stamps) HIP_TRY(hipEventRecord(ev[3], s));
 		open_row = by_stamps;
 		roll_partition(ctx);

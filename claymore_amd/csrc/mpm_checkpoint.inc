@@ -314,7 +314,6 @@ int mpm_checkpoint_load(mpm_ctx* ctx, const void* buf, size_t bytes) {
 	}
 	// (a run that failed between two substeps may have left these set: the restored grid is the canonical one)
 	ctx->grid_preupdated = false;
-	ctx->fuse_dt_once	 = 0.f;
 	ctx->rebuild_cleared = false;
 	ctx->grid_momentum	 = h.grid_velocity == 0;
 	if(ctx->load_gauge) HIP_TRY(hipMemsetAsync(ctx->d_load_acc, 0, sizeof(double) * kLoadAccDoubles, s));// (the gauge is no part of a checkpoint: it starts over)
@@ -390,7 +389,7 @@ int mpm_checkpoint_load(mpm_ctx* ctx, const void* buf, size_t bytes) {
 	}
 	// the per-block look-up rows are derived data: rebuild them (the stored lists are already sorted)
 	{
-		int rc = launch_prepare(ctx, r, n, false, r, &ctx->d_status[ST_PBC], h.pbc, false, false);
+		int rc = launch_prepare(ctx, PrepareFor::CheckpointLoad);
 		if(rc) return rc;
 	}
 	HIP_TRY(hipGetLastError());

@@ -446,30 +446,31 @@ int grp_reduce(mpm_group* g, int gid) {
 int grp_send_recv(mpm_group* g) {
 	return g->world > 1 ? grp_exchange(g, g->d_send, g->d_recv, g->offs, g->ctx->s_comm) : MPM_OK;
 }
-// interior: the interior G2P2G of this substep is enqueued too (ev.g2p2g_end marks its end)
-int grp_exchange_halo(mpm_group* g, int gid, bool interior, float dt, float next_dt, const SubstepEvents& ev) {
+// interior: the interior G2P2G of this substep is enqueued too (plan.ev.g2p2g_end marks its end)
+int grp_exchange_halo(mpm_group* g, const SubstepPlan& plan, int gid, bool interior) {
 	mpm_ctx* ctx	 = g->ctx;
 	const bool early = g->early_exchange && interior;
 	int rc			 = grp_halo_capacity(g, grp_halo_offsets(g));
 	if(rc || (rc = grp_wait_peers_done(g))) return rc;
-	if(interior && !early) GRP_TRY(g2p2g_interior(ctx, dt, next_dt, ev));
+	if(interior && !early) GRP_TRY(g2p2g_interior(ctx, plan));
 	if((rc = grp_collect(g, gid, early ? ctx->s_compute : ctx->s_comm))) return rc;
 	if(early) {
 		GRP_HIP(hipEventRecord(ctx->ev_halo, ctx->s_compute));
 		GRP_HIP(hipStreamWaitEvent(ctx->s_comm, ctx->ev_halo, 0));
 	}
 	if((rc = grp_send_recv(g))) return rc;
-	if(early) GRP_TRY(g2p2g_interior(ctx, dt, next_dt, ev));
+	if(early) GRP_TRY(g2p2g_interior(ctx, plan));
 	return grp_reduce(g, gid);
 }
 // Compute half: the collect right behind the halo-first G2P2G, then the interior G2P2G, all on the compute stream - it can be enqueued
 // while the read-back of the previous substep's counts is still outstanding.
-int grp_halo_compute_half(mpm_group* g, int gid, float dt, float next_dt, bool counts_known, const SubstepEvents& ev) {
-	mpm_ctx* ctx = g->ctx;
-	int rc		 = counts_known ? grp_halo_capacity(g, grp_halo_offsets(g)) : MPM_OK;// (otherwise the buffer of the last exchange is used: the comm half checks it against the counts)
+int grp_halo_compute_half(mpm_group* g, const SubstepPlan& plan, int gid) {
+	mpm_ctx* ctx			= g->ctx;
+	const bool counts_known = !plan.counts_pending;
+	int rc					= counts_known ? grp_halo_capacity(g, grp_halo_offsets(g)) : MPM_OK;// (otherwise the buffer of the last exchange is used: the comm half checks it against the counts)
 	if(rc || (rc = grp_wait_peers_done(g)) || (rc = grp_collect(g, gid, ctx->s_compute, counts_known))) return rc;
 	GRP_HIP(hipEventRecord(ctx->ev_halo, ctx->s_compute));
-	GRP_TRY(g2p2g_interior(ctx, dt, next_dt, ev, counts_known));
+	GRP_TRY(g2p2g_interior(ctx, plan));
 	return MPM_OK;
 }
 // Comm half (needs the counts on the host): the grouped send / receive and the reduce on the comm stream, which waits for the collect's
@@ -657,7 +658,7 @@ int mpm_group_initial_setup(mpm_group* g) {
 	GRP_TRY(mpm_initial_setup(g->ctx));
 	int rc = grp_tag(g);
 	if(rc) return rc;
-	rc = grp_exchange_halo(g, 0, false, 0.f, 0.f, g->ctx->ev);
+	rc = grp_exchange_halo(g, default_plan(g->ctx), 0, false);
 	if(rc) return rc;
 	GRP_TRY(mpm_sync(g->ctx));
 	g->ctx->group_summed = true;
@@ -689,15 +690,14 @@ int mpm_group_resume(mpm_group* g) {
 // The enqueue half (everything up to the status read-back) and the wait half are separate: mpm_group_run_fixed puts the next
 // substep's grid update and halo-first G2P2G between them.
 namespace {
-// ev: the timing events this substep records (the windowed loop alternates two sets: a substep's events are read after the next
-// substep's first half has been enqueued).  device_sized: a status read-back is still outstanding, the halo-first launch takes its
-// block count from device memory.
-int grp_substep_begin(mpm_group* g, float dt, float next_dt, bool device_sized, const SubstepEvents& ev) {
-	GRP_TRY(mgsp_begin(g->ctx, dt, next_dt, device_sized, ev));
+// plan.ev: the timing events this substep records (the windowed loop alternates two sets: a substep's events are read after the next
+// substep's first half has been enqueued).  plan.counts_pending: the halo-first launch takes its block count from device memory.
+int grp_substep_begin(mpm_group* g, const SubstepPlan& plan) {
+	GRP_TRY(mgsp_begin(g->ctx, plan));
 	return MPM_OK;
 }
 // everything of a substep behind the halo exchange: rebuild, key export, all-gather, tagging, the status read-back
-int grp_substep_tail(mpm_group* g, const SubstepEvents& ev) {
+int grp_substep_tail(mpm_group* g, const SubstepPlan& plan) {
 	mpm_ctx* ctx  = g->ctx;
 	const int pad = g->pad;
 	int rc		  = grp_key_buffers(g);
@@ -713,29 +713,30 @@ int grp_substep_tail(mpm_group* g, const SubstepEvents& ev) {
 		// one GPU cannot show: MPM_GROUP_OVERLAP_TAG=1 keeps the path for that experiment (the MGSP suite passes with it on).
 		for(hipEvent_t* e: {&ctx->ev_tag0, &ctx->ev_tag1})
 			if(!*e) GRP_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
-		GRP_TRY(mgsp_rebuild_export(ctx, g->d_keys_mine, pad, true));
+		StillLaunch rebuild_tail;
+		GRP_TRY(mgsp_rebuild_export(ctx, plan, g->d_keys_mine, pad, &rebuild_tail));
 		GRP_HIP(hipEventRecord(ctx->ev_tag0, ctx->s_compute));
 		GRP_HIP(hipStreamWaitEvent(ctx->s_comm, ctx->ev_tag0, 0));
-		GRP_TRY(launch_rebuild_prepare(ctx));
+		GRP_TRY(launch_rebuild_prepare(ctx, rebuild_tail));
 		rc = grp_all_gather(g, g->d_keys_mine, g->d_keys_all, 3 * (size_t) pad, ctx->s_comm);
 		if(rc) return rc;
-		GRP_TRY(mgsp_tag(ctx, g->d_keys_all, pad, g->world, g->rank, ev, ctx->s_comm));
+		GRP_TRY(mgsp_tag(ctx, plan, g->d_keys_all, pad, g->world, g->rank, ctx->s_comm));
 		GRP_HIP(hipEventRecord(ctx->ev_tag1, ctx->s_comm));
 		GRP_HIP(hipStreamWaitEvent(ctx->s_compute, ctx->ev_tag1, 0));
-		GRP_HIP(hipEventRecord(ev.end, ctx->s_compute));
+		GRP_HIP(hipEventRecord(plan.ev.end, ctx->s_compute));
 	} else {
-		GRP_TRY(mpm_mgsp_rebuild_export(ctx, g->d_keys_mine, pad));
+		GRP_TRY(mgsp_rebuild_export(ctx, plan, g->d_keys_mine, pad, nullptr));
 		rc = grp_all_gather(g, g->d_keys_mine, g->d_keys_all, 3 * (size_t) pad, ctx->s_compute);
 		if(rc) return rc;
-		GRP_TRY(mgsp_tag(ctx, g->d_keys_all, pad, g->world, g->rank, ev));
+		GRP_TRY(mgsp_tag(ctx, plan, g->d_keys_all, pad, g->world, g->rank));
 	}
-	GRP_TRY(mgsp_end_enqueue(ctx, ev));
+	GRP_TRY(mgsp_end_enqueue(ctx, plan));
 	g->pad_enqueued = pad;
 	return MPM_OK;
 }
-int grp_substep_enqueue(mpm_group* g, float dt, float next_dt, const SubstepEvents& ev) {
-	int rc = grp_exchange_halo(g, 1, true, dt, next_dt, ev);
-	return rc ? rc : grp_substep_tail(g, ev);
+int grp_substep_enqueue(mpm_group* g, const SubstepPlan& plan) {
+	int rc = grp_exchange_halo(g, plan, 1, true);
+	return rc ? rc : grp_substep_tail(g, plan);
 }
 // takes over the counts of the substep whose read-back is outstanding (timed from ev.start); truncated: a key list outgrew the padding it
 // was exported with
@@ -758,13 +759,13 @@ int grp_substep_wait(mpm_group* g, const SubstepEvents& ev, float* max_vel_sqr, 
 int mpm_group_substep(mpm_group* g, float dt, float next_dt, float* max_vel_sqr) {
 	if(!g || !g->ctx) return MPM_ERR_INVALID;
 	g->ctx->group_summed = false;
-	const SubstepEvents& ev = g->ctx->ev;
-	int rc					= grp_substep_begin(g, dt, next_dt, false, ev);
+	const SubstepPlan plan = mgsp_plan(g->ctx, dt, next_dt);
+	int rc				   = grp_substep_begin(g, plan);
 	if(rc) return rc;
-	rc = grp_substep_enqueue(g, dt, next_dt, ev);
+	rc = grp_substep_enqueue(g, plan);
 	if(rc) return rc;
 	bool truncated = false;
-	rc			   = grp_substep_wait(g, ev, max_vel_sqr, &truncated);
+	rc			   = grp_substep_wait(g, plan.ev, max_vel_sqr, &truncated);
 	if(rc) return rc;
 	if(truncated) {// a key list was truncated (same verdict on every rank): tag again with the larger padding
 		g->retags++;
@@ -786,17 +787,20 @@ int mpm_group_run_fixed(mpm_group* g, int nsteps, float dt) {
 	bool pending = false;// the read-back of the previous substep is outstanding
 	bool retagged = false;// the wait half had to repeat the last tagging (a key list outgrew its padding)
 	bool lean_prev_end = false;// (lean events) the previous substep of this run recorded its end event: the next one is timed from it
-	auto bail = [&](int rc) {// an interrupted run leaves no promise about the grid behind
-		ctx->fuse_dt_once = 0.f, ctx->grid_preupdated = false, ctx->rebuild_cleared = false;
+	// The deferred order needs the exchange in its RCCL ordering (collect on the compute stream in front of the interior launch); the
+	// in-process transport's default (interior first, host synchronisations inside the exchange) keeps one wait per substep.
+	const bool defer = !g->no_defer && g->early_exchange;
+	const bool lean	 = defer && !g->overlap_tag;// (the deferred order records the halo event itself; the overlapped tagging keeps its own end event)
+	auto bail = [&](int rc) {// an interrupted run leaves no promise about the grid behind (FlagGuard), and no read-back in flight
+		FlagGuard guard {ctx};
 		if(pending) hipEventSynchronize(ctx->ev_pending ? ctx->ev_pending : ctx->ev_status);
-		ctx->lean_events = false;
 		return rc;
 	};
 	auto finish = [&](int par, bool may_retag) {// the wait half of a substep
 		// (lean events: no start event - a substep is timed from the end of the one before it, the first of a run from its G2P2G start)
 		SubstepEvents ev = g->ev2[par];
-		if(ctx->lean_events) ev.start = lean_prev_end ? g->ev2[par ^ 1].end : ev.g2p2g_start;
-		lean_prev_end  = ctx->lean_events;
+		if(lean) ev.start = lean_prev_end ? g->ev2[par ^ 1].end : ev.g2p2g_start;
+		lean_prev_end  = lean;
 		float mv	   = 0.f;
 		bool truncated = false;
 		int rc		   = grp_substep_wait(g, ev, &mv, &truncated);
@@ -816,30 +820,26 @@ int mpm_group_run_fixed(mpm_group* g, int nsteps, float dt) {
 		}
 		return rc;
 	};
-	// The deferred order needs the exchange in its RCCL ordering (collect on the compute stream in front of the interior launch); the
-	// in-process transport's default (interior first, host synchronisations inside the exchange) keeps one wait per substep.
-	const bool defer = !g->no_defer && g->early_exchange;
-	ctx->lean_events = defer && !g->overlap_tag;// (the deferred order records the halo event itself; the overlapped tagging keeps its own end event)
 	for(int i = 0; i < nsteps; ++i) {
 		const int par = i & 1;
+		SubstepPlan plan {dt, dt, g->ev2[par]};
 		// the next substep's dt is known: its grid update rides on this substep's carry-over (carry_grid_kernel<true>, which writes the
 		// max |v|^2 slots: this substep's clear resets them); the last substep of the call leaves the canonical state behind
-		if(i + 1 < nsteps) ctx->fuse_dt_once = dt;
-		const SubstepEvents& ev = g->ev2[par];
-		int rc					= grp_substep_begin(g, dt, dt, pending, ev);// (its own grid update rode on the previous substep's carry-over)
+		if(i + 1 < nsteps) plan.fuse_dt = dt;
+		plan.rebuild_clear = true, plan.counts_pending = pending, plan.lean_events = lean;
+		int rc = grp_substep_begin(g, plan);// (its own grid update rode on the previous substep's carry-over)
 		if(rc) return bail(rc);
 		if(defer) {
-			if((rc = grp_halo_compute_half(g, 1, dt, dt, !pending, ev))) return bail(rc);
+			if((rc = grp_halo_compute_half(g, plan, 1))) return bail(rc);
 			retagged = false;
 			if(pending && (rc = finish(par ^ 1, false))) return bail(rc);// the GPU is busy with the interior launch while the host looks at the counts
-			if((rc = grp_halo_comm_half(g, 1, retagged)) || (rc = grp_substep_tail(g, ev))) return bail(rc);
+			if((rc = grp_halo_comm_half(g, 1, retagged)) || (rc = grp_substep_tail(g, plan))) return bail(rc);
 		} else {
-			if((rc = grp_substep_enqueue(g, dt, dt, ev))) return bail(rc);
+			if((rc = grp_substep_enqueue(g, plan))) return bail(rc);
 		}
 		pending = true;
 		if((!defer || i + 1 == nsteps) && (rc = finish(par, true))) return bail(rc);
 	}
-	ctx->lean_events  = false;
 	ctx->group_summed = true;// (the last carry-over is not fused: grid[0] holds the summed momentum)
 	return MPM_OK;
 }
@@ -887,7 +887,7 @@ int mpm_group_main_loop(mpm_group* g, int frames, int fps, float dt_default, voi
 			next_dt = mpm_group_compute_dt(g, std::sqrt(mv2), cur_time + dt, next_time, dt_default);
 			if(!(next_dt > 0.f)) next_dt = mpm_group_compute_dt(g, std::sqrt(mv2), 0.f, seconds_pf, dt_default);// first dt of the next frame
 			GRP_TRY(mpm_g2p2g_halo(ctx, dt, next_dt));
-			rc = grp_exchange_halo(g, 1, true, dt, next_dt, ctx->ev);
+			rc = grp_exchange_halo(g, default_plan(ctx, dt, next_dt), 1, true);
 			if(rc) return rc;
 			GRP_TRY(mpm_rebuild_partition(ctx, nullptr));
 			rc = grp_tag(g);

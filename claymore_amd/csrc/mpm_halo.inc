@@ -272,23 +272,19 @@ int mpm_halo_tag_end(mpm_ctx* ctx, int* halo_particle_blocks, int* send_counts) 
 	return MPM_OK;
 }
 
-// fused_clear: the caller runs the rebuild in the same substep without looking at the old table in between (mpm_mgsp_begin ...
-// mpm_mgsp_rebuild_export): the rebuild's part of the clear kernel rides on this launch
-// device_sized: the number of halo blocks is read from device memory (the host has not read the last tagging's counts back yet: the
-// windowed loop of mpm_group_run_fixed); ctx->n_halo is then an estimate that sizes the launch.  ev.g2p2g_start marks the start.
-static int g2p2g_halo(mpm_ctx* ctx, float dt, float next_dt, bool fused_clear, bool device_sized, const SubstepEvents& ev) {
+// plan.rebuild_clear: mpm_mgsp_begin ... mpm_mgsp_rebuild_export.  plan.counts_pending: the number of halo blocks is read from device memory,
+// ctx->n_halo is then an estimate that sizes the launch.  plan.ev.g2p2g_start marks the start.
+static int g2p2g_halo(mpm_ctx* ctx, const SubstepPlan& plan) {
 	if(!ctx || !ctx->ready || !ctx->halo_tagged) return MPM_ERR_NOT_READY;
 	FlagGuard guard {ctx};
 	HIP_TRY(hipSetDevice(ctx->device));
 	hipStream_t s = ctx->s_compute;
-	int rc		  = launch_g2p2g_prologue(ctx, fused_clear, fused_clear && ctx->fuse_dt_once > 0.f);
+	int rc		  = launch_g2p2g_prologue(ctx, plan);
 	if(rc) return rc;
-	HIP_TRY(hipEventRecord(ev.g2p2g_start, s));
-	if(device_sized) {
-		for(auto& m: ctx->models) launch_g2p2g_model(ctx, m, ctx->d_halo_list, &ctx->d_halo_counts[0], ctx->n_halo, dt, next_dt, s);
-	} else if(ctx->n_halo)
-		for(auto& m: ctx->models) launch_g2p2g_model(ctx, m, ctx->d_halo_list, nullptr, ctx->n_halo, dt, next_dt, s);
-	if(!ctx->lean_events) {// (lean: the group loop records the event itself, once, behind its collect kernels)
+	HIP_TRY(hipEventRecord(plan.ev.g2p2g_start, s));
+	if(plan.counts_pending || ctx->n_halo)
+		for(auto& m: ctx->models) launch_g2p2g_model(ctx, plan, m, ctx->d_halo_list, plan.counts_pending ? &ctx->d_halo_counts[0] : nullptr, ctx->n_halo, s);
+	if(!plan.lean_events) {// (lean: the group loop records the event itself, once, behind its collect kernels)
 		HIP_TRY(hipEventRecord(ctx->ev_halo, s));// the comm stream waits for this before collecting
 		HIP_TRY(hipStreamWaitEvent(ctx->s_comm, ctx->ev_halo, 0));
 	}
@@ -297,30 +293,30 @@ static int g2p2g_halo(mpm_ctx* ctx, float dt, float next_dt, bool fused_clear, b
 }
 int mpm_g2p2g_halo(mpm_ctx* ctx, float dt, float next_dt) {
 	phase_call(ctx);
-	return ctx ? g2p2g_halo(ctx, dt, next_dt, false, false, ctx->ev) : MPM_ERR_NOT_READY;
+	return ctx ? g2p2g_halo(ctx, default_plan(ctx, dt, next_dt)) : MPM_ERR_NOT_READY;
 }
 
-// counts_known: the host has seen the counts of the tagging this launch runs on.  In the windowed group loop it has not (the read-back of
-// the previous substep is still outstanding): n_inner is then one tagging old, and a rank whose interior block count has just left zero
+// plan.counts_pending: the host has not seen the counts of the tagging this launch runs on (the windowed group loop: the read-back of
+// the previous substep is still outstanding).  n_inner is then one tagging old, and a rank whose interior block count has just left zero
 // must not skip the launch - its interior blocks would be processed by neither pass and their particles would silently be gone.
-// ev.g2p2g_end marks the end.
-static int g2p2g_interior(mpm_ctx* ctx, float dt, float next_dt, const SubstepEvents& ev, bool counts_known = true) {
+// plan.ev.g2p2g_end marks the end.
+static int g2p2g_interior(mpm_ctx* ctx, const SubstepPlan& plan) {
 	if(!ctx || !ctx->ready || !ctx->halo_tagged) return MPM_ERR_NOT_READY;
 	HIP_TRY(hipSetDevice(ctx->device));
 	hipStream_t s = ctx->s_compute;
 #if defined(MPM_EXPERIMENT) && defined(MPM_HACK_STALE_INTERIOR)// test only: round 4's bug - the launch is skipped on a count that is one tagging old (tests/test_mgsp_gpu.py shows that the library's books catch it)
 	if(ctx->n_inner)
 #else
-	if(ctx->n_inner || !counts_known)// all particle blocks in their own order, the halo ones skipped by flag (the block count is read from the status block)
+	if(ctx->n_inner || plan.counts_pending)// all particle blocks in their own order, the halo ones skipped by flag (the block count is read from the status block)
 #endif
-		for(auto& m: ctx->models) launch_g2p2g_model(ctx, m, nullptr, &ctx->d_status[ST_PBC], ctx->pbc, dt, next_dt, s, ctx->d_inner_list);
-	HIP_TRY(hipEventRecord(ev.g2p2g_end, s));
+		for(auto& m: ctx->models) launch_g2p2g_model(ctx, plan, m, nullptr, &ctx->d_status[ST_PBC], ctx->pbc, s, ctx->d_inner_list);
+	HIP_TRY(hipEventRecord(plan.ev.g2p2g_end, s));
 	HIP_TRY(hipGetLastError());
 	return MPM_OK;
 }
 int mpm_g2p2g_interior(mpm_ctx* ctx, float dt, float next_dt) {
 	phase_call(ctx);
-	return ctx ? g2p2g_interior(ctx, dt, next_dt, ctx->ev) : MPM_ERR_NOT_READY;
+	return ctx ? g2p2g_interior(ctx, default_plan(ctx, dt, next_dt)) : MPM_ERR_NOT_READY;
 }
 
 // the blocks shared with peers [peer0, peer0 + npeers) from grid gid on stream s, sizes from device memory (halo_collect_kernel);
@@ -372,28 +368,33 @@ int mpm_halo_dump(mpm_ctx* ctx, int* overlap, int* halo_list, int* n_halo, int* 
 }
 
 // ---- fused substep (one host synchronisation) ----------------------------------------------------------------
-static int mgsp_begin(mpm_ctx* ctx, float dt, float next_dt, bool device_sized, const SubstepEvents& ev) {
+static int mgsp_begin(mpm_ctx* ctx, const SubstepPlan& plan) {
 	if(!ctx || !ctx->ready || !ctx->halo_tagged) return MPM_ERR_NOT_READY;
 	HIP_TRY(hipSetDevice(ctx->device));
-	if(!ctx->lean_events) HIP_TRY(hipEventRecord(ev.start, ctx->s_compute));
-	int rc = launch_grid_update(ctx, dt);
+	if(!plan.lean_events) HIP_TRY(hipEventRecord(plan.ev.start, ctx->s_compute));
+	int rc = launch_grid_update(ctx, plan.dt);
 	if(rc) return rc;
 	rc = halo_alloc(ctx);
 	if(rc) return rc;
-	return g2p2g_halo(ctx, dt, next_dt, true, device_sized, ev);
+	return g2p2g_halo(ctx, plan);
+}
+static SubstepPlan mgsp_plan(const mpm_ctx* ctx, float dt, float next_dt) {// a fused substep that knows nothing about the next one (mpm_mgsp_begin, mpm_group_substep)
+	SubstepPlan plan   = default_plan(ctx, dt, next_dt);
+	plan.rebuild_clear = true;
+	return plan;
 }
 int mpm_mgsp_begin(mpm_ctx* ctx, float dt, float next_dt) {
 	phase_call(ctx);
-	return ctx ? mgsp_begin(ctx, dt, next_dt, false, ctx->ev) : MPM_ERR_NOT_READY;
+	return ctx ? mgsp_begin(ctx, mgsp_plan(ctx, dt, next_dt)) : MPM_ERR_NOT_READY;
 }
 
-// without_prepare: the rebuild's last kernel is left to the caller (launch_rebuild_prepare), see mgsp_rebuild_export_early
-static int mgsp_rebuild_export(mpm_ctx* ctx, int* dev_keys, int pad_rows, bool without_prepare) {
+// tail != null: the rebuild's last kernel is left to the caller (launch_rebuild_prepare with *tail), see grp_substep_tail
+static int mgsp_rebuild_export(mpm_ctx* ctx, const SubstepPlan& plan, int* dev_keys, int pad_rows, StillLaunch* tail) {
 	if(!ctx || !ctx->ready || !dev_keys || pad_rows < 2) return MPM_ERR_INVALID;
 	HIP_TRY(hipSetDevice(ctx->device));
 	int rc = halo_alloc(ctx);
 	if(rc) return rc;
-	rc = launch_rebuild(ctx, 0.f, without_prepare);
+	rc = launch_rebuild(ctx, plan, tail);
 	if(rc) return rc;
 	// the partition just rebuilt (it becomes current at mpm_mgsp_end); the export also resets the overlap marks and halo counters for
 	// the tagging that follows, and puts this rank's status word into row 0
@@ -402,12 +403,12 @@ static int mgsp_rebuild_export(mpm_ctx* ctx, int* dev_keys, int pad_rows, bool w
 
 int mpm_mgsp_rebuild_export(mpm_ctx* ctx, int* dev_keys, int pad_rows) {
 	phase_call(ctx);
-	return mgsp_rebuild_export(ctx, dev_keys, pad_rows, false);
+	return mgsp_rebuild_export(ctx, SubstepPlan {}, dev_keys, pad_rows, nullptr);
 }
 
 // on: the stream the two tagging kernels run on (the compute stream, or - group loop - the comm stream beside the rebuild's last kernel);
-// ev.end is recorded there when the tagging runs on the compute stream (the caller records it otherwise)
-static int mgsp_tag(mpm_ctx* ctx, const int* dev_all_keys, int pad_rows, int world, int rank, const SubstepEvents& ev, hipStream_t on = nullptr) {
+// plan.ev.end is recorded there when the tagging runs on the compute stream (the caller records it otherwise)
+static int mgsp_tag(mpm_ctx* ctx, const SubstepPlan& plan, const int* dev_all_keys, int pad_rows, int world, int rank, hipStream_t on = nullptr) {
 	if(!ctx || !ctx->ready || !dev_all_keys || world < 1 || world > 32) return MPM_ERR_INVALID;
 	HIP_TRY(hipSetDevice(ctx->device));
 	int rc = halo_alloc(ctx);
@@ -417,26 +418,26 @@ static int mgsp_tag(mpm_ctx* ctx, const int* dev_all_keys, int pad_rows, int wor
 	rc = halo_tag(ctx, ctx->rollid ^ 1, dev_all_keys, pad_rows, world, rank, s);
 	if(rc) return rc;
 	// (counts, peer list lengths / status words and the max |v|^2 slots come back with the status block at mpm_mgsp_end)
-	if(!on && !ctx->lean_events) HIP_TRY(hipEventRecord(ev.end, s));// (lean: the read-back's event is the substep's end)
+	if(!on && !plan.lean_events) HIP_TRY(hipEventRecord(plan.ev.end, s));// (lean: the read-back's event is the substep's end)
 	ctx->mgsp_world = world;
 	ctx->mgsp_rank	= rank;
 	return MPM_OK;
 }
 int mpm_mgsp_tag(mpm_ctx* ctx, const int* dev_all_keys, int pad_rows, int world, int rank) {
 	phase_call(ctx);
-	return ctx ? mgsp_tag(ctx, dev_all_keys, pad_rows, world, rank, ctx->ev) : MPM_ERR_INVALID;
+	return ctx ? mgsp_tag(ctx, default_plan(ctx), dev_all_keys, pad_rows, world, rank) : MPM_ERR_INVALID;
 }
 
 // The end of a fused substep in two halves: mgsp_end_enqueue rolls the partitions (host bookkeeping) and enqueues the read-back of the
 // status block behind everything the substep has enqueued; mgsp_end_wait waits for it and takes the counts over.  mpm_mgsp_end does
 // both at once; the windowed loop of mpm_group_run_fixed enqueues the next substep's grid update and halo-first G2P2G in between.
-// lean_events: ev.end, the substep's timed end event, is recorded behind the read-back in place of ev_status
-static int mgsp_end_enqueue(mpm_ctx* ctx, const SubstepEvents& ev) {
+// plan.lean_events: plan.ev.end, the substep's timed end event, is recorded behind the read-back in place of ev_status
+static int mgsp_end_enqueue(mpm_ctx* ctx, const SubstepPlan& plan) {
 	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
 	HIP_TRY(hipSetDevice(ctx->device));
 	roll_partition(ctx);
 	HIP_TRY(hipMemcpyAsync(ctx->h_status, ctx->d_status, sizeof(int) * kStatusBlock, hipMemcpyDeviceToHost, ctx->s_compute));
-	ctx->ev_pending = ctx->lean_events ? ev.end : ctx->ev_status;
+	ctx->ev_pending = plan.lean_events ? plan.ev.end : ctx->ev_status;
 	HIP_TRY(hipEventRecord(ctx->ev_pending, ctx->s_compute));
 	return MPM_OK;
 }
@@ -486,7 +487,7 @@ static int mgsp_end_wait(mpm_ctx* ctx, int rank, int* send_counts, int* halo_par
 int mpm_mgsp_end(mpm_ctx* ctx, int* send_counts, int* halo_particle_blocks, int* max_peer_rows, float* max_vel_sqr) {
 	phase_call(ctx);
 	if(!ctx) return MPM_ERR_NOT_READY;
-	int rc = mgsp_end_enqueue(ctx, ctx->ev);
+	int rc = mgsp_end_enqueue(ctx, default_plan(ctx));
 	if(rc) return rc;
 	return mgsp_end_wait(ctx, ctx->mgsp_rank, send_counts, halo_particle_blocks, max_peer_rows, max_vel_sqr, ctx->ev);
 }

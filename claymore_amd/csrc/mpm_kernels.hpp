@@ -58,7 +58,7 @@ enum {
 	ST_STREAK = 44,// ... and how many of them in a row up to now: bumped by the still compaction, zeroed by the full one
 	ST_WORDS = 64
 };
-// The STILL PATH of the rebuild (compact / register / prepare; launch_rebuild offers it with allow_still, mpm_run_fixed on a single context only).
+// The STILL PATH of the rebuild (compact / register / prepare; launch_rebuild offers it where the substep's plan says offer_still: mpm_run_fixed on a single context only).
 // When no particle changed its block in the G2P2G just run, the particle blocks are those of the partition it ran in - and with them the neighbour
 // and exterior blocks, every block's size and bins and every look-up row.  The new partition is then the old one under the IDENTITY numbering:
 // keys and table entries are copied, the registration kernels return, and prepare derives its row from the one that stands.  Every kernel of the

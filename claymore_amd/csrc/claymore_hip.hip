@@ -22,6 +22,7 @@
 #include "mpm_mesh_fill.hpp"
 #include "mpm_particle_ids.hpp"
 #include "mpm_collider_loads.hpp"
+#include "mpm_storage.hpp"
 
 using namespace mpm;
 
@@ -36,10 +37,10 @@ constexpr int kStampRows   = 64 + 1;
 constexpr int kStatusBlock = kStatusCore + kStampRows * kStampRow * 2;
 static_assert(kStatusCore % 2 == 0, "the stamps are 8-byte values");
 
+// OWNERSHIP: every device array below is a DevBuf (mpm_storage.hpp), freed with the struct that holds it; the two rosters behind mpm_ctx
+// state the size of every array that follows the block or the bin capacity.
 struct Partition {
-	int* table = nullptr;
-	int* keys  = nullptr;
-	int* count = nullptr;
+	DevBuf<int> table, keys, count;
 };
 
 struct Model {
@@ -48,20 +49,20 @@ struct Model {
 	mpm_material_params p {};
 	MaterialConst mc {};
 	size_t n	 = 0;
-	float* d_xyz = nullptr;// initial particle array; also the staging buffer of retrieve
+	DevBuf<float> d_xyz;// initial particle array; also the staging buffer of retrieve
 	float v0[3]	 = {0, 0, 0};
-	float* bins[2]	 = {nullptr, nullptr};
-	int* ids[2]		 = {nullptr, nullptr};// tracked contexts only (mpm_track_particle_ids): one int32 per bin slot, rolled and regrown with bins[] (mpm_particle_ids.hpp)
-	size_t bin_cap	 = 0;
-	int* binoff[2]	 = {nullptr, nullptr};
-	int* list[2]	 = {nullptr, nullptr};
-	int* size		 = nullptr;
-	int* row_of		 = nullptr;
-	int* out_count	 = nullptr;
-	int* keep		 = nullptr;// per block of the numbering G2P2G ran in: its particle count if every particle stayed with an unchanged sort key, else -1
-	int* blockinfo	 = nullptr;// [block][kInfoRow], written by prepare_blocks_kernel
-	bool pair		 = false;  // the lists are in the pair layout (mpm_kernels.hpp) and G2P2G carries two particles per lane (mpm_g2p2g_pair.hpp)
-	int* pairinfo[2] = {nullptr, nullptr};// pair layout only, [block][kPairChunks]: [0] full pairs per chunk of a block's sorted list (written by the sort, read by G2P2G), [1] what G2P2G hands on to the next sort
+	DevBuf<float> bins[2];
+	DevBuf<int> ids[2];// tracked contexts only (mpm_track_particle_ids): one int32 per bin slot, rolled and regrown with bins[] (mpm_particle_ids.hpp)
+	size_t bin_cap = 0;
+	DevBuf<int> binoff[2];
+	DevBuf<int> list[2];
+	DevBuf<int> size;
+	DevBuf<int> row_of;
+	DevBuf<int> out_count;
+	DevBuf<int> keep;// per block of the numbering G2P2G ran in: its particle count if every particle stayed with an unchanged sort key, else -1
+	DevBuf<int> blockinfo;// [block][kInfoRow], written by prepare_blocks_kernel
+	bool pair = false;// the lists are in the pair layout (mpm_kernels.hpp) and G2P2G carries two particles per lane (mpm_g2p2g_pair.hpp)
+	DevBuf<int> pairinfo[2];// pair layout only, [block][kPairChunks]: [0] full pairs per chunk of a block's sorted list (written by the sort, read by G2P2G), [1] what G2P2G hands on to the next sort
 	int64_t bincount = 0;
 	int64_t bincount_src = 0;// bins in use in bins[rollid] (the source of the next g2p2g): the previous bincount
 	int64_t bucketed = 0;// particles currently in the advection lists (device-counted at each rebuild)
@@ -135,17 +136,17 @@ struct mpm_ctx {
 	int streak_seen	 = 0;
 	std::vector<hipEvent_t> ev_ring;// 3 events per substep of a window (substep start, G2P2G start / end; its end is the next one's start) + the window's closing event
 	Partition part[2];
-	float* grid[2] = {nullptr, nullptr};
+	DevBuf<float> grid[2];
 	int rollid	   = 0;
 	int pbc = 0, nbc = 0, ebc = 0;
 	int pbc_prev = 0;// particle blocks of the previous numbering (the one the particle data is laid out in)
 	std::vector<Model> models;
-	int* d_status		  = nullptr;// ST_WORDS ints
-	int* h_status		  = nullptr;// pinned
-	unsigned* d_maxvel	  = nullptr;
-	float* h_maxvel		  = nullptr;// pinned
-	double* d_totals	  = nullptr;
-	unsigned long long* d_counter = nullptr;
+	DevBuf<int> d_status;// kStatusBlock ints; the d_ / h_ pointers into it and into its pinned mirror (halo counts, peer rows, max |v|^2, stamps) are VIEWS, set once at set-up
+	PinnedBuf<int> h_status;
+	unsigned* d_maxvel = nullptr;
+	float* h_maxvel	   = nullptr;
+	DevBuf<double> d_totals;
+	DevBuf<unsigned long long> d_counter;
 	bool ready = false;
 	int capacity_events = 0;// number of capacity growths so far (check_capacity)
 	bool track_ids = false;// mpm_track_particle_ids: every model carries ids[2], moved beside every G2P2G launch
@@ -154,16 +155,17 @@ struct mpm_ctx {
 	bool has_collision = false;// level-set collision object of the MGSP grid update
 	CollisionObject collision {};// (collision.time is the clock: the time of the next grid update)
 	bool collision_running = false;// the clock advances by dt with every grid update (mpm_set_collision_clock)
-	float4* d_sdf = nullptr;
+	DevBuf<float4> d_sdf;
 	// analytic collision shapes (mpm_set_collision_shape): slot s is in use where shape[s].shape.kind != 0; they share the one clock above
 	ShapeSlot shape[kMaxShapes] {};
 	int shape_count = 0;// highest slot in use + 1
-	// heightfields (mpm_set_collision_heightfield): slot s holds one where shape[s].shape.kind == kShapeHeightfield; hf[s].table is owned
-	// by the context (freed on replace, on removal and in mpm_destroy).  hf_count > 0 selects the terrain kernels.
+	// heightfields (mpm_set_collision_heightfield): slot s holds one where shape[s].shape.kind == kShapeHeightfield; hf[s].table is a view of
+	// slot_table[s], which the context owns (a slot holds at most one of heightfield or volume).  hf_count > 0 selects the terrain kernels.
+	DevBuf<float4> slot_table[kMaxShapes];
 	Heightfield hf[kMaxShapes] {};
 	int hf_count = 0;// slots that hold a heightfield
 	// volumes (mpm_set_collision_volume, mpm_set_collision_volume_mesh): slot s holds one where shape[s].shape.kind == kShapeVolume; vol[s].table is
-	// owned by the context like a heightfield's; vol_desc[s] is the descriptor as installed (mpm_get_collision_volume).  vol_count > 0 selects
+	// a view of slot_table[s] like a heightfield's; vol_desc[s] is the descriptor as installed (mpm_get_collision_volume).  vol_count > 0 selects
 	// the volume kernels.
 	Volume vol[kMaxShapes] {};
 	mpm_collision_volume vol_desc[kMaxShapes] {};
@@ -171,9 +173,9 @@ struct mpm_ctx {
 	mpm_timers timers {};
 	float last_g2p2g_ms = 0.f;
 	// halo state (MGSP)
-	int* d_overlap	   = nullptr;// per neighbour block: bit mask of peers that also own it
-	int* d_halo_list   = nullptr;// particle blocks touching an overlap block
-	int* d_inner_list  = nullptr;// per particle block: 1 = interior (not touched by the halo-first pass)
+	DevBuf<int> d_overlap;// per neighbour block: bit mask of peers that also own it
+	DevBuf<int> d_halo_list;// particle blocks touching an overlap block
+	DevBuf<int> d_inner_list;// per particle block: 1 = interior (not touched by the halo-first pass)
 	int* d_halo_counts = nullptr;// [0]=halo blocks, [1]=interior blocks, [2+peer]=send count for peer
 	int* h_halo_counts = nullptr;// pinned mirror
 	int* d_peer_rows   = nullptr;// key-list lengths exported by every rank (fused substep); lives behind d_halo_counts
@@ -188,14 +190,64 @@ struct mpm_ctx {
 	// mpm_run_fixed keeps the update out of the carry-over.  Both arrays exist only while it is on.
 	bool load_gauge = false;
 	mpm_load_options load_opt {};
-	double* d_load_partials = nullptr;// kLoadGroups x [kLoadRows][kLoadSums]
-	double* d_load_acc		= nullptr;// kLoadAccDoubles
+	DevBuf<double> d_load_partials;// kLoadGroups x [kLoadRows][kLoadSums]
+	DevBuf<double> d_load_acc;// kLoadAccDoubles
 	int group_refs	   = 0;// mpm_group handles on this context (grp_common_init / mpm_group_destroy): the single-context readouts refuse it
-	int* d_send_ids[32] = {nullptr};
+	DevBuf<int> d_send_ids[32];
 	int n_halo = 0, n_inner = 0;
 	int send_count[32] = {0};
 	std::string err;
 };
+
+// THE TWO ROSTERS: every array whose size follows the block capacity - f(buf, elements per block, extra elements) - or a model's bin capacity -
+// f(buf, elements per bin) -, each size stated once.  Set-up, growth, a checkpoint load and the halo arrays' first use all size by them: a new
+// per-block array is one line here.  lazy: the halo arrays too, which halo_alloc / halo_send_lists allocate on first use (null until then).
+template<class F>
+static void for_block_arrays(mpm_ctx* ctx, bool lazy, F&& f) {
+	for(int i = 0; i < 2; ++i) f(ctx->part[i].keys, 3, 0), f(ctx->grid[i], 256, 0);
+	for(auto& m: ctx->models) {
+		for(int i = 0; i < 2; ++i) f(m.binoff[i], 1, 1), f(m.list[i], ctx->g.ppb, 0);
+		f(m.size, 1, 1), f(m.row_of, 1, 1), f(m.out_count, 1, 1), f(m.keep, 1, 1);
+		f(m.blockinfo, kInfoRow, 0);
+		if(m.pair)
+			for(int i = 0; i < 2; ++i) f(m.pairinfo[i], kPairChunks, kPairChunks);
+	}
+	if(!lazy) return;
+	f(ctx->d_overlap, 1, 1), f(ctx->d_halo_list, 1, 1), f(ctx->d_inner_list, 1, 1);
+	for(auto& ids: ctx->d_send_ids) f(ids, 1, 1);
+}
+template<class F>
+static void for_bin_arrays(mpm_ctx* ctx, Model& m, F&& f) {
+	for(int i = 0; i < 2; ++i) {
+		f(m.bins[i], m.nch * kBin);
+		if(ctx->track_ids) f(m.ids[i], kBin);
+	}
+}
+// Every block array (lazy: and every halo array that exists) to at least ncap blocks, every bin array of m to at least nb bins; an array that does
+// not exist yet is allocated.  A failure half-way leaves every array at least as large as it was.
+static hipError_t size_block_arrays(mpm_ctx* ctx, size_t ncap, bool lazy) {
+	hipError_t e = hipSuccess;
+	for_block_arrays(ctx, lazy, [&](auto& buf, size_t per, size_t extra) {
+		if(e == hipSuccess && (buf.p || !lazy)) e = buf.grow(ncap * per + extra, ctx->s_compute);
+	});
+	return e;
+}
+static hipError_t size_bin_arrays(mpm_ctx* ctx, Model& m, size_t nb) {
+	hipError_t e = hipSuccess;
+	for_bin_arrays(ctx, m, [&](auto& buf, size_t per) {
+		if(e == hipSuccess) e = buf.grow(nb * per, ctx->s_compute);
+	});
+	return e;
+}
+// A lazily allocated array of the block roster comes to life at the present capacity, with the size its roster line states.
+template<class B>
+static hipError_t alloc_block_array(mpm_ctx* ctx, B& want) {
+	hipError_t e = hipSuccess;
+	for_block_arrays(ctx, true, [&](auto& buf, size_t per, size_t extra) {
+		if((void*) &buf == (void*) &want) e = buf.alloc((size_t) ctx->g.cap * per + extra, ctx->s_compute);
+	});
+	return e;
+}
 
 // The plan of a public phase-level entry, and what every driver starts from: the context's own events, nothing offered.
 static SubstepPlan default_plan(const mpm_ctx* ctx, float dt = 0.f, float next_dt = 0.f) {
@@ -259,40 +311,6 @@ static int fail(mpm_ctx* ctx, int code, const std::string& msg) {
 // until the next group call that completes (mpm_group_retrieve_velocity).
 static inline void phase_call(mpm_ctx* ctx) {
 	if(ctx) ctx->group_summed = false;
-}
-
-template<typename T>
-static hipError_t dalloc(T** p, size_t n) {
-	return hipMalloc((void**) p, sizeof(T) * (n ? n : 1));
-}
-
-// Scratch device array that is released on every exit path of the function that owns it.
-template<typename T>
-struct DevScratch {
-	T* p = nullptr;
-	DevScratch() = default;
-	DevScratch(const DevScratch&) = delete;
-	DevScratch& operator=(const DevScratch&) = delete;
-	~DevScratch() {
-		if(p) hipFree(p);
-	}
-	hipError_t alloc(size_t n) { return dalloc(&p, n); }
-};
-
-// Replace *p (old_n elements) by a zero-initialised array of new_n elements holding the old contents.
-template<typename T>
-static hipError_t regrow(T** p, size_t old_n, size_t new_n, hipStream_t s) {
-	T* q		 = nullptr;
-	hipError_t e = hipMalloc((void**) &q, sizeof(T) * new_n);
-	if(e != hipSuccess) return e;
-	if((e = hipMemsetAsync(q, 0, sizeof(T) * new_n, s)) != hipSuccess || (*p && old_n && (e = hipMemcpyAsync(q, *p, sizeof(T) * old_n, hipMemcpyDeviceToDevice, s)) != hipSuccess)
-	   || (e = hipStreamSynchronize(s)) != hipSuccess) {
-		hipFree(q);// *p is untouched: the caller still owns a valid array of old_n elements
-		return e;
-	}
-	if(*p) hipFree(*p);
-	*p = q;
-	return hipSuccess;
 }
 
 static inline unsigned cdiv(size_t a, size_t b) {
@@ -498,40 +516,6 @@ void mpm_destroy(mpm_ctx* ctx) {
 	if(!ctx) return;
 	hipSetDevice(ctx->device);
 	hipDeviceSynchronize();
-	hipFree(ctx->d_sdf);
-	for(int i = 0; i < kMaxShapes; ++i) hipFree(const_cast<float4*>(ctx->hf[i].table)), hipFree(const_cast<float4*>(ctx->vol[i].table));
-	for(int i = 0; i < 2; ++i) {
-		hipFree(ctx->part[i].table);
-		hipFree(ctx->part[i].keys);
-		hipFree(ctx->part[i].count);
-		hipFree(ctx->grid[i]);
-	}
-	for(auto& m: ctx->models) {
-		hipFree(m.d_xyz);
-		hipFree(m.blockinfo);
-		hipFree(m.pairinfo[0]);
-		hipFree(m.pairinfo[1]);
-		for(int i = 0; i < 2; ++i) {
-			hipFree(m.bins[i]);
-			hipFree(m.ids[i]);
-			hipFree(m.binoff[i]);
-			hipFree(m.list[i]);
-		}
-		hipFree(m.size);
-		hipFree(m.row_of);
-		hipFree(m.out_count);
-		hipFree(m.keep);
-	}
-	hipFree(ctx->d_status);
-	hipFree(ctx->d_totals);
-	hipFree(ctx->d_counter);
-	hipFree(ctx->d_load_partials);
-	hipFree(ctx->d_load_acc);
-	hipFree(ctx->d_overlap);
-	hipFree(ctx->d_halo_list);
-	hipFree(ctx->d_inner_list);
-	for(auto& p: ctx->d_send_ids) hipFree(p);
-	if(ctx->h_status) hipHostFree(ctx->h_status);
 	for(hipEvent_t e: {ctx->ev.start, ctx->ev.g2p2g_start, ctx->ev.g2p2g_end, ctx->ev.end})
 		if(e) hipEventDestroy(e);
 	if(ctx->ev_comm) hipEventDestroy(ctx->ev_comm);
@@ -542,7 +526,7 @@ void mpm_destroy(mpm_ctx* ctx) {
 	for(hipEvent_t e: ctx->ev_ring) hipEventDestroy(e);
 	if(ctx->s_compute) hipStreamDestroy(ctx->s_compute);
 	if(ctx->s_comm) hipStreamDestroy(ctx->s_comm);
-	delete ctx;
+	delete ctx;// (every device array goes with its owner: mpm_storage.hpp)
 }
 
 const char* mpm_last_error(const mpm_ctx* ctx) {
@@ -564,13 +548,13 @@ int mpm_add_model(mpm_ctx* ctx, int material, const mpm_material_params* params,
 	m.nch	   = material == MPM_J_FLUID ? 4 : (material == MPM_FIXED_COROTATED ? 9 : 10);// floats per particle in a bin (mpm_g2p2g.hpp: {x, y, z, J}, or a 32-B record {x, y, z, b...} + a row of b21 (+ log Jp))
 	m.n		   = n;
 	for(int d = 0; d < 3; ++d) m.v0[d] = v0 ? v0[d] : 0.f;
-	HIP_TRY(dalloc(&m.d_xyz, 3 * n));
+	HIP_TRY(m.d_xyz.alloc(3 * n, ctx->s_compute));
 	if(n) {// an empty model is legal (an MGSP rank whose slab of a model is empty, an empty sampled SDF)
 		HIP_TRY(hipMemcpyAsync(m.d_xyz, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, ctx->s_compute));
 		HIP_TRY(hipStreamSynchronize(ctx->s_compute));
 	}
 	if(model_id) *model_id = (int) ctx->models.size();
-	ctx->models.push_back(m);
+	ctx->models.push_back(std::move(m));
 	return MPM_OK;
 }
 
@@ -608,9 +592,8 @@ int mpm_initial_setup(mpm_ctx* ctx) {
 	hipStream_t s	   = ctx->s_compute;
 	const size_t table = (size_t) g.G * g.G * g.G;
 	const int r = ctx->rollid, n = r ^ 1;
-	HIP_TRY(dalloc(&ctx->d_status, kStatusBlock));
-	HIP_TRY(hipHostMalloc((void**) &ctx->h_status, sizeof(int) * kStatusBlock));
-	memset(ctx->h_status, 0, sizeof(int) * kStatusBlock);
+	HIP_TRY(ctx->d_status.alloc(kStatusBlock, s));
+	HIP_TRY(ctx->h_status.alloc(kStatusBlock));
 	ctx->d_halo_counts = ctx->d_status + ST_WORDS;
 	ctx->h_halo_counts = ctx->h_status + ST_WORDS;
 	ctx->d_peer_rows   = ctx->d_halo_counts + 2 + 32;
@@ -619,14 +602,12 @@ int mpm_initial_setup(mpm_ctx* ctx) {
 	ctx->h_maxvel	   = reinterpret_cast<float*>(ctx->h_status + ST_WORDS + kHaloWords);
 	ctx->d_stamps	   = reinterpret_cast<unsigned long long*>(ctx->d_status + kStatusCore);
 	ctx->h_stamps	   = reinterpret_cast<const unsigned long long*>(ctx->h_status + kStatusCore);
-	HIP_TRY(dalloc(&ctx->d_totals, 4));
-	HIP_TRY(dalloc(&ctx->d_counter, 1));
-	HIP_TRY(hipMemsetAsync(ctx->d_status, 0, sizeof(int) * kStatusBlock, s));
+	HIP_TRY(ctx->d_totals.alloc(4, s));
+	HIP_TRY(ctx->d_counter.alloc(1, s));
 	for(int i = 0; i < 2; ++i) {
-		HIP_TRY(dalloc(&ctx->part[i].table, table));
-		HIP_TRY(dalloc(&ctx->part[i].count, 1));
+		HIP_TRY(ctx->part[i].table.alloc(table, s));
+		HIP_TRY(ctx->part[i].count.alloc(1, s));
 		HIP_TRY(hipMemsetAsync(ctx->part[i].table, 0xff, sizeof(int) * table, s));
-		HIP_TRY(hipMemsetAsync(ctx->part[i].count, 0, sizeof(int), s));
 	}
 	// Pass 1: activate particle blocks with a provisional capacity = table size bound by the particle count
 	size_t total_particles = 0;
@@ -634,7 +615,7 @@ int mpm_initial_setup(mpm_ctx* ctx) {
 	size_t prov = std::min(table, total_particles + 1);
 	if(ctx->cfg.max_blocks > 0) prov = std::min<size_t>(table, (size_t) ctx->cfg.max_blocks);
 	Partition& P = ctx->part[n];
-	HIP_TRY(dalloc(&P.keys, 3 * prov));
+	HIP_TRY(P.keys.alloc(3 * prov, s));
 	g.cap = (int) prov;
 	for(auto& m: ctx->models)
 		if(m.n) activate_blocks_kernel<<<cdiv(m.n, 256), 256, 0, s>>>(g, m.n, m.d_xyz, P.table, P.keys, P.count, ctx->d_status);
@@ -647,15 +628,9 @@ int mpm_initial_setup(mpm_ctx* ctx) {
 	// capacities below can be sized by the exterior block count that is actually there (a compact body has ~1.15 exterior
 	// blocks per particle block, a thin sheet up to 27: sizing by a fixed multiple of pbc wasted 8 GB at C3)
 	if(ctx->cfg.max_blocks <= 0 && (size_t) pbc * 27 > prov) {// the provisional list must hold every block that can be registered
-		int* keys		  = nullptr;
-		const size_t need = std::min(table, (size_t) pbc * 27 + 1);
-		HIP_TRY(dalloc(&keys, 3 * need));
-		HIP_TRY(hipMemcpyAsync(keys, P.keys, sizeof(int) * 3 * (size_t) pbc, hipMemcpyDeviceToDevice, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		HIP_TRY(hipFree(P.keys));
-		P.keys = keys;
-		prov   = need;
-		g.cap  = (int) prov;
+		prov = std::min(table, (size_t) pbc * 27 + 1);
+		HIP_TRY(P.keys.grow(3 * prov, s));
+		g.cap = (int) prov;
 	}
 	// (one-time set-up: the phase counters start from the activation's count; the published counts are formed on the host below)
 	HIP_TRY(hipMemcpyAsync(&ctx->d_status[ST_CNT_P], P.count, sizeof(int), hipMemcpyDeviceToDevice, s));
@@ -680,40 +655,22 @@ int mpm_initial_setup(mpm_ctx* ctx) {
 	// 3/2 of the exterior blocks + slack, i.e. below the 3/4 fill level at which check_capacity() grows it
 	size_t cap = ctx->cfg.max_blocks > 0 ? (size_t) ctx->cfg.max_blocks : std::min(table, (size_t) ctx->ebc * 3 / 2 + 4096);
 	if(cap < (size_t) ctx->ebc) return fail(ctx, MPM_ERR_CAPACITY, "Too much exterior blocks: " + std::to_string(ctx->ebc) + " (max_blocks " + std::to_string(cap) + ")");
-	{
-		int* keys = nullptr;
-		HIP_TRY(dalloc(&keys, 3 * cap));
+	if(P.keys.n > 3 * cap) {// the provisional list was the longer one: the final one holds the registered keys alone
+		DevBuf<int> keys;
+		HIP_TRY(keys.alloc(3 * cap, s));
 		HIP_TRY(hipMemcpyAsync(keys, P.keys, sizeof(int) * 3 * (size_t) ctx->ebc, hipMemcpyDeviceToDevice, s));
 		HIP_TRY(hipStreamSynchronize(s));
-		HIP_TRY(hipFree(P.keys));
-		P.keys = keys;
-		HIP_TRY(dalloc(&ctx->part[r].keys, 3 * cap));
+		P.keys = std::move(keys);
 	}
 	g.cap = (int) cap;
-	for(int i = 0; i < 2; ++i) {
-		HIP_TRY(dalloc(&ctx->grid[i], cap * 256));
-	}
+	for(auto& m: ctx->models) m.pair = ((pair_mask() >> m.material) & 1) != 0 && g.ppb <= kPairChunks * kListChunk;
+	HIP_TRY(size_block_arrays(ctx, cap, false));
 	// per model: bucket particles per block, allocate bins, fill bins + identity advection records
 	for(size_t mi = 0; mi < ctx->models.size(); ++mi) {
 		Model& m  = ctx->models[mi];
 		m.bin_cap = m.n / kBin + cap + 1;
-		for(int i = 0; i < 2; ++i) {
-			HIP_TRY(dalloc(&m.bins[i], m.bin_cap * m.nch * kBin));
-			if(ctx->track_ids) HIP_TRY(dalloc(&m.ids[i], m.bin_cap * kBin));
-			HIP_TRY(dalloc(&m.binoff[i], cap + 1));
-			HIP_TRY(dalloc(&m.list[i], cap * (size_t) g.ppb));
-		}
-		HIP_TRY(dalloc(&m.size, cap + 1));
-		HIP_TRY(dalloc(&m.row_of, cap + 1));
-		HIP_TRY(dalloc(&m.out_count, cap + 1));
-		HIP_TRY(dalloc(&m.keep, cap + 1));
+		HIP_TRY(size_bin_arrays(ctx, m, m.bin_cap));
 		HIP_TRY(hipMemsetAsync(m.keep, 0xff, sizeof(int) * (cap + 1), s));
-		HIP_TRY(dalloc(&m.blockinfo, cap * (size_t) kInfoRow));
-		m.pair = ((pair_mask() >> m.material) & 1) != 0 && g.ppb <= kPairChunks * kListChunk;
-		if(m.pair)
-			for(int i = 0; i < 2; ++i) HIP_TRY(dalloc(&m.pairinfo[i], (cap + 1) * (size_t) kPairChunks));
-		HIP_TRY(hipMemsetAsync(m.out_count, 0, sizeof(int) * (cap + 1), s));
-		HIP_TRY(hipMemsetAsync(m.size, 0, sizeof(int) * (cap + 1), s));
 		if(m.n) bucket_particles_kernel<<<cdiv(m.n, 256), 256, 0, s>>>(g, m.n, m.d_xyz, P.table, m.out_count, m.list[1], ctx->d_status);
 		if(pbc) {
 			init_bins_kernel<<<cdiv(pbc, 256), 256, 0, s>>>(pbc, m.out_count, m.size, m.row_of, m.binoff[r], m.binoff[n], &ctx->d_status[ST_BINS0 + mi]);
@@ -1049,57 +1006,39 @@ static int launch_rebuild(mpm_ctx* ctx, const SubstepPlan& plan, StillLaunch* ta
 // capacity the capacity grows by 3/2.  Runs at a host synchronisation, after a rebuild; every
 // array indexed by block number (keys, grids, lists, sizes, bin offsets, halo lists) or by bin is reallocated and
 // copied.  The dense table is sized by the domain, not by the capacity.
-static int grow_capacity(mpm_ctx* ctx) {
-	if(!ctx->cfg.grow) return MPM_OK;
-	hipStream_t s	   = ctx->s_compute;
-	const size_t table = (size_t) ctx->g.G * ctx->g.G * ctx->g.G;
-	const size_t cap   = (size_t) ctx->g.cap;
-	if((size_t) ctx->ebc * 4 > cap * 3 && cap < table) {
-		const size_t ncap = std::min(table, cap * 3 / 2 + 1);
-		HIP_TRY(hipDeviceSynchronize());// both streams idle: buffers are about to be replaced
-		for(int i = 0; i < 2; ++i) {
-			HIP_TRY(regrow(&ctx->part[i].keys, 3 * cap, 3 * ncap, s));
-			HIP_TRY(regrow(&ctx->grid[i], cap * 256, ncap * 256, s));
-		}
-		for(auto& m: ctx->models) {
-			for(int i = 0; i < 2; ++i) {
-				HIP_TRY(regrow(&m.binoff[i], cap + 1, ncap + 1, s));
-				HIP_TRY(regrow(&m.list[i], cap * (size_t) ctx->g.ppb, ncap * (size_t) ctx->g.ppb, s));
-			}
-			HIP_TRY(regrow(&m.size, cap + 1, ncap + 1, s));
-			HIP_TRY(regrow(&m.row_of, cap + 1, ncap + 1, s));
-			HIP_TRY(regrow(&m.out_count, cap + 1, ncap + 1, s));
-			HIP_TRY(regrow(&m.keep, cap + 1, ncap + 1, s));
-			HIP_TRY(regrow(&m.blockinfo, cap * (size_t) kInfoRow, ncap * (size_t) kInfoRow, s));
-			if(m.pair)
-				for(int i = 0; i < 2; ++i) HIP_TRY(regrow(&m.pairinfo[i], (cap + 1) * (size_t) kPairChunks, (ncap + 1) * (size_t) kPairChunks, s));
-		}
-		if(ctx->d_overlap) {
-			HIP_TRY(regrow(&ctx->d_overlap, cap + 1, ncap + 1, s));
-			HIP_TRY(regrow(&ctx->d_halo_list, cap + 1, ncap + 1, s));
-			HIP_TRY(regrow(&ctx->d_inner_list, cap + 1, ncap + 1, s));
-		}
-		for(int p = 0; p < 32; ++p)
-			if(ctx->d_send_ids[p]) HIP_TRY(regrow(&ctx->d_send_ids[p], cap + 1, ncap + 1, s));
-		ctx->g.cap = (int) ncap;
-		ctx->relaid = true;
-		ctx->capacity_events++;
-	}
+// The two MECHANISMS: both streams idle (buffers are about to be replaced), every array of the roster grown, then the books.
+static int reserve_blocks(mpm_ctx* ctx, size_t ncap) {
+	HIP_TRY(hipDeviceSynchronize());
+	HIP_TRY(size_block_arrays(ctx, ncap, true));
+	ctx->g.cap	= (int) ncap;
+	ctx->relaid = true;
+	ctx->capacity_events++;
+	return MPM_OK;
+}
+static int reserve_bins(mpm_ctx* ctx, Model& m, size_t nb) {
+	HIP_TRY(hipDeviceSynchronize());
+	HIP_TRY(size_bin_arrays(ctx, m, nb));
+	m.bin_cap	= nb;
+	ctx->relaid = true;
+	ctx->capacity_events++;
+	return MPM_OK;
+}
+// The POLICY.  Bins: past 3/4 full by 3/2, and never below the worst case of the block capacity - every block ends with one partially filled bin.
+static int grow_bins(mpm_ctx* ctx) {
 	for(auto& m: ctx->models) {
-		// worst case: every block ends with one partially filled bin
 		const size_t need = m.n / kBin + (size_t) ctx->g.cap + 1;
-		if((size_t) m.bincount * 4 > m.bin_cap * 3 || need > m.bin_cap) {
-			const size_t nb = std::max(need, (size_t) m.bincount * 4 > m.bin_cap * 3 ? m.bin_cap * 3 / 2 + 1 : m.bin_cap);
-			HIP_TRY(hipDeviceSynchronize());
-			for(int i = 0; i < 2; ++i) HIP_TRY(regrow(&m.bins[i], m.bin_cap * m.nch * kBin, nb * m.nch * kBin, s));
-			if(ctx->track_ids)
-				for(int i = 0; i < 2; ++i) HIP_TRY(regrow(&m.ids[i], m.bin_cap * kBin, nb * kBin, s));
-			m.bin_cap = nb;
-			ctx->relaid = true;
-			ctx->capacity_events++;
-		}
+		if((size_t) m.bincount * 4 > m.bin_cap * 3 || need > m.bin_cap)
+			if(int rc = reserve_bins(ctx, m, std::max(need, (size_t) m.bincount * 4 > m.bin_cap * 3 ? m.bin_cap * 3 / 2 + 1 : m.bin_cap))) return rc;
 	}
 	return MPM_OK;
+}
+static int grow_capacity(mpm_ctx* ctx) {
+	if(!ctx->cfg.grow) return MPM_OK;
+	const size_t table = (size_t) ctx->g.G * ctx->g.G * ctx->g.G;
+	const size_t cap   = (size_t) ctx->g.cap;
+	if((size_t) ctx->ebc * 4 > cap * 3 && cap < table)
+		if(int rc = reserve_blocks(ctx, std::min(table, cap * 3 / 2 + 1))) return rc;
+	return grow_bins(ctx);
 }
 
 // the host's half of a rebuild that needs no device data: the roll (gmpm_simulator.cuh:578)
@@ -1396,23 +1335,22 @@ int mpm_set_collision_object(mpm_ctx* ctx, const mpm_collision_object* obj, cons
 	if(!ctx) return MPM_ERR_INVALID;
 	HIP_TRY(hipSetDevice(ctx->device));
 	HIP_TRY(hipDeviceSynchronize());
-	if(ctx->d_sdf) HIP_TRY(hipFree(ctx->d_sdf));
-	ctx->d_sdf			   = nullptr;
+	HIP_TRY(ctx->d_sdf.reset());
 	ctx->has_collision	   = false;
 	ctx->collision_running = false;// installing or removing an object stops the clock
 	if(!obj) return MPM_OK;
 	if(!sdf || !gx || !gy || !gz) return fail(ctx, MPM_ERR_INVALID, "collision object without a signed distance field");
 	if(!boundary_type_ok(obj)) return fail(ctx, MPM_ERR_INVALID, "[ERROR] Wrong Boundary Type!");// boundary_condition.cuh:244
 	const size_t N = (size_t) 1 << ctx->cfg.domain_bits, n = N * N * N;
-	float* stage = nullptr;
-	HIP_TRY(dalloc(&stage, 4 * n));
-	HIP_TRY(dalloc(&ctx->d_sdf, n));
+	DevBuf<float> stage;
+	HIP_TRY(stage.alloc(4 * n, ctx->s_compute));
+	HIP_TRY(ctx->d_sdf.alloc(n, ctx->s_compute));
 	const float* src[4] = {sdf, gx, gy, gz};
 	for(int c = 0; c < 4; ++c) HIP_TRY(hipMemcpy(stage + c * n, src[c], sizeof(float) * n, hipMemcpyHostToDevice));
 	pack_sdf_kernel<<<cdiv(n, 256), 256, 0, ctx->s_compute>>>(n, stage, stage + n, stage + 2 * n, stage + 3 * n, ctx->d_sdf);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipStreamSynchronize(ctx->s_compute));
-	HIP_TRY(hipFree(stage));
+	HIP_TRY(stage.reset());
 	ctx->collision		 = slot_object(obj);
 	ctx->collision.field = ctx->d_sdf;
 	ctx->has_collision	 = true;
@@ -1467,28 +1405,23 @@ static void count_slots(mpm_ctx* ctx) {
 	}
 }
 // What sits in a slot.  All empty: nothing (shape.shape.kind 0); an analytic shape fills `shape` alone; a heightfield `shape` and `hf`; a volume
-// `shape`, `vol` and `desc`, its descriptor as installed.
+// `shape`, `vol` and `desc`, its descriptor as installed; `table` is the heightfield's or the volume's (hf.table / vol.table: set by install_slot).
 struct SlotOccupant {
 	ShapeSlot shape {};
 	Heightfield hf {};
 	Volume vol {};
 	mpm_collision_volume desc {};
+	DevBuf<float4> table;
 };
 // What every accepted install or removal of any kind does to slot `slot`: wait for the device, free the table of a heightfield or a volume
-// that sat there, put the new occupant in (o.hf.table / o.vol.table: the new heightfield's / volume's, owned by the context from here on),
-// stop the clock and - on an install - set it to obj->time.
-static int install_slot(mpm_ctx* ctx, int slot, const SlotOccupant& o, const mpm_collision_object* obj) {
-	const float4* fresh = o.hf.table ? o.hf.table : o.vol.table;
-	hipError_t e		= hipSetDevice(ctx->device);
+// that sat there, put the new occupant in (o.table: the new heightfield's / volume's, owned by the context's slot_table from here on; a
+// refused install frees it with o), stop the clock and - on an install - set it to obj->time.
+static int install_slot(mpm_ctx* ctx, int slot, SlotOccupant& o, const mpm_collision_object* obj) {
+	hipError_t e = hipSetDevice(ctx->device);
 	if(e == hipSuccess) e = hipDeviceSynchronize();
-	if(e != hipSuccess) {// nothing was touched: the old occupant stays
-		if(fresh) hipFree(const_cast<float4*>(fresh));
-		return fail(ctx, MPM_ERR_DEVICE, std::string("collision slot: ") + hipGetErrorString(e));
-	}
+	if(e != hipSuccess) return fail(ctx, MPM_ERR_DEVICE, std::string("collision slot: ") + hipGetErrorString(e));// nothing was touched: the old occupant stays
 	// the old table goes first; should freeing it fail, its memory is in an unknown state, so the slot is emptied rather than left pointing at it
-	const float4* old = ctx->hf[slot].table ? ctx->hf[slot].table : ctx->vol[slot].table;
-	if(old && (e = hipFree(const_cast<float4*>(old))) != hipSuccess) {
-		if(fresh) hipFree(const_cast<float4*>(fresh));
+	if((e = ctx->slot_table[slot].reset()) != hipSuccess) {
 		ctx->hf[slot]		= Heightfield {};
 		ctx->vol[slot]		= Volume {};
 		ctx->vol_desc[slot] = mpm_collision_volume {};
@@ -1496,8 +1429,11 @@ static int install_slot(mpm_ctx* ctx, int slot, const SlotOccupant& o, const mpm
 		count_slots(ctx);
 		return fail(ctx, MPM_ERR_DEVICE, std::string("collision slot: freeing the old table -> ") + hipGetErrorString(e) + " (the slot is now empty)");
 	}
-	ctx->hf[slot]		   = o.hf;
-	ctx->vol[slot]		   = o.vol;
+	ctx->slot_table[slot] = std::move(o.table);
+	ctx->hf[slot]		  = o.hf;
+	ctx->vol[slot]		  = o.vol;
+	if(o.shape.shape.kind == kShapeHeightfield) ctx->hf[slot].table = ctx->slot_table[slot];
+	if(o.shape.shape.kind == kShapeVolume) ctx->vol[slot].table = ctx->slot_table[slot];
 	ctx->vol_desc[slot]	   = o.desc;
 	ctx->shape[slot]	   = o.shape;// (kind 0: empty)
 	ctx->collision_running = false;// installing or removing a collider stops the clock
@@ -1553,13 +1489,9 @@ int mpm_set_collision_heightfield(mpm_ctx* ctx, int slot, const mpm_collision_ob
 	std::vector<float4> table(n);
 	if(!heightfield_build(heights, f.nx, f.nz, f.spacing, table.data())) return fail(ctx, MPM_ERR_INVALID, "collision heightfield: a height or a derived table entry is not finite");
 	HIP_TRY(hipSetDevice(ctx->device));
-	float4* d = nullptr;
-	HIP_TRY(dalloc(&d, n));
-	if(hipError_t e = hipMemcpy(d, table.data(), sizeof(float4) * n, hipMemcpyHostToDevice)) {
-		hipFree(d);
+	HIP_TRY(o.table.alloc(n, ctx->s_compute));
+	if(hipError_t e = hipMemcpy(o.table, table.data(), sizeof(float4) * n, hipMemcpyHostToDevice))
 		return fail(ctx, MPM_ERR_DEVICE, std::string("collision heightfield: copying the table -> ") + hipGetErrorString(e));
-	}
-	f.table = d;
 	return install_slot(ctx, slot, o, obj);
 }
 
@@ -1569,8 +1501,8 @@ int mpm_set_collision_heightfield(mpm_ctx* ctx, int slot, const mpm_collision_ob
 struct MeshRecords {
 	std::vector<MeshTri> rec;
 	std::vector<MeshPseudo> pseudo;
-	DevScratch<MeshTri> d_rec;
-	DevScratch<MeshPseudo> d_pseudo;
+	DevBuf<MeshTri> d_rec;
+	DevBuf<MeshPseudo> d_pseudo;
 	float extent = 0.f;// largest coordinate magnitude in play: the caller's starting value (the domain's 1, or 0 and a box's corners later) or a vertex's
 	// empty, or why the mesh is refused ("collision mesh: ...", mesh_build's)
 	std::string build(const float* verts, size_t nv, const int32_t* tris, size_t nt, float extent0) {
@@ -1580,9 +1512,9 @@ struct MeshRecords {
 		for(size_t i = 0; rep.reason.empty() && i < 3 * nv; ++i) extent = std::max(extent, std::fabs(verts[i]));
 		return rep.reason;
 	}
-	hipError_t alloc() {
-		const hipError_t e = d_rec.alloc(rec.size());
-		return e == hipSuccess ? d_pseudo.alloc(rec.size()) : e;
+	hipError_t alloc(hipStream_t s) {
+		const hipError_t e = d_rec.alloc(rec.size(), s);
+		return e == hipSuccess ? d_pseudo.alloc(rec.size(), s) : e;
 	}
 	hipError_t upload() {
 		const hipError_t e = hipMemcpy(d_rec.p, rec.data(), sizeof(MeshTri) * rec.size(), hipMemcpyHostToDevice);
@@ -1592,16 +1524,15 @@ struct MeshRecords {
 };
 
 // The table of `box` (dims, origin, spacing; its inside_out is the query's, the argument is what goes into the words) from a built mesh:
-// wait for the device, allocate the table and the records, upload, run collision_mesh_table_kernel.  MPM_OK: *out is the caller's table.
-// Anything else: the table is freed (the records go with m) and the context is untouched; the message reads "<who>: ... the <noun> of n <unit> ...".
-static int mesh_table_build(mpm_ctx* ctx, MeshRecords& m, const Volume& box, int inside_out, const char* who, const char* noun, const char* unit, float4** out) {
+// wait for the device, allocate the table and the records, upload, run collision_mesh_table_kernel.  MPM_OK: out holds the table.
+// Anything else: out is empty (the records go with m) and the context is untouched; the message reads "<who>: ... the <noun> of n <unit> ...".
+static int mesh_table_build(mpm_ctx* ctx, MeshRecords& m, const Volume& box, int inside_out, const char* who, const char* noun, const char* unit, DevBuf<float4>& out) {
 	HIP_TRY(hipSetDevice(ctx->device));
 	HIP_TRY(hipDeviceSynchronize());
 	const size_t n = (size_t) box.dims[0] * (size_t) box.dims[1] * (size_t) box.dims[2], nt = m.rec.size();
-	float4* table  = nullptr;
-	if(dalloc(&table, n) != hipSuccess || m.alloc() != hipSuccess) {
+	DevBuf<float4> table;
+	if(table.alloc(n, ctx->s_compute) != hipSuccess || m.alloc(ctx->s_compute) != hipSuccess) {
 		(void) hipGetLastError();
-		if(table) hipFree(table);
 		return fail(ctx, MPM_ERR_CAPACITY, std::string(who) + ": no device memory for the " + noun + " of " + std::to_string(n) + " " + unit + " and " + std::to_string(nt) + " triangle records");
 	}
 	hipError_t e = m.upload();
@@ -1612,11 +1543,8 @@ static int mesh_table_build(mpm_ctx* ctx, MeshRecords& m, const Volume& box, int
 		e = hipGetLastError();
 	}
 	if(e == hipSuccess) e = hipStreamSynchronize(ctx->s_compute);
-	if(e != hipSuccess) {
-		hipFree(table);
-		return fail(ctx, MPM_ERR_DEVICE, std::string(who) + ": building the " + noun + " -> " + hipGetErrorString(e));
-	}
-	*out = table;
+	if(e != hipSuccess) return fail(ctx, MPM_ERR_DEVICE, std::string(who) + ": building the " + noun + " -> " + hipGetErrorString(e));
+	out = std::move(table);
 	return MPM_OK;
 }
 
@@ -1635,12 +1563,11 @@ int mpm_set_collision_mesh(mpm_ctx* ctx, const mpm_collision_object* obj, const 
 	Volume nodes {};// the domain's nodes as a table: N^3 samples dx apart from 0
 	nodes.dims[0] = nodes.dims[1] = nodes.dims[2] = N;
 	nodes.spacing = 1.f / (float) N;
-	float4* field = nullptr;
-	if(int rc = mesh_table_build(ctx, m, nodes, opt && opt->inside_out ? 1 : 0, "collision mesh", "field", "nodes", &field)) return rc;
-	if(ctx->d_sdf) hipFree(ctx->d_sdf);
-	ctx->d_sdf			   = field;
+	DevBuf<float4> field;
+	if(int rc = mesh_table_build(ctx, m, nodes, opt && opt->inside_out ? 1 : 0, "collision mesh", "field", "nodes", field)) return rc;
+	ctx->d_sdf			   = std::move(field);
 	ctx->collision		   = slot_object(obj);
-	ctx->collision.field   = field;
+	ctx->collision.field   = ctx->d_sdf;
 	ctx->has_collision	   = true;
 	ctx->collision_running = false;// installing an object stops the clock
 	return MPM_OK;
@@ -1650,8 +1577,8 @@ int mpm_set_collision_mesh(mpm_ctx* ctx, const mpm_collision_object* obj, const 
 static int read_table_box(mpm_ctx* ctx, const char* who, const float4* table, int d1, int d2, const int lo[3], const int dims[3], float* out4) {
 	const size_t n = (size_t) dims[0] * (size_t) dims[1] * (size_t) dims[2];
 	HIP_TRY(hipSetDevice(ctx->device));
-	DevScratch<float4> stage;
-	if(dalloc(&stage.p, n) != hipSuccess) {
+	DevBuf<float4> stage;
+	if(stage.alloc(n, ctx->s_compute) != hipSuccess) {
 		(void) hipGetLastError();
 		return fail(ctx, MPM_ERR_CAPACITY, std::string(who) + ": no device memory for the box");
 	}
@@ -1731,16 +1658,12 @@ int mpm_set_collision_volume(mpm_ctx* ctx, int slot, const mpm_collision_object*
 	const size_t n = (size_t) v.dims[0] * (size_t) v.dims[1] * (size_t) v.dims[2];
 	if(!volume_samples_finite(field4, n)) return fail(ctx, MPM_ERR_INVALID, "collision volume: a sample of field4 is not finite");
 	HIP_TRY(hipSetDevice(ctx->device));
-	float4* d = nullptr;
-	if(dalloc(&d, n) != hipSuccess) {
+	if(o.table.alloc(n, ctx->s_compute) != hipSuccess) {
 		(void) hipGetLastError();
 		return fail(ctx, MPM_ERR_CAPACITY, "collision volume: no device memory for the table of " + std::to_string(n) + " samples");
 	}
-	if(hipError_t e = hipMemcpy(d, field4, sizeof(float4) * n, hipMemcpyHostToDevice)) {
-		hipFree(d);
+	if(hipError_t e = hipMemcpy(o.table, field4, sizeof(float4) * n, hipMemcpyHostToDevice))
 		return fail(ctx, MPM_ERR_DEVICE, std::string("collision volume: copying the table -> ") + hipGetErrorString(e));
-	}
-	v.table = d;
 	o.desc	= volume_descriptor(v, vol->pad);
 	return install_slot(ctx, slot, o, obj);
 }
@@ -1767,9 +1690,7 @@ int mpm_set_collision_volume_mesh(mpm_ctx* ctx, int slot, const mpm_collision_ob
 			return fail(ctx, MPM_ERR_INVALID, "collision volume: dims sized from the mesh's bounding box, spacing and pad leave 2..1024 per axis or 2^27 samples");
 	}
 	for(int d = 0; d < 3; ++d) m.extent = std::max(m.extent, std::max(std::fabs(v.origin[d]), std::fabs(v.origin[d] + (float) (v.dims[d] - 1) * v.spacing)));// the box's corners count too
-	float4* table = nullptr;
-	if(int rc = mesh_table_build(ctx, m, v, 0, "collision volume", "table", "samples", &table)) return rc;
-	v.table = table;
+	if(int rc = mesh_table_build(ctx, m, v, 0, "collision volume", "table", "samples", o.table)) return rc;
 	o.desc	= volume_descriptor(v, pad);
 	return install_slot(ctx, slot, o, obj);
 }
@@ -1800,9 +1721,9 @@ struct MeshFillPlan {
 	unsigned ntiles = 0, ngroups = 0;
 	unsigned long long total = 0, shortcuts = 0;
 	MeshRecords mesh;
-	DevScratch<unsigned char> masks;
-	DevScratch<unsigned> counts, bsum;
-	DevScratch<unsigned long long> boff;// [ngroups] the groups' offsets, [ngroups] the total, [ngroups + 1] the shortcut tiles (statistics)
+	DevBuf<unsigned char> masks;
+	DevBuf<unsigned> counts, bsum;
+	DevBuf<unsigned long long> boff;// [ngroups] the groups' offsets, [ngroups] the total, [ngroups + 1] the shortcut tiles (statistics)
 	float ms[3] = {0.f, 0.f, 0.f};		// classify, scan, emit - measured only when asked for
 };
 // Events around the kernels of a timed call; released with the scope
@@ -1860,13 +1781,12 @@ static int mesh_fill_count(std::string& err, const char* who, int bits, const fl
 	P.total = P.shortcuts = 0;
 	if(!P.ntiles) return MPM_OK;
 	P.ngroups = cdiv(P.ntiles, kMeshFillGroup);
-	if(P.mesh.alloc() != hipSuccess || P.masks.alloc((size_t) P.ntiles * 64) != hipSuccess || P.counts.alloc(P.ntiles) != hipSuccess
-	   || P.bsum.alloc(P.ngroups) != hipSuccess || P.boff.alloc((size_t) P.ngroups + 2) != hipSuccess) {
+	if(P.mesh.alloc(s) != hipSuccess || P.masks.alloc((size_t) P.ntiles * 64, s) != hipSuccess || P.counts.alloc(P.ntiles, s) != hipSuccess
+	   || P.bsum.alloc(P.ngroups, s) != hipSuccess || P.boff.alloc((size_t) P.ngroups + 2, s) != hipSuccess) {
 		(void) hipGetLastError();
 		return refuse(MPM_ERR_CAPACITY, "no device memory for the work buffers of " + std::to_string(P.ntiles) + " tiles and " + std::to_string(nt) + " triangle records");
 	}
 	FILL_TRY(P.mesh.upload());
-	FILL_TRY(hipMemsetAsync(P.boff.p, 0, sizeof(unsigned long long) * ((size_t) P.ngroups + 2), s));
 	MeshFillEvents ev(timed);
 	ev.mark(0, s);
 	mesh_fill_classify_kernel<<<P.ntiles, 64, 0, s>>>(P.mesh.d_rec.p, P.mesh.d_pseudo.p, (int) nt, P.a, P.masks.p, P.counts.p, P.boff.p + P.ngroups + 1);
@@ -1913,8 +1833,8 @@ static int sample_mesh(int domain_bits, const float* verts, size_t nv, const int
 	*n = (size_t) P.total;
 	if(xyz && P.total > cap) return MPM_ERR_CAPACITY;
 	if((xyz || out8) && P.total) {
-		DevScratch<float> d_xyz;
-		if(d_xyz.alloc(3 * (size_t) P.total) != hipSuccess) {
+		DevBuf<float> d_xyz;
+		if(d_xyz.alloc(3 * (size_t) P.total, nullptr) != hipSuccess) {
 			(void) hipGetLastError();
 			return MPM_ERR_CAPACITY;
 		}
@@ -1957,17 +1877,14 @@ int mpm_add_model_mesh(mpm_ctx* ctx, int material, const mpm_material_params* pa
 	m.nch	   = material == MPM_J_FLUID ? 4 : (material == MPM_FIXED_COROTATED ? 9 : 10);// as mpm_add_model
 	m.n		   = (size_t) P.total;
 	for(int d = 0; d < 3; ++d) m.v0[d] = v0 ? v0[d] : 0.f;
-	if(dalloc(&m.d_xyz, 3 * m.n) != hipSuccess) {// the model's own array: the emit kernel writes into it
+	if(m.d_xyz.alloc(3 * m.n, ctx->s_compute) != hipSuccess) {// the model's own array: the emit kernel writes into it
 		(void) hipGetLastError();
 		return fail(ctx, MPM_ERR_CAPACITY, "mpm_add_model_mesh: no device memory for " + std::to_string(P.total) + " positions");
 	}
-	if(int rc = mesh_fill_emit(err, "mpm_add_model_mesh", P, m.d_xyz, ctx->s_compute, false)) {
-		hipFree(m.d_xyz);
-		return fail(ctx, rc, err);
-	}
+	if(int rc = mesh_fill_emit(err, "mpm_add_model_mesh", P, m.d_xyz, ctx->s_compute, false)) return fail(ctx, rc, err);
 	if(model_id) *model_id = (int) ctx->models.size();
 	if(n_out) *n_out = m.n;
-	ctx->models.push_back(m);
+	ctx->models.push_back(std::move(m));
 	return MPM_OK;
 }
 
@@ -2041,11 +1958,11 @@ static int readout_particles(mpm_ctx* ctx, int model, ReadoutKind kind, float* c
 	hipStream_t s	 = ctx->s_compute;
 	Model& m		 = ctx->models[model];
 	const size_t cap = std::min(*n, m.n);
-	DevScratch<float> scratch[3];
+	DevBuf<float> scratch[3];
 	ReadoutOut out {{m.d_xyz, nullptr, nullptr}, cap, ctx->d_counter, 0.0, nullptr, m.material, m.mc};
 	for(int c = 1; c < 3; ++c)
 		if(host[c]) {
-			HIP_TRY(scratch[c].alloc(kReadoutWidth[kind][c] * cap));
+			HIP_TRY(scratch[c].alloc(kReadoutWidth[kind][c] * cap, s));
 			out.col[c] = scratch[c].p;
 		}
 	if(kind == kReadIds) out.ids = reinterpret_cast<int*>(out.col[1]);
@@ -2083,9 +2000,8 @@ static int readout_velocity(mpm_ctx* ctx, int model, float* xyz, float* vel, flo
 static int readout_totals(mpm_ctx* ctx, int model, ReadoutKind kind, int nwords, double* out) {
 	HIP_TRY(hipSetDevice(ctx->device));
 	hipStream_t s = ctx->s_compute;
-	DevScratch<double> d_out;
-	HIP_TRY(d_out.alloc(nwords));
-	HIP_TRY(hipMemsetAsync(d_out.p, 0, sizeof(double) * nwords, s));
+	DevBuf<double> d_out;
+	HIP_TRY(d_out.alloc(nwords, s));
 	for(int mi = model < 0 ? 0 : model; mi < (model < 0 ? (int) ctx->models.size() : model + 1); ++mi) {
 		Model& m = ctx->models[mi];
 		if(m.n) launch_readout(ctx, m, kind, ReadoutOut {{}, 0, nullptr, (double) (kind == kReadMomentum ? m.mc.mass : m.mc.volume), d_out.p, m.material, m.mc}, s);
@@ -2307,8 +2223,8 @@ int mpm_sample_grid(mpm_ctx* ctx, const float* xyz, size_t n, float* out4) {
 	if(!n) return MPM_OK;
 	HIP_TRY(hipSetDevice(ctx->device));
 	hipStream_t s = ctx->s_compute;
-	DevScratch<float> d_xyz, d_out;
-	if(d_xyz.alloc(3 * n) != hipSuccess || d_out.alloc(4 * n) != hipSuccess) {
+	DevBuf<float> d_xyz, d_out;
+	if(d_xyz.alloc(3 * n, s) != hipSuccess || d_out.alloc(4 * n, s) != hipSuccess) {
 		(void) hipGetLastError();
 		return fail(ctx, MPM_ERR_CAPACITY, "mpm_sample_grid: no device memory for " + std::to_string(n) + " points");
 	}
@@ -2334,8 +2250,8 @@ int mpm_grid_volume(mpm_ctx* ctx, const int origin[3], const int dims[3], int st
 	if(int rc = readout_state(ctx, "mpm_grid_volume")) return rc;
 	HIP_TRY(hipSetDevice(ctx->device));
 	hipStream_t s = ctx->s_compute;
-	DevScratch<float> d_out;
-	if(d_out.alloc(4 * cells) != hipSuccess) {
+	DevBuf<float> d_out;
+	if(d_out.alloc(4 * cells, s) != hipSuccess) {
 		(void) hipGetLastError();// (the context stays usable)
 		return fail(ctx, MPM_ERR_CAPACITY, "mpm_grid_volume: no device memory for " + std::to_string(16 * cells) + " bytes");
 	}
@@ -2377,12 +2293,11 @@ int mpm_grid_box_totals(mpm_ctx* ctx, const int lo[3], const int hi[3], double o
 	if(empty) return MPM_OK;
 	HIP_TRY(hipSetDevice(ctx->device));
 	hipStream_t s = ctx->s_compute;
-	DevScratch<double> d_out;
-	if(d_out.alloc(kBoxSums) != hipSuccess) {
+	DevBuf<double> d_out;
+	if(d_out.alloc(kBoxSums, s) != hipSuccess) {
 		(void) hipGetLastError();
 		return fail(ctx, MPM_ERR_CAPACITY, "mpm_grid_box_totals: no device memory");
 	}
-	HIP_TRY(hipMemsetAsync(d_out.p, 0, sizeof(double) * kBoxSums, s));
 	grid_box_totals_kernel<<<std::min(256u, cdiv(ctx->nbc, kGridFieldThreads / 64)), kGridFieldThreads, 0, s>>>(ctx->nbc, ctx->part[ctx->rollid].keys, ctx->grid[0], box, d_out.p);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(out, d_out.p, sizeof(double) * kBoxSums, hipMemcpyDeviceToHost, s));
@@ -2408,8 +2323,8 @@ int mpm_grid_isosurface(mpm_ctx* ctx, float iso_mass, const int lo[3], const int
 	}
 	HIP_TRY(hipSetDevice(ctx->device));
 	hipStream_t s = ctx->s_compute;
-	DevScratch<float> d_xyz, d_vel;
-	if(cap && (d_xyz.alloc(9 * cap) != hipSuccess || (tri_vel && d_vel.alloc(9 * cap) != hipSuccess))) {
+	DevBuf<float> d_xyz, d_vel;
+	if(cap && (d_xyz.alloc(9 * cap, s) != hipSuccess || (tri_vel && d_vel.alloc(9 * cap, s) != hipSuccess))) {
 		(void) hipGetLastError();// (the context stays usable; *n is left as it was)
 		return fail(ctx, MPM_ERR_CAPACITY, "mpm_grid_isosurface: no device memory for " + std::to_string(cap) + " triangles");
 	}
@@ -2454,8 +2369,8 @@ int mpm_collider_loads(mpm_ctx* ctx, float dt, const mpm_load_options* opt, doub
 	if(int rc = loads_state(ctx, dt, "mpm_collider_loads")) return rc;
 	HIP_TRY(hipSetDevice(ctx->device));
 	hipStream_t s = ctx->s_compute;
-	DevScratch<double> d_part, d_out;
-	if(d_part.alloc((size_t) kLoadGroups * kLoadRows * kLoadSums) != hipSuccess || d_out.alloc(kLoadRows * kLoadSums) != hipSuccess) {
+	DevBuf<double> d_part, d_out;
+	if(d_part.alloc((size_t) kLoadGroups * kLoadRows * kLoadSums, s) != hipSuccess || d_out.alloc(kLoadRows * kLoadSums, s) != hipSuccess) {
 		(void) hipGetLastError();
 		return fail(ctx, MPM_ERR_CAPACITY, "mpm_collider_loads: no device memory");
 	}
@@ -2474,9 +2389,9 @@ int mpm_collider_contacts(mpm_ctx* ctx, float dt, int32_t* node_row4, float* rec
 	if(cap > SIZE_MAX / (8 * sizeof(float))) return fail(ctx, MPM_ERR_CAPACITY, "mpm_collider_contacts: no device memory for " + std::to_string(cap) + " records");
 	HIP_TRY(hipSetDevice(ctx->device));
 	hipStream_t s = ctx->s_compute;
-	DevScratch<int> d_nr;
-	DevScratch<float> d_rec;
-	if(cap && (d_nr.alloc(4 * cap) != hipSuccess || d_rec.alloc(8 * cap) != hipSuccess)) {
+	DevBuf<int> d_nr;
+	DevBuf<float> d_rec;
+	if(cap && (d_nr.alloc(4 * cap, s) != hipSuccess || d_rec.alloc(8 * cap, s) != hipSuccess)) {
 		(void) hipGetLastError();// (the context stays usable; *n is left as it was)
 		return fail(ctx, MPM_ERR_CAPACITY, "mpm_collider_contacts: no device memory for " + std::to_string(cap) + " records");
 	}
@@ -2504,17 +2419,16 @@ int mpm_load_gauge(mpm_ctx* ctx, int on, const mpm_load_options* opt) {
 	HIP_TRY(hipSetDevice(ctx->device));
 	if(!on) {
 		HIP_TRY(hipStreamSynchronize(ctx->s_compute));
-		hipFree(ctx->d_load_partials);
-		hipFree(ctx->d_load_acc);
-		ctx->d_load_partials = ctx->d_load_acc = nullptr;
-		ctx->load_gauge						   = false;
+		(void) ctx->d_load_partials.reset();
+		(void) ctx->d_load_acc.reset();
+		ctx->load_gauge = false;
 		return MPM_OK;
 	}
-	if(!ctx->d_load_partials && dalloc(&ctx->d_load_partials, (size_t) kLoadGroups * kLoadRows * kLoadSums) != hipSuccess) {
+	if(!ctx->d_load_partials && ctx->d_load_partials.alloc((size_t) kLoadGroups * kLoadRows * kLoadSums, ctx->s_compute) != hipSuccess) {
 		(void) hipGetLastError();
 		return fail(ctx, MPM_ERR_CAPACITY, "mpm_load_gauge: no device memory");
 	}
-	if(!ctx->d_load_acc && dalloc(&ctx->d_load_acc, kLoadAccDoubles) != hipSuccess) {
+	if(!ctx->d_load_acc && ctx->d_load_acc.alloc(kLoadAccDoubles, ctx->s_compute) != hipSuccess) {
 		(void) hipGetLastError();
 		return fail(ctx, MPM_ERR_CAPACITY, "mpm_load_gauge: no device memory");
 	}
@@ -2552,9 +2466,9 @@ int mpm_load_gauge_read(mpm_ctx* ctx, double out[MPM_LOAD_ROWS][8], double* elap
 int mpm_test_eig(const float* F, size_t n, float* out12, int device) {
 	if(!F || !out12 || n == 0) return MPM_ERR_INVALID;
 	HIP_TRY0(hipSetDevice(device));
-	DevScratch<float> dF, dO;
-	HIP_TRY0(dF.alloc(9 * n));
-	HIP_TRY0(dO.alloc(12 * n));
+	DevBuf<float> dF, dO;
+	HIP_TRY0(dF.alloc(9 * n, nullptr));
+	HIP_TRY0(dO.alloc(12 * n, nullptr));
 	HIP_TRY0(hipMemcpy(dF.p, F, sizeof(float) * 9 * n, hipMemcpyHostToDevice));
 	test_eig_kernel<<<cdiv(n, 256), 256>>>(n, dF.p, dO.p);
 	HIP_TRY0(hipGetLastError());
@@ -2565,12 +2479,12 @@ int mpm_test_eig(const float* F, size_t n, float* out12, int device) {
 int mpm_test_stress(int material, const mpm_material_params* p, const float* F, const float* logjp, size_t n, float* out19, int device) {
 	if(material < 1 || material > 3 || !p) return MPM_ERR_INVALID;
 	HIP_TRY0(hipSetDevice(device));
-	DevScratch<float> dF, dL, dO;
-	HIP_TRY0(dF.alloc(9 * n));
-	HIP_TRY0(dO.alloc(19 * n));
+	DevBuf<float> dF, dL, dO;
+	HIP_TRY0(dF.alloc(9 * n, nullptr));
+	HIP_TRY0(dO.alloc(19 * n, nullptr));
 	HIP_TRY0(hipMemcpy(dF.p, F, sizeof(float) * 9 * n, hipMemcpyHostToDevice));
 	if(logjp) {
-		HIP_TRY0(dL.alloc(n));
+		HIP_TRY0(dL.alloc(n, nullptr));
 		HIP_TRY0(hipMemcpy(dL.p, logjp, sizeof(float) * n, hipMemcpyHostToDevice));
 	}
 	test_stress_kernel<<<cdiv(n, 256), 256>>>(material, make_material_const(*p), n, dF.p, dL.p, dO.p, nullptr);
@@ -2582,9 +2496,9 @@ int mpm_test_stress(int material, const mpm_material_params* p, const float* F, 
 // The shared half of the three collider queries below: points up, test_collision_query_kernel, four floats per point down
 static int test_collision_query(ShapeSlot c, const Heightfield& f, float time, const float* xyz, size_t n, float* out4, const Volume& vol = Volume {}) {
 	c.pose = collision_pose(c.obj, time);
-	DevScratch<float> dX, dO;
-	HIP_TRY0(dX.alloc(3 * n));
-	HIP_TRY0(dO.alloc(4 * n));
+	DevBuf<float> dX, dO;
+	HIP_TRY0(dX.alloc(3 * n, nullptr));
+	HIP_TRY0(dO.alloc(4 * n, nullptr));
 	HIP_TRY0(hipMemcpy(dX.p, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
 	test_collision_query_kernel<<<cdiv(n, 256), 256>>>(c, f, vol, n, dX.p, dO.p);
 	HIP_TRY0(hipGetLastError());
@@ -2610,8 +2524,8 @@ int mpm_test_collision_heightfield(const mpm_collision_object* obj, const mpm_he
 	std::vector<float4> table(cells);
 	if(!heightfield_build(heights, f.nx, f.nz, f.spacing, table.data())) return MPM_ERR_INVALID;
 	HIP_TRY0(hipSetDevice(device));
-	DevScratch<float4> dT;
-	HIP_TRY0(dT.alloc(cells));
+	DevBuf<float4> dT;
+	HIP_TRY0(dT.alloc(cells, nullptr));
 	HIP_TRY0(hipMemcpy(dT.p, table.data(), sizeof(float4) * cells, hipMemcpyHostToDevice));
 	f.table = dT.p;
 	return test_collision_query(c, f, time, xyz, n, out4);
@@ -2625,8 +2539,8 @@ int mpm_test_collision_volume(const mpm_collision_object* obj, const mpm_collisi
 	const size_t cells = (size_t) v.dims[0] * (size_t) v.dims[1] * (size_t) v.dims[2];
 	if(!volume_samples_finite(field4, cells)) return MPM_ERR_INVALID;
 	HIP_TRY0(hipSetDevice(device));
-	DevScratch<float4> dT;
-	HIP_TRY0(dT.alloc(cells));
+	DevBuf<float4> dT;
+	HIP_TRY0(dT.alloc(cells, nullptr));
 	HIP_TRY0(hipMemcpy(dT.p, field4, sizeof(float4) * cells, hipMemcpyHostToDevice));
 	v.table = dT.p;
 	return test_collision_query(c, Heightfield {}, time, xyz, n, out4, v);

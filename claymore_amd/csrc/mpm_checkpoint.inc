@@ -156,21 +156,17 @@ int mpm_checkpoint_save(mpm_ctx* ctx, void* buf, size_t capacity, size_t* writte
 		for(int b = 0; b < h.pbc; ++b) off[b + 1] = off[b] + hsize[b];
 		if(off[h.pbc] != M.bucketed) return fail(ctx, MPM_ERR_INVALID, "checkpoint: list sizes do not add up to the bucketed particle count");
 		if(h.pbc && M.bucketed) {
-			long long* d_off = nullptr;
-			int* d_packed	 = nullptr;
-			HIP_TRY(dalloc(&d_off, (size_t) h.pbc + 1));
-			HIP_TRY(dalloc(&d_packed, (size_t) M.bucketed));
+			DevBuf<long long> d_off;
+			DevBuf<int> d_packed, d_info;
+			HIP_TRY(d_off.alloc((size_t) h.pbc + 1, ctx->s_compute));
+			HIP_TRY(d_packed.alloc((size_t) M.bucketed, ctx->s_compute));
 			HIP_TRY(hipMemcpy(d_off, off.data(), sizeof(long long) * ((size_t) h.pbc + 1), hipMemcpyHostToDevice));
-			int* d_info = nullptr;
-			if(M.pair) HIP_TRY(dalloc(&d_info, (size_t) h.pbc * kPairChunks));
+			if(M.pair) HIP_TRY(d_info.alloc((size_t) h.pbc * kPairChunks, ctx->s_compute));
 			pack_lists_kernel<<<h.pbc, 64, 0, ctx->s_compute>>>(ctx->g.ppb, M.size, M.row_of, d_off, M.list[M.list_in], d_packed, M.pair ? 1 : 0, M.pairinfo[0], d_info);
 			HIP_TRY(hipGetLastError());
 			HIP_TRY(hipStreamSynchronize(ctx->s_compute));
 			HIP_TRY(hipMemcpy(out + L.lists[mi], d_packed, sizeof(int) * (size_t) M.bucketed, hipMemcpyDeviceToHost));
 			if(M.pair) HIP_TRY(hipMemcpy(out + L.pairinfo[mi], d_info, sizeof(int) * (size_t) h.pbc * kPairChunks, hipMemcpyDeviceToHost));
-			hipFree(d_off);
-			hipFree(d_packed);
-			hipFree(d_info);
 		}
 	}
 	if(written) *written = h.total_bytes;
@@ -288,27 +284,20 @@ int mpm_checkpoint_load(mpm_ctx* ctx, const void* buf, size_t bytes) {
 	// make room (block-indexed arrays need max(ebc, prev_count) + 1 entries, bins bincount_src)
 	const int need = std::max(h.ebc, h.prev_count);
 	if(need > ctx->g.cap) {
-		const bool grow = ctx->cfg.grow;
-		if(!grow) return fail(ctx, MPM_ERR_CAPACITY, "checkpoint needs " + std::to_string(need) + " blocks, capacity is " + std::to_string(ctx->g.cap));
-		const int ebc0 = ctx->ebc;
-		while(need > ctx->g.cap) {// reuse the growth path: pretend the context is that full
-			const int before = ctx->g.cap;
-			ctx->ebc		 = ctx->g.cap;
-			int rc			 = grow_capacity(ctx);
-			if(rc || ctx->g.cap <= before) {// (the capacity stops growing at the table size)
-				ctx->ebc = ebc0;
-				return rc ? rc : fail(ctx, MPM_ERR_CAPACITY, "checkpoint needs " + std::to_string(need) + " blocks, more than the domain holds");
-			}
+		if(!ctx->cfg.grow) return fail(ctx, MPM_ERR_CAPACITY, "checkpoint needs " + std::to_string(need) + " blocks, capacity is " + std::to_string(ctx->g.cap));
+		const size_t table = (size_t) table_blocks;
+		while((size_t) need > (size_t) ctx->g.cap) {// the steps the growth policy would take (grow_capacity), the bins following the block capacity
+			const size_t ncap = std::min(table, (size_t) ctx->g.cap * 3 / 2 + 1);
+			if(ncap <= (size_t) ctx->g.cap) return fail(ctx, MPM_ERR_CAPACITY, "checkpoint needs " + std::to_string(need) + " blocks, more than the domain holds");// (the capacity stops growing at the table size)
+			if(int rc = reserve_blocks(ctx, ncap)) return rc;
+			if(int rc = grow_bins(ctx)) return rc;
 		}
-		ctx->ebc = ebc0;
 	}
 	for(int m = 0; m < h.nmodels; ++m) {
 		Model& M = ctx->models[m];
 		const size_t nb = std::max<size_t>((size_t) h.models[m].bincount_src, (size_t) h.models[m].bincount);
 		if(nb > M.bin_cap) {
-			for(int i = 0; i < 2; ++i) HIP_TRY(regrow(&M.bins[i], M.bin_cap * M.nch * kBin, nb * M.nch * kBin, s));
-			if(ctx->track_ids)
-				for(int i = 0; i < 2; ++i) HIP_TRY(regrow(&M.ids[i], M.bin_cap * kBin, nb * kBin, s));
+			HIP_TRY(size_bin_arrays(ctx, M, nb));
 			M.bin_cap = nb;
 		}
 	}
@@ -344,23 +333,19 @@ int mpm_checkpoint_load(mpm_ctx* ctx, const void* buf, size_t bytes) {
 		HIP_TRY(hipMemcpyAsync(M.bins[r], in + L.bins[mi], sizeof(float) * (size_t) M.bincount_src * M.nch * kBin, hipMemcpyHostToDevice, s));
 		const std::vector<long long>& off = offs[mi];
 		if(h.pbc && M.bucketed) {
-			long long* d_off = nullptr;
-			int* d_packed	 = nullptr;
-			hipError_t e	 = dalloc(&d_off, (size_t) h.pbc + 1);
-			if(e == hipSuccess) e = dalloc(&d_packed, (size_t) M.bucketed);
+			DevBuf<long long> d_off;
+			DevBuf<int> d_packed, d_info;
+			hipError_t e = d_off.alloc((size_t) h.pbc + 1, s);
+			if(e == hipSuccess) e = d_packed.alloc((size_t) M.bucketed, s);
 			if(e == hipSuccess) e = hipMemcpyAsync(d_off, off.data(), sizeof(long long) * ((size_t) h.pbc + 1), hipMemcpyHostToDevice, s);
 			if(e == hipSuccess) e = hipMemcpyAsync(d_packed, in + L.lists[mi], sizeof(int) * (size_t) M.bucketed, hipMemcpyHostToDevice, s);
-			int* d_info = nullptr;
-			if(e == hipSuccess && M.pair) e = dalloc(&d_info, (size_t) h.pbc * kPairChunks);
+			if(e == hipSuccess && M.pair) e = d_info.alloc((size_t) h.pbc * kPairChunks, s);
 			if(e == hipSuccess && M.pair) e = hipMemcpyAsync(d_info, in + L.pairinfo[mi], sizeof(int) * (size_t) h.pbc * kPairChunks, hipMemcpyHostToDevice, s);
 			if(e == hipSuccess) {
 				unpack_lists_kernel<<<h.pbc, 64, 0, s>>>(ctx->g.ppb, M.size, M.row_of, d_off, M.list[M.list_in], d_packed, M.pair ? 1 : 0, M.pairinfo[0], d_info);
 				e = hipGetLastError();
 			}
 			if(e == hipSuccess) e = hipStreamSynchronize(s);
-			hipFree(d_off);
-			hipFree(d_packed);
-			hipFree(d_info);
 			if(e != hipSuccess) return fail(ctx, MPM_ERR_DEVICE, std::string("checkpoint: ") + hipGetErrorString(e));
 		}
 	}

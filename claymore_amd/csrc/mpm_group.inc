@@ -132,13 +132,9 @@ struct mpm_group {
 	ncclComm_t comm = nullptr;
 	LocalHub* hub	= nullptr;
 	int pad			= 0;// padded key-list length (rows of 3 ints, row 0 = true count) of the tagging all-gather
-	int* d_keys_mine = nullptr;
-	int* d_keys_all	 = nullptr;
-	int keys_pad	 = 0;
-	float* d_send	 = nullptr;
-	float* d_recv	 = nullptr;
-	size_t xcap		 = 0;// floats
-	float* d_scalar	 = nullptr;
+	DevBuf<int> d_keys_mine, d_keys_all;// 3 pad ints and world times that (grp_key_buffers): d_keys_all, allocated last, says what padding both hold
+	DevBuf<float> d_send, d_recv;// the same number of floats each (grp_halo_capacity): d_recv, allocated last, says how many both hold
+	DevBuf<float> d_scalar;
 	int send_counts[32] = {};
 	size_t offs[33]		= {};
 	int n_halo_blocks	= 0;
@@ -310,7 +306,7 @@ int grp_all_reduce_max(mpm_group* g, float* v) {
 
 int grp_key_buffers(mpm_group* g) {
 	if(g->hub && g->hub->have_kdone) {// (asynchronous in-process gather: the peers may still be reading d_keys_mine)
-		const bool realloc = !(g->keys_pad == g->pad && g->d_keys_mine);
+		const bool realloc = g->d_keys_all.n != 3 * (size_t) g->pad * g->world;
 		for(int p = 0; p < g->world; ++p)
 			if(p != g->rank && g->hub->ev_kdone[p]) {
 				if(realloc)
@@ -319,15 +315,12 @@ int grp_key_buffers(mpm_group* g) {
 					GRP_HIP(hipStreamWaitEvent(g->ctx->s_compute, g->hub->ev_kdone[p], 0));
 			}
 	}
-	if(g->keys_pad == g->pad && g->d_keys_mine) return MPM_OK;
+	if(g->d_keys_all.n == 3 * (size_t) g->pad * g->world) return MPM_OK;
 	GRP_HIP(hipStreamSynchronize(g->ctx->s_compute));
-	hipFree(g->d_keys_mine);
-	hipFree(g->d_keys_all);
-	g->d_keys_mine = g->d_keys_all = nullptr;
-	GRP_HIP(hipMalloc((void**) &g->d_keys_mine, sizeof(int) * 3 * (size_t) g->pad));
-	GRP_HIP(hipMalloc((void**) &g->d_keys_all, sizeof(int) * 3 * (size_t) g->pad * g->world));
-	GRP_HIP(hipMemsetAsync(g->d_keys_mine, 0, sizeof(int) * 3 * (size_t) g->pad, g->ctx->s_compute));
-	g->keys_pad = g->pad;
+	(void) g->d_keys_mine.reset();
+	(void) g->d_keys_all.reset();
+	GRP_HIP(g->d_keys_mine.alloc(3 * (size_t) g->pad, g->ctx->s_compute));
+	GRP_HIP(g->d_keys_all.alloc(3 * (size_t) g->pad * g->world, g->ctx->s_compute));
 	return MPM_OK;
 }
 
@@ -398,17 +391,16 @@ size_t grp_halo_offsets(mpm_group* g) {
 	return g->offs[g->world];
 }
 int grp_halo_capacity(mpm_group* g, size_t total) {
-	if(total <= g->xcap) return MPM_OK;
+	if(total <= g->d_recv.n) return MPM_OK;
 	if(g->hub && g->hub->have_done)// (asynchronous in-process exchange: no peer may still be reading the buffer that is about to go)
 		for(int p = 0; p < g->world; ++p)
 			if(p != g->rank && g->hub->ev_done[p]) GRP_HIP(hipEventSynchronize(g->hub->ev_done[p]));
 	GRP_HIP(hipDeviceSynchronize());
-	hipFree(g->d_send);
-	hipFree(g->d_recv);
-	g->d_send = g->d_recv = nullptr;
-	g->xcap				  = total + total / 2 + kHaloRow;
-	GRP_HIP(hipMalloc((void**) &g->d_send, sizeof(float) * g->xcap));
-	GRP_HIP(hipMalloc((void**) &g->d_recv, sizeof(float) * g->xcap));
+	(void) g->d_send.reset();
+	(void) g->d_recv.reset();
+	const size_t xcap = total + total / 2 + kHaloRow;
+	GRP_HIP(g->d_send.alloc(xcap, g->ctx->s_compute));
+	GRP_HIP(g->d_recv.alloc(xcap, g->ctx->s_compute));
 	return MPM_OK;
 }
 // asynchronous in-process exchange: the peers may still be reading d_send
@@ -426,7 +418,7 @@ int grp_wait_peers_done(mpm_group* g) {
 int grp_collect(mpm_group* g, int gid, hipStream_t s, bool counts_known = true) {
 	int est = 0;
 	for(int p = 0; p < g->world; ++p) est = std::max(est, p == g->rank ? 0 : g->send_counts[p]);
-	if(g->world > 1 && g->d_send && (est > 0 || !counts_known)) GRP_TRY(halo_collect(g->ctx, s, gid, 0, g->world, g->rank, est, g->d_send, g->xcap));
+	if(g->world > 1 && g->d_send && (est > 0 || !counts_known)) GRP_TRY(halo_collect(g->ctx, s, gid, 0, g->world, g->rank, est, g->d_send, g->d_recv.n));
 	return MPM_OK;
 }
 // the received blocks into grid gid (comm stream); the compute stream waits for them
@@ -478,7 +470,7 @@ int grp_halo_compute_half(mpm_group* g, const SubstepPlan& plan, int gid) {
 int grp_halo_comm_half(mpm_group* g, int gid, bool collect_again = false) {
 	mpm_ctx* ctx	   = g->ctx;
 	const size_t total = grp_halo_offsets(g);
-	if(total > g->xcap || collect_again) {// the counts outgrew the buffer the collect ran into (grow it), or the send lists were rebuilt after it ran: collect again (behind the interior launch, this once)
+	if(total > g->d_recv.n || collect_again) {// the counts outgrew the buffer the collect ran into (grow it), or the send lists were rebuilt after it ran: collect again (behind the interior launch, this once)
 		int rc = grp_halo_capacity(g, total);
 		if(rc || (rc = grp_collect(g, gid, ctx->s_compute))) return rc;
 		GRP_HIP(hipEventRecord(ctx->ev_halo, ctx->s_compute));
@@ -494,7 +486,7 @@ int grp_common_init(mpm_group* g) {
 	if(const char* e = getenv("MPM_GROUP_PAD_TIGHT")) g->tight_pad = e[0] == '1';
 	if(const char* e = getenv("MPM_GROUP_OVERLAP_TAG")) g->overlap_tag = e[0] != '0';
 	GRP_HIP(hipSetDevice(g->ctx->device));
-	GRP_HIP(hipMalloc((void**) &g->d_scalar, sizeof(float)));
+	GRP_HIP(g->d_scalar.alloc(1, g->ctx->s_compute));
 	for(SubstepEvents& ev: g->ev2)
 		for(hipEvent_t* e: {&ev.start, &ev.g2p2g_start, &ev.g2p2g_end, &ev.end}) GRP_HIP(hipEventCreate(e));
 	if(g->hub && g->early_exchange) {
@@ -627,11 +619,6 @@ void mpm_group_destroy(mpm_group* g) {
 		}
 		if(last) delete g->hub;
 	}
-	hipFree(g->d_keys_mine);
-	hipFree(g->d_keys_all);
-	hipFree(g->d_send);
-	hipFree(g->d_recv);
-	hipFree(g->d_scalar);
 	if(g->ev_sent) hipEventDestroy(g->ev_sent);
 	if(g->ev_done) hipEventDestroy(g->ev_done);
 	if(g->ev_keys) hipEventDestroy(g->ev_keys);
@@ -950,9 +937,9 @@ int mpm_group_particle_momentum(mpm_group* g, int model, double out[5]) {
 	memcpy(row + 2, mine, sizeof(mine));
 	GRP_HIP(hipSetDevice(ctx->device));
 	hipStream_t s = ctx->s_compute;
-	DevScratch<int> d_row, d_all;
-	GRP_HIP(d_row.alloc(kRow));
-	GRP_HIP(d_all.alloc((size_t) kRow * g->world));
+	DevBuf<int> d_row, d_all;
+	GRP_HIP(d_row.alloc(kRow, s));
+	GRP_HIP(d_all.alloc((size_t) kRow * g->world, s));
 	GRP_HIP(hipMemcpyAsync(d_row.p, row, sizeof(row), hipMemcpyHostToDevice, s));
 	const int grc = grp_all_gather(g, d_row.p, d_all.p, kRow, s);
 	if(grc) return rc ? grp_readout_fail(g, rc, mine_err) : grc;// (a group that a failed call left broken: this rank's own reason first)

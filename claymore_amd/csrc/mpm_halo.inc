@@ -164,10 +164,9 @@ __global__ __launch_bounds__(256) void halo_reduce_kernel(GridCfg cfg, int n, co
 
 static int halo_alloc(mpm_ctx* ctx) {
 	if(ctx->d_overlap) return MPM_OK;
-	const size_t cap = (size_t) ctx->g.cap;
-	HIP_TRY(dalloc(&ctx->d_overlap, cap + 1));
-	HIP_TRY(dalloc(&ctx->d_halo_list, cap + 1));
-	HIP_TRY(dalloc(&ctx->d_inner_list, cap + 1));
+	HIP_TRY(alloc_block_array(ctx, ctx->d_halo_list));
+	HIP_TRY(alloc_block_array(ctx, ctx->d_inner_list));
+	HIP_TRY(alloc_block_array(ctx, ctx->d_overlap));// (last: the three exist together)
 	// (the halo counters and the peers' key-list lengths live in the status block: they come back with the one read-back of a synchronisation)
 	for(int p = 0; p < 32; ++p) ctx->h_peer_rows[p] = 0;
 	return MPM_OK;
@@ -188,7 +187,7 @@ static int halo_send_lists(mpm_ctx* ctx, PeerSendLists* send, int peer0, int npe
 	*send = PeerSendLists {};
 	for(int p = peer0; p < peer0 + npeers; ++p) {
 		if(p == rank) continue;
-		if(!ctx->d_send_ids[p]) HIP_TRY(dalloc(&ctx->d_send_ids[p], (size_t) ctx->g.cap + 1));
+		if(!ctx->d_send_ids[p]) HIP_TRY(alloc_block_array(ctx, ctx->d_send_ids[p]));
 		send->ids[p] = ctx->d_send_ids[p];
 	}
 	return MPM_OK;

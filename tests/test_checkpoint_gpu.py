@@ -150,7 +150,8 @@ def test_checkpoint_hash_covers_the_constitutive_parameters(material, field, val
 
 
 def test_checkpoint_into_a_smaller_capacity_grows_it():
-    """The checkpoint needs more blocks than the loading context has: the load grows the capacity (check_capacity path)."""
+    """The checkpoint needs more blocks than the loading context has: the load grows the capacity in the steps of the growth rule
+    (reserve_blocks, the bins following), to exactly the capacity those steps arrive at."""
     # a sphere centred on a block corner occupies 2^3 particle blocks; two cells further along the diagonal it straddles 3^3
     dx = 1.0 / 64
     sc = {"name": "diag_sphere", "bits": 6, "dt": 1e-4, "config": {},
@@ -163,6 +164,7 @@ def test_checkpoint_into_a_smaller_capacity_grows_it():
     for _ in range(80):                      # the moving spheres straddle more blocks at some point
         a.run_fixed(5, sc["dt"])
         if a.counts().exterior_blocks > ebc0:
+            ebc_ckpt = a.counts().exterior_blocks
             ckpt = a.save_checkpoint().copy()
             break
     if ckpt is None:
@@ -174,10 +176,20 @@ def test_checkpoint_into_a_smaller_capacity_grows_it():
     sc["config"]["max_blocks"] = ebc0        # exactly what set-up needs
     b = build_engine(sc)
     b.initial_setup()
-    cap0, _, _ = b.capacity()
+    cap0, _, ev0 = b.capacity()
     assert cap0 == ebc0
     b.load_checkpoint(ckpt)
-    assert b.capacity()[0] > cap0
+    # the capacity the growth rule arrives at, step by step (c -> min(blocks of the domain, 3/2 c + 1)), from cap0 until it holds the longer of the
+    # checkpoint's two key lists: the current numbering's (the exterior block count read above) and the previous one's (header words 8 and 9)
+    ebc_saved, prev_saved = (int(v) for v in np.frombuffer(ckpt.tobytes()[32:40], dtype=np.int32))
+    assert ebc_saved == ebc_ckpt > ebc0
+    need = max(ebc_saved, prev_saved)
+    want_cap, steps = cap0, 0
+    while want_cap < need:
+        want_cap, steps = min(64 ** 3 // 64, want_cap * 3 // 2 + 1), steps + 1
+    cap1, bins1, ev1 = b.capacity()
+    print("checkpoint into a smaller capacity: (capacity, bin capacity, growth_events) = (%d, %s, %d), need %d, cap0 %d" % (cap1, bins1[:1], ev1, need, cap0))
+    assert cap1 > cap0 and cap1 == want_cap and ev1 - ev0 >= steps >= 1, (cap0, need, cap1, want_cap, ev0, ev1, steps)
     b.run_fixed(10, sc["dt"])
     ok, err = _close(b.retrieve_positions(0), want, 2e-6)
     assert ok, err

@@ -480,6 +480,74 @@ def test_group_substep_reports_this_ranks_max_velocity():
         assert all(3.9 < v < 4.2 for v in mv), mv                   # |v|^2 = 2^2 (+ a few mm/s of gravity)
 
 
+def _run_growth_ranks(parts, calls, per_call, dt):
+    """One in-process group over the per-rank scenes `parts`, `calls` x run_fixed(per_call).  Per rank: the exterior block count at set-up,
+    its peak at the calls' ends, capacity() after set-up and at the end, the diagnostics, the positions per model."""
+    world = len(parts)
+    lg = LocalGroup(world)
+    ranks = [MgspGroupRank(parts[r], r, world, device=0, local_group=lg, prepartitioned=True) for r in range(world)]
+    lg.create()
+    out, errors = [None] * world, []
+
+    def work(r):
+        try:
+            sim = ranks[r]
+            sim.initial_setup()
+            ebc0 = peak = sim.eng.counts().exterior_blocks
+            cap0 = sim.eng.capacity()
+            for _ in range(calls):
+                sim.run_fixed(per_call, dt)
+                peak = max(peak, sim.eng.counts().exterior_blocks)
+            d = sim.eng.diagnostics()
+            out[r] = {"ebc0": ebc0, "peak": peak, "cap0": cap0, "cap1": sim.eng.capacity(), "lost": d.lost_particles, "dropped": d.dropped_particles,
+                      "xyz": [sim.eng.retrieve_positions(m) for m in range(len(sim.eng.models))]}
+        except Exception as e:  # noqa: BLE001
+            errors.append(repr(e))
+
+    th = [threading.Thread(target=work, args=(r,)) for r in range(world)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join(timeout=300)
+    for r in ranks:
+        r.close()
+    assert not errors, errors
+    return out
+
+
+def test_a_grouped_rank_grows_its_block_capacity_inside_run_fixed():
+    """Block-capacity growth of a grouped context: besides the arrays every context has it regrows the halo lists (overlap marks, halo and
+    interior lists) and the per-peer send lists.  The scene of test_capacity_grows_inside_a_long_run_between_windows (two touching spheres
+    flying apart: about 40 % more exterior blocks over 300 substeps) cut for 2 ranks, every rank 70 % full at set-up - below the 3/4 mark - in
+    one mpm_group_run_fixed call; same trajectory as the same group with room to spare."""
+    from claymore_amd.mgsp import partition_scene
+    world, nsteps = 2, 300
+    sc = scenes.two_spheres(bits=6, radius_cells=5.0, gap_cells=0.5, speed=-3.0)
+    nm = len(sc["models"])
+
+    def parts(max_blocks=None):
+        ps = [partition_scene(sc, r, world) for r in range(world)]
+        for r, p in enumerate(ps):
+            p["config"] = dict(sc["config"], **({"max_blocks": max_blocks[r]} if max_blocks else {}))
+        return ps
+    roomy = _run_growth_ranks(parts(), 30, nsteps // 30, sc["dt"])
+    tight = _run_growth_ranks(parts([int(o["ebc0"] / 0.70) for o in roomy]), 1, nsteps, sc["dt"])
+    print("grouped growth: roomy (ebc0, peak) %s; tight capacity (blocks, bins, events) at set-up %s, at the end %s" % (
+        [(o["ebc0"], o["peak"]) for o in roomy], [o["cap0"] for o in tight], [o["cap1"] for o in tight]))
+    must = [r for r in range(world) if roomy[r]["peak"] > tight[r]["cap0"][0] * 3 // 4]      # these ranks will have to grow
+    assert all(o["cap0"][2] == 0 for o in tight) and must, [(o["ebc0"], o["peak"]) for o in roomy]
+    for r in must:
+        assert tight[r]["cap1"][2] >= 1 and tight[r]["cap1"][0] > tight[r]["cap0"][0], (r, tight[r]["cap0"], tight[r]["cap1"])
+    assert all(o["lost"] == 0 and o["dropped"] == 0 for o in roomy + tight)
+    for m in range(nm):
+        want = np.concatenate([o["xyz"][m] for o in roomy]).astype(np.float64)
+        got = np.concatenate([o["xyz"][m] for o in tight]).astype(np.float64)
+        assert got.shape == want.shape
+        idx, _ = match(want, got)
+        rel = np.abs(got[idx] - want).max(axis=1) / np.abs(want).max(axis=1)
+        assert rel.max() < 2e-6, (m, rel.max())
+
+
 @pytest.fixture(scope="session")
 def rccl_double_library(tmp_path_factory):
     """Build tests/rccl_double/rccl_double.cpp (an in-process double of the RCCL calls the group driver binds) with hipcc, once per session."""

@@ -71,6 +71,15 @@ class MeshFill(C.Structure):
     _fields_ = [("margin", C.c_float), ("lo", C.c_int * 3), ("hi", C.c_int * 3), ("use_box", C.c_int), ("reserved", C.c_int * 8)]
 
 
+STATE_F, STATE_B = 0, 1                # MPM_STATE_F, MPM_STATE_B
+STATE_KINDS = {"f": STATE_F, "b": STATE_B}
+
+
+class ParticleInit(C.Structure):
+    _fields_ = [("velocity", C.c_void_p), ("affine9", C.c_void_p), ("state9", C.c_void_p), ("logjp", C.c_void_p),
+                ("state_kind", C.c_int), ("reserved", C.c_int * 3)]
+
+
 LOAD_ROWS = 6                          # MPM_LOAD_ROWS
 LOAD_ROW_NAMES = ("field", "slot0", "slot1", "slot2", "slot3", "walls")
 
@@ -179,6 +188,8 @@ HIP_ONLY = {
     "sample_mesh": (_i, [_i, _vp, _sz, _vp, _sz, _P(MeshFill), _vp, _P(_sz), _i]),
     "add_model_mesh": (_i, [_vp, _i, _P(MaterialParams), _vp, _sz, _vp, _sz, _P(MeshFill), _fp, _ip, _P(_sz)]),
     "test_mesh_fill": (_i, [_i, _vp, _sz, _vp, _sz, _P(MeshFill), _P(C.c_double), _i]),
+    "add_model_particles": (_i, [_vp, _i, _P(MaterialParams), _vp, _sz, _fp, _P(ParticleInit), _ip]),
+    "set_model_velocity_field": (_i, [_vp, _i, _fp, _fp, _fp]),
     "checkpoint_size": (_i, [_vp, _P(_sz)]),
     "checkpoint_save": (_i, [_vp, _vp, _sz, _P(_sz)]),
     "checkpoint_load": (_i, [_vp, _vp, _sz]),

@@ -20,6 +20,7 @@
 #include "mpm_grid_isosurface.hpp"
 #include "mpm_collision_mesh.hpp"
 #include "mpm_mesh_fill.hpp"
+#include "mpm_particle_init.hpp"
 #include "mpm_particle_ids.hpp"
 #include "mpm_collider_loads.hpp"
 #include "mpm_storage.hpp"
@@ -51,6 +52,12 @@ struct Model {
 	size_t n	 = 0;
 	DevBuf<float> d_xyz;// initial particle array; also the staging buffer of retrieve
 	float v0[3]	 = {0, 0, 0};
+	// per-particle initial conditions (mpm_add_model_particles; mpm_particle_init.hpp): the caller's arrays in the order of d_xyz, null where not given,
+	// released when mpm_initial_setup returns; or a velocity field v0 + G (x - pivot) (mpm_set_model_velocity_field), never both a field and a velocity / affine array
+	DevBuf<float> d_init_velocity, d_init_affine, d_init_state, d_init_logjp;
+	int init_state_f = 0;// d_init_state holds F (MPM_STATE_F), else b as mpm_retrieve_state returns it
+	bool has_field	 = false;
+	VelocityField field {};
 	DevBuf<float> bins[2];
 	DevBuf<int> ids[2];// tracked contexts only (mpm_track_particle_ids): one int32 per bin slot, rolled and regrown with bins[] (mpm_particle_ids.hpp)
 	size_t bin_cap = 0;
@@ -533,11 +540,61 @@ const char* mpm_last_error(const mpm_ctx* ctx) {
 	return ctx ? ctx->err.c_str() : "null context";
 }
 
-int mpm_add_model(mpm_ctx* ctx, int material, const mpm_material_params* params, const float* xyz, size_t n, const float v0[3], int* model_id) {
+// The view of a model's per-particle arrays that the set-up kernels take.
+static ParticleInit particle_init_view(const Model& m) {
+	ParticleInit a;
+	a.velocity = m.d_init_velocity.n ? m.d_init_velocity.p : nullptr;
+	a.affine9  = m.d_init_affine.n ? m.d_init_affine.p : nullptr;
+	a.state9   = m.d_init_state.n ? m.d_init_state.p : nullptr;
+	a.logjp	   = m.d_init_logjp.n ? m.d_init_logjp.p : nullptr;
+	a.state_f  = m.init_state_f;
+	return a;
+}
+
+// mpm_add_model_particles' arrays: copied into buffers the model owns, then checked on the device by one reduction kernel (the host walks no row).
+static int stage_particle_init(mpm_ctx* ctx, Model& m, const mpm_particle_init* init) {
+	const char* who = "mpm_add_model_particles";
+	for(int r: init->reserved)
+		if(r) return fail(ctx, MPM_ERR_INVALID, std::string(who) + ": a reserved word of mpm_particle_init is not 0");
+	const bool fluid = m.material == MPM_J_FLUID;
+	if(init->state9 && init->state_kind != MPM_STATE_B && init->state_kind != MPM_STATE_F)
+		return fail(ctx, MPM_ERR_INVALID, std::string(who) + ": unknown state_kind " + std::to_string(init->state_kind) + " (MPM_STATE_B or MPM_STATE_F)");
+	if(!m.n) return MPM_OK;// (an empty model carries nothing)
+	hipStream_t s = ctx->s_compute;
+	const bool with_logjp = init->logjp && (m.material == MPM_SAND || m.material == MPM_NACC);// (ignored where the material has no log Jp)
+	struct {
+		const float* host;
+		DevBuf<float>* dev;
+		size_t per;
+	} cols[4] = {{init->velocity, &m.d_init_velocity, 3}, {init->affine9, &m.d_init_affine, 9}, {init->state9, &m.d_init_state, 9}, {with_logjp ? init->logjp : nullptr, &m.d_init_logjp, 1}};
+	for(auto& c: cols) {
+		if(!c.host) continue;
+		if(c.dev->alloc(c.per * m.n, s) != hipSuccess) return fail(ctx, MPM_ERR_CAPACITY, std::string(who) + ": no device memory for the per-particle arrays");
+		HIP_TRY(hipMemcpyAsync(c.dev->p, c.host, sizeof(float) * c.per * m.n, hipMemcpyHostToDevice, s));
+	}
+	m.init_state_f = init->state9 && init->state_kind == MPM_STATE_F ? 1 : 0;
+	const ParticleInit a = particle_init_view(m);
+	if(!a.velocity && !a.affine9 && !a.state9 && !a.logjp) return MPM_OK;
+	DevBuf<int> flag;
+	HIP_TRY(flag.alloc(1, s));
+	validate_particle_init_kernel<<<std::min(4096u, cdiv(m.n, 256)), 256, 0, s>>>(m.n, fluid, a, flag.p);
+	int bad = 0;
+	HIP_TRY(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	if(bad & kInitBadVelocity) return fail(ctx, MPM_ERR_INVALID, std::string(who) + ": velocity holds a value that is not finite");
+	if(bad & kInitBadAffine) return fail(ctx, MPM_ERR_INVALID, std::string(who) + ": affine9 holds a value that is not finite");
+	if(bad & kInitBadState) return fail(ctx, MPM_ERR_INVALID, std::string(who) + ": state9 holds a value that is not finite");
+	if(bad & kInitBadLogJp) return fail(ctx, MPM_ERR_INVALID, std::string(who) + ": logjp holds a value that is not finite");
+	if(bad & kInitNotPositive) return fail(ctx, MPM_ERR_INVALID, std::string(who) + (fluid ? ": state9 holds a J that is not strictly positive" : ": state9 holds a |b00|, b11 or b22 that is not strictly positive"));
+	return MPM_OK;
+}
+
+static int add_model(mpm_ctx* ctx, const char* who_name, int material, const mpm_material_params* params, const float* xyz, size_t n, const float v0[3], const mpm_particle_init* init, int* model_id) {
 	if(!ctx) return MPM_ERR_INVALID;
-	if(!params) return fail(ctx, MPM_ERR_INVALID, "mpm_add_model: material parameters are missing");
-	if(ctx->ready) return fail(ctx, MPM_ERR_INVALID, "mpm_add_model: models must be added before mpm_initial_setup");
-	if(!xyz && n) return fail(ctx, MPM_ERR_INVALID, "mpm_add_model: positions are missing");
+	const std::string who = who_name;
+	if(!params) return fail(ctx, MPM_ERR_INVALID, who + ": material parameters are missing");
+	if(ctx->ready) return fail(ctx, MPM_ERR_INVALID, who + ": models must be added before mpm_initial_setup");
+	if(!xyz && n) return fail(ctx, MPM_ERR_INVALID, who + ": positions are missing");
 	if(material < 0 || material > 3) return fail(ctx, MPM_ERR_INVALID, "unknown material");
 	if((int) ctx->models.size() >= kMaxModels) return fail(ctx, MPM_ERR_CAPACITY, "too many models");
 	HIP_TRY(hipSetDevice(ctx->device));
@@ -553,8 +610,40 @@ int mpm_add_model(mpm_ctx* ctx, int material, const mpm_material_params* params,
 		HIP_TRY(hipMemcpyAsync(m.d_xyz, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, ctx->s_compute));
 		HIP_TRY(hipStreamSynchronize(ctx->s_compute));
 	}
+	if(init)// (a refused call changes nothing: m goes with this scope)
+		if(int rc = stage_particle_init(ctx, m, init)) return rc;
 	if(model_id) *model_id = (int) ctx->models.size();
 	ctx->models.push_back(std::move(m));
+	return MPM_OK;
+}
+
+int mpm_add_model(mpm_ctx* ctx, int material, const mpm_material_params* params, const float* xyz, size_t n, const float v0[3], int* model_id) {
+	return add_model(ctx, "mpm_add_model", material, params, xyz, n, v0, nullptr, model_id);
+}
+
+int mpm_add_model_particles(mpm_ctx* ctx, int material, const mpm_material_params* params, const float* xyz, size_t n, const float v0[3], const mpm_particle_init* init, int* model_id) {
+	return add_model(ctx, init ? "mpm_add_model_particles" : "mpm_add_model", material, params, xyz, n, v0, init, model_id);
+}
+
+int mpm_set_model_velocity_field(mpm_ctx* ctx, int model, const float v0[3], const float grad9[9], const float pivot[3]) {
+	if(!ctx) return MPM_ERR_INVALID;
+	const std::string who = "mpm_set_model_velocity_field";
+	if(ctx->ready) return fail(ctx, MPM_ERR_INVALID, who + ": the field is set before mpm_initial_setup");
+	if(model < 0 || model >= (int) ctx->models.size()) return fail(ctx, MPM_ERR_INVALID, who + ": no model " + std::to_string(model));
+	Model& m = ctx->models[model];
+	if(m.d_init_velocity.n || m.d_init_affine.n) return fail(ctx, MPM_ERR_INVALID, who + ": the model was added with a velocity or affine9 array");
+	VelocityField f {};
+	for(int d = 0; d < 3; ++d) f.v0[d] = v0 ? v0[d] : 0.f, f.pivot[d] = pivot ? pivot[d] : 0.f;
+	for(int d = 0; d < 9; ++d) f.G[d] = grad9 ? grad9[d] : 0.f;
+	for(float x: f.v0)
+		if(!std::isfinite(x)) return fail(ctx, MPM_ERR_INVALID, who + ": v0 is not finite");
+	for(float x: f.G)
+		if(!std::isfinite(x)) return fail(ctx, MPM_ERR_INVALID, who + ": grad9 is not finite");
+	for(float x: f.pivot)
+		if(!std::isfinite(x)) return fail(ctx, MPM_ERR_INVALID, who + ": pivot is not finite");
+	m.field		= f;
+	m.has_field = true;
+	for(int d = 0; d < 3; ++d) m.v0[d] = f.v0[d];
 	return MPM_OK;
 }
 
@@ -674,7 +763,10 @@ int mpm_initial_setup(mpm_ctx* ctx) {
 		if(m.n) bucket_particles_kernel<<<cdiv(m.n, 256), 256, 0, s>>>(g, m.n, m.d_xyz, P.table, m.out_count, m.list[1], ctx->d_status);
 		if(pbc) {
 			init_bins_kernel<<<cdiv(pbc, 256), 256, 0, s>>>(pbc, m.out_count, m.size, m.row_of, m.binoff[r], m.binoff[n], &ctx->d_status[ST_BINS0 + mi]);
-			fill_bins_kernel<<<pbc, 256, 0, s>>>(g, m.nch, m.mc.log_jp0, m.d_xyz, m.list[1], m.size, m.binoff[r], m.bins[r], m.list[0]);
+			if(m.d_init_state.n || m.d_init_logjp.n)// a per-particle material state (mpm_particle_init.hpp)
+				fill_bins_state_kernel<<<pbc, 256, 0, s>>>(g, m.nch, m.mc.log_jp0, m.d_xyz, m.list[1], m.size, m.binoff[r], m.bins[r], m.list[0], particle_init_view(m));
+			else
+				fill_bins_kernel<<<pbc, 256, 0, s>>>(g, m.nch, m.mc.log_jp0, m.d_xyz, m.list[1], m.size, m.binoff[r], m.bins[r], m.list[0]);
 			if(ctx->track_ids) fill_ids_kernel<<<pbc, 256, 0, s>>>(g.ppb, m.list[1], m.size, m.binoff[r], m.ids[r]);
 		}
 		m.list_in = 0;
@@ -699,13 +791,24 @@ int mpm_initial_setup(mpm_ctx* ctx) {
 	HIP_TRY(hipMemcpyAsync(ctx->part[r].count, P.count, sizeof(int), hipMemcpyDeviceToDevice, s));
 	// rasterize (gmpm_simulator.cuh:763-771)
 	HIP_TRY(hipMemsetAsync(ctx->grid[0], 0, sizeof(float) * 256 * (size_t) ctx->nbc, s));
-	for(auto& m: ctx->models)// (m.list[1] still holds the particle ids by block that bucket_particles_kernel wrote; every particle of the model is in a block: ST_LOST was checked above)
-		if(m.n && pbc) rasterize_blocks_kernel<<<pbc, 256, 0, s>>>(g, m.d_xyz, m.list[1], m.size, ctx->part[r].keys, ctx->part[r].table, ctx->grid[0], m.mc.mass, m.v0[0], m.v0[1], m.v0[2]);
+	for(auto& m: ctx->models) {// (m.list[1] still holds the particle ids by block that bucket_particles_kernel wrote; every particle of the model is in a block: ST_LOST was checked above)
+		if(!m.n || !pbc) continue;
+		VelocityField f = m.field;
+		for(int d = 0; d < 3; ++d) f.v0[d] = m.v0[d];
+		if(m.has_field)// per-particle velocities (mpm_particle_init.hpp): from a field, or from the model's arrays
+			rasterize_particles_kernel<true><<<pbc, 256, 0, s>>>(g, m.d_xyz, m.list[1], m.size, ctx->part[r].keys, ctx->part[r].table, ctx->grid[0], m.mc.mass, ParticleInit {}, f);
+		else if(m.d_init_velocity.n || m.d_init_affine.n)
+			rasterize_particles_kernel<false><<<pbc, 256, 0, s>>>(g, m.d_xyz, m.list[1], m.size, ctx->part[r].keys, ctx->part[r].table, ctx->grid[0], m.mc.mass, particle_init_view(m), f);
+		else
+			rasterize_blocks_kernel<<<pbc, 256, 0, s>>>(g, m.d_xyz, m.list[1], m.size, ctx->part[r].keys, ctx->part[r].table, ctx->grid[0], m.mc.mass, m.v0[0], m.v0[1], m.v0[2]);
+	}
 	// the first G2P2G: current == previous numbering (roll r), lists as filled above
 	rc = launch_prepare(ctx, PrepareFor::Setup);
 	if(rc) return rc;
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipStreamSynchronize(s));
+	for(auto& m: ctx->models)// the per-particle initial conditions have been used
+		for(DevBuf<float>* b: {&m.d_init_velocity, &m.d_init_affine, &m.d_init_state, &m.d_init_logjp}) (void) b->reset();
 	ctx->ready		   = true;
 	ctx->relaid		   = true;
 	ctx->grid_momentum = true;

@@ -1198,8 +1198,9 @@ __global__ __launch_bounds__(256) void fill_bins_kernel(GridCfg cfg, int nch, fl
 }
 // rasterize, mgmpm_kernels.cuh:153-219, block by block (round 6): one workgroup per particle block - the particles are bucketed by block when this
 // runs (ids[block][slot], size[block]) - sums the B-spline masses of the block's particles in an LDS image of the 8^3 node cube that starts at node
-// 4 * key of the block, and writes every touched node back with ONE global atomic per channel; the initial velocity is uniform per model, so the three
-// momentum channels are the mass times v0.  (A per-particle form with 27 x 4 global atomics per particle took 98.6 ms at 40 M particles and 253.7 ms at
+// 4 * key of the block, and writes every touched node back with ONE global atomic per channel; this kernel serves the models whose initial velocity is one v0, so the three
+// momentum channels are the mass times v0 - a model with per-particle velocities or a velocity field goes through rasterize_particles_kernel
+// (mpm_particle_init.hpp), which keeps this structure with four LDS images.  (A per-particle form with 27 x 4 global atomics per particle took 98.6 ms at 40 M particles and 253.7 ms at
 // 100 M - 40 % of a 110-substep profile run; it is gone: every particle reaches this kernel through a block, mpm_initial_setup rejects the others.)
 // Where a particle's stencil lands in the cube: node N = lround(x / dx), stencil base = N - 1, block key = (N - 2) / 4 (truncating, particle_block_key).
 //  - inside the domain (N >= 2) the block owns the cells N - 2 with (N - 2) / 4 == key, so the base is 1..4 in the cube and the stencil 1..6;

@@ -25,6 +25,12 @@ def stress_totals_dict(out):
     return {"count": int(out[0]), "stress_integral": np.array(out[1:7], dtype=np.float64), "max_von_mises": float(out[7])}
 
 
+def skew(omega):
+    """The 3 x 3 matrix W with W x = omega x x (float64)."""
+    wx, wy, wz = (float(x) for x in omega)
+    return np.array([[0.0, -wz, wy], [wz, 0.0, -wx], [-wy, wx, 0.0]])
+
+
 def _position_keys(xyz):
     """The position bits of every row as one sortable record."""
     x = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
@@ -100,17 +106,86 @@ class Engine:
         self._check(self.api.default_material(int(material), self.cfg.domain_bits, C.byref(p)))
         return p
 
-    def init_model(self, material, positions, v0=(0.0, 0.0, 0.0), params=None, **param_overrides):
+    def init_model(self, material, positions, v0=(0.0, 0.0, 0.0), params=None, velocity=None, affine=None, state=None, logjp=None,
+                   state_kind="b", **param_overrides):
+        """Add a model.  The four keyword arrays are its per-particle initial conditions (mpm_add_model_particles, HIP library only), in the
+        order of `positions`; with all of them None this is mpm_add_model.
+        velocity (n, 3): v_p in world units (None: v0 for every particle).  affine (n, 3, 3): the APIC matrix, affine[p, r, c] = C_rc as
+        retrieve_velocity(affine=True) returns it (None: 0).  state (n, 9) or (n, 3, 3): what retrieve_state returns - b = F F^T with the
+        reflection mark in the sign of entry 0, J in entry 0 for the J-fluid - with state_kind "b", or the deformation gradient
+        F[p, r, c] with state_kind "f" (None: stress-free).  logjp (n,): sand / NACC (None: the material's log_jp0)."""
         xyz = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
         p = params if params is not None else self.default_material(material)
         for k, v in param_overrides.items():
             setattr(p, k, v)
         v = (C.c_float * 3)(*[float(x) for x in v0])
         mid = C.c_int(-1)
-        self._check(self.api.add_model(self.ctx, int(material), C.byref(p), xyz.ctypes.data_as(C.c_void_p),
-                                       xyz.shape[0], v, C.byref(mid)))
-        self.models.append({"material": int(material), "n": xyz.shape[0], "params": p})
+        n = xyz.shape[0]
+        if velocity is None and affine is None and state is None and logjp is None:
+            self._check(self.api.add_model(self.ctx, int(material), C.byref(p), xyz.ctypes.data_as(C.c_void_p), n, v, C.byref(mid)))
+        else:
+            if not hasattr(self.api, "add_model_particles"):
+                raise EngineError(_ffi.MPM_ERR_INVALID, "init_model: per-particle initial conditions need the HIP library (this API has no add_model_particles)")
+            if state_kind not in _ffi.STATE_KINDS:
+                raise ValueError(f"init_model: state_kind {state_kind!r} ('b' or 'f')")
+            keep = []                                                    # the arrays live until the call returns
+
+            def col(a, width, name, transpose=False):
+                if a is None:
+                    return None
+                a = np.asarray(a, dtype=np.float32)
+                if a.size != n * width:
+                    raise ValueError(f"init_model: {name} holds {a.size} values for {n} particles ({n * width} expected)")
+                if transpose and a.ndim == 3:                            # [p, r, c] -> the library's column-major 9 floats (index 3 c + r)
+                    a = a.transpose(0, 2, 1)
+                a = np.ascontiguousarray(a).reshape(n, width)
+                keep.append(a)
+                return a.ctypes.data
+            init = _ffi.ParticleInit()
+            init.velocity = col(velocity, 3, "velocity")
+            init.affine9 = col(affine, 9, "affine", transpose=True)
+            init.state9 = col(state, 9, "state", transpose=(state_kind == "f"))
+            init.logjp = col(logjp, 1, "logjp")
+            init.state_kind = _ffi.STATE_KINDS[state_kind]
+            self._check(self.api.add_model_particles(self.ctx, int(material), C.byref(p), xyz.ctypes.data_as(C.c_void_p), n, v, C.byref(init), C.byref(mid)))
+        self.models.append({"material": int(material), "n": n, "params": p})
         return mid.value
+
+    def set_model_velocity_field(self, model, v0=(0.0, 0.0, 0.0), grad=None, omega=None, pivot=(0.0, 0.0, 0.0)):
+        """Start a model that has been added (init_model or init_model_mesh, before initial_setup) in the linear velocity field
+        v_p = v0 + G (x_p - pivot), C_p = G (mpm_set_model_velocity_field, HIP library only).  grad: G as a 3 x 3 array, grad[r][c] = dv_r / dx_c;
+        omega: shorthand for the skew matrix of a rigid rotation, v = v0 + omega x (x - pivot).  Giving both adds them."""
+        if not hasattr(self.api, "set_model_velocity_field"):
+            raise EngineError(_ffi.MPM_ERR_INVALID, "set_model_velocity_field needs the HIP library")
+        G = np.zeros((3, 3), dtype=np.float64)
+        if grad is not None:
+            G += np.asarray(grad, dtype=np.float64).reshape(3, 3)
+        if omega is not None:
+            G += skew(omega)
+        g9 = (C.c_float * 9)(*[float(x) for x in G.T.ravel()])          # column-major
+        self._check(self.api.set_model_velocity_field(self.ctx, int(model), (C.c_float * 3)(*[float(x) for x in v0]), g9,
+                                                      (C.c_float * 3)(*[float(x) for x in pivot])))
+
+    def snapshot_models(self):
+        """The models as they stand, ready for build_engine: a list of {material, params, xyz, velocity, affine, state, logjp, state_kind: "b"}
+        per model, the rows of retrieve_state and retrieve_velocity(affine=True) joined on the position bits.  A context built from them -
+        with another GPU count, max_ppc or capacity - starts from the same positions and the same material state, bit for bit.  Its
+        velocities are RE-SAMPLED from the grid of the last P2G (what retrieve_velocity reads, before the next grid update): this is a
+        re-seed, not a restart - the bit-exact restart is the checkpoint (save_checkpoint / load_checkpoint)."""
+        out = []
+        for mi, m in enumerate(self.models):
+            xs, st, lj = self.retrieve_state(mi)
+            xv, vel, aff = self.retrieve_velocity(mi, affine=True)
+            ks, kv = _position_keys(xs), _position_keys(xv)
+            os_, ov = np.lexsort((ks["z"], ks["y"], ks["x"])), np.lexsort((kv["z"], kv["y"], kv["x"]))
+            if not np.array_equal(ks[os_], kv[ov]):
+                raise ValueError("snapshot_models: the two readouts hold different positions")
+            p = m["params"]
+            prm = {name: getattr(p, name) for name, _ in _ffi.MaterialParams._fields_ if name != "reserved"}
+            has_lj = m["material"] in (_ffi.SAND, _ffi.NACC)
+            out.append({"material": m["material"], "params": prm, "xyz": xs[os_].copy(), "velocity": vel[ov].copy(), "affine": aff[ov].copy(),
+                        "state": st[os_].copy(), "logjp": lj[os_].copy() if has_lj else None, "state_kind": "b"})
+        return out
 
     @staticmethod
     def _mesh_fill_args(vertices, faces, margin, box, who):
@@ -732,8 +807,12 @@ def build_engine(scene, device=0, api=None):
     for m in scene["models"]:
         if "mesh" in m:  # {"vertices", "faces"[, "margin", "box"]}: filled on the device (init_model_mesh)
             eng.init_model_mesh(m["material"], v0=m.get("v0", (0, 0, 0)), **m["mesh"], **m.get("params", {}))
-        else:
-            eng.init_model(m["material"], m["xyz"], m.get("v0", (0, 0, 0)), **m.get("params", {}))
+        else:  # "velocity", "affine", "state", "logjp" (+ "state_kind"): per-particle initial conditions, in the order of "xyz"
+            eng.init_model(m["material"], m["xyz"], m.get("v0", (0, 0, 0)), velocity=m.get("velocity"), affine=m.get("affine"), state=m.get("state"),
+                           logjp=m.get("logjp"), state_kind=m.get("state_kind", "b"), **m.get("params", {}))
+        if m.get("omega") is not None or m.get("velocity_gradient") is not None:  # a linear velocity field about "pivot"; "v0" is its constant part
+            eng.set_model_velocity_field(len(eng.models) - 1, m.get("v0", (0, 0, 0)), grad=m.get("velocity_gradient"), omega=m.get("omega"),
+                                         pivot=m.get("pivot", (0, 0, 0)))
     if scene.get("collision"):
         eng.set_collision_object(**{**scene["collision"], "animate": False})
     if scene.get("collision_mesh"):  # the level-set object from a triangle mesh (it and "collision" are one object: the later install wins)

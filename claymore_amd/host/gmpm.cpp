@@ -20,7 +20,8 @@
 // A top-level "collision_mesh" object installs the level-set collision object from an OBJ file (mpm_set_collision_mesh; in main below).
 // simulation.output_loads (default false): the load gauge runs (mpm_load_gauge) and `loads_frame[f].json` beside each frame holds, per row (the
 // level-set object, the four slots, the domain walls), the force and torque on the collider averaged over the frame, the touched-node count and
-// the elapsed time (mpm_load_gauge_read at the frame's end).
+// the elapsed time (mpm_load_gauge_read at the frame's end).  A model object may carry "omega": [x, y, z] or "velocity_gradient": [9 numbers, row-major] with an
+// optional "pivot": the model starts in the linear velocity field v = velocity + G (x - pivot) (model_field.hpp, mpm_set_model_velocity_field).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -36,6 +37,7 @@
 #include "../../include/claymore_amd.h"
 #include "mini_json.hpp"
 #include "particle_io.hpp"
+#include "model_field.hpp"
 
 namespace {
 
@@ -420,9 +422,13 @@ int main(int argc, char** argv) {
 			p.beta = num(m, "beta", p.beta);
 			p.xi   = num(m, "xi", p.xi);
 		}
+		// "velocity" is v0; "omega" / "velocity_gradient" (with an optional "pivot") make it the linear field of model_field.hpp
+		pio::ModelField field;
+		const int has_field = pio::parse_model_field(m, field);
+		if(has_field < 0) return 1;
 		float v0[3];
-		for(int d = 0; d < 3; ++d) v0[d] = (float) m["velocity"][d].number();
-		max_v0 = std::max(max_v0, std::sqrt(v0[0] * v0[0] + v0[1] * v0[1] + v0[2] * v0[2]));
+		for(int d = 0; d < 3; ++d) v0[d] = field.v0[d];
+		if(!has_field) max_v0 = std::max(max_v0, std::sqrt(v0[0] * v0[0] + v0[1] * v0[1] + v0[2] * v0[2]));
 		int id = -1;
 		pio::Points pts;
 		const std::string file = m["file"].string();
@@ -457,6 +463,14 @@ int main(int argc, char** argv) {
 			rc	= mpm_add_model(ctx, mat, &p, pts.empty() ? nullptr : pts[0].data(), pts.size(), v0, &id);
 			if(rc) die(ctx, rc);
 		}
+		if(has_field) {
+			if((rc = mpm_set_model_velocity_field(ctx, id, field.v0, field.grad9, field.pivot))) die(ctx, rc);
+			for(const auto& x: pts) {// (the first dt follows the fastest particle)
+				double v[3];
+				field.at(x.data(), v);
+				max_v0 = std::max(max_v0, (float) std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]));
+			}
+		}
 		std::printf("init %d-th model with %zu particles\n", id, pts.size());
 		const std::string frame0 = out_dir + "/model_id[" + std::to_string(id) + "]_frame[0].bgeo";
 		if(out_vel || out_stress || out_ids) {
@@ -464,7 +478,9 @@ int main(int argc, char** argv) {
 			std::vector<int32_t> id0(out_ids ? pts.size() : 0);// (the sampled points are the input array: id = index)
 			for(size_t i = 0; i < id0.size(); ++i) id0[i] = (int32_t) i;
 			for(size_t i = 0; i < pts.size(); ++i) {
-				for(int d = 0; d < 3 && out_vel; ++d) v[3 * i + d] = v0[d];
+				double vi[3] = {v0[0], v0[1], v0[2]};
+				if(has_field && out_vel) field.at(pts[i].data(), vi);
+				for(int d = 0; d < 3 && out_vel; ++d) v[3 * i + d] = (float) vi[d];
 				if(out_stress) s9[9 * i + 6] = 1.f;// J
 			}
 			pio::write_bgeo_frame(frame0, pts.empty() ? nullptr : pts[0].data(), pts.size(), out_vel ? v.data() : nullptr, out_stress ? s9.data() : nullptr, out_ids && !id0.empty() ? id0.data() : nullptr);

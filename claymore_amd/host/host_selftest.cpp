@@ -6,6 +6,7 @@
 
 #include "mini_json.hpp"
 #include "particle_io.hpp"
+#include "model_field.hpp"
 #include "../csrc/mpm_collision_mesh.hpp"
 #include "../csrc/mpm_mesh_fill.hpp"
 #if !defined(__HIPCC__)
@@ -16,6 +17,28 @@ struct float4 {
 #include "../csrc/mpm_collision_volume.hpp"
 
 int main(int argc, char** argv) {
+	if(argc == 3 && !std::strcmp(argv[1], "--model-field")) {// host_selftest --model-field '{"velocity": .., "omega": .., "pivot": ..}': a scene file's model object ->
+		// "field|none", then v0 (3), grad9 column-major (9), pivot (3) as gmpm hands them to mpm_set_model_velocity_field, and the velocity at (1, 2, 3)
+		mj::ValuePtr m;
+		try {
+			m = mj::parse(argv[2]);
+		} catch(const std::exception& e) {
+			std::cerr << "cannot parse the model object: " << e.what() << "\n";
+			return 2;
+		}
+		pio::ModelField f;
+		const int rc = pio::parse_model_field(*m, f);
+		if(rc < 0) return 1;
+		std::cout << (rc ? "field" : "none");
+		for(float x: f.v0) std::cout << " " << x;
+		for(float x: f.grad9) std::cout << " " << x;
+		for(float x: f.pivot) std::cout << " " << x;
+		const float at[3] = {1.f, 2.f, 3.f};
+		double v[3];
+		f.at(at, v);
+		std::cout << " " << v[0] << " " << v[1] << " " << v[2] << "\n";
+		return 0;
+	}
 	if(argc == 4 && !std::strcmp(argv[1], "--bgeo-from")) {// host_selftest --bgeo-from points.f32 out.bgeo: raw float32 xyz -> BGEO frame
 		std::ifstream in(argv[2], std::ios::binary | std::ios::ate);
 		if(!in) return 3;

@@ -38,6 +38,9 @@ PARTITION_SHAPE = None  # None: slabs along every model's longest axis; or a key
 ALIGN_TO_BLOCKS = False  # True (bench.py's strong scaling, the tools): the slabs' cut planes are moved to the nearest particle-block faces (scenes.split_slabs)
 
 
+PER_PARTICLE_KEYS = ("velocity", "affine", "state", "logjp")  # arrays of a model dict in the order of its "xyz" (Engine.init_model)
+
+
 def partition_scene(scene, rank, world, axis=None, shape=None, align=None):
     """Static particle partition: every model is cut into `world` equal-count pieces of the initial lattice.  Default: slabs along the
     model's LONGEST axis (axis=None): slabs as thick as possible keep the interfaces - the halo blocks that have to be computed first, sent
@@ -52,18 +55,22 @@ def partition_scene(scene, rank, world, axis=None, shape=None, align=None):
     sc = dict(scene)
     sc["models"] = []
     for m in scene["models"]:
-        if shape is not None:
-            mm = dict(m)
-            mm["xyz"] = scenes.split_boxes(m["xyz"], scenes.PARTITION_SHAPES[shape](world), block=block)[rank]
-            sc["models"].append(mm)
-            continue
-        ax = axis
-        if ax is None:
-            xyz = m["xyz"]
-            ax = int(np.argmax(xyz.max(axis=0) - xyz.min(axis=0))) if xyz.shape[0] else 0
-        part = scenes.split_slabs(m["xyz"], world, ax, block=block)[rank]
+        per = [k for k in PER_PARTICLE_KEYS if m.get(k) is not None]  # per-particle initial conditions are cut with the positions
         mm = dict(m)
-        mm["xyz"] = part
+        if shape is not None:
+            cut = scenes.split_boxes(m["xyz"], scenes.PARTITION_SHAPES[shape](world), block=block, return_index=bool(per))
+        else:
+            ax = axis
+            if ax is None:
+                xyz = m["xyz"]
+                ax = int(np.argmax(xyz.max(axis=0) - xyz.min(axis=0))) if xyz.shape[0] else 0
+            cut = scenes.split_slabs(m["xyz"], world, ax, block=block, return_index=bool(per))
+        if per:
+            mm["xyz"] = cut[0][rank]
+            for k in per:
+                mm[k] = np.asarray(m[k])[cut[1][rank]]
+        else:
+            mm["xyz"] = cut[rank]
         sc["models"].append(mm)
     return sc
 

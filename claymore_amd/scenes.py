@@ -133,14 +133,54 @@ def fluid_dam(bits=10, size_cells=(256, 192, 256), min_corner=(12, 12, 12)):
             "models": [{"material": J_FLUID, "xyz": lattice_box(bits, lo, hi), "v0": (0, 0, 0), "params": {}}]}
 
 
-def split_slabs(xyz, parts, axis=0, block=None, tolerance=0.10):
+def spinning_ball(bits=6, radius_cells=6.0, omega=(0.0, 0.0, 20.0), center=(0.5, 0.5, 0.5), v0=(0.0, 0.0, 0.0), youngs=5e3):
+    """A fixed-corotated sphere in free space (gravity 0) that starts in rigid rotation `omega` (rad/s) about its centre: the velocity field
+    v = v0 + omega x (x - centre), given to the engine as a model-level field (Engine.set_model_velocity_field)."""
+    prm = {"volume": _vol(bits), "youngs_modulus": youngs, "poisson_ratio": 0.4, "rho": 1e3}
+    return {"name": "spinning_ball", "bits": bits, "dt": 1e-4, "config": {"max_ppc": 128, "gravity": 0.0},
+            "models": [{"material": FIXED_COROTATED, "xyz": lattice_sphere(bits, center, radius_cells), "v0": tuple(v0), "omega": tuple(omega),
+                        "pivot": tuple(center), "params": prm}]}
+
+
+def sheared_block(bits=6, size_cells=(10, 8, 6), rate=15.0, v0=(0.25, 0.0, -0.5), youngs=5e3):
+    """A fixed-corotated block in the middle of the domain (gravity 0) that starts in the shear flow v = v0 + G (x - centre) with
+    G = rate * [[0, 1, 0], [0, 0, 0.5], [0, 0, 0]] (dv_x / dy = rate, dv_y / dz = rate / 2), a model-level field like spinning_ball's."""
+    n = 1 << bits
+    lo = np.array([(n - s) // 2 for s in size_cells])
+    hi = lo + np.array(size_cells)
+    centre = tuple(float(c) for c in (lo + hi - 1) * 0.5 / n)  # the lattice nodes lo .. hi - 1 carry the particles
+    G = [0.0, rate, 0.0, 0.0, 0.0, 0.5 * rate, 0.0, 0.0, 0.0]  # row-major: G[r][c] = dv_r / dx_c
+    prm = {"volume": _vol(bits), "youngs_modulus": youngs, "poisson_ratio": 0.4, "rho": 1e3}
+    return {"name": "sheared_block", "bits": bits, "dt": 1e-4, "config": {"max_ppc": 128, "gravity": 0.0},
+            "models": [{"material": FIXED_COROTATED, "xyz": lattice_box(bits, lo, hi), "v0": tuple(v0), "velocity_gradient": G, "pivot": centre,
+                        "params": prm}]}
+
+
+def model_velocity_field(m):
+    """(a, A) of a model dict's velocity field v = a + A x in float64 - A = "velocity_gradient" (row-major) + skew("omega"), a = v0 - A pivot -
+    or None for a model without one."""
+    if m.get("omega") is None and m.get("velocity_gradient") is None:
+        return None
+    A = np.zeros((3, 3))
+    if m.get("velocity_gradient") is not None:
+        A += np.asarray(m["velocity_gradient"], dtype=np.float64).reshape(3, 3)
+    if m.get("omega") is not None:
+        wx, wy, wz = (float(x) for x in m["omega"])
+        A += np.array([[0.0, -wz, wy], [wz, 0.0, -wx], [-wy, wx, 0.0]])
+    return np.asarray(m.get("v0", (0, 0, 0)), dtype=np.float64) - A @ np.asarray(m.get("pivot", (0, 0, 0)), dtype=np.float64), A
+
+
+def split_slabs(xyz, parts, axis=0, block=None, tolerance=0.10, return_index=False):
     """Static particle partition of MGSP: equal-count slabs of the initial lattice along `axis`.
 
     block = (origin, width): the particle blocks' faces along the axis lie at origin + k * width (block_faces()).  The equal-count cuts are then
     moved to the nearest face, so that no particle block is shared by two ranks at the start: a slab whose two cut planes pass through blocks
     owns two layers of half-filled blocks, and G2P2G's cost is per iteration of a block, not per particle (C3 cut 8 ways along y: 77 block layers,
     9.6 per rank - an equal-count slab touches 11 layers, an aligned one holds 9 or 10).  Kept only if no piece grows beyond (1 + tolerance) of
-    the equal share (and none is empty); otherwise the equal-count cut stands."""
+    the equal share (and none is empty); otherwise the equal-count cut stands.
+
+    return_index=True: (pieces, indices) - indices[i] the rows of `xyz` that piece i holds, in its order (pieces[i] == xyz[indices[i]]), so
+    that per-particle arrays (velocity, affine, state ...) can be split with the positions."""
     col = xyz[:, axis]
     n = xyz.shape[0]
     sorted_already = col.size < 2 or bool(np.all(col[1:] >= col[:-1]))  # the lattice samplers emit particles sorted along x
@@ -156,12 +196,20 @@ def split_slabs(xyz, parts, axis=0, block=None, tolerance=0.10):
         if sizes.min() > 0 and sizes.max() <= (1.0 + tolerance) * n / parts:
             bounds = snapped
         if order is not None:
-            return [np.ascontiguousarray(xyz[order[bounds[i]:bounds[i + 1]]]) for i in range(parts)]
-        return [np.ascontiguousarray(xyz[bounds[i]:bounds[i + 1]]) for i in range(parts)]
+            return _slab_pieces(xyz, [order[bounds[i]:bounds[i + 1]] for i in range(parts)], return_index)
+        return _slab_pieces(xyz, [slice(bounds[i], bounds[i + 1]) for i in range(parts)], return_index)
     if sorted_already:
-        return [np.ascontiguousarray(xyz[bounds[i]:bounds[i + 1]]) for i in range(parts)]
+        return _slab_pieces(xyz, [slice(bounds[i], bounds[i + 1]) for i in range(parts)], return_index)
     order = np.argsort(col, kind="stable")
-    return [np.ascontiguousarray(xyz[idx]) for idx in np.array_split(order, parts)]
+    return _slab_pieces(xyz, np.array_split(order, parts), return_index)
+
+
+def _slab_pieces(xyz, rows, return_index):
+    """split_slabs' return: the pieces xyz[rows[i]] (rows: slices or index arrays) and, if asked for, the rows as int64 index arrays."""
+    pieces = [np.ascontiguousarray(xyz[r]) for r in rows]
+    if not return_index:
+        return pieces
+    return pieces, [np.arange(r.start, r.stop, dtype=np.int64) if isinstance(r, slice) else np.asarray(r, dtype=np.int64) for r in rows]
 
 
 def block_faces(bits):
@@ -171,14 +219,23 @@ def block_faces(bits):
     return 1.5 * dx, 4.0 * dx
 
 
-def split_boxes(xyz, shape, block=None):
+def split_boxes(xyz, shape, block=None, return_index=False):
     """Static particle partition into shape = (nx, ny, nz) equal-count boxes of the initial lattice: nx slabs along x, each cut into ny along
     y, each of those into nz along z; block: cut planes moved to particle-block faces (split_slabs) (the reference's scenarios put their per-GPU bodies side by side in x and z, Projects/MGSP/mgsp.cu:52-57,
-    :67-72; SURVEY 8(e): "slabs / octants").  Returns the nx * ny * nz particle arrays, x-major."""
+    :67-72; SURVEY 8(e): "slabs / octants").  Returns the nx * ny * nz particle arrays, x-major; return_index=True: (arrays, indices) with
+    arrays[i] == xyz[indices[i]] (split_slabs)."""
     parts = [xyz]
+    index = [np.arange(xyz.shape[0], dtype=np.int64)] if return_index else None
     for axis, n in enumerate(shape):
-        parts = [q for p in parts for q in split_slabs(p, n, axis, block=block)] if n > 1 else parts
-    return parts
+        if n <= 1:
+            continue
+        if return_index:
+            cut = [split_slabs(p, n, axis, block=block, return_index=True) for p in parts]
+            index = [rows[sub] for rows, (_, subs) in zip(index, cut) for sub in subs]
+            parts = [q for pieces, _ in cut for q in pieces]
+        else:
+            parts = [q for p in parts for q in split_slabs(p, n, axis, block=block)]
+    return (parts, index) if return_index else parts
 
 
 PARTITION_SHAPES = {  # name -> world size -> (nx, ny, nz); "octants" halves every axis it can (x first: 2 -> x, 4 -> x z, 8 -> x y z)

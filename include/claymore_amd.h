@@ -491,6 +491,41 @@ int mpm_add_model_mesh(mpm_ctx* ctx, int material, const mpm_material_params* pa
  * tiles decided from their centre, classify ms, scan ms, emit ms, 0, 0}. */
 int mpm_test_mesh_fill(int domain_bits, const float* verts, size_t nv, const int32_t* tris, size_t nt, const mpm_mesh_fill* opt /* may be NULL */, double* out8, int device);
 
+/* Extension (the reference starts every particle at rest in its material, all with one velocity): per-particle initial conditions - the
+ * inverse of the readouts above.  Set-up only: a model given none of this is set up exactly as mpm_add_model's.  HIP library only.
+ * mpm_add_model_particles is mpm_add_model with up to four arrays in the order of xyz, copied to the device during the call, checked there
+ * and released when mpm_initial_setup returns:
+ *   velocity  v_p in world units (NULL: v0 for every particle);
+ *   affine9   the APIC matrix C_p, column-major exactly as mpm_retrieve_velocity returns it: affine9[9*i + 3*c + r] = C_rc (NULL: 0).
+ *             The set-up P2G gives node i the momentum m w_ip (v_p + C_p (x_i - x_p)), x_i - x_p in world units;
+ *   state9    the inverse of mpm_retrieve_state (NULL: the stress-free state).  Solids with state_kind MPM_STATE_B: the symmetric b = F F^T as
+ *             mpm_retrieve_state returns it, the sign of entry 0 marking a reflected F; the entries [0] [4] [8] and [1] [2] [5] are read and
+ *             stored verbatim, so readout -> re-seed -> readout is bit for bit.  Solids with MPM_STATE_F: F in the layout of mpm_test_stress's
+ *             input (column-major); the library forms b = F F^T in float32 and sets the mark where det F < 0.  MPM_J_FLUID: state9[9*i] is J
+ *             with MPM_STATE_B, and J = det of the 3 x 3 with MPM_STATE_F;
+ *   logjp     log Jp (MPM_SAND / MPM_NACC only, ignored for the other materials; NULL: params->log_jp0).
+ * init == NULL is mpm_add_model.
+ * mpm_set_model_velocity_field gives a model that has been added, by any of the three calls - mpm_add_model_mesh's models included, whose
+ * positions never reach the host -, the linear field v_p = v0 + G (x_p - pivot), C_p = G, evaluated in the set-up kernel (grad9 column-major:
+ * grad9[3*c + r] = G_rc; NULL pointers read as zeros).  It replaces the model's v0; APIC with quadratic B-splines carries a linear field
+ * exactly, so mpm_retrieve_velocity returns the field and G right after set-up (a spinning or shearing body).
+ * Errors: MPM_ERR_INVALID, mpm_last_error says which, and a refused call changes nothing - after mpm_initial_setup; a reserved word that is
+ * not 0; an unknown state_kind; a value that is not finite in any array or in the field; |b00|, b11, b22 or J not strictly positive; a
+ * velocity field on a model that was added with a velocity or affine9 array; a model number that does not exist.  MPM_ERR_CAPACITY when the
+ * device cannot hold the arrays. */
+typedef struct mpm_particle_init {
+	const float* velocity; /* n*3, world units.  NULL: v0 for every particle */
+	const float* affine9;  /* n*9, C_p, column-major exactly as mpm_retrieve_velocity returns it
+							  (affine9[9*i + 3*c + r] = C_rc).  NULL: 0 */
+	const float* state9;   /* n*9.  NULL: stress-free (mpm_add_model's state) */
+	const float* logjp;	   /* n, SAND / NACC only.  NULL: params->log_jp0 */
+	int state_kind;		   /* what state9 holds for FC / SAND / NACC: MPM_STATE_B or MPM_STATE_F */
+	int reserved[3];	   /* must be 0 */
+} mpm_particle_init;
+int mpm_add_model_particles(mpm_ctx* ctx, int material, const mpm_material_params* params, const float* xyz, size_t n, const float v0[3],
+							const mpm_particle_init* init /* NULL == mpm_add_model */, int* model_id);
+int mpm_set_model_velocity_field(mpm_ctx* ctx, int model, const float v0[3], const float grad9[9] /* column-major */, const float pivot[3]);
+
 /* Current capacities and the number of times check_capacity() (gmpm_simulator.cuh:283-300) has grown them: blocks
  * (exterior count limit), bins per model (bin_capacity[8]).  HIP library only. */
 int mpm_get_capacity(mpm_ctx* ctx, int64_t* block_capacity, int64_t* bin_capacity, int* growth_events);

@@ -88,6 +88,20 @@ class LoadOptions(C.Structure):
     _fields_ = [("has_pivot", C.c_int * LOAD_ROWS), ("pivot", C.c_float * 3 * LOAD_ROWS)]
 
 
+class RigidBody(C.Structure):
+    _fields_ = [("mass", C.c_float), ("inertia", C.c_float * 6), ("com", C.c_float * 3), ("gravity", C.c_int), ("lock", C.c_int),
+                ("force", C.c_float * 3), ("torque", C.c_float * 3), ("reserved", C.c_int * 8)]
+
+
+class RigidBodyState(C.Structure):
+    _fields_ = [("position", C.c_double * 3), ("orientation", C.c_double * 4), ("velocity", C.c_double * 3), ("omega", C.c_double * 3),
+                ("angular_momentum", C.c_double * 3), ("last_impulse", C.c_double * 3), ("last_angular_impulse", C.c_double * 3),
+                ("last_touched_mass", C.c_double), ("max_mass_ratio", C.c_double), ("last_touched_nodes", C.c_int64), ("updates", C.c_int64)]
+
+
+BODY_LOCKS = {"x": 1, "y": 2, "z": 4, "rx": 8, "ry": 16, "rz": 32}
+
+
 class Counts(C.Structure):
     _fields_ = [("particle_blocks", C.c_int), ("neighbor_blocks", C.c_int), ("exterior_blocks", C.c_int),
                 ("model_count", C.c_int), ("bins", C.c_int64 * 8), ("particles", C.c_int64 * 8)]
@@ -171,6 +185,11 @@ HIP_ONLY = {
     "collider_contacts": (_i, [_vp, _f, _vp, _vp, _P(_sz)]),
     "load_gauge": (_i, [_vp, _i, _P(LoadOptions)]),
     "load_gauge_read": (_i, [_vp, _P(C.c_double * 8), _P(C.c_double), _ip, _i]),
+    "set_collider_body": (_i, [_vp, _i, _P(RigidBody)]),
+    "get_collider_body": (_i, [_vp, _i, _P(RigidBody), _P(RigidBodyState)]),
+    "set_collider_body_state": (_i, [_vp, _i, _P(C.c_double), _P(C.c_double), _P(C.c_double), _P(C.c_double)]),
+    "shape_mass_properties": (_i, [_P(CollisionShape), _f, _P(RigidBody)]),
+    "mesh_mass_properties": (_i, [_vp, _sz, _vp, _sz, _f, _P(RigidBody)]),
     "halo_dump": (_i, [_vp, _vp, _vp, _ip, _vp]),
     "dump_block_rows": (_i, [_vp, _i, _vp, _P(_sz)]),
     "set_collision_clock": (_i, [_vp, _i, _f]),

@@ -23,6 +23,7 @@
 #include "mpm_particle_init.hpp"
 #include "mpm_particle_ids.hpp"
 #include "mpm_collider_loads.hpp"
+#include "mpm_rigid_body.hpp"
 #include "mpm_storage.hpp"
 
 using namespace mpm;
@@ -199,6 +200,16 @@ struct mpm_ctx {
 	mpm_load_options load_opt {};
 	DevBuf<double> d_load_partials;// kLoadGroups x [kLoadRows][kLoadSums]
 	DevBuf<double> d_load_acc;// kLoadAccDoubles
+	// rigid bodies (mpm_set_collider_body; mpm_rigid_body.hpp): bit s of body_mask = slot s is a body, its state, constants and float32 pose live in
+	// d_body (allocated at the first install, with the partials of grid_update_body_kernel); body_c / body_desc are the host's copies of the constants.
+	// frozen: slot s was a body and is prescribed again, at rest at frozen_pose[s] (until the next install over the slot)
+	int body_mask = 0;
+	DevBuf<BodyBlock> d_body;
+	DevBuf<double> d_body_partials;// kLoadGroups x [kLoadRows][kLoadSums]
+	BodyConst body_c[kMaxBodies] {};
+	mpm_rigid_body body_desc[kMaxBodies] {};
+	bool frozen[kMaxBodies] = {};
+	CollisionPose frozen_pose[kMaxBodies] {};
 	int group_refs	   = 0;// mpm_group handles on this context (grp_common_init / mpm_group_destroy): the single-context readouts refuse it
 	DevBuf<int> d_send_ids[32];
 	int n_halo = 0, n_inner = 0;
@@ -355,7 +366,7 @@ static int still_launch_override(const char* e) {
 }
 
 // The installed colliders as the grid update that is being enqueued sees them, handed to `launch` in the type of their kernels: VolumeColliderArgs
-// with a volume in a slot, else TerrainArgs with a heightfield in a slot, ShapeArgs with analytic shapes alone, CollisionArgs with the level-set object alone, NoCollision without any.
+// with a volume in a slot (BodyArgs around it with a rigid body in a slot), else TerrainArgs with a heightfield in a slot, ShapeArgs with analytic shapes alone, CollisionArgs with the level-set object alone, NoCollision without any.
 // One pose per installed collider, all at the one clock's current time T (the start of the substep), by value; a running clock then moves
 // on, T = T + dt in one float32 addition (the drivers' own cur_time += dt).  Called once per applied grid update - by the stand-alone
 // kernel's launch or by the fused carry-over's, never by both.
@@ -373,11 +384,13 @@ static void with_collider(mpm_ctx* ctx, float dt, F&& launch) {
 	if(ctx->has_collision) a.col.field = CollisionArgs {ctx->collision, collision_pose(ctx->collision, T)};
 	for(int i = 0; i < ctx->shape_count; ++i) {
 		a.col.slot[i] = ctx->shape[i];
-		if(a.col.slot[i].shape.kind) a.col.slot[i].pose = collision_pose(a.col.slot[i].obj, T);
+		if(a.col.slot[i].shape.kind) a.col.slot[i].pose = ctx->frozen[i] ? ctx->frozen_pose[i] : collision_pose(a.col.slot[i].obj, T);
 	}
 	for(int i = 0; i < kMaxShapes; ++i) a.hf[i] = ctx->hf[i], va.vol[i] = ctx->vol[i];
 	if(ctx->collision_running) ctx->collision.time = T + dt;
-	if(ctx->vol_count)
+	if(ctx->body_mask)// (a body slot's pose and pivot are read from the device; its object travels with trans = com and no velocity)
+		launch(BodyArgs {va, ctx->d_body.p->pose, ctx->d_body.p->st, ctx->body_mask, 0});
+	else if(ctx->vol_count)
 		launch(va);
 	else if(ctx->hf_count)
 		launch(a);
@@ -828,7 +841,7 @@ static LoadPivots load_pivots(const mpm_ctx* ctx, const mpm_load_options* opt) {
 			if(opt && opt->has_pivot[r])
 				piv.p[r][d] = (double) opt->pivot[r][d];
 			else if(o)
-				piv.p[r][d] = (double) collision_pose(*o, T).shift[d];
+				piv.p[r][d] = (double) (r >= 1 && ctx->frozen[r - 1] ? ctx->frozen_pose[r - 1] : collision_pose(*o, T)).shift[d];
 		}
 	}
 	return piv;
@@ -839,7 +852,13 @@ static int launch_collider_loads(mpm_ctx* ctx, float dt, const mpm_load_options*
 	hipStream_t s		 = ctx->s_compute;
 	const LoadPivots piv = load_pivots(ctx, opt);
 	with_collider_at_clock(ctx, [&](const auto& col) {
-		collider_loads_kernel<<<kLoadGroups, 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, col, piv, partials);
+		if constexpr(std::is_same_v<std::decay_t<decltype(col)>, BodyArgs>) {// the same frame without the stores; a body row's default pivot is its x, read on the device
+			BodyArgs b = col;
+			for(int i = 0; i < kMaxBodies; ++i)
+				if(((b.mask >> i) & 1) && !(opt && opt->has_pivot[1 + i])) b.state_pivots |= 1 << i;
+			grid_update_body_kernel<BodyArgs, false><<<kLoadGroups, 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, b, piv, partials, nullptr);
+		} else
+			collider_loads_kernel<<<kLoadGroups, 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, col, piv, partials);
 	});
 	collider_loads_reduce_kernel<<<1, kLoadReduceThreads, 0, s>>>(partials, kLoadGroups, out, accumulate, (double) dt);
 	HIP_TRY(hipGetLastError());
@@ -859,12 +878,25 @@ static int launch_grid_update(mpm_ctx* ctx, float dt) {
 		return MPM_OK;// (the carry-over that applied this update has advanced the object's clock)
 	}
 	HIP_TRY(hipMemsetAsync(ctx->d_maxvel, 0, sizeof(unsigned) * kMaxVelSlots * kMaxVelStride, s));
+	if(ctx->body_mask) {// the update and its loads in one pass, then the bodies' step (mpm_rigid_body.hpp); the clock moves as for any applied update
+		const LoadPivots piv = load_pivots(ctx, nullptr);
+		with_collider(ctx, dt, [&](const auto& col) {
+			if constexpr(std::is_same_v<std::decay_t<decltype(col)>, BodyArgs>) {
+				BodyArgs b	   = col;
+				b.state_pivots = b.mask;
+				grid_update_body_kernel<BodyArgs, true><<<kLoadGroups, 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, b, piv, ctx->d_body_partials, ctx->d_maxvel);
+			}
+		});
+		body_step_kernel<<<1, kLoadReduceThreads, 0, s>>>(ctx->d_body_partials, kLoadGroups, ctx->d_body, ctx->body_mask, dt, ctx->cfg.gravity, &ctx->d_status[ST_NONFINITE]);
+		HIP_TRY(hipGetLastError());
+		return MPM_OK;
+	}
 	if(ctx->nbc) {
 		const int est = std::min(ctx->g.cap, ctx->nbc + ctx->nbc / 16 + 64);// (an estimate between two synchronisations of mpm_run_fixed)
 		with_collider(ctx, dt, [&](const auto& col) {
 			if constexpr(std::is_same_v<std::decay_t<decltype(col)>, NoCollision>)
 				grid_update_kernel<<<cdiv(est, 16), 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, ctx->d_maxvel);
-			else
+			else if constexpr(!std::is_same_v<std::decay_t<decltype(col)>, BodyArgs>)// (bodies took the branch above)
 				grid_update_collider_kernel<<<cdiv(est, 4), 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, col, ctx->d_maxvel);
 		});
 	}
@@ -1064,6 +1096,7 @@ static int launch_rebuild(mpm_ctx* ctx, const SubstepPlan& plan, StillLaunch* ta
 	Partition& Pn = ctx->part[n];
 	Partition& Pr = ctx->part[r];
 	const bool fused = fuse_dt > 0.f;
+	if(fused && ctx->body_mask) return fail(ctx, MPM_ERR_INTERNAL, "a grid update with a rigid body installed cannot ride on the carry-over (it has no BodyArgs instantiation)");
 	const int still = plan.offer_still && !ctx->relaid ? 1 : 0;
 	ctx->relaid		= false;
 	ctx->grid_momentum = !fused;// the carry-over below writes grid[0]: the P2G's mass and momentum, or (fused) the updated velocities
@@ -1092,7 +1125,8 @@ static int launch_rebuild(mpm_ctx* ctx, const SubstepPlan& plan, StillLaunch* ta
 	register_blocks_kernel<0, 1><<<rg8, 256, 0, s>>>(g, &st[ST_CNT_P], nullptr, &st[ST_CNT_N], &st[ST_PBC], Pn.table, Pn.keys, st, still);
 	if(fused) {
 		with_collider(ctx, fuse_dt, [&](const auto& col) {
-			carry_grid_kernel<true, std::decay_t<decltype(col)>><<<2048, 256, 0, s>>>(g, st, Pn.keys, Pr.table, ctx->grid[1], ctx->grid[0], fuse_dt, ctx->d_maxvel, col);
+			if constexpr(!std::is_same_v<std::decay_t<decltype(col)>, BodyArgs>)// (no driver fuses an update with a body installed: mpm_run_fixed)
+				carry_grid_kernel<true, std::decay_t<decltype(col)>><<<2048, 256, 0, s>>>(g, st, Pn.keys, Pr.table, ctx->grid[1], ctx->grid[0], fuse_dt, ctx->d_maxvel, col);
 		});
 		ctx->grid_preupdated = true;
 		ctx->preupdate_dt	 = fuse_dt;
@@ -1296,7 +1330,8 @@ int mpm_run_fixed(mpm_ctx* ctx, int nsteps, float dt) {
 		hipEvent_t* ev		 = &ctx->ev_ring[3 * in_window];
 		SubstepPlan plan {dt, dt};
 		plan.offer_still = still_on, plan.rebuild_clear = true;
-		if(it + 1 < nsteps && !ctx->load_gauge) plan.fuse_dt = dt;// the last substep leaves the canonical state behind; the load gauge reads every update's momenta first
+		// the last substep leaves the canonical state behind; the load gauge reads every update's momenta first; a rigid body's update is a kernel of its own
+		if(it + 1 < nsteps && !ctx->load_gauge && !ctx->body_mask) plan.fuse_dt = dt;
 		if(by_stamps)
 			plan.stamp_row = ctx->d_stamps + (size_t) in_window * kStampRow;// (its clear writes the previous substep's end)
 		else {
@@ -1529,6 +1564,8 @@ static int install_slot(mpm_ctx* ctx, int slot, SlotOccupant& o, const mpm_colli
 		ctx->vol[slot]		= Volume {};
 		ctx->vol_desc[slot] = mpm_collision_volume {};
 		ctx->shape[slot]	= ShapeSlot {};
+		ctx->body_mask &= ~(1 << slot);
+		ctx->frozen[slot] = false;
 		count_slots(ctx);
 		return fail(ctx, MPM_ERR_DEVICE, std::string("collision slot: freeing the old table -> ") + hipGetErrorString(e) + " (the slot is now empty)");
 	}
@@ -1539,6 +1576,8 @@ static int install_slot(mpm_ctx* ctx, int slot, SlotOccupant& o, const mpm_colli
 	if(o.shape.shape.kind == kShapeVolume) ctx->vol[slot].table = ctx->slot_table[slot];
 	ctx->vol_desc[slot]	   = o.desc;
 	ctx->shape[slot]	   = o.shape;// (kind 0: empty)
+	ctx->body_mask &= ~(1 << slot);// any install over a slot, or emptying it, removes its rigid body
+	ctx->frozen[slot]	   = false;
 	ctx->collision_running = false;// installing or removing a collider stops the clock
 	if(obj) ctx->collision.time = obj->time;
 	count_slots(ctx);
@@ -2557,6 +2596,126 @@ int mpm_load_gauge_read(mpm_ctx* ctx, double out[MPM_LOAD_ROWS][8], double* elap
 		memcpy(&count, &acc[kLoadRows * kLoadSums + 1], sizeof(count));
 		*updates = (int) std::min<long long>(count, INT32_MAX);
 	}
+	return MPM_OK;
+}
+
+// Rigid bodies (mpm_rigid_body.hpp).  Every check and every allocation comes before the first change: a refused call changes nothing.
+static bool is_body(const mpm_ctx* ctx, int slot) {
+	return slot_ok(slot) && ((ctx->body_mask >> slot) & 1);
+}
+static void fill_rigid_body(mpm_rigid_body* out, double mass, const double (&I6)[6], const double (&com)[3]) {
+	*out	  = mpm_rigid_body {};
+	out->mass = (float) mass;
+	for(int i = 0; i < 6; ++i) out->inertia[i] = (float) I6[i];
+	for(int d = 0; d < 3; ++d) out->com[d] = (float) com[d];
+	out->gravity = 1;
+}
+int mpm_set_collider_body(mpm_ctx* ctx, int slot, const mpm_rigid_body* body) {
+	static_assert(sizeof(mpm_rigid_body_state) == sizeof(BodyState) && offsetof(mpm_rigid_body_state, updates) == offsetof(BodyState, updates), "the ABI's state is the kernels'");
+	if(!ctx) return MPM_ERR_INVALID;
+	if(!slot_ok(slot)) return fail(ctx, MPM_ERR_INVALID, "mpm_set_collider_body: slot outside 0..3");
+	HIP_TRY(hipSetDevice(ctx->device));
+	hipStream_t s = ctx->s_compute;
+	if(!body) {// prescribed again: at rest, at the pose the body has reached
+		if(!is_body(ctx, slot)) return fail(ctx, MPM_ERR_INVALID, "mpm_set_collider_body: the slot holds no rigid body");
+		BodyPose bp;
+		HIP_TRY(hipStreamSynchronize(s));
+		HIP_TRY(hipMemcpy(&bp, &ctx->d_body.p->pose[slot], sizeof(bp), hipMemcpyDeviceToHost));
+		CollisionPose p = collision_pose(ctx->shape[slot].obj, 0.f);// (inv = 1, growth = 0)
+		for(int i = 0; i < 9; ++i) p.rot[i] = bp.rot[i];
+		for(int d = 0; d < 3; ++d) p.shift[d] = bp.shift[d];
+		ctx->frozen_pose[slot] = p;
+		ctx->frozen[slot]	   = true;
+		ctx->body_mask &= ~(1 << slot);
+		return MPM_OK;
+	}
+	if(ctx->group_refs > 0 || ctx->mgsp_rank >= 0 || ctx->halo_tagged) return fail(ctx, MPM_ERR_INVALID, "mpm_set_collider_body: the context belongs (or belonged) to a multi-GPU group; bodies in groups are not computed");
+	const ShapeSlot& sl = ctx->shape[slot];
+	const int kind		= sl.shape.kind;
+	if(kind == 0) return fail(ctx, MPM_ERR_INVALID, "mpm_set_collider_body: the slot is empty");
+	if(kind == kShapeHalfspace || kind == kShapeHeightfield) return fail(ctx, MPM_ERR_INVALID, "mpm_set_collider_body: a half-space or a heightfield is unbounded and cannot be a rigid body");
+	for(int r: body->reserved)
+		if(r) return fail(ctx, MPM_ERR_INVALID, "mpm_set_collider_body: reserved words must be 0");
+	// where the collider stands now: a body, a slot released from one, or a prescribed collider at the clock's time
+	CollisionPose now = ctx->frozen[slot] ? ctx->frozen_pose[slot] : collision_pose(sl.obj, ctx->collision.time);
+	float v0[3] = {sl.obj.trans_vel[0], sl.obj.trans_vel[1], sl.obj.trans_vel[2]}, w0[3] = {sl.obj.omega[0], sl.obj.omega[1], sl.obj.omega[2]};
+	const bool again = is_body(ctx, slot);// new constants for a body in motion: it keeps its float64 state (below); the checks see its float32 pose
+	BodyState old {};
+	if(again) {
+		BodyPose bp;
+		HIP_TRY(hipStreamSynchronize(s));
+		HIP_TRY(hipMemcpy(&old, &ctx->d_body.p->st[slot], sizeof(old), hipMemcpyDeviceToHost));
+		body_pose(old, bp);
+		for(int i = 0; i < 9; ++i) now.rot[i] = bp.rot[i];
+		for(int d = 0; d < 3; ++d) now.shift[d] = bp.shift[d], v0[d] = bp.vel[d], w0[d] = bp.omega[d];
+	}
+	if(const char* msg = body_object_ok(sl.obj.scale, sl.obj.dsdt, now.rot, sl.obj.trans, v0, w0)) return fail(ctx, MPM_ERR_INVALID, std::string("mpm_set_collider_body: ") + msg);
+	BodyConst c;
+	if(const char* msg = body_constants(body->mass, body->inertia, body->com, body->gravity, body->lock, body->force, body->torque, c)) return fail(ctx, MPM_ERR_INVALID, std::string("mpm_set_collider_body: ") + msg);
+	BodyState st;
+	body_start(now.rot, now.shift, sl.obj.trans, v0, w0, c, st);
+	if(again) body_reconstant(old, ctx->body_c[slot], c, st);
+	BodyPose pose;
+	body_pose(st, pose);
+	if((!ctx->d_body && ctx->d_body.alloc(1, s) != hipSuccess) || (!ctx->d_body_partials && ctx->d_body_partials.alloc((size_t) kLoadGroups * kLoadRows * kLoadSums, s) != hipSuccess)) {
+		(void) hipGetLastError();
+		return fail(ctx, MPM_ERR_CAPACITY, "mpm_set_collider_body: no device memory");
+	}
+	HIP_TRY(hipStreamSynchronize(s));
+	HIP_TRY(hipMemcpy(&ctx->d_body.p->st[slot], &st, sizeof(st), hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(&ctx->d_body.p->c[slot], &c, sizeof(c), hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(&ctx->d_body.p->pose[slot], &pose, sizeof(pose), hipMemcpyHostToDevice));
+	CollisionObject& o = ctx->shape[slot].obj;// re-pivoted to the centre of mass, without a velocity of its own: collision_respond's object velocity is exactly 0
+	for(int d = 0; d < 3; ++d) o.trans[d] = body->com[d], o.trans_vel[d] = 0.f, o.omega[d] = 0.f;
+	ctx->body_c[slot]	 = c;
+	ctx->body_desc[slot] = *body;
+	ctx->frozen[slot]	 = false;
+	ctx->body_mask |= 1 << slot;
+	return MPM_OK;
+}
+
+int mpm_get_collider_body(mpm_ctx* ctx, int slot, mpm_rigid_body* body_out, mpm_rigid_body_state* state_out) {
+	if(!ctx) return MPM_ERR_INVALID;
+	if(!is_body(ctx, slot)) return fail(ctx, MPM_ERR_INVALID, "mpm_get_collider_body: the slot holds no rigid body");
+	if(body_out) *body_out = ctx->body_desc[slot];
+	if(state_out) {
+		HIP_TRY(hipSetDevice(ctx->device));
+		HIP_TRY(hipStreamSynchronize(ctx->s_compute));
+		HIP_TRY(hipMemcpy(state_out, &ctx->d_body.p->st[slot], sizeof(BodyState), hipMemcpyDeviceToHost));
+	}
+	return MPM_OK;
+}
+
+int mpm_set_collider_body_state(mpm_ctx* ctx, int slot, const double position[3], const double orientation[4], const double velocity[3], const double omega[3]) {
+	if(!ctx) return MPM_ERR_INVALID;
+	if(!is_body(ctx, slot)) return fail(ctx, MPM_ERR_INVALID, "mpm_set_collider_body_state: the slot holds no rigid body");
+	HIP_TRY(hipSetDevice(ctx->device));
+	HIP_TRY(hipStreamSynchronize(ctx->s_compute));
+	BodyState st;
+	HIP_TRY(hipMemcpy(&st, &ctx->d_body.p->st[slot], sizeof(st), hipMemcpyDeviceToHost));
+	if(const char* msg = body_restart(st, ctx->body_c[slot], position, orientation, velocity, omega)) return fail(ctx, MPM_ERR_INVALID, std::string("mpm_set_collider_body_state: ") + msg);
+	BodyPose pose;
+	body_pose(st, pose);
+	HIP_TRY(hipMemcpy(&ctx->d_body.p->st[slot], &st, sizeof(st), hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(&ctx->d_body.p->pose[slot], &pose, sizeof(pose), hipMemcpyHostToDevice));
+	return MPM_OK;
+}
+
+int mpm_shape_mass_properties(const mpm_collision_shape* shape, float density, mpm_rigid_body* out) {
+	if(!shape || !out) return MPM_ERR_INVALID;
+	double mass, I6[6], com[3];
+	if(body_shape_mass(shape->kind, shape->inside_out, shape->a, shape->b, shape->radius, (double) density, mass, I6, com)) return MPM_ERR_INVALID;
+	fill_rigid_body(out, mass, I6, com);
+	return MPM_OK;
+}
+
+int mpm_mesh_mass_properties(const float* verts, size_t nv, const int32_t* tris, size_t nt, float density, mpm_rigid_body* out) {
+	if(!verts || !tris || !out) return MPM_ERR_INVALID;
+	MeshRecords m;
+	if(!m.build(verts, nv, tris, nt, 1.f).empty()) return MPM_ERR_INVALID;
+	double mass, I6[6], com[3];
+	if(body_mesh_mass(verts, nv, tris, nt, (double) density, mass, I6, com)) return MPM_ERR_INVALID;
+	fill_rigid_body(out, mass, I6, com);
 	return MPM_OK;
 }
 

@@ -482,6 +482,10 @@ int grp_halo_comm_half(mpm_group* g, int gid, bool collect_again = false) {
 
 int grp_common_init(mpm_group* g) {
 	g->ctx->group_refs++;// (undone by mpm_group_destroy, which every failure below leads to)
+	if(g->ctx->body_mask) {// (the handle does not outlive the refusal: the context keeps the message)
+		g->ctx->err = "a context with a rigid body (mpm_set_collider_body) cannot join a group: bodies in multi-GPU groups are not computed";
+		return gfail(g, MPM_ERR_INVALID, g->ctx->err);
+	}
 	if(const char* e = getenv("MPM_GROUP_DEFER")) g->no_defer = e[0] == '0';
 	if(const char* e = getenv("MPM_GROUP_PAD_TIGHT")) g->tight_pad = e[0] == '1';
 	if(const char* e = getenv("MPM_GROUP_OVERLAP_TAG")) g->overlap_tag = e[0] != '0';

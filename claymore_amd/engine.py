@@ -80,6 +80,7 @@ class Engine:
         if self.track_ids:
             self._check(self.api.track_particle_ids(self.ctx, 1))
         self.models = []
+        self._slot_geom = {}  # slot -> what set_collider_body(density=...) integrates over (_slot_geometry)
         self.cur_time = 0.0
         self.dt = None
 
@@ -420,6 +421,7 @@ class Engine:
         install leaves the one clock stopped at `time`: install all colliders, then start it - or pass animate=True with the last one."""
         if kind is None:
             self._check(self.api.set_collision_shape(self.ctx, int(slot), None, None))
+            self._slot_geometry(slot, None)
             return
         obj = _ffi.CollisionObject()
         self._check(self.api.default_collision_object(C.byref(obj)))
@@ -437,6 +439,7 @@ class Engine:
             sh.a[d], sh.b[d] = float(a[d]), float(b[d])
         sh.radius = float(radius)
         self._check(self.api.set_collision_shape(self.ctx, int(slot), C.byref(obj), C.byref(sh)))
+        self._slot_geometry(slot, ("shape", sh))
         if animate:
             self.set_collision_clock(True, float(obj.time))
 
@@ -448,6 +451,7 @@ class Engine:
         slots are the shapes' (set_collision_shape); every install leaves the one clock stopped at `time`."""
         if heights is None:
             self._check(self.api.set_collision_heightfield(self.ctx, int(slot), None, None, None))
+            self._slot_geometry(slot, None)
             return
         if spacing is None:
             raise ValueError("set_collision_heightfield: spacing is required")
@@ -469,6 +473,7 @@ class Engine:
         hf.spacing = float(spacing)
         hf.inside_out = 1 if inside_out else 0
         self._check(self.api.set_collision_heightfield(self.ctx, int(slot), C.byref(obj), C.byref(hf), h.ctypes.data))
+        self._slot_geometry(slot, None)
         if animate:
             self.set_collision_clock(True, float(obj.time))
 
@@ -517,6 +522,7 @@ class Engine:
         (set_collision_shape); every install leaves the one clock stopped at `time`."""
         if field4 is None:
             self._check(self.api.set_collision_volume(self.ctx, int(slot), None, None, None))
+            self._slot_geometry(slot, None)
             return
         if spacing is None:
             raise ValueError("set_collision_volume: spacing is required")
@@ -530,6 +536,7 @@ class Engine:
         vol.spacing = float(spacing)
         vol.inside_out = 1 if inside_out else 0
         self._check(self.api.set_collision_volume(self.ctx, int(slot), C.byref(obj), C.byref(vol), t.ctypes.data))
+        self._slot_geometry(slot, None)
         if animate:
             self.set_collision_clock(True, float(obj.time))
 
@@ -555,6 +562,7 @@ class Engine:
         vol.inside_out = 1 if inside_out else 0
         vol.pad = int(pad)
         self._check(self.api.set_collision_volume_mesh(self.ctx, int(slot), C.byref(obj), C.byref(vol), v.ctypes.data, v.shape[0], f.ctypes.data, f.shape[0]))
+        self._slot_geometry(slot, ("mesh", v, f))
         if animate:
             self.set_collision_clock(True, float(obj.time))
 
@@ -772,6 +780,93 @@ class Engine:
         self._check(self.api.load_gauge_read(self.ctx, out, C.byref(elapsed), C.byref(updates), 1 if reset else 0))
         return self._load_rows(out, elapsed.value), elapsed.value, updates.value
 
+    # ---- rigid bodies (mpm_rigid_body.hpp) ----
+    def _slot_geometry(self, slot, what):
+        """What set_collider_body(density=...) integrates over: the analytic shape or the mesh the slot was given (None: neither)."""
+        self._slot_geom[int(slot)] = what
+
+    @staticmethod
+    def shape_mass_properties(kind, density, a=(0.0, 0.0, 0.0), b=(0.0, 0.0, 0.0), radius=0.0, api=None):
+        """mass, inertia (6,) {xx yy zz xy xz yz} about com, com (3,) of a homogeneous sphere, box or capsule (mpm_shape_mass_properties; no device)."""
+        api = api if api is not None else _ffi.load_hip()
+        sh = _ffi.CollisionShape()
+        sh.kind = _ffi.SHAPE_NAMES[kind] if isinstance(kind, str) else int(kind)
+        for d in range(3):
+            sh.a[d], sh.b[d] = float(a[d]), float(b[d])
+        sh.radius = float(radius)
+        out = _ffi.RigidBody()
+        rc = api.shape_mass_properties(C.byref(sh), float(density), C.byref(out))
+        if rc:
+            raise EngineError(rc, "shape_mass_properties: the shape has no mass properties (unbounded, degenerate or density <= 0)")
+        return float(out.mass), np.array(out.inertia[:], dtype=np.float32), np.array(out.com[:], dtype=np.float32)
+
+    @staticmethod
+    def mesh_mass_properties(vertices, faces, density, api=None):
+        """The same of a closed, outward-oriented triangle mesh (mpm_mesh_mass_properties; float64 polyhedral integrals, no device)."""
+        api = api if api is not None else _ffi.load_hip()
+        v = np.ascontiguousarray(vertices, dtype=np.float32)
+        f = np.ascontiguousarray(faces, dtype=np.int32)
+        if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+            raise ValueError(f"mesh_mass_properties: vertices must be (nv, 3) and faces (nt, 3), got {v.shape} and {f.shape}")
+        out = _ffi.RigidBody()
+        rc = api.mesh_mass_properties(v.ctypes.data, v.shape[0], f.ctypes.data, f.shape[0], float(density), C.byref(out))
+        if rc:
+            raise EngineError(rc, "mesh_mass_properties: the mesh is refused (not closed, degenerate, no positive volume) or density <= 0")
+        return float(out.mass), np.array(out.inertia[:], dtype=np.float32), np.array(out.com[:], dtype=np.float32)
+
+    def set_collider_body(self, slot, mass=None, inertia=None, com=None, density=None, gravity=True, lock="", force=(0.0, 0.0, 0.0), torque=(0.0, 0.0, 0.0)):
+        """Make the collider in `slot` a rigid body (mpm_set_collider_body): from now on its pose and velocity are state on the device, advanced at
+        every grid update by the impulse the material puts on it.  mass, inertia (6 values xx yy zz xy xz yz, body frame, about com) and com
+        (material coordinates) are given, or density= fills those not given from the slot's analytic shape or the mesh of
+        set_collision_volume_mesh.  lock: a string such as "x z rx ry" (world translations x y z, rotations rx ry rz) or the bit mask.  force,
+        torque: constant, world.  mass=None and density=None: the slot is prescribed again, at rest at the pose it has reached."""
+        if mass is None and density is None:
+            if inertia is not None or com is not None or lock or tuple(force) != (0.0, 0.0, 0.0) or tuple(torque) != (0.0, 0.0, 0.0):
+                raise EngineError(_ffi.MPM_ERR_INVALID, "set_collider_body: constants without mass= or density= (with neither the slot is released from its body)")
+            self._check(self.api.set_collider_body(self.ctx, int(slot), None))
+            return
+        if density is not None:
+            geom = self._slot_geom.get(int(slot))
+            if geom is None:
+                raise EngineError(_ffi.MPM_ERR_INVALID, "set_collider_body: density= needs a slot holding an analytic shape or a volume built from a mesh")
+            if geom[0] == "shape":
+                sh = geom[1]
+                m, i6, c = self.shape_mass_properties(sh.kind, density, sh.a[:], sh.b[:], sh.radius, api=self.api)
+            else:
+                m, i6, c = self.mesh_mass_properties(geom[1], geom[2], density, api=self.api)
+            mass = m if mass is None else mass
+            inertia = i6 if inertia is None else inertia
+            com = c if com is None else com
+        if inertia is None or com is None:
+            raise EngineError(_ffi.MPM_ERR_INVALID, "set_collider_body: mass, inertia and com are given together (or density=)")
+        body = _ffi.RigidBody()
+        body.mass = float(mass)
+        for i, x in enumerate(np.asarray(inertia, dtype=np.float32).ravel()[:6]):
+            body.inertia[i] = float(x)
+        for d in range(3):
+            body.com[d], body.force[d], body.torque[d] = float(com[d]), float(force[d]), float(torque[d])
+        body.gravity = 1 if gravity else 0
+        body.lock = int(lock) if not isinstance(lock, str) else sum(_ffi.BODY_LOCKS[w] for w in lock.split())
+        self._check(self.api.set_collider_body(self.ctx, int(slot), C.byref(body)))
+
+    def collider_body(self, slot):
+        """The body in `slot` (mpm_get_collider_body): its constants and its float64 state - position, orientation (w x y z), velocity, omega,
+        angular_momentum, last_impulse, last_angular_impulse, last_touched_mass, last_touched_nodes, max_mass_ratio, updates."""
+        b, st = _ffi.RigidBody(), _ffi.RigidBodyState()
+        self._check(self.api.get_collider_body(self.ctx, int(slot), C.byref(b), C.byref(st)))
+        out = {"mass": float(b.mass), "inertia": np.array(b.inertia[:], dtype=np.float32), "com": np.array(b.com[:], dtype=np.float32), "gravity": bool(b.gravity),
+               "lock": int(b.lock), "force": np.array(b.force[:], dtype=np.float32), "torque": np.array(b.torque[:], dtype=np.float32)}
+        for name in ("position", "orientation", "velocity", "omega", "angular_momentum", "last_impulse", "last_angular_impulse"):
+            out[name] = np.array(getattr(st, name)[:], dtype=np.float64)
+        out.update(last_touched_mass=float(st.last_touched_mass), max_mass_ratio=float(st.max_mass_ratio), last_touched_nodes=int(st.last_touched_nodes), updates=int(st.updates))
+        return out
+
+    def set_collider_body_state(self, slot, position=None, orientation=None, velocity=None, omega=None):
+        """A restart (mpm_set_collider_body_state): any of position (3), orientation (w x y z), velocity (3), omega (3) replaces that part of the state."""
+        def arr(v, n):
+            return None if v is None else (C.c_double * n)(*[float(x) for x in v])
+        self._check(self.api.set_collider_body_state(self.ctx, int(slot), arr(position, 3), arr(orientation, 4), arr(velocity, 3), arr(omega, 3)))
+
     def last_g2p2g_ms(self):
         ms = C.c_float(0)
         self._check(self.api.last_g2p2g_ms(self.ctx, C.byref(ms)))
@@ -819,6 +914,7 @@ def build_engine(scene, device=0, api=None):
         eng.set_collision_mesh(**{**scene["collision_mesh"], "animate": False})
     colliders = scene.get("colliders") or []
     for slot, c in enumerate(colliders):
+        body, c = c.get("body"), {k: v for k, v in c.items() if k != "body"}  # "body": {...}: Engine.set_collider_body's keywords, installed behind the collider
         if c.get("kind") == "heightfield":
             eng.set_collision_heightfield(slot, **{**{k: v for k, v in c.items() if k != "kind"}, "animate": False})
         elif c.get("kind") == "volume":
@@ -827,6 +923,8 @@ def build_engine(scene, device=0, api=None):
             eng.set_collision_volume_mesh(slot, **{**{k: v for k, v in c.items() if k != "kind"}, "animate": False})
         else:
             eng.set_collision_shape(slot, **{**c, "animate": False})
+        if body is not None:
+            eng.set_collider_body(slot, **body)
     # one clock for all colliders: started once, after the last install (every install stops it)
     fields = [scene[k] for k in ("collision", "collision_mesh") if scene.get(k)]
     moving = [c for c in fields + list(colliders) if c.get("animate")]

@@ -18,6 +18,8 @@
 // the INT point attribute "id" - the particle's index among the model's sampled points - with the frame's points written in ascending id
 // order, so the point order is the same in every frame; the other attributes are joined to the ids on the position bits.  A top-level "colliders" array installs analytic collision shapes (parse_collider below).
 // A top-level "collision_mesh" object installs the level-set collision object from an OBJ file (mpm_set_collision_mesh; in main below).
+// "body": {...} in an entry of "colliders" makes it a rigid body (install_body below); simulation.output_bodies (default false) writes
+// `bodies_frame[f].json` beside each frame: every body's pose, velocities and last impulse (mpm_get_collider_body).
 // simulation.output_loads (default false): the load gauge runs (mpm_load_gauge) and `loads_frame[f].json` beside each frame holds, per row (the
 // level-set object, the four slots, the domain walls), the force and torque on the collider averaged over the frame, the touched-node count and
 // the elapsed time (mpm_load_gauge_read at the frame's end).  A model object may carry "omega": [x, y, z] or "velocity_gradient": [9 numbers, row-major] with an
@@ -190,6 +192,56 @@ bool parse_volume_collider(const mj::Value& c, const std::string& shape, mpm_col
 	return parse_collider_motion(c, obj, moving);
 }
 
+// "body": {...} inside an entry of "colliders" makes that collider a rigid body (mpm_set_collider_body) once it is installed: "mass", "inertia"
+// [xx, yy, zz, xy, xz, yz] and "com" [x, y, z], or "density" - which fills those not given from the analytic shape (sh) or the OBJ mesh (verts, tris)
+// through mpm_shape_mass_properties / mpm_mesh_mass_properties -, "gravity" (default true), "lock": "x z rx ry", "force", "torque".  The entry's
+// "velocity" and "omega" are the body's v0 and (true) angular velocity.
+bool install_body(mpm_ctx* ctx, int slot, const mj::Value& b, const mpm_collision_shape* sh, const std::vector<float>& verts, const std::vector<int32_t>& tris) {
+	mpm_rigid_body body;
+	std::memset(&body, 0, sizeof(body));
+	body.gravity = 1;
+	if(b.has("density")) {
+		const float rho = num(b, "density", 0.f);
+		const int rc	= sh ? mpm_shape_mass_properties(sh, rho, &body) : mpm_mesh_mass_properties(verts.data(), verts.size() / 3, tris.data(), tris.size() / 3, rho, &body);
+		if(rc) {
+			std::fprintf(stderr, "gmpm: collider %d: \"density\" needs a sphere, a box, a capsule or a closed mesh, and a density > 0\n", slot);
+			return false;
+		}
+	} else if(!b.has("mass") || !b.has("inertia") || !b.has("com")) {
+		std::fprintf(stderr, "gmpm: collider %d: a body needs \"density\", or \"mass\", \"inertia\" and \"com\"\n", slot);
+		return false;
+	}
+	body.mass = num(b, "mass", body.mass);
+	if(b.has("inertia")) {
+		if(b["inertia"].type != mj::Value::Array || b["inertia"].arr.size() != 6) {
+			std::fprintf(stderr, "gmpm: collider %d: body \"inertia\" must be [xx, yy, zz, xy, xz, yz]\n", slot);
+			return false;
+		}
+		for(int i = 0; i < 6; ++i) body.inertia[i] = (float) b["inertia"][i].number();
+	}
+	vec3(b, "com", body.com);
+	vec3(b, "force", body.force);
+	vec3(b, "torque", body.torque);
+	if(b.has("gravity") && b["gravity"].type == mj::Value::Bool) body.gravity = b["gravity"].b ? 1 : 0;
+	if(b.has("lock")) {
+		std::istringstream words(b["lock"].string());
+		for(std::string w; words >> w;) {
+			static const char* names[6] = {"x", "y", "z", "rx", "ry", "rz"};
+			int bit = -1;
+			for(int i = 0; i < 6; ++i)
+				if(w == names[i]) bit = i;
+			if(bit < 0) {
+				std::fprintf(stderr, "gmpm: collider %d: unknown body lock '%s' (expected x y z rx ry rz)\n", slot, w.c_str());
+				return false;
+			}
+			body.lock |= 1 << bit;
+		}
+	}
+	const int rc = mpm_set_collider_body(ctx, slot, &body);
+	if(rc) die(ctx, rc);
+	return true;
+}
+
 // One entry of "colliders": {"shape": "halfspace" ("point", "normal") | "sphere" ("center", "radius") | "box" ("center", "half_extents") |
 // "capsule" ("a", "b", "radius") | "heightfield" (below) | "mesh" | "volume" (parse_volume_collider above), "type": "sticky|slip|separate", "friction", "velocity", "omega", "inside_out"}.  A collider with
 // "velocity" or "omega" moves: it translates, and turns about its point / center / a, with the context's clock, which then starts at 0.
@@ -358,6 +410,7 @@ int main(int argc, char** argv) {
 	const bool out_stress	  = sim.has("output_stress") && sim["output_stress"].type == mj::Value::Bool && sim["output_stress"].b;
 	const bool out_ids		  = sim.has("output_ids") && sim["output_ids"].type == mj::Value::Bool && sim["output_ids"].b;
 	const bool out_loads	  = sim.has("output_loads") && sim["output_loads"].type == mj::Value::Bool && sim["output_loads"].b;
+	const bool out_bodies	  = sim.has("output_bodies") && sim["output_bodies"].type == mj::Value::Bool && sim["output_bodies"].b;
 	int grid_stride			  = 0;// simulation.output_grid: 0 = no grid files
 	if(sim.has("output_grid")) {
 		const mj::Value& og = sim["output_grid"];
@@ -530,6 +583,7 @@ int main(int argc, char** argv) {
 	}
 
 	// "colliders": analytic collision shapes (mpm_set_collision_shape), at most MPM_MAX_COLLISION_SHAPES, slot = position in the array
+	int bodies = 0;// bit s: slot s is a rigid body ("body": {...} in its entry)
 	if(doc->has("colliders")) {
 		const mj::Value& cols = (*doc)["colliders"];
 		if(cols.arr.size() > (size_t) MPM_MAX_COLLISION_SHAPES) {
@@ -551,11 +605,19 @@ int main(int argc, char** argv) {
 				rc = shape == "mesh" ? mpm_set_collision_volume_mesh(ctx, (int) ci, &obj, &vol, verts.data(), verts.size() / 3, tris.data(), tris.size() / 3)
 									 : mpm_set_collision_volume(ctx, (int) ci, &obj, &vol, field4.data());
 				if(rc) die(ctx, rc);
+				if(cols[ci].has("body")) {
+					if(!install_body(ctx, (int) ci, cols[ci]["body"], nullptr, verts, tris)) return 1;
+					bodies |= 1 << ci;
+				}
 				continue;
 			}
 			if(!parse_collider(cols[ci], obj, sh, moving, hf, heights, scene_dir)) return 1;
 			rc = hf.nx ? mpm_set_collision_heightfield(ctx, (int) ci, &obj, &hf, heights.data()) : mpm_set_collision_shape(ctx, (int) ci, &obj, &sh);
 			if(rc) die(ctx, rc);
+			if(cols[ci].has("body")) {
+				if(!install_body(ctx, (int) ci, cols[ci]["body"], hf.nx ? nullptr : &sh, {}, {})) return 1;
+				bodies |= 1 << ci;
+			}
 		}
 		std::printf("has %zu colliders%s\n", cols.arr.size(), moving ? ", clock running" : "");
 		if(moving && (rc = mpm_set_collision_clock(ctx, 1, 0.f))) die(ctx, rc);// one clock for all of them, started after the last install
@@ -608,6 +670,32 @@ int main(int argc, char** argv) {
 		std::fprintf(f, "\n}}\n");
 		std::fclose(f);
 	};
+	// simulation.output_bodies: bodies_frame[f].json beside each frame holds every rigid body's pose, velocities and last impulse (mpm_get_collider_body)
+	auto write_bodies = [&](int frame) {
+		FILE* f = std::fopen((out_dir + "/bodies_frame[" + std::to_string(frame) + "].json").c_str(), "w");
+		if(!f) {
+			std::fprintf(stderr, "gmpm: cannot write the bodies of frame %d\n", frame);
+			std::exit(1);
+		}
+		std::fprintf(f, "{\"frame\": %d, \"bodies\": {", frame);
+		bool first = true;
+		for(int s = 0; s < MPM_MAX_COLLISION_SHAPES; ++s) {
+			if(!((bodies >> s) & 1)) continue;
+			mpm_rigid_body_state st;
+			int rs = mpm_get_collider_body(ctx, s, nullptr, &st);
+			if(rs) die(ctx, rs);
+			std::fprintf(f, "%s\n  \"slot%d\": {\"position\": [%.17g, %.17g, %.17g], \"orientation\": [%.17g, %.17g, %.17g, %.17g], \"velocity\": [%.17g, %.17g, %.17g], \"omega\": [%.17g, %.17g, %.17g], "
+					"\"angular_momentum\": [%.17g, %.17g, %.17g], \"last_impulse\": [%.17g, %.17g, %.17g], \"last_angular_impulse\": [%.17g, %.17g, %.17g], \"last_touched_mass\": %.17g, "
+					"\"max_mass_ratio\": %.17g, \"last_touched_nodes\": %lld, \"updates\": %lld}",
+					first ? "" : ",", s, st.position[0], st.position[1], st.position[2], st.orientation[0], st.orientation[1], st.orientation[2], st.orientation[3], st.velocity[0], st.velocity[1],
+					st.velocity[2], st.omega[0], st.omega[1], st.omega[2], st.angular_momentum[0], st.angular_momentum[1], st.angular_momentum[2], st.last_impulse[0], st.last_impulse[1],
+					st.last_impulse[2], st.last_angular_impulse[0], st.last_angular_impulse[1], st.last_angular_impulse[2], st.last_touched_mass, st.max_mass_ratio,
+					(long long) st.last_touched_nodes, (long long) st.updates);
+			first = false;
+		}
+		std::fprintf(f, "\n}}\n");
+		std::fclose(f);
+	};
 	const auto wall0 = std::chrono::steady_clock::now();
 	for(int frame = 1; frame <= frames; ++frame) {
 		for(float t = 0.f; t < spf;) {
@@ -640,6 +728,7 @@ int main(int argc, char** argv) {
 		}
 		if(surface_iso > 0.f) write_surface(frame);
 		if(out_loads) write_loads(frame);
+		if(out_bodies) write_bodies(frame);
 		for(size_t mi = 0; mi < counts.size(); ++mi) {// output_model, :594-634
 			buf.resize(3 * counts[mi]);
 			vbuf.clear();

@@ -322,6 +322,37 @@ def sphere_through_block_analytic(bits=6, block_cells=(20, 10, 20), radius_cells
     return _as_shape(sc, radius_cells / (1 << bits))
 
 
+def ball_into_sand(bits=6, radius_cells=4.0, density=8e3, drop_cells=2.0, bed_cells=(32, 12, 32), friction=0.4, speed=0.0, dt=1e-4):
+    """A dense sphere - a rigid body (Engine.set_collider_body: the material pushes it back) - dropped from `drop_cells` above (or thrown down at `speed` onto) a bed of
+    Drucker-Prager sand (rho 1e3) that lies on the floor.  The sphere is eight times as dense as the sand, so the mass of the nodes it touches
+    stays well below its own (the explicit coupling's stable range; Engine.collider_body(0)["max_mass_ratio"] tells)."""
+    dx, n = 1.0 / (1 << bits), 1 << bits
+    lo = [(n - bed_cells[0]) // 2, 8, (n - bed_cells[2]) // 2]
+    hi = [lo[d] + int(bed_cells[d]) for d in range(3)]
+    centre = (0.5 + 0.25 * dx, (hi[1] + drop_cells + radius_cells) * dx, 0.5 - 0.25 * dx)
+    return {"name": "ball_into_sand", "bits": bits, "dt": dt, "config": {"max_ppc": 128},
+            "models": [{"material": SAND, "xyz": lattice_box(bits, lo, hi), "v0": (0.0, 0.0, 0.0), "params": {"volume": _vol(bits)}}],
+            "colliders": [{"kind": "sphere", "a": centre, "radius": radius_cells * dx, "type": 2, "friction": friction, "trans_vel": (0.0, -speed, 0.0),
+                           "body": {"density": density}}]}
+
+
+def floating_box(bits=6, half_cells=(6, 8, 6), density=5e2, pool_cells=(40, 20, 40), speed=0.0, dt=1e-4):
+    """A box of half the fluid's density - a rigid body - set down half submerged (or pushed down at `speed`) in a pool of the J-fluid (rho 1e3) on the floor: it bobs
+    about the depth at which it displaces its own weight.  The box is 16 cells tall by default: the nodes it touches form a one-cell shell
+    around its wetted faces, whose mass then stays near a fifth of the box's (max_mass_ratio)."""
+    dx, n = 1.0 / (1 << bits), 1 << bits
+    lo = [(n - pool_cells[0]) // 2, 8, (n - pool_cells[2]) // 2]
+    hi = [lo[d] + int(pool_cells[d]) for d in range(3)]
+    centre = (0.5, hi[1] * dx, 0.5)
+    xyz = lattice_box(bits, lo, hi)
+    b = np.array(half_cells, dtype=np.float64) * dx
+    inside = np.all(np.abs(xyz.astype(np.float64) - np.array(centre)) < b + 0.5 * dx, axis=1)  # no fluid where the box stands
+    return {"name": "floating_box", "bits": bits, "dt": dt, "config": {"max_ppc": 128},
+            "models": [{"material": J_FLUID, "xyz": np.ascontiguousarray(xyz[~inside]), "v0": (0.0, 0.0, 0.0), "params": {"volume": _vol(bits)}}],
+            "colliders": [{"kind": "box", "a": centre, "b": tuple(float(v) for v in b), "type": 1, "friction": 0.0, "trans_vel": (0.0, -speed, 0.0),
+                           "body": {"density": density}}]}
+
+
 def colliders_demo(bits=6, boundary="slip", friction=0.3, speed=1.0, dt=1e-4):
     """One of each: an elastic block falls onto a tilted floor wedge (half-space) beside a sticky box and a fixed rod (capsule), while a sphere
     sweeps through along +x; the clock runs.  Four analytic colliders, no level set."""

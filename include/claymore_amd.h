@@ -648,6 +648,57 @@ int mpm_collider_loads(mpm_ctx* ctx, float dt, const mpm_load_options* opt, doub
 int mpm_collider_contacts(mpm_ctx* ctx, float dt, int32_t* node_row4, float* rec8, size_t* n);
 int mpm_load_gauge(mpm_ctx* ctx, int on, const mpm_load_options* opt);
 int mpm_load_gauge_read(mpm_ctx* ctx, double out[MPM_LOAD_ROWS][8], double* elapsed, int* updates, int reset);
+/* Rigid bodies (an extension; INTEGRATION.md section 5, claymore_amd/csrc/mpm_rigid_body.hpp): a BODY is a slot collider whose pose and velocity
+ * are state on the device instead of functions of the collision clock.  Every applied grid update treats it as prescribed at its present
+ * (x, q, v, omega): the material's nodes take the response, and the body afterwards takes the equal and opposite impulse - J and L of its load
+ * row above, L about x - so what grid and body exchange is conserved to the last bit per update.
+ * Eligible: slots 0 .. 3 holding a SPHERE, a BOX, a CAPSULE or a volume.  MPM_ERR_INVALID (mpm_last_error names the reason) for an empty slot, a
+ *   HALFSPACE or a heightfield (unbounded); obj.scale != 1 or obj.dsdt != 0; an obj.rot_mat that is not a rotation (|R^T R - I| entries above
+ *   1e-5, det < 0); mass <= 0 or not finite; an inertia that is not symmetric positive definite; a NaN anywhere; non-zero reserved words; a
+ *   context that belongs or belonged to a group or has been through the halo tagging.  A group refuses to adopt a context that has a body.  The
+ *   level-set object (row 0) cannot be a body.  A refused call changes nothing.
+ * Start: where the collider stands at the moment of the call.  q0 from obj.rot_mat; the slot's object is re-pivoted to the centre of mass
+ *   (internal trans := com, x0 = trans + R0 (com - trans) in float64: every node's material point is what it was, up to float32 rounding, exactly
+ *   so when com == obj.trans and rot_mat is the identity); v0 = obj.trans_vel; omega0 = obj.omega read as a TRUE angular velocity (world; not
+ *   the plus-sign cross product of the prescribed colliders); l0 = R Ib R^T omega0.  A body ignores the collision clock: it advances with every
+ *   applied grid update, whether the clock runs or not.
+ * The step, h = (double) dt, in float64 with + - x / and sqrt alone:
+ *   v <- v + (J + h force) / mass (+ (double) gravity * h on y with the gravity flag), locked components 0, x <- x + h v;
+ *   l <- l + L + h torque, omega = R(q) Ib^-1 R(q)^T l, locked components 0 (then l <- R Ib R^T omega);
+ *   q <- (q + h/2 (0, omega) (x) q) / |...|: the axis and the norm are exact, the angle falls short by (h |omega|)^3 / 12 per step.
+ *   lock bits 0 .. 2: world translation x, y, z; 3 .. 5: rotation about world x, y, z.  A non-finite J, L or state: MPM_ERR_NONFINITE at the
+ *   next synchronisation.
+ * The coupling is explicit: stable while the mass of the touched nodes stays below the body's; max_mass_ratio is the largest ratio seen.
+ *   Bodies do not collide with each other, with prescribed colliders or with the domain walls.  With a body installed mpm_run_fixed keeps the
+ *   grid update a kernel of its own (as with the load gauge); mpm_collider_loads' default pivot of a body row is its x at the time of the call.
+ * mpm_set_collider_body on a slot that already holds a body gives it new constants: q, v, omega, the counters and the last impulses keep their float64
+ *   words, x moves by R(q) (com_new - com_old) so that no node's material point moves, l = R Ib_new R^T omega.
+ * mpm_set_collider_body: body NULL makes the slot prescribed again, at rest at the pose it has reached.  Installing any collider over the slot,
+ *   or emptying it, removes the body.  mpm_get_collider_body: either output may be NULL; MPM_ERR_INVALID for a slot without a body.
+ * mpm_set_collider_body_state: a restart; a NULL keeps that part; the orientation is normalised, l follows from omega.  Bodies, like colliders,
+ *   are not part of a checkpoint: a load leaves them as they are.
+ * mpm_shape_mass_properties, mpm_mesh_mass_properties: mass, inertia and com of a homogeneous solid of `density`, in the coordinates the shape
+ *   or the mesh is given in (gravity = 1, lock = 0, force = torque = 0); host only, no context: the closed forms of sphere, box and capsule,
+ *   float64 polyhedral integrals under mpm_set_collision_mesh's validation.  HIP library only. */
+typedef struct mpm_rigid_body {
+	float mass;
+	float inertia[6]; /* xx yy zz xy xz yz, body frame, about com */
+	float com[3];
+	int gravity;
+	int lock;
+	float force[3];
+	float torque[3];
+	int reserved[8]; /* must be 0 */
+} mpm_rigid_body;
+typedef struct mpm_rigid_body_state {
+	double position[3], orientation[4] /* w x y z */, velocity[3], omega[3], angular_momentum[3], last_impulse[3], last_angular_impulse[3], last_touched_mass, max_mass_ratio;
+	int64_t last_touched_nodes, updates;
+} mpm_rigid_body_state;
+int mpm_set_collider_body(mpm_ctx* ctx, int slot, const mpm_rigid_body* body);
+int mpm_get_collider_body(mpm_ctx* ctx, int slot, mpm_rigid_body* body_out, mpm_rigid_body_state* state_out);
+int mpm_set_collider_body_state(mpm_ctx* ctx, int slot, const double position[3], const double orientation[4], const double velocity[3], const double omega[3]);
+int mpm_shape_mass_properties(const mpm_collision_shape* shape, float density, mpm_rigid_body* out);
+int mpm_mesh_mass_properties(const float* verts, size_t nv, const int32_t* tris, size_t nt, float density, mpm_rigid_body* out);
 /* How the library was built: "claymore_hip <abi> experiment=<none | list of -D switches>".  A product library reports
  * experiment=none (claymore_amd/csrc/mpm_device_math.hpp: the switches that change what the kernels compute only exist under
  * -DMPM_EXPERIMENT); tests/test_abi.py asserts it for the shipped library.  Needs no device. */

@@ -3,14 +3,15 @@
 libraries in ONE process, interleaved (lib A, lib B, lib A, ...), so that a parent build and a branch build are compared on the same
 box under the same conditions.
 
-    python tools/collider_substep.py [--scene c1|c2|c3] [--steps 200] [--warmup 50] [--reps 3] [--objects none,static,moving,shape,shapes4,ground_hf,ground_shape,ground_field,vol_mesh,vol_mesh4,field_mesh] [--phase 20]
+    python tools/collider_substep.py [--scene c1|c2|c3] [--steps 200] [--warmup 50] [--reps 3] [--objects none,static,moving,shape,body,shapes4,ground_hf,ground_shape,ground_field,vol_mesh,vol_mesh4,field_mesh] [--phase 20]
                                      [--loads] [--out FILE] [lib.so ...]
 
 Scene: C2 (one elastic sphere of ~5 M particles dropped at 256^3; the level-set field is 256^3 float4 = 256 MiB) or C3 (the sand column at
 512^3; the field is 2 GiB).  The object is a sphere below the material, far enough that nothing touches it during the measurement: the
 kernel evaluates it at every grid node with mass either way, which is the cost in question.  A library without the clock's entry points
 (a parent build) runs `none` and `static` only.  `shape`: the same sphere given in closed form (mpm_set_collision_shape: no field, no loads);
-`shapes4`: that sphere, a floor half-space, a box and a capsule in the four slots, all clear of the material.  A library without
+`body`: that sphere as a rigid body (mpm_set_collider_body, every axis locked, so at rest like the prescribed one: mpm_run_fixed then applies every update through grid_update_body_kernel +
+body_step_kernel, unfused); `shapes4`: that sphere, a floor half-space, a box and a capsule in the four slots, all clear of the material.  A library without
 mpm_set_collision_shape skips both.  `ground_hf` / `ground_shape` / `ground_field`: one flat ground just under the material given three ways -
 a heightfield (mpm_set_collision_heightfield: an (N + 1)^2 table of constant height at spacing dx, four float4 gathers per massed cell), the
 half-space shape at that height, and the level set of the same plane (sdf = y - height, gradient +y) - the same physics (the level set
@@ -77,11 +78,15 @@ def main():
                     continue
                 if (obj == "ground_hf" and not hasattr(api, "set_collision_heightfield")) or (obj == "ground_shape" and not hasattr(api, "set_collision_shape")):
                     continue
+                if obj == "body" and not hasattr(api, "set_collider_body"):
+                    continue
                 eng = build_engine(sc, api=api)
                 free0 = torch.cuda.mem_get_info()[0]
                 t_install = time.perf_counter()
-                if obj in ("shape", "shapes4"):
+                if obj in ("shape", "shapes4", "body"):
                     eng.set_collision_shape(0, "sphere", a=(0.5, 0.12, 0.5), radius=0.06, type=1, friction=0.3, trans=(0.5, 0.12, 0.5))
+                if obj == "body":  # the same sphere as a rigid body, every axis locked (at rest like the prescribed one): every update is grid_update_body_kernel + body_step_kernel
+                    eng.set_collider_body(0, density=2500.0, gravity=False, lock="x y z rx ry rz")
                 if obj == "shapes4":
                     eng.set_collision_shape(1, "halfspace", a=(0.5, 0.02, 0.5), b=(0.0, -1.0, 0.0), inside_out=True, type=1, friction=0.3)
                     eng.set_collision_shape(2, "box", a=(0.2, 0.1, 0.2), b=(0.05, 0.04, 0.05), type=0)

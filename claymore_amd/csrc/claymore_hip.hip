@@ -369,9 +369,9 @@ static int still_launch_override(const char* e) {
 // with a volume in a slot (BodyArgs around it with a rigid body in a slot), else TerrainArgs with a heightfield in a slot, ShapeArgs with analytic shapes alone, CollisionArgs with the level-set object alone, NoCollision without any.
 // One pose per installed collider, all at the one clock's current time T (the start of the substep), by value; a running clock then moves
 // on, T = T + dt in one float32 addition (the drivers' own cur_time += dt).  Called once per applied grid update - by the stand-alone
-// kernel's launch or by the fused carry-over's, never by both.
+// kernel's launch or by the fused carry-over's, never by both.  state_pivots: BodyArgs' own, for the launches whose kernel sums loads.
 template<class F>
-static void with_collider(mpm_ctx* ctx, float dt, F&& launch) {
+static void with_collider(mpm_ctx* ctx, float dt, F&& launch, int state_pivots = 0) {
 	if(!ctx->has_collision && !ctx->shape_count) {
 		launch(NoCollision {});
 		return;
@@ -389,7 +389,7 @@ static void with_collider(mpm_ctx* ctx, float dt, F&& launch) {
 	for(int i = 0; i < kMaxShapes; ++i) a.hf[i] = ctx->hf[i], va.vol[i] = ctx->vol[i];
 	if(ctx->collision_running) ctx->collision.time = T + dt;
 	if(ctx->body_mask)// (a body slot's pose and pivot are read from the device; its object travels with trans = com and no velocity)
-		launch(BodyArgs {va, ctx->d_body.p->pose, ctx->d_body.p->st, ctx->body_mask, 0});
+		launch(BodyArgs {va, ctx->d_body.p->pose, ctx->d_body.p->st, ctx->body_mask, state_pivots});
 	else if(ctx->vol_count)
 		launch(va);
 	else if(ctx->hf_count)
@@ -402,9 +402,9 @@ static void with_collider(mpm_ctx* ctx, float dt, F&& launch) {
 // The installed colliders at the clock's current time T as with_collider hands them out, without its side effect: the clock stays where it is.
 // What a readout of the coming grid update needs (mpm_collider_loads.hpp); the two launches that apply an update call with_collider itself.
 template<class F>
-static void with_collider_at_clock(mpm_ctx* ctx, F&& launch) {
+static void with_collider_at_clock(mpm_ctx* ctx, F&& launch, int state_pivots = 0) {
 	const float T = ctx->collision.time;
-	with_collider(ctx, 0.f, launch);
+	with_collider(ctx, 0.f, launch, state_pivots);
 	ctx->collision.time = T;
 }
 
@@ -851,15 +851,10 @@ static LoadPivots load_pivots(const mpm_ctx* ctx, const mpm_load_options* opt) {
 static int launch_collider_loads(mpm_ctx* ctx, float dt, const mpm_load_options* opt, double* partials, double* out, int accumulate) {
 	hipStream_t s		 = ctx->s_compute;
 	const LoadPivots piv = load_pivots(ctx, opt);
-	with_collider_at_clock(ctx, [&](const auto& col) {
-		if constexpr(std::is_same_v<std::decay_t<decltype(col)>, BodyArgs>) {// the same frame without the stores; a body row's default pivot is its x, read on the device
-			BodyArgs b = col;
-			for(int i = 0; i < kMaxBodies; ++i)
-				if(((b.mask >> i) & 1) && !(opt && opt->has_pivot[1 + i])) b.state_pivots |= 1 << i;
-			grid_update_body_kernel<BodyArgs, false><<<kLoadGroups, 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, b, piv, partials, nullptr);
-		} else
-			collider_loads_kernel<<<kLoadGroups, 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, col, piv, partials);
-	});
+	int state_pivots	 = ctx->body_mask;// a body row's default pivot is its x, read on the device
+	for(int i = 0; i < kMaxBodies; ++i)
+		if(opt && opt->has_pivot[1 + i]) state_pivots &= ~(1 << i);
+	with_collider_at_clock(ctx, [&](const auto& col) { collider_loads_kernel<<<kLoadGroups, 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, col, piv, partials); }, state_pivots);
 	collider_loads_reduce_kernel<<<1, kLoadReduceThreads, 0, s>>>(partials, kLoadGroups, out, accumulate, (double) dt);
 	HIP_TRY(hipGetLastError());
 	return MPM_OK;
@@ -878,28 +873,20 @@ static int launch_grid_update(mpm_ctx* ctx, float dt) {
 		return MPM_OK;// (the carry-over that applied this update has advanced the object's clock)
 	}
 	HIP_TRY(hipMemsetAsync(ctx->d_maxvel, 0, sizeof(unsigned) * kMaxVelSlots * kMaxVelStride, s));
-	if(ctx->body_mask) {// the update and its loads in one pass, then the bodies' step (mpm_rigid_body.hpp); the clock moves as for any applied update
-		const LoadPivots piv = load_pivots(ctx, nullptr);
-		with_collider(ctx, dt, [&](const auto& col) {
-			if constexpr(std::is_same_v<std::decay_t<decltype(col)>, BodyArgs>) {
-				BodyArgs b	   = col;
-				b.state_pivots = b.mask;
-				grid_update_body_kernel<BodyArgs, true><<<kLoadGroups, 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, b, piv, ctx->d_body_partials, ctx->d_maxvel);
-			}
-		});
-		body_step_kernel<<<1, kLoadReduceThreads, 0, s>>>(ctx->d_body_partials, kLoadGroups, ctx->d_body, ctx->body_mask, dt, ctx->cfg.gravity, &ctx->d_status[ST_NONFINITE]);
-		HIP_TRY(hipGetLastError());
-		return MPM_OK;
-	}
-	if(ctx->nbc) {
-		const int est = std::min(ctx->g.cap, ctx->nbc + ctx->nbc / 16 + 64);// (an estimate between two synchronisations of mpm_run_fixed)
-		with_collider(ctx, dt, [&](const auto& col) {
-			if constexpr(std::is_same_v<std::decay_t<decltype(col)>, NoCollision>)
-				grid_update_kernel<<<cdiv(est, 16), 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, ctx->d_maxvel);
-			else if constexpr(!std::is_same_v<std::decay_t<decltype(col)>, BodyArgs>)// (bodies took the branch above)
-				grid_update_collider_kernel<<<cdiv(est, 4), 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, col, ctx->d_maxvel);
-		});
-	}
+	if(!ctx->nbc && !ctx->body_mask) return MPM_OK;// (no block: no update is applied)
+	const int est = std::min(ctx->g.cap, ctx->nbc + ctx->nbc / 16 + 64);// (an estimate between two synchronisations of mpm_run_fixed)
+	const LoadPivots piv = ctx->body_mask ? load_pivots(ctx, nullptr) : LoadPivots {};// (at the clock's time before this update moves it)
+	with_collider(ctx, dt, [&](const auto& col) {
+		using Collider = std::decay_t<decltype(col)>;
+		if constexpr(kCarriesBodies<Collider>) {// the update and its loads in one pass, then the bodies' step (mpm_rigid_body.hpp); the clock moves as for any applied update
+			grid_update_body_kernel<<<kLoadGroups, 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, col, piv, ctx->d_body_partials, ctx->d_maxvel);
+			body_step_kernel<<<1, kLoadReduceThreads, 0, s>>>(ctx->d_body_partials, kLoadGroups, ctx->d_body, ctx->body_mask, dt, ctx->cfg.gravity, &ctx->d_status[ST_NONFINITE]);
+		} else if constexpr(!kCollides<Collider>)
+			grid_update_kernel<<<cdiv(est, 16), 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, ctx->d_maxvel);
+		else
+			grid_update_collider_kernel<<<cdiv(est, 4), 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, col, ctx->d_maxvel);
+	}, ctx->body_mask);
+	if(ctx->body_mask) HIP_TRY(hipGetLastError());
 	return MPM_OK;
 }
 
@@ -1125,7 +1112,7 @@ static int launch_rebuild(mpm_ctx* ctx, const SubstepPlan& plan, StillLaunch* ta
 	register_blocks_kernel<0, 1><<<rg8, 256, 0, s>>>(g, &st[ST_CNT_P], nullptr, &st[ST_CNT_N], &st[ST_PBC], Pn.table, Pn.keys, st, still);
 	if(fused) {
 		with_collider(ctx, fuse_dt, [&](const auto& col) {
-			if constexpr(!std::is_same_v<std::decay_t<decltype(col)>, BodyArgs>)// (no driver fuses an update with a body installed: mpm_run_fixed)
+			if constexpr(!kCarriesBodies<std::decay_t<decltype(col)>>)// (no driver fuses an update with a body installed: refused above)
 				carry_grid_kernel<true, std::decay_t<decltype(col)>><<<2048, 256, 0, s>>>(g, st, Pn.keys, Pr.table, ctx->grid[1], ctx->grid[0], fuse_dt, ctx->d_maxvel, col);
 		});
 		ctx->grid_preupdated = true;

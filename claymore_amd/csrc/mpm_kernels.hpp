@@ -335,6 +335,8 @@ struct CollisionArgs {
 	CollisionPose pose;
 };
 struct NoCollision {};
+template<class Collider>
+constexpr bool kCollides = !std::is_same_v<Collider, NoCollision>;
 // Analytic collision shapes (mpm_collision_shapes.hpp): per massed cell walls and gravity, then the level-set object if one is installed,
 // then slots 0 .. 3 in order, each acting on the velocity the previous collider left.  Everything travels by value: count, has_field and
 // the kinds are wave-uniform (scalar compares); the slot loop is a real loop (#pragma nounroll) that reads the slot it is at from the
@@ -370,8 +372,9 @@ struct VolumeColliderArgs {
 };
 
 // The two ends every grid_cell overload shares, so that a change is made once.  Prologue: momentum -> velocity with the walls' zeroes and
-// gravity, and the cell's node coordinates.
-MPM_DEV void grid_cell_walls_gravity(const GridCfg& cfg, int kx, int ky, int kz, int cell, float dt, const float4& v, float (&vel)[3], int (&node)[3]) {
+// gravity, and the cell's node coordinates.  wall_dv, where asked for: what the walls did to the velocity, (zeroed component - p / m) on each axis a
+// wall zeroes (the load readout's wall row, mpm_collider_loads.hpp; gravity is not in it).
+MPM_DEV void grid_cell_walls_gravity(const GridCfg& cfg, int kx, int ky, int kz, int cell, float dt, const float4& v, float (&vel)[3], int (&node)[3], float (*wall_dv)[3] = nullptr) {
 #pragma clang fp contract(off)
 	const bool wx = kx < cfg.boundary || kx >= cfg.G - cfg.boundary;
 	const bool wy = ky < cfg.boundary || ky >= cfg.G - cfg.boundary;
@@ -380,6 +383,11 @@ MPM_DEV void grid_cell_walls_gravity(const GridCfg& cfg, int kx, int ky, int kz,
 	vel[0] = wx ? 0.0f : v.y * mass_inv;
 	vel[1] = (wy ? 0.0f : v.z * mass_inv) + cfg.gravity * dt;
 	vel[2] = wz ? 0.0f : v.w * mass_inv;
+	if(wall_dv) {
+		(*wall_dv)[0] = wx ? 0.0f - v.y * mass_inv : 0.0f;
+		(*wall_dv)[1] = wy ? 0.0f - v.z * mass_inv : 0.0f;
+		(*wall_dv)[2] = wz ? 0.0f - v.w * mass_inv : 0.0f;
+	}
 	node[0] = kx * 4 + (cell >> 4);
 	node[1] = ky * 4 + ((cell >> 2) & 3);
 	node[2] = kz * 4 + (cell & 3);
@@ -417,18 +425,37 @@ MPM_DEV float grid_cell(const GridCfg& cfg, const CollisionArgs& col, int kx, in
 	collision_resolve(col.obj, col.pose, node, cfg.dx, cfg.G * 4, (float) cfg.boundary * cfg.dx * 4.f, (float) (cfg.G - cfg.boundary) * 4.f * cfg.dx, vel);
 	return grid_cell_store_doubled_q(vel, v);
 }
-// The same for ShapeArgs, TerrainArgs and VolumeColliderArgs, one function: the prologue + the optional field object + the slot loop.  The heightfield
-// branch is compiled in for TerrainArgs (and VolumeColliderArgs, which carries one) alone, the volume branch for VolumeColliderArgs alone (no run-time test of
-// a table pointer), so without a heightfield the code is that of the analytic shapes and without a volume that of the terrain.
+// The same for ShapeArgs, TerrainArgs and VolumeColliderArgs, one function: the prologue + the optional field object + the slot loop.
+// The argument types with slots are those shape_args takes (terrain_args: those that carry heightfield tables beside them); a further type joins
+// by adding its overloads (BodyArgs: mpm_rigid_body.hpp).
 MPM_DEV const ShapeArgs& shape_args(const ShapeArgs& a) { return a; }
 MPM_DEV const ShapeArgs& shape_args(const TerrainArgs& a) { return a.col; }
 MPM_DEV const ShapeArgs& shape_args(const VolumeColliderArgs& a) { return a.ter.col; }
 MPM_DEV const TerrainArgs& terrain_args(const TerrainArgs& a) { return a; }
 MPM_DEV const TerrainArgs& terrain_args(const VolumeColliderArgs& a) { return a.ter; }
+// What slot s does to the velocity at the node position X, the collider standing at `pose`: THE kind dispatch, which every walk of a cell through
+// the slots calls (grid_cell here, load_cell in mpm_collider_loads.hpp, the body response in mpm_rigid_body.hpp).  The heightfield branch is compiled
+// in for TerrainArgs (and VolumeColliderArgs, which carries one) alone, the volume branch for VolumeColliderArgs alone (no run-time test of a table
+// pointer), so without a heightfield the code is that of the analytic shapes and without a volume that of the terrain.  The kind is wave-uniform; an
+// empty slot (kind 0) does nothing.
+template<class Args>
+MPM_DEV void slot_resolve(const Args& a, int s, const CollisionPose& pose, const float (&X)[3], float (&vel)[3]) {
+#pragma clang fp contract(off)
+	const ShapeSlot& c = shape_args(a).slot[s];
+	if constexpr(!std::is_same_v<Args, ShapeArgs>)
+		if(c.shape.kind == kShapeHeightfield) return heightfield_resolve(c.obj, pose, terrain_args(a).hf[s], X, vel);
+	if constexpr(std::is_same_v<Args, VolumeColliderArgs>)
+		if(c.shape.kind == kShapeVolume) return volume_resolve(c.obj, pose, a.vol[s], X, vel);
+	if(c.shape.kind != 0) shape_resolve(c.obj, pose, c.shape, X, vel);
+}
+// ... at the slot's own pose: a prescribed collider.
+template<class Args>
+MPM_DEV void slot_resolve(const Args& a, int s, const float (&X)[3], float (&vel)[3]) {
+	slot_resolve(a, s, shape_args(a).slot[s].pose, X, vel);
+}
 template<class Args>
 MPM_DEV float grid_cell(const GridCfg& cfg, const Args& a, int kx, int ky, int kz, int cell, float dt, float4& v) {
 #pragma clang fp contract(off)
-	static_assert(std::is_same_v<Args, ShapeArgs> || std::is_same_v<Args, TerrainArgs> || std::is_same_v<Args, VolumeColliderArgs>, "a collider kind needs its grid_cell");
 	const ShapeArgs& col = shape_args(a);
 	float vel[3];
 	int node[3];
@@ -436,19 +463,7 @@ MPM_DEV float grid_cell(const GridCfg& cfg, const Args& a, int kx, int ky, int k
 	if(col.has_field) collision_resolve(col.field.obj, col.field.pose, node, cfg.dx, cfg.G * 4, (float) cfg.boundary * cfg.dx * 4.f, (float) (cfg.G - cfg.boundary) * 4.f * cfg.dx, vel);
 	const float X[3] = {(float) node[0] * cfg.dx, (float) node[1] * cfg.dx, (float) node[2] * cfg.dx};
 #pragma nounroll
-	for(int s = 0; s < col.count; ++s) {
-		if constexpr(std::is_same_v<Args, TerrainArgs> || std::is_same_v<Args, VolumeColliderArgs>)
-			if(col.slot[s].shape.kind == kShapeHeightfield) {
-				heightfield_resolve(col.slot[s].obj, col.slot[s].pose, terrain_args(a).hf[s], X, vel);
-				continue;
-			}
-		if constexpr(std::is_same_v<Args, VolumeColliderArgs>)
-			if(col.slot[s].shape.kind == kShapeVolume) {
-				volume_resolve(col.slot[s].obj, col.slot[s].pose, a.vol[s], X, vel);
-				continue;
-			}
-		if(col.slot[s].shape.kind != 0) shape_resolve(col.slot[s].obj, col.slot[s].pose, col.slot[s].shape, X, vel);
-	}
+	for(int s = 0; s < col.count; ++s) slot_resolve(a, s, X, vel);
 	return grid_cell_store_doubled_q(vel, v);
 }
 // The stand-alone frame: one wave per grid block, lane = cell.  The kernel of the phase-level callers (mpm_grid_update, mpm_substep, the

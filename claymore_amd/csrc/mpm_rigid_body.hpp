@@ -12,8 +12,9 @@
 //      NumPy with the same bits;
 //   2. the host side (plain C++): the start state from a collider's pose, the checks of an install, the mass properties of the analytic shapes
 //      (closed forms) and of a closed triangle mesh (float64 polyhedral integrals);
-//   3. the kernels (HIP only): BodyArgs and its load_cell, grid_update_body_kernel (ONE pass over the grid in collider_loads_kernel's frame: the
-//      update and its loads together) and body_step_kernel (collider_loads_reduce_kernel's additions, then one lane per body runs body_step).
+//   3. the kernels (HIP only): BodyArgs with its slot_resolve and row_pivot - what a body adds to the one cell walk and the one load frame of
+//      mpm_collider_loads.hpp -, grid_update_body_kernel (ONE pass over the grid, loads_frame with the stores: the update and its loads together)
+//      and body_step_kernel (load_totals, the readout's reduction, then one lane per body runs body_step).
 //
 // THE STEP, h = (double) dt, J and L the slot's row sums (impulse and angular impulse ON THE COLLIDER, L about x):
 //   1. v <- v + (J + h force) (1 / mass), and + (double) gravity * h on y if the gravity flag is set; locked components become 0; x <- x + h v
@@ -382,167 +383,63 @@ struct BodyArgs {
 	const BodyState* state;
 	int mask, state_pivots;
 };
+template<class Collider>
+constexpr bool kCarriesBodies = std::is_same_v<Collider, BodyArgs>;// (what the host's launches ask instead of naming the type)
 MPM_DEV const ShapeArgs& shape_args(const BodyArgs& a) { return a.va.ter.col; }
 
-// load_cell with bodies among the slots.  A body slot at the node X, in this order and without contraction:
-//   r = X - shift;  vb = vel + omega x r (a true cross product);  rel = velocity - vb;  r2 = rel;  <shape|volume>_resolve(obj0, pose, ..., r2)
+// slot_resolve with bodies among the slots: BodyArgs' part in load_cell, whose every other statement is the prescribed colliders'.  A body slot at
+// the node X, in this order and without contraction:
+//   r = X - shift;  vb = vel + omega x r (a true cross product);  rel = velocity - vb;  r2 = rel;  slot_resolve(..., pose, X, r2)
 //   if any component of r2 differs from rel IN ITS BITS (a NaN differs): velocity = r2 + vb;  else the node is not touched and its velocity keeps
 //   its bits.  (On bits, so that a response which turns -0 into +0 - `v - v_obj + v_obj` with v_obj = 0 - does so for a body at rest as well.)
-// with pose = {rot, shift} of the BodyPose, inv = 1, growth = 0.  Everything else is the generic load_cell's statements.
-template<class Sink>
-MPM_DEV void load_cell(const GridCfg& cfg, const BodyArgs& a, int kx, int ky, int kz, int cell, float dt, bool active, const float4& v, Sink&& sink) {
+// with pose = {rot, shift} of the BodyPose, inv = 1, growth = 0.
+MPM_DEV void slot_resolve(const BodyArgs& a, int s, const float (&X)[3], float (&vel)[3]) {
 #pragma clang fp contract(off)
-	float vel[3] = {0.f, 0.f, 0.f}, dv[3] = {0.f, 0.f, 0.f};
-	int node[3]	 = {kx * 4 + (cell >> 4), ky * 4 + ((cell >> 2) & 3), kz * 4 + (cell & 3)};
-	if(active) {
-		grid_cell_walls_gravity(cfg, kx, ky, kz, cell, dt, v, vel, node);
-		const bool wx = kx < cfg.boundary || kx >= cfg.G - cfg.boundary;
-		const bool wy = ky < cfg.boundary || ky >= cfg.G - cfg.boundary;
-		const bool wz = kz < cfg.boundary || kz >= cfg.G - cfg.boundary;
-		const float mass_inv = 1.f / v.x;
-		dv[0] = wx ? 0.0f - v.y * mass_inv : 0.0f;
-		dv[1] = wy ? 0.0f - v.z * mass_inv : 0.0f;
-		dv[2] = wz ? 0.0f - v.w * mass_inv : 0.0f;
+	if(!((a.mask >> s) & 1)) return slot_resolve(a.va, s, X, vel);
+	const BodyPose& bp = a.pose[s];// (wave-uniform: s is)
+	CollisionPose pose;
+#pragma unroll
+	for(int i = 0; i < 9; ++i) pose.rot[i] = bp.rot[i];
+	pose.inv = 1.f, pose.growth = 0.f;
+	float r[3], vb[3], rel[3], r2[3];
+#pragma unroll
+	for(int d = 0; d < 3; ++d) pose.shift[d] = bp.shift[d], r[d] = X[d] - bp.shift[d];
+	vb[0] = bp.vel[0] + (bp.omega[1] * r[2] - bp.omega[2] * r[1]);
+	vb[1] = bp.vel[1] + (bp.omega[2] * r[0] - bp.omega[0] * r[2]);
+	vb[2] = bp.vel[2] + (bp.omega[0] * r[1] - bp.omega[1] * r[0]);
+#pragma unroll
+	for(int d = 0; d < 3; ++d) rel[d] = vel[d] - vb[d], r2[d] = rel[d];
+	slot_resolve(a.va, s, pose, X, r2);
+	auto differs = [](float x, float y) { return __float_as_uint(x) != __float_as_uint(y) || x != x; };
+	if(differs(r2[0], rel[0]) || differs(r2[1], rel[1]) || differs(r2[2], rel[2])) {
+#pragma unroll
+		for(int d = 0; d < 3; ++d) vel[d] = r2[d] + vb[d];
 	}
-	auto touched = [&]() { return active && !(dv[0] == 0.0f && dv[1] == 0.0f && dv[2] == 0.0f); };
-	sink(kLoadWallRow, touched(), node, dv, vel);
-	auto row = [&](int r, auto&& resolve) {
-		const float before[3] = {vel[0], vel[1], vel[2]};
-		if(active) resolve();
-#pragma unroll
-		for(int d = 0; d < 3; ++d) dv[d] = vel[d] - before[d];
-		sink(r, touched(), node, dv, vel);
-	};
-	const float bc_lo = (float) cfg.boundary * cfg.dx * 4.f, bc_hi = (float) (cfg.G - cfg.boundary) * 4.f * cfg.dx;
-	const ShapeArgs& col = a.va.ter.col;
-	int here = 0;// (the generic load_cell says why)
-	asm volatile("" : "+s"(here));
-	const CollisionArgs& field = (&col.field)[here];
-	if(col.has_field) row(0, [&]() { collision_resolve(field.obj, field.pose, node, cfg.dx, cfg.G * 4, bc_lo, bc_hi, vel); });
-	const float X[3] = {(float) node[0] * cfg.dx, (float) node[1] * cfg.dx, (float) node[2] * cfg.dx};
-#pragma nounroll
-	for(int s = 0; s < col.count; ++s) {
-		const int kind = col.slot[s].shape.kind;
-		if(kind == 0) continue;
-		auto resolve = [&](const CollisionPose& pose, float (&u)[3]) {
-			if(kind == kShapeHeightfield)
-				heightfield_resolve(col.slot[s].obj, pose, a.va.ter.hf[s], X, u);
-			else if(kind == kShapeVolume)
-				volume_resolve(col.slot[s].obj, pose, a.va.vol[s], X, u);
-			else
-				shape_resolve(col.slot[s].obj, pose, col.slot[s].shape, X, u);
-		};
-		if((a.mask >> s) & 1) {
-			row(1 + s, [&]() {
-				const BodyPose& bp = a.pose[s];// (wave-uniform: s is)
-				CollisionPose pose;
-#pragma unroll
-				for(int i = 0; i < 9; ++i) pose.rot[i] = bp.rot[i];
-				pose.inv = 1.f, pose.growth = 0.f;
-				float r[3], vb[3], rel[3], r2[3];
-#pragma unroll
-				for(int d = 0; d < 3; ++d) pose.shift[d] = bp.shift[d], r[d] = X[d] - bp.shift[d];
-				vb[0] = bp.vel[0] + (bp.omega[1] * r[2] - bp.omega[2] * r[1]);
-				vb[1] = bp.vel[1] + (bp.omega[2] * r[0] - bp.omega[0] * r[2]);
-				vb[2] = bp.vel[2] + (bp.omega[0] * r[1] - bp.omega[1] * r[0]);
-#pragma unroll
-				for(int d = 0; d < 3; ++d) rel[d] = vel[d] - vb[d], r2[d] = rel[d];
-				resolve(pose, r2);
-				auto differs = [](float x, float y) { return __float_as_uint(x) != __float_as_uint(y) || x != x; };
-				if(differs(r2[0], rel[0]) || differs(r2[1], rel[1]) || differs(r2[2], rel[2])) {
-#pragma unroll
-					for(int d = 0; d < 3; ++d) vel[d] = r2[d] + vb[d];
-				}
-			});
-		} else
-			row(1 + s, [&]() { resolve(col.slot[s].pose, vel); });
+}
+// A body row's pivot is the state's x, read here, where state_pivots says so (mpm_collider_loads' default for a body, and every applied update's).
+MPM_DEV void row_pivot(const BodyArgs& a, const LoadPivots& piv, int row, double (&p)[3]) {
+	p[0] = piv.p[row][0], p[1] = piv.p[row][1], p[2] = piv.p[row][2];
+	if(row >= 1 && row <= kMaxBodies && ((a.state_pivots >> (row - 1)) & 1)) {
+		const BodyState& st = a.state[row - 1];
+		p[0] = st.x[0], p[1] = st.x[1], p[2] = st.x[2];
 	}
 }
 
-// The grid update with bodies, ONE pass in collider_loads_kernel's frame: kLoadGroups workgroups, the same walk over the blocks, the same wave
-// reduction into per-wave LDS rows - hence the same order of every addition, and totals that equal mpm_collider_loads' bit for bit.  Per massed
-// cell load_cell runs once; with APPLY the final velocity is stored and the doubled |v|^2 folded into the max slots.  Without APPLY this is the
-// readout itself (mpm_collider_loads and the gauge with a body installed: a body row's default pivot is the state's x, read here).
-template<class Collider, bool APPLY>
+// The grid update with bodies, ONE pass: loads_frame with the stores - the readout's walk over the blocks, its wave reduction into per-wave LDS
+// rows, hence the same order of every addition, and totals that equal mpm_collider_loads' bit for bit, because they are the same statements.
+// (The readout with a body installed is collider_loads_kernel<BodyArgs>.)
+template<class Collider>
 __global__ __launch_bounds__(256) void grid_update_body_kernel(GridCfg cfg, const int* __restrict__ nbc_ptr, float* grid, const int* __restrict__ keys, float dt, Collider col, LoadPivots piv, double* __restrict__ partials, unsigned* __restrict__ max_vel_bits) {
-#pragma clang fp contract(off)
-	__shared__ double s_part[4][kLoadRows][kLoadSums];
-	const int cell = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	for(int i = threadIdx.x; i < 4 * kLoadRows * kLoadSums; i += 256) (&s_part[0][0][0])[i] = 0.0;
-	__syncthreads();
-	const int nblocks = min(*nbc_ptr, cfg.cap);
-	float vel_sqr	  = 0.f;
-	for(int blockno = (blockIdx.x * 256 + threadIdx.x) >> 6; blockno < nblocks; blockno += gridDim.x * 4) {
-		const int kx = keys[3 * blockno], ky = keys[3 * blockno + 1], kz = keys[3 * blockno + 2];
-		float* g	 = grid + (size_t) blockno * 256 + cell;
-		float4 v	 = {g[0], 0.f, 0.f, 0.f};
-		const bool active = v.x > 0.0f;
-		if(active) {
-			v.y = g[64];
-			v.z = g[128];
-			v.w = g[192];
-		}
-		float fv[3] = {0.f, 0.f, 0.f};// the velocity the last collider left
-		load_cell(cfg, col, kx, ky, kz, cell, dt, active, v, [&](int row, bool touched, const int (&node)[3], const float (&dv)[3], const float (&vel)[3]) {
-#pragma clang fp contract(off)
-			fv[0] = vel[0], fv[1] = vel[1], fv[2] = vel[2];
-			if(!__any(touched)) return;
-			double p0 = piv.p[row][0], p1 = piv.p[row][1], p2 = piv.p[row][2];
-			if(row >= 1 && row <= kMaxBodies && ((col.state_pivots >> (row - 1)) & 1)) {
-				const BodyState& st = col.state[row - 1];
-				p0 = st.x[0], p1 = st.x[1], p2 = st.x[2];
-			}
-			const double m	= (double) v.x;
-			const double j0 = touched ? -(m * (double) dv[0]) : 0.0, j1 = touched ? -(m * (double) dv[1]) : 0.0, j2 = touched ? -(m * (double) dv[2]) : 0.0;
-			const double r0 = (double) ((float) node[0] * cfg.dx) - p0, r1 = (double) ((float) node[1] * cfg.dx) - p1, r2 = (double) ((float) node[2] * cfg.dx) - p2;
-			const double l0 = touched ? r1 * j2 - r2 * j1 : 0.0, l1 = touched ? r2 * j0 - r0 * j2 : 0.0, l2 = touched ? r0 * j1 - r1 * j0 : 0.0;
-			const double n = (double) __popcll(__ballot(touched));
-			const double s1 = load_wave_sum(j0), s2 = load_wave_sum(j1), s3 = load_wave_sum(j2);
-			const double s4 = load_wave_sum(l0), s5 = load_wave_sum(l1), s6 = load_wave_sum(l2);
-			const double s7 = load_wave_sum(touched ? m : 0.0);
-			if(cell == 0) {
-				double* p = s_part[wave][row];
-				p[0] += n, p[1] += s1, p[2] += s2, p[3] += s3, p[4] += s4, p[5] += s5, p[6] += s6, p[7] += s7;
-			}
-		});
-		if constexpr(APPLY) {
-			if(active) {
-				vel_sqr = fmaxf(vel_sqr, grid_cell_store_doubled_q(fv, v));
-				g[64]	= v.y;
-				g[128]	= v.z;
-				g[192]	= v.w;
-			}
-		}
-	}
-	if constexpr(APPLY) wave_max_vel(vel_sqr, max_vel_bits);
-	__syncthreads();
-	if(threadIdx.x < kLoadRows * kLoadSums) {
-		const double* p = &s_part[0][0][0] + threadIdx.x;
-		partials[(size_t) blockIdx.x * (kLoadRows * kLoadSums) + threadIdx.x] = ((p[0] + p[kLoadRows * kLoadSums]) + p[2 * kLoadRows * kLoadSums]) + p[3 * kLoadRows * kLoadSums];
-	}
+	loads_frame<true>(cfg, nbc_ptr, grid, keys, dt, col, piv, partials, max_vel_bits);
 }
 
-// One workgroup of kLoadReduceThreads: collider_loads_reduce_kernel's additions in its order, then lane s < kMaxBodies of wave 0 steps body s of
-// `mask` with its row's totals and writes BodyState and BodyPose.  A non-finite J, L or state raises the status block's non-finite flag.
+// One workgroup of kLoadReduceThreads: load_totals - the readout's reduction -, then lane s < kMaxBodies of wave 0 steps body s of `mask` with its
+// row's totals and writes BodyState and BodyPose.  A non-finite J, L or state raises the status block's non-finite flag.
 __global__ __launch_bounds__(kLoadReduceThreads) void body_step_kernel(const double* __restrict__ partials, int groups, BodyBlock* __restrict__ blk, int mask, float dt, float gravity, int* __restrict__ nonfinite) {
 #pragma clang fp contract(off)
-	constexpr int E = kLoadRows * kLoadSums, W = kLoadReduceThreads / 64;
-	__shared__ double s_sum[W][E];
-	__shared__ double s_tot[E];
-	const int e = threadIdx.x & 63, w = threadIdx.x >> 6;
-	if(e < E) {
-		const int per = (groups + W - 1) / W;
-		double sum	  = 0.0;
-		for(int g = w * per; g < min(groups, (w + 1) * per); ++g) sum += partials[(size_t) g * E + e];
-		s_sum[w][e] = sum;
-	}
-	__syncthreads();
-	if(threadIdx.x < E) {
-		double total = s_sum[0][threadIdx.x];
-#pragma unroll
-		for(int i = 1; i < W; ++i) total += s_sum[i][threadIdx.x];
-		s_tot[threadIdx.x] = total;
-	}
+	__shared__ double s_tot[kLoadRows * kLoadSums];
+	const double total = load_totals(partials, groups);
+	if(threadIdx.x < kLoadRows * kLoadSums) s_tot[threadIdx.x] = total;
 	__syncthreads();
 	if(threadIdx.x < kMaxBodies && ((mask >> threadIdx.x) & 1)) {
 		const int s		= threadIdx.x;

@@ -14,6 +14,7 @@ import collider_load_model as lm
 import collision_shape_model as sm
 import collision_volume_model as vm
 import grid_update_model as gm
+import heightfield_model as hm
 import rigid_body_model as bm
 from claymore_amd import _ffi, scenes
 from claymore_amd.engine import EngineError, build_engine
@@ -106,6 +107,17 @@ def test_two_bodies_a_prescribed_collider_the_field_and_the_walls(ctx):
     nr, loads = check_update(ctx, 11, [a, p, None, b], bodies, field=(f, sdf, grad))
     assert nr["used"] == [lm.WALLS, 0, 1, 2, 4] and (loads[[0, 1, 2, 4, 5], 0] > 100).all(), loads[:, 0]
     assert (nr["touched"][1] & nr["touched"][4]).sum() > 20                                # slot 3 acts on what slot 0 left
+
+
+def test_two_bodies_around_a_prescribed_heightfield_and_a_prescribed_volume(ctx):
+    """Every kind of the slot dispatch in one walk with bodies installed: a sphere body, tests/test_collision_volume_gpu.py's mixed-slots heightfield
+    (it cuts the block), a prescribed volume, a tilted box body."""
+    a = sm.make("sphere", type=1, friction=0.3, trans_vel=(0.2, -0.1, 0.3), omega=(1.0, 2.0, -1.0))
+    h = hm.make("65x65", type=1, friction=0.3, trans_vel=(0.5, 0.0, 0.0))
+    v = vm.sphere_volume(shape="box", type=1, friction=0.3, trans_vel=(0.0, 0.5, 0.0))
+    b = sm.make("box", type=2, friction=0.25, trans=(0.5, 0.5, 0.5), rot_mat=sm.TILT, trans_vel=(-0.3, 0.2, 0.1), omega=(0.5, -1.5, 1.0))
+    nr, loads = check_update(ctx, 16, [a, h, v, b], {0: body(a["a"]), 3: body(b["a"], gravity=False)})
+    assert nr["used"] == [lm.WALLS, 1, 2, 3, 4] and (loads[[1, 2, 3, 4, 5], 0] > 0).all(), loads[:, 0]
 
 
 def test_capsule_body_and_mesh_built_volume_body(ctx):

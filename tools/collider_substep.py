@@ -11,7 +11,7 @@ Scene: C2 (one elastic sphere of ~5 M particles dropped at 256^3; the level-set 
 kernel evaluates it at every grid node with mass either way, which is the cost in question.  A library without the clock's entry points
 (a parent build) runs `none` and `static` only.  `shape`: the same sphere given in closed form (mpm_set_collision_shape: no field, no loads);
 `body`: that sphere as a rigid body (mpm_set_collider_body, every axis locked, so at rest like the prescribed one: mpm_run_fixed then applies every update through grid_update_body_kernel +
-body_step_kernel, unfused); `shapes4`: that sphere, a floor half-space, a box and a capsule in the four slots, all clear of the material.  A library without
+body_step_kernel, unfused; with --loads the readout ahead of it is collider_loads_kernel<BodyArgs>, the same frame without the stores); `shapes4`: that sphere, a floor half-space, a box and a capsule in the four slots, all clear of the material.  A library without
 mpm_set_collision_shape skips both.  `ground_hf` / `ground_shape` / `ground_field`: one flat ground just under the material given three ways -
 a heightfield (mpm_set_collision_heightfield: an (N + 1)^2 table of constant height at spacing dx, four float4 gathers per massed cell), the
 half-space shape at that height, and the level set of the same plane (sdf = y - height, gradient +y) - the same physics (the level set

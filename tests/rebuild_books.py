@@ -159,10 +159,14 @@ def census_findings(cur, pbc, size, pos_keys, listed_in, where=()):
     return F
 
 
-def check_books(ckpt, rows_per_model, bits, max_ppc, counts=None):
+def check_books(ckpt, rows_per_model, bits, max_ppc, counts=None, loaded=False):
     """ckpt: a checkpoint saved after a rebuild; rows_per_model: per model the (particle blocks, 64) int rows of mpm_dump_block_rows; counts
     (optional): the per-model particle counts of mpm_get_counts.  The caller asserts mpm_check_table == 0 (the dense tables are not in a
     checkpoint; here "the table" of a numbering is its key list).
+
+    loaded: the checkpoint was saved right after mpm_checkpoint_load, before any rebuild.  The loader lays the lists out anew - unpack_lists_kernel
+    puts block b's list into row b and writes row_of[b] = b for every model that holds a particle -, so row_of is held to the identity there
+    instead of to the block's number in the previous numbering (what the compaction of a rebuild writes).  Everything else is held as it is.
 
     Lanes 0 .. 26 of a row are held to -1 where the previous numbering has no block at key + dir(l) (a key outside the domain included) and
     to binoff_src of that block where it was a PARTICLE block of the previous numbering.  Where it was a neighbour or exterior block the lane
@@ -217,6 +221,8 @@ def check_books(ckpt, rows_per_model, bits, max_ppc, counts=None):
         pk = block_keys(pos[ok])
         F += census_findings(cur, pbc, size, pk, blk[ok], where=(m,))
         want_row = np.array([prev_t.get(tuple(k), -1) for k in cur[:pbc].tolist()], dtype=np.int64).reshape(-1)
+        if loaded:
+            want_row = np.arange(pbc) if M["bucketed"] else np.full(pbc, -1)
         bad = np.flatnonzero((want_row >= 0) & (row_of != want_row))
         if bad.size:
             F.append(("row_of", m, bad[:4].tolist(), row_of[bad[:4]].tolist(), want_row[bad[:4]].tolist()))

@@ -209,6 +209,7 @@ HIP_ONLY = {
     "test_mesh_fill": (_i, [_i, _vp, _sz, _vp, _sz, _P(MeshFill), _P(C.c_double), _i]),
     "add_model_particles": (_i, [_vp, _i, _P(MaterialParams), _vp, _sz, _fp, _P(ParticleInit), _ip]),
     "set_model_velocity_field": (_i, [_vp, _i, _fp, _fp, _fp]),
+    "emit_particles": (_i, [_vp, _i, _vp, _sz, _fp, _P(ParticleInit), _P(C.c_int32)]),
     "checkpoint_size": (_i, [_vp, _P(_sz)]),
     "checkpoint_save": (_i, [_vp, _vp, _sz, _P(_sz)]),
     "checkpoint_load": (_i, [_vp, _vp, _sz]),

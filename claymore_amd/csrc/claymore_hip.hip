@@ -22,6 +22,7 @@
 #include "mpm_mesh_fill.hpp"
 #include "mpm_particle_init.hpp"
 #include "mpm_particle_ids.hpp"
+#include "mpm_particle_emit.hpp"
 #include "mpm_collider_loads.hpp"
 #include "mpm_rigid_body.hpp"
 #include "mpm_storage.hpp"
@@ -685,6 +686,40 @@ static int check_status(mpm_ctx* ctx) {
 	return MPM_OK;
 }
 
+// The particles one model is laid out from, in one order: set-up's own arrays, or the staging columns of an emission (mpm_particle_emit.hpp).
+struct LayModel {
+	size_t n;
+	const float* xyz;
+	ParticleInit init;
+	bool with_state;// the bins take the material state from init (fill_bins_state_kernel), else the stress-free one (fill_bins_kernel)
+	const int* staged_ids;// tracked contexts: the id of particle i (null: i itself, fill_ids_kernel)
+};
+// Model mi into the blocks of `table` (pbc particle blocks; the two partitions hold the same numbering): particles bucketed per block, bins handed out,
+// bins and identity advection records filled, ids beside them.  m.list[1] is left holding the particle indices by block, m.size their counts.
+static int lay_model_bins(mpm_ctx* ctx, size_t mi, const int* table, int pbc, const LayModel& in) {
+	Model& m	  = ctx->models[mi];
+	const GridCfg& g = ctx->g;
+	hipStream_t s = ctx->s_compute;
+	const int r = ctx->rollid, n = r ^ 1;
+	HIP_TRY(hipMemsetAsync(m.keep, 0xff, sizeof(int) * ((size_t) g.cap + 1), s));
+	if(in.n) bucket_particles_kernel<<<cdiv(in.n, 256), 256, 0, s>>>(g, in.n, in.xyz, table, m.out_count, m.list[1], ctx->d_status);
+	if(pbc) {
+		init_bins_kernel<<<cdiv(pbc, 256), 256, 0, s>>>(pbc, m.out_count, m.size, m.row_of, m.binoff[r], m.binoff[n], &ctx->d_status[ST_BINS0 + mi]);
+		if(in.with_state)// a per-particle material state (mpm_particle_init.hpp)
+			fill_bins_state_kernel<<<pbc, 256, 0, s>>>(g, m.nch, m.mc.log_jp0, in.xyz, m.list[1], m.size, m.binoff[r], m.bins[r], m.list[0], in.init);
+		else
+			fill_bins_kernel<<<pbc, 256, 0, s>>>(g, m.nch, m.mc.log_jp0, in.xyz, m.list[1], m.size, m.binoff[r], m.bins[r], m.list[0]);
+		if(ctx->track_ids) {
+			if(in.staged_ids)
+				emit_fill_ids_kernel<<<pbc, 256, 0, s>>>(g.ppb, m.list[1], m.size, m.binoff[r], in.staged_ids, m.ids[r]);
+			else
+				fill_ids_kernel<<<pbc, 256, 0, s>>>(g.ppb, m.list[1], m.size, m.binoff[r], m.ids[r]);
+		}
+	}
+	m.list_in = 0;
+	return MPM_OK;
+}
+
 // initial_setup, gmpm_simulator.cuh:637-781
 int mpm_initial_setup(mpm_ctx* ctx) {
 	phase_call(ctx);
@@ -772,17 +807,7 @@ int mpm_initial_setup(mpm_ctx* ctx) {
 		Model& m  = ctx->models[mi];
 		m.bin_cap = m.n / kBin + cap + 1;
 		HIP_TRY(size_bin_arrays(ctx, m, m.bin_cap));
-		HIP_TRY(hipMemsetAsync(m.keep, 0xff, sizeof(int) * (cap + 1), s));
-		if(m.n) bucket_particles_kernel<<<cdiv(m.n, 256), 256, 0, s>>>(g, m.n, m.d_xyz, P.table, m.out_count, m.list[1], ctx->d_status);
-		if(pbc) {
-			init_bins_kernel<<<cdiv(pbc, 256), 256, 0, s>>>(pbc, m.out_count, m.size, m.row_of, m.binoff[r], m.binoff[n], &ctx->d_status[ST_BINS0 + mi]);
-			if(m.d_init_state.n || m.d_init_logjp.n)// a per-particle material state (mpm_particle_init.hpp)
-				fill_bins_state_kernel<<<pbc, 256, 0, s>>>(g, m.nch, m.mc.log_jp0, m.d_xyz, m.list[1], m.size, m.binoff[r], m.bins[r], m.list[0], particle_init_view(m));
-			else
-				fill_bins_kernel<<<pbc, 256, 0, s>>>(g, m.nch, m.mc.log_jp0, m.d_xyz, m.list[1], m.size, m.binoff[r], m.bins[r], m.list[0]);
-			if(ctx->track_ids) fill_ids_kernel<<<pbc, 256, 0, s>>>(g.ppb, m.list[1], m.size, m.binoff[r], m.ids[r]);
-		}
-		m.list_in = 0;
+		if(int rc = lay_model_bins(ctx, mi, P.table, pbc, {m.n, m.d_xyz, particle_init_view(m), m.d_init_state.n || m.d_init_logjp.n, nullptr})) return rc;
 	}
 	int rc = read_status(ctx);// bin totals of the models
 	if(rc) return rc;
@@ -1250,6 +1275,269 @@ int mpm_rebuild_partition(mpm_ctx* ctx, mpm_counts* counts) {
 	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
 	HIP_TRY(hipSetDevice(ctx->device));
 	return rebuild_and_sync(ctx, default_plan(ctx), counts);
+}
+
+// Particle emission (mpm_particle_emit.hpp): a re-lay at a substep boundary.  PHASE 1 reads the context and writes scratch alone - every
+// live particle gathered into staging columns, the new ones appended and checked, the merged set's partition built in a scratch table and counted - so
+// that every refusal leaves the context as it was.  PHASE 2 grows what has to grow, then lays the merged columns out with set-up's own kernels
+// (lay_model_bins, launch_prepare), carries the old grid over by block key and rasterises the new particles on top.
+namespace {
+struct EmitColumns {
+	DevBuf<float> xyz, state9, logjp;
+	DevBuf<int> ids;
+	bool tracked = false;
+	size_t live = 0, total = 0;
+	EmitStage view() const { return EmitStage {xyz.p, state9.p, logjp.p, tracked ? ids.p : nullptr}; }
+};
+}// namespace
+int mpm_emit_particles(mpm_ctx* ctx, int model, const float* xyz, size_t n, const float v0[3], const mpm_particle_init* init, int32_t* first_id) {
+	if(!ctx) return MPM_ERR_INVALID;
+	const std::string who = "mpm_emit_particles";
+	if(!ctx->ready) return fail(ctx, MPM_ERR_NOT_READY, who + ": particles are emitted after mpm_initial_setup (before it, add them with the model)");
+	if(model < 0 || model >= (int) ctx->models.size()) return fail(ctx, MPM_ERR_INVALID, who + ": no model " + std::to_string(model));
+	if(!xyz && n) return fail(ctx, MPM_ERR_INVALID, who + ": positions are missing");
+	if(init) {
+		for(int r: init->reserved)
+			if(r) return fail(ctx, MPM_ERR_INVALID, who + ": a reserved word of mpm_particle_init is not 0");
+		if(init->state9 && init->state_kind != MPM_STATE_B && init->state_kind != MPM_STATE_F)
+			return fail(ctx, MPM_ERR_INVALID, who + ": unknown state_kind " + std::to_string(init->state_kind) + " (MPM_STATE_B or MPM_STATE_F)");
+	}
+	VelocityField f {};
+	for(int d = 0; d < 3; ++d) {
+		f.v0[d] = v0 ? v0[d] : 0.f;
+		if(!std::isfinite(f.v0[d])) return fail(ctx, MPM_ERR_INVALID, who + ": v0 is not finite");
+	}
+	if(ctx->group_refs > 0 || ctx->mgsp_rank >= 0 || ctx->halo_tagged || ctx->d_overlap.p)// (the halo arrays outlive a tagging that a checkpoint load has made stale)
+		return fail(ctx, MPM_ERR_INVALID, who + ": the context belongs (or belonged) to a multi-GPU group or has been through the halo tagging; emission into groups is not computed");
+	if(!ctx->grid_momentum || ctx->grid_preupdated)
+		return fail(ctx, MPM_ERR_INVALID, who + ": the grid holds velocities (a grid update without its rebuild): emit at a substep boundary");
+	if(ctx->track_ids && !ctx->ids_valid) return fail(ctx, MPM_ERR_INVALID, who + ": the ids are not valid (load them with mpm_particle_ids_load first)");
+	Model& M = ctx->models[model];
+	if(M.n + n > (size_t) 0x7fffffff) return fail(ctx, MPM_ERR_CAPACITY, who + ": a model holds at most 2^31 - 1 particles");
+	const int32_t old_n = (int32_t) M.n;
+	if(n == 0) {
+		if(first_id) *first_id = old_n;
+		return MPM_OK;
+	}
+	HIP_TRY(hipSetDevice(ctx->device));
+	HIP_TRY(hipDeviceSynchronize());
+	hipStream_t s		= ctx->s_compute;
+	const size_t nm		= ctx->models.size();
+	const size_t table	= (size_t) ctx->g.G * ctx->g.G * ctx->g.G;
+	const bool fluid	= M.material == MPM_J_FLUID;
+	const auto no_memory = [&](hipError_t e) { return e == hipSuccess ? 0 : fail(ctx, MPM_ERR_CAPACITY, who + ": no device memory for the staging arrays (" + hipGetErrorString(e) + ")"); };
+#define EMIT_ALLOC(expr)                      \
+	do {                                      \
+		if(int rc_ = no_memory(expr)) return rc_; \
+	} while(0)
+	// ---- phase 1: gather, append, check, count - the context is only read ----
+	std::vector<EmitColumns> cols(nm);
+	DevBuf<unsigned long long> d_gathered;
+	DevBuf<int> d_flags;// [0] emission's own, [1] validate_particle_init_kernel's
+	EMIT_ALLOC(d_gathered.alloc(nm, s));
+	EMIT_ALLOC(d_flags.alloc(2, s));
+	size_t total_particles = 0;
+	for(size_t mi = 0; mi < nm; ++mi) {
+		const Model& m = ctx->models[mi];
+		EmitColumns& c = cols[mi];
+		c.live		   = (size_t) m.bucketed;
+		c.total		   = c.live + ((int) mi == model ? n : 0);
+		c.tracked	   = ctx->track_ids;
+		total_particles += c.total;
+		EMIT_ALLOC(c.xyz.alloc(3 * c.total, s));
+		EMIT_ALLOC(c.state9.alloc(9 * c.total, s));
+		EMIT_ALLOC(c.logjp.alloc(c.total, s));
+		if(c.tracked) EMIT_ALLOC(c.ids.alloc(c.total, s));
+		if(c.live && ctx->pbc) emit_gather_kernel<<<ctx->pbc, kReadoutThreads, 0, s>>>(make_readout_args(ctx, m), c.view(), (unsigned long long) c.live, d_gathered + mi);
+	}
+	EmitColumns& E = cols[model];
+	HIP_TRY(hipMemcpyAsync(E.xyz + 3 * E.live, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, s));
+	DevBuf<float> d_velocity, d_affine, d_state, d_logjp;
+	ParticleInit a;
+	if(init) {
+		const bool with_logjp = init->logjp && (M.material == MPM_SAND || M.material == MPM_NACC);// (ignored where the material has no log Jp)
+		struct {
+			const float* host;
+			DevBuf<float>* dev;
+			const float** view;
+			size_t per;
+		} up[4] = {{init->velocity, &d_velocity, &a.velocity, 3}, {init->affine9, &d_affine, &a.affine9, 9}, {init->state9, &d_state, &a.state9, 9}, {with_logjp ? init->logjp : nullptr, &d_logjp, &a.logjp, 1}};
+		for(auto& c: up) {
+			if(!c.host) continue;
+			EMIT_ALLOC(c.dev->alloc(c.per * n, s));
+			HIP_TRY(hipMemcpyAsync(c.dev->p, c.host, sizeof(float) * c.per * n, hipMemcpyHostToDevice, s));
+			*c.view = c.dev->p;
+		}
+		a.state_f = init->state9 && init->state_kind == MPM_STATE_F ? 1 : 0;
+		if(a.velocity || a.affine9 || a.state9 || a.logjp) validate_particle_init_kernel<<<std::min(4096u, cdiv(n, 256)), 256, 0, s>>>(n, fluid, a, d_flags + 1);
+	}
+	emit_append_kernel<<<std::min(4096u, cdiv(n, 256)), 256, 0, s>>>(ctx->g, n, E.live, fluid, M.mc.log_jp0, old_n, a, E.view(), d_flags);
+	{
+		std::vector<unsigned long long> gathered(nm);
+		int flags[2] = {0, 0};
+		HIP_TRY(hipMemcpyAsync(gathered.data(), d_gathered, sizeof(unsigned long long) * nm, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipMemcpyAsync(flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipStreamSynchronize(s));
+		for(size_t mi = 0; mi < nm; ++mi)
+			if(gathered[mi] != cols[mi].live)
+				return fail(ctx, MPM_ERR_INTERNAL, who + ": the lists of model " + std::to_string(mi) + " hold " + std::to_string(gathered[mi]) + " particles, the books " + std::to_string(cols[mi].live));
+		if(flags[0] & kEmitBadPosition) return fail(ctx, MPM_ERR_INVALID, who + ": xyz holds a value that is not finite");
+		if(flags[0] & kEmitOutside) return fail(ctx, MPM_ERR_INVALID, who + ": particles outside the domain");
+		if(flags[1] & kInitBadVelocity) return fail(ctx, MPM_ERR_INVALID, who + ": velocity holds a value that is not finite");
+		if(flags[1] & kInitBadAffine) return fail(ctx, MPM_ERR_INVALID, who + ": affine9 holds a value that is not finite");
+		if(flags[1] & kInitBadState) return fail(ctx, MPM_ERR_INVALID, who + ": state9 holds a value that is not finite");
+		if(flags[1] & kInitBadLogJp) return fail(ctx, MPM_ERR_INVALID, who + ": logjp holds a value that is not finite");
+		if(flags[1] & kInitNotPositive) return fail(ctx, MPM_ERR_INVALID, who + (fluid ? ": state9 holds a J that is not strictly positive" : ": state9 holds a |b00|, b11 or b22 that is not strictly positive"));
+	}
+	// the partition of the merged set, in a scratch table with a status block of its own (the three kernels are set-up's, in set-up's order)
+	Partition S;
+	DevBuf<int> s_status;
+	GridCfg sg = ctx->g;
+	int pbc = 0, nbc = 0, ebc = 0;
+	{
+		EMIT_ALLOC(S.table.alloc(table, s));
+		EMIT_ALLOC(S.count.alloc(1, s));
+		EMIT_ALLOC(s_status.alloc(ST_WORDS, s));
+		HIP_TRY(hipMemsetAsync(S.table, 0xff, sizeof(int) * table, s));
+		size_t prov = std::min(table, total_particles + 1);
+		EMIT_ALLOC(S.keys.alloc(3 * prov, s));
+		sg.cap = (int) prov;
+		for(size_t mi = 0; mi < nm; ++mi)
+			if(cols[mi].total) activate_blocks_kernel<<<cdiv(cols[mi].total, 256), 256, 0, s>>>(sg, cols[mi].total, cols[mi].xyz, S.table, S.keys, S.count, s_status);
+		HIP_TRY(hipMemcpyAsync(&pbc, S.count, sizeof(int), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		if((size_t) pbc * 27 > prov) {// the scratch list holds every block that can be registered
+			prov = std::min(table, (size_t) pbc * 27 + 1);
+			EMIT_ALLOC(S.keys.grow(3 * prov, s));
+			sg.cap = (int) prov;
+		}
+		int* st = s_status;
+		HIP_TRY(hipMemcpyAsync(&st[ST_CNT_P], S.count, sizeof(int), hipMemcpyDeviceToDevice, s));
+		register_blocks_kernel<0, 1><<<std::max(1u, std::min(4096u, cdiv((size_t) pbc * 8, 256))), 256, 0, s>>>(sg, &st[ST_CNT_P], nullptr, &st[ST_CNT_N], &st[ST_PBC], S.table, S.keys, st, 0);
+		register_blocks_kernel<-1, 1><<<std::max(1u, std::min(8192u, cdiv((size_t) pbc * 32, 256))), 256, 0, s>>>(sg, &st[ST_CNT_P], &st[ST_CNT_N], &st[ST_CNT_E], &st[ST_NBC], S.table, S.keys, st, 0);
+		int hs[ST_WORDS];
+		HIP_TRY(hipMemcpyAsync(hs, st, sizeof(hs), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipStreamSynchronize(s));
+		if(hs[ST_OVERFLOW]) return fail(ctx, MPM_ERR_INTERNAL, who + ": the scratch partition overflowed");
+		nbc = hs[ST_NBC];
+		ebc = hs[ST_CNT_P] + hs[ST_CNT_N] + hs[ST_CNT_E];
+	}
+	const bool grow = ctx->cfg.grow != 0;
+	if(ebc > ctx->g.cap && !grow) return fail(ctx, MPM_ERR_CAPACITY, who + ": " + std::to_string(ebc) + " blocks needed, block capacity " + std::to_string(ctx->g.cap) + " (grow = 0)");
+	// per model and block: how many particles, how many bins
+	std::vector<DevBuf<int>> counts(nm);
+	std::vector<int> bins(nm, 0);
+	{
+		DevBuf<int> d_bins;
+		EMIT_ALLOC(d_bins.alloc(nm, s));
+		for(size_t mi = 0; mi < nm; ++mi) {
+			EMIT_ALLOC(counts[mi].alloc((size_t) pbc + 1, s));
+			if(!cols[mi].total) continue;
+			emit_count_kernel<<<cdiv(cols[mi].total, 256), 256, 0, s>>>(sg, cols[mi].total, cols[mi].xyz, S.table, counts[mi], d_flags);
+			emit_bins_kernel<<<cdiv(pbc, 256), 256, 0, s>>>(pbc, counts[mi], d_bins + mi);
+		}
+		int flag = 0;
+		HIP_TRY(hipMemcpyAsync(&flag, d_flags, sizeof(int), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipMemcpyAsync(bins.data(), d_bins, sizeof(int) * nm, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipStreamSynchronize(s));
+		if(flag & kEmitOutside) return fail(ctx, MPM_ERR_INTERNAL, who + ": a gathered particle has no block");
+		// (as at set-up: a block that starts with more particles than it has list slots is refused whatever the overflow policy)
+		if(flag & kEmitBlockFull) return fail(ctx, MPM_ERR_CAPACITY, who + ": a block would hold more than max_ppc*64 = " + std::to_string(ctx->g.ppb) + " particles");
+		for(size_t mi = 0; mi < nm; ++mi)
+			if((size_t) bins[mi] > ctx->models[mi].bin_cap && !grow)
+				return fail(ctx, MPM_ERR_CAPACITY, who + ": model " + std::to_string(mi) + " needs " + std::to_string(bins[mi]) + " bins, bin capacity " + std::to_string(ctx->models[mi].bin_cap) + " (grow = 0)");
+	}
+	// the old grid and its keys, kept aside
+	const int r = ctx->rollid, old_nbc = ctx->nbc;
+	DevBuf<float> old_grid;
+	DevBuf<int> old_keys;
+	EMIT_ALLOC(old_grid.alloc(256 * (size_t) old_nbc, s));
+	EMIT_ALLOC(old_keys.alloc(3 * (size_t) old_nbc, s));
+	HIP_TRY(hipMemcpyAsync(old_grid, ctx->grid[0], sizeof(float) * 256 * (size_t) old_nbc, hipMemcpyDeviceToDevice, s));
+	HIP_TRY(hipMemcpyAsync(old_keys, ctx->part[r].keys, sizeof(int) * 3 * (size_t) old_nbc, hipMemcpyDeviceToDevice, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	// ---- phase 2: nothing refuses from here on.  Capacities first (the growth policy's steps; every array keeps what it holds) ----
+	phase_call(ctx);
+	while(ebc > ctx->g.cap)
+		if(int rc = reserve_blocks(ctx, std::min(table, (size_t) ctx->g.cap * 3 / 2 + 1))) return rc;
+	const size_t new_n = M.n + n;
+	for(size_t mi = 0; mi < nm; ++mi) {
+		Model& m		  = ctx->models[mi];
+		const size_t need = std::max((size_t) bins[mi], grow ? ((int) mi == model ? new_n : m.n) / kBin + (size_t) ctx->g.cap + 1 : 0);
+		if(need > m.bin_cap)// (by the policy's 3/2 at the least: a tap emits layer after layer and must not regrow its bins for every one)
+			if(int rc = reserve_bins(ctx, m, std::max(need, m.bin_cap * 3 / 2 + 1))) return rc;
+	}
+	HIP_TRY(M.d_xyz.grow(3 * new_n, s));
+	const GridCfg& g = ctx->g;
+	// the partition, in both rolls (previous numbering == current numbering, as set-up leaves it), and the counts the kernels read
+	ctx->pbc = pbc, ctx->nbc = nbc, ctx->ebc = ebc, ctx->pbc_prev = pbc;
+	{
+		HIP_TRY(hipMemcpyAsync(ctx->h_status, ctx->d_status, sizeof(int) * ST_WORDS, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		int* st	   = ctx->h_status;
+		st[ST_PBC] = pbc, st[ST_NBC] = nbc, st[ST_EBC] = ebc, st[ST_PBCPREV] = pbc;
+		st[ST_CNT_P] = st[ST_CNT_N] = st[ST_CNT_E] = 0;
+		for(size_t mi = 0; mi < (size_t) kMaxModels; ++mi) {
+			st[ST_BINS0 + mi]	 = 0;// (init_bins_kernel hands the bins out from here)
+			st[ST_BINSPREV + mi] = mi < nm ? bins[mi] : 0;
+			st[ST_PART0 + mi]	 = mi < nm ? (int) cols[mi].total : 0;
+		}
+		HIP_TRY(hipMemcpyAsync(ctx->d_status, st, sizeof(int) * ST_WORDS, hipMemcpyHostToDevice, s));
+		for(int i = 0; i < 2; ++i) {
+			HIP_TRY(hipMemcpyAsync(ctx->part[i].table, S.table, sizeof(int) * table, hipMemcpyDeviceToDevice, s));
+			HIP_TRY(hipMemcpyAsync(ctx->part[i].keys, S.keys, sizeof(int) * 3 * (size_t) ebc, hipMemcpyDeviceToDevice, s));
+			HIP_TRY(hipMemcpyAsync(ctx->part[i].count, &st[ST_EBC], sizeof(int), hipMemcpyHostToDevice, s));
+		}
+		HIP_TRY(hipStreamSynchronize(s));
+	}
+	for(size_t mi = 0; mi < nm; ++mi) {
+		Model& m = ctx->models[mi];
+		HIP_TRY(hipMemsetAsync(m.size, 0, sizeof(int) * ((size_t) g.cap + 1), s));
+		HIP_TRY(hipMemsetAsync(m.out_count, 0, sizeof(int) * ((size_t) g.cap + 1), s));
+		if(m.pair)
+			for(int i = 0; i < 2; ++i) HIP_TRY(hipMemsetAsync(m.pairinfo[i], 0, sizeof(int) * ((size_t) g.cap + 1) * kPairChunks, s));
+		const EmitColumns& c = cols[mi];
+		ParticleInit staged;
+		staged.state9 = c.state9, staged.logjp = c.logjp;
+		if(int rc = lay_model_bins(ctx, mi, S.table, pbc, {c.total, c.xyz, staged, true, c.tracked ? c.ids.p : nullptr})) return rc;
+	}
+	// the grid: zero, the old blocks under their new numbers, the new particles on top (set-up's P2G of them alone; M.list[1] is free again)
+	HIP_TRY(hipMemsetAsync(ctx->grid[0], 0, sizeof(float) * 256 * (size_t) nbc, s));
+	HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof(int) * 2, s));
+	if(old_nbc) emit_carry_grid_kernel<<<std::min(2048u, cdiv(old_nbc, 4)), 256, 0, s>>>(g, old_nbc, nbc, old_keys, old_grid, ctx->part[r].table, ctx->grid[0], d_flags);
+	{
+		int* fresh = counts[model];
+		HIP_TRY(hipMemsetAsync(fresh, 0, sizeof(int) * ((size_t) pbc + 1), s));
+		const float* nxyz = E.xyz + 3 * E.live;
+		bucket_particles_kernel<<<cdiv(n, 256), 256, 0, s>>>(g, n, nxyz, ctx->part[r].table, fresh, M.list[1], s_status);
+		rasterize_particles_kernel<false><<<pbc, 256, 0, s>>>(g, nxyz, M.list[1], fresh, ctx->part[r].keys, ctx->part[r].table, ctx->grid[0], M.mc.mass, a, f);
+	}
+	int rc = launch_prepare(ctx, PrepareFor::Setup);
+	if(rc) return rc;
+	HIP_TRY(hipGetLastError());
+	rc = read_status(ctx);
+	if(rc) return rc;
+	{
+		int flag = 0;
+		HIP_TRY(hipMemcpy(&flag, d_flags, sizeof(int), hipMemcpyDeviceToHost));
+		if(flag & kEmitCarryMiss) return fail(ctx, MPM_ERR_INTERNAL, who + ": a block of the old grid has no number in the new partition");
+	}
+	// the books
+	M.n = new_n;
+	for(size_t mi = 0; mi < nm; ++mi) {
+		Model& m	   = ctx->models[mi];
+		m.bincount	   = ctx->h_status[ST_BINS0 + mi];
+		m.bincount_src = m.bincount;
+		m.bucketed	   = (int64_t) cols[mi].total;
+		if(m.bincount != bins[mi]) return fail(ctx, MPM_ERR_INTERNAL, who + ": model " + std::to_string(mi) + " took " + std::to_string(m.bincount) + " bins, " + std::to_string(bins[mi]) + " were counted");
+	}
+	ctx->relaid = true;
+	if(first_id) *first_id = old_n;
+#undef EMIT_ALLOC
+	return grow_capacity(ctx);// (the policy's own look at the new fill levels)
 }
 
 int mpm_substep(mpm_ctx* ctx, float dt, float step_time, float frame_time, float dt_default, float* next_dt, float* max_vel) {

@@ -81,6 +81,7 @@ class Engine:
             self._check(self.api.track_particle_ids(self.ctx, 1))
         self.models = []
         self._slot_geom = {}  # slot -> what set_collider_body(density=...) integrates over (_slot_geometry)
+        self.emitters = []    # scenes.Emitter objects, served by main_loop (serve_emitters)
         self.cur_time = 0.0
         self.dt = None
 
@@ -127,30 +128,53 @@ class Engine:
         else:
             if not hasattr(self.api, "add_model_particles"):
                 raise EngineError(_ffi.MPM_ERR_INVALID, "init_model: per-particle initial conditions need the HIP library (this API has no add_model_particles)")
-            if state_kind not in _ffi.STATE_KINDS:
-                raise ValueError(f"init_model: state_kind {state_kind!r} ('b' or 'f')")
-            keep = []                                                    # the arrays live until the call returns
-
-            def col(a, width, name, transpose=False):
-                if a is None:
-                    return None
-                a = np.asarray(a, dtype=np.float32)
-                if a.size != n * width:
-                    raise ValueError(f"init_model: {name} holds {a.size} values for {n} particles ({n * width} expected)")
-                if transpose and a.ndim == 3:                            # [p, r, c] -> the library's column-major 9 floats (index 3 c + r)
-                    a = a.transpose(0, 2, 1)
-                a = np.ascontiguousarray(a).reshape(n, width)
-                keep.append(a)
-                return a.ctypes.data
-            init = _ffi.ParticleInit()
-            init.velocity = col(velocity, 3, "velocity")
-            init.affine9 = col(affine, 9, "affine", transpose=True)
-            init.state9 = col(state, 9, "state", transpose=(state_kind == "f"))
-            init.logjp = col(logjp, 1, "logjp")
-            init.state_kind = _ffi.STATE_KINDS[state_kind]
+            init, keep = self._particle_init("init_model", n, velocity, affine, state, logjp, state_kind)   # (keep: the arrays live until the call returns)
             self._check(self.api.add_model_particles(self.ctx, int(material), C.byref(p), xyz.ctypes.data_as(C.c_void_p), n, v, C.byref(init), C.byref(mid)))
         self.models.append({"material": int(material), "n": n, "params": p})
         return mid.value
+
+    @staticmethod
+    def _particle_init(who, n, velocity, affine, state, logjp, state_kind):
+        """The four per-particle arrays of init_model / emit as an mpm_particle_init, and the float32 arrays it points into."""
+        if state_kind not in _ffi.STATE_KINDS:
+            raise ValueError(f"{who}: state_kind {state_kind!r} ('b' or 'f')")
+        keep = []
+
+        def col(a, width, name, transpose=False):
+            if a is None:
+                return None
+            a = np.asarray(a, dtype=np.float32)
+            if a.size != n * width:
+                raise ValueError(f"{who}: {name} holds {a.size} values for {n} particles ({n * width} expected)")
+            if transpose and a.ndim == 3:                            # [p, r, c] -> the library's column-major 9 floats (index 3 c + r)
+                a = a.transpose(0, 2, 1)
+            a = np.ascontiguousarray(a).reshape(n, width)
+            keep.append(a)
+            return a.ctypes.data
+        init = _ffi.ParticleInit()
+        init.velocity = col(velocity, 3, "velocity")
+        init.affine9 = col(affine, 9, "affine", transpose=True)
+        init.state9 = col(state, 9, "state", transpose=(state_kind == "f"))
+        init.logjp = col(logjp, 1, "logjp")
+        init.state_kind = _ffi.STATE_KINDS[state_kind]
+        return init, keep
+
+    def emit(self, model, positions, v0=(0.0, 0.0, 0.0), velocity=None, affine=None, state=None, logjp=None, state_kind="b"):
+        """Add particles to `model` of an engine that has been set up, at a substep boundary (mpm_emit_particles, HIP library only): an inflow.
+        The arguments are init_model's - positions (n, 3), v0 for every particle unless `velocity` (n, 3) is given, `affine`, `state`, `logjp`
+        and `state_kind` as there.  Returns first_id: the new particles are numbers first_id .. first_id + n - 1 of the model (their ids in a
+        track_ids engine).  Every old particle keeps its state bit for bit, the grid gains the new particles' set-up P2G; the call costs a
+        re-lay of all particles, so emit a layer at a time, not a particle at a time."""
+        if not hasattr(self.api, "emit_particles"):
+            raise EngineError(_ffi.MPM_ERR_INVALID, "emit needs the HIP library (this API has no emit_particles)")
+        xyz = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        n = xyz.shape[0]
+        init, keep = self._particle_init("emit", n, velocity, affine, state, logjp, state_kind)
+        first = C.c_int32(-1)
+        self._check(self.api.emit_particles(self.ctx, int(model), xyz.ctypes.data_as(C.c_void_p), n, (C.c_float * 3)(*[float(x) for x in v0]),
+                                            C.byref(init), C.byref(first)))
+        self.models[model]["n"] += n
+        return first.value
 
     def set_model_velocity_field(self, model, v0=(0.0, 0.0, 0.0), grad=None, omega=None, pivot=(0.0, 0.0, 0.0)):
         """Start a model that has been added (init_model or init_model_mesh, before initial_setup) in the linear velocity field
@@ -263,12 +287,27 @@ class Engine:
     def run_fixed(self, nsteps, dt):
         self._check(self.api.run_fixed(self.ctx, int(nsteps), dt))
 
+    def serve_emitters(self, t=None):
+        """Emit what every attached emitter (scenes.Emitter; build_engine attaches a scene's "emitters") has due at the substep boundary `t`
+        (default: cur_time).  Returns the number of particles emitted."""
+        t = self.cur_time if t is None else t
+        total = 0
+        for em in self.emitters:
+            pts = em.due(t)
+            if pts.shape[0]:
+                self.emit(em.model, pts, v0=em.velocity)
+                total += pts.shape[0]
+        return total
+
     def main_loop(self, nframes, fps, dt_default, on_frame=None):
-        """GmpmSimulator::main_loop (gmpm_simulator.cuh:303-592): adaptive dt, `nframes` frames."""
+        """GmpmSimulator::main_loop (gmpm_simulator.cuh:303-592): adaptive dt, `nframes` frames.  Attached emitters are served after set-up
+        and after every substep."""
         spf = 1.0 / fps
         max_v0 = 0.0
         dt = self.compute_dt(max_v0, 0.0, spf, dt_default)
         self.initial_setup()
+        if self.emitters:
+            self.serve_emitters()
         steps = 0
         for frame in range(1, nframes + 1):
             t = 0.0
@@ -278,6 +317,8 @@ class Engine:
                 self.cur_time += dt
                 dt = next_dt
                 steps += 1
+                if self.emitters:
+                    self.serve_emitters()
             if on_frame:
                 on_frame(frame, self)
         return steps
@@ -890,7 +931,8 @@ def weld_triangles(tris, vel=None):
 
 
 def build_engine(scene, device=0, api=None):
-    """Create an Engine for a scene dict (claymore_amd.scenes) and add its models (no setup yet).  scene["track_ids"]: Engine's track_ids."""
+    """Create an Engine for a scene dict (claymore_amd.scenes) and add its models (no setup yet).  scene["track_ids"]: Engine's track_ids;
+    scene["emitters"]: particle sources (scenes.Emitter.from_dict), attached as Engine.emitters and served by Engine.main_loop."""
     cfg = _ffi.Config()
     a = api if api is not None else _ffi.load_hip()
     rc = a.default_config(scene["bits"], C.byref(cfg))
@@ -930,4 +972,7 @@ def build_engine(scene, device=0, api=None):
     moving = [c for c in fields + list(colliders) if c.get("animate")]
     if moving:
         eng.set_collision_clock(True, float(moving[0].get("time", 0.0)))
+    if scene.get("emitters"):  # particle sources (scenes.Emitter), served by main_loop at the substep boundaries
+        from .scenes import Emitter
+        eng.emitters = [Emitter.from_dict(scene["bits"], e) for e in scene["emitters"]]
     return eng

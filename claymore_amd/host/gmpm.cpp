@@ -24,6 +24,9 @@
 // level-set object, the four slots, the domain walls), the force and torque on the collider averaged over the frame, the touched-node count and
 // the elapsed time (mpm_load_gauge_read at the frame's end).  A model object may carry "omega": [x, y, z] or "velocity_gradient": [9 numbers, row-major] with an
 // optional "pivot": the model starts in the linear velocity field v = velocity + G (x - pivot) (model_field.hpp, mpm_set_model_velocity_field).
+// A top-level "emitters" array holds particle sources (emitter_rule.hpp: a box or disc nozzle, a velocity, a start and an end time, a model):
+// what is due is added to its model between two mpm_substep calls (mpm_emit_particles), so later frames of that model carry more points; with
+// simulation.output_ids the new points have the largest ids and the ascending-id order of the older ones stays as it was.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -40,6 +43,7 @@
 #include "mini_json.hpp"
 #include "particle_io.hpp"
 #include "model_field.hpp"
+#include "emitter_rule.hpp"
 
 namespace {
 
@@ -634,6 +638,33 @@ int main(int argc, char** argv) {
 	std::printf("block count on device %d: %d, %d, %d\n", gpuid, c.particle_blocks, c.neighbor_blocks, c.exterior_blocks);
 	float cur_time = 0.f;
 	long steps	   = 0;
+	// "emitters": particle sources (emitter_rule.hpp), served at every substep boundary - after set-up and after each mpm_substep: what is due goes
+	// to its model through mpm_emit_particles with the emitter's velocity, and the frames of that model carry more points from then on
+	std::vector<pio::Emitter> emitters;
+	if(doc->has("emitters")) {
+		const mj::Value& list = (*doc)["emitters"];
+		for(size_t ei = 0; ei < list.arr.size(); ++ei) {
+			pio::Emitter em;
+			if(!pio::parse_emitter(list[ei], bits, em)) return 1;
+			if(em.model < 0 || em.model >= (int) counts.size()) {
+				std::fprintf(stderr, "gmpm: an emitter names model %d, the scene has %zu\n", em.model, counts.size());
+				return 1;
+			}
+			emitters.push_back(std::move(em));
+		}
+		std::printf("has %zu emitters\n", emitters.size());
+	}
+	auto serve_emitters = [&](double t) {
+		for(auto& em: emitters) {
+			const std::vector<float> pts = em.due(t);
+			if(pts.empty()) continue;
+			const float v[3] = {(float) em.velocity[0], (float) em.velocity[1], (float) em.velocity[2]};
+			const int re	 = mpm_emit_particles(ctx, em.model, pts.data(), pts.size() / 3, v, nullptr, nullptr);
+			if(re) die(ctx, re);
+			counts[em.model] += pts.size() / 3;
+		}
+	};
+	serve_emitters(0.0);
 	std::vector<float> buf, vbuf, sbuf;
 	pio::AsyncWriter io;
 	// simulation.output_surface: the iso-surface of the mass grid beside the frame (frame 0: the grid of the set-up's P2G): count, then fetch
@@ -711,6 +742,7 @@ int main(int argc, char** argv) {
 			cur_time += dt;
 			dt = next_dt;
 			++steps;
+			if(!emitters.empty()) serve_emitters((double) cur_time);
 		}
 		if(frame > frames) break;
 		mpm_get_counts(ctx, &c);

@@ -7,6 +7,7 @@
 #include "mini_json.hpp"
 #include "particle_io.hpp"
 #include "model_field.hpp"
+#include "emitter_rule.hpp"
 #include "../csrc/mpm_collision_mesh.hpp"
 #include "../csrc/mpm_mesh_fill.hpp"
 #if !defined(__HIPCC__)
@@ -37,6 +38,28 @@ int main(int argc, char** argv) {
 		double v[3];
 		f.at(at, v);
 		std::cout << " " << v[0] << " " << v[1] << " " << v[2] << "\n";
+		return 0;
+	}
+	if(argc >= 5 && !std::strcmp(argv[1], "--emitter")) {// host_selftest --emitter '{"shape": .., "velocity": .., ..}' BITS T1 [T2 ..]: an entry of a scene file's "emitters" ->
+		// per substep boundary (ascending times, as decimal or hex floats) "due N", then the N points gmpm would emit there, "x y z" as float32 bits in hex
+		mj::ValuePtr e;
+		try {
+			e = mj::parse(argv[2]);
+		} catch(const std::exception& ex) {
+			std::cerr << "cannot parse the emitter object: " << ex.what() << "\n";
+			return 2;
+		}
+		pio::Emitter em;
+		if(!pio::parse_emitter(*e, std::atoi(argv[3]), em)) return 1;
+		for(int i = 4; i < argc; ++i) {
+			const std::vector<float> pts = em.due(std::strtod(argv[i], nullptr));
+			std::printf("due %zu\n", pts.size() / 3);
+			for(size_t p = 0; p < pts.size(); p += 3) {
+				uint32_t b[3];
+				std::memcpy(b, &pts[p], sizeof(b));
+				std::printf("%08x %08x %08x\n", b[0], b[1], b[2]);
+			}
+		}
 		return 0;
 	}
 	if(argc == 4 && !std::strcmp(argv[1], "--bgeo-from")) {// host_selftest --bgeo-from points.f32 out.bgeo: raw float32 xyz -> BGEO frame

@@ -494,3 +494,98 @@ def two_paddles(bits=6, radius_cells=6.0, paddle_cells=(3.0, 10.0, 10.0), gap_ce
                           "friction": friction, "trans_vel": (-side * speed, 0.0, 0.0), "animate": True})
     return {"name": "two_paddles", "bits": bits, "dt": dt, "config": {"max_ppc": 128, "gravity": 0.0},
             "models": [{"material": material, "xyz": lattice_sphere(bits, tuple(c), radius_cells), "v0": (0, 0, 0), "params": prm}], "colliders": colliders}
+
+
+class Emitter:
+    """A host-side particle source: a nozzle that turns into calls of Engine.emit (mpm_emit_particles), one lattice layer at a time.
+
+    shape "box": lo, hi (world units) - the nozzle's cross-section is the box's extent on the two axes across the flow, its plane passes through
+    the box's centre; shape "disc": center, radius, and a normal along the flow axis.  velocity: along one principal axis (the flow axis; a
+    disc's normal must name the same axis).  The particles are the reference's lattice - 8 per cell, at node -+ 0.25 dx, i.e. the odd
+    multiples of dx / 4 - cut by the cross-section, in the lattice plane nearest the nozzle's centre.  One layer is due every
+    (dx / 2) / |v| seconds: t_k = start + k (dx / 2) / |v| for every t_k < end.  A layer due at t_k is handed out by the first due(t) with
+    t >= t_k, at x + v (t - t_k): the stream is the same lattice whatever the substep sizes are.  The same rule in C++: host/emitter_rule.hpp."""
+
+    def __init__(self, bits, shape, velocity, start=0.0, end=np.inf, model=0, lo=None, hi=None, center=None, radius=None, normal=None):
+        v = np.asarray(velocity, dtype=np.float64).reshape(3)
+        if np.count_nonzero(v) != 1 or not np.isfinite(v).all():
+            raise ValueError(f"Emitter: velocity {tuple(v)} must be along one principal axis")
+        self.bits, self.model, self.velocity = int(bits), int(model), v
+        self.axis = int(np.flatnonzero(v)[0])
+        self.start, self.end = float(start), float(end)
+        n = 1 << self.bits
+        h = 0.5 / n                                                  # the lattice spacing, dx / 2
+        self.period = h / abs(v[self.axis])
+        if shape == "disc":
+            if center is None or radius is None:
+                raise ValueError("Emitter: a disc needs center and radius")
+            if normal is not None and (np.count_nonzero(normal) != 1 or int(np.flatnonzero(normal)[0]) != self.axis):
+                raise ValueError("Emitter: a disc's normal must lie along the velocity's axis")
+            c = np.asarray(center, dtype=np.float64).reshape(3)
+        elif shape == "box":
+            if lo is None or hi is None:
+                raise ValueError("Emitter: a box needs lo and hi")
+            lo, hi = np.asarray(lo, dtype=np.float64).reshape(3), np.asarray(hi, dtype=np.float64).reshape(3)
+            c = (lo + hi) / 2
+        else:
+            raise ValueError(f"Emitter: unknown shape {shape!r} ('box' or 'disc')")
+        j = int(min(max(np.floor(c[self.axis] / h), 0), 2 * n - 1))  # the lattice plane (j + 1/2) h nearest the centre; a tie goes to the lower one
+        if j > 0 and c[self.axis] == j * h:
+            j -= 1
+        t = [d for d in range(3) if d != self.axis]
+        coords = (np.arange(2 * n) + 0.5) * h
+        A, B = np.meshgrid(coords, coords, indexing="ij")
+        if shape == "disc":
+            keep = (A - c[t[0]]) ** 2 + (B - c[t[1]]) ** 2 <= float(radius) ** 2
+        else:
+            keep = (A >= lo[t[0]]) & (A <= hi[t[0]]) & (B >= lo[t[1]]) & (B <= hi[t[1]])
+        self.layer = np.empty((int(keep.sum()), 3), dtype=np.float64)
+        self.layer[:, self.axis] = (j + 0.5) * h
+        self.layer[:, t[0]], self.layer[:, t[1]] = A[keep], B[keep]
+        self.next_layer = 0
+
+    @classmethod
+    def from_dict(cls, bits, d):
+        """An entry of a scene's "emitters": {"model", "shape": "box" | "disc", "velocity", "start", "end", and lo / hi or center / radius / normal}."""
+        keys = ("lo", "hi", "center", "radius", "normal")
+        return cls(bits, d["shape"], d["velocity"], d.get("start", 0.0), d.get("end", np.inf), d.get("model", 0), **{k: d[k] for k in keys if k in d})
+
+    def due(self, t):
+        """The positions to emit at the substep boundary `t`, (m, 3) float32 - every layer that is due and has not been handed out - or an empty array."""
+        out = []
+        while True:
+            tk = self.start + self.next_layer * self.period
+            if not (tk < self.end and tk <= t):
+                break
+            out.append(self.layer + self.velocity[None, :] * (t - tk))
+            self.next_layer += 1
+        if not out:
+            return np.zeros((0, 3), dtype=np.float32)
+        return np.ascontiguousarray(np.concatenate(out), dtype=np.float32)
+
+
+def faucet(bits=6, radius_cells=3.0, speed=2.0, height_cells=None, start=0.0, end=0.05, dt=1e-4):
+    """A J-fluid jet into the unit box: the model starts EMPTY and a disc nozzle under the top wall zone pours it in, straight down at `speed`
+    (scene key "emitters", Engine.main_loop serves them).  The nozzle sits height_cells above the floor (default: 10 cells under the top)."""
+    n = 1 << bits
+    dx = 1.0 / n
+    y = (n - 10 if height_cells is None else height_cells) * dx
+    return {"name": "faucet", "bits": bits, "dt": dt, "config": {"max_ppc": 16},
+            "models": [{"material": J_FLUID, "xyz": np.zeros((0, 3), dtype=np.float32), "v0": (0.0, 0.0, 0.0), "params": {"volume": _vol(bits), "rho": 1e3}}],
+            "emitters": [{"model": 0, "shape": "disc", "center": (0.5, y, 0.5), "normal": (0.0, -1.0, 0.0), "radius": radius_cells * dx,
+                          "velocity": (0.0, -speed, 0.0), "start": start, "end": end}]}
+
+
+def sand_pour(bits=6, radius_cells=2.5, speed=1.0, drop_cells=10.0, start=0.0, end=0.05, dt=1e-4):
+    """Sand poured from a disc onto block_on_ramp's heightfield: the scene's elastic block is replaced by an empty sand model that a nozzle
+    drop_cells above the terrain's centre fills."""
+    sc = block_on_ramp(bits=bits, dt=dt)
+    n = 1 << bits
+    dx = 1.0 / n
+    ground = float(sc["colliders"][0]["heights"][n // 2, n // 2])
+    sc["name"] = "sand_pour"
+    sc["config"] = {"max_ppc": 16}
+    sc["models"] = [{"material": SAND, "xyz": np.zeros((0, 3), dtype=np.float32), "v0": (0.0, 0.0, 0.0), "params": {}}]
+    sc["emitters"] = [{"model": 0, "shape": "disc", "center": (0.5, ground + drop_cells * dx, 0.5), "normal": (0.0, -1.0, 0.0), "radius": radius_cells * dx,
+                       "velocity": (0.0, -speed, 0.0), "start": start, "end": end}]
+    return sc

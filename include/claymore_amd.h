@@ -526,6 +526,39 @@ int mpm_add_model_particles(mpm_ctx* ctx, int material, const mpm_material_param
 							const mpm_particle_init* init /* NULL == mpm_add_model */, int* model_id);
 int mpm_set_model_velocity_field(mpm_ctx* ctx, int model, const float v0[3], const float grad9[9] /* column-major */, const float pivot[3]);
 
+/* Extension (the reference's scenes hold the particles they start with): add n particles to model `model` of a context that has been set up -
+ * an inflow.  HIP library only, single contexts only.  xyz, v0 and the arrays of `init` mean exactly what mpm_add_model_particles says (NULL
+ * arrays: v0, C_p = 0, the stress-free state, params->log_jp0), are checked on the device the same way, and the model's material and
+ * parameters are reused.  An empty model, and a context whose models are all empty, can be emitted into.
+ * When: at a substep boundary with the grid holding momenta - mpm_retrieve_velocity's state, which mpm_initial_setup, mpm_substep,
+ * mpm_run_fixed and mpm_checkpoint_load leave.
+ * What it is: a re-lay, O(all particles) per call like a capacity growth or a checkpoint load, not a change of the substep loop (DESIGN.md
+ * 3.8).  Afterwards
+ *   - every old particle's position and stored state (b with its mark, or J; log Jp) and, in a tracked context, its id have the bits they
+ *     had; the new particles carry the given state bit for bit; the particle order of the readouts is unspecified as always;
+ *   - a grid node that no new particle's 27-node stencil reaches has the bits it had (its block may have a new number); a node that is
+ *     reached holds the old value plus m w for the mass and m w (v_p + C_p (x_i - x_p)) for the momentum of every new particle - the
+ *     set-up P2G of mpm_add_model_particles, without a stress term, as at set-up;
+ *   - the model's particle count and mpm_get_counts grow by n; the cumulative lost / dropped / discarded counters are untouched;
+ *   - in a tracked context the new particles have the ids old n .. old n + n - 1 in input order (n: everything the model was ever given);
+ *     *first_id (may be NULL) receives old n in an untracked context too;
+ *   - the next rebuild is not offered the still path; the collision clock, colliders, rigid bodies, the load gauge and the timers are untouched.
+ * Capacities grow by the usual policy (mpm_config.grow; mpm_get_capacity's growth_events counts it).  Transient device memory: 56 B per
+ * particle of the context (52 B untracked) plus the old grid, released before return.
+ * Checkpoints: one saved after emissions carries the grown n; it loads into a context whose models were added with that many particles
+ * (any positions: they only size it), ids through mpm_particle_ids_load as usual.
+ * Errors - a refused call changes nothing, every readout, checkpoint and later substep is bit for bit that of a context that never saw it:
+ * MPM_ERR_NOT_READY before mpm_initial_setup.  MPM_ERR_INVALID for a bad model; a NULL xyz with n > 0; a reserved word that is not 0; an
+ * unknown state_kind; a value that is not finite; a state that is not strictly positive; a position set-up would count as outside the
+ * domain; a grid that holds velocities (between mpm_grid_update and mpm_rebuild_partition); a context that belongs or belonged to a group or
+ * has been through the halo tagging; a tracked context whose ids are not valid.  MPM_ERR_CAPACITY for a block that would hold more than
+ * max_ppc * 64 particles of the model (whatever drop_overflow says, as at set-up), with grow = 0 for block or bin capacities that do not
+ * suffice, and when the device cannot hold the staging arrays.  n == 0 is MPM_OK and changes nothing.
+ * Not offered: removing particles (a removed particle's share of the grid momentum cannot be subtracted exactly - v_p and C_p exist only in
+ * the registers of the substep kernels), groups and MGSP ranks, an incremental emission inside the rebuild. */
+int mpm_emit_particles(mpm_ctx* ctx, int model, const float* xyz, size_t n, const float v0[3], const mpm_particle_init* init /* may be NULL */,
+					   int32_t* first_id /* may be NULL */);
+
 /* Current capacities and the number of times check_capacity() (gmpm_simulator.cuh:283-300) has grown them: blocks
  * (exterior count limit), bins per model (bin_capacity[8]).  HIP library only. */
 int mpm_get_capacity(mpm_ctx* ctx, int64_t* block_capacity, int64_t* bin_capacity, int* growth_events);

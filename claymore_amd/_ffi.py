@@ -80,6 +80,19 @@ class ParticleInit(C.Structure):
                 ("state_kind", C.c_int), ("reserved", C.c_int * 3)]
 
 
+MAX_SINK_REGIONS = 8                   # MPM_MAX_SINK_REGIONS
+
+
+class Removal(C.Structure):
+    _fields_ = [("regions", C.POINTER(CollisionShape)), ("nregions", C.c_int), ("ids", C.c_void_p), ("nids", C.c_size_t),
+                ("removed_xyz", C.c_void_p), ("removed_ids", C.c_void_p), ("removed_model", C.c_void_p), ("capacity", C.c_size_t),
+                ("reserved", C.c_int * 4)]
+
+
+class RemovalResult(C.Structure):
+    _fields_ = [("removed", C.c_int64 * 8), ("mass", C.c_double), ("momentum", C.c_double * 3), ("relaid", C.c_int), ("reserved", C.c_int * 3)]
+
+
 LOAD_ROWS = 6                          # MPM_LOAD_ROWS
 LOAD_ROW_NAMES = ("field", "slot0", "slot1", "slot2", "slot3", "walls")
 
@@ -210,6 +223,8 @@ HIP_ONLY = {
     "add_model_particles": (_i, [_vp, _i, _P(MaterialParams), _vp, _sz, _fp, _P(ParticleInit), _ip]),
     "set_model_velocity_field": (_i, [_vp, _i, _fp, _fp, _fp]),
     "emit_particles": (_i, [_vp, _i, _vp, _sz, _fp, _P(ParticleInit), _P(C.c_int32)]),
+    "count_particles_in": (_i, [_vp, _i, _P(CollisionShape), _i, _P(C.c_int64)]),
+    "remove_particles": (_i, [_vp, _i, _P(Removal), _P(RemovalResult)]),
     "checkpoint_size": (_i, [_vp, _P(_sz)]),
     "checkpoint_save": (_i, [_vp, _vp, _sz, _P(_sz)]),
     "checkpoint_load": (_i, [_vp, _vp, _sz]),

@@ -23,6 +23,7 @@
 #include "mpm_particle_init.hpp"
 #include "mpm_particle_ids.hpp"
 #include "mpm_particle_emit.hpp"
+#include "mpm_particle_remove.hpp"
 #include "mpm_collider_loads.hpp"
 #include "mpm_rigid_body.hpp"
 #include "mpm_storage.hpp"
@@ -75,6 +76,7 @@ struct Model {
 	int64_t bincount = 0;
 	int64_t bincount_src = 0;// bins in use in bins[rollid] (the source of the next g2p2g): the previous bincount
 	int64_t bucketed = 0;// particles currently in the advection lists (device-counted at each rebuild)
+	int64_t removed	 = 0;// particles mpm_remove_particles has taken out of this model so far (reporting only: the books carry them in books_bias)
 	int list_in		 = 0;// which list buffer g2p2g reads next
 };
 
@@ -1289,7 +1291,149 @@ struct EmitColumns {
 	size_t live = 0, total = 0;
 	EmitStage view() const { return EmitStage {xyz.p, state9.p, logjp.p, tracked ? ids.p : nullptr}; }
 };
+// The partition of a staged particle set, in a scratch table with a status block of its own
+struct ScratchPartition {
+	Partition S;
+	DevBuf<int> status;
+	GridCfg sg {};
+	int pbc = 0, nbc = 0, ebc = 0;
+};
 }// namespace
+// What emission and removal (mpm_particle_remove.hpp) share of the re-lay: the staging allocations' refusal, the scratch partition, the per-block
+// counts, the installation of partition and bins, the books.  Each launches what mpm_emit_particles launched at that place, in that order.
+static int relay_no_memory(mpm_ctx* ctx, const std::string& who, hipError_t e) {
+	return e == hipSuccess ? 0 : fail(ctx, MPM_ERR_CAPACITY, who + ": no device memory for the staging arrays (" + hipGetErrorString(e) + ")");
+}
+#define RELAY_ALLOC(expr)                                       \
+	do {                                                        \
+		if(int rc_ = relay_no_memory(ctx, who, expr)) return rc_; \
+	} while(0)
+static int relay_alloc_columns(mpm_ctx* ctx, const std::string& who, EmitColumns& c) {
+	hipStream_t s = ctx->s_compute;
+	RELAY_ALLOC(c.xyz.alloc(3 * c.total, s));
+	RELAY_ALLOC(c.state9.alloc(9 * c.total, s));
+	RELAY_ALLOC(c.logjp.alloc(c.total, s));
+	if(c.tracked) RELAY_ALLOC(c.ids.alloc(c.total, s));
+	return MPM_OK;
+}
+// PHASE 1: the partition of the staged set (the three kernels are set-up's, in set-up's order); refuses a block capacity that does not suffice with grow = 0
+static int relay_scratch_partition(mpm_ctx* ctx, const std::string& who, const std::vector<EmitColumns>& cols, size_t total_particles, ScratchPartition& P) {
+	hipStream_t s	   = ctx->s_compute;
+	const size_t nm	   = cols.size();
+	const size_t table = (size_t) ctx->g.G * ctx->g.G * ctx->g.G;
+	Partition& S	   = P.S;
+	GridCfg& sg		   = P.sg;
+	sg				   = ctx->g;
+	int pbc			   = 0;
+	RELAY_ALLOC(S.table.alloc(table, s));
+	RELAY_ALLOC(S.count.alloc(1, s));
+	RELAY_ALLOC(P.status.alloc(ST_WORDS, s));
+	HIP_TRY(hipMemsetAsync(S.table, 0xff, sizeof(int) * table, s));
+	size_t prov = std::min(table, total_particles + 1);
+	RELAY_ALLOC(S.keys.alloc(3 * prov, s));
+	sg.cap = (int) prov;
+	for(size_t mi = 0; mi < nm; ++mi)
+		if(cols[mi].total) activate_blocks_kernel<<<cdiv(cols[mi].total, 256), 256, 0, s>>>(sg, cols[mi].total, cols[mi].xyz, S.table, S.keys, S.count, P.status);
+	HIP_TRY(hipMemcpyAsync(&pbc, S.count, sizeof(int), hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	if((size_t) pbc * 27 > prov) {// the scratch list holds every block that can be registered
+		prov = std::min(table, (size_t) pbc * 27 + 1);
+		RELAY_ALLOC(S.keys.grow(3 * prov, s));
+		sg.cap = (int) prov;
+	}
+	int* st = P.status;
+	HIP_TRY(hipMemcpyAsync(&st[ST_CNT_P], S.count, sizeof(int), hipMemcpyDeviceToDevice, s));
+	register_blocks_kernel<0, 1><<<std::max(1u, std::min(4096u, cdiv((size_t) pbc * 8, 256))), 256, 0, s>>>(sg, &st[ST_CNT_P], nullptr, &st[ST_CNT_N], &st[ST_PBC], S.table, S.keys, st, 0);
+	register_blocks_kernel<-1, 1><<<std::max(1u, std::min(8192u, cdiv((size_t) pbc * 32, 256))), 256, 0, s>>>(sg, &st[ST_CNT_P], &st[ST_CNT_N], &st[ST_CNT_E], &st[ST_NBC], S.table, S.keys, st, 0);
+	int hs[ST_WORDS];
+	HIP_TRY(hipMemcpyAsync(hs, st, sizeof(hs), hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipStreamSynchronize(s));
+	if(hs[ST_OVERFLOW]) return fail(ctx, MPM_ERR_INTERNAL, who + ": the scratch partition overflowed");
+	P.pbc = pbc;
+	P.nbc = hs[ST_NBC];
+	P.ebc = hs[ST_CNT_P] + hs[ST_CNT_N] + hs[ST_CNT_E];
+	if(P.ebc > ctx->g.cap && !ctx->cfg.grow) return fail(ctx, MPM_ERR_CAPACITY, who + ": " + std::to_string(P.ebc) + " blocks needed, block capacity " + std::to_string(ctx->g.cap) + " (grow = 0)");
+	return MPM_OK;
+}
+// PHASE 1: per model and block of the scratch partition how many particles (counts), per model how many bins; d_flags[0] takes emit_count_kernel's flags
+static int relay_count_bins(mpm_ctx* ctx, const std::string& who, const std::vector<EmitColumns>& cols, const ScratchPartition& P, std::vector<DevBuf<int>>& counts, std::vector<int>& bins, int* d_flags) {
+	hipStream_t s	= ctx->s_compute;
+	const size_t nm = cols.size();
+	const int pbc	= P.pbc;
+	DevBuf<int> d_bins;
+	RELAY_ALLOC(d_bins.alloc(nm, s));
+	for(size_t mi = 0; mi < nm; ++mi) {
+		RELAY_ALLOC(counts[mi].alloc((size_t) pbc + 1, s));
+		if(!cols[mi].total) continue;
+		emit_count_kernel<<<cdiv(cols[mi].total, 256), 256, 0, s>>>(P.sg, cols[mi].total, cols[mi].xyz, P.S.table, counts[mi], d_flags);
+		emit_bins_kernel<<<cdiv(pbc, 256), 256, 0, s>>>(pbc, counts[mi], d_bins + mi);
+	}
+	int flag = 0;
+	HIP_TRY(hipMemcpyAsync(&flag, d_flags, sizeof(int), hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(bins.data(), d_bins, sizeof(int) * nm, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipStreamSynchronize(s));
+	if(flag & kEmitOutside) return fail(ctx, MPM_ERR_INTERNAL, who + ": a gathered particle has no block");
+	// (as at set-up: a block that starts with more particles than it has list slots is refused whatever the overflow policy)
+	if(flag & kEmitBlockFull) return fail(ctx, MPM_ERR_CAPACITY, who + ": a block would hold more than max_ppc*64 = " + std::to_string(ctx->g.ppb) + " particles");
+	for(size_t mi = 0; mi < nm; ++mi)
+		if((size_t) bins[mi] > ctx->models[mi].bin_cap && !ctx->cfg.grow)
+			return fail(ctx, MPM_ERR_CAPACITY, who + ": model " + std::to_string(mi) + " needs " + std::to_string(bins[mi]) + " bins, bin capacity " + std::to_string(ctx->models[mi].bin_cap) + " (grow = 0)");
+	return MPM_OK;
+}
+// PHASE 2: the scratch partition into both rolls (previous numbering == current numbering, as set-up leaves it), the counts the kernels read, and
+// every model's staged columns laid out with set-up's kernels (lay_model_bins)
+static int relay_install(mpm_ctx* ctx, const std::vector<EmitColumns>& cols, const ScratchPartition& P, const std::vector<int>& bins) {
+	hipStream_t s	   = ctx->s_compute;
+	const size_t nm	   = cols.size();
+	const size_t table = (size_t) ctx->g.G * ctx->g.G * ctx->g.G;
+	const GridCfg& g   = ctx->g;
+	const int pbc = P.pbc, nbc = P.nbc, ebc = P.ebc;
+	ctx->pbc = pbc, ctx->nbc = nbc, ctx->ebc = ebc, ctx->pbc_prev = pbc;
+	{
+		HIP_TRY(hipMemcpyAsync(ctx->h_status, ctx->d_status, sizeof(int) * ST_WORDS, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		int* st	   = ctx->h_status;
+		st[ST_PBC] = pbc, st[ST_NBC] = nbc, st[ST_EBC] = ebc, st[ST_PBCPREV] = pbc;
+		st[ST_CNT_P] = st[ST_CNT_N] = st[ST_CNT_E] = 0;
+		for(size_t mi = 0; mi < (size_t) kMaxModels; ++mi) {
+			st[ST_BINS0 + mi]	 = 0;// (init_bins_kernel hands the bins out from here)
+			st[ST_BINSPREV + mi] = mi < nm ? bins[mi] : 0;
+			st[ST_PART0 + mi]	 = mi < nm ? (int) cols[mi].total : 0;
+		}
+		HIP_TRY(hipMemcpyAsync(ctx->d_status, st, sizeof(int) * ST_WORDS, hipMemcpyHostToDevice, s));
+		for(int i = 0; i < 2; ++i) {
+			HIP_TRY(hipMemcpyAsync(ctx->part[i].table, P.S.table, sizeof(int) * table, hipMemcpyDeviceToDevice, s));
+			HIP_TRY(hipMemcpyAsync(ctx->part[i].keys, P.S.keys, sizeof(int) * 3 * (size_t) ebc, hipMemcpyDeviceToDevice, s));
+			HIP_TRY(hipMemcpyAsync(ctx->part[i].count, &st[ST_EBC], sizeof(int), hipMemcpyHostToDevice, s));
+		}
+		HIP_TRY(hipStreamSynchronize(s));
+	}
+	for(size_t mi = 0; mi < nm; ++mi) {
+		Model& m = ctx->models[mi];
+		HIP_TRY(hipMemsetAsync(m.size, 0, sizeof(int) * ((size_t) g.cap + 1), s));
+		HIP_TRY(hipMemsetAsync(m.out_count, 0, sizeof(int) * ((size_t) g.cap + 1), s));
+		if(m.pair)
+			for(int i = 0; i < 2; ++i) HIP_TRY(hipMemsetAsync(m.pairinfo[i], 0, sizeof(int) * ((size_t) g.cap + 1) * kPairChunks, s));
+		const EmitColumns& c = cols[mi];
+		ParticleInit staged;
+		staged.state9 = c.state9, staged.logjp = c.logjp;
+		if(int rc = lay_model_bins(ctx, mi, P.S.table, pbc, {c.total, c.xyz, staged, true, c.tracked ? c.ids.p : nullptr})) return rc;
+	}
+	return MPM_OK;
+}
+// PHASE 2, after launch_prepare and read_status: every model's bins and bucketed count as the re-lay left them
+static int relay_books(mpm_ctx* ctx, const std::string& who, const std::vector<EmitColumns>& cols, const std::vector<int>& bins) {
+	for(size_t mi = 0; mi < cols.size(); ++mi) {
+		Model& m	   = ctx->models[mi];
+		m.bincount	   = ctx->h_status[ST_BINS0 + mi];
+		m.bincount_src = m.bincount;
+		m.bucketed	   = (int64_t) cols[mi].total;
+		if(m.bincount != bins[mi]) return fail(ctx, MPM_ERR_INTERNAL, who + ": model " + std::to_string(mi) + " took " + std::to_string(m.bincount) + " bins, " + std::to_string(bins[mi]) + " were counted");
+	}
+	return MPM_OK;
+}
 int mpm_emit_particles(mpm_ctx* ctx, int model, const float* xyz, size_t n, const float v0[3], const mpm_particle_init* init, int32_t* first_id) {
 	if(!ctx) return MPM_ERR_INVALID;
 	const std::string who = "mpm_emit_particles";
@@ -1325,17 +1469,12 @@ int mpm_emit_particles(mpm_ctx* ctx, int model, const float* xyz, size_t n, cons
 	const size_t nm		= ctx->models.size();
 	const size_t table	= (size_t) ctx->g.G * ctx->g.G * ctx->g.G;
 	const bool fluid	= M.material == MPM_J_FLUID;
-	const auto no_memory = [&](hipError_t e) { return e == hipSuccess ? 0 : fail(ctx, MPM_ERR_CAPACITY, who + ": no device memory for the staging arrays (" + hipGetErrorString(e) + ")"); };
-#define EMIT_ALLOC(expr)                      \
-	do {                                      \
-		if(int rc_ = no_memory(expr)) return rc_; \
-	} while(0)
 	// ---- phase 1: gather, append, check, count - the context is only read ----
 	std::vector<EmitColumns> cols(nm);
 	DevBuf<unsigned long long> d_gathered;
 	DevBuf<int> d_flags;// [0] emission's own, [1] validate_particle_init_kernel's
-	EMIT_ALLOC(d_gathered.alloc(nm, s));
-	EMIT_ALLOC(d_flags.alloc(2, s));
+	RELAY_ALLOC(d_gathered.alloc(nm, s));
+	RELAY_ALLOC(d_flags.alloc(2, s));
 	size_t total_particles = 0;
 	for(size_t mi = 0; mi < nm; ++mi) {
 		const Model& m = ctx->models[mi];
@@ -1344,10 +1483,7 @@ int mpm_emit_particles(mpm_ctx* ctx, int model, const float* xyz, size_t n, cons
 		c.total		   = c.live + ((int) mi == model ? n : 0);
 		c.tracked	   = ctx->track_ids;
 		total_particles += c.total;
-		EMIT_ALLOC(c.xyz.alloc(3 * c.total, s));
-		EMIT_ALLOC(c.state9.alloc(9 * c.total, s));
-		EMIT_ALLOC(c.logjp.alloc(c.total, s));
-		if(c.tracked) EMIT_ALLOC(c.ids.alloc(c.total, s));
+		if(int rc = relay_alloc_columns(ctx, who, c)) return rc;
 		if(c.live && ctx->pbc) emit_gather_kernel<<<ctx->pbc, kReadoutThreads, 0, s>>>(make_readout_args(ctx, m), c.view(), (unsigned long long) c.live, d_gathered + mi);
 	}
 	EmitColumns& E = cols[model];
@@ -1364,7 +1500,7 @@ int mpm_emit_particles(mpm_ctx* ctx, int model, const float* xyz, size_t n, cons
 		} up[4] = {{init->velocity, &d_velocity, &a.velocity, 3}, {init->affine9, &d_affine, &a.affine9, 9}, {init->state9, &d_state, &a.state9, 9}, {with_logjp ? init->logjp : nullptr, &d_logjp, &a.logjp, 1}};
 		for(auto& c: up) {
 			if(!c.host) continue;
-			EMIT_ALLOC(c.dev->alloc(c.per * n, s));
+			RELAY_ALLOC(c.dev->alloc(c.per * n, s));
 			HIP_TRY(hipMemcpyAsync(c.dev->p, c.host, sizeof(float) * c.per * n, hipMemcpyHostToDevice, s));
 			*c.view = c.dev->p;
 		}
@@ -1390,72 +1526,20 @@ int mpm_emit_particles(mpm_ctx* ctx, int model, const float* xyz, size_t n, cons
 		if(flags[1] & kInitBadLogJp) return fail(ctx, MPM_ERR_INVALID, who + ": logjp holds a value that is not finite");
 		if(flags[1] & kInitNotPositive) return fail(ctx, MPM_ERR_INVALID, who + (fluid ? ": state9 holds a J that is not strictly positive" : ": state9 holds a |b00|, b11 or b22 that is not strictly positive"));
 	}
-	// the partition of the merged set, in a scratch table with a status block of its own (the three kernels are set-up's, in set-up's order)
-	Partition S;
-	DevBuf<int> s_status;
-	GridCfg sg = ctx->g;
-	int pbc = 0, nbc = 0, ebc = 0;
-	{
-		EMIT_ALLOC(S.table.alloc(table, s));
-		EMIT_ALLOC(S.count.alloc(1, s));
-		EMIT_ALLOC(s_status.alloc(ST_WORDS, s));
-		HIP_TRY(hipMemsetAsync(S.table, 0xff, sizeof(int) * table, s));
-		size_t prov = std::min(table, total_particles + 1);
-		EMIT_ALLOC(S.keys.alloc(3 * prov, s));
-		sg.cap = (int) prov;
-		for(size_t mi = 0; mi < nm; ++mi)
-			if(cols[mi].total) activate_blocks_kernel<<<cdiv(cols[mi].total, 256), 256, 0, s>>>(sg, cols[mi].total, cols[mi].xyz, S.table, S.keys, S.count, s_status);
-		HIP_TRY(hipMemcpyAsync(&pbc, S.count, sizeof(int), hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		if((size_t) pbc * 27 > prov) {// the scratch list holds every block that can be registered
-			prov = std::min(table, (size_t) pbc * 27 + 1);
-			EMIT_ALLOC(S.keys.grow(3 * prov, s));
-			sg.cap = (int) prov;
-		}
-		int* st = s_status;
-		HIP_TRY(hipMemcpyAsync(&st[ST_CNT_P], S.count, sizeof(int), hipMemcpyDeviceToDevice, s));
-		register_blocks_kernel<0, 1><<<std::max(1u, std::min(4096u, cdiv((size_t) pbc * 8, 256))), 256, 0, s>>>(sg, &st[ST_CNT_P], nullptr, &st[ST_CNT_N], &st[ST_PBC], S.table, S.keys, st, 0);
-		register_blocks_kernel<-1, 1><<<std::max(1u, std::min(8192u, cdiv((size_t) pbc * 32, 256))), 256, 0, s>>>(sg, &st[ST_CNT_P], &st[ST_CNT_N], &st[ST_CNT_E], &st[ST_NBC], S.table, S.keys, st, 0);
-		int hs[ST_WORDS];
-		HIP_TRY(hipMemcpyAsync(hs, st, sizeof(hs), hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipStreamSynchronize(s));
-		if(hs[ST_OVERFLOW]) return fail(ctx, MPM_ERR_INTERNAL, who + ": the scratch partition overflowed");
-		nbc = hs[ST_NBC];
-		ebc = hs[ST_CNT_P] + hs[ST_CNT_N] + hs[ST_CNT_E];
-	}
+	// the partition of the merged set, in a scratch table with a status block of its own; per model and block: how many particles, how many bins
+	ScratchPartition SP;
+	if(int rc = relay_scratch_partition(ctx, who, cols, total_particles, SP)) return rc;
+	const int pbc = SP.pbc, nbc = SP.nbc, ebc = SP.ebc;
 	const bool grow = ctx->cfg.grow != 0;
-	if(ebc > ctx->g.cap && !grow) return fail(ctx, MPM_ERR_CAPACITY, who + ": " + std::to_string(ebc) + " blocks needed, block capacity " + std::to_string(ctx->g.cap) + " (grow = 0)");
-	// per model and block: how many particles, how many bins
 	std::vector<DevBuf<int>> counts(nm);
 	std::vector<int> bins(nm, 0);
-	{
-		DevBuf<int> d_bins;
-		EMIT_ALLOC(d_bins.alloc(nm, s));
-		for(size_t mi = 0; mi < nm; ++mi) {
-			EMIT_ALLOC(counts[mi].alloc((size_t) pbc + 1, s));
-			if(!cols[mi].total) continue;
-			emit_count_kernel<<<cdiv(cols[mi].total, 256), 256, 0, s>>>(sg, cols[mi].total, cols[mi].xyz, S.table, counts[mi], d_flags);
-			emit_bins_kernel<<<cdiv(pbc, 256), 256, 0, s>>>(pbc, counts[mi], d_bins + mi);
-		}
-		int flag = 0;
-		HIP_TRY(hipMemcpyAsync(&flag, d_flags, sizeof(int), hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipMemcpyAsync(bins.data(), d_bins, sizeof(int) * nm, hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipStreamSynchronize(s));
-		if(flag & kEmitOutside) return fail(ctx, MPM_ERR_INTERNAL, who + ": a gathered particle has no block");
-		// (as at set-up: a block that starts with more particles than it has list slots is refused whatever the overflow policy)
-		if(flag & kEmitBlockFull) return fail(ctx, MPM_ERR_CAPACITY, who + ": a block would hold more than max_ppc*64 = " + std::to_string(ctx->g.ppb) + " particles");
-		for(size_t mi = 0; mi < nm; ++mi)
-			if((size_t) bins[mi] > ctx->models[mi].bin_cap && !grow)
-				return fail(ctx, MPM_ERR_CAPACITY, who + ": model " + std::to_string(mi) + " needs " + std::to_string(bins[mi]) + " bins, bin capacity " + std::to_string(ctx->models[mi].bin_cap) + " (grow = 0)");
-	}
+	if(int rc = relay_count_bins(ctx, who, cols, SP, counts, bins, d_flags)) return rc;
 	// the old grid and its keys, kept aside
 	const int r = ctx->rollid, old_nbc = ctx->nbc;
 	DevBuf<float> old_grid;
 	DevBuf<int> old_keys;
-	EMIT_ALLOC(old_grid.alloc(256 * (size_t) old_nbc, s));
-	EMIT_ALLOC(old_keys.alloc(3 * (size_t) old_nbc, s));
+	RELAY_ALLOC(old_grid.alloc(256 * (size_t) old_nbc, s));
+	RELAY_ALLOC(old_keys.alloc(3 * (size_t) old_nbc, s));
 	HIP_TRY(hipMemcpyAsync(old_grid, ctx->grid[0], sizeof(float) * 256 * (size_t) old_nbc, hipMemcpyDeviceToDevice, s));
 	HIP_TRY(hipMemcpyAsync(old_keys, ctx->part[r].keys, sizeof(int) * 3 * (size_t) old_nbc, hipMemcpyDeviceToDevice, s));
 	HIP_TRY(hipStreamSynchronize(s));
@@ -1472,38 +1556,8 @@ int mpm_emit_particles(mpm_ctx* ctx, int model, const float* xyz, size_t n, cons
 	}
 	HIP_TRY(M.d_xyz.grow(3 * new_n, s));
 	const GridCfg& g = ctx->g;
-	// the partition, in both rolls (previous numbering == current numbering, as set-up leaves it), and the counts the kernels read
-	ctx->pbc = pbc, ctx->nbc = nbc, ctx->ebc = ebc, ctx->pbc_prev = pbc;
-	{
-		HIP_TRY(hipMemcpyAsync(ctx->h_status, ctx->d_status, sizeof(int) * ST_WORDS, hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		int* st	   = ctx->h_status;
-		st[ST_PBC] = pbc, st[ST_NBC] = nbc, st[ST_EBC] = ebc, st[ST_PBCPREV] = pbc;
-		st[ST_CNT_P] = st[ST_CNT_N] = st[ST_CNT_E] = 0;
-		for(size_t mi = 0; mi < (size_t) kMaxModels; ++mi) {
-			st[ST_BINS0 + mi]	 = 0;// (init_bins_kernel hands the bins out from here)
-			st[ST_BINSPREV + mi] = mi < nm ? bins[mi] : 0;
-			st[ST_PART0 + mi]	 = mi < nm ? (int) cols[mi].total : 0;
-		}
-		HIP_TRY(hipMemcpyAsync(ctx->d_status, st, sizeof(int) * ST_WORDS, hipMemcpyHostToDevice, s));
-		for(int i = 0; i < 2; ++i) {
-			HIP_TRY(hipMemcpyAsync(ctx->part[i].table, S.table, sizeof(int) * table, hipMemcpyDeviceToDevice, s));
-			HIP_TRY(hipMemcpyAsync(ctx->part[i].keys, S.keys, sizeof(int) * 3 * (size_t) ebc, hipMemcpyDeviceToDevice, s));
-			HIP_TRY(hipMemcpyAsync(ctx->part[i].count, &st[ST_EBC], sizeof(int), hipMemcpyHostToDevice, s));
-		}
-		HIP_TRY(hipStreamSynchronize(s));
-	}
-	for(size_t mi = 0; mi < nm; ++mi) {
-		Model& m = ctx->models[mi];
-		HIP_TRY(hipMemsetAsync(m.size, 0, sizeof(int) * ((size_t) g.cap + 1), s));
-		HIP_TRY(hipMemsetAsync(m.out_count, 0, sizeof(int) * ((size_t) g.cap + 1), s));
-		if(m.pair)
-			for(int i = 0; i < 2; ++i) HIP_TRY(hipMemsetAsync(m.pairinfo[i], 0, sizeof(int) * ((size_t) g.cap + 1) * kPairChunks, s));
-		const EmitColumns& c = cols[mi];
-		ParticleInit staged;
-		staged.state9 = c.state9, staged.logjp = c.logjp;
-		if(int rc = lay_model_bins(ctx, mi, S.table, pbc, {c.total, c.xyz, staged, true, c.tracked ? c.ids.p : nullptr})) return rc;
-	}
+	// the partition, in both rolls, the counts the kernels read, and every model's columns into bins
+	if(int rc = relay_install(ctx, cols, SP, bins)) return rc;
 	// the grid: zero, the old blocks under their new numbers, the new particles on top (set-up's P2G of them alone; M.list[1] is free again)
 	HIP_TRY(hipMemsetAsync(ctx->grid[0], 0, sizeof(float) * 256 * (size_t) nbc, s));
 	HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof(int) * 2, s));
@@ -1512,7 +1566,7 @@ int mpm_emit_particles(mpm_ctx* ctx, int model, const float* xyz, size_t n, cons
 		int* fresh = counts[model];
 		HIP_TRY(hipMemsetAsync(fresh, 0, sizeof(int) * ((size_t) pbc + 1), s));
 		const float* nxyz = E.xyz + 3 * E.live;
-		bucket_particles_kernel<<<cdiv(n, 256), 256, 0, s>>>(g, n, nxyz, ctx->part[r].table, fresh, M.list[1], s_status);
+		bucket_particles_kernel<<<cdiv(n, 256), 256, 0, s>>>(g, n, nxyz, ctx->part[r].table, fresh, M.list[1], SP.status);
 		rasterize_particles_kernel<false><<<pbc, 256, 0, s>>>(g, nxyz, M.list[1], fresh, ctx->part[r].keys, ctx->part[r].table, ctx->grid[0], M.mc.mass, a, f);
 	}
 	int rc = launch_prepare(ctx, PrepareFor::Setup);
@@ -1527,16 +1581,9 @@ int mpm_emit_particles(mpm_ctx* ctx, int model, const float* xyz, size_t n, cons
 	}
 	// the books
 	M.n = new_n;
-	for(size_t mi = 0; mi < nm; ++mi) {
-		Model& m	   = ctx->models[mi];
-		m.bincount	   = ctx->h_status[ST_BINS0 + mi];
-		m.bincount_src = m.bincount;
-		m.bucketed	   = (int64_t) cols[mi].total;
-		if(m.bincount != bins[mi]) return fail(ctx, MPM_ERR_INTERNAL, who + ": model " + std::to_string(mi) + " took " + std::to_string(m.bincount) + " bins, " + std::to_string(bins[mi]) + " were counted");
-	}
+	if(int rc2 = relay_books(ctx, who, cols, bins)) return rc2;
 	ctx->relaid = true;
 	if(first_id) *first_id = old_n;
-#undef EMIT_ALLOC
 	return grow_capacity(ctx);// (the policy's own look at the new fill levels)
 }
 
@@ -1869,6 +1916,229 @@ int mpm_set_collision_shape(mpm_ctx* ctx, int slot, const mpm_collision_object* 
 	}
 	return install_slot(ctx, slot, o, obj);
 }
+
+// Particle removal (mpm_particle_remove.hpp): emission's mirror image, a re-lay at a substep boundary.  PHASE 1 reads the context and
+// writes scratch alone - the selected particles counted (nothing selected: the call ends there), every model split into the survivors' staging columns
+// and the removed list, the survivors' partition built in a scratch table and counted, the removed particles' stencil nodes marked in the old
+// numbering.  PHASE 2 lays the survivors out with set-up's own kernels (relay_install), carries the old grid over by block key, rasterises the
+// survivors' set-up mass into a scratch grid and rescales the marked nodes to it.
+namespace {
+struct SinkQuery {
+	SinkSelect sel {};
+	DevBuf<unsigned> bitmap;
+	DevBuf<int> d_ids;
+};
+}// namespace
+// the regions as mpm_set_collision_shape would install them (make_shape_slot: the same checks, the half-space normal normalised the same way)
+static int sink_regions(mpm_ctx* ctx, const std::string& who, const mpm_collision_shape* regions, int nregions, SinkSelect& q) {
+	if(nregions < 0 || nregions > MPM_MAX_SINK_REGIONS) return fail(ctx, MPM_ERR_INVALID, who + ": nregions outside 0.." + std::to_string(MPM_MAX_SINK_REGIONS));
+	if(nregions && !regions) return fail(ctx, MPM_ERR_INVALID, who + ": regions are missing");
+	mpm_collision_object obj;
+	mpm_default_collision_object(&obj);
+	for(int i = 0; i < nregions; ++i) {
+		ShapeSlot slot;
+		if(const char* msg = make_shape_slot(&obj, &regions[i], slot)) return fail(ctx, MPM_ERR_INVALID, who + ": region " + std::to_string(i) + ": " + msg);
+		q.region[i] = slot.shape;
+	}
+	q.nregions = nregions;
+	return MPM_OK;
+}
+// emission's preconditions, with emission's codes
+static int sink_preconditions(mpm_ctx* ctx, const std::string& who, int model) {
+	if(!ctx->ready) return fail(ctx, MPM_ERR_NOT_READY, who + ": particles are removed after mpm_initial_setup");
+	if(model < -1 || model >= (int) ctx->models.size()) return fail(ctx, MPM_ERR_INVALID, who + ": no model " + std::to_string(model));
+	if(ctx->group_refs > 0 || ctx->mgsp_rank >= 0 || ctx->halo_tagged || ctx->d_overlap.p)
+		return fail(ctx, MPM_ERR_INVALID, who + ": the context belongs (or belonged) to a multi-GPU group or has been through the halo tagging; removal from groups is not computed");
+	if(!ctx->grid_momentum || ctx->grid_preupdated)
+		return fail(ctx, MPM_ERR_INVALID, who + ": the grid holds velocities (a grid update without its rebuild): remove at a substep boundary");
+	if(ctx->track_ids && !ctx->ids_valid) return fail(ctx, MPM_ERR_INVALID, who + ": the ids are not valid (load them with mpm_particle_ids_load first)");
+	return MPM_OK;
+}
+// the count pass: how many live particles of each selected model the query selects (the one thing a call that selects nothing launches)
+static int sink_count(mpm_ctx* ctx, int model, const SinkQuery& q, int64_t out[8]) {
+	hipStream_t s	= ctx->s_compute;
+	const size_t nm = ctx->models.size();
+	for(int i = 0; i < 8; ++i) out[i] = 0;
+	unsigned long long found[8] = {0};
+	HIP_TRY(hipMemsetAsync(ctx->d_totals, 0, sizeof(double) * 4, s));// (four 8-byte words the context owns; the models go through them four at a time)
+	for(size_t first = 0; first < nm; first += 4) {
+		bool any = false;
+		for(size_t mi = first; mi < std::min(nm, first + 4); ++mi) {
+			const Model& m = ctx->models[mi];
+			if((model >= 0 && (int) mi != model) || !m.bucketed || !ctx->pbc) continue;
+			sink_count_kernel<<<ctx->pbc, kReadoutThreads, 0, s>>>(make_readout_args(ctx, m), q.sel, reinterpret_cast<unsigned long long*>(ctx->d_totals.p) + (mi - first));
+			any = true;
+		}
+		if(!any) continue;
+		HIP_TRY(hipMemcpyAsync(found + first, ctx->d_totals, sizeof(unsigned long long) * 4, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipMemsetAsync(ctx->d_totals, 0, sizeof(double) * 4, s));
+	}
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipStreamSynchronize(s));
+	for(size_t mi = 0; mi < nm; ++mi) out[mi] = (int64_t) found[mi];
+	return MPM_OK;
+}
+
+int mpm_count_particles_in(mpm_ctx* ctx, int model, const mpm_collision_shape* regions, int nregions, int64_t out[8]) {
+	if(!ctx) return MPM_ERR_INVALID;
+	const std::string who = "mpm_count_particles_in";
+	if(int rc = sink_preconditions(ctx, who, model)) return rc;
+	if(!out) return fail(ctx, MPM_ERR_INVALID, who + ": out is missing");
+	SinkQuery q;
+	if(int rc = sink_regions(ctx, who, regions, nregions, q.sel)) return rc;
+	HIP_TRY(hipSetDevice(ctx->device));
+	HIP_TRY(hipDeviceSynchronize());
+	return sink_count(ctx, model, q, out);
+}
+
+int mpm_remove_particles(mpm_ctx* ctx, int model, const mpm_removal* what, mpm_removal_result* out) {
+	if(!ctx) return MPM_ERR_INVALID;
+	const std::string who = "mpm_remove_particles";
+	if(int rc = sink_preconditions(ctx, who, model)) return rc;
+	if(!what) return fail(ctx, MPM_ERR_INVALID, who + ": the removal is missing");
+	for(int w: what->reserved)
+		if(w) return fail(ctx, MPM_ERR_INVALID, who + ": a reserved word of mpm_removal is not 0");
+	SinkQuery q;
+	if(int rc = sink_regions(ctx, who, what->regions, what->nregions, q.sel)) return rc;
+	if(what->nids) {
+		if(!what->ids) return fail(ctx, MPM_ERR_INVALID, who + ": ids are missing");
+		if(model < 0) return fail(ctx, MPM_ERR_INVALID, who + ": ids name the particles of one model (model >= 0)");
+		if(!ctx->track_ids) return fail(ctx, MPM_ERR_INVALID, who + ": ids need a tracked context (mpm_track_particle_ids)");
+		const size_t n = ctx->models[model].n;
+		for(size_t i = 0; i < what->nids; ++i)
+			if(what->ids[i] < 0 || (size_t) what->ids[i] >= n) return fail(ctx, MPM_ERR_INVALID, who + ": id " + std::to_string(what->ids[i]) + " outside 0.." + std::to_string((long long) n - 1));
+	}
+	HIP_TRY(hipSetDevice(ctx->device));
+	HIP_TRY(hipDeviceSynchronize());
+	hipStream_t s	   = ctx->s_compute;
+	const size_t nm	   = ctx->models.size();
+	const size_t table = (size_t) ctx->g.G * ctx->g.G * ctx->g.G;
+	mpm_removal_result res {};
+	// ---- phase 1: count, split, partition, mark - the context is only read ----
+	if(what->nids) {
+		const size_t n = ctx->models[model].n;
+		RELAY_ALLOC(q.bitmap.alloc((n + 31) / 32, s));
+		RELAY_ALLOC(q.d_ids.alloc(what->nids, s));
+		HIP_TRY(hipMemcpyAsync(q.d_ids, what->ids, sizeof(int) * what->nids, hipMemcpyHostToDevice, s));
+		sink_bitmap_kernel<<<cdiv(what->nids, 256), 256, 0, s>>>(what->nids, q.d_ids, q.bitmap);
+		q.sel.bitmap = q.bitmap;
+		q.sel.nbits	 = (unsigned) n;
+	}
+	if(int rc = sink_count(ctx, model, q, res.removed)) return rc;
+	size_t selected = 0;
+	for(size_t mi = 0; mi < nm; ++mi) selected += (size_t) res.removed[mi];
+	if(out) *out = res;
+	if(selected == 0) return MPM_OK;// (relaid = 0: nothing was written, the still path stays on offer)
+	const bool wants_list = what->removed_xyz || what->removed_ids || what->removed_model;
+	if(wants_list && what->capacity < selected)
+		return fail(ctx, MPM_ERR_CAPACITY, who + ": " + std::to_string(selected) + " particles are selected, the removed-particle arrays hold " + std::to_string(what->capacity));
+	double before[4], after[4];
+	if(int rc = mpm_grid_totals(ctx, before)) return rc;
+	std::vector<EmitColumns> cols(nm);
+	DevBuf<unsigned long long> d_gathered;// [mi] survivors of model mi, [nm] the removed list's length
+	DevBuf<int> d_flags;
+	DevBuf<float> d_rxyz;
+	DevBuf<int> d_rids, d_rmodel;
+	RELAY_ALLOC(d_gathered.alloc(nm + 1, s));
+	RELAY_ALLOC(d_flags.alloc(2, s));
+	RELAY_ALLOC(d_rxyz.alloc(3 * selected, s));
+	RELAY_ALLOC(d_rids.alloc(selected, s));
+	RELAY_ALLOC(d_rmodel.alloc(selected, s));
+	const SinkRemoved gone {d_rxyz.p, d_rids.p, d_rmodel.p, (unsigned long long) selected, d_gathered + nm};
+	size_t survivors = 0;
+	for(size_t mi = 0; mi < nm; ++mi) {
+		const Model& m = ctx->models[mi];
+		EmitColumns& c = cols[mi];
+		c.live = c.total = (size_t) (m.bucketed - res.removed[mi]);
+		c.tracked		 = ctx->track_ids;
+		survivors += c.total;
+		if(int rc = relay_alloc_columns(ctx, who, c)) return rc;
+		if(!m.bucketed || !ctx->pbc) continue;
+		if(model >= 0 && (int) mi != model)// (a model the call does not select: emission's gather, as it stands)
+			emit_gather_kernel<<<ctx->pbc, kReadoutThreads, 0, s>>>(make_readout_args(ctx, m), c.view(), (unsigned long long) c.live, d_gathered + mi);
+		else
+			sink_gather_kernel<<<ctx->pbc, kReadoutThreads, 0, s>>>(make_readout_args(ctx, m), q.sel, (int) mi, c.view(), (unsigned long long) c.live, d_gathered + mi, gone);
+	}
+	{
+		std::vector<unsigned long long> gathered(nm + 1);
+		HIP_TRY(hipMemcpyAsync(gathered.data(), d_gathered, sizeof(unsigned long long) * (nm + 1), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipStreamSynchronize(s));
+		for(size_t mi = 0; mi < nm; ++mi)
+			if(gathered[mi] != cols[mi].live)
+				return fail(ctx, MPM_ERR_INTERNAL, who + ": the lists of model " + std::to_string(mi) + " hold " + std::to_string(gathered[mi]) + " survivors, the count pass left " + std::to_string(cols[mi].live));
+		if(gathered[nm] != selected) return fail(ctx, MPM_ERR_INTERNAL, who + ": " + std::to_string(gathered[nm]) + " particles gathered for removal, " + std::to_string(selected) + " counted");
+	}
+	ScratchPartition SP;
+	if(int rc = relay_scratch_partition(ctx, who, cols, survivors, SP)) return rc;
+	const int pbc = SP.pbc, nbc = SP.nbc;
+	std::vector<DevBuf<int>> counts(nm);
+	std::vector<int> bins(nm, 0);
+	if(int rc = relay_count_bins(ctx, who, cols, SP, counts, bins, d_flags)) return rc;
+	// the old grid and its keys, kept aside; the removed particles' nodes marked in the old numbering; the scratch mass grid and the new marks
+	const int r = ctx->rollid, old_nbc = ctx->nbc;
+	DevBuf<float> old_grid, mass_grid;
+	DevBuf<int> old_keys;
+	DevBuf<unsigned long long> old_marks, new_marks;
+	RELAY_ALLOC(old_grid.alloc(256 * (size_t) old_nbc, s));
+	RELAY_ALLOC(old_keys.alloc(3 * (size_t) old_nbc, s));
+	RELAY_ALLOC(old_marks.alloc((size_t) old_nbc, s));
+	RELAY_ALLOC(new_marks.alloc((size_t) nbc, s));
+	RELAY_ALLOC(mass_grid.alloc(256 * (size_t) nbc, s));
+	HIP_TRY(hipMemcpyAsync(old_grid, ctx->grid[0], sizeof(float) * 256 * (size_t) old_nbc, hipMemcpyDeviceToDevice, s));
+	HIP_TRY(hipMemcpyAsync(old_keys, ctx->part[r].keys, sizeof(int) * 3 * (size_t) old_nbc, hipMemcpyDeviceToDevice, s));
+	sink_mark_kernel<<<cdiv(selected, 256), 256, 0, s>>>(ctx->g, selected, d_rxyz, ctx->part[r].table, old_nbc, old_marks);
+	std::vector<float> h_rxyz;
+	std::vector<int> h_rids, h_rmodel;
+	if(what->removed_xyz) h_rxyz.resize(3 * selected);
+	if(what->removed_ids) h_rids.resize(selected);
+	if(what->removed_model) h_rmodel.resize(selected);
+	if(what->removed_xyz) HIP_TRY(hipMemcpyAsync(h_rxyz.data(), d_rxyz, sizeof(float) * 3 * selected, hipMemcpyDeviceToHost, s));
+	if(what->removed_ids) HIP_TRY(hipMemcpyAsync(h_rids.data(), d_rids, sizeof(int) * selected, hipMemcpyDeviceToHost, s));
+	if(what->removed_model) HIP_TRY(hipMemcpyAsync(h_rmodel.data(), d_rmodel, sizeof(int) * selected, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipStreamSynchronize(s));
+	// ---- phase 2: nothing refuses from here on (capacities neither shrink nor grow: the survivors need no more than the context holds) ----
+	phase_call(ctx);
+	const GridCfg& g = ctx->g;
+	if(int rc = relay_install(ctx, cols, SP, bins)) return rc;
+	// the grid: zero, the old blocks under their new numbers with their marks, the survivors' set-up mass beside it (m.list[1] and m.size are as
+	// lay_model_bins left them), the marked nodes rescaled
+	HIP_TRY(hipMemsetAsync(ctx->grid[0], 0, sizeof(float) * 256 * (size_t) nbc, s));
+	HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof(int) * 2, s));
+	if(old_nbc) sink_carry_grid_kernel<<<std::min(2048u, cdiv(old_nbc, 4)), 256, 0, s>>>(g, old_nbc, nbc, old_keys, old_grid, old_marks, ctx->part[r].table, ctx->grid[0], new_marks, d_flags);
+	for(size_t mi = 0; mi < nm; ++mi) {
+		const Model& m = ctx->models[mi];
+		if(!cols[mi].total || !pbc) continue;
+		rasterize_blocks_kernel<<<pbc, 256, 0, s>>>(g, cols[mi].xyz, m.list[1], m.size, ctx->part[r].keys, ctx->part[r].table, mass_grid, m.mc.mass, 0.f, 0.f, 0.f);
+	}
+	if(nbc) sink_rescale_grid_kernel<<<std::min(2048u, cdiv(nbc, 4)), 256, 0, s>>>(nbc, new_marks, mass_grid, ctx->grid[0]);
+	int rc = launch_prepare(ctx, PrepareFor::Setup);
+	if(rc) return rc;
+	HIP_TRY(hipGetLastError());
+	rc = read_status(ctx);
+	if(rc) return rc;
+	{
+		int flag = 0;
+		HIP_TRY(hipMemcpy(&flag, d_flags, sizeof(int), hipMemcpyDeviceToHost));
+		if(flag & kSinkCarryMiss) return fail(ctx, MPM_ERR_INTERNAL, who + ": a dropped block of the old grid holds mass at a node no removed particle reaches");
+	}
+	// the books: n stays (everything the model was ever given), the removed particles balance through books_bias
+	if(int rc2 = relay_books(ctx, who, cols, bins)) return rc2;
+	for(size_t mi = 0; mi < nm; ++mi) ctx->models[mi].removed += res.removed[mi];
+	ctx->books_bias += (long long) selected;
+	ctx->relaid = true;
+	if(int rc2 = mpm_grid_totals(ctx, after)) return rc2;
+	res.mass = before[0] - after[0];
+	for(int d = 0; d < 3; ++d) res.momentum[d] = before[1 + d] - after[1 + d];
+	res.relaid = 1;
+	if(out) *out = res;
+	if(what->removed_xyz) memcpy(what->removed_xyz, h_rxyz.data(), sizeof(float) * 3 * selected);
+	if(what->removed_ids) memcpy(what->removed_ids, h_rids.data(), sizeof(int) * selected);
+	if(what->removed_model) memcpy(what->removed_model, h_rmodel.data(), sizeof(int) * selected);
+	return MPM_OK;
+}
+#undef RELAY_ALLOC
 
 // Heightfield ----------------------------------------------------------------------------------------------------------------------------
 // mpm_collision_object + mpm_heightfield -> the slot and the table's description (table = nullptr: the caller's); nullptr, or the message

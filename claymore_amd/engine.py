@@ -82,6 +82,7 @@ class Engine:
         self.models = []
         self._slot_geom = {}  # slot -> what set_collider_body(density=...) integrates over (_slot_geometry)
         self.emitters = []    # scenes.Emitter objects, served by main_loop (serve_emitters)
+        self.sinks = []       # scenes.Sink objects, served by main_loop before the emitters (serve_sinks)
         self.cur_time = 0.0
         self.dt = None
 
@@ -130,7 +131,7 @@ class Engine:
                 raise EngineError(_ffi.MPM_ERR_INVALID, "init_model: per-particle initial conditions need the HIP library (this API has no add_model_particles)")
             init, keep = self._particle_init("init_model", n, velocity, affine, state, logjp, state_kind)   # (keep: the arrays live until the call returns)
             self._check(self.api.add_model_particles(self.ctx, int(material), C.byref(p), xyz.ctypes.data_as(C.c_void_p), n, v, C.byref(init), C.byref(mid)))
-        self.models.append({"material": int(material), "n": n, "params": p})
+        self.models.append({"material": int(material), "n": n, "params": p, "removed": 0})
         return mid.value
 
     @staticmethod
@@ -175,6 +176,74 @@ class Engine:
                                             C.byref(init), C.byref(first)))
         self.models[model]["n"] += n
         return first.value
+
+    @staticmethod
+    def _sink_regions(who, regions):
+        """A list of region dicts as an array of mpm_collision_shape: set_collision_shape's keywords (kind, a, b, radius, inside_out), or the scene
+        files' keys - "point" / "normal" (half-space), "center" (sphere, box), "half_extents" (box); a capsule has a, b and radius only."""
+        regions = [] if regions is None else ([regions] if isinstance(regions, dict) else list(regions))
+        arr = (_ffi.CollisionShape * max(1, len(regions)))()
+        alias = {"point": "a", "center": "a", "normal": "b", "half_extents": "b"}
+        for sh, reg in zip(arr, regions):
+            r = {alias.get(k, k): v for k, v in reg.items()}
+            unknown = set(r) - {"kind", "shape", "a", "b", "radius", "inside_out"}
+            if unknown:
+                raise ValueError(f"{who}: unknown region keys {sorted(unknown)}")
+            kind = r.get("kind", r.get("shape"))
+            sh.kind = _ffi.SHAPE_NAMES[kind] if isinstance(kind, str) else int(kind)
+            sh.inside_out = 1 if r.get("inside_out") else 0
+            a, b = r.get("a", (0.0, 0.0, 0.0)), r.get("b", (0.0, 0.0, 0.0))
+            for d in range(3):
+                sh.a[d], sh.b[d] = float(a[d]), float(b[d])
+            sh.radius = float(r.get("radius", 0.0))
+        return arr, len(regions)
+
+    def count_in(self, regions, model=-1):
+        """How many live particles of each model lie in the regions (mpm_count_particles_in, HIP library only): the predicate of `remove` alone,
+        nothing is written.  regions: one dict or a list of up to 8, as `remove` takes them; model: one model, or -1 for all.  Returns a list with
+        one count per model."""
+        if not hasattr(self.api, "count_particles_in"):
+            raise EngineError(_ffi.MPM_ERR_INVALID, "count_in needs the HIP library (this API has no count_particles_in)")
+        arr, n = self._sink_regions("count_in", regions)
+        out = (C.c_int64 * 8)()
+        self._check(self.api.count_particles_in(self.ctx, int(model), arr, n, out))
+        return [int(out[m]) for m in range(len(self.models))]
+
+    def remove(self, regions=None, ids=None, model=-1, return_removed=False):
+        """Take particles out of an engine that has been set up, at a substep boundary (mpm_remove_particles, HIP library only): a sink.  A live
+        particle of `model` (-1: every model) goes when it lies in any of the `regions` - dicts with set_collision_shape's keywords (kind, a, b,
+        radius, inside_out) or the scene files' keys (point / normal, center, half_extents), in domain coordinates - or when its id is in `ids`
+        (track_ids engines, model >= 0).  Returns {"removed": per-model counts, "mass", "momentum": what left the grid, "relaid"} and, with
+        return_removed, "xyz" (k, 3), "ids" (k,) (-1 untracked) and "model" (k,) of the removed particles in unspecified order.  Survivors keep
+        their state bit for bit and the velocity field they were in; a call that selects nothing costs one counting pass and changes nothing
+        (relaid False).  models[m]["n"] stays - removed ids are never reused -, models[m]["removed"] accumulates."""
+        if not hasattr(self.api, "remove_particles"):
+            raise EngineError(_ffi.MPM_ERR_INVALID, "remove needs the HIP library (this API has no remove_particles)")
+        arr, n = self._sink_regions("remove", regions)
+        what = _ffi.Removal()
+        what.regions, what.nregions = arr, n
+        idarr = None
+        if ids is not None:
+            idarr = np.ascontiguousarray(ids, dtype=np.int32).ravel()
+            what.ids, what.nids = idarr.ctypes.data, idarr.size
+        res = _ffi.RemovalResult()
+        xyz = rid = rmodel = None
+        if return_removed:
+            if ids is None:                                                # the regions alone: their count sizes the arrays
+                cap = sum(self.count_in(regions, model)) if n else 0
+            else:                                                          # ids too: no more than every live particle of the model
+                cap = int(self.counts().particles[model]) if model >= 0 else 0
+            xyz, rid, rmodel = np.empty((cap, 3), np.float32), np.empty(cap, np.int32), np.empty(cap, np.int32)
+            what.removed_xyz, what.removed_ids, what.removed_model, what.capacity = xyz.ctypes.data, rid.ctypes.data, rmodel.ctypes.data, cap
+        self._check(self.api.remove_particles(self.ctx, int(model), C.byref(what), C.byref(res)))
+        removed = [int(res.removed[m]) for m in range(len(self.models))]
+        for m, k in enumerate(removed):
+            self.models[m]["removed"] = self.models[m].get("removed", 0) + k
+        out = {"removed": removed, "mass": float(res.mass), "momentum": np.array(list(res.momentum)), "relaid": bool(res.relaid)}
+        if return_removed:
+            k = sum(removed)
+            out.update(xyz=xyz[:k].copy(), ids=rid[:k].copy(), model=rmodel[:k].copy())
+        return out
 
     def set_model_velocity_field(self, model, v0=(0.0, 0.0, 0.0), grad=None, omega=None, pivot=(0.0, 0.0, 0.0)):
         """Start a model that has been added (init_model or init_model_mesh, before initial_setup) in the linear velocity field
@@ -256,7 +325,7 @@ class Engine:
         mid, n = C.c_int(-1), C.c_size_t(0)
         self._check(self.api.add_model_mesh(self.ctx, int(material), C.byref(p), v.ctypes.data, v.shape[0], f.ctypes.data, f.shape[0], C.byref(opt),
                                             vel, C.byref(mid), C.byref(n)))
-        self.models.append({"material": int(material), "n": int(n.value), "params": p})
+        self.models.append({"material": int(material), "n": int(n.value), "params": p, "removed": 0})
         return mid.value
 
     def initial_setup(self):
@@ -299,13 +368,25 @@ class Engine:
                 total += pts.shape[0]
         return total
 
+    def serve_sinks(self, t=None):
+        """Sweep every attached sink (scenes.Sink; build_engine attaches a scene's "sinks") that has a sweep due at the substep boundary `t`
+        (default: cur_time): one Engine.remove per sink, however many of its sweeps are due.  Returns the number of particles removed."""
+        t = self.cur_time if t is None else t
+        total = 0
+        for sk in self.sinks:
+            if sk.due(t):
+                total += sum(self.remove(regions=[sk.region], model=sk.model)["removed"])
+        return total
+
     def main_loop(self, nframes, fps, dt_default, on_frame=None):
-        """GmpmSimulator::main_loop (gmpm_simulator.cuh:303-592): adaptive dt, `nframes` frames.  Attached emitters are served after set-up
-        and after every substep."""
+        """GmpmSimulator::main_loop (gmpm_simulator.cuh:303-592): adaptive dt, `nframes` frames.  Attached sinks and emitters are served after
+        set-up and after every substep, sinks first."""
         spf = 1.0 / fps
         max_v0 = 0.0
         dt = self.compute_dt(max_v0, 0.0, spf, dt_default)
         self.initial_setup()
+        if self.sinks:
+            self.serve_sinks()
         if self.emitters:
             self.serve_emitters()
         steps = 0
@@ -317,6 +398,8 @@ class Engine:
                 self.cur_time += dt
                 dt = next_dt
                 steps += 1
+                if self.sinks:
+                    self.serve_sinks()
                 if self.emitters:
                     self.serve_emitters()
             if on_frame:
@@ -650,7 +733,7 @@ class Engine:
         """Full state at the current substep boundary as a numpy byte array (HIP engine only)."""
         n = C.c_size_t(0)
         self._check(self.api.checkpoint_size(self.ctx, C.byref(n)))
-        buf = np.empty(n.value, dtype=np.uint8)
+        buf = np.zeros(n.value, dtype=np.uint8)  # (zeros: the padding between the sections is no part of what the library writes)
         w = C.c_size_t(0)
         self._check(self.api.checkpoint_save(self.ctx, buf.ctypes.data, buf.size, C.byref(w)))
         return buf[: w.value]
@@ -932,7 +1015,8 @@ def weld_triangles(tris, vel=None):
 
 def build_engine(scene, device=0, api=None):
     """Create an Engine for a scene dict (claymore_amd.scenes) and add its models (no setup yet).  scene["track_ids"]: Engine's track_ids;
-    scene["emitters"]: particle sources (scenes.Emitter.from_dict), attached as Engine.emitters and served by Engine.main_loop."""
+    scene["emitters"]: particle sources (scenes.Emitter.from_dict), attached as Engine.emitters and served by Engine.main_loop;
+    scene["sinks"]: particle sinks (scenes.Sink.from_dict), attached as Engine.sinks and served there before the emitters."""
     cfg = _ffi.Config()
     a = api if api is not None else _ffi.load_hip()
     rc = a.default_config(scene["bits"], C.byref(cfg))
@@ -975,4 +1059,7 @@ def build_engine(scene, device=0, api=None):
     if scene.get("emitters"):  # particle sources (scenes.Emitter), served by main_loop at the substep boundaries
         from .scenes import Emitter
         eng.emitters = [Emitter.from_dict(scene["bits"], e) for e in scene["emitters"]]
+    if scene.get("sinks"):  # particle sinks (scenes.Sink), served by main_loop at the substep boundaries, before the emitters
+        from .scenes import Sink
+        eng.sinks = [Sink.from_dict(scene["bits"], e) for e in scene["sinks"]]
     return eng

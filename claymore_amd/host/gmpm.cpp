@@ -27,6 +27,10 @@
 // A top-level "emitters" array holds particle sources (emitter_rule.hpp: a box or disc nozzle, a velocity, a start and an end time, a model):
 // what is due is added to its model between two mpm_substep calls (mpm_emit_particles), so later frames of that model carry more points; with
 // simulation.output_ids the new points have the largest ids and the ascending-id order of the older ones stays as it was.
+// A top-level "sinks" array holds particle sinks (sink_rule.hpp: the shape keys of "colliders" - halfspace, sphere, box or capsule, at rest -
+// plus "model" (default -1: all), "start", "end" and "period"): a sink with a sweep due takes the particles in its region out between two
+// mpm_substep calls (mpm_remove_particles), before the emitters are served, so later frames carry fewer points.  simulation.output_removed
+// (default false) writes `removed_frame[f].json` beside each frame: per-model counts, mass and momentum removed since the last frame.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -44,6 +48,7 @@
 #include "particle_io.hpp"
 #include "model_field.hpp"
 #include "emitter_rule.hpp"
+#include "sink_rule.hpp"
 
 namespace {
 
@@ -664,6 +669,67 @@ int main(int argc, char** argv) {
 			counts[em.model] += pts.size() / 3;
 		}
 	};
+	// "sinks": particle sinks (sink_rule.hpp), swept at every substep boundary before the emitters are served: a sink with a sweep due takes the
+	// particles of its model(s) that lie in its region out through mpm_remove_particles, and the frames carry fewer points from then on.
+	// simulation.output_removed: removed_frame[f].json holds what the sinks took since the last frame - per-model counts, mass and momentum
+	struct SceneSink {
+		pio::Sink rule;
+		mpm_collision_shape region;
+	};
+	std::vector<SceneSink> sinks;
+	const bool out_removed = sim.has("output_removed") && sim["output_removed"].type == mj::Value::Bool && sim["output_removed"].b;
+	if(doc->has("sinks")) {
+		const mj::Value& list = (*doc)["sinks"];
+		for(size_t si = 0; si < list.arr.size(); ++si) {
+			SceneSink sk;
+			mpm_collision_object obj;
+			mpm_heightfield hf;
+			std::vector<float> heights;
+			bool moving = false;
+			if(!pio::parse_sink(list[si], sk.rule) || !parse_collider(list[si], obj, sk.region, moving, hf, heights, scene_dir)) return 1;
+			if(hf.nx > 0 || moving) {
+				std::fprintf(stderr, "gmpm: a sink is a halfspace, sphere, box or capsule at rest\n");
+				return 1;
+			}
+			if(sk.rule.model < -1 || sk.rule.model >= (int) counts.size()) {
+				std::fprintf(stderr, "gmpm: a sink names model %d, the scene has %zu\n", sk.rule.model, counts.size());
+				return 1;
+			}
+			sinks.push_back(sk);
+		}
+		std::printf("has %zu sinks\n", sinks.size());
+	}
+	long long removed_since[8] = {0};
+	double removed_mass = 0.0, removed_momentum[3] = {0.0, 0.0, 0.0};
+	auto serve_sinks = [&](double t) {
+		for(auto& sk: sinks) {
+			if(!sk.rule.due(t)) continue;
+			mpm_removal what;
+			std::memset(&what, 0, sizeof(what));
+			what.regions  = &sk.region;
+			what.nregions = 1;
+			mpm_removal_result res;
+			const int rr = mpm_remove_particles(ctx, sk.rule.model, &what, &res);
+			if(rr) die(ctx, rr);
+			for(size_t mi = 0; mi < counts.size(); ++mi) removed_since[mi] += (long long) res.removed[mi];
+			removed_mass += res.mass;
+			for(int d = 0; d < 3; ++d) removed_momentum[d] += res.momentum[d];
+		}
+	};
+	auto write_removed = [&](int frame) {
+		FILE* f = std::fopen((out_dir + "/removed_frame[" + std::to_string(frame) + "].json").c_str(), "w");
+		if(!f) {
+			std::fprintf(stderr, "gmpm: cannot write the removed particles of frame %d\n", frame);
+			std::exit(1);
+		}
+		std::fprintf(f, "{\"frame\": %d, \"removed\": [", frame);
+		for(size_t mi = 0; mi < counts.size(); ++mi) std::fprintf(f, "%s%lld", mi ? ", " : "", removed_since[mi]);
+		std::fprintf(f, "], \"mass\": %.17g, \"momentum\": [%.17g, %.17g, %.17g]}\n", removed_mass, removed_momentum[0], removed_momentum[1], removed_momentum[2]);
+		std::fclose(f);
+		for(auto& k: removed_since) k = 0;
+		removed_mass = removed_momentum[0] = removed_momentum[1] = removed_momentum[2] = 0.0;
+	};
+	if(!sinks.empty()) serve_sinks(0.0);
 	serve_emitters(0.0);
 	std::vector<float> buf, vbuf, sbuf;
 	pio::AsyncWriter io;
@@ -742,6 +808,7 @@ int main(int argc, char** argv) {
 			cur_time += dt;
 			dt = next_dt;
 			++steps;
+			if(!sinks.empty()) serve_sinks((double) cur_time);
 			if(!emitters.empty()) serve_emitters((double) cur_time);
 		}
 		if(frame > frames) break;
@@ -761,6 +828,7 @@ int main(int argc, char** argv) {
 		if(surface_iso > 0.f) write_surface(frame);
 		if(out_loads) write_loads(frame);
 		if(out_bodies) write_bodies(frame);
+		if(out_removed) write_removed(frame);
 		for(size_t mi = 0; mi < counts.size(); ++mi) {// output_model, :594-634
 			buf.resize(3 * counts[mi]);
 			vbuf.clear();

@@ -8,6 +8,7 @@
 #include "particle_io.hpp"
 #include "model_field.hpp"
 #include "emitter_rule.hpp"
+#include "sink_rule.hpp"
 #include "../csrc/mpm_collision_mesh.hpp"
 #include "../csrc/mpm_mesh_fill.hpp"
 #if !defined(__HIPCC__)
@@ -60,6 +61,21 @@ int main(int argc, char** argv) {
 				std::printf("%08x %08x %08x\n", b[0], b[1], b[2]);
 			}
 		}
+		return 0;
+	}
+	if(argc >= 4 && !std::strcmp(argv[1], "--sink")) {// host_selftest --sink '{"period": .., "start": .., "end": .., "model": ..}' T1 [T2 ..]: an entry of a scene file's "sinks" ->
+		// "model M", then per substep boundary (ascending times, as decimal or hex floats) "due K": the sweeps gmpm's one call there serves
+		mj::ValuePtr e;
+		try {
+			e = mj::parse(argv[2]);
+		} catch(const std::exception& ex) {
+			std::cerr << "cannot parse the sink object: " << ex.what() << "\n";
+			return 2;
+		}
+		pio::Sink sk;
+		if(!pio::parse_sink(*e, sk)) return 1;
+		std::printf("model %d\n", sk.model);
+		for(int i = 3; i < argc; ++i) std::printf("due %ld\n", sk.due(std::strtod(argv[i], nullptr)));
 		return 0;
 	}
 	if(argc == 4 && !std::strcmp(argv[1], "--bgeo-from")) {// host_selftest --bgeo-from points.f32 out.bgeo: raw float32 xyz -> BGEO frame

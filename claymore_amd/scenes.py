@@ -589,3 +589,66 @@ def sand_pour(bits=6, radius_cells=2.5, speed=1.0, drop_cells=10.0, start=0.0, e
     sc["emitters"] = [{"model": 0, "shape": "disc", "center": (0.5, ground + drop_cells * dx, 0.5), "normal": (0.0, -1.0, 0.0), "radius": radius_cells * dx,
                        "velocity": (0.0, -speed, 0.0), "start": start, "end": end}]
     return sc
+
+
+class Sink:
+    """A host-side particle sink: a region that turns into calls of Engine.remove (mpm_remove_particles), one sweep at a time.
+
+    region: one region dict of Engine.remove - set_collision_shape's keywords (kind, a, b, radius, inside_out) or the scene files' keys (point /
+    normal, center, half_extents) -, in domain coordinates; model: the model it drains, -1 for all.  Sweep k is due at t_k = start + k period
+    for every t_k < end; it is served by the first substep boundary t >= t_k, and several sweeps that are due at one boundary make one call
+    (a second sweep of the same particles would find nothing).  A sweep that selects nothing costs one counting pass.  The same rule in C++:
+    host/sink_rule.hpp."""
+
+    def __init__(self, bits, region, model=-1, start=0.0, end=np.inf, period=None):
+        if period is None or not (float(period) > 0.0) or not np.isfinite(float(period)):
+            raise ValueError("Sink: period is required and must be > 0")
+        if not isinstance(region, dict) or ("kind" not in region and "shape" not in region):
+            raise ValueError("Sink: region must be a dict with a kind")
+        self.bits, self.model, self.region = int(bits), int(model), dict(region)
+        self.start, self.end, self.period = float(start), float(end), float(period)
+        self.next_sweep = 0
+
+    @classmethod
+    def from_dict(cls, bits, d):
+        """An entry of a scene's "sinks": the region's keys beside {"model", "start", "end", "period"}."""
+        own = ("model", "start", "end", "period")
+        return cls(bits, {k: v for k, v in d.items() if k not in own}, d.get("model", -1), d.get("start", 0.0), d.get("end", np.inf), d.get("period"))
+
+    def due(self, t):
+        """How many sweeps the substep boundary `t` serves: every sweep that is due and has not been served (0: no call)."""
+        k = 0
+        while True:
+            tk = self.start + self.next_sweep * self.period
+            if not (tk < self.end and tk <= t):
+                break
+            self.next_sweep += 1
+            k += 1
+        return k
+
+
+def fountain(bits=6, radius_cells=3.0, speed=2.0, height_cells=None, sink_cells=4.0, period=None, start=0.0, end=0.05, dt=1e-4):
+    """faucet with a drain: a sink box over the whole floor that reaches sink_cells above the floor's wall zone (8 cells, where the sticky wall
+    holds the grid still and nothing would ever arrive), swept every `period` (default: the emitter's layer period, one sweep per emitted
+    layer).  What the nozzle pours in leaves through the floor, so the particle count reaches a steady state (scene key "sinks")."""
+    sc = faucet(bits=bits, radius_cells=radius_cells, speed=speed, height_cells=height_cells, start=start, end=end, dt=dt)
+    dx = 1.0 / (1 << bits)
+    top = (8.0 + sink_cells) * dx
+    sc["name"] = "fountain"
+    sc["sinks"] = [{"model": 0, "kind": "box", "center": (0.5, top / 2, 0.5), "half_extents": (0.5, top / 2, 0.5),
+                    "start": start, "period": (dx / 2) / speed if period is None else period}]
+    return sc
+
+
+def drain(bits=6, block_cells=12, gap_cells=4.0, period=1e-3, dt=1e-4):
+    """A J-fluid block that falls through a gap into a sink slab: the block hangs gap_cells above a half-space sink whose plane lies under it,
+    and everything that sinks below the plane is taken out at the next sweep."""
+    n = 1 << bits
+    dx = 1.0 / n
+    lo = n // 2 - block_cells // 2
+    y0 = n // 3
+    plane = (y0 - gap_cells) * dx
+    return {"name": "drain", "bits": bits, "dt": dt, "config": {"max_ppc": 16},
+            "models": [{"material": J_FLUID, "xyz": lattice_box(bits, (lo, y0, lo), (lo + block_cells, y0 + block_cells, lo + block_cells)), "v0": (0.0, 0.0, 0.0),
+                        "params": {"volume": _vol(bits), "rho": 1e3}}],
+            "sinks": [{"model": 0, "kind": "halfspace", "point": (0.5, plane, 0.5), "normal": (0.0, 1.0, 0.0), "period": period}]}

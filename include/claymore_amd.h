@@ -554,10 +554,67 @@ int mpm_set_model_velocity_field(mpm_ctx* ctx, int model, const float v0[3], con
  * has been through the halo tagging; a tracked context whose ids are not valid.  MPM_ERR_CAPACITY for a block that would hold more than
  * max_ppc * 64 particles of the model (whatever drop_overflow says, as at set-up), with grow = 0 for block or bin capacities that do not
  * suffice, and when the device cannot hold the staging arrays.  n == 0 is MPM_OK and changes nothing.
- * Not offered: removing particles (a removed particle's share of the grid momentum cannot be subtracted exactly - v_p and C_p exist only in
- * the registers of the substep kernels), groups and MGSP ranks, an incremental emission inside the rebuild. */
+ * Not offered: groups and MGSP ranks, an incremental emission inside the rebuild.  (Removal: mpm_remove_particles below.) */
 int mpm_emit_particles(mpm_ctx* ctx, int model, const float* xyz, size_t n, const float v0[3], const mpm_particle_init* init /* may be NULL */,
 					   int32_t* first_id /* may be NULL */);
+
+/* Extension: take particles out of a context that has been set up - a sink, emission's mirror image.  HIP library only, single contexts only.
+ * Which particles: a live particle of a selected model (model >= 0: that one; -1: all) goes when the signed distance of any region at its
+ * position is <= 0, or when its id is in `ids`.  The regions are mpm_collision_shape's four kinds in domain coordinates, without a pose: the
+ * point that is tested is the particle's float32 world position, as the readouts return it, and the distance is the very function the
+ * colliders evaluate.  They pass the checks of mpm_set_collision_shape (a half-space's normal is normalised the same way); inside_out selects
+ * the complement; a NaN distance selects nothing.  `ids` (tracked contexts, model >= 0) names particles of that model; an id that names no live
+ * particle is ignored and not counted, duplicates are fine.  mpm_count_particles_in is the predicate alone: out[m] = how many particles of
+ * model m the regions select; it writes nothing.
+ * When: mpm_emit_particles' preconditions - after set-up, at a substep boundary with the grid holding momenta, a single context that never
+ * belonged to a group, ids valid if tracked.
+ * What it is: a re-lay, O(all particles) like an emission, not a change of the substep loop.  A removed particle's share of
+ * the grid momentum cannot be subtracted exactly (v_p and C_p exist only in the registers of the substep kernels) - and need not be: what the
+ * next substep reads off the grid is the node velocity p / m, and the next P2G rewrites mass and momentum.  So the removal keeps every node's
+ * velocity and gives it the mass of the particles that remain.  Afterwards
+ *   - every survivor's position and stored state (b with its mark, or J; log Jp) and, in a tracked context, its id have the bits they had;
+ *   - mpm_get_counts shrinks by removed[m]; the model's n - everything it was ever given - stays: a later emission continues its ids from n
+ *     and a removed id never returns; the cumulative lost / dropped / discarded counters are untouched; a checkpoint saved afterwards loads
+ *     like one saved after particles were lost;
+ *   - a grid node that no removed particle's 27-node stencil reaches has the bits it had (its block may have a new number).  A reached node
+ *     with old mass m_old > 0: with m' the set-up rasteriser's mass of all surviving particles of all models at that node, m' == 0 leaves +0 in
+ *     all four channels, else the mass is m' and each momentum p_old * r, r = m' / m_old (one float32 division).  A reached node whose old mass
+ *     is not > 0 keeps its bits.  A block of the old grid that the survivors' partition does not hold is dropped;
+ *   - out->removed[m]: particles taken out of model m; out->mass and out->momentum: mpm_grid_totals before the call minus after it;
+ *     out->relaid = 1, and the next rebuild is not offered the still path.  Capacities neither shrink nor grow.  A model may become empty,
+ *     and so may every model of the context.
+ * Nothing selected: MPM_OK with relaid = 0.  The call has launched its count pass alone, the context is untouched bit for bit and the still
+ * path stays on offer - which is what makes a sink that is polled every few substeps affordable.
+ * removed_xyz (3 per particle) / removed_ids / removed_model (any may be NULL; `capacity` particles each) receive the removed particles in an
+ * unspecified order, the three arrays row by row alike; the id is -1 in an untracked context.
+ * Errors - a refused call changes nothing: mpm_emit_particles' list (MPM_ERR_NOT_READY before set-up; MPM_ERR_INVALID for a bad model, a
+ * non-zero reserved word, a grid that holds velocities, a group or halo-tagged context, ids that are not valid), MPM_ERR_INVALID for an invalid
+ * region or nregions > 8, for `ids` with model < 0 or in an untracked context, for an id outside 0 .. n - 1; MPM_ERR_CAPACITY when `capacity`
+ * is smaller than the number selected (out->removed then holds the true counts) or the device cannot hold the staging arrays (emission's
+ * 56 B per surviving particle, the old grid, 1 KiB per neighbour block for m', 20 B per removed particle).  MPM_ERR_INTERNAL if a dropped block
+ * held mass at a node no removed particle reaches.
+ * Not offered: groups and MGSP ranks, the oracle, a removal inside the substep. */
+enum { MPM_MAX_SINK_REGIONS = 8 };
+typedef struct mpm_removal {
+	const mpm_collision_shape* regions; /* nregions of them, 0..8 */
+	int nregions;
+	const int32_t* ids; /* nids of them; NULL with nids == 0 */
+	size_t nids;
+	float* removed_xyz;	/* capacity * 3, may be NULL */
+	int32_t* removed_ids;	/* capacity, may be NULL */
+	int32_t* removed_model; /* capacity, may be NULL */
+	size_t capacity;
+	int reserved[4]; /* must be 0 */
+} mpm_removal;
+typedef struct mpm_removal_result {
+	int64_t removed[8];
+	double mass;
+	double momentum[3];
+	int relaid;
+	int reserved[3];
+} mpm_removal_result;
+int mpm_count_particles_in(mpm_ctx* ctx, int model /* -1: all */, const mpm_collision_shape* regions, int nregions, int64_t out[8]);
+int mpm_remove_particles(mpm_ctx* ctx, int model /* -1: all */, const mpm_removal* what, mpm_removal_result* out /* may be NULL */);
 
 /* Current capacities and the number of times check_capacity() (gmpm_simulator.cuh:283-300) has grown them: blocks
  * (exterior count limit), bins per model (bin_capacity[8]).  HIP library only. */

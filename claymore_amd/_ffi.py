@@ -115,6 +115,17 @@ class RigidBodyState(C.Structure):
 BODY_LOCKS = {"x": 1, "y": 2, "z": 4, "rx": 8, "ry": 16, "rz": 32}
 
 
+FORCE_UNIFORM, FORCE_POINT, FORCE_VORTEX, FORCE_DRAG = 1, 2, 3, 4   # MPM_FORCE_*
+FORCE_NAMES = {"uniform": FORCE_UNIFORM, "point": FORCE_POINT, "vortex": FORCE_VORTEX, "drag": FORCE_DRAG}
+MAX_FORCE_FIELDS = 4                   # MPM_MAX_FORCE_FIELDS
+
+
+class ForceField(C.Structure):
+    _fields_ = [("kind", C.c_int), ("falloff", C.c_int), ("vec", C.c_float * 3), ("centre", C.c_float * 3), ("strength", C.c_float),
+                ("swirl", C.c_float), ("pull", C.c_float), ("lift", C.c_float), ("soft", C.c_float), ("feather", C.c_float),
+                ("region", CollisionShape), ("reserved", C.c_int * 6)]
+
+
 class Counts(C.Structure):
     _fields_ = [("particle_blocks", C.c_int), ("neighbor_blocks", C.c_int), ("exterior_blocks", C.c_int),
                 ("model_count", C.c_int), ("bins", C.c_int64 * 8), ("particles", C.c_int64 * 8)]
@@ -203,6 +214,9 @@ HIP_ONLY = {
     "set_collider_body_state": (_i, [_vp, _i, _P(C.c_double), _P(C.c_double), _P(C.c_double), _P(C.c_double)]),
     "shape_mass_properties": (_i, [_P(CollisionShape), _f, _P(RigidBody)]),
     "mesh_mass_properties": (_i, [_vp, _sz, _vp, _sz, _f, _P(RigidBody)]),
+    "set_force_field": (_i, [_vp, _i, _P(ForceField)]),
+    "get_force_field": (_i, [_vp, _i, _P(ForceField)]),
+    "test_force_field": (_i, [_P(ForceField), _i, _f, _f, _vp, _vp, _sz, _vp, _i]),
     "halo_dump": (_i, [_vp, _vp, _vp, _ip, _vp]),
     "dump_block_rows": (_i, [_vp, _i, _vp, _P(_sz)]),
     "set_collision_clock": (_i, [_vp, _i, _f]),

@@ -24,6 +24,7 @@
 #include "mpm_particle_ids.hpp"
 #include "mpm_particle_emit.hpp"
 #include "mpm_particle_remove.hpp"
+#include "mpm_force_field.hpp"
 #include "mpm_collider_loads.hpp"
 #include "mpm_rigid_body.hpp"
 #include "mpm_storage.hpp"
@@ -213,6 +214,9 @@ struct mpm_ctx {
 	mpm_rigid_body body_desc[kMaxBodies] {};
 	bool frozen[kMaxBodies] = {};
 	CollisionPose frozen_pose[kMaxBodies] {};
+	// force fields (mpm_set_force_field; mpm_force_field.hpp): the slots as the kernels read them, by value - nothing on the device.  force.count > 0:
+	// launch_grid_update runs grid_force_kernel ahead of every applied update and mpm_run_fixed keeps the update out of the carry-over.
+	ForceArgs force {};
 	int group_refs	   = 0;// mpm_group handles on this context (grp_common_init / mpm_group_destroy): the single-context readouts refuse it
 	DevBuf<int> d_send_ids[32];
 	int n_halo = 0, n_inner = 0;
@@ -875,13 +879,14 @@ static LoadPivots load_pivots(const mpm_ctx* ctx, const mpm_load_options* opt) {
 }
 // collider_loads_kernel and its reduction on the compute stream: the totals of the update that dt would apply now into out (accumulate 0) or
 // added to out, with dt and the call count behind them (accumulate 1).  partials: kLoadGroups x [kLoadRows][kLoadSums] doubles.
-static int launch_collider_loads(mpm_ctx* ctx, float dt, const mpm_load_options* opt, double* partials, double* out, int accumulate) {
+// forces: the fields the coming update's pre-pass will apply (the readout), or none when that pass has run already (the gauge).
+static int launch_collider_loads(mpm_ctx* ctx, float dt, const mpm_load_options* opt, double* partials, double* out, int accumulate, const ForceArgs& forces) {
 	hipStream_t s		 = ctx->s_compute;
 	const LoadPivots piv = load_pivots(ctx, opt);
 	int state_pivots	 = ctx->body_mask;// a body row's default pivot is its x, read on the device
 	for(int i = 0; i < kMaxBodies; ++i)
 		if(opt && opt->has_pivot[1 + i]) state_pivots &= ~(1 << i);
-	with_collider_at_clock(ctx, [&](const auto& col) { collider_loads_kernel<<<kLoadGroups, 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, col, piv, partials); }, state_pivots);
+	with_collider_at_clock(ctx, [&](const auto& col) { collider_loads_kernel<<<kLoadGroups, 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, col, piv, partials, forces); }, state_pivots);
 	collider_loads_reduce_kernel<<<1, kLoadReduceThreads, 0, s>>>(partials, kLoadGroups, out, accumulate, (double) dt);
 	HIP_TRY(hipGetLastError());
 	return MPM_OK;
@@ -890,9 +895,14 @@ static int launch_collider_loads(mpm_ctx* ctx, float dt, const mpm_load_options*
 // grid-update phase, gmpm_simulator.cuh:326-347
 static int launch_grid_update(mpm_ctx* ctx, float dt) {
 	hipStream_t s = ctx->s_compute;
+	// the force fields' pass over the momenta (mpm_force_field.hpp), ahead of everything that reads them: the gauge, the bodies, the update
+	if(ctx->force.count > 0 && !ctx->grid_preupdated && ctx->nbc) {
+		const int est = std::min(ctx->g.cap, ctx->nbc + ctx->nbc / 16 + 64);
+		grid_force_kernel<<<cdiv(est, 4), 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, ctx->force);
+	}
 	// the load gauge reads the momenta this update is about to turn into velocities (a grid that holds none, or a grouped context's, is not read)
 	if(ctx->load_gauge && ctx->grid_momentum && !ctx->grid_preupdated && ctx->group_refs == 0 && ctx->mgsp_rank < 0 && !ctx->halo_tagged)
-		if(int rc = launch_collider_loads(ctx, dt, &ctx->load_opt, ctx->d_load_partials, ctx->d_load_acc, 1)) return rc;
+		if(int rc = launch_collider_loads(ctx, dt, &ctx->load_opt, ctx->d_load_partials, ctx->d_load_acc, 1, ForceArgs {})) return rc;
 	ctx->grid_momentum = false;// (from here on grid[0] holds velocities, until a rebuild carries the next P2G over)
 	if(ctx->grid_preupdated) {
 		ctx->grid_preupdated = false;
@@ -1111,6 +1121,7 @@ static int launch_rebuild(mpm_ctx* ctx, const SubstepPlan& plan, StillLaunch* ta
 	Partition& Pr = ctx->part[r];
 	const bool fused = fuse_dt > 0.f;
 	if(fused && ctx->body_mask) return fail(ctx, MPM_ERR_INTERNAL, "a grid update with a rigid body installed cannot ride on the carry-over (it has no BodyArgs instantiation)");
+	if(fused && ctx->force.count) return fail(ctx, MPM_ERR_INTERNAL, "a grid update with a force field installed cannot ride on the carry-over (the fields' pass runs ahead of a stand-alone update)");
 	const int still = plan.offer_still && !ctx->relaid ? 1 : 0;
 	ctx->relaid		= false;
 	ctx->grid_momentum = !fused;// the carry-over below writes grid[0]: the P2G's mass and momentum, or (fused) the updated velocities
@@ -1652,8 +1663,9 @@ int mpm_run_fixed(mpm_ctx* ctx, int nsteps, float dt) {
 		hipEvent_t* ev		 = &ctx->ev_ring[3 * in_window];
 		SubstepPlan plan {dt, dt};
 		plan.offer_still = still_on, plan.rebuild_clear = true;
-		// the last substep leaves the canonical state behind; the load gauge reads every update's momenta first; a rigid body's update is a kernel of its own
-		if(it + 1 < nsteps && !ctx->load_gauge && !ctx->body_mask) plan.fuse_dt = dt;
+		// the last substep leaves the canonical state behind; the load gauge reads every update's momenta first; a rigid body's update is a kernel of its own;
+		// the force fields' pass runs ahead of a stand-alone update
+		if(it + 1 < nsteps && !ctx->load_gauge && !ctx->body_mask && !ctx->force.count) plan.fuse_dt = dt;
 		if(by_stamps)
 			plan.stamp_row = ctx->d_stamps + (size_t) in_window * kStampRow;// (its clear writes the previous substep's end)
 		else {
@@ -3061,7 +3073,7 @@ int mpm_collider_loads(mpm_ctx* ctx, float dt, const mpm_load_options* opt, doub
 		(void) hipGetLastError();
 		return fail(ctx, MPM_ERR_CAPACITY, "mpm_collider_loads: no device memory");
 	}
-	if(int rc = launch_collider_loads(ctx, dt, opt, d_part.p, d_out.p, 0)) return rc;
+	if(int rc = launch_collider_loads(ctx, dt, opt, d_part.p, d_out.p, 0, ctx->force)) return rc;
 	HIP_TRY(hipMemcpyAsync(&out[0][0], d_out.p, sizeof(double) * kLoadRows * kLoadSums, hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
 	return MPM_OK;
@@ -3084,7 +3096,7 @@ int mpm_collider_contacts(mpm_ctx* ctx, float dt, int32_t* node_row4, float* rec
 	}
 	HIP_TRY(hipMemsetAsync(ctx->d_counter, 0, sizeof(unsigned long long), s));
 	with_collider_at_clock(ctx, [&](const auto& col) {
-		collider_contacts_kernel<<<kLoadGroups, 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, col, (unsigned long long) cap, d_nr.p, d_rec.p, ctx->d_counter);
+		collider_contacts_kernel<<<kLoadGroups, 256, 0, s>>>(ctx->g, &ctx->d_status[ST_NBC], ctx->grid[0], ctx->part[ctx->rollid].keys, dt, col, (unsigned long long) cap, d_nr.p, d_rec.p, ctx->d_counter, ctx->force);
 	});
 	HIP_TRY(hipGetLastError());
 	unsigned long long count = 0;
@@ -3351,6 +3363,102 @@ int mpm_test_collision_volume(const mpm_collision_object* obj, const mpm_collisi
 	HIP_TRY0(hipMemcpy(dT.p, field4, sizeof(float4) * cells, hipMemcpyHostToDevice));
 	v.table = dT.p;
 	return test_collision_query(c, Heightfield {}, time, xyz, n, out4, v);
+}
+
+// Force fields ------------------------------------------------------------------------------------------------------------------------------
+// mpm_force_field -> the slot the kernels read (the vortex axis and a half-space region's normal normalised; fields a kind does not read are
+// kept as given); nullptr, or the message that names the offending field
+static const char* make_force_slot(const mpm_force_field* f, ForceSlot& out) {
+	if(f->kind < MPM_FORCE_UNIFORM || f->kind > MPM_FORCE_DRAG) return "force field: unknown kind";
+	if(f->falloff < 0 || f->falloff > 2) return "force field: falloff outside 0..2";
+	for(int w: f->reserved)
+		if(w) return "force field: a reserved word is not 0";
+	if(!shape_finite3(f->vec)) return "force field: vec is not finite";
+	if(!shape_finite3(f->centre)) return "force field: centre is not finite";
+	if(!std::isfinite(f->strength)) return "force field: strength is not finite";
+	if(!std::isfinite(f->swirl) || !std::isfinite(f->pull) || !std::isfinite(f->lift)) return "force field: swirl, pull or lift is not finite";
+	if(!std::isfinite(f->soft) || f->soft < 0.f) return "force field: soft must be finite and >= 0";
+	if(!std::isfinite(f->feather) || f->feather < 0.f) return "force field: feather must be finite and >= 0";
+	if(f->kind == MPM_FORCE_DRAG && f->strength < 0.f) return "force field: strength of a DRAG field must be >= 0";
+	ForceSlot c {};
+	c.kind	  = f->kind;
+	c.falloff = f->falloff;
+	for(int d = 0; d < 3; ++d) c.vec[d] = f->vec[d], c.centre[d] = f->centre[d];
+	if(f->kind == MPM_FORCE_VORTEX) {
+		const float len = sqrtf(f->vec[0] * f->vec[0] + f->vec[1] * f->vec[1] + f->vec[2] * f->vec[2]);
+		if(!(len > 0.f) || !std::isfinite(len)) return "force field: the axis vec of a VORTEX field must not be zero";
+		for(int d = 0; d < 3; ++d) c.vec[d] = f->vec[d] / len;// (a unit axis stays exactly itself)
+	}
+	c.strength = f->strength, c.swirl = f->swirl, c.pull = f->pull, c.lift = f->lift, c.soft = f->soft, c.feather = f->feather;
+	if(f->region.kind) {
+		const mpm_collision_shape& r = f->region;
+		if(!shape_finite3(r.a) || !std::isfinite(r.radius) || (r.kind != MPM_SHAPE_SPHERE && !shape_finite3(r.b))) return "force field: region: a number is not finite";
+		mpm_collision_object obj;
+		mpm_default_collision_object(&obj);
+		ShapeSlot slot;
+		if(const char* msg = make_shape_slot(&obj, &r, slot)) return msg;// ("collision shape: ...": the region's own field)
+		c.region = slot.shape;
+	}
+	out = c;
+	return nullptr;
+}
+static bool force_slot_ok(int slot) {
+	return slot >= 0 && slot < MPM_MAX_FORCE_FIELDS;
+}
+
+int mpm_set_force_field(mpm_ctx* ctx, int slot, const mpm_force_field* f) {
+	static_assert(MPM_MAX_FORCE_FIELDS == kMaxForceFields && MPM_FORCE_DRAG == kForceDrag, "the ABI's kinds and slots are the kernels'");
+	if(!ctx) return MPM_ERR_INVALID;
+	if(!force_slot_ok(slot)) return fail(ctx, MPM_ERR_INVALID, "mpm_set_force_field: slot outside 0..3");
+	ForceSlot c {};
+	if(f) {
+		if(const char* msg = make_force_slot(f, c)) return fail(ctx, MPM_ERR_INVALID, std::string("mpm_set_force_field: ") + msg);
+		if(ctx->group_refs > 0 || ctx->mgsp_rank >= 0 || ctx->halo_tagged)
+			return fail(ctx, MPM_ERR_INVALID, "mpm_set_force_field: the context belongs (or belonged) to a multi-GPU group; force fields in groups are not computed");
+		if(ctx->grid_preupdated) return fail(ctx, MPM_ERR_INVALID, "mpm_set_force_field: the next grid update has been applied already: install at a substep boundary");
+	}
+	ctx->force.slot[slot] = c;// (kind 0: empty.  By value with the next launch: nothing enqueued reads it)
+	ctx->force.count	  = 0;
+	for(int i = 0; i < kMaxForceFields; ++i)
+		if(ctx->force.slot[i].kind) ctx->force.count = i + 1;
+	return MPM_OK;
+}
+
+int mpm_get_force_field(mpm_ctx* ctx, int slot, mpm_force_field* out) {
+	if(!ctx) return MPM_ERR_INVALID;
+	if(!force_slot_ok(slot)) return fail(ctx, MPM_ERR_INVALID, "mpm_get_force_field: slot outside 0..3");
+	if(!out) return fail(ctx, MPM_ERR_INVALID, "mpm_get_force_field: NULL out");
+	const ForceSlot& c = ctx->force.slot[slot];
+	mpm_force_field o {};
+	o.kind = c.kind, o.falloff = c.falloff;
+	for(int d = 0; d < 3; ++d) o.vec[d] = c.vec[d], o.centre[d] = c.centre[d], o.region.a[d] = c.region.a[d], o.region.b[d] = c.region.b[d];
+	o.strength = c.strength, o.swirl = c.swirl, o.pull = c.pull, o.lift = c.lift, o.soft = c.soft, o.feather = c.feather;
+	o.region.kind = c.region.kind, o.region.inside_out = c.region.inside_out, o.region.radius = c.region.radius;
+	*out = o;
+	return MPM_OK;
+}
+
+int mpm_test_force_field(const mpm_force_field* fields, int n_fields, float dt, float dx, const float* xyz, const float* mp4, size_t n, float* out4, int device) {
+	(void) dx;// (positions are domain points already; kept for the call shape of the grid kernels)
+	if(n_fields < 0 || n_fields > MPM_MAX_FORCE_FIELDS || (n_fields && !fields)) return MPM_ERR_INVALID;
+	ForceArgs fa {};
+	for(int i = 0; i < n_fields; ++i) {
+		if(fields[i].kind == 0) continue;
+		if(make_force_slot(&fields[i], fa.slot[i])) return MPM_ERR_INVALID;
+		fa.count = i + 1;
+	}
+	if(!xyz || !mp4 || !out4 || n == 0) return MPM_ERR_INVALID;
+	HIP_TRY0(hipSetDevice(device));
+	DevBuf<float> dX, dM, dO;
+	HIP_TRY0(dX.alloc(3 * n, nullptr));
+	HIP_TRY0(dM.alloc(4 * n, nullptr));
+	HIP_TRY0(dO.alloc(4 * n, nullptr));
+	HIP_TRY0(hipMemcpy(dX.p, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice));
+	HIP_TRY0(hipMemcpy(dM.p, mp4, sizeof(float) * 4 * n, hipMemcpyHostToDevice));
+	test_force_field_kernel<<<cdiv(n, 256), 256>>>(fa, dt, n, dX.p, dM.p, dO.p);
+	HIP_TRY0(hipGetLastError());
+	HIP_TRY0(hipMemcpy(out4, dO.p, sizeof(float) * 4 * n, hipMemcpyDeviceToHost));
+	return MPM_OK;
 }
 
 int mpm_streams(mpm_ctx* ctx, void** compute_stream, void** comm_stream) {

@@ -21,6 +21,7 @@
 // lane holds eight doubles at most (no private array indexed at run time, no scratch).
 #pragma once
 #include "mpm_kernels.hpp"
+#include "mpm_force_field.hpp"
 
 namespace mpm {
 
@@ -111,9 +112,26 @@ MPM_DEV double load_wave_sum(double x) {
 
 // The totals' first stage, a workgroup of 256: workgroup g writes its [kLoadRows][kLoadSums] partial sums to partials + g * kLoadRows * kLoadSums.
 // With APPLY the pass is the grid update as well: per massed cell the velocity the last collider left is stored and the doubled |v|^2 folded into
-// the max slots.
-template<bool APPLY, class Collider, class Grid>
-MPM_DEV void loads_frame(const GridCfg& cfg, const int* __restrict__ nbc_ptr, Grid* grid, const int* __restrict__ keys, float dt, const Collider& col, const LoadPivots& piv, double* __restrict__ partials, unsigned* __restrict__ max_vel_bits) {
+// the max slots.  before(kx, ky, kz, cell, v, active): what happens to the register copy of a cell ahead of the walk (forced_cell for the readouts, which
+// see the momenta the force fields' pass will leave; nothing for the applying pass, which runs behind that pass).
+struct NoFields {
+	MPM_DEV void operator()(int, int, int, int, float4&, bool) const {}
+};
+// The force fields on the register copy of a massed cell, behind one wave-uniform branch (mpm_force_field.hpp).
+struct ForcedCell {
+	const GridCfg& cfg;
+	const ForceArgs& forces;
+	float dt;
+	MPM_DEV void operator()(int kx, int ky, int kz, int cell, float4& v, bool active) const {
+		if(forces.count > 0) {
+			float X[3];
+			force_node_position(kx, ky, kz, cell, cfg.dx, X);
+			if(active) force_cell(forces, X, dt, v);
+		}
+	}
+};
+template<bool APPLY, class Collider, class Grid, class Before = NoFields>
+MPM_DEV void loads_frame(const GridCfg& cfg, const int* __restrict__ nbc_ptr, Grid* grid, const int* __restrict__ keys, float dt, const Collider& col, const LoadPivots& piv, double* __restrict__ partials, unsigned* __restrict__ max_vel_bits, const Before& before = NoFields {}) {
 #pragma clang fp contract(off)
 	__shared__ double s_part[4][kLoadRows][kLoadSums];
 	const int cell = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -122,6 +140,7 @@ MPM_DEV void loads_frame(const GridCfg& cfg, const int* __restrict__ nbc_ptr, Gr
 	float vel_sqr = 0.f;
 	for_each_cell(cfg, nbc_ptr, grid, keys, [&](int kx, int ky, int kz, Grid* g, float4& v, bool active) {
 		float fv[3] = {0.f, 0.f, 0.f};// the velocity the last collider left
+		before(kx, ky, kz, cell, v, active);
 		load_cell(cfg, col, kx, ky, kz, cell, dt, active, v, [&](int row, bool touched, const int (&node)[3], const float (&dv)[3], const float (&vel)[3]) {
 #pragma clang fp contract(off)
 			if constexpr(APPLY) fv[0] = vel[0], fv[1] = vel[1], fv[2] = vel[2];
@@ -160,8 +179,8 @@ MPM_DEV void loads_frame(const GridCfg& cfg, const int* __restrict__ nbc_ptr, Gr
 }
 // The readout: the frame without the stores.
 template<class Collider>
-__global__ __launch_bounds__(256) void collider_loads_kernel(GridCfg cfg, const int* __restrict__ nbc_ptr, const float* __restrict__ grid, const int* __restrict__ keys, float dt, Collider col, LoadPivots piv, double* __restrict__ partials) {
-	loads_frame<false>(cfg, nbc_ptr, grid, keys, dt, col, piv, partials, nullptr);
+__global__ __launch_bounds__(256) void collider_loads_kernel(GridCfg cfg, const int* __restrict__ nbc_ptr, const float* __restrict__ grid, const int* __restrict__ keys, float dt, Collider col, LoadPivots piv, double* __restrict__ partials, ForceArgs forces) {
+	loads_frame<false>(cfg, nbc_ptr, grid, keys, dt, col, piv, partials, nullptr, ForcedCell {cfg, forces, dt});
 }
 
 // The second stage, one workgroup of kLoadReduceThreads: the partials of `groups` workgroups in index order - wave w adds its 64 workgroups one
@@ -201,9 +220,10 @@ __global__ __launch_bounds__(kLoadReduceThreads) void collider_loads_reduce_kern
 // The contact map: one record per touched (node, row), appended through a wave-aggregated integer counter (one atomic per touched wave and
 // row); records beyond `capacity` are counted and not written.  node_row4: int32 {i, j, k, row}; rec8: float32 {m, dv[3], v_after[3], 0}.
 template<class Collider>
-__global__ __launch_bounds__(256) void collider_contacts_kernel(GridCfg cfg, const int* __restrict__ nbc_ptr, const float* __restrict__ grid, const int* __restrict__ keys, float dt, Collider col, unsigned long long capacity, int* __restrict__ node_row4, float* __restrict__ rec8, unsigned long long* counter) {
+__global__ __launch_bounds__(256) void collider_contacts_kernel(GridCfg cfg, const int* __restrict__ nbc_ptr, const float* __restrict__ grid, const int* __restrict__ keys, float dt, Collider col, unsigned long long capacity, int* __restrict__ node_row4, float* __restrict__ rec8, unsigned long long* counter, ForceArgs forces) {
 	const int cell = threadIdx.x & 63;
 	for_each_cell(cfg, nbc_ptr, grid, keys, [&](int kx, int ky, int kz, const float*, float4& v, bool active) {
+		ForcedCell {cfg, forces, dt}(kx, ky, kz, cell, v, active);
 		load_cell(cfg, col, kx, ky, kz, cell, dt, active, v, [&](int row, bool touched, const int (&node)[3], const float (&dv)[3], const float (&vel)[3]) {
 			const unsigned long long mask = __ballot(touched);
 			if(!mask) return;

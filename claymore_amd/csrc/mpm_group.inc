@@ -486,6 +486,10 @@ int grp_common_init(mpm_group* g) {
 		g->ctx->err = "a context with a rigid body (mpm_set_collider_body) cannot join a group: bodies in multi-GPU groups are not computed";
 		return gfail(g, MPM_ERR_INVALID, g->ctx->err);
 	}
+	if(g->ctx->force.count) {
+		g->ctx->err = "a context with a force field (mpm_set_force_field) cannot join a group: force fields in multi-GPU groups are not computed";
+		return gfail(g, MPM_ERR_INVALID, g->ctx->err);
+	}
 	if(const char* e = getenv("MPM_GROUP_DEFER")) g->no_defer = e[0] == '0';
 	if(const char* e = getenv("MPM_GROUP_PAD_TIGHT")) g->tight_pad = e[0] == '1';
 	if(const char* e = getenv("MPM_GROUP_OVERLAP_TAG")) g->overlap_tag = e[0] != '0';

@@ -238,6 +238,7 @@ int mpm_halo_tag_begin(mpm_ctx* ctx) {
 	phase_call(ctx);
 	if(!ctx || !ctx->ready) return MPM_ERR_NOT_READY;
 	if(ctx->body_mask) return fail(ctx, MPM_ERR_INVALID, "mpm_halo_tag_begin: the context has a rigid body (mpm_set_collider_body); bodies in multi-GPU groups are not computed");
+	if(ctx->force.count) return fail(ctx, MPM_ERR_INVALID, "mpm_halo_tag_begin: the context has a force field (mpm_set_force_field); force fields in multi-GPU groups are not computed");
 	HIP_TRY(hipSetDevice(ctx->device));
 	int rc = halo_alloc(ctx);
 	if(rc) return rc;
@@ -426,6 +427,7 @@ static int mgsp_tag(mpm_ctx* ctx, const SubstepPlan& plan, const int* dev_all_ke
 int mpm_mgsp_tag(mpm_ctx* ctx, const int* dev_all_keys, int pad_rows, int world, int rank) {
 	phase_call(ctx);
 	if(ctx && ctx->body_mask) return fail(ctx, MPM_ERR_INVALID, "mpm_mgsp_tag: the context has a rigid body (mpm_set_collider_body); bodies in multi-GPU groups are not computed");
+	if(ctx && ctx->force.count) return fail(ctx, MPM_ERR_INVALID, "mpm_mgsp_tag: the context has a force field (mpm_set_force_field); force fields in multi-GPU groups are not computed");
 	return ctx ? mgsp_tag(ctx, default_plan(ctx), dev_all_keys, pad_rows, world, rank) : MPM_ERR_INVALID;
 }
 

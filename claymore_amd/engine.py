@@ -83,6 +83,7 @@ class Engine:
         self._slot_geom = {}  # slot -> what set_collider_body(density=...) integrates over (_slot_geometry)
         self.emitters = []    # scenes.Emitter objects, served by main_loop (serve_emitters)
         self.sinks = []       # scenes.Sink objects, served by main_loop before the emitters (serve_sinks)
+        self.forces = []      # scenes.ForceEntry objects, served by main_loop before the sinks (serve_forces)
         self.cur_time = 0.0
         self.dt = None
 
@@ -379,12 +380,14 @@ class Engine:
         return total
 
     def main_loop(self, nframes, fps, dt_default, on_frame=None):
-        """GmpmSimulator::main_loop (gmpm_simulator.cuh:303-592): adaptive dt, `nframes` frames.  Attached sinks and emitters are served after
-        set-up and after every substep, sinks first."""
+        """GmpmSimulator::main_loop (gmpm_simulator.cuh:303-592): adaptive dt, `nframes` frames.  Attached force entries, sinks and emitters
+        are served after set-up and after every substep, in that order."""
         spf = 1.0 / fps
         max_v0 = 0.0
         dt = self.compute_dt(max_v0, 0.0, spf, dt_default)
         self.initial_setup()
+        if self.forces:
+            self.serve_forces()
         if self.sinks:
             self.serve_sinks()
         if self.emitters:
@@ -398,6 +401,8 @@ class Engine:
                 self.cur_time += dt
                 dt = next_dt
                 steps += 1
+                if self.forces:
+                    self.serve_forces()
                 if self.sinks:
                     self.serve_sinks()
                 if self.emitters:
@@ -566,6 +571,58 @@ class Engine:
         self._slot_geometry(slot, ("shape", sh))
         if animate:
             self.set_collision_clock(True, float(obj.time))
+
+    def set_force_field(self, slot, kind=None, *, vec=(0.0, 0.0, 0.0), centre=(0.0, 0.0, 0.0), strength=0.0, swirl=0.0, pull=0.0, lift=0.0, soft=0.0,
+                        falloff=0, region=None, feather=0.0):
+        """Install a force field in slot 0 .. 3 (mpm_set_force_field, HIP engine only) at a substep boundary; kind=None empties the slot.  kind:
+        "uniform" (vec: the acceleration), "point" (centre, strength, falloff 0..2, soft), "vortex" (vec: the axis through centre; swirl, pull,
+        lift), "drag" (toward the velocity vec at the rate strength) or the MPM_FORCE_* number.  region: a dict in the vocabulary
+        Engine.remove(regions=...) takes, in domain coordinates (None: everywhere), with a soft edge `feather` wide.  Every grid update then
+        applies the installed fields to every grid node with mass before walls, gravity and colliders, slots in order."""
+        if kind is None:
+            self._check(self.api.set_force_field(self.ctx, int(slot), None))
+            return
+        f = _ffi.ForceField()
+        f.kind = _ffi.FORCE_NAMES[kind] if isinstance(kind, str) else int(kind)
+        f.falloff = int(falloff)
+        for d in range(3):
+            f.vec[d], f.centre[d] = float(vec[d]), float(centre[d])
+        f.strength, f.swirl, f.pull, f.lift, f.soft, f.feather = float(strength), float(swirl), float(pull), float(lift), float(soft), float(feather)
+        if region is not None:
+            f.region = self._sink_regions("set_force_field", region)[0][0]
+        self._check(self.api.set_force_field(self.ctx, int(slot), C.byref(f)))
+
+    def force_fields(self):
+        """The four slots as installed (mpm_get_force_field: unit axis, unit region normal): a list of dicts with set_force_field's keywords,
+        None for an empty slot."""
+        names = {v: k for k, v in _ffi.FORCE_NAMES.items()}
+        shapes = {v: k for k, v in _ffi.SHAPE_NAMES.items()}
+        out = []
+        for slot in range(_ffi.MAX_FORCE_FIELDS):
+            f = _ffi.ForceField()
+            self._check(self.api.get_force_field(self.ctx, slot, C.byref(f)))
+            if f.kind == 0:
+                out.append(None)
+                continue
+            r = f.region
+            region = None if r.kind == 0 else {"kind": shapes[r.kind], "a": tuple(r.a), "b": tuple(r.b), "radius": r.radius, "inside_out": bool(r.inside_out)}
+            out.append({"kind": names[f.kind], "vec": tuple(f.vec), "centre": tuple(f.centre), "strength": f.strength, "swirl": f.swirl, "pull": f.pull,
+                        "lift": f.lift, "soft": f.soft, "falloff": f.falloff, "region": region, "feather": f.feather})
+        return out
+
+    def serve_forces(self, t=None):
+        """Install or remove what every attached force entry (scenes.ForceEntry; build_engine attaches a scene's "forces", entry i in slot i) asks
+        for at the substep boundary `t` (default: cur_time).  Returns the number of slots changed."""
+        t = self.cur_time if t is None else t
+        changed = 0
+        for slot, fe in enumerate(self.forces):
+            act = fe.due(t)
+            if act > 0:
+                self.set_force_field(slot, **fe.field)
+            elif act < 0:
+                self.set_force_field(slot, None)
+            changed += act != 0
+        return changed
 
     def set_collision_heightfield(self, slot, heights=None, *, origin=(0.0, 0.0), spacing=None, inside_out=False, animate=False, **fields):
         """Install a heightfield - terrain y = h(x, z) in material coordinates - in slot 0 .. 3 (mpm_set_collision_heightfield, HIP engine
@@ -1016,7 +1073,8 @@ def weld_triangles(tris, vel=None):
 def build_engine(scene, device=0, api=None):
     """Create an Engine for a scene dict (claymore_amd.scenes) and add its models (no setup yet).  scene["track_ids"]: Engine's track_ids;
     scene["emitters"]: particle sources (scenes.Emitter.from_dict), attached as Engine.emitters and served by Engine.main_loop;
-    scene["sinks"]: particle sinks (scenes.Sink.from_dict), attached as Engine.sinks and served there before the emitters."""
+    scene["sinks"]: particle sinks (scenes.Sink.from_dict), attached as Engine.sinks and served there before the emitters;
+    scene["forces"]: force fields (scenes.ForceEntry.from_dict, entry i for slot i), attached as Engine.forces and served there first."""
     cfg = _ffi.Config()
     a = api if api is not None else _ffi.load_hip()
     rc = a.default_config(scene["bits"], C.byref(cfg))
@@ -1062,4 +1120,9 @@ def build_engine(scene, device=0, api=None):
     if scene.get("sinks"):  # particle sinks (scenes.Sink), served by main_loop at the substep boundaries, before the emitters
         from .scenes import Sink
         eng.sinks = [Sink.from_dict(scene["bits"], e) for e in scene["sinks"]]
+    if scene.get("forces"):  # force fields (scenes.ForceEntry), installed and removed by main_loop at the substep boundaries, before the sinks
+        from .scenes import ForceEntry
+        if len(scene["forces"]) > _ffi.MAX_FORCE_FIELDS:
+            raise ValueError(f"a scene holds at most {_ffi.MAX_FORCE_FIELDS} forces")
+        eng.forces = [ForceEntry.from_dict(e) for e in scene["forces"]]
     return eng

@@ -31,6 +31,10 @@
 // plus "model" (default -1: all), "start", "end" and "period"): a sink with a sweep due takes the particles in its region out between two
 // mpm_substep calls (mpm_remove_particles), before the emitters are served, so later frames carry fewer points.  simulation.output_removed
 // (default false) writes `removed_frame[f].json` beside each frame: per-model counts, mass and momentum removed since the last frame.
+// A top-level "forces" array holds up to four force fields (force_rule.hpp: "kind" uniform | point | vortex | drag with "vec", "centre", "strength",
+// "swirl", "pull", "lift", "soft", "falloff", "feather", an optional "region" with the shape keys of "colliders", at rest, and "start" / "end"):
+// entry i is installed in slot i (mpm_set_force_field) at the first substep boundary inside [start, end) and removed at the first one outside,
+// before sinks and emitters are served.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -49,6 +53,7 @@
 #include "model_field.hpp"
 #include "emitter_rule.hpp"
 #include "sink_rule.hpp"
+#include "force_rule.hpp"
 
 namespace {
 
@@ -729,6 +734,63 @@ int main(int argc, char** argv) {
 		for(auto& k: removed_since) k = 0;
 		removed_mass = removed_momentum[0] = removed_momentum[1] = removed_momentum[2] = 0.0;
 	};
+	// "forces": force fields (force_rule.hpp), entry i in slot i: installed and removed through mpm_set_force_field at the substep boundaries, before
+	// the sinks and the emitters are served.  "region" holds the shape keys of "colliders" (halfspace, sphere, box or capsule, at rest).
+	struct SceneForce {
+		pio::ForceRule rule;
+		mpm_force_field field;
+	};
+	std::vector<SceneForce> forces;
+	if(doc->has("forces")) {
+		const mj::Value& list = (*doc)["forces"];
+		if(list.arr.size() > MPM_MAX_FORCE_FIELDS) {
+			std::fprintf(stderr, "gmpm: a scene holds at most %d forces\n", (int) MPM_MAX_FORCE_FIELDS);
+			return 1;
+		}
+		for(size_t fi = 0; fi < list.arr.size(); ++fi) {
+			const mj::Value& e = list[fi];
+			SceneForce sf;
+			std::memset(&sf.field, 0, sizeof(sf.field));
+			pio::parse_force_rule(e, sf.rule);
+			const std::string kind = e.has("kind") ? e["kind"].string() : "";
+			sf.field.kind = kind == "uniform" ? MPM_FORCE_UNIFORM : kind == "point" ? MPM_FORCE_POINT : kind == "vortex" ? MPM_FORCE_VORTEX : kind == "drag" ? MPM_FORCE_DRAG : 0;
+			if(!sf.field.kind) {
+				std::fprintf(stderr, "gmpm: unknown force kind '%s' (expected uniform, point, vortex or drag)\n", kind.c_str());
+				return 1;
+			}
+			vec3(e, "vec", sf.field.vec);
+			vec3(e, "centre", sf.field.centre);
+			sf.field.falloff  = (int) num(e, "falloff", 0.f);
+			sf.field.strength = num(e, "strength", 0.f);
+			sf.field.swirl	  = num(e, "swirl", 0.f);
+			sf.field.pull	  = num(e, "pull", 0.f);
+			sf.field.lift	  = num(e, "lift", 0.f);
+			sf.field.soft	  = num(e, "soft", 0.f);
+			sf.field.feather  = num(e, "feather", 0.f);
+			if(e.has("region")) {
+				mpm_collision_object obj;
+				mpm_heightfield hf;
+				std::vector<float> heights;
+				bool moving = false;
+				if(!parse_collider(e["region"], obj, sf.field.region, moving, hf, heights, scene_dir)) return 1;
+				if(hf.nx > 0 || moving) {
+					std::fprintf(stderr, "gmpm: a force's region is a halfspace, sphere, box or capsule at rest\n");
+					return 1;
+				}
+			}
+			forces.push_back(sf);
+		}
+		std::printf("has %zu forces\n", forces.size());
+	}
+	auto serve_forces = [&](double t) {
+		for(size_t fi = 0; fi < forces.size(); ++fi) {
+			const int act = forces[fi].rule.due(t);
+			if(!act) continue;
+			const int rf = mpm_set_force_field(ctx, (int) fi, act > 0 ? &forces[fi].field : nullptr);
+			if(rf) die(ctx, rf);
+		}
+	};
+	if(!forces.empty()) serve_forces(0.0);
 	if(!sinks.empty()) serve_sinks(0.0);
 	serve_emitters(0.0);
 	std::vector<float> buf, vbuf, sbuf;
@@ -808,6 +870,7 @@ int main(int argc, char** argv) {
 			cur_time += dt;
 			dt = next_dt;
 			++steps;
+			if(!forces.empty()) serve_forces((double) cur_time);
 			if(!sinks.empty()) serve_sinks((double) cur_time);
 			if(!emitters.empty()) serve_emitters((double) cur_time);
 		}

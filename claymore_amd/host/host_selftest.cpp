@@ -9,6 +9,7 @@
 #include "model_field.hpp"
 #include "emitter_rule.hpp"
 #include "sink_rule.hpp"
+#include "force_rule.hpp"
 #include "../csrc/mpm_collision_mesh.hpp"
 #include "../csrc/mpm_mesh_fill.hpp"
 #if !defined(__HIPCC__)
@@ -76,6 +77,20 @@ int main(int argc, char** argv) {
 		if(!pio::parse_sink(*e, sk)) return 1;
 		std::printf("model %d\n", sk.model);
 		for(int i = 3; i < argc; ++i) std::printf("due %ld\n", sk.due(std::strtod(argv[i], nullptr)));
+		return 0;
+	}
+	if(argc >= 4 && !std::strcmp(argv[1], "--force")) {// host_selftest --force '{"start": .., "end": ..}' T1 [T2 ..]: the times of an entry of a scene file's "forces" ->
+		// per substep boundary (ascending times) what gmpm does there: 1 install, -1 remove, 0 nothing
+		mj::ValuePtr e;
+		try {
+			e = mj::parse(argv[2]);
+		} catch(const std::exception& ex) {
+			std::cerr << "cannot parse the force object: " << ex.what() << "\n";
+			return 2;
+		}
+		pio::ForceRule fr;
+		pio::parse_force_rule(*e, fr);
+		for(int i = 3; i < argc; ++i) std::printf("%d\n", fr.due(std::strtod(argv[i], nullptr)));
 		return 0;
 	}
 	if(argc == 4 && !std::strcmp(argv[1], "--bgeo-from")) {// host_selftest --bgeo-from points.f32 out.bgeo: raw float32 xyz -> BGEO frame

@@ -652,3 +652,57 @@ def drain(bits=6, block_cells=12, gap_cells=4.0, period=1e-3, dt=1e-4):
             "models": [{"material": J_FLUID, "xyz": lattice_box(bits, (lo, y0, lo), (lo + block_cells, y0 + block_cells, lo + block_cells)), "v0": (0.0, 0.0, 0.0),
                         "params": {"volume": _vol(bits), "rho": 1e3}}],
             "sinks": [{"model": 0, "kind": "halfspace", "point": (0.5, plane, 0.5), "normal": (0.0, 1.0, 0.0), "period": period}]}
+
+
+class ForceEntry:
+    """A scene's force field with its lifetime: `field` holds Engine.set_force_field's keywords (kind, vec, centre, strength, swirl, pull, lift,
+    soft, falloff, region, feather).  The rule: the entry is installed at the first substep boundary t where start <= t < end holds and removed
+    at the first boundary where it no longer holds (start == end: never installed).  The same rule in C++: host/force_rule.hpp."""
+
+    def __init__(self, field, start=0.0, end=np.inf):
+        if not isinstance(field, dict) or "kind" not in field:
+            raise ValueError("ForceEntry: field must be a dict with a kind")
+        self.field, self.start, self.end = dict(field), float(start), float(end)
+        self.installed = False
+
+    @classmethod
+    def from_dict(cls, d):
+        """An entry of a scene's "forces": set_force_field's keywords beside {"start", "end"}."""
+        return cls({k: v for k, v in d.items() if k not in ("start", "end")}, d.get("start", 0.0), d.get("end", np.inf))
+
+    def due(self, t):
+        """What the substep boundary `t` asks for: +1 install, -1 remove, 0 nothing."""
+        want = self.start <= t < self.end
+        act = int(want) - int(self.installed)
+        self.installed = want
+        return act
+
+
+def sand_in_wind(bits=6, column_cells=(8, 16, 8), wind=(3.0, 0.0, 0.0), rate=50.0, feather_cells=2.0, start=0.0, end=np.inf, dt=1e-4):
+    """A sand column under gravity with wind from the side: a DRAG field toward the horizontal velocity `wind` in a box over the upper half of
+    the domain, its edge feathered over feather_cells (scene key "forces")."""
+    n = 1 << bits
+    dx = 1.0 / n
+    lo = (n // 2 - column_cells[0] // 2, 8, n // 2 - column_cells[2] // 2)
+    sc = {"name": "sand_in_wind", "bits": bits, "dt": dt, "config": {"max_ppc": 16},
+          "models": [{"material": SAND, "xyz": lattice_box(bits, lo, tuple(lo[d] + column_cells[d] for d in range(3))), "v0": (0.0, 0.0, 0.0),
+                      "params": {"volume": _vol(bits), "rho": 1e3}}],
+          "forces": [{"kind": "drag", "vec": tuple(wind), "strength": rate, "feather": feather_cells * dx, "start": start, "end": end,
+                      "region": {"kind": "box", "center": (0.5, (lo[1] + column_cells[1]) * dx, 0.5), "half_extents": (0.5, column_cells[1] * dx / 2, 0.5)}}]}
+    return sc
+
+
+def stirred_tank(bits=6, pool_cells=(24, 10, 24), swirl=40.0, pull=0.0, radius_cells=8.0, end=5e-3, dt=1e-4):
+    """J-fluid in a box-shaped container (an inside-out box, slip), stirred: a VORTEX field about the vertical axis through the middle of the pool in a capsule region along
+    that axis, switched off at `end` (scene keys "colliders", "forces")."""
+    n = 1 << bits
+    dx = 1.0 / n
+    lo = (n // 2 - pool_cells[0] // 2, 10, n // 2 - pool_cells[2] // 2)
+    top = (lo[1] + pool_cells[1]) * dx
+    return {"name": "stirred_tank", "bits": bits, "dt": dt, "config": {"max_ppc": 16},
+            "models": [{"material": J_FLUID, "xyz": lattice_box(bits, lo, tuple(lo[d] + pool_cells[d] for d in range(3))), "v0": (0.0, 0.0, 0.0),
+                        "params": {"volume": _vol(bits), "rho": 1e3}}],
+            "colliders": [{"kind": "box", "a": (0.5, 0.5, 0.5), "b": ((pool_cells[0] / 2 + 2) * dx, 0.5 - 9 * dx, (pool_cells[2] / 2 + 2) * dx), "inside_out": True,
+                           "type": 1, "friction": 0.0}],
+            "forces": [{"kind": "vortex", "vec": (0.0, 1.0, 0.0), "centre": (0.5, 0.0, 0.5), "swirl": swirl, "pull": pull, "start": 0.0, "end": end,
+                        "region": {"kind": "capsule", "a": (0.5, lo[1] * dx, 0.5), "b": (0.5, top, 0.5), "radius": radius_cells * dx}}]}

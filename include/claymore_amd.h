@@ -789,6 +789,52 @@ int mpm_get_collider_body(mpm_ctx* ctx, int slot, mpm_rigid_body* body_out, mpm_
 int mpm_set_collider_body_state(mpm_ctx* ctx, int slot, const double position[3], const double orientation[4], const double velocity[3], const double omega[3]);
 int mpm_shape_mass_properties(const mpm_collision_shape* shape, float density, mpm_rigid_body* out);
 int mpm_mesh_mass_properties(const float* verts, size_t nv, const int32_t* tris, size_t nt, float density, mpm_rigid_body* out);
+
+/* Extension (the reference knows one scalar gravity on y): force fields on the grid - a tilted gravity, wind, a stirrer, an attractor, damping.
+ * Up to MPM_MAX_FORCE_FIELDS of them, in slots 0..3, installed, replaced and removed at any substep boundary.  Every applied grid update then
+ * applies them to the {mass m, momentum p} of every grid node with mass, BEFORE walls, gravity and colliders, slots in order, each on the
+ * momentum the previous one left; the mass is never written.  X is the node position the collider slots see.  HIP library only.
+ * Region and weight w.  `region` is an mpm_collision_shape in domain coordinates, without pose or clock (as mpm_remove_particles' regions;
+ *   inside_out is honoured); region.kind 0: w = 1 everywhere.  feather == 0: w = sdis <= 0 ? 1 : 0.  feather > 0: w = sdis < 0 ?
+ *   min(1, -sdis / feather) : 0.  A NaN sdis gives 0.  A node with w == 0 is skipped by that slot: its words keep their bits.
+ * Kinds (float32, no contraction, + - * / sqrtf only; INTEGRATION.md section 5 has the order of every operation):
+ *   UNIFORM  a = vec.
+ *   POINT    r = centre - X, d2 = r.r + soft^2, d = sqrt(d2); a = strength r / d (falloff 0), strength r / d2 (1), strength r / (d2 d) (2);
+ *            d == 0 gives a = 0; a negative strength repels.
+ *   VORTEX   the axis n^ = vec / |vec| (normalised on install) runs through centre: r = X - centre, rp = r - (r.n^) n^,
+ *            a = swirl (n^ x rp) - pull rp + lift n^.
+ *   these three: p += m a (w dt).
+ *   DRAG     toward the velocity vec at the rate strength (wind; damping with vec = 0), implicit Euler of dv/dt = -w strength (v - vec):
+ *            s = w strength dt, p = (p + s m vec) / (1 + s).
+ * With a field installed mpm_run_fixed keeps every grid update a launch of its own (the fields' pass runs ahead of it); a context without
+ * one allocates and launches nothing for this.  mpm_collider_loads / mpm_collider_contacts and the load gauge see the forced momenta; fields
+ * belong to no load row, as gravity belongs to none.  Fields do not act on rigid bodies, are not part of a checkpoint (a load leaves the
+ * installed ones in place, the parameter hash does not know them) and are not offered in multi-GPU groups and MGSP ranks. */
+enum { MPM_FORCE_UNIFORM = 1, MPM_FORCE_POINT, MPM_FORCE_VORTEX, MPM_FORCE_DRAG };
+enum { MPM_MAX_FORCE_FIELDS = 4 };
+typedef struct mpm_force_field {
+	int kind;
+	int falloff;	 /* POINT: 0, 1 or 2 (others: 0) */
+	float vec[3];	 /* UNIFORM: acceleration; VORTEX: axis (any length > 0; normalised on install); DRAG: target velocity */
+	float centre[3]; /* POINT, VORTEX */
+	float strength;	 /* POINT: pull (negative: repels); DRAG: rate (>= 0) */
+	float swirl, pull, lift; /* VORTEX */
+	float soft;		 /* POINT: softening length (>= 0) */
+	float feather;	 /* width of the region's soft edge (>= 0) */
+	mpm_collision_shape region; /* kind 0: everywhere */
+	int reserved[6]; /* must be 0 */
+} mpm_force_field;
+/* Install a field in slot 0..3 or empty the slot (f == NULL).  MPM_ERR_INVALID (mpm_last_error names the field; a refused call changes
+ * nothing): slot outside 0..3, unknown kind or falloff, any non-finite number, a zero axis, strength < 0 for DRAG, soft < 0 or feather < 0, a
+ * region mpm_set_collision_shape would refuse, a reserved word that is not 0; a context that belongs, or belonged, to a group or an MGSP
+ * rank (and mpm_group_create* refuse a context with a field installed). */
+int mpm_set_force_field(mpm_ctx* ctx, int slot, const mpm_force_field* f);
+/* The field as installed (unit axis, unit region normal); kind 0: the slot is empty. */
+int mpm_get_force_field(mpm_ctx* ctx, int slot, mpm_force_field* out);
+/* Function-level entry point (as mpm_test_collision_shape): the fields' statements for one node, on the device, at n arbitrary points
+ * xyz[n*3] with given {m, p} mp4[n*4] -> out4[n*4]; fields[i] sits in slot i (kind 0: empty), n_fields 0..4.  The fields are validated as
+ * mpm_set_force_field validates them before the device is touched.  dx is not used by the evaluation. */
+int mpm_test_force_field(const mpm_force_field* fields, int n_fields, float dt, float dx, const float* xyz, const float* mp4, size_t n, float* out4, int device);
 /* How the library was built: "claymore_hip <abi> experiment=<none | list of -D switches>".  A product library reports
  * experiment=none (claymore_amd/csrc/mpm_device_math.hpp: the switches that change what the kernels compute only exist under
  * -DMPM_EXPERIMENT); tests/test_abi.py asserts it for the shipped library.  Needs no device. */

@@ -4,7 +4,7 @@ libraries in ONE process, interleaved (lib A, lib B, lib A, ...), so that a pare
 box under the same conditions.
 
     python tools/collider_substep.py [--scene c1|c2|c3] [--steps 200] [--warmup 50] [--reps 3] [--objects none,static,moving,shape,body,shapes4,ground_hf,ground_shape,ground_field,vol_mesh,vol_mesh4,field_mesh] [--phase 20]
-                                     [--loads] [--out FILE] [lib.so ...]
+                                     [--loads] [--forces none,uniform,drag_box,four] [--out FILE] [lib.so ...]
 
 Scene: C2 (one elastic sphere of ~5 M particles dropped at 256^3; the level-set field is 256^3 float4 = 256 MiB) or C3 (the sand column at
 512^3; the field is 2 GiB).  The object is a sphere below the material, far enough that nothing touches it during the measurement: the
@@ -23,7 +23,12 @@ object: a float4 per node of the whole domain); `install_ms` is the wall-clock t
 `object_bytes`: device memory taken by installing the collider (hipMemGetInfo before and after).  Prints one JSON line per (rep, library, object) with the library's per-substep averages
 (HIP events on the compute stream) and the wall-clock time per substep, then a summary of medians.  --loads: a library with mpm_load_gauge then switches the
 load gauge on and measures again - `loads_*`: mpm_run_fixed with every grid update a kernel of its own behind collider_loads_kernel and its reduction (no fused
-carry-over), and the phase-level grid update, whose time then holds the readout's two kernels as well: `loads_phase_grid_ms - phase_grid_ms` is their cost."""
+carry-over), and the phase-level grid update, whose time then holds the readout's two kernels as well: `loads_phase_grid_ms - phase_grid_ms` is their cost.
+--forces: every (library, object) is measured once per entry of the list - `none`: no force field; `uniform`: one UNIFORM field; `drag_box`: one DRAG
+field in a feathered box around the material; `four`: UNIFORM in a half-space, DRAG in a feathered box, VORTEX in a capsule and POINT in a sphere, all four
+slots (mpm_set_force_field; a library without it runs `none` only).  With a field mpm_run_fixed applies every grid update in a launch of its own behind
+grid_force_kernel (no fused carry-over): `grid_ms` then holds the fields' pass and the update, `partition_ms` a rebuild without the update, and
+`phase_grid_ms - phase_grid_ms of none` is the fields' pass alone."""
 import argparse
 import ctypes as C
 import json
@@ -58,6 +63,7 @@ def main():
     ap.add_argument("--objects", default="none,static,moving,shape,shapes4")
     ap.add_argument("--phase", type=int, default=20)
     ap.add_argument("--loads", action="store_true")
+    ap.add_argument("--forces", default="none")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     sc = scenes.sphere_drop() if a.scene == "c2" else scenes.sphere_drop(bits=7, radius_cells=26.5) if a.scene == "c1" else scenes.sand_column()
@@ -69,9 +75,18 @@ def main():
     meshes = [scenes.icosphere(c, r, 5) for c, r in bodies] if any(o in a.objects.split(",") for o in ("vol_mesh", "vol_mesh4", "field_mesh")) else []
     apis = [(os.path.basename(os.path.dirname(os.path.abspath(p))) + "/" + os.path.basename(p), load(p)) for p in a.libs]
     rows, lines = [], []
+    box = {"kind": "box", "a": (0.5, 0.4, 0.5), "b": (0.3, 0.35, 0.3)}
+    force_sets = {"none": [], "uniform": [dict(kind="uniform", vec=(0.5, 0.0, 0.25))],
+                  "drag_box": [dict(kind="drag", vec=(1.0, 0.0, 0.0), strength=5.0, region=box, feather=8.0 / n)],
+                  "four": [dict(kind="uniform", vec=(0.5, 0.0, 0.25), region={"kind": "halfspace", "a": (0.5, 0.5, 0.5), "b": (0.0, 1.0, 0.0)}),
+                           dict(kind="drag", vec=(1.0, 0.0, 0.0), strength=5.0, region=box, feather=8.0 / n),
+                           dict(kind="vortex", vec=(0.0, 1.0, 0.0), centre=(0.5, 0.0, 0.5), swirl=2.0, pull=0.5, region={"kind": "capsule", "a": (0.5, 0.1, 0.5), "b": (0.5, 0.7, 0.5), "radius": 0.2}),
+                           dict(kind="point", centre=(0.5, 0.4, 0.5), strength=0.5, falloff=1, soft=0.05, region={"kind": "sphere", "a": (0.5, 0.4, 0.5), "radius": 0.3})]}
     for rep in range(a.reps):
         for name, api in apis:
-            for obj in a.objects.split(","):
+            for obj, force in ((o, f) for o in a.objects.split(",") for f in a.forces.split(",")):
+                if force != "none" and not hasattr(api, "set_force_field"):
+                    continue
                 if (obj == "moving" and not hasattr(api, "set_collision_clock")) or (obj in ("shape", "shapes4") and not hasattr(api, "set_collision_shape")):
                     continue
                 if obj in ("vol_mesh", "vol_mesh4") and not hasattr(api, "set_collision_volume_mesh"):
@@ -113,6 +128,8 @@ def main():
                 install_ms = (time.perf_counter() - t_install) * 1e3
                 object_bytes = free0 - torch.cuda.mem_get_info()[0]
                 eng.initial_setup()
+                for slot, f in enumerate(force_sets[force]):
+                    eng.set_force_field(slot, **f)
                 eng.run_fixed(a.warmup, sc["dt"])
                 t0 = time.perf_counter()
                 eng.run_fixed(a.steps, sc["dt"])
@@ -124,7 +141,7 @@ def main():
                     phase.append(eng.timers().grid_update_ms)
                     eng.g2p2g(sc["dt"], sc["dt"])
                     eng.rebuild_partition()
-                row = {"rep": rep, "lib": name, "build": api.build_info().decode(), "scene": a.scene, "object": obj, "steps": a.steps, "wall_ms": round(wall, 5),
+                row = {"rep": rep, "lib": name, "build": api.build_info().decode(), "scene": a.scene, "object": obj, "forces": force, "steps": a.steps, "wall_ms": round(wall, 5),
                        "grid_ms": round(t.grid_update_ms, 5), "g2p2g_ms": round(t.g2p2g_ms, 5), "partition_ms": round(t.partition_ms, 5), "total_ms": round(t.total_ms, 5),
                        "phase_grid_ms": round(statistics.median(phase), 5) if phase else None, "object_bytes": int(object_bytes), "install_ms": round(install_ms, 3)}
                 if a.loads and hasattr(api, "load_gauge"):
@@ -149,15 +166,15 @@ def main():
                 lines.append(json.dumps(row))
                 print(lines[-1], flush=True)
     for name, _ in apis:
-        for obj in a.objects.split(","):
-            sel = [r for r in rows if r["lib"] == name and r["object"] == obj]
+        for obj, force in ((o, f) for o in a.objects.split(",") for f in a.forces.split(",")):
+            sel = [r for r in rows if r["lib"] == name and r["object"] == obj and r["forces"] == force]
             if sel:
                 med = {k: round(statistics.median(r[k] for r in sel), 5) for k in ("wall_ms", "grid_ms", "g2p2g_ms", "partition_ms", "total_ms") + (("phase_grid_ms",) if a.phase else ())}
                 med.update(partition_lo=min(r["partition_ms"] for r in sel), partition_hi=max(r["partition_ms"] for r in sel), object_bytes=sel[0]["object_bytes"], install_ms=round(statistics.median(r["install_ms"] for r in sel), 3))
                 med.update(lo=min(r["wall_ms"] for r in sel), hi=max(r["wall_ms"] for r in sel))
                 if "loads_wall_ms" in sel[0]:
                     med.update({k: round(statistics.median(r[k] for r in sel), 5) for k in ("loads_wall_ms", "loads_grid_ms", "loads_g2p2g_ms", "loads_partition_ms", "loads_total_ms") + (("loads_phase_grid_ms",) if a.phase else ())})
-                lines.append(json.dumps({"summary": name, "object": obj, "n": len(sel), **med}))
+                lines.append(json.dumps({"summary": name, "object": obj, "forces": force, "n": len(sel), **med}))
                 print(lines[-1], flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
